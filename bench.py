@@ -2,6 +2,8 @@
 """bench.py — Msamples/s (pixels x spp / s) of the path-tracing hot path on the book-1 final scene.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR     # + the last timed step's frame as DIR/rgb_sum.npy
+    python bench.py --full                                                # + roofline, variants and the CPU baseline
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = one full render of the workload (BASELINE.json configs[1]: book-1 random spheres, 1200x800, 500 spp, depth 50)
@@ -9,7 +11,8 @@ through the C ABI, output left in HBM. With N GPUs (one process per GPU) the fra
 the LIBRARY (rt_render_gather: grouped ncclSend/ncclRecv, RCCL over xGMI, then the root's untile kernel); torch.distributed (gloo)
 only carries the 128-byte RCCL id, the barrier and the max over ranks. Per-GPU work is held fixed (weak scaling: the image grows to
 N x 960k pixels at the same aspect and view); `variants.strong_4096` is the SAME 4096x4096 image at every N (strong scaling).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times the steps and prints the headline; what takes renders of its own
+(the strong-scaling leg, the roofline's counting render, the host-resident / SAH / other-config variants, the CPU baseline) runs with --full.
 """
 import argparse
 import json
@@ -27,6 +30,7 @@ NODE_BYTES, SPHERE_BYTES, RAY_BYTES, HIT_BYTES = 32, 20, 32, 8
 LDS_PEAK_GCYC = 256 * 2.4                          # 614.4: 256 CUs x 2.4 GHz LDS-array cycles per second, in 1e9 (one 256-byte-wide access slot per CU and cycle)
 PMC_PROFILE = os.path.join("profiles", "r03_pmc_book1.json")
 PMC_PROFILE_C5 = os.path.join("profiles", "r03_pmc_c5.json")
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: a larger frame (many ranks) is written as a fixed, seeded sample of its pixels
 
 
 def host_cores():
@@ -54,6 +58,20 @@ def image_size(n_gpus, base_w=1200, base_h=800):
     s = math.sqrt(n_gpus)
     # whole 32 x 32 tiles: a shard whose tiles all lie inside the image finds a path's next work item by arithmetic
     return int(round(base_w * s / 32)) * 32, int(round(base_h * s / 32)) * 32
+
+
+def dump_frame(frame, out_dir):
+    """The frame the timed path computed in its last step (float32 per-pixel RGB sums, H x W x 3) as out_dir/rgb_sum.npy. Above
+    DUMP_MAX_BYTES, a seeded sample of whole pixels instead: rgb_sum.npy (k x 3) and their row-major indices, rgb_sum_pixel_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = np.ascontiguousarray(frame.detach().cpu().numpy(), dtype=np.float32)
+    if a.nbytes > DUMP_MAX_BYTES:
+        n = a.shape[0] * a.shape[1]
+        idx = np.sort(np.random.default_rng(1).choice(n, DUMP_MAX_BYTES // 2 // (3 * 4), replace=False))
+        np.save(os.path.join(out_dir, "rgb_sum_pixel_index.npy"), idx.astype(np.float64))
+        a = a.reshape(n, 3)[idx]
+    np.save(os.path.join(out_dir, "rgb_sum.npy"), a)
 
 
 def other_configs(pkg, ctx, A, B, dev, stream):
@@ -128,11 +146,15 @@ def main():
     ap.add_argument("--spp", type=int, default=500)
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline duration (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: target CPU-baseline duration (0 = skip)")
     ap.add_argument("--pool-slots", type=int, default=0)
-    ap.add_argument("--strong-spp", type=int, default=64, help="spp of the 4096x4096 strong-scaling leg (0 = skip)")
-    ap.add_argument("--no-variants", action="store_true")
+    ap.add_argument("--strong-spp", type=int, default=64, help="with --full: spp of the 4096x4096 strong-scaling leg (0 = skip)")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: roofline and CPU baseline only")
+    ap.add_argument("--full", action="store_true", help="after the headline: strong-scaling leg, roofline, variants, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's frame as DIR/rgb_sum.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import rta
@@ -232,9 +254,11 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_frame(last, args.dump_outputs)     # before any --full leg renders into frame1
 
     # per-rank device statistics of the timed steps
     seg = sum(s["segments"] for s in stats_acc)
@@ -247,7 +271,7 @@ def main():
 
     # ---- strong-scaling leg: the SAME 4096x4096 book-1 image at every N, RGB8 out (write_color on the devices, 3 B/pixel gathered) ----
     strong = None
-    if args.strong_spp > 0 and not args.no_variants:
+    if args.full and args.strong_spp > 0 and not args.no_variants:
         try:
             SW = SH = 4096
             scam = hs.camera(SW / SH)
@@ -298,6 +322,16 @@ def main():
         "kernel_ms_per_step": {"k_extend": round(ext_ms / args.steps, 3), "k_shade": round(shade_ms / args.steps, 3), "generate+resolve": round(other_ms / args.steps, 3),
                                "gather+untile": round(gather_ms / args.steps, 3), "launches_per_step": launches // max(1, args.steps)},
     }
+
+    def emit():
+        print(json.dumps(out))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        emit()
+        return
 
     try:
         # ---- roofline of the dominant kernel (k_extend = BVH traversal), rank 0's launches ----
@@ -443,10 +477,7 @@ def main():
             out["cpu_baseline"] = cb
     except Exception as e:
         out["cpu_baseline"] = {"error": repr(e)}
-    print(json.dumps(out))
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    emit()
 
 
 if __name__ == "__main__":

@@ -5,7 +5,8 @@
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/prof3
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof3/bench_stats -o run -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 --no-variants > gpurun_out/prof3/bench_under_rocprof.json 2> gpurun_out/prof3/bench_under_rocprof.err || exit 1
+OUT=$_                                    # the directory just made: this run's bench and trace files
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_stats" -o run -- python3 bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 --no-variants > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err" || exit 1
 echo "kernel-trace done" >> gpurun_out/prof3/progress.log
 bash scripts/pmc_passes.sh R3 > gpurun_out/prof3/pmc_book1_summary.txt 2>&1 || exit 1
 echo "pmc book1 done" >> gpurun_out/prof3/progress.log
@@ -26,5 +27,5 @@ SEG=$(grep -o "segments [0-9]*" gpurun_out/pmcR31.log | tail -1 | cut -d" " -f2)
 python3 scripts/pmc_to_json.py R3 $SEG profiles/r03_pmc_book1.json "scripts/pmc_passes.sh R3 (on the GPU box)" > /dev/null || exit 1
 SEG5=$(grep -o "segments [0-9]*" gpurun_out/pmcC5c1.log | tail -1 | cut -d" " -f2)
 python3 scripts/pmc_to_json.py C5c $SEG5 profiles/r03_pmc_c5.json "scripts/pmc_c5.sh C5c 16 (on the GPU box)" > /dev/null || exit 1
-timeout -k 10 500 python3 bench.py > gpurun_out/prof3/bench.json 2> gpurun_out/prof3/bench.err || exit 1
-cat gpurun_out/prof3/bench.json
+timeout -k 10 500 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
+cat "$OUT/bench.json"
