@@ -120,6 +120,13 @@ pub struct RtUploadOptions {
     pub struct_bytes: u32, pub layout_flags: u32, pub lds_top_records: u32, pub octant_axes: u32, pub leaf_collapse: u32, pub list_park_cost: f32,
 }
 
+// progressive rendering: a frame in resumable sample passes (rt_render_pass); RtPassOptions.flags
+pub const RT_PASS_ACCUMULATE: u32 = 1;    // add into the output buffer(s), folding on from the value already there
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtPassOptions {
+    pub struct_bytes: u32, pub flags: u32, pub first_sample: u32, pub frame_samples: u32,
+}
+
 pub const RT_N_PRIM_TYPES: usize = 6;
 #[repr(C)] #[derive(Clone, Copy, Default, Debug)]
 pub struct RtStats {
@@ -170,6 +177,13 @@ extern "C" {
                      rgb_sum_host: *mut f32, stats: *mut RtStats) -> c_int;
     pub fn rt_render_device(ctx: *mut RtCtx, scene: *const RtScene, cam: *const RtCamera, params: *const RtParams,
                             rgb_sum_device: *mut c_void, stats: *mut RtStats) -> c_int;
+    /// host only: validates a pass and reports the samples per work item of the frame
+    pub fn rt_pass_check(params: *const RtParams, options: *const RtPassOptions, out_samples_per_item: *mut u32) -> c_int;
+    /// samples first_sample .. first_sample + spp - 1; sq_sum_host may be null
+    pub fn rt_render_pass(ctx: *mut RtCtx, scene: *const RtScene, cam: *const RtCamera, params: *const RtParams, options: *const RtPassOptions,
+                          rgb_sum_host: *mut f32, sq_sum_host: *mut f32, stats: *mut RtStats) -> c_int;
+    pub fn rt_render_pass_device(ctx: *mut RtCtx, scene: *const RtScene, cam: *const RtCamera, params: *const RtParams, options: *const RtPassOptions,
+                                 rgb_sum_device: *mut c_void, sq_sum_device: *mut c_void, stats: *mut RtStats) -> c_int;
     pub fn rt_untile(params: *const RtParams, gathered: *const f32, rgb_sum: *mut f32) -> c_int;
     /// write_color (main.rs:141-169) on the device
     pub fn rt_resolve_device(ctx: *mut RtCtx, rgb_sum_device: *const c_void, width: u32, height: u32,

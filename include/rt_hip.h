@@ -299,6 +299,49 @@ int rt_render(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtPar
 int rt_render_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* params,
                      void* rgb_sum_device, RtStats* stats);
 
+/* ---- progressive rendering: a frame in resumable sample passes, with per-pixel second moments ----------------------------------------
+ *
+ * A PASS renders samples first_sample .. first_sample + params->samples_per_pixel - 1 of every pixel of the shard, into the layout
+ * rt_render writes (full frame, or this shard's tiles back to back; rt_output_floats floats).
+ *   - RT_PASS_ACCUMULATE unset: the pass overwrites the output buffer(s).
+ *   - RT_PASS_ACCUMULATE set: the pass adds into them; its per-pixel fold starts from the value already there.
+ *   - frame_samples = the samples per pixel the whole frame will have. It fixes how samples are grouped into work items (m samples per
+ *     item, rt_pass_check), exactly as rt_render groups them for samples_per_pixel = frame_samples.
+ * A sample's random stream is a pure function of (seed, pixel, ABSOLUTE sample index), and each pixel's sums are folded sequentially in
+ * sample order in f32. Hence the guarantee: passes that cover [0, N) in order, all with frame_samples = N, the first without ACCUMULATE
+ * and the rest with it, leave in the buffer EXACTLY (bit for bit) what rt_render with samples_per_pixel = N writes — in every layout
+ * (sharded / tile-compact included) and with every RtParams flag, tail_paths, pool_slots and NaN policy rt_render accepts.
+ * Constraints (anything else is RT_ERR_INVALID, with the reason in rt_last_error, and the output is left untouched):
+ *   - first_sample is a multiple of m; the pass ends on a multiple of m or at frame_samples;
+ *   - first_sample + samples_per_pixel <= frame_samples < 2^32;
+ *   - struct_bytes >= sizeof(RtPassOptions) as this header declares it; no unknown bit in flags.
+ *
+ * Optional second output sq_sum (NULL = not wanted): the same layout and size as rgb_sum. Per pixel and channel it holds the sum of the
+ * SQUARED item sums over the items folded so far, accumulated under the same rule (a series of passes gives the bits of one pass over
+ * [0, N)). With m = 1 (the default below 2^32 - 2^28 samples per image) that is the sum of L^2 over the samples; with m > 1 it is the
+ * batch-means second moment. With S = rgb_sum, Q = sq_sum and k = items folded (samples / m, rounded up), the standard error of the
+ * pixel MEAN is
+ *     SE = sqrt((Q - S^2 / k) / (k (k - 1))) / m.
+ * Q - S^2/k cancels in f32 for near-constant pixels (a pixel that sees only the sky has a meaningless SE at the level of the rounding):
+ * compute it in f64 and clamp it at 0.
+ *
+ * RtStats.samples counts the pass's samples. The host variant uploads the caller's sums before the fold when ACCUMULATE is set and
+ * copies them back after it. Passes do not go through the collective entry points (rt_render_multi*, rt_render_gather): a one-process-
+ * per-GPU caller accumulates its shard's passes with rt_render_pass_device and gathers once at the end (rt_untile_device). */
+enum { RT_PASS_ACCUMULATE = 1u };
+typedef struct RtPassOptions {
+    uint32_t struct_bytes;    /* sizeof(RtPassOptions) as the caller compiled it (the struct may grow at its end) */
+    uint32_t flags;           /* RT_PASS_*; an unknown bit is RT_ERR_INVALID */
+    uint32_t first_sample;    /* first sample index of the pass (absolute) */
+    uint32_t frame_samples;   /* samples per pixel of the whole frame, >= first_sample + params->samples_per_pixel */
+} RtPassOptions;
+/* Host only, no device: validates (params, options) and reports the samples per work item m of the frame. */
+int rt_pass_check(const RtParams* params, const RtPassOptions* options, uint32_t* out_samples_per_item);
+int rt_render_pass(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* params, const RtPassOptions* options,
+                   float* rgb_sum_host, float* sq_sum_host /* NULL = not wanted */, RtStats* stats);
+int rt_render_pass_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* params, const RtPassOptions* options,
+                          void* rgb_sum_device, void* sq_sum_device /* NULL = not wanted */, RtStats* stats);
+
 /* Host-side helper: scatter `shard_count` gathered shard buffers (each rt_output_floats long,
    in shard order) into a full-frame rgb_sum. */
 int rt_untile(const RtParams* params, const float* gathered, float* rgb_sum);

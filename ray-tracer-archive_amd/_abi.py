@@ -15,6 +15,7 @@ RT_BVH_REFERENCE, RT_BVH_SAH = 0, 1
 RT_NAN_PER_SAMPLE, RT_NAN_REFERENCE = 0, 1
 RT_FLAG_COUNTERS, RT_FLAG_TIMING, RT_FLAG_SAMPLE_BLOCKS, RT_FLAG_FUSED = 1, 2, 4, 8
 RT_OUT_RGB_SUM_F32, RT_OUT_RGB8 = 0, 1
+RT_PASS_ACCUMULATE = 1
 RT_COMM_ID_BYTES = 128
 # RtUploadOptions.layout_flags
 (RT_LAYOUT_LISTS_AS_REFERENCE, RT_LAYOUT_LISTS_CULLED, RT_LAYOUT_NO_MEMBER_BOXES, RT_LAYOUT_MEMBER_BOXES, RT_LAYOUT_CHILD_ORDER_AS_REFERENCE,
@@ -102,6 +103,10 @@ class RtUploadOptions(C.Structure):
                 ("leaf_collapse", C.c_uint32), ("list_park_cost", C.c_float)]
 
 
+class RtPassOptions(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32), ("first_sample", C.c_uint32), ("frame_samples", C.c_uint32)]
+
+
 class RtWideInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("n_leaf_entries", C.c_uint64), ("n_inner_entries", C.c_uint64), ("n_prims", C.c_uint64),
                 ("depth", C.c_uint32), ("_pad", C.c_uint32), ("mean_children", C.c_double), ("mean_leaf_members", C.c_double)]
@@ -113,7 +118,8 @@ RT_HIP_SYMBOLS = ["rt_ctx_create", "rt_ctx_destroy", "rt_scene_upload", "rt_scen
                   "rt_scene_compile_dump", "rt_ctx_create_multi", "rt_ctx_destroy_multi", "rt_scene_upload_multi", "rt_scene_destroy_multi",
                   "rt_render_multi", "rt_render_multi_rgb8", "rt_last_error_multi", "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_selftest",
                   "rt_render_gather", "rt_untile_rgb8", "rt_untile_device", "rt_scene_top_layout_check", "rt_scene_upload_ex", "rt_scene_upload_multi_ex",
-                  "rt_runtime_libraries", "rt_test_fail_next_renders", "rt_test_device_workers", "rt_scene_compile_info_ex", "rt_scene_compile_dump_ex", "rt_scene_wide_layout_check"]
+                  "rt_runtime_libraries", "rt_test_fail_next_renders", "rt_test_device_workers", "rt_scene_compile_info_ex", "rt_scene_compile_dump_ex", "rt_scene_wide_layout_check",
+                  "rt_pass_check", "rt_render_pass", "rt_render_pass_device"]
 RT_HOST_SYMBOLS = ["rt_host_scene_create", "rt_host_scene_desc", "rt_host_scene_camera", "rt_host_scene_destroy", "rt_host_camera_new",
                    "rt_host_write_color", "rt_host_tonemap", "rt_host_write_png", "rt_host_write_jpeg", "rt_host_write_image"]
 
@@ -150,6 +156,12 @@ def declare(lib):
     lib.rt_render.argtypes = [vp, vp, P(RtCamera), P(RtParams), P(C.c_float), P(RtStats)]
     lib.rt_render_device.restype = i32
     lib.rt_render_device.argtypes = [vp, vp, P(RtCamera), P(RtParams), vp, P(RtStats)]
+    lib.rt_pass_check.restype = i32
+    lib.rt_pass_check.argtypes = [P(RtParams), P(RtPassOptions), P(u32)]
+    lib.rt_render_pass.restype = i32
+    lib.rt_render_pass.argtypes = [vp, vp, P(RtCamera), P(RtParams), P(RtPassOptions), P(C.c_float), P(C.c_float), P(RtStats)]
+    lib.rt_render_pass_device.restype = i32
+    lib.rt_render_pass_device.argtypes = [vp, vp, P(RtCamera), P(RtParams), P(RtPassOptions), vp, vp, P(RtStats)]
     lib.rt_untile.restype = i32
     lib.rt_untile.argtypes = [P(RtParams), P(C.c_float), P(C.c_float)]
     lib.rt_resolve_device.restype = i32

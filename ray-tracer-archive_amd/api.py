@@ -46,6 +46,15 @@ def make_params(width, height, spp, max_depth=50, seed=1, nan_policy=A.RT_NAN_PE
     return A.RtParams(width, height, spp, max_depth, seed, nan_policy, flags, tile_size, shard_index, shard_count, pool_slots, tail_paths, 0)
 
 
+def pass_check(params, first_sample, frame_samples, accumulate=False):
+    """rt_pass_check (host only): the samples per work item m of the frame; raises RtError (RT_ERR_INVALID, with the reason) for a pass
+    that does not satisfy the contract of include/rt_hip.h."""
+    opt = A.RtPassOptions(C.sizeof(A.RtPassOptions), A.RT_PASS_ACCUMULATE if accumulate else 0, first_sample, frame_samples)
+    m = C.c_uint32(0)
+    _check(lib().rt_pass_check(C.byref(params), C.byref(opt), C.byref(m)))
+    return m.value
+
+
 def output_floats(params):
     n = C.c_uint64(0)
     _check(lib().rt_output_floats(C.byref(params), C.byref(n)))
@@ -191,11 +200,38 @@ def runtime_libraries():
     return [p for p in buf.value.decode().split("\n") if p], code == A.RT_OK
 
 
+def scene_fingerprint(desc):
+    """sha256 (hex) over the arrays and scalars of an RtSceneDesc: what a progressive checkpoint records of the scene it was rendered from."""
+    import hashlib
+    h = hashlib.sha256()
+
+    def arr(ptr, n, ctype):
+        h.update(int(n).to_bytes(8, "little"))
+        if n and ptr:
+            h.update(C.string_at(C.cast(ptr, C.c_void_p).value, int(n) * C.sizeof(ctype)))
+
+    arr(desc.hittables, desc.n_hittables, A.RtHittable)
+    arr(desc.children, desc.n_children, C.c_int32)
+    arr(desc.materials, desc.n_materials, A.RtMaterial)
+    arr(desc.textures, desc.n_textures, A.RtTexture)
+    arr(desc.perlins, desc.n_perlins, A.RtPerlin)
+    h.update(int(desc.n_images).to_bytes(8, "little"))
+    for k in range(desc.n_images if desc.images else 0):
+        im = desc.images[k]
+        h.update(np.array([im.width, im.height], dtype=np.uint32).tobytes())
+        if im.data:
+            h.update(C.string_at(C.cast(im.data, C.c_void_p).value, im.width * im.height * 3))
+    h.update(np.array([desc.world, desc.lights, desc.background_mode, desc.bvh_builder], dtype=np.int32).tobytes())
+    h.update(np.array(desc.background.tuple(), dtype=np.float64).tobytes() + int(desc.bvh_seed).to_bytes(8, "little"))
+    return h.hexdigest()
+
+
 class Scene:
     def __init__(self, ctx, desc, options=None):
         self.ctx = ctx
         self._h = C.c_void_p()
         _check(lib().rt_scene_upload_ex(ctx._h, C.byref(desc), C.byref(options) if options is not None else None, C.byref(self._h)), ctx._h)
+        self.fingerprint = scene_fingerprint(desc)     # (progressive checkpoints: the scene a frame's sums belong to)
 
     def close(self):
         if self._h and self.ctx._h:
@@ -214,6 +250,7 @@ class Context:
 
     def __init__(self, device_id=0, stream=None):
         self._h = C.c_void_p()
+        self.device_id = device_id
         _check(lib().rt_ctx_create(device_id, C.c_void_p(stream) if stream else None, C.byref(self._h)))
 
     def upload(self, desc, layout_flags=0, **more):
@@ -239,6 +276,40 @@ class Context:
         st = A.RtStats()
         _check(lib().rt_render_device(self._h, scene._h, C.byref(cam), C.byref(params), C.c_void_p(device_ptr), C.byref(st)), self._h)
         return st.as_dict()
+
+    def render_pass(self, scene, cam, params, first_sample, frame_samples, accumulate, rgb_sum=None, sq_sum=None):
+        """rt_render_pass / rt_render_pass_device: samples first_sample .. first_sample + params.samples_per_pixel - 1 of a frame of
+        frame_samples samples per pixel, overwriting (accumulate False) or adding into (True) rgb_sum and, if given, sq_sum.
+
+        Host variant: rgb_sum / sq_sum are numpy float32 arrays of output_floats(params) elements (None: a new one; accumulating needs
+        the caller's). Device variant: torch tensors on this context's GPU (both of them, or rgb_sum alone). Returns
+        (rgb_sum, sq_sum, stats); a full-frame host result is shaped (H, W, 3)."""
+        opt = A.RtPassOptions(C.sizeof(A.RtPassOptions), A.RT_PASS_ACCUMULATE if accumulate else 0, first_sample, frame_samples)
+        st = A.RtStats()
+        n = output_floats(params)
+        if rgb_sum is not None and hasattr(rgb_sum, "data_ptr"):
+            import torch
+            for t in (rgb_sum, sq_sum):
+                if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
+                    raise ValueError(f"device buffers must be contiguous float32 CUDA tensors of {n} elements")
+            torch.cuda.synchronize(rgb_sum.device)        # the library's stream is not torch's
+            _check(lib().rt_render_pass_device(self._h, scene._h, C.byref(cam), C.byref(params), C.byref(opt), C.c_void_p(rgb_sum.data_ptr()),
+                                               C.c_void_p(sq_sum.data_ptr()) if sq_sum is not None else None, C.byref(st)), self._h)
+            return rgb_sum, sq_sum, st.as_dict()
+        if rgb_sum is None:
+            if accumulate:
+                raise ValueError("an accumulating host pass needs the sums to add into (rgb_sum)")
+            rgb_sum = np.empty(n, dtype=np.float32)
+        for a in (rgb_sum, sq_sum):
+            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or a.size != n):
+                raise ValueError(f"host buffers must be C-contiguous float32 numpy arrays of {n} elements")
+        fp = C.POINTER(C.c_float)
+        _check(lib().rt_render_pass(self._h, scene._h, C.byref(cam), C.byref(params), C.byref(opt), rgb_sum.ctypes.data_as(fp),
+                                    sq_sum.ctypes.data_as(fp) if sq_sum is not None else None, C.byref(st)), self._h)
+        if params.shard_count <= 1:
+            rgb_sum = rgb_sum.reshape(params.height, params.width, 3)
+            sq_sum = sq_sum.reshape(params.height, params.width, 3) if sq_sum is not None else None
+        return rgb_sum, sq_sum, st.as_dict()
 
     # ---- one process per GPU: RCCL communicator on this context (rt_multi.cpp) ----
     def comm_init_rank(self, unique_id, rank, world):

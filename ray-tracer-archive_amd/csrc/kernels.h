@@ -126,6 +126,11 @@ struct RenderDev {
     uint32_t row_items;           // unsharded renders: work items of one full-height row of tiles (tile_size * width * n_blocks), 0 = not used. Every
     FastDiv div_row_items;        // such row holds the same number, clipped edge tile or not, so item -> tile is arithmetic (no search in tile_prefix)
     rtd::Float4* blocksum;  // [total_items]: RGB sum of one work item's samples
+    // a pass of a progressive render (rt_render_pass): samples first_sample .. spp - 1 of every pixel (spp is the pass's END, an absolute
+    // index; n_blocks counts the pass's items). Every sample index that keys the RNG is absolute. rt_render: first_sample 0.
+    uint32_t first_sample;
+    uint32_t accumulate;    // k_resolve folds on from the value already in the output (RT_PASS_ACCUMULATE) instead of from 0
+    float* sq_sum;          // k_resolve: also the sum of the squared item sums per pixel and channel, same layout as the output; nullptr = not wanted
 };
 
 struct LaunchCfg {

@@ -589,10 +589,10 @@ struct PathState {
 #endif
 };
 // The RNG of the path that renders `sample` of the pixel of work item `work`, after `n` draws (rt_weekend.rs:8-19's stream, DESIGN "RNG contract")
-// `sample`: out — the stored index for a multi-sample item (with_acc), else the item's own block number (one sample per item)
+// `sample`: out — the stored index for a multi-sample item (with_acc), else the pass's first sample + the item's block number (one sample per item)
 DEVI Rng path_rng(const RenderDev& rd, uint32_t item, bool with_acc, uint32_t stored_sample, uint32_t n, uint32_t& sample) {
     const uint32_t pixel = fdivu(item, rd.div_nblocks), blk = item - pixel * rd.n_blocks;
-    sample = with_acc ? stored_sample : (blk << rd.block_shift);
+    sample = with_acc ? stored_sample : rd.first_sample + (blk << rd.block_shift);
     Rng g; g.s = path_base(rd.seed, (uint64_t)pixel, sample) + (uint64_t)n * kGamma; g.n = n;
     return g;
 }
@@ -848,7 +848,9 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
                         // the free-path draws are keyed by the path's RNG base: pixel from the work item, sample from the state word
                         const uint32_t item = __float_as_uint(pool.s0[qbase + slot].w), pixel = fdivu(item, rd.div_nblocks);
                         seg = pool.sd[qbase + slot] & 0xFFu;
-                        const uint32_t smp = rd.block_shift != 0u ? __float_as_uint(pool.s1[qbase + slot].w) : (item - pixel * rd.n_blocks);
+                        // (s1 exists exactly when an item is several samples, rt_api.cpp; testing the pointer instead of block_shift keeps this
+                        // instance's scalar registers as they were with the pass offset added: the FEAT = 127 walks sit at the SGPR limit)
+                        const uint32_t smp = pool.s1 != nullptr ? __float_as_uint(pool.s1[qbase + slot].w) : rd.first_sample + (item - pixel * rd.n_blocks);
                         mkey = path_base(rd.seed, (uint64_t)pixel, smp);
                     }
                     if (rd.first_in_shade != 0u) {
@@ -1526,7 +1528,7 @@ DEVI float first_sphere_hit(const RenderDev& rd, V3 o, V3 d, uint32_t from) {
 // A fresh path for work item `work` (first sample of its block).
 DEVI void start_item(const RenderDev& rd, uint32_t work, PathState& s, Rng& g, V3& o, V3& d, float& tm) {
     const WorkItem it = decode_work(rd, work);
-    const uint32_t sample = it.blk << rd.block_shift;
+    const uint32_t sample = rd.first_sample + (it.blk << rd.block_shift);   // absolute: a pass starts at first_sample
     new_camera_ray(rd, it.x, it.y, sample, g, o, d, tm);
     s.T = v3(1, 1, 1); s.acc = v3(0, 0, 0);
     s.work = item_id(rd, it.x, it.y, it.blk); s.sample = sample; s.from = 0u;
@@ -1863,7 +1865,7 @@ DEVI bool finish_sample(const RenderDev& rd, PathState& s, Rng& g, uint32_t& dep
     if (!fin_ok && rd.nan_policy == RT_NAN_PER_SAMPLE_K) L = v3(0.f, 0.f, 0.f);
     s.acc = s.acc + L;
     const uint32_t sample = ++s.sample;
-    if ((sample & ((1u << rd.block_shift) - 1u)) != 0u && sample < rd.spp) {
+    if ((sample & ((1u << rd.block_shift) - 1u)) != 0u && sample < rd.spp) {   // (rd.spp: the end of this pass, absolute)
         uint32_t x, y, blk; item_pixel(rd, s.work, x, y, blk);
         new_camera_ray(rd, x, y, sample, g, o, d, tm);   // next sample of the same block
         s.T = v3(1, 1, 1); depth = 0; s.from = 0u;
@@ -2033,6 +2035,9 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
 // ------------------------------------------------------------------------------------------------
 // k_resolve — per-pixel sum of block sums, in block order
 // ------------------------------------------------------------------------------------------------
+// The fold is sequential in sample order, in f32, with no atomics: a pass that starts from the value already in the output
+// (rd.accumulate) continues exactly the additions one render over all samples makes, so passes over [0, a), [a, b), ... leave the same
+// bits as one render over [0, b) (rt_render_pass). sq_sum folds the squares of the same item sums in the same order.
 __global__ void __launch_bounds__(256) k_resolve(RenderDev rd, float* __restrict__ out) {
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;          // one thread per in-image pixel of this shard
     if (gid >= rd.tile_prefix[rd.n_local_tiles]) return;
@@ -2041,15 +2046,29 @@ __global__ void __launch_bounds__(256) k_resolve(RenderDev rd, float* __restrict
     const TileGeom g = tile_geom(rd, lt);
     const uint32_t valid = g.w * g.h, p = gid - rd.tile_prefix[lt];
     const uint64_t base = (uint64_t)rd.tile_prefix[lt] * rd.n_blocks + p;
-    float r = 0.f, gg = 0.f, b = 0.f;
-    for (uint32_t blk = 0; blk < rd.n_blocks; ++blk) {
-        const Float4 v = rd.blocksum[base + (uint64_t)blk * valid];
-        r += v.x; gg += v.y; b += v.z;
-    }
     uint32_t px, py;
     tile_pixel(rd, g, p, px, py);
-    float* q = rd.shard_count <= 1u ? out + ((uint64_t)(g.y0 + py) * rd.width + (g.x0 + px)) * 3u
-                                    : out + ((uint64_t)lt * ts2 + (uint64_t)py * rd.tile_size + px) * 3u;   // tile-compact layout
+    const uint64_t o = rd.shard_count <= 1u ? ((uint64_t)(g.y0 + py) * rd.width + (g.x0 + px)) * 3u
+                                            : ((uint64_t)lt * ts2 + (uint64_t)py * rd.tile_size + px) * 3u;   // tile-compact layout
+    float* q = out + o;
+    float r = 0.f, gg = 0.f, b = 0.f;
+    if (rd.accumulate != 0u) { r = q[0]; gg = q[1]; b = q[2]; }
+    if (rd.sq_sum != nullptr) {
+        float* qs = rd.sq_sum + o;
+        float r2 = 0.f, g2 = 0.f, b2 = 0.f;
+        if (rd.accumulate != 0u) { r2 = qs[0]; g2 = qs[1]; b2 = qs[2]; }
+        for (uint32_t blk = 0; blk < rd.n_blocks; ++blk) {
+            const Float4 v = rd.blocksum[base + (uint64_t)blk * valid];
+            r += v.x; gg += v.y; b += v.z;
+            r2 += v.x * v.x; g2 += v.y * v.y; b2 += v.z * v.z;   // (-ffp-contract=off: a rounded product, then the add)
+        }
+        qs[0] = r2; qs[1] = g2; qs[2] = b2;
+    } else {
+        for (uint32_t blk = 0; blk < rd.n_blocks; ++blk) {
+            const Float4 v = rd.blocksum[base + (uint64_t)blk * valid];
+            r += v.x; gg += v.y; b += v.z;
+        }
+    }
     q[0] = r; q[1] = gg; q[2] = b;
 }
 

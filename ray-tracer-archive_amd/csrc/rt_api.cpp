@@ -61,15 +61,52 @@ int rti::validate_params(RtCtx* ctx, const RtParams* p) {
     return RT_OK;
 }
 
-static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, void* d_out, RtStats* stats);
+// Samples per work item, as 1 << shift, for a frame of `frame_samples` samples per pixel: 1 whenever the whole IMAGE (all shards, so that
+// every shard sums the same way) has fewer than 2^32 - 2^28 samples (what a u32 item index can address) — a path is then one sample,
+// nothing is regenerated mid-flight and the radiance of every sample is stored on its own (16 B each: 64 GB for an unsharded render at
+// the limit; this is a 288 GB device, and a sharded render holds its own shard's samples only). Larger renders group 2, 4, ...
+// consecutive samples of a pixel into one item. rt_render and every pass of a progressive frame (rt_pass_check) group by this rule.
+static uint32_t frame_block_shift(const RtParams& p, uint32_t frame_samples) {
+    uint32_t block_shift = (p.flags & RT_FLAG_SAMPLE_BLOCKS) ? 4u : 0u;
+    while ((1u << block_shift) > frame_samples && block_shift > 0) --block_shift;
+    const uint64_t image_pixels = (uint64_t)p.width * p.height;
+    while ((1u << block_shift) < frame_samples && image_pixels * ((frame_samples + (1u << block_shift) - 1) >> block_shift) >= kMaxItems) ++block_shift;
+    return block_shift;
+}
+
+// RtPassOptions against the params (rt_pass_check): the message names what is wrong. *shift = the frame's grouping.
+static int check_pass(RtCtx* ctx, const RtParams* p, const RtPassOptions* o, uint32_t* shift) {
+    const int v = validate_params(ctx, p); if (v != RT_OK) return v;
+    if (!o) return set_err(ctx, RT_ERR_INVALID, "pass options are null");
+    if (o->struct_bytes < sizeof(RtPassOptions) || o->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtPassOptions.struct_bytes is not set (sizeof(RtPassOptions))");
+    if (o->flags & ~(uint32_t)RT_PASS_ACCUMULATE) return set_err(ctx, RT_ERR_INVALID, "RtPassOptions.flags holds an unknown bit");
+    const uint64_t end = (uint64_t)o->first_sample + p->samples_per_pixel;
+    if (end > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "first_sample + samples_per_pixel must be < 2^32");
+    if (o->frame_samples < end) return set_err(ctx, RT_ERR_INVALID, "frame_samples is smaller than the end of the pass (first_sample + samples_per_pixel)");
+    const uint32_t s = frame_block_shift(*p, o->frame_samples), m = 1u << s;
+    if (o->first_sample & (m - 1u))
+        return set_err(ctx, RT_ERR_INVALID, "first_sample is not a multiple of the samples per work item (" + std::to_string(m) + " for this frame)");
+    if ((end & (m - 1u)) && end != o->frame_samples)
+        return set_err(ctx, RT_ERR_INVALID, "the pass ends inside a work item of " + std::to_string(m) + " samples (end on a multiple of it, or at frame_samples)");
+    if (shift) *shift = s;
+    return RT_OK;
+}
+
+static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions& pass, void* d_out, void* d_sq, RtStats* stats);
 
 // A render that fails half way (a HIP error, out of memory) must not leave work or recorded events in flight on the
 // caller's stream: drain it before the error goes back.
-int rti::render_checked(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, void* d_out, RtStats* stats) {
+static int render_pass_checked(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions& pass, void* d_out, void* d_sq,
+                               RtStats* stats) {
     if (ctx->fail_renders != 0u) { --ctx->fail_renders; return set_err(ctx, RT_ERR_DEVICE, "injected failure (rt_test_fail_next_renders)"); }
-    const int r = render_impl(ctx, scene, cam, prm, d_out, stats);
+    const int r = render_impl(ctx, scene, cam, prm, pass, d_out, d_sq, stats);
     if (r != RT_OK) { const std::string keep = ctx->err; (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); ctx->err = keep; g_last_error = keep; }
     return r;
+}
+// the whole frame as one pass that overwrites: what rt_render computes
+static RtPassOptions one_shot(const RtParams* prm) { return RtPassOptions{(uint32_t)sizeof(RtPassOptions), 0u, 0u, prm->samples_per_pixel}; }
+int rti::render_checked(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, void* d_out, RtStats* stats) {
+    return render_pass_checked(ctx, scene, cam, prm, one_shot(prm), d_out, nullptr, stats);
 }
 
 template <class T>
@@ -137,7 +174,7 @@ int rt_ctx_destroy(RtCtx* ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     for (auto& pl : ctx->pool) for (auto& b : pl) b.release();
     comm_release(ctx);
-    ctx->blocksum.release(); ctx->counters.release(); ctx->out_tmp.release(); ctx->tile_prefix.release(); ctx->shard_tmp.release();
+    ctx->blocksum.release(); ctx->counters.release(); ctx->out_tmp.release(); ctx->sq_tmp.release(); ctx->tile_prefix.release(); ctx->shard_tmp.release();
     for (hipEvent_t ev : ctx->events) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->ev_gather) if (ev) (void)hipEventDestroy(ev);
     if (ctx->h_count) (void)hipHostFree(ctx->h_count);
@@ -666,7 +703,7 @@ int rt_output_floats(const RtParams* p, uint64_t* out_n) {
         if (e_ != hipSuccess) return set_err(ctx, RT_ERR_DEVICE, std::string(rtk::launch_note() ? rtk::launch_note() : #call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, void* d_out, RtStats* stats) {
+static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions& pass, void* d_out, void* d_sq, RtStats* stats) {
     using clk = std::chrono::steady_clock;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Tiling tl; make_tiling(*prm, tl);
@@ -676,7 +713,9 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     cp3(rd.cam_origin, cam->origin); cp3(rd.cam_llc, cam->lower_left_corner); cp3(rd.cam_horizontal, cam->horizontal); cp3(rd.cam_vertical, cam->vertical);
     cp3(rd.cam_u, cam->u); cp3(rd.cam_v, cam->v);
     rd.cam_lens_radius = (float)cam->lens_radius; rd.cam_time0 = (float)cam->time0; rd.cam_time1 = (float)cam->time1;
-    rd.width = prm->width; rd.height = prm->height; rd.spp = prm->samples_per_pixel; rd.max_depth = prm->max_depth; rd.seed = prm->seed;
+    // a pass renders samples first_sample .. first_sample + samples_per_pixel - 1: rd.spp is its END (absolute), n_blocks its items per pixel
+    rd.width = prm->width; rd.height = prm->height; rd.spp = pass.first_sample + prm->samples_per_pixel; rd.max_depth = prm->max_depth; rd.seed = prm->seed;
+    rd.first_sample = pass.first_sample; rd.accumulate = (pass.flags & RT_PASS_ACCUMULATE) ? 1u : 0u; rd.sq_sum = (float*)d_sq;
     rd.nan_policy = prm->nan_policy; rd.bg_mode = scene->bg_mode; for (int i = 0; i < 3; ++i) rd.bg[i] = scene->bg[i];
     rd.tile_size = tl.ts; rd.tiles_x = tl.tiles_x; rd.tiles_y = tl.tiles_y; rd.shard_index = si; rd.shard_count = sc;
     // in-image pixels per local tile (edge tiles are clipped) -> prefix table
@@ -689,18 +728,9 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
         if (valid_pixels > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "more than 2^32 - 1 pixels in one shard (shard the image further)");
         prefix[lt + 1] = (uint32_t)valid_pixels;
     }
-    // samples per work item: 1 whenever the whole IMAGE (all shards, so that every shard sums the same way) has fewer
-    // than 2^32 - 2^28 samples (what a u32 item index can address) — a path is then one sample, nothing is regenerated
-    // mid-flight and the radiance of every sample is stored on its own (16 B each: 64 GB for an unsharded render at the
-    // limit; this is a 288 GB device, and a sharded render holds its own shard's samples only). Larger renders group
-    // 2, 4, ... consecutive samples of a pixel into one item.
-    uint32_t block_shift = (prm->flags & RT_FLAG_SAMPLE_BLOCKS) ? 4u : 0u;
-    while ((1u << block_shift) > rd.spp && block_shift > 0) --block_shift;
-    {
-        const uint64_t image_pixels = (uint64_t)prm->width * prm->height;
-        while ((1u << block_shift) < rd.spp && image_pixels * ((rd.spp + (1u << block_shift) - 1) >> block_shift) >= kMaxItems) ++block_shift;
-    }
-    rd.block_shift = block_shift; rd.n_blocks = (rd.spp + (1u << block_shift) - 1) >> block_shift;
+    // samples per work item: the frame's grouping (frame_block_shift); the pass starts on an item boundary (check_pass)
+    const uint32_t block_shift = frame_block_shift(*prm, pass.frame_samples);
+    rd.block_shift = block_shift; rd.n_blocks = (prm->samples_per_pixel + (1u << block_shift) - 1) >> block_shift;
     const uint64_t total_items = valid_pixels * rd.n_blocks;
     if (total_items >= kMaxItems) return set_err(ctx, RT_ERR_INVALID, "too many work items for one shard (image too large)");
     rd.total_items = (uint32_t)total_items;
@@ -903,7 +933,10 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     const uint32_t launched = lanes[0].launched + (n_lanes > 1 ? lanes[1].launched : 0u), drained = lanes[0].drained + (n_lanes > 1 ? lanes[1].drained : 0u);
     hipEvent_t r0 = nullptr, r1 = nullptr;
     if (timing) HIP_TRY(ctx, next_event(r0));
-    if (sc > 1) HIP_TRY(ctx, hipMemsetAsync(d_out, 0, (size_t)tl.n_local * tl.ts * tl.ts * 3 * sizeof(float), ctx->stream));   // clipped pixels of edge tiles stay 0
+    if (sc > 1 && !rd.accumulate) {   // clipped pixels of edge tiles stay 0 (an accumulating pass finds them 0 from its first pass)
+        HIP_TRY(ctx, hipMemsetAsync(d_out, 0, (size_t)tl.n_local * tl.ts * tl.ts * 3 * sizeof(float), ctx->stream));
+        if (d_sq) HIP_TRY(ctx, hipMemsetAsync(d_sq, 0, (size_t)tl.n_local * tl.ts * tl.ts * 3 * sizeof(float), ctx->stream));
+    }
     HIP_TRY(ctx, rtk::launch_resolve(rd, (float*)d_out, (uint32_t)valid_pixels, ctx->stream));
     if (timing) { HIP_TRY(ctx, next_event(r1)); spans.push_back({r0, r1, 2}); }
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, c64, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -923,7 +956,7 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
                 ++it;
             }
         }
-        stats->samples = valid_pixels * rd.spp;
+        stats->samples = valid_pixels * prm->samples_per_pixel;
         stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];
 #if defined(RT_STAMPS) || defined(RT_SHADE_STAMPS)
         const bool copy_counts = true;    // k_extend's pass statistics travel in these slots (scripts/gpu_stamps.py)
@@ -946,27 +979,62 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     return RT_OK;
 }
 
+int rt_pass_check(const RtParams* params, const RtPassOptions* options, uint32_t* out_samples_per_item) {
+    uint32_t shift = 0;
+    const int r = check_pass(nullptr, params, options, &shift);
+    if (r != RT_OK) return r;
+    if (out_samples_per_item) *out_samples_per_item = 1u << shift;
+    return RT_OK;
+}
+
+int rt_render_pass_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions* options, void* rgb_sum_device,
+                          void* sq_sum_device, RtStats* stats) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    if (!scene || !cam || !rgb_sum_device) return set_err(ctx, RT_ERR_INVALID, "scene / cam / output is null");
+    const int v = check_pass(ctx, prm, options, nullptr); if (v != RT_OK) return v;
+    return render_pass_checked(ctx, scene, cam, prm, *options, rgb_sum_device, sq_sum_device, stats);
+}
+
+int rt_render_pass(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions* options, float* rgb_sum_host,
+                   float* sq_sum_host, RtStats* stats) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    if (!scene || !cam || !rgb_sum_host) return set_err(ctx, RT_ERR_INVALID, "scene / cam / output is null");
+    const int v = check_pass(ctx, prm, options, nullptr); if (v != RT_OK) return v;
+    uint64_t n = 0; rt_output_floats(prm, &n);
+    const size_t bytes = n * sizeof(float);
+    const bool acc = (options->flags & RT_PASS_ACCUMULATE) != 0u;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, ctx->out_tmp.ensure(bytes));
+    if (sq_sum_host) HIP_TRY(ctx, ctx->sq_tmp.ensure(bytes));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (acc) {   // the fold goes on from the caller's sums
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->out_tmp.p, rgb_sum_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (sq_sum_host) HIP_TRY(ctx, hipMemcpyAsync(ctx->sq_tmp.p, sq_sum_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const int r = render_pass_checked(ctx, scene, cam, prm, *options, ctx->out_tmp.p, sq_sum_host ? ctx->sq_tmp.p : nullptr, stats);
+    if (r != RT_OK) return r;
+    HIP_TRY(ctx, hipMemcpyAsync(rgb_sum_host, ctx->out_tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (sq_sum_host) HIP_TRY(ctx, hipMemcpyAsync(sq_sum_host, ctx->sq_tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT_OK;
+}
+
+// the one-shot entry points are the pass {first_sample 0, frame_samples spp, overwrite}: one code path
 int rt_render_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, void* rgb_sum_device, RtStats* stats) {
     if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
     if (!scene || !cam || !rgb_sum_device) return set_err(ctx, RT_ERR_INVALID, "scene / cam / output is null");
-    const int v = validate_params(ctx, prm); if (v != RT_OK) return v;
-    return render_checked(ctx, scene, cam, prm, rgb_sum_device, stats);
+    if (!prm) return validate_params(ctx, prm);
+    const RtPassOptions one = one_shot(prm);
+    return rt_render_pass_device(ctx, scene, cam, prm, &one, rgb_sum_device, nullptr, stats);
 }
 
 int rt_render(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, float* rgb_sum_host, RtStats* stats) {
     if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
     if (!scene || !cam || !rgb_sum_host) return set_err(ctx, RT_ERR_INVALID, "scene / cam / output is null");
-    const int v = validate_params(ctx, prm); if (v != RT_OK) return v;
-    uint64_t n = 0; rt_output_floats(prm, &n);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, ctx->out_tmp.ensure(n * sizeof(float)));
-    const auto t0 = std::chrono::steady_clock::now();
-    const int r = render_checked(ctx, scene, cam, prm, ctx->out_tmp.p, stats);
-    if (r != RT_OK) return r;
-    HIP_TRY(ctx, hipMemcpyAsync(rgb_sum_host, ctx->out_tmp.p, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return RT_OK;
+    if (!prm) return validate_params(ctx, prm);
+    const RtPassOptions one = one_shot(prm);
+    return rt_render_pass(ctx, scene, cam, prm, &one, rgb_sum_host, nullptr, stats);
 }
 
 int rt_untile(const RtParams* p, const float* gathered, float* rgb_sum) { return untile_host<float>(p, gathered, rgb_sum); }

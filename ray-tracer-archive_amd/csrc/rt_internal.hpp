@@ -36,6 +36,7 @@ struct RtCtx {
     std::string err;
     // grow-only work buffers
     rti::DevBuf pool[2][6]; rti::DevBuf blocksum; rti::DevBuf counters; rti::DevBuf out_tmp; rti::DevBuf tile_prefix;
+    rti::DevBuf sq_tmp;                          // rt_render_pass (host variant): the squared sums on their way to and from the caller
     uint32_t* h_count = nullptr;                 // pinned
     unsigned long long* h_counters = nullptr;    // pinned
     std::vector<hipEvent_t> events;
