@@ -126,6 +126,11 @@ pub const RT_PASS_ACCUMULATE: u32 = 1;    // add into the output buffer(s), fold
 pub struct RtPassOptions {
     pub struct_bytes: u32, pub flags: u32, pub first_sample: u32, pub frame_samples: u32,
 }
+// adaptive sampling: passes over the pixels whose standard error is still above the tolerance (rt_adaptive_select)
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtAdaptiveOptions {
+    pub struct_bytes: u32, pub min_samples: u32, pub rel_error: f64, pub abs_error: f64,
+}
 
 pub const RT_N_PRIM_TYPES: usize = 6;
 #[repr(C)] #[derive(Clone, Copy, Default, Debug)]
@@ -184,6 +189,19 @@ extern "C" {
                           rgb_sum_host: *mut f32, sq_sum_host: *mut f32, stats: *mut RtStats) -> c_int;
     pub fn rt_render_pass_device(ctx: *mut RtCtx, scene: *const RtScene, cam: *const RtCamera, params: *const RtParams, options: *const RtPassOptions,
                                  rgb_sum_device: *mut c_void, sq_sum_device: *mut c_void, stats: *mut RtStats) -> c_int;
+    /// host only: validates adaptive options for a frame (min_samples >= 2 work items, tolerances finite and >= 0, first_sample on an item boundary)
+    pub fn rt_adaptive_check(params: *const RtParams, options: *const RtAdaptiveOptions, first_sample: u32, frame_samples: u32) -> c_int;
+    /// the active list: ascending output slots with counts == first_sample that are below min_samples or not converged; *n_out entries
+    pub fn rt_adaptive_select(ctx: *mut RtCtx, params: *const RtParams, options: *const RtAdaptiveOptions, first_sample: u32, frame_samples: u32,
+                              rgb_sum_device: *const c_void, sq_sum_device: *const c_void, counts_device: *const c_void, pixels_device_out: *mut c_void,
+                              n_out: *mut u32) -> c_int;
+    /// samples first_sample .. first_sample + spp - 1 of the listed slots only; counts[slot] = first_sample + spp; sq_sum_device may be null
+    pub fn rt_render_pass_pixels_device(ctx: *mut RtCtx, scene: *const RtScene, cam: *const RtCamera, params: *const RtParams, options: *const RtPassOptions,
+                                        pixels_device: *const c_void, n_pixels: u32, rgb_sum_device: *mut c_void, sq_sum_device: *mut c_void,
+                                        counts_device: *mut c_void, stats: *mut RtStats) -> c_int;
+    /// write_color with each pixel's own count (full frame); a count of 0 gives black
+    pub fn rt_resolve_counts_device(ctx: *mut RtCtx, rgb_sum_device: *const c_void, counts_device: *const c_void, width: u32, height: u32,
+                                    rgb8_device: *mut c_void) -> c_int;
     pub fn rt_untile(params: *const RtParams, gathered: *const f32, rgb_sum: *mut f32) -> c_int;
     /// write_color (main.rs:141-169) on the device
     pub fn rt_resolve_device(ctx: *mut RtCtx, rgb_sum_device: *const c_void, width: u32, height: u32,

@@ -342,6 +342,45 @@ int rt_render_pass(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const 
 int rt_render_pass_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* params, const RtPassOptions* options,
                           void* rgb_sum_device, void* sq_sum_device /* NULL = not wanted */, RtStats* stats);
 
+/* ---- adaptive sampling: passes over the pixels that are still noisy ---------------------------------------------------------------------
+ *
+ * OUTPUT SLOTS are the pixels of the rgb_sum layout: rt_output_floats / 3 of them (the full frame, slot = y * width + x; or this shard's
+ * tiles back to back, slot = local tile * tile_size^2 + row-major position in the tile). Clipped pixels of edge tiles are slots too, but
+ * never image pixels: they are never selected and never accepted in a list.
+ * The caller owns a COUNTS buffer, one uint32_t per slot: the samples each pixel holds. Invariant: every pixel's rgb_sum / sq_sum equals,
+ * bit for bit, what ONE rt_render_pass over [0, counts[p]) (same frame_samples) writes for that pixel. A frame starts with counts 0.
+ *
+ * rt_adaptive_select writes the ACTIVE LIST: the in-image slots p, ascending, with
+ *     counts[p] == first_sample  (the pixel took every pass so far: a pixel that stopped never comes back),
+ *     first_sample < frame_samples, and
+ *     counts[p] < min_samples, or the pixel is not converged.
+ * Converged, per channel, in f64 and in this order (m = samples per work item of the frame, k = counts / m rounded up):
+ *     S = rgb_sum, Q = sq_sum;  var = max(Q - S*S/k, 0) / (k (k - 1));  tol = abs_error + rel_error * |S / counts|;  var / (m*m) <= tol*tol
+ * (the standard error above, squared); a non-finite S or Q, or k < 2, is not converged. The list does not depend on any atomic ordering.
+ *
+ * rt_render_pass_pixels_device renders samples [first_sample, first_sample + spp) of the listed pixels only, under the RtPassOptions
+ * rules of a pass (ACCUMULATE per listed pixel), sets counts[p] = first_sample + spp for them and leaves every other slot's rgb, sq and
+ * count untouched (clipped slots included). Before anything is rendered a device kernel checks the list: every entry an in-image slot,
+ * strictly ascending, counts[entry] == first_sample. A list that fails is RT_ERR_INVALID with the reason, and nothing is written.
+ * n_pixels == 0 is a no-op. RtStats.samples = n_pixels * spp. The loop of a frame is: select, pass, select, pass, ... until the list is
+ * empty, then rt_resolve_counts_device. Stopping on a pixel's own samples is a (small) bias: the invariant holds, an unbiased mean does not. */
+typedef struct RtAdaptiveOptions {
+    uint32_t struct_bytes;    /* sizeof(RtAdaptiveOptions) as the caller compiled it (the struct may grow at its end) */
+    uint32_t min_samples;     /* every pixel takes at least this many samples; >= 2 m */
+    double rel_error;         /* tolerance of the standard error relative to the pixel mean, >= 0 and finite */
+    double abs_error;         /* absolute tolerance of the standard error, >= 0 and finite */
+} RtAdaptiveOptions;
+/* Host only, no device: validates (params, options, first_sample, frame_samples): first_sample on a work-item boundary, <= frame_samples. */
+int rt_adaptive_check(const RtParams* params, const RtAdaptiveOptions* options, uint32_t first_sample, uint32_t frame_samples);
+/* pixels_device_out: room for rt_output_floats / 3 entries; *n_out = the list's length. Blocks until done. */
+int rt_adaptive_select(RtCtx* ctx, const RtParams* params, const RtAdaptiveOptions* options, uint32_t first_sample, uint32_t frame_samples,
+                       const void* rgb_sum_device, const void* sq_sum_device, const void* counts_device, void* pixels_device_out, uint32_t* n_out);
+int rt_render_pass_pixels_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* params, const RtPassOptions* options,
+                                 const void* pixels_device, uint32_t n_pixels, void* rgb_sum_device, void* sq_sum_device /* NULL = not wanted */,
+                                 void* counts_device, RtStats* stats);
+/* write_color with every pixel's own count (full frame, width * height counts): spp = counts[p]; a count of 0 gives (0, 0, 0). */
+int rt_resolve_counts_device(RtCtx* ctx, const void* rgb_sum_device, const void* counts_device, uint32_t width, uint32_t height, void* rgb8_device);
+
 /* Host-side helper: scatter `shard_count` gathered shard buffers (each rt_output_floats long,
    in shard order) into a full-frame rgb_sum. */
 int rt_untile(const RtParams* params, const float* gathered, float* rgb_sum);

@@ -107,6 +107,10 @@ class RtPassOptions(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32), ("first_sample", C.c_uint32), ("frame_samples", C.c_uint32)]
 
 
+class RtAdaptiveOptions(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("min_samples", C.c_uint32), ("rel_error", C.c_double), ("abs_error", C.c_double)]
+
+
 class RtWideInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("n_leaf_entries", C.c_uint64), ("n_inner_entries", C.c_uint64), ("n_prims", C.c_uint64),
                 ("depth", C.c_uint32), ("_pad", C.c_uint32), ("mean_children", C.c_double), ("mean_leaf_members", C.c_double)]
@@ -119,7 +123,8 @@ RT_HIP_SYMBOLS = ["rt_ctx_create", "rt_ctx_destroy", "rt_scene_upload", "rt_scen
                   "rt_render_multi", "rt_render_multi_rgb8", "rt_last_error_multi", "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_selftest",
                   "rt_render_gather", "rt_untile_rgb8", "rt_untile_device", "rt_scene_top_layout_check", "rt_scene_upload_ex", "rt_scene_upload_multi_ex",
                   "rt_runtime_libraries", "rt_test_fail_next_renders", "rt_test_device_workers", "rt_scene_compile_info_ex", "rt_scene_compile_dump_ex", "rt_scene_wide_layout_check",
-                  "rt_pass_check", "rt_render_pass", "rt_render_pass_device"]
+                  "rt_pass_check", "rt_render_pass", "rt_render_pass_device",
+                  "rt_adaptive_check", "rt_adaptive_select", "rt_render_pass_pixels_device", "rt_resolve_counts_device"]
 RT_HOST_SYMBOLS = ["rt_host_scene_create", "rt_host_scene_desc", "rt_host_scene_camera", "rt_host_scene_destroy", "rt_host_camera_new",
                    "rt_host_write_color", "rt_host_tonemap", "rt_host_write_png", "rt_host_write_jpeg", "rt_host_write_image"]
 
@@ -162,6 +167,14 @@ def declare(lib):
     lib.rt_render_pass.argtypes = [vp, vp, P(RtCamera), P(RtParams), P(RtPassOptions), P(C.c_float), P(C.c_float), P(RtStats)]
     lib.rt_render_pass_device.restype = i32
     lib.rt_render_pass_device.argtypes = [vp, vp, P(RtCamera), P(RtParams), P(RtPassOptions), vp, vp, P(RtStats)]
+    lib.rt_adaptive_check.restype = i32
+    lib.rt_adaptive_check.argtypes = [P(RtParams), P(RtAdaptiveOptions), u32, u32]
+    lib.rt_adaptive_select.restype = i32
+    lib.rt_adaptive_select.argtypes = [vp, P(RtParams), P(RtAdaptiveOptions), u32, u32, vp, vp, vp, vp, P(u32)]
+    lib.rt_render_pass_pixels_device.restype = i32
+    lib.rt_render_pass_pixels_device.argtypes = [vp, vp, P(RtCamera), P(RtParams), P(RtPassOptions), vp, u32, vp, vp, vp, P(RtStats)]
+    lib.rt_resolve_counts_device.restype = i32
+    lib.rt_resolve_counts_device.argtypes = [vp, vp, vp, u32, u32, vp]
     lib.rt_untile.restype = i32
     lib.rt_untile.argtypes = [P(RtParams), P(C.c_float), P(C.c_float)]
     lib.rt_resolve_device.restype = i32

@@ -55,6 +55,24 @@ def pass_check(params, first_sample, frame_samples, accumulate=False):
     return m.value
 
 
+def adaptive_options(min_samples, rel_error=0.0, abs_error=0.0):
+    return A.RtAdaptiveOptions(C.sizeof(A.RtAdaptiveOptions), int(min_samples), float(rel_error), float(abs_error))
+
+
+def adaptive_check(params, options, first_sample, frame_samples):
+    """rt_adaptive_check (host only): raises RtError (RT_ERR_INVALID, with the reason) for options the contract refuses."""
+    _check(lib().rt_adaptive_check(C.byref(params), C.byref(options), first_sample, frame_samples))
+
+
+def _check_device(a, b, n, what, float_):
+    """a (and b, unless None) are contiguous CUDA tensors of n elements (n None: any), float32 or a 32-bit integer type."""
+    import torch
+    ok = (torch.float32,) if float_ else (torch.int32, torch.uint32) if hasattr(torch, "uint32") else (torch.int32,)
+    for t in (a, b):
+        if t is not None and (not t.is_cuda or t.dtype not in ok or not t.is_contiguous() or (n is not None and t.numel() != n)):
+            raise ValueError(f"{what}: contiguous CUDA tensors of {'float32' if float_ else '32-bit integers'}" + (f", {n} elements" if n is not None else ""))
+
+
 def output_floats(params):
     n = C.c_uint64(0)
     _check(lib().rt_output_floats(C.byref(params), C.byref(n)))
@@ -310,6 +328,49 @@ class Context:
             rgb_sum = rgb_sum.reshape(params.height, params.width, 3)
             sq_sum = sq_sum.reshape(params.height, params.width, 3) if sq_sum is not None else None
         return rgb_sum, sq_sum, st.as_dict()
+
+    # ---- adaptive sampling (include/rt_hip.h, "adaptive sampling"): device tensors only ----
+    def adaptive_select(self, params, options, first_sample, frame_samples, rgb_sum, sq_sum, counts, pixels_out):
+        """rt_adaptive_select: writes the active list (ascending output slots, int32/uint32 tensor of at least output_floats / 3 entries)
+        into pixels_out and returns its length."""
+        slots = output_floats(params) // 3
+        _check_device(rgb_sum, sq_sum, n=3 * slots, what="rgb_sum / sq_sum", float_=True)
+        _check_device(counts, pixels_out, n=slots, what="counts / pixels_out", float_=False)
+        n = C.c_uint32(0)
+        import torch
+        torch.cuda.synchronize(rgb_sum.device)
+        _check(lib().rt_adaptive_select(self._h, C.byref(params), C.byref(options), first_sample, frame_samples, C.c_void_p(rgb_sum.data_ptr()),
+                                        C.c_void_p(sq_sum.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(pixels_out.data_ptr()), C.byref(n)), self._h)
+        return n.value
+
+    def render_pass_pixels(self, scene, cam, params, first_sample, frame_samples, accumulate, pixels, n_pixels, rgb_sum, sq_sum, counts):
+        """rt_render_pass_pixels_device: samples first_sample .. first_sample + params.samples_per_pixel - 1 of the first n_pixels slots
+        of `pixels` only; counts of those slots become the pass's end. sq_sum may be None. Returns the stats."""
+        slots = output_floats(params) // 3
+        _check_device(rgb_sum, sq_sum, n=3 * slots, what="rgb_sum / sq_sum", float_=True)
+        _check_device(counts, None, n=slots, what="counts", float_=False)
+        _check_device(pixels, None, n=None, what="pixels", float_=False)
+        if n_pixels > pixels.numel():
+            raise ValueError("n_pixels is larger than the pixel list")
+        opt = A.RtPassOptions(C.sizeof(A.RtPassOptions), A.RT_PASS_ACCUMULATE if accumulate else 0, first_sample, frame_samples)
+        st = A.RtStats()
+        import torch
+        torch.cuda.synchronize(rgb_sum.device)
+        _check(lib().rt_render_pass_pixels_device(self._h, scene._h, C.byref(cam), C.byref(params), C.byref(opt), C.c_void_p(pixels.data_ptr()), n_pixels,
+                                                  C.c_void_p(rgb_sum.data_ptr()), C.c_void_p(sq_sum.data_ptr()) if sq_sum is not None else None,
+                                                  C.c_void_p(counts.data_ptr()), C.byref(st)), self._h)
+        return st.as_dict()
+
+    def resolve_counts_device(self, rgb_sum, counts, width, height, rgb8_out):
+        """rt_resolve_counts_device: write_color of a full frame with every pixel's own sample count, into a uint8 tensor."""
+        _check_device(rgb_sum, None, n=3 * width * height, what="rgb_sum", float_=True)
+        _check_device(counts, None, n=width * height, what="counts", float_=False)
+        import torch
+        if not rgb8_out.is_cuda or rgb8_out.dtype != torch.uint8 or not rgb8_out.is_contiguous() or rgb8_out.numel() != 3 * width * height:
+            raise ValueError("rgb8_out must be a contiguous uint8 CUDA tensor of width * height * 3 elements")
+        torch.cuda.synchronize(rgb_sum.device)
+        _check(lib().rt_resolve_counts_device(self._h, C.c_void_p(rgb_sum.data_ptr()), C.c_void_p(counts.data_ptr()), width, height,
+                                              C.c_void_p(rgb8_out.data_ptr())), self._h)
 
     # ---- one process per GPU: RCCL communicator on this context (rt_multi.cpp) ----
     def comm_init_rank(self, unique_id, rank, world):

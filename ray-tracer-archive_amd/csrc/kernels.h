@@ -131,6 +131,12 @@ struct RenderDev {
     uint32_t first_sample;
     uint32_t accumulate;    // k_resolve folds on from the value already in the output (RT_PASS_ACCUMULATE) instead of from 0
     float* sq_sum;          // k_resolve: also the sum of the squared item sums per pixel and channel, same layout as the output; nullptr = not wanted
+    // a pass over a PIXEL LIST (rt_render_pass_pixels_device; n_list = 0: every pixel of the shard). Work item w = blk * n_list + i renders
+    // block blk of output slot list[i], so consecutive items go to neighbouring listed pixels; list_map[slot] = i for every listed slot.
+    const uint32_t* list; uint32_t n_list;
+    const uint32_t* list_map;
+    FastDiv div_list;       // n_list
+    uint32_t* counts;       // k_resolve_list: counts[slot] = spp (the pass's end)
 };
 
 struct LaunchCfg {
@@ -158,6 +164,20 @@ hipError_t launch_shade(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev&
 // whether the kernels compiled for these features can test the first sphere where a ray is made (RenderDev::first_in_shade)
 bool can_test_first_in_shade(uint32_t features);
 hipError_t launch_resolve(const RenderDev& rd, float* out, uint32_t n_valid_pixels, hipStream_t stream);
+// adaptive sampling (kernels.hip: the list pass's resolve; adaptive.hip: list check, slot -> list index map, selection, per-pixel write_color)
+hipError_t launch_resolve_list(const RenderDev& rd, float* out, hipStream_t stream);
+hipError_t launch_list_check(const uint32_t* list, uint32_t n, const uint32_t* counts, uint32_t first_sample, uint32_t width, uint32_t height, uint32_t shard_count,
+                             uint32_t shard_index, uint32_t tile_size, uint32_t tiles_x, uint32_t slots, uint32_t* verdict, hipStream_t stream);
+hipError_t launch_list_map(const uint32_t* list, uint32_t n, uint32_t* map, hipStream_t stream);
+struct SelectArgs {
+    const float* rgb; const float* sq; const uint32_t* counts;
+    uint32_t slots, first_sample, frame_samples, m, min_samples;
+    double rel_error, abs_error;
+    uint32_t width, height, shard_count, shard_index, tile_size, tiles_x;   // slot -> pixel: clipped slots of edge tiles are never selected
+};
+// wave ballots (masks: slots / 64 rounded up), one-workgroup scan of their popcounts (offsets, *n_out), scatter into out
+hipError_t launch_select(const SelectArgs& a, unsigned long long* masks, uint32_t* offsets, uint32_t* out, uint32_t* n_out, hipStream_t stream);
+hipError_t launch_write_color_counts(const float* rgb_sum, const uint32_t* counts, uint32_t n_pixels, uint8_t* rgb8, hipStream_t stream);
 hipError_t launch_write_color(const float* rgb_sum, uint32_t n_pixels, uint32_t spp, uint8_t* rgb8, hipStream_t stream);
 // multi-GPU root: gathered shard buffers -> full frame (rt_multi.cpp)
 hipError_t launch_untile_f32(const float* gathered, float* frame, uint32_t width, uint32_t height, uint32_t ts, uint32_t tiles_x, uint32_t world, uint64_t per_shard,

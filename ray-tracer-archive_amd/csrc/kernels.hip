@@ -428,7 +428,23 @@ DEVI uint32_t find_tile(const RenderDev& rd, uint64_t key, uint32_t scale, uint3
     }
     return lo;
 }
+// output slot (rgb_sum layout / 3) -> pixel: full frame y * width + x; tile-compact local tile * ts^2 + row-major position in the tile
+DEVI void slot_pixel(const RenderDev& rd, uint32_t slot, uint32_t& x, uint32_t& y) {
+    if (rd.shard_count <= 1u) { y = fdivu(slot, rd.div_width); x = slot - y * rd.width; return; }
+    const uint32_t lt = fdivu(slot, rd.div_ts2), r = slot - lt * (rd.tile_size * rd.tile_size);
+    const uint32_t py = fdivu(r, rd.div_ts), tile = rd.shard_index + lt * rd.shard_count, ty = fdivu(tile, rd.div_tiles_x);
+    x = (tile - ty * rd.tiles_x) * rd.tile_size + (r - py * rd.tile_size); y = ty * rd.tile_size + py;
+}
+// LIST: a pass over a pixel list (kernels.h RenderDev::list), compiled as kernel instances of its own so that the
+// register figures of the every-pixel instances do not move (a runtime branch cost k_shade 2 VGPRs and 8 B of scratch)
+template <bool LIST>
 DEVI WorkItem decode_work(const RenderDev& rd, uint32_t w) {
+    if constexpr (LIST) {   // w = blk * n_list + i
+        WorkItem it;
+        it.blk = fdivu(w, rd.div_list);
+        slot_pixel(rd, rd.list[w - it.blk * rd.n_list], it.x, it.y);
+        return it;
+    }
     uint32_t lt, r;
     if (rd.tiles_all_full != 0u) {
         lt = fdivu(w, rd.div_item_tile);
@@ -468,8 +484,17 @@ DEVI void item_pixel(const RenderDev& rd, uint32_t item, uint32_t& x, uint32_t& 
     y = fdivu(pixel, rd.div_width); x = pixel - y * rd.width;
 }
 // slot of an item's sum in blocksum = its work item number (inverse of decode_work)
+template <bool LIST>
 DEVI uint32_t item_slot(const RenderDev& rd, uint32_t item) {
     uint32_t x, y, blk; item_pixel(rd, item, x, y, blk);
+    if constexpr (LIST) {   // list pass: the pixel's output slot -> its list index (inverse of decode_work's list branch)
+        uint32_t slot = y * rd.width + x;
+        if (rd.shard_count > 1u) {
+            const uint32_t tx = fdivu(x, rd.div_ts), ty = fdivu(y, rd.div_ts);
+            slot = fdivu(ty * rd.tiles_x + tx - rd.shard_index, rd.div_shards) * (rd.tile_size * rd.tile_size) + (y - ty * rd.tile_size) * rd.tile_size + (x - tx * rd.tile_size);
+        }
+        return blk * rd.n_list + rd.list_map[slot];
+    }
     const uint32_t tx = fdivu(x, rd.div_ts), ty = fdivu(y, rd.div_ts);
     const uint32_t lt = fdivu(ty * rd.tiles_x + tx - rd.shard_index, rd.div_shards);
     const uint32_t x0 = tx * rd.tile_size, y0 = ty * rd.tile_size, w = min(rd.tile_size, rd.width - x0), h = min(rd.tile_size, rd.height - y0);
@@ -575,7 +600,7 @@ enum : uint32_t { SH_FINISHED = 1u, SH_TIME_ZERO = 2u };
 template <uint32_t FEAT> DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& d, float tm, PathState& s, Rng& g, uint32_t& depth, uint2 hit, V3& L,
                                                      unsigned long long& c_light_rect, unsigned long long& c_light_sphere);
 DEVI bool finish_sample(const RenderDev& rd, PathState& s, Rng& g, uint32_t& depth, V3 L, V3& o, V3& d, float& tm);
-DEVI void start_item(const RenderDev& rd, uint32_t work, PathState& s, Rng& g, V3& o, V3& d, float& tm);
+template <bool LIST> DEVI void start_item(const RenderDev& rd, uint32_t work, PathState& s, Rng& g, V3& o, V3& d, float& tm);
 // L, the radiance of the sample in flight, is not part of the state: `emitted` is non-zero only for
 // DiffuseLight, which never scatters (material.rs:12-14,184-190), and the background is returned on a miss
 // (main.rs:74-76) — so radiance is only ever added by the event that ENDS the path, in the same shading step
@@ -601,7 +626,7 @@ constexpr int kShadeBatch = 16;   // DRAIN: lanes on DONE that trigger a shading
 // 6 waves, and 210.5 ms at 8 with 44 B of scratch)
 // bytes of the record array of an LDS-resident scene as it is staged (kernels.h SceneDev::rec_unit)
 __host__ DEVI uint32_t lds_record_bytes(const SceneDev& sc) { return sc.n_records * (sc.rec_unit > 32u ? sc.rec_unit : 32u); }
-template <int MODE, uint32_t FEAT, bool COUNT, uint32_t TPB, bool DRAIN>
+template <int MODE, uint32_t FEAT, bool COUNT, uint32_t TPB, bool DRAIN, bool LIST>
 __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const uint32_t* __restrict__ count_ptr,
                                                  uint32_t* __restrict__ head, uint32_t* __restrict__ count_out_to_zero,
                                                  unsigned long long* __restrict__ counters, RenderDev rd) {
@@ -1138,12 +1163,12 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
                     if (sh & SH_FINISHED) {
                         if (COUNT) c_samples++;
                         if (finish_sample(rd, ps, g, depth, L, so, sd, tm)) {
-                            const uint32_t w = item_slot(rd, ps.work);
+                            const uint32_t w = item_slot<LIST>(rd, ps.work);
                             rd.blocksum[w] = Float4{ps.acc.x, ps.acc.y, ps.acc.z, 0.f};
                             want = true;
                             // regeneration: the next item of this path's lineage (kernels.h RenderDev::lineage), if there is one
                             const uint32_t next = w + rd.lineage;
-                            if (next < rd.total_items) { start_item(rd, next, ps, g, so, sd, tm); depth = 0; want = false; }
+                            if (next < rd.total_items) { start_item<LIST>(rd, next, ps, g, so, sd, tm); depth = 0; want = false; }
                         }
                     }
                     o = so; d = sd;
@@ -1526,14 +1551,16 @@ DEVI float first_sphere_hit(const RenderDev& rd, V3 o, V3 d, uint32_t from) {
 }
 
 // A fresh path for work item `work` (first sample of its block).
+template <bool LIST>
 DEVI void start_item(const RenderDev& rd, uint32_t work, PathState& s, Rng& g, V3& o, V3& d, float& tm) {
-    const WorkItem it = decode_work(rd, work);
+    const WorkItem it = decode_work<LIST>(rd, work);
     const uint32_t sample = rd.first_sample + (it.blk << rd.block_shift);   // absolute: a pass starts at first_sample
     new_camera_ray(rd, it.x, it.y, sample, g, o, d, tm);
     s.T = v3(1, 1, 1); s.acc = v3(0, 0, 0);
     s.work = item_id(rd, it.x, it.y, it.blk); s.sample = sample; s.from = 0u;
 }
 
+template <bool LIST>
 __global__ void __launch_bounds__(kShadeThreads) k_generate(PoolDev pool, RenderDev rd, uint32_t n_init, uint32_t* __restrict__ out_count) {
     // the first fill of the pool needs no allocator: work item i goes to queue (i / 512) mod kQueues, slot (i / 4096) * 512 + i mod 512
     // of it (the host passes n_init <= total_items), and the counters get their values from kQueues threads. (With the atomics +
@@ -1545,7 +1572,7 @@ __global__ void __launch_bounds__(kShadeThreads) k_generate(PoolDev pool, Render
     }
     if (i < n_init) {
         PathState s; V3 o, d; float tm; Rng g;
-        start_item(rd, i, s, g, o, d, tm);
+        start_item<LIST>(rd, i, s, g, o, d, tm);
         if (rd.first_in_shade != 0u) tm = first_sphere_hit(rd, o, d, 0u);         // (the time slot of a motionless scene: kernels.h)
         const uint32_t q = (i >> 9) & (kQueues - 1u), slot = ((i / (512u * kQueues)) << 9) | (i & 511u);
         store_path(pool, q * rd.queue_cap + slot, o, d, tm, s, g.n, 0u, rd.block_shift != 0u);
@@ -1874,7 +1901,7 @@ DEVI bool finish_sample(const RenderDev& rd, PathState& s, Rng& g, uint32_t& dep
     return true;
 }
 
-template <uint32_t FEAT, bool COUNT>
+template <uint32_t FEAT, bool COUNT, bool LIST>
 // The Cornell variant (rects, instance transforms, light sampling) at 6 waves per SIMD (79 VGPRs and 20 B of scratch instead of 87 and
 // none): k_shade 36.0 -> 32.2 ms on config 4. The full variant loses at every forced occupancy (5: 34.0 -> 36.7 ms on the book-2 final
 // scene, 6: 43.0), the sphere-only ones already run 8 waves.
@@ -1968,13 +1995,13 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
             // one sample done
             if (COUNT) c_samples++;
             if (finish_sample(rd, s, g, depth, L, o, d, tm)) {
-                const uint32_t w = item_slot(rd, s.work);
+                const uint32_t w = item_slot<LIST>(rd, s.work);
                 rd.blocksum[w] = Float4{s.acc.x, s.acc.y, s.acc.z, 0.f};
                 // ---- regeneration: the path goes on with the next item of its lineage (w + lineage), which no other path will ever ask for:
                 // no counter, no atomic, no barrier (round 2 drew items from a per-queue counter: one returning atomic and three barriers
                 // per workgroup) ----
                 const uint32_t next = w + rd.lineage;
-                if (next < rd.total_items) { start_item(rd, next, s, g, o, d, tm); depth = 0u; began = true; }
+                if (next < rd.total_items) { start_item<LIST>(rd, next, s, g, o, d, tm); depth = 0u; began = true; }
                 else alive = false;
             }
         }
@@ -2072,6 +2099,36 @@ __global__ void __launch_bounds__(256) k_resolve(RenderDev rd, float* __restrict
     q[0] = r; q[1] = gg; q[2] = b;
 }
 
+// k_resolve of a pass over a pixel list: one thread per list entry, item sums blocksum[blk * n_list + i] folded in block order with
+// k_resolve's arithmetic, into the entry's output slot; counts[slot] = the pass's end
+__global__ void __launch_bounds__(256) k_resolve_list(RenderDev rd, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rd.n_list) return;
+    const uint32_t slot = rd.list[i];
+    const uint64_t o = (uint64_t)slot * 3u;
+    float* q = out + o;
+    float r = 0.f, gg = 0.f, b = 0.f;
+    if (rd.accumulate != 0u) { r = q[0]; gg = q[1]; b = q[2]; }
+    if (rd.sq_sum != nullptr) {
+        float* qs = rd.sq_sum + o;
+        float r2 = 0.f, g2 = 0.f, b2 = 0.f;
+        if (rd.accumulate != 0u) { r2 = qs[0]; g2 = qs[1]; b2 = qs[2]; }
+        for (uint32_t blk = 0; blk < rd.n_blocks; ++blk) {
+            const Float4 v = rd.blocksum[(uint64_t)blk * rd.n_list + i];
+            r += v.x; gg += v.y; b += v.z;
+            r2 += v.x * v.x; g2 += v.y * v.y; b2 += v.z * v.z;
+        }
+        qs[0] = r2; qs[1] = g2; qs[2] = b2;
+    } else {
+        for (uint32_t blk = 0; blk < rd.n_blocks; ++blk) {
+            const Float4 v = rd.blocksum[(uint64_t)blk * rd.n_list + i];
+            r += v.x; gg += v.y; b += v.z;
+        }
+    }
+    q[0] = r; q[1] = gg; q[2] = b;
+    rd.counts[slot] = rd.spp;
+}
+
 // write_color (main.rs:141-169) on the device
 __global__ void __launch_bounds__(256) k_write_color(const float* __restrict__ rgb_sum, uint32_t n_pixels, uint32_t spp, uint8_t* __restrict__ rgb8) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2124,19 +2181,19 @@ template <class K> static hipError_t check_no_static_lds(K kernel) {
 template <int MODE, uint32_t FEAT, bool COUNT, uint32_t TPB>
 static hipError_t launch_extend_g(uint32_t n_groups, size_t lds_bytes, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
                                   uint32_t* head, uint32_t* cz, unsigned long long* counters, hipStream_t stream) {
-    hipLaunchKernelGGL((k_extend<MODE, FEAT, COUNT, TPB, false>), dim3(n_groups), dim3(TPB), lds_bytes, stream, sc, pool, count_ptr, head, cz, counters, rd);
+    hipLaunchKernelGGL((k_extend<MODE, FEAT, COUNT, TPB, false, false>), dim3(n_groups), dim3(TPB), lds_bytes, stream, sc, pool, count_ptr, head, cz, counters, rd);
     return hipGetLastError();
 }
 // the drain form: one lane per path of the pool (upper bound max_count; the kernel reads the real count), 256-thread groups
-template <int MODE, uint32_t FEAT, bool COUNT>
+template <int MODE, uint32_t FEAT, bool COUNT, bool LIST>
 static hipError_t launch_drain_c(const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, uint32_t max_count, const uint32_t* count_ptr, uint32_t* head, uint32_t* cz,
                                  unsigned long long* counters, hipStream_t stream) {
     const size_t lds_bytes = MODE == M_LDS ? ((size_t)lds_record_bytes(sc) + (size_t)sc.n_spheres * 16u + sc.ext_blob_bytes) : MODE == M_TOP ? (size_t)sc.n_top * 32u : 0u;
     constexpr uint32_t T = kExtendThreads;
     static thread_local bool checked = false;
-    if (!checked) { const hipError_t e = check_no_static_lds(k_extend<MODE, FEAT, COUNT, T, true>); if (e != hipSuccess) return e; checked = true; }
+    if (!checked) { const hipError_t e = check_no_static_lds(k_extend<MODE, FEAT, COUNT, T, true, LIST>); if (e != hipSuccess) return e; checked = true; }
     // max_count = upper bound of the paths in ONE queue
-    hipLaunchKernelGGL((k_extend<MODE, FEAT, COUNT, T, true>), dim3(rd.q_n * ((max_count + T - 1u) / T)), dim3(T), lds_bytes, stream, sc, pool, count_ptr, head, cz, counters, rd);
+    hipLaunchKernelGGL((k_extend<MODE, FEAT, COUNT, T, true, LIST>), dim3(rd.q_n * ((max_count + T - 1u) / T)), dim3(T), lds_bytes, stream, sc, pool, count_ptr, head, cz, counters, rd);
     return hipGetLastError();
 }
 template <int MODE, uint32_t FEAT, bool COUNT>
@@ -2149,18 +2206,18 @@ static hipError_t launch_extend_c(const LaunchCfg& cfg, const SceneDev& sc, cons
     constexpr uint32_t T0 = kExtendThreads, T1 = kNoLds ? T0 : 2u * T0, T2 = kNoLds ? T0 : 4u * T0;
     static thread_local size_t cached_lds = ~(size_t)0; static thread_local int nb[3] = {0, 0, 0}; static thread_local int pick = 0;
     if (cached_lds != lds_bytes) {
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[0], k_extend<MODE, FEAT, COUNT, T0, false>, (int)T0, lds_bytes);
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[0], k_extend<MODE, FEAT, COUNT, T0, false, false>, (int)T0, lds_bytes);
         if (e != hipSuccess) return e;
         nb[1] = nb[2] = 0;
-        e = check_no_static_lds(k_extend<MODE, FEAT, COUNT, T0, false>);
+        e = check_no_static_lds(k_extend<MODE, FEAT, COUNT, T0, false, false>);
         if (e != hipSuccess) return e;
         if (!kNoLds) {
-            e = check_no_static_lds(k_extend<MODE, FEAT, COUNT, T1, false>);
-            if (e == hipSuccess) e = check_no_static_lds(k_extend<MODE, FEAT, COUNT, T2, false>);
+            e = check_no_static_lds(k_extend<MODE, FEAT, COUNT, T1, false, false>);
+            if (e == hipSuccess) e = check_no_static_lds(k_extend<MODE, FEAT, COUNT, T2, false, false>);
             if (e != hipSuccess) return e;
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[1], k_extend<MODE, FEAT, COUNT, T1, false>, (int)T1, lds_bytes);
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[1], k_extend<MODE, FEAT, COUNT, T1, false, false>, (int)T1, lds_bytes);
             if (e != hipSuccess) return e;
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[2], k_extend<MODE, FEAT, COUNT, T2, false>, (int)T2, lds_bytes);
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[2], k_extend<MODE, FEAT, COUNT, T2, false, false>, (int)T2, lds_bytes);
             if (e != hipSuccess) return e;
         }
 #ifdef RT_EXTEND_PER_CU_MAX
@@ -2248,8 +2305,9 @@ hipError_t launch_drain(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev&
                         uint32_t* head, uint32_t* cz, unsigned long long* counters, bool count, hipStream_t stream) {
     if (max_count == 0u) return hipSuccess;
     const uint32_t v = pick_variant(cfg.features);
-#define RT_DRN(M, F) (count ? launch_drain_c<M, F, true>(sc, pool, rd, max_count, count_ptr, head, cz, counters, stream) \
-                            : launch_drain_c<M, F, false>(sc, pool, rd, max_count, count_ptr, head, cz, counters, stream))
+#define RT_DRN_L(M, F, L) (count ? launch_drain_c<M, F, true, L>(sc, pool, rd, max_count, count_ptr, head, cz, counters, stream) \
+                                 : launch_drain_c<M, F, false, L>(sc, pool, rd, max_count, count_ptr, head, cz, counters, stream))
+#define RT_DRN(M, F) (rd.n_list != 0u ? RT_DRN_L(M, F, true) : RT_DRN_L(M, F, false))
 #define RT_DRN_V(M) (v == 0u ? RT_DRN(M, 0u) : v == kVariantMesh ? RT_DRN(M, kVariantMesh) : v == kVariantBox ? RT_DRN(M, kVariantBox) : RT_DRN(M, F_ALL))
     if (cfg.scene_in_lds) return RT_DRN_V(M_LDS);
     if (sc.nodes16) return RT_DRN_V(M_C16);
@@ -2257,14 +2315,22 @@ hipError_t launch_drain(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev&
     return RT_DRN_V(M_HBM);
 #undef RT_DRN_V
 #undef RT_DRN
+#undef RT_DRN_L
 }
 
+template <uint32_t FEAT, bool LIST>
+static void launch_shade_l(uint32_t blocks, const SceneDev& sc, const PoolDev& in, const PoolDev& out, const RenderDev& rd, const uint32_t* count_in,
+                           uint32_t* count_out, uint32_t* hz, unsigned long long* counters, bool count,
+                           hipStream_t stream) {
+    if (count) hipLaunchKernelGGL((k_shade<FEAT, true, LIST>), dim3(blocks), dim3(kShadeThreads), sc.shade_blob_bytes, stream, sc, in, out, rd, count_in, count_out, hz, counters);
+    else hipLaunchKernelGGL((k_shade<FEAT, false, LIST>), dim3(blocks), dim3(kShadeThreads), sc.shade_blob_bytes, stream, sc, in, out, rd, count_in, count_out, hz, counters);
+}
 template <uint32_t FEAT>
 static void launch_shade_t(uint32_t blocks, const SceneDev& sc, const PoolDev& in, const PoolDev& out, const RenderDev& rd, const uint32_t* count_in,
                            uint32_t* count_out, uint32_t* hz, unsigned long long* counters, bool count,
                            hipStream_t stream) {
-    if (count) hipLaunchKernelGGL((k_shade<FEAT, true>), dim3(blocks), dim3(kShadeThreads), sc.shade_blob_bytes, stream, sc, in, out, rd, count_in, count_out, hz, counters);
-    else hipLaunchKernelGGL((k_shade<FEAT, false>), dim3(blocks), dim3(kShadeThreads), sc.shade_blob_bytes, stream, sc, in, out, rd, count_in, count_out, hz, counters);
+    if (rd.n_list != 0u) launch_shade_l<FEAT, true>(blocks, sc, in, out, rd, count_in, count_out, hz, counters, count, stream);
+    else launch_shade_l<FEAT, false>(blocks, sc, in, out, rd, count_in, count_out, hz, counters, count, stream);
 }
 
 hipError_t launch_shade(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& in, const PoolDev& out, const RenderDev& rd, uint32_t max_count,
@@ -2283,7 +2349,8 @@ hipError_t launch_shade(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev&
 hipError_t launch_generate(const PoolDev& pool, const RenderDev& rd, uint32_t n_init, uint32_t* out_count, hipStream_t stream) {
     const uint32_t blocks = (n_init + kShadeThreads - 1u) / kShadeThreads;
     if (blocks == 0u) return hipSuccess;
-    hipLaunchKernelGGL(k_generate, dim3(blocks), dim3(kShadeThreads), 0, stream, pool, rd, n_init, out_count);
+    if (rd.n_list != 0u) hipLaunchKernelGGL(k_generate<true>, dim3(blocks), dim3(kShadeThreads), 0, stream, pool, rd, n_init, out_count);
+    else hipLaunchKernelGGL(k_generate<false>, dim3(blocks), dim3(kShadeThreads), 0, stream, pool, rd, n_init, out_count);
     return hipGetLastError();
 }
 
@@ -2293,6 +2360,13 @@ hipError_t launch_resolve(const RenderDev& rd, float* out, uint32_t n_valid_pixe
     const uint32_t blocks = (n_valid_pixels + 255u) / 256u;
     if (blocks == 0u) return hipSuccess;
     hipLaunchKernelGGL(k_resolve, dim3(blocks), dim3(256), 0, stream, rd, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_resolve_list(const RenderDev& rd, float* out, hipStream_t stream) {
+    const uint32_t blocks = (rd.n_list + 255u) / 256u;
+    if (blocks == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_resolve_list, dim3(blocks), dim3(256), 0, stream, rd, out);
     return hipGetLastError();
 }
 

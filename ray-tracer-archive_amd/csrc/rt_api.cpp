@@ -92,14 +92,17 @@ static int check_pass(RtCtx* ctx, const RtParams* p, const RtPassOptions* o, uin
     return RT_OK;
 }
 
-static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions& pass, void* d_out, void* d_sq, RtStats* stats);
+// a pass over a pixel list (rt_render_pass_pixels_device): `list` holds n entries the device has checked (rt_api.cpp check_list)
+struct ListPass { const uint32_t* list; uint32_t n; uint32_t* counts; };
+static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions& pass, void* d_out, void* d_sq, RtStats* stats,
+                       const ListPass* lp);
 
 // A render that fails half way (a HIP error, out of memory) must not leave work or recorded events in flight on the
 // caller's stream: drain it before the error goes back.
 static int render_pass_checked(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions& pass, void* d_out, void* d_sq,
-                               RtStats* stats) {
+                               RtStats* stats, const ListPass* lp = nullptr) {
     if (ctx->fail_renders != 0u) { --ctx->fail_renders; return set_err(ctx, RT_ERR_DEVICE, "injected failure (rt_test_fail_next_renders)"); }
-    const int r = render_impl(ctx, scene, cam, prm, pass, d_out, d_sq, stats);
+    const int r = render_impl(ctx, scene, cam, prm, pass, d_out, d_sq, stats, lp);
     if (r != RT_OK) { const std::string keep = ctx->err; (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); ctx->err = keep; g_last_error = keep; }
     return r;
 }
@@ -175,6 +178,7 @@ int rt_ctx_destroy(RtCtx* ctx) {
     for (auto& pl : ctx->pool) for (auto& b : pl) b.release();
     comm_release(ctx);
     ctx->blocksum.release(); ctx->counters.release(); ctx->out_tmp.release(); ctx->sq_tmp.release(); ctx->tile_prefix.release(); ctx->shard_tmp.release();
+    ctx->list_map.release(); ctx->sel_masks.release(); ctx->sel_offsets.release(); ctx->adaptive_word.release();
     for (hipEvent_t ev : ctx->events) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->ev_gather) if (ev) (void)hipEventDestroy(ev);
     if (ctx->h_count) (void)hipHostFree(ctx->h_count);
@@ -703,7 +707,8 @@ int rt_output_floats(const RtParams* p, uint64_t* out_n) {
         if (e_ != hipSuccess) return set_err(ctx, RT_ERR_DEVICE, std::string(rtk::launch_note() ? rtk::launch_note() : #call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions& pass, void* d_out, void* d_sq, RtStats* stats) {
+static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions& pass, void* d_out, void* d_sq, RtStats* stats,
+                       const ListPass* lp) {
     using clk = std::chrono::steady_clock;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Tiling tl; make_tiling(*prm, tl);
@@ -731,7 +736,7 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     // samples per work item: the frame's grouping (frame_block_shift); the pass starts on an item boundary (check_pass)
     const uint32_t block_shift = frame_block_shift(*prm, pass.frame_samples);
     rd.block_shift = block_shift; rd.n_blocks = (prm->samples_per_pixel + (1u << block_shift) - 1) >> block_shift;
-    const uint64_t total_items = valid_pixels * rd.n_blocks;
+    const uint64_t total_items = (lp ? (uint64_t)lp->n : valid_pixels) * rd.n_blocks;
     if (total_items >= kMaxItems) return set_err(ctx, RT_ERR_INVALID, "too many work items for one shard (image too large)");
     rd.total_items = (uint32_t)total_items;
     rd.n_local_tiles = tl.n_local;
@@ -793,6 +798,11 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     HIP_TRY(ctx, hipMemcpyAsync(ctx->tile_prefix.p, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // `prefix` is a stack vector
     rd.tile_prefix = (const uint32_t*)ctx->tile_prefix.p;
+    if (lp) {   // list pass: work item w = blk * n + i renders block blk of slot list[i]; list_map[slot] = i takes a finished item back (kernels.hip item_slot)
+        HIP_TRY(ctx, ctx->list_map.ensure((size_t)tl.n_local * tl.ts * tl.ts * 4u));
+        HIP_TRY(ctx, rtk::launch_list_map(lp->list, lp->n, (uint32_t*)ctx->list_map.p, ctx->stream));
+        rd.list = lp->list; rd.n_list = lp->n; rd.list_map = (const uint32_t*)ctx->list_map.p; rd.div_list = rtk::make_fastdiv(lp->n); rd.counts = lp->counts;
+    }
     // counters, one 128-byte line each (they are hit by atomics from every workgroup):
     // line 0 unused since round 3 (it held the queues' next-work-item counters; a path now finds its next item by itself, kernels.h RenderDev::lineage),
     // line 1 queue head, lines 2,3 pool counts; 64-bit statistics from line 4
@@ -933,11 +943,12 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     const uint32_t launched = lanes[0].launched + (n_lanes > 1 ? lanes[1].launched : 0u), drained = lanes[0].drained + (n_lanes > 1 ? lanes[1].drained : 0u);
     hipEvent_t r0 = nullptr, r1 = nullptr;
     if (timing) HIP_TRY(ctx, next_event(r0));
-    if (sc > 1 && !rd.accumulate) {   // clipped pixels of edge tiles stay 0 (an accumulating pass finds them 0 from its first pass)
+    if (sc > 1 && !rd.accumulate && !lp) {   // clipped pixels of edge tiles stay 0 (an accumulating pass finds them 0 from its first pass; a list pass writes listed slots only)
         HIP_TRY(ctx, hipMemsetAsync(d_out, 0, (size_t)tl.n_local * tl.ts * tl.ts * 3 * sizeof(float), ctx->stream));
         if (d_sq) HIP_TRY(ctx, hipMemsetAsync(d_sq, 0, (size_t)tl.n_local * tl.ts * tl.ts * 3 * sizeof(float), ctx->stream));
     }
-    HIP_TRY(ctx, rtk::launch_resolve(rd, (float*)d_out, (uint32_t)valid_pixels, ctx->stream));
+    if (lp) HIP_TRY(ctx, rtk::launch_resolve_list(rd, (float*)d_out, ctx->stream));
+    else HIP_TRY(ctx, rtk::launch_resolve(rd, (float*)d_out, (uint32_t)valid_pixels, ctx->stream));
     if (timing) { HIP_TRY(ctx, next_event(r1)); spans.push_back({r0, r1, 2}); }
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, c64, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -956,7 +967,7 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
                 ++it;
             }
         }
-        stats->samples = valid_pixels * prm->samples_per_pixel;
+        stats->samples = (lp ? (uint64_t)lp->n : valid_pixels) * prm->samples_per_pixel;
         stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];
 #if defined(RT_STAMPS) || defined(RT_SHADE_STAMPS)
         const bool copy_counts = true;    // k_extend's pass statistics travel in these slots (scripts/gpu_stamps.py)
@@ -1017,6 +1028,104 @@ int rt_render_pass(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const 
     if (sq_sum_host) HIP_TRY(ctx, hipMemcpyAsync(sq_sum_host, ctx->sq_tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT_OK;
+}
+
+// ---- adaptive sampling (include/rt_hip.h): selection of the active list, passes over a pixel list, per-pixel write_color ----------------
+static int check_adaptive(RtCtx* ctx, const RtParams* p, const RtAdaptiveOptions* o, uint32_t first_sample, uint32_t frame_samples, uint32_t* samples_per_item) {
+    const int v = validate_params(ctx, p); if (v != RT_OK) return v;
+    if (!o) return set_err(ctx, RT_ERR_INVALID, "adaptive options are null");
+    if (o->struct_bytes < sizeof(RtAdaptiveOptions) || o->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtAdaptiveOptions.struct_bytes is not set (sizeof(RtAdaptiveOptions))");
+    if (!(std::isfinite(o->rel_error) && o->rel_error >= 0.0)) return set_err(ctx, RT_ERR_INVALID, "RtAdaptiveOptions.rel_error must be finite and >= 0");
+    if (!(std::isfinite(o->abs_error) && o->abs_error >= 0.0)) return set_err(ctx, RT_ERR_INVALID, "RtAdaptiveOptions.abs_error must be finite and >= 0");
+    if (frame_samples == 0u) return set_err(ctx, RT_ERR_INVALID, "frame_samples must be >= 1");
+    if (first_sample > frame_samples) return set_err(ctx, RT_ERR_INVALID, "first_sample is beyond frame_samples");
+    const uint32_t m = 1u << frame_block_shift(*p, frame_samples);
+    if ((uint64_t)o->min_samples < 2ull * m)
+        return set_err(ctx, RT_ERR_INVALID, "RtAdaptiveOptions.min_samples must be >= 2 work items (" + std::to_string(2ull * m) + " samples for this frame)");
+    if (first_sample & (m - 1u)) return set_err(ctx, RT_ERR_INVALID, "first_sample is not a multiple of the samples per work item (" + std::to_string(m) + " for this frame)");
+    if (samples_per_item) *samples_per_item = m;
+    return RT_OK;
+}
+
+int rt_adaptive_check(const RtParams* params, const RtAdaptiveOptions* options, uint32_t first_sample, uint32_t frame_samples) {
+    return check_adaptive(nullptr, params, options, first_sample, frame_samples, nullptr);
+}
+
+static uint32_t output_slots(const RtParams* p) { uint64_t n = 0; rt_output_floats(p, &n); return (uint32_t)(n / 3u); }
+
+int rt_adaptive_select(RtCtx* ctx, const RtParams* prm, const RtAdaptiveOptions* options, uint32_t first_sample, uint32_t frame_samples, const void* rgb_sum_device,
+                       const void* sq_sum_device, const void* counts_device, void* pixels_device_out, uint32_t* n_out) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    if (!rgb_sum_device || !sq_sum_device || !counts_device || !pixels_device_out || !n_out) return set_err(ctx, RT_ERR_INVALID, "a buffer or n_out is null");
+    uint32_t m = 1u;
+    const int v = check_adaptive(ctx, prm, options, first_sample, frame_samples, &m); if (v != RT_OK) return v;
+    *n_out = 0u;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Tiling tl; make_tiling(*prm, tl);
+    rtk::SelectArgs a{};
+    a.rgb = (const float*)rgb_sum_device; a.sq = (const float*)sq_sum_device; a.counts = (const uint32_t*)counts_device;
+    a.slots = output_slots(prm); a.first_sample = first_sample; a.frame_samples = frame_samples; a.m = m; a.min_samples = options->min_samples;
+    a.rel_error = options->rel_error; a.abs_error = options->abs_error;
+    a.width = prm->width; a.height = prm->height; a.shard_count = prm->shard_count <= 1u ? 1u : prm->shard_count; a.shard_index = prm->shard_count <= 1u ? 0u : prm->shard_index;
+    a.tile_size = tl.ts; a.tiles_x = tl.tiles_x;
+    const size_t n_waves = (a.slots + 63u) / 64u;
+    HIP_TRY(ctx, ctx->sel_masks.ensure(n_waves * 8u));
+    HIP_TRY(ctx, ctx->sel_offsets.ensure(n_waves * 4u));
+    HIP_TRY(ctx, ctx->adaptive_word.ensure(4u));
+    HIP_TRY(ctx, rtk::launch_select(a, (unsigned long long*)ctx->sel_masks.p, (uint32_t*)ctx->sel_offsets.p, (uint32_t*)pixels_device_out, (uint32_t*)ctx->adaptive_word.p,
+                                    ctx->stream));
+    uint32_t n = 0u;
+    HIP_TRY(ctx, hipMemcpyAsync(&n, ctx->adaptive_word.p, 4u, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *n_out = n;
+    return RT_OK;
+}
+
+// The device checks a pixel list before any kernel uses its entries as addresses: every entry an in-image slot, strictly ascending,
+// counts[entry] == first_sample. RT_ERR_INVALID with the reason otherwise; nothing has been written then.
+static int check_list(RtCtx* ctx, const RtParams* prm, const uint32_t* list, uint32_t n, const uint32_t* counts, uint32_t first_sample, uint32_t slots) {
+    Tiling tl; make_tiling(*prm, tl);
+    HIP_TRY(ctx, ctx->adaptive_word.ensure(4u));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->adaptive_word.p, 0, 4u, ctx->stream));
+    HIP_TRY(ctx, rtk::launch_list_check(list, n, counts, first_sample, prm->width, prm->height, prm->shard_count <= 1u ? 1u : prm->shard_count,
+                                        prm->shard_count <= 1u ? 0u : prm->shard_index, tl.ts, tl.tiles_x, slots, (uint32_t*)ctx->adaptive_word.p, ctx->stream));
+    uint32_t verdict = 0u;
+    HIP_TRY(ctx, hipMemcpyAsync(&verdict, ctx->adaptive_word.p, 4u, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (verdict == 0u) return RT_OK;
+    std::string why = "pixel list:";
+    if (verdict & 1u) why += " an entry is >= the number of output slots (" + std::to_string(slots) + ");";
+    if (verdict & 8u) why += " an entry is a clipped slot of an edge tile, not an image pixel;";
+    if (verdict & 2u) why += " the entries are not strictly ascending (or repeat);";
+    if (verdict & 4u) why += " counts[entry] != first_sample for an entry (the pixel did not take every pass so far);";
+    why.pop_back();
+    return set_err(ctx, RT_ERR_INVALID, why);
+}
+
+int rt_render_pass_pixels_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions* options, const void* pixels_device,
+                                 uint32_t n_pixels, void* rgb_sum_device, void* sq_sum_device, void* counts_device, RtStats* stats) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    if (!scene || !cam || !rgb_sum_device || !counts_device) return set_err(ctx, RT_ERR_INVALID, "scene / cam / output / counts is null");
+    const int v = check_pass(ctx, prm, options, nullptr); if (v != RT_OK) return v;
+    const uint32_t slots = output_slots(prm);
+    if (n_pixels > slots) return set_err(ctx, RT_ERR_INVALID, "n_pixels is larger than the number of output slots (" + std::to_string(slots) + ")");
+    if (n_pixels == 0u) { if (stats) std::memset(stats, 0, sizeof(*stats)); return RT_OK; }
+    if (!pixels_device) return set_err(ctx, RT_ERR_INVALID, "pixel list is null");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int c = check_list(ctx, prm, (const uint32_t*)pixels_device, n_pixels, (const uint32_t*)counts_device, options->first_sample, slots);
+    if (c != RT_OK) return c;
+    const ListPass lp{(const uint32_t*)pixels_device, n_pixels, (uint32_t*)counts_device};
+    return render_pass_checked(ctx, scene, cam, prm, *options, rgb_sum_device, sq_sum_device, stats, &lp);
+}
+
+int rt_resolve_counts_device(RtCtx* ctx, const void* rgb_sum_device, const void* counts_device, uint32_t width, uint32_t height, void* rgb8_device) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    if (!rgb_sum_device || !counts_device || !rgb8_device) return set_err(ctx, RT_ERR_INVALID, "bad argument");
+    if (width == 0 || height == 0 || (uint64_t)width * height * 3u > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "bad image size");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, rtk::launch_write_color_counts((const float*)rgb_sum_device, (const uint32_t*)counts_device, width * height, (uint8_t*)rgb8_device, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 

@@ -46,6 +46,8 @@ struct RtCtx {
     rti::DevBuf comm_words;                      // status words of the agreement that precedes every exchange (rt_multi.cpp agree_on_status)
     uint32_t* h_words = nullptr;                 // pinned: the same words on the host
     hipEvent_t ev_gather[2] = {nullptr, nullptr}; // brackets the exchange (RtStats.gather_ms); made at the first gather, kept
+    rti::DevBuf list_map;                        // adaptive sampling: output slot -> list index of a list pass (rt_render_pass_pixels_device)
+    rti::DevBuf sel_masks, sel_offsets, adaptive_word;   // rt_adaptive_select's wave ballots and their scan; the list check's verdict / the list's length
     uint32_t fail_renders = 0;                   // rt_test_fail_next_renders: renders still to fail (fault injection for the failure-path tests)
 };
 
