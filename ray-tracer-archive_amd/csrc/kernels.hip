@@ -2234,7 +2234,7 @@ static hipError_t launch_extend_c(const LaunchCfg& cfg, const SceneDev& sc, cons
     // the resident set, or fewer workgroups when the queue is short (the host's upper bound of it): a wave needs 64 rays to be worth
     // starting, and every workgroup started stages the scene and reads the queue size — the floor of the launches of a render's tail
     const uint32_t tpb = pick == 0 ? T0 : pick == 1 ? T1 : T2;
-    const uint32_t per_cu = std::max<uint32_t>(1u, (uint32_t)nb[pick] / std::max<uint32_t>(1u, cfg.extend_share));
+    const uint32_t per_cu = std::max<uint32_t>(1u, (uint32_t)nb[pick]);
     uint32_t groups = std::min<uint32_t>(cfg.n_cu * per_cu, std::max<uint32_t>(1u, (cfg.max_rays + tpb - 1u) / tpb));
     const uint32_t gq = std::max<uint32_t>(1u, rd.q_n * 64u / tpb);     // workgroups that make up q_n waves: every queue gets the same number of waves
     groups = (groups + gq - 1u) / gq * gq;

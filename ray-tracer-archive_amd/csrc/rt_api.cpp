@@ -142,7 +142,7 @@ static int ctx_init(RtCtx* ctx, void* stream) {
     if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) ctx->n_cu = prop.multiProcessorCount;
     if (stream) { ctx->stream = (hipStream_t)stream; ctx->own_stream = false; }
     else { HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)); ctx->own_stream = true; }
-    HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_count, 8 * rtk::kQueues * sizeof(uint32_t), hipHostMallocDefault));   // ring of 8 x (one pool size per queue)
+    HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_count, 4 * rtk::kQueues * sizeof(uint32_t), hipHostMallocDefault));   // ring of 4 (render_impl kRing) x (one pool size per queue)
     HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_counters, sizeof(unsigned long long) * 16, hipHostMallocDefault));
     HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_words, 128 * sizeof(uint32_t), hipHostMallocDefault));
     return RT_OK;
@@ -185,7 +185,6 @@ int rt_ctx_destroy(RtCtx* ctx) {
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->h_words) (void)hipHostFree(ctx->h_words);
     ctx->comm_words.release();
-    if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return RT_OK;
@@ -209,7 +208,6 @@ struct DevNodes {
     std::vector<unsigned char> main, top;   // main: records + DONE + IDLE + twins; top: the LDS copies (M_TOP)
     uint32_t n = 0, n_top = 0, n_twins = 0;
     uint32_t walk_start = 0;                // address of the record a walk begins at: the root, or the park twin of the leaf tested first
-    uint32_t unit = 32u, b_off = 16u;       // address step from a record to the next, and from a record's first half to its second (kernels.h SceneDev::rec_unit)
     uint32_t records() const { return n + 2u + n_twins; }
 };
 static void node_boxes(const std::vector<rtd::Node>& nodes, std::vector<rtd::NodeDev>& out) {
@@ -235,17 +233,13 @@ static void node_boxes(const std::vector<rtd::Node>& nodes, std::vector<rtd::Nod
         out[i] = rtd::NodeDev{c[0], c[1], h[0], h[1], c[2], h[2], 0u, 0u};
     }
 }
-// `layout` (LDS-resident scenes only, max_top = 0; scripts/ only, RT_LDS_RECORDS): 0 = 32-byte records one after the other; 1 = the first
-// halves of all records, then the second halves (a record's address counts in 16-byte steps); 2 = 32-byte records 48 bytes apart. In 0 every
-// first half sits on an even 16-byte column of the LDS's 64 banks and every second half on an odd one: the sixteen lanes of a ds_read_b128
-// group meet in 8 columns, not 16. Measured: the bank-conflict cycles drop, the kernel does not move.
+// Records are 32 bytes, one after the other (kernels.h SceneDev::rec_unit = 32, rec_b = 16).
 // `first_leaf`: leaf word of primitives every walk tests before it enters the tree (0: none) — a park twin of its own that resumes at the root.
-static bool device_nodes(const std::vector<rtd::Node>& nodes, uint32_t max_top, DevNodes& out, int layout = 0, uint32_t first_leaf = 0u) {
+static bool device_nodes(const std::vector<rtd::Node>& nodes, uint32_t max_top, DevNodes& out, uint32_t first_leaf = 0u) {
     const size_t n = nodes.size();
     out = DevNodes();
     out.n = (uint32_t)n;
-    if (max_top != 0u) layout = 0;
-    const uint32_t unit = layout == 1 ? 16u : layout == 2 ? 48u : 32u;
+    constexpr uint32_t unit = 32u;
     // ---- the top (optional) ----
     std::vector<uint32_t> slot(n, 0xFFFFFFFFu);
     if (max_top != 0u && n != 0) {
@@ -263,7 +257,7 @@ static bool device_nodes(const std::vector<rtd::Node>& nodes, uint32_t max_top, 
     }
     for (const rtd::Node& nd : nodes) if (nd.leaf != 0u) out.n_twins++;
     if (first_leaf != 0u) out.n_twins++;
-    const uint64_t top_bytes = (uint64_t)out.n_top * 32u, total_bytes = top_bytes + (uint64_t)out.records() * std::max(unit, 32u);
+    const uint64_t top_bytes = (uint64_t)out.n_top * 32u, total_bytes = top_bytes + (uint64_t)out.records() * unit;
     if (total_bytes >= 0xFFFFFFF0ull) return false;                      // 32-bit byte addresses
     const uint32_t special = (uint32_t)top_bytes + (uint32_t)n * unit, done = special, idle = special + unit, twin0 = special + 2u * unit;
     auto U = [&](size_t i) -> uint32_t { return i >= n ? done : (slot[i] != 0xFFFFFFFFu ? slot[i] * 32u : (uint32_t)top_bytes + (uint32_t)i * unit); };
@@ -297,14 +291,8 @@ static bool device_nodes(const std::vector<rtd::Node>& nodes, uint32_t max_top, 
     put((uint32_t)n * unit, self_loop(done, done, rtd::LEAF_DONE));
     put((uint32_t)n * unit + unit, self_loop(idle, idle, rtd::LEAF_IDLE));
     // the bytes as they lie in memory (and, staged by a linear copy, in LDS)
-    const size_t nr = recs.size();
-    out.unit = unit; out.b_off = layout == 1 ? (uint32_t)nr * 16u : 16u;
-    out.main.assign(nr * std::max(unit, 32u), 0);
-    for (size_t r = 0; r < nr; ++r) {
-        const unsigned char* src = reinterpret_cast<const unsigned char*>(&recs[r]);
-        std::memcpy(out.main.data() + r * unit, src, 16);
-        std::memcpy(out.main.data() + r * unit + out.b_off, src + 16, 16);
-    }
+    const unsigned char* bytes = reinterpret_cast<const unsigned char*>(recs.data());
+    out.main.assign(bytes, bytes + recs.size() * sizeof(rtd::NodeDev));
     return true;
 }
 // Compressed layout (device_types.h Node16) for scenes that do not fit LDS. The grid spans the union of the finite boxes; a corner
@@ -410,12 +398,10 @@ static size_t lds_scene_bytes(const rtc::CompiledScene& cs) {
     return (cs.nodes.size() + 2 + twins) * 32 + cs.spheres.size() * 16;
 }
 
-// ---- layout options: RtUploadOptions of the ABI, resolved once per upload ---------------------------------------------------------------
-// Environment variables are OVERRIDES for the experiment scripts under scripts/ only (they predate the ABI fields and keep the A/B
-// scripts one-liners); no test and no host path sets them. A process that never sets them gets exactly what its RtUploadOptions say.
+// ---- layout options: RtUploadOptions of the ABI, resolved once per upload (the library reads no environment variable for them) -----------
 struct rti::UploadOpts {
     rtc::CompileOptions compile;
-    bool lds_scene = true, node16 = true, octant_order = true, shade_lds = true, perlin_lds = true, extend_lds_tables = true, wide_nodes = false;
+    bool lds_scene = true, node16 = true, octant_order = true, shade_lds = true, extend_lds_tables = true, wide_nodes = false;
     uint32_t max_top = 1024u, octant_axes = 0u /* 0 = pick; else 8 | mask */;
 };
 // RtUploadOptions as the ABI promises them: unknown or contradictory switches are refused, not dropped
@@ -445,7 +431,7 @@ static rti::UploadOpts resolve_options(const RtUploadOptions* o) {
         u.octant_order = !(f & RT_LAYOUT_CHILD_ORDER_AS_REFERENCE);
         u.lds_scene = !(f & RT_LAYOUT_SCENE_IN_HBM);
         u.node16 = !(f & RT_LAYOUT_NODES_32B);
-        u.shade_lds = u.perlin_lds = !(f & RT_LAYOUT_NO_SHADE_TABLES_IN_LDS);
+        u.shade_lds = !(f & RT_LAYOUT_NO_SHADE_TABLES_IN_LDS);
         u.extend_lds_tables = !(f & RT_LAYOUT_NO_EXTEND_TABLES_IN_LDS);
         u.wide_nodes = (f & RT_LAYOUT_WIDE_NODES) != 0u;
         if (u.wide_nodes) u.compile.big_spheres_first = false;      // the 8-wide walk tests nothing before the tree
@@ -454,21 +440,6 @@ static rti::UploadOpts resolve_options(const RtUploadOptions* o) {
         if (o->struct_bytes >= 20u) u.compile.leaf_collapse = o->leaf_collapse;
         if (o->struct_bytes >= 24u && o->list_park_cost > 0.f) u.compile.park_cost = o->list_park_cost;
     }
-    auto env = [](const char* n) -> const char* { const char* e = getenv(n); return e && e[0] ? e : nullptr; };
-    if (const char* e = env("RT_LIST_CULL")) u.compile.cull_lists = e[0] == '2' ? 1 : (e[0] == '0' ? 0 : u.compile.cull_lists);
-    if (const char* e = env("RT_BIG_SPHERES_FIRST")) u.compile.big_spheres_first = e[0] != '0';
-    if (const char* e = env("RT_PAIR_BOXES")) u.compile.member_boxes = e[0] == '2' ? 1 : (e[0] == '0' ? 0 : u.compile.member_boxes);
-    if (const char* e = env("RT_LIST_PARK_COST")) u.compile.park_cost = std::max(0.0, std::atof(e));
-    if (const char* e = env("RT_LEAF_COLLAPSE")) u.compile.leaf_collapse = (uint32_t)std::strtoul(e, nullptr, 10);
-    if (const char* e = env("RT_LDS_SCENE")) u.lds_scene = u.lds_scene && e[0] != '0';
-    if (const char* e = env("RT_TOP_NODES")) u.max_top = (uint32_t)std::strtoul(e, nullptr, 10);
-    if (const char* e = env("RT_NODE16")) u.node16 = u.node16 && e[0] != '0';
-    if (const char* e = env("RT_OCTANT_ORDER")) u.octant_order = u.octant_order && e[0] != '0';
-    if (const char* e = env("RT_OCTANT_AXES")) u.octant_axes = 8u | ((uint32_t)std::strtoul(e, nullptr, 10) & 7u);
-    if (const char* e = env("RT_SHADE_LDS")) u.shade_lds = u.shade_lds && e[0] != '0';
-    if (const char* e = env("RT_SHADE_PERLIN_LDS")) u.perlin_lds = e[0] != '0';
-    if (const char* e = env("RT_EXTEND_LDS_TABLES")) u.extend_lds_tables = u.extend_lds_tables && e[0] != '0';
-    if (const char* e = env("RT_WIDE_NODES")) { u.wide_nodes = e[0] != '0'; if (u.wide_nodes) u.compile.big_spheres_first = false; }
     u.max_top = std::min<uint32_t>(u.max_top, (128u * 1024u) / 32u);
     return u;
 }
@@ -484,7 +455,6 @@ struct rti::SceneImage {
     std::vector<unsigned char> blob, eblob;
     uint32_t sb[12] = {0}, perlin_only = 0u, eb[5] = {0}, eb_rect_stride = 32u;
     uint32_t features = 0u;
-    bool sort_rays = true;
     rtw::WideTree wide; bool use_wide = false;     // 8-wide nodes for k_extend_wide (a static BVH that does not fit LDS)
 };
 void rti::scene_image_free(SceneImage* im) { delete im; }
@@ -499,7 +469,6 @@ int rti::scene_image_build(const RtSceneDesc* desc, const RtUploadOptions* optio
     if (rc != RT_OK) { err = "scene: " + cs.error; return rc; }
     im->in_lds = opt.lds_scene && lds_scene_bytes(cs) <= kLdsSceneBudget;
     im->features = scene_features(cs);
-    if (const char* e = getenv("RT_SORT_RAYS")) im->sort_rays = e[0] != '0';     // scripts/ only
     // RT_LAYOUT_WIDE_NODES: a static BVH in HBM (spheres / rects / triangles / boxes under box nodes only) walked 8 lanes to a ray over an
     // 8-wide tree (kernels.hip k_extend_wide) instead of the binary records below.
     if (!im->in_lds && opt.wide_nodes && opt.node16 && (im->features & ~(rtk::F_RECT | rtk::F_TRI)) == 0u && cs.prologue.empty() && cs.first_leaf == 0u && rtw::eligible(cs.nodes)) {   // (k_extend_wide tests nothing before the tree)
@@ -529,10 +498,7 @@ int rti::scene_image_build(const RtSceneDesc* desc, const RtUploadOptions* optio
             if (octants) { im->n16.swap(all); im->oct_stride = stride; im->oct_mask = mask; }
         }
     }
-    int lds_layout = 0;
-    if (const char* e = getenv("RT_LDS_RECORDS")) lds_layout = e[0] == '1' ? 1 : e[0] == '2' ? 2 : 0;     // scripts/ only: 1 = halves apart, 2 = 48 bytes apart
-    if (lds_layout == 2 && lds_scene_bytes(cs) + (lds_scene_bytes(cs) - cs.spheres.size() * 16) / 2 > 78 * 1024) lds_layout = 1;   // (two workgroups per CU or not at all)
-    if (!im->c16 && !device_nodes(cs.nodes, im->in_lds ? 0u : opt.max_top, im->dn, im->in_lds ? lds_layout : 0, cs.first_leaf)) { err = "scene: node array beyond 4 GB"; return RT_ERR_UNSUPPORTED; }
+    if (!im->c16 && !device_nodes(cs.nodes, im->in_lds ? 0u : opt.max_top, im->dn, cs.first_leaf)) { err = "scene: node array beyond 4 GB"; return RT_ERR_UNSUPPORTED; }
     im->top = !im->c16 && im->dn.n_top != 0u;
     // k_shade's small tables as one blob for LDS staging (kernels.h SceneDev::shade_blob): only when it is small
     {
@@ -548,7 +514,7 @@ int rti::scene_image_build(const RtSceneDesc* desc, const RtUploadOptions* optio
         if (!(opt.shade_lds && blob.size() <= 8 * 1024)) blob.clear();
         // a scene with noise textures whose other tables are too big to stage: the Perlin tables alone (7 KB each). A turbulence is a chain of
         // 7 x 8 x 4 dependent look-ups, and a wave waits for the one lane that makes it
-        if (blob.empty() && opt.perlin_lds && !cs.perlins.empty() && cs.perlins.size() * sizeof(rtd::PerlinTable) <= 16 * 1024) {
+        if (blob.empty() && opt.shade_lds && !cs.perlins.empty() && cs.perlins.size() * sizeof(rtd::PerlinTable) <= 16 * 1024) {
             put(cs.perlins.data(), cs.perlins.size() * sizeof(rtd::PerlinTable)); im->perlin_only = 1u;
             // ... and the tables that do not grow with the primitive count, if they are small: material, texture, transform, wrapper, light
             const size_t small = cs.mat_a.size() * 20 + cs.xforms.size() * sizeof(rtd::Xform) + cs.wraps.size() * sizeof(rtd::Wrap) + cs.lights.size() * sizeof(rtd::Light) +
@@ -607,7 +573,7 @@ int rti::scene_image_upload(RtCtx* ctx, const SceneImage& im, RtScene** out_scen
     // a small scene whose shading tables are not staged in LDS: the material record of every sphere by SPHERE index (one dependent load fewer in
     // k_shade: book-1 waits ~700 cycles of a wave's ~20 000 for the material's record after the sphere's)
     std::vector<rtd::Float4> sphere_ma; std::vector<uint32_t> sphere_mb;
-    if (im.blob.empty() && !cs.spheres.empty() && cs.spheres.size() <= 65536 && !(getenv("RT_SPHERE_MATS") && getenv("RT_SPHERE_MATS")[0] == '0')) {
+    if (im.blob.empty() && !cs.spheres.empty() && cs.spheres.size() <= 65536) {
         sphere_ma.resize(cs.spheres.size()); sphere_mb.resize(cs.spheres.size());
         for (size_t k = 0; k < cs.spheres.size(); ++k) { const uint32_t m = cs.sphere_meta[k] & rtd::META_MAT_MASK; sphere_ma[k] = cs.mat_a[m]; sphere_mb[k] = cs.mat_b[m]; }
         up(s->sphere_mat_a, sphere_ma); up(s->sphere_mat_b, sphere_mb);
@@ -621,10 +587,10 @@ int rti::scene_image_upload(RtCtx* ctx, const SceneImage& im, RtScene** out_scen
     const uint32_t* sb = im.sb; const uint32_t* eb = im.eb;
     d.nodes = (const rtd::Float4*)s->nodes.p; d.n_nodes = (uint32_t)cs.nodes.size();
     d.top_nodes = im.top ? (const rtd::Float4*)s->top_nodes.p : nullptr; d.n_top = im.top ? im.dn.n_top : 0u; d.n_records = im.c16 ? (uint32_t)im.n16.size() : im.dn.records();
-    d.rec_unit = im.c16 ? 16u : im.dn.unit; d.rec_b = im.c16 ? 0u : im.dn.b_off;
+    d.rec_unit = im.c16 ? 16u : 32u; d.rec_b = im.c16 ? 0u : 16u;
     d.walk_start = im.c16 ? 0u : im.dn.walk_start; d.first_leaf = cs.first_leaf;
     d.oct_stride = im.oct_stride; d.oct_mask = im.oct_mask;
-    d.sort_rays = (im.c16 && im.sort_rays) ? 1u : 0u;
+    d.sort_rays = im.c16 ? 1u : 0u;
     d.wide = im.use_wide ? (const uint4*)s->wide.p : nullptr; d.n_wide = im.use_wide ? im.wide.n_nodes : 0u;
     d.nodes16 = im.c16 ? 1u : 0u; for (int a = 0; a < 3; ++a) { d.grid_lo[a] = im.grid_lo[a]; d.grid_scale[a] = im.grid_scale[a]; }
     d.n_prologue = (uint32_t)cs.prologue.size();
@@ -750,10 +716,10 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
         rd.tile_slack = fits ? (uint32_t)std::min<uint64_t>(tl.n_local, clipped / ts2 + 1) : tl.n_local;
         // one device, every tile: item -> tile by arithmetic (kernels.h RenderDev::row_items)
         const uint64_t row_items = (uint64_t)tl.ts * prm->width * rd.n_blocks;
-        const bool by_rows = sc == 1u && fits && row_items <= 0xFFFFFFFFull && !(getenv("RT_TILE_SEARCH") && getenv("RT_TILE_SEARCH")[0] == '1');   // (scripts/ only: the search, for A/B)
+        const bool by_rows = sc == 1u && fits && row_items <= 0xFFFFFFFFull;
         rd.row_items = by_rows ? (uint32_t)row_items : 0u;
         // any shard whose tiles all lie inside the image: the table is a multiplication (the 4096^2 strong-scaling frame at every shard count)
-        rd.tiles_all_full = fits && clipped == 0 && !(getenv("RT_TILE_SEARCH") && getenv("RT_TILE_SEARCH")[0] == '1') ? 1u : 0u;
+        rd.tiles_all_full = fits && clipped == 0 ? 1u : 0u;
         rd.div_row_items = rtk::make_fastdiv(by_rows ? (uint32_t)row_items : 1u);
     }
 
@@ -792,8 +758,10 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     }
     HIP_TRY(ctx, ctx->blocksum.ensure((size_t)total_items * 16));
     rd.blocksum = (rtd::Float4*)ctx->blocksum.p;
-    // diagnostic: RT_DEBUG_POISON=1 fills the per-item sums with NaN first, so an item no kernel ever finished shows up in the frame
-    if (const char* e = getenv("RT_DEBUG_POISON")) if (e[0] == '1') HIP_TRY(ctx, hipMemsetAsync(ctx->blocksum.p, 0xFF, (size_t)total_items * 16, ctx->stream));
+#ifdef RT_DEBUG_POISON
+    // diagnostic build (scripts/sweep.py "poison"): the per-item sums filled with NaN first, so an item no kernel ever finished shows up in the frame
+    HIP_TRY(ctx, hipMemsetAsync(ctx->blocksum.p, 0xFF, (size_t)total_items * 16, ctx->stream));
+#endif
     HIP_TRY(ctx, ctx->tile_prefix.ensure(prefix.size() * 4));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->tile_prefix.p, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // `prefix` is a stack vector
@@ -822,12 +790,11 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     cfg.n_cu = (uint32_t)ctx->n_cu; cfg.extend_geometry = extend_geometry; cfg.features = scene->features; cfg.scene_in_lds = scene->in_lds;
 
     size_t ev_used = 0;
-    auto next_event_on = [&](hipEvent_t& ev, hipStream_t st) -> hipError_t {
+    auto next_event = [&](hipEvent_t& ev) -> hipError_t {
         if (ev_used == ctx->events.size()) { hipEvent_t e; hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; ctx->events.push_back(e); }
         ev = ctx->events[ev_used++];
-        return hipEventRecord(ev, st);
+        return hipEventRecord(ev, ctx->stream);
     };
-    auto next_event = [&](hipEvent_t& ev) -> hipError_t { return next_event_on(ev, ctx->stream); };
     struct Span { hipEvent_t a, b; int kind; };
     std::vector<Span> spans;
 
@@ -837,7 +804,7 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     rd.n_init = n_init; rd.lineage = P;
     rd.q_lo = 0u; rd.q_n = rtk::kQueues; rd.q_shift = rtk::kQShift;
     // the ground sphere tested where a ray is made (kernels.h RenderDev::first_in_shade): a scene without motion, one such sphere, no counting
-    rd.first_in_shade = scene->first_id != 0u && rtk::can_test_first_in_shade(scene->features) && !counting && !(getenv("RT_FIRST_IN_SHADE") && getenv("RT_FIRST_IN_SHADE")[0] == '0') ? 1u : 0u;
+    rd.first_in_shade = scene->first_id != 0u && rtk::can_test_first_in_shade(scene->features) && !counting ? 1u : 0u;
     rd.first_id = scene->first_id; for (int k = 0; k < 8; ++k) rd.first_prim[k] = scene->first_prim[k];
     HIP_TRY(ctx, rtk::launch_generate(pd[0], rd, n_init, c_count[0], ctx->stream));
     if (timing) { HIP_TRY(ctx, next_event(e1)); spans.push_back({e0, e1, 2}); }
@@ -855,92 +822,53 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     // record order a k_extend launch of that scene did not get shorter than 1.5-2 ms however few rays it carried — the longest far-first walk
     // of the launch — and 2^21 was the best hand-over: 185.9 ms against 211.5 at 2^18.)
     uint32_t drain_at = prm->tail_paths ? prm->tail_paths : (1u << 18);          // RtParams.tail_paths (1 = never: a pool holds 8 queues of >= 1 path)
-    if (const char* e = getenv("RT_DRAIN_AT")) drain_at = (uint32_t)std::strtoul(e, nullptr, 10);   // scripts/ only
     // the 8-wide walk resolves hits that tie within rounding in its own way; handing a tail to the per-path kernel (binary records) would
     // make such pixels depend on WHEN the hand-over happens, so a wide scene's wavefront loop runs to its end
     if (scene->dev.wide != nullptr) drain_at = 0u;
     if (prm->flags & RT_FLAG_FUSED) drain_at = 0xFFFFFFFFu;
 
-    // ---- lanes: the pool's 8 queues as ONE wavefront loop, or as TWO halves of 4 queues on two streams ------------------------------------
-    // k_extend (an LDS-resident scene) is bound by the LDS array and VALU issue and touches HBM for 40 bytes a segment; k_shade waits on
-    // memory latency for 58 % of its wave time and leaves the LDS idle. Run one after the other each has the chip to itself and leaves
-    // the other's unit unused. With two halves in flight, half A's k_shade runs WHILE half B's k_extend does: k_extend is launched with
-    // half of a CU's resident slots (cfg.extend_share = 2) and the shading workgroups of the other half fill the rest. The extends of the
-    // two lanes are chained by events (A1, B1, A2, B2, ...) so that at any time one extend and one shade are in flight; a lane's shade
-    // follows its extend in stream order. The picture does not depend on any of this (per-item sums; RNG keyed by pixel and sample).
-    struct Pending { hipEvent_t ev; uint32_t ring; };
-    struct Lane {
-        hipStream_t st; uint32_t q_lo, q_n, q_shift;
-        uint32_t live; int cur; uint32_t launched, drained; bool done;
-        std::vector<Pending> pending; size_t head;
-    };
-    bool overlap = false;
-    if (const char* e = getenv("RT_OVERLAP")) overlap = e[0] == '1';
-    if (prm->flags & RT_FLAG_FUSED) overlap = false;
-    if (overlap && !ctx->stream2) { if (hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess) overlap = false; }
-    const uint32_t n_lanes = overlap ? 2u : 1u, per_lane = rtk::kQueues / n_lanes;
-    Lane lanes[2];
+    // ---- the wavefront loop over the pool's kQueues queues ----------------------------------------------------------------------------------
     // upper bound of the size of the LARGEST queue from here on (a queue never grows): it sizes the grids, and 0 ends the render
-    const uint32_t live0 = std::min<uint32_t>(rd.queue_cap, (n_init + rtk::kQueues - 1u) / rtk::kQueues + 512u);
-    for (uint32_t l = 0; l < n_lanes; ++l) lanes[l] = Lane{l == 0 ? ctx->stream : ctx->stream2, l * per_lane, per_lane, rtk::kQShift - (overlap ? 1u : 0u), live0, 0, 0u, 0u, false, {}, 0};
-    if (overlap) {   // the second stream starts behind k_generate
-        hipEvent_t eg = nullptr; HIP_TRY(ctx, next_event(eg));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, eg, 0));
-    }
-    cfg.extend_share = overlap ? 2u : 1u;
-    std::vector<uint32_t> iter_live;     // RT_DEBUG_ITER=1 (with RT_FLAG_TIMING): the host's bound of the largest queue at every iteration
-    hipEvent_t last_extend = nullptr;    // overlap: end of the most recent k_extend of either lane
-    auto take = [&](Lane& L, const Pending& pd_) {
-        uint32_t m = 0; for (uint32_t k = 0; k < L.q_n; ++k) m = std::max(m, ctx->h_count[pd_.ring * rtk::kQueues + L.q_lo + k]);
-        L.live = std::min(L.live, m);
-    };
-    // one step of a lane: nothing (done), the drain launch, or one wavefront iteration. Returns a HIP/RT status through `rc`.
-    auto step = [&](Lane& L, uint32_t lane_index) -> int {
-        while (L.head < L.pending.size() && hipEventQuery(L.pending[L.head].ev) == hipSuccess) take(L, L.pending[L.head++]);
-        if (L.live != 0u && L.pending.size() - L.head >= kAhead) {
-            HIP_TRY(ctx, hipEventSynchronize(L.pending[L.head].ev));
-            take(L, L.pending[L.head++]);
-        }
-        if (L.live == 0u) { L.done = true; return RT_OK; }
-        rtk::RenderDev r = rd; r.q_lo = L.q_lo; r.q_n = L.q_n; r.q_shift = L.q_shift;
-        if ((uint64_t)L.live * rtk::kQueues <= drain_at) {
-            hipEvent_t ea = nullptr, eb = nullptr;
-            if (timing) HIP_TRY(ctx, next_event_on(ea, L.st));
-            LAUNCH_TRY(rtk::launch_drain(cfg, scene->dev, pd[L.cur], r, L.live, c_count[L.cur], c_head, c_count[1 - L.cur], c64, counting, L.st));
-            if (timing) { HIP_TRY(ctx, next_event_on(eb, L.st)); spans.push_back({ea, eb, 3}); }
-            L.drained = L.live * L.q_n;
-            L.done = true;
-            return RT_OK;
-        }
-        hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr;
-        if (overlap && last_extend) HIP_TRY(ctx, hipStreamWaitEvent(L.st, last_extend, 0));     // extends alternate between the lanes
-        if (timing) HIP_TRY(ctx, next_event_on(ea, L.st));
-        cfg.max_rays = (uint32_t)std::min<uint64_t>((uint64_t)L.live * L.q_n, 0xFFFFFFFFull);
-        LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd[L.cur], r, c_count[L.cur], c_head, c_count[1 - L.cur], c64, counting, L.st));
-        if (timing || overlap) HIP_TRY(ctx, next_event_on(eb, L.st));
-        if (overlap) last_extend = eb;
-        HIP_TRY(ctx, rtk::launch_shade(cfg, scene->dev, pd[L.cur], pd[1 - L.cur], r, L.live, c_count[L.cur], c_count[1 - L.cur], c_head, c64, counting, L.st));
-        if (timing) { HIP_TRY(ctx, next_event_on(ec, L.st)); spans.push_back({ea, eb, 0}); spans.push_back({eb, ec, 1}); if (lane_index == 0u) iter_live.push_back(L.live); }
-        L.cur = 1 - L.cur;
-        const uint32_t ring = (L.launched % kRing) + lane_index * kRing;
-        HIP_TRY(ctx, hipMemcpy2DAsync(ctx->h_count + ring * rtk::kQueues, sizeof(uint32_t), c_count[L.cur], kLine, sizeof(uint32_t), rtk::kQueues, hipMemcpyDeviceToHost,
-                                      L.st));   // the kQueues pool sizes, one per line (a lane reads its own queues' entries)
-        hipEvent_t ev = nullptr;
-        HIP_TRY(ctx, next_event_on(ev, L.st));
-        L.pending.push_back({ev, ring});
-        if (++L.launched > 100000000u) return set_err(ctx, RT_ERR_DEVICE, "render loop did not terminate");
-        return RT_OK;
+    uint32_t live = std::min<uint32_t>(rd.queue_cap, (n_init + rtk::kQueues - 1u) / rtk::kQueues + 512u);
+    uint32_t launched = 0u, drained = 0u;
+    int cur = 0;
+    struct Pending { hipEvent_t ev; uint32_t ring; };
+    std::vector<Pending> pending; size_t head = 0;
+    auto take = [&](const Pending& pd_) {
+        uint32_t m = 0; for (uint32_t k = 0; k < rtk::kQueues; ++k) m = std::max(m, ctx->h_count[pd_.ring * rtk::kQueues + k]);
+        live = std::min(live, m);
     };
     for (;;) {
-        bool any = false;
-        for (uint32_t l = 0; l < n_lanes; ++l) if (!lanes[l].done) { const int rc = step(lanes[l], l); if (rc != RT_OK) return rc; any = any || !lanes[l].done; }
-        if (!any) break;
+        while (head < pending.size() && hipEventQuery(pending[head].ev) == hipSuccess) take(pending[head++]);
+        if (live != 0u && pending.size() - head >= kAhead) {
+            HIP_TRY(ctx, hipEventSynchronize(pending[head].ev));
+            take(pending[head++]);
+        }
+        if (live == 0u) break;
+        if ((uint64_t)live * rtk::kQueues <= drain_at) {
+            hipEvent_t ea = nullptr, eb = nullptr;
+            if (timing) HIP_TRY(ctx, next_event(ea));
+            LAUNCH_TRY(rtk::launch_drain(cfg, scene->dev, pd[cur], rd, live, c_count[cur], c_head, c_count[1 - cur], c64, counting, ctx->stream));
+            if (timing) { HIP_TRY(ctx, next_event(eb)); spans.push_back({ea, eb, 3}); }
+            drained = live * rtk::kQueues;
+            break;
+        }
+        hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr;
+        if (timing) HIP_TRY(ctx, next_event(ea));
+        cfg.max_rays = (uint32_t)std::min<uint64_t>((uint64_t)live * rtk::kQueues, 0xFFFFFFFFull);
+        LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd[cur], rd, c_count[cur], c_head, c_count[1 - cur], c64, counting, ctx->stream));
+        if (timing) HIP_TRY(ctx, next_event(eb));
+        HIP_TRY(ctx, rtk::launch_shade(cfg, scene->dev, pd[cur], pd[1 - cur], rd, live, c_count[cur], c_count[1 - cur], c_head, c64, counting, ctx->stream));
+        if (timing) { HIP_TRY(ctx, next_event(ec)); spans.push_back({ea, eb, 0}); spans.push_back({eb, ec, 1}); }
+        cur = 1 - cur;
+        const uint32_t ring = launched % kRing;
+        HIP_TRY(ctx, hipMemcpy2DAsync(ctx->h_count + ring * rtk::kQueues, sizeof(uint32_t), c_count[cur], kLine, sizeof(uint32_t), rtk::kQueues, hipMemcpyDeviceToHost,
+                                      ctx->stream));   // the kQueues pool sizes, one per line
+        hipEvent_t ev = nullptr;
+        HIP_TRY(ctx, next_event(ev));
+        pending.push_back({ev, ring});
+        if (++launched > 100000000u) return set_err(ctx, RT_ERR_DEVICE, "render loop did not terminate");
     }
-    if (overlap) {   // the resolve (first stream) waits for the second lane
-        hipEvent_t ej = nullptr; HIP_TRY(ctx, next_event_on(ej, ctx->stream2));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ej, 0));
-    }
-    const uint32_t launched = lanes[0].launched + (n_lanes > 1 ? lanes[1].launched : 0u), drained = lanes[0].drained + (n_lanes > 1 ? lanes[1].drained : 0u);
     hipEvent_t r0 = nullptr, r1 = nullptr;
     if (timing) HIP_TRY(ctx, next_event(r0));
     if (sc > 1 && !rd.accumulate && !lp) {   // clipped pixels of edge tiles stay 0 (an accumulating pass finds them 0 from its first pass; a list pass writes listed slots only)
@@ -957,15 +885,6 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
         for (const Span& s : spans) {
             float ms = 0.f; if (hipEventElapsedTime(&ms, s.a, s.b) != hipSuccess) continue;
             if (s.kind == 0) stats->extend_ms += ms; else if (s.kind == 1) stats->shade_ms += ms; else if (s.kind == 3) stats->drain_ms += ms; else stats->other_ms += ms;
-        }
-        if (const char* e = getenv("RT_DEBUG_ITER")) if (e[0] == '1' && timing) {
-            size_t it = 0;
-            for (size_t k = 0; k + 1 < spans.size(); ++k) {
-                if (spans[k].kind != 0 || spans[k + 1].kind != 1 || it >= iter_live.size()) continue;
-                float a = 0.f, b = 0.f; hipEventElapsedTime(&a, spans[k].a, spans[k].b); hipEventElapsedTime(&b, spans[k + 1].a, spans[k + 1].b);
-                std::fprintf(stderr, "iter %3zu  paths <= %10llu  k_extend %9.1f us  k_shade %8.1f us\n", it, (unsigned long long)iter_live[it] * rtk::kQueues, a * 1e3, b * 1e3);
-                ++it;
-            }
         }
         stats->samples = (lp ? (uint64_t)lp->n : valid_pixels) * prm->samples_per_pixel;
         stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];

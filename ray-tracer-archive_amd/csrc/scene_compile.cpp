@@ -53,8 +53,8 @@ struct Compiler {
     std::map<std::pair<long long, std::pair<long long, std::pair<long long, long long>>>, uint32_t> xform_cache;
     bool box_pair_members = false;
     bool big_spheres_first = true;
-    bool cull_lists = true;   // HittableList members behind culling boxes (emit_list_culled); RT_LIST_CULL=0: every member probed by every ray, as the reference does
-    double park_cost = 6.0;   // what a stop of the walk at a leaf costs, in primitive tests (RT_LIST_PARK_COST)
+    bool cull_lists = true;   // HittableList members behind culling boxes (emit_list_culled); RT_LAYOUT_LISTS_AS_REFERENCE: every member probed by every ray, as the reference does
+    double park_cost = 6.0;   // what a stop of the walk at a leaf costs, in primitive tests (RtUploadOptions.list_park_cost)
     std::map<std::vector<long long>, uint32_t> wrap_cache;
 
     Compiler(const RtSceneDesc& desc, CompiledScene& o) : d(desc), out(o) {}
@@ -689,7 +689,7 @@ struct Compiler {
     }
 
     // ---- optional: a box node whose whole subtree is one contiguous run of primitives of one kind, `limit` of them at most, becomes a leaf ----
-    // (fewer stops of the walk for more primitive tests; the closest hit is the same. RT_LEAF_COLLAPSE=n, default off.)
+    // (fewer stops of the walk for more primitive tests; the closest hit is the same. RtUploadOptions.leaf_collapse = n, default off.)
     void collapse_small_subtrees(uint32_t limit) {
         std::vector<rtd::Node>& src = out.nodes;
         const size_t n = src.size();

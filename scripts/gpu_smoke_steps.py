@@ -12,10 +12,8 @@ def go(tag, W, H, spp, **kw):
     t = time.time()
     img, st = ctx.render(scene, hs.camera(W / H), p.make_params(W, H, spp, **kw))
     print("done ", tag, "%.1f ms" % ((time.time() - t) * 1e3), "samples", st["samples"], "segments", st["segments"], "iters", st["iterations"], "drain", st["drain_paths"], "pool", st["pool_slots"], flush=True)
-os.environ["RT_DRAIN_AT"] = "0"
-go("wavefront 96x64x4", 96, 64, 4)
-go("wavefront 400x225x16", 400, 225, 16)
-os.environ.pop("RT_DRAIN_AT")
+go("wavefront 96x64x4", 96, 64, 4, tail_paths=1)
+go("wavefront 400x225x16", 400, 225, 16, tail_paths=1)
 go("default 96x64x4 (drain)", 96, 64, 4)
 go("default 400x225x16", 400, 225, 16)
 go("fused pool 4096", 96, 64, 4, flags=A.RT_FLAG_FUSED, pool_slots=4096)

@@ -18,8 +18,7 @@ else:
     hs = p.HostScene("book1", 1); W, H, spp = 1200, 800, 500
 scene = ctx.upload(hs.desc)
 cam = hs.camera(W / H)
-os.environ["RT_DRAIN_AT"] = "0"
-prm = p.make_params(W, H, spp, flags=2)
+prm = p.make_params(W, H, spp, flags=2, tail_paths=1)     # no drain: every segment in k_extend
 ctx.render(scene, cam, prm)
 img, st = ctx.render(scene, cam, prm)
 d = st['debug']

@@ -19,8 +19,7 @@ for n in (2, 3, 4, 5, 6, 8, 12, 20):
     for seed in range(6):
         b, desc = build(n, seed)
         sc = ctx.upload(desc)
-        os.environ["RT_DRAIN_AT"] = "0"
-        w, sw = ctx.render(sc, cam, p.make_params(96, 64, 4, seed=3, max_depth=2, flags=A.RT_FLAG_COUNTERS))
+        w, sw = ctx.render(sc, cam, p.make_params(96, 64, 4, seed=3, max_depth=2, flags=A.RT_FLAG_COUNTERS, tail_paths=1))
         f, sf = ctx.render(sc, cam, p.make_params(96, 64, 4, seed=3, max_depth=2, flags=A.RT_FLAG_COUNTERS | A.RT_FLAG_FUSED))
         if 0: print("NaN pixels: wavefront", int(np.isnan(w).any(axis=2).sum()), "fused", int(np.isnan(f).any(axis=2).sum()), "segments", sw["segments"], sf["segments"], "samples", sw["samples"], sf["samples"], "iters", sw["iterations"], sf["iterations"])
         nd = int((~np.isclose(w, f, equal_nan=True)).any(axis=2).sum())

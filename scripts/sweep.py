@@ -15,6 +15,7 @@ VARIANTS = {
     "tol4": ["RT_SPHERE_TOL=1e-4f"],
     "libm": ["RT_LIBM_SINCOS=1"],
     "stamps": ["RT_STAMPS=1"],
+    "poison": ["RT_DEBUG_POISON=1"],     # per-item sums NaN-filled before every render: an item no kernel finished shows in the frame
     "sk9": ["RT_SERVE_KINDS_MIN=9u"], "sk9b32": ["RT_SERVE_KINDS_MIN=9u", "RT_LEAF_BATCH=32"], "sk9b16": ["RT_SERVE_KINDS_MIN=9u", "RT_LEAF_BATCH=16"],
     "c16all": ["RT_C16_LOAD_ALL=1"],
     "sw7": ["RT_SHADE_WAVES=7"], "sw5": ["RT_SHADE_WAVES=5"], "sw6": ["RT_SHADE_WAVES=6"], "sw8": ["RT_SHADE_WAVES=8"],

@@ -78,6 +78,19 @@ def test_product_never_touches_the_oracle():
                 assert "oracle" not in txt and "liboracle" not in txt, os.path.join(dp, f)
 
 
+def test_library_reads_no_environment_but_the_rccl_path():
+    # the library's behaviour comes from its arguments; the one environment read says where librccl is (rt_multi.cpp)
+    pk = os.path.join(ROOT, "ray-tracer-archive_amd")
+    reads = []
+    for dp, _, files in os.walk(pk):
+        for f in files:
+            if f.endswith((".c", ".cc", ".cpp", ".hip", ".h", ".hpp")):
+                for line in open(os.path.join(dp, f), errors="ignore"):
+                    if "getenv" in line:
+                        reads.append((f, re.findall(r'getenv\s*\(\s*"([A-Za-z0-9_]+)"', line)))
+    assert reads == [("rt_multi.cpp", ["RT_RCCL_LIB"])]
+
+
 def test_rust_shim_covers_the_header():
     """docs/gpu_ffi.rs (the `extern "C"` block a maintainer adds as raytracer/src/gpu_ffi.rs; never compiled here: no Rust toolchain) binds
     every function include/rt_hip.h declares, and its #[repr(C)] structs list the header's fields in the header's order."""

@@ -248,7 +248,7 @@ def test_parameter_corners_are_pool_independent(pkg, gpu):
 
 def test_drain_kernel_is_bit_identical(pkg, gpu, earth):
     """The tail of a render is carried by ONE fused launch (one lane per path: walk, shade in place, next ray, new work while there is
-    any). Wherever the hand-over happens — never (RT_DRAIN_AT=0), at the default, or at the first ray (RT_FLAG_FUSED: the whole
+    any). Wherever the hand-over happens — never (tail_paths = 1), at the default, or at the first ray (RT_FLAG_FUSED: the whole
     render by that kernel, including its own regeneration from a tiny pool) — the frame, the sample count and the segment count are
     the same, on every kernel feature set: spheres only, rects + instance transforms + lights, media + textures + moving spheres."""
     import os

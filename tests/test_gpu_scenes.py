@@ -260,7 +260,7 @@ def test_list_culling_and_prologue_change_nothing_but_the_counters(pkg, orc, gpu
     """A root list with one of everything next to a BVH (so that the compiler culls its members, scene_compile.cpp emit_list_culled):
     a hollow glass sphere (negative radius), a moving sphere (prologue), a fog that holds the whole scene (prologue), a small medium in
     a rotated box, an instanced box, loose rects, triangles and a nested list. The culled layout, the layout forced for every scene
-    (RT_LIST_CULL=2) and the reference's layout (every member in front of every ray) render the same frame bit for bit; the oracle agrees
+    (RT_LAYOUT_LISTS_CULLED) and the reference's layout (every member in front of every ray) render the same frame bit for bit; the oracle agrees
     within the usual tolerances; the culled walk makes fewer primitive tests."""
     rng = np.random.default_rng(11)
     b = pkg.SceneBuilder(background=(0.55, 0.65, 0.9))
