@@ -131,6 +131,14 @@ pub struct RtPassOptions {
 pub struct RtAdaptiveOptions {
     pub struct_bytes: u32, pub min_samples: u32, pub rel_error: f64, pub abs_error: f64,
 }
+// denoising: non-local means over the sample variance (rt_denoise_device); a field left 0 takes its default
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtDenoiseOptions {
+    pub struct_bytes: u32, pub window_radius: u32, pub patch_radius: u32, pub samples_per_item: u32,
+    pub strength: f64, pub alpha: f64, pub eps: f64,
+}
+pub const RT_DENOISE_MAX_WINDOW_RADIUS: u32 = 16;
+pub const RT_DENOISE_MAX_PATCH_RADIUS: u32 = 4;
 
 pub const RT_N_PRIM_TYPES: usize = 6;
 #[repr(C)] #[derive(Clone, Copy, Default, Debug)]
@@ -202,6 +210,11 @@ extern "C" {
     /// write_color with each pixel's own count (full frame); a count of 0 gives black
     pub fn rt_resolve_counts_device(ctx: *mut RtCtx, rgb_sum_device: *const c_void, counts_device: *const c_void, width: u32, height: u32,
                                     rgb8_device: *mut c_void) -> c_int;
+    /// host only: validates a frame size and denoise options (null = defaults)
+    pub fn rt_denoise_check(width: u32, height: u32, options: *const RtDenoiseOptions) -> c_int;
+    /// filtered MEAN radiance (width * height * 3 f32) from rgb_sum, sq_sum and the sample count; counts_device null = uniform `samples`
+    pub fn rt_denoise_device(ctx: *mut RtCtx, options: *const RtDenoiseOptions, width: u32, height: u32, rgb_sum_device: *const c_void,
+                             sq_sum_device: *const c_void, samples: u32, counts_device: *const c_void, mean_out_device: *mut c_void) -> c_int;
     pub fn rt_untile(params: *const RtParams, gathered: *const f32, rgb_sum: *mut f32) -> c_int;
     /// write_color (main.rs:141-169) on the device
     pub fn rt_resolve_device(ctx: *mut RtCtx, rgb_sum_device: *const c_void, width: u32, height: u32,

@@ -381,6 +381,45 @@ int rt_render_pass_pixels_device(RtCtx* ctx, const RtScene* scene, const RtCamer
 /* write_color with every pixel's own count (full frame, width * height counts): spp = counts[p]; a count of 0 gives (0, 0, 0). */
 int rt_resolve_counts_device(RtCtx* ctx, const void* rgb_sum_device, const void* counts_device, uint32_t width, uint32_t height, void* rgb8_device);
 
+/* ---- denoising: non-local means over the sample variance ---------------------------------------------------------------------------------
+ *
+ * A filtered preview of a low-sample frame from nothing but what a pass already leaves: rgb_sum, sq_sum and the sample count (uniform, or
+ * the adaptive COUNTS buffer). Non-local means with the patch distance normalised by the per-pixel variance of the mean (Rousselle, Knaus,
+ * Zwicker 2012). Full frame, row-major, width x height; S = rgb_sum, Q = sq_sum, n_p = the pixel's samples, m = samples per work item
+ * (rt_pass_check), k_p = n_p / m rounded up.
+ * PREPARE, per pixel and channel, in f64, rounded to f32:  u = S / n_p;  v = max(Q - S^2 / k_p, 0) / (k_p (k_p - 1)) / m^2  (SE squared).
+ * A pixel is INVALID when n_p == 0, k_p < 2, or one of its S, Q is not finite.
+ * FILTER, with window radius r, patch radius f, strength k, variance cancellation alpha and eps; for a valid pixel p and every VALID q of
+ * the image with |q - p|_inf <= r:
+ *     t      = ((u[p+o] - u[q+o])^2 - alpha (v[p+o] + min(v[p+o], v[q+o]))) / (eps + k^2 (v[p+o] + v[q+o]))
+ *     d(p,q) = the mean of t over the patch offsets |o|_inf <= f whose p+o and q+o are both valid image pixels, and the three channels
+ *     w(p,q) = exp(-max(d, 0))                    (w(p,p) = 1)
+ *     out[p] = sum_q w(p,q) u[q] / sum_q w(p,q)   per channel
+ * An invalid pixel is copied through (out = u, or 0 with no sample) and is nobody's neighbour. The filter step runs in f32.
+ * mean_out: width * height * 3 floats, the MEAN radiance (not sums), device memory the caller owns, not one of the inputs; the inputs are
+ * never written. RGB8 of it: rt_resolve_device with samples_per_pixel = 1.
+ * A field left 0 takes its default: window_radius 10, patch_radius 3, strength 0.45, alpha 1, eps 1e-10 (the paper's values), so a
+ * negative or non-finite strength / alpha / eps is RT_ERR_INVALID. Caps: window_radius <= 16, patch_radius <= 4 — a workgroup stages its
+ * 32 x 32 tile plus an (r + f) halo of u and v in LDS (72 x 72 x 24 B = 122 KiB at the caps, plus 22 KiB of box-sum buffers, of 160 KiB).
+ * The result does not depend on the launch shape and is the same bits on every call. */
+#define RT_DENOISE_MAX_WINDOW_RADIUS 16
+#define RT_DENOISE_MAX_PATCH_RADIUS 4
+typedef struct RtDenoiseOptions {
+    uint32_t struct_bytes;      /* sizeof(RtDenoiseOptions) as the caller compiled it (the struct may grow at its end) */
+    uint32_t window_radius;     /* r; 0 = 10 */
+    uint32_t patch_radius;      /* f; 0 = 3 */
+    uint32_t samples_per_item;  /* m of the frame the sums belong to (rt_pass_check); 0 = 1 */
+    double strength;            /* k; 0 = 0.45 */
+    double alpha;               /* 0 = 1 */
+    double eps;                 /* 0 = 1e-10 */
+} RtDenoiseOptions;
+/* Host only, no device: validates (width, height, options; NULL = defaults) and reports the reason through rt_last_error. */
+int rt_denoise_check(uint32_t width, uint32_t height, const RtDenoiseOptions* options);
+/* samples: every pixel's count when counts_device is NULL (>= 1); else counts_device holds width * height uint32_t. Two kernels on the
+   context's stream; blocks until done. A refused call writes nothing. */
+int rt_denoise_device(RtCtx* ctx, const RtDenoiseOptions* options /* NULL = defaults */, uint32_t width, uint32_t height, const void* rgb_sum_device,
+                      const void* sq_sum_device, uint32_t samples, const void* counts_device /* NULL = uniform `samples` */, void* mean_out_device);
+
 /* Host-side helper: scatter `shard_count` gathered shard buffers (each rt_output_floats long,
    in shard order) into a full-frame rgb_sum. */
 int rt_untile(const RtParams* params, const float* gathered, float* rgb_sum);

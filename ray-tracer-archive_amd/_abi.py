@@ -17,6 +17,7 @@ RT_FLAG_COUNTERS, RT_FLAG_TIMING, RT_FLAG_SAMPLE_BLOCKS, RT_FLAG_FUSED = 1, 2, 4
 RT_OUT_RGB_SUM_F32, RT_OUT_RGB8 = 0, 1
 RT_PASS_ACCUMULATE = 1
 RT_COMM_ID_BYTES = 128
+RT_DENOISE_MAX_WINDOW_RADIUS, RT_DENOISE_MAX_PATCH_RADIUS = 16, 4
 # RtUploadOptions.layout_flags
 (RT_LAYOUT_LISTS_AS_REFERENCE, RT_LAYOUT_LISTS_CULLED, RT_LAYOUT_NO_MEMBER_BOXES, RT_LAYOUT_MEMBER_BOXES, RT_LAYOUT_CHILD_ORDER_AS_REFERENCE,
  RT_LAYOUT_SCENE_IN_HBM, RT_LAYOUT_NODES_32B, RT_LAYOUT_NO_SHADE_TABLES_IN_LDS, RT_LAYOUT_NO_EXTEND_TABLES_IN_LDS, RT_LAYOUT_WIDE_NODES) = (1 << k for k in range(10))
@@ -111,6 +112,11 @@ class RtAdaptiveOptions(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("min_samples", C.c_uint32), ("rel_error", C.c_double), ("abs_error", C.c_double)]
 
 
+class RtDenoiseOptions(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("window_radius", C.c_uint32), ("patch_radius", C.c_uint32), ("samples_per_item", C.c_uint32),
+                ("strength", C.c_double), ("alpha", C.c_double), ("eps", C.c_double)]
+
+
 class RtWideInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("n_leaf_entries", C.c_uint64), ("n_inner_entries", C.c_uint64), ("n_prims", C.c_uint64),
                 ("depth", C.c_uint32), ("_pad", C.c_uint32), ("mean_children", C.c_double), ("mean_leaf_members", C.c_double)]
@@ -124,7 +130,8 @@ RT_HIP_SYMBOLS = ["rt_ctx_create", "rt_ctx_destroy", "rt_scene_upload", "rt_scen
                   "rt_render_gather", "rt_untile_rgb8", "rt_untile_device", "rt_scene_top_layout_check", "rt_scene_upload_ex", "rt_scene_upload_multi_ex",
                   "rt_runtime_libraries", "rt_test_fail_next_renders", "rt_test_device_workers", "rt_scene_compile_info_ex", "rt_scene_compile_dump_ex", "rt_scene_wide_layout_check",
                   "rt_pass_check", "rt_render_pass", "rt_render_pass_device",
-                  "rt_adaptive_check", "rt_adaptive_select", "rt_render_pass_pixels_device", "rt_resolve_counts_device"]
+                  "rt_adaptive_check", "rt_adaptive_select", "rt_render_pass_pixels_device", "rt_resolve_counts_device",
+                  "rt_denoise_check", "rt_denoise_device"]
 RT_HOST_SYMBOLS = ["rt_host_scene_create", "rt_host_scene_desc", "rt_host_scene_camera", "rt_host_scene_destroy", "rt_host_camera_new",
                    "rt_host_write_color", "rt_host_tonemap", "rt_host_write_png", "rt_host_write_jpeg", "rt_host_write_image"]
 
@@ -175,6 +182,10 @@ def declare(lib):
     lib.rt_render_pass_pixels_device.argtypes = [vp, vp, P(RtCamera), P(RtParams), P(RtPassOptions), vp, u32, vp, vp, vp, P(RtStats)]
     lib.rt_resolve_counts_device.restype = i32
     lib.rt_resolve_counts_device.argtypes = [vp, vp, vp, u32, u32, vp]
+    lib.rt_denoise_check.restype = i32
+    lib.rt_denoise_check.argtypes = [u32, u32, P(RtDenoiseOptions)]
+    lib.rt_denoise_device.restype = i32
+    lib.rt_denoise_device.argtypes = [vp, P(RtDenoiseOptions), u32, u32, vp, vp, u32, vp, vp]
     lib.rt_untile.restype = i32
     lib.rt_untile.argtypes = [P(RtParams), P(C.c_float), P(C.c_float)]
     lib.rt_resolve_device.restype = i32

@@ -227,6 +227,20 @@ class Adaptive:
         self.ctx.resolve_counts_device(rgb, cnt, p.width, p.height, out)
         return out.cpu().numpy().reshape(p.height, p.width, 3)
 
+    def denoised(self, rgb8=False, **opts):
+        """The frame filtered by rt_denoise_device with every pixel's own count (opts: denoise_options fields): the mean radiance, f32
+        (H, W, 3), or its write_color bytes with rgb8=True. A pixel below two work items is copied through; a sharded frame is untiled first."""
+        from .denoise import denoise_frame
+        import torch
+        p, dev = self.params, self._rgb.device
+        if p.shard_count <= 1:
+            rgb, sq, cnt = self._rgb, self._sq, self._counts
+        else:
+            rgb = torch.from_numpy(np.ascontiguousarray(self.rgb_sum()).reshape(-1)).to(dev)
+            sq = torch.from_numpy(np.ascontiguousarray(self.sq_sum()).reshape(-1)).to(dev)
+            cnt = torch.from_numpy(np.ascontiguousarray(self.counts()).view(np.int32).reshape(-1)).to(dev)
+        return denoise_frame(self.ctx, rgb, sq, p.width, p.height, self.samples_per_item, counts=cnt, rgb8=rgb8, **opts)
+
     # ---- checkpoints ----
     def save(self, path):
         """An .npz checkpoint: sums, counts, samples_done, frame_samples, the options, the RtParams fields, the camera and the scene."""

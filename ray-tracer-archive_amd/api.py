@@ -64,6 +64,16 @@ def adaptive_check(params, options, first_sample, frame_samples):
     _check(lib().rt_adaptive_check(C.byref(params), C.byref(options), first_sample, frame_samples))
 
 
+def denoise_options(window_radius=0, patch_radius=0, samples_per_item=0, strength=0.0, alpha=0.0, eps=0.0):
+    """RtDenoiseOptions; a field left 0 takes its default (window 10, patch 3, m 1, strength 0.45, alpha 1, eps 1e-10)."""
+    return A.RtDenoiseOptions(C.sizeof(A.RtDenoiseOptions), int(window_radius), int(patch_radius), int(samples_per_item), float(strength), float(alpha), float(eps))
+
+
+def denoise_check(width, height, options=None):
+    """rt_denoise_check (host only): raises RtError (RT_ERR_INVALID, with the reason) for a size or options the filter refuses."""
+    _check(lib().rt_denoise_check(width, height, C.byref(options) if options is not None else None))
+
+
 def _check_device(a, b, n, what, float_):
     """a (and b, unless None) are contiguous CUDA tensors of n elements (n None: any), float32 or a 32-bit integer type."""
     import torch
@@ -371,6 +381,25 @@ class Context:
         torch.cuda.synchronize(rgb_sum.device)
         _check(lib().rt_resolve_counts_device(self._h, C.c_void_p(rgb_sum.data_ptr()), C.c_void_p(counts.data_ptr()), width, height,
                                               C.c_void_p(rgb8_out.data_ptr())), self._h)
+
+    # ---- denoising (include/rt_hip.h, "denoising"): device tensors only ----
+    def denoise(self, rgb_sum, sq_sum, width, height, samples=0, counts=None, options=None, out=None):
+        """rt_denoise_device: the filtered MEAN radiance of a full frame from its sums (float32 CUDA tensors of width * height * 3
+        elements) and either the uniform sample count `samples` or per-pixel `counts` (32-bit integer tensor of width * height). Returns
+        `out` (a new float32 tensor of width * height * 3 elements when None); a refused call raises RtError and leaves `out` untouched."""
+        import torch
+        n = 3 * width * height
+        _check_device(rgb_sum, sq_sum, n=n, what="rgb_sum / sq_sum", float_=True)
+        if counts is not None:
+            _check_device(counts, None, n=width * height, what="counts", float_=False)
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=rgb_sum.device)
+        _check_device(out, None, n=n, what="out", float_=True)
+        torch.cuda.synchronize(rgb_sum.device)        # the library's stream is not torch's
+        _check(lib().rt_denoise_device(self._h, C.byref(options) if options is not None else None, width, height, C.c_void_p(rgb_sum.data_ptr()),
+                                       C.c_void_p(sq_sum.data_ptr()), int(samples), C.c_void_p(counts.data_ptr()) if counts is not None else None,
+                                       C.c_void_p(out.data_ptr())), self._h)
+        return out
 
     # ---- one process per GPU: RCCL communicator on this context (rt_multi.cpp) ----
     def comm_init_rank(self, unique_id, rank, world):

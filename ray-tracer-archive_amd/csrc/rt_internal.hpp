@@ -25,6 +25,13 @@ struct DevBuf {
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
+// a DevBuf that frees itself with its owner (rt_ctx_destroy deletes the context with its device current)
+struct OwnedDevBuf : DevBuf {
+    OwnedDevBuf() = default;
+    OwnedDevBuf(const OwnedDevBuf&) = delete;
+    OwnedDevBuf& operator=(const OwnedDevBuf&) = delete;
+    ~OwnedDevBuf() { release(); }
+};
 
 }  // namespace rti
 
@@ -47,6 +54,7 @@ struct RtCtx {
     hipEvent_t ev_gather[2] = {nullptr, nullptr}; // brackets the exchange (RtStats.gather_ms); made at the first gather, kept
     rti::DevBuf list_map;                        // adaptive sampling: output slot -> list index of a list pass (rt_render_pass_pixels_device)
     rti::DevBuf sel_masks, sel_offsets, adaptive_word;   // rt_adaptive_select's wave ballots and their scan; the list check's verdict / the list's length
+    rti::OwnedDevBuf denoise_planes;             // rt_denoise_device: per-pixel mean and variance of the mean, three float2 planes (denoise.hip)
     uint32_t fail_renders = 0;                   // rt_test_fail_next_renders: renders still to fail (fault injection for the failure-path tests)
 };
 

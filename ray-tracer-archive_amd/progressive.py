@@ -181,6 +181,27 @@ class Progressive:
         self.ctx.resolve_device(src.data_ptr(), p.width, p.height, self.samples_done, out.data_ptr())
         return out.cpu().numpy().reshape(p.height, p.width, 3)
 
+    def denoised(self, rgb8=False, **opts):
+        """The frame so far filtered by rt_denoise_device (non-local means over the sample variance; opts: denoise_options fields, the
+        frame's samples per work item is filled in): the mean radiance, f32 (H, W, 3), or its write_color bytes with rgb8=True. A
+        sharded frame is untiled first: the other shards' pixels hold no sums and come out as they are, 0."""
+        from .denoise import denoise_frame
+        if self.samples_done == 0:
+            raise ValueError("no samples rendered yet")
+        if self._sq is None:
+            raise ValueError("this frame keeps no squared sums (sq_sum=False)")
+        import torch
+        p, dev = self.params, self._rgb.device
+        if p.shard_count <= 1:
+            return denoise_frame(self.ctx, self._rgb, self._sq, p.width, p.height, self.samples_per_item, samples=self.samples_done, rgb8=rgb8, **opts)
+        from .adaptive import slot_pixels
+        x, y, ok = slot_pixels(p)
+        cnt = np.zeros((p.height, p.width), dtype=np.int32)          # the other shards' pixels hold no sample: nobody's neighbours
+        cnt[y[ok], x[ok]] = self.samples_done
+        rgb = torch.from_numpy(np.ascontiguousarray(self.rgb_sum()).reshape(-1)).to(dev)
+        sq = torch.from_numpy(np.ascontiguousarray(self.sq_sum()).reshape(-1)).to(dev)
+        return denoise_frame(self.ctx, rgb, sq, p.width, p.height, self.samples_per_item, counts=torch.from_numpy(cnt.reshape(-1)).to(dev), rgb8=rgb8, **opts)
+
     def save(self, path):
         """An .npz checkpoint: the sums, samples_done, frame_samples, the RtParams fields, the camera and the scene fingerprint."""
         z = dict(version=np.int64(CHECKPOINT_VERSION), samples_done=np.int64(self.samples_done), frame_samples=np.int64(self.frame_samples),
