@@ -137,6 +137,17 @@ pub struct RtDenoiseOptions {
     pub struct_bytes: u32, pub window_radius: u32, pub patch_radius: u32, pub samples_per_item: u32,
     pub strength: f64, pub alpha: f64, pub eps: f64,
 }
+// ray queries: the closest hit of caller-supplied rays (rt_trace_rays); t_max <= 0 or +inf = no limit
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtRay { pub o: [f32; 3], pub time: f32, pub d: [f32; 3], pub t_max: f32 }
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtRayHit {
+    pub t: f32, pub hittable: i32, pub material: i32, pub flags: u32,
+    pub p: [f32; 3], pub u: f32, pub n: [f32; 3], pub v: f32,
+}
+pub const RT_RAYHIT_HIT: u32 = 1; pub const RT_RAYHIT_FRONT_FACE: u32 = 2; pub const RT_RAYHIT_INVALID_RAY: u32 = 4;
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtRayQueryOptions { pub struct_bytes: u32, pub flags: u32, pub pool_slots: u32, pub _pad: u32 }
 pub const RT_DENOISE_MAX_WINDOW_RADIUS: u32 = 16;
 pub const RT_DENOISE_MAX_PATCH_RADIUS: u32 = 4;
 
@@ -215,6 +226,13 @@ extern "C" {
     /// filtered MEAN radiance (width * height * 3 f32) from rgb_sum, sq_sum and the sample count; counts_device null = uniform `samples`
     pub fn rt_denoise_device(ctx: *mut RtCtx, options: *const RtDenoiseOptions, width: u32, height: u32, rgb_sum_device: *const c_void,
                              sq_sum_device: *const c_void, samples: u32, counts_device: *const c_void, mean_out_device: *mut c_void) -> c_int;
+    /// host only: validates ray-query options (null = defaults) and a ray count
+    pub fn rt_ray_query_check(options: *const RtRayQueryOptions, n_rays: u64) -> c_int;
+    /// closest hits of n_rays RtRay records in device memory, one RtRayHit each (device memory, 16-byte aligned)
+    pub fn rt_trace_rays_device(ctx: *mut RtCtx, scene: *const RtScene, options: *const RtRayQueryOptions, rays_device: *const c_void, n_rays: u64,
+                                hits_device: *mut c_void, stats: *mut RtStats) -> c_int;
+    pub fn rt_trace_rays(ctx: *mut RtCtx, scene: *const RtScene, options: *const RtRayQueryOptions, rays_host: *const RtRay, n_rays: u64,
+                         hits_host: *mut RtRayHit, stats: *mut RtStats) -> c_int;
     pub fn rt_untile(params: *const RtParams, gathered: *const f32, rgb_sum: *mut f32) -> c_int;
     /// write_color (main.rs:141-169) on the device
     pub fn rt_resolve_device(ctx: *mut RtCtx, rgb_sum_device: *const c_void, width: u32, height: u32,

@@ -420,6 +420,50 @@ int rt_denoise_check(uint32_t width, uint32_t height, const RtDenoiseOptions* op
 int rt_denoise_device(RtCtx* ctx, const RtDenoiseOptions* options /* NULL = defaults */, uint32_t width, uint32_t height, const void* rgb_sum_device,
                       const void* sq_sum_device, uint32_t samples, const void* counts_device /* NULL = uniform `samples` */, void* mean_out_device);
 
+/* ---- ray queries: the closest hit of caller-supplied rays ----------------------------------------------------------------------------------
+ *
+ * hits[i] is the HitRecord that `world.hit(ray_i, 0.001, inf)` returns (main.rs:74, hittable.rs:11-19) for the uploaded scene: t, p, the
+ * normal after set_face_normal and the replay of the Translate / RotateY / FlipFace wrappers above the primitive, u, v and front_face. The
+ * rays go through the traversal kernels a render uses, in the layout the scene was uploaded with (every RT_LAYOUT_* answers queries).
+ *   - t_min is the renderer's 0.001 and cannot be chosen. A closest hit beyond the ray's t_max is a MISS (t_max <= 0, +inf or NaN: no limit).
+ *   - u, v are always computed (a render computes them for textured scenes only): sphere.rs:32-37, aarect.rs:41-42, barycentrics for a
+ *     triangle, 0 for a moving sphere (moving_sphere.rs leaves them unset).
+ *   - a MISS is t = +inf, hittable = material = -1, flags = 0, every other field 0.
+ *   - material: index into RtSceneDesc.materials. hittable: index of the primitive's own RtHittable record — for a side of a Box the
+ *     Box's record, never a wrapper, a list or a BVH.
+ *   - Rays are f32 and live in device memory for the *_device variant (n_rays records of 32 bytes, 16-byte aligned; hits: 48 bytes each,
+ *     16-byte aligned). The device path computes in f32; an f32 ray is exact in the f64 of the reference.
+ *   - INVALID rays never reach a traversal kernel: the kernel that reads the caller's rays drops them, and their hit is a miss with
+ *     RT_RAYHIT_INVALID_RAY set. Invalid is: a non-finite origin, direction or time; or a direction whose squared length |d|^2, formed in
+ *     f32, is not a positive normal number — the zero direction, and directions so short or so long that |d|^2 underflows (|d| below
+ *     about 1.1e-19) or overflows (|d| above about 1.8e19), for which the walk's 1 / |d|^2 would be inf or 0.
+ *   - A scene that holds a ConstantMedium is RT_ERR_UNSUPPORTED and nothing is written: a medium's hit is a random draw keyed by (path,
+ *     segment, medium) and a bare ray has no path. A deliberate limit. Every query ray starts on nothing (there is no "the primitive this
+ *     ray leaves" input), there is no any-hit mode and no multi-GPU entry point.
+ *   - Options: an unknown bit in flags (known: RT_FLAG_TIMING), struct_bytes < sizeof(RtRayQueryOptions) or n_rays >= 2^32 is
+ *     RT_ERR_INVALID with the reason in rt_last_error, and nothing is written. n_rays == 0 is a no-op. pool_slots caps the rays in flight
+ *     (0 = the renderer's rule: all of them, up to 2^28 and to 70 % of the free device memory); longer lists run in chunks.
+ *   - Determinism: hits[i] is a function of (scene, layout, ray i) alone — not of the chunk size, of the ray's place in the list, or of
+ *     the host / device variant — and the same call gives the same bytes every time.
+ *   - RtStats: samples = segments = n_rays minus the invalid ones; render_ms; with RT_FLAG_TIMING also extend_ms (the traversal kernels)
+ *     and other_ms (the two kernels that read the rays and write the hits). Both variants block until done. */
+typedef struct RtRay    { float o[3]; float time; float d[3]; float t_max; } RtRay;       /* 32 B; t_max <= 0 or +inf = no limit */
+typedef struct RtRayHit { float t; int32_t hittable; int32_t material; uint32_t flags;    /* 48 B */
+                          float p[3]; float u; float n[3]; float v; } RtRayHit;
+enum { RT_RAYHIT_HIT = 1u, RT_RAYHIT_FRONT_FACE = 2u, RT_RAYHIT_INVALID_RAY = 4u };
+typedef struct RtRayQueryOptions {
+    uint32_t struct_bytes;    /* sizeof(RtRayQueryOptions) as the caller compiled it (the struct may grow at its end) */
+    uint32_t flags;           /* RT_FLAG_TIMING; an unknown bit is RT_ERR_INVALID */
+    uint32_t pool_slots;      /* rays in flight; 0 = default */
+    uint32_t _pad;
+} RtRayQueryOptions;
+/* Host only, no device: validates (options, n_rays) and reports the reason through rt_last_error. */
+int rt_ray_query_check(const RtRayQueryOptions* options /* NULL = defaults */, uint64_t n_rays);
+int rt_trace_rays_device(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options /* NULL = defaults */, const void* rays_device, uint64_t n_rays,
+                         void* hits_device, RtStats* stats);
+int rt_trace_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options /* NULL = defaults */, const RtRay* rays_host, uint64_t n_rays,
+                  RtRayHit* hits_host, RtStats* stats);
+
 /* Host-side helper: scatter `shard_count` gathered shard buffers (each rt_output_floats long,
    in shard order) into a full-frame rgb_sum. */
 int rt_untile(const RtParams* params, const float* gathered, float* rgb_sum);

@@ -74,6 +74,21 @@ def denoise_check(width, height, options=None):
     _check(lib().rt_denoise_check(width, height, C.byref(options) if options is not None else None))
 
 
+# numpy views of RtRay / RtRayHit (include/rt_hip.h, "ray queries"): 32 and 48 bytes, field for field
+RAY_DTYPE = np.dtype([("o", np.float32, 3), ("time", np.float32), ("d", np.float32, 3), ("t_max", np.float32)])
+RAYHIT_DTYPE = np.dtype([("t", np.float32), ("hittable", np.int32), ("material", np.int32), ("flags", np.uint32),
+                         ("p", np.float32, 3), ("u", np.float32), ("n", np.float32, 3), ("v", np.float32)])
+
+
+def ray_query_options(flags=0, pool_slots=0):
+    return A.RtRayQueryOptions(C.sizeof(A.RtRayQueryOptions), flags, pool_slots, 0)
+
+
+def ray_query_check(options=None, n_rays=0):
+    """rt_ray_query_check (host only): raises RtError (RT_ERR_INVALID, with the reason) for options or a ray count a query refuses."""
+    _check(lib().rt_ray_query_check(C.byref(options) if options is not None else None, n_rays))
+
+
 def _check_device(a, b, n, what, float_):
     """a (and b, unless None) are contiguous CUDA tensors of n elements (n None: any), float32 or a 32-bit integer type."""
     import torch
@@ -381,6 +396,46 @@ class Context:
         torch.cuda.synchronize(rgb_sum.device)
         _check(lib().rt_resolve_counts_device(self._h, C.c_void_p(rgb_sum.data_ptr()), C.c_void_p(counts.data_ptr()), width, height,
                                               C.c_void_p(rgb8_out.data_ptr())), self._h)
+
+    # ---- ray queries (include/rt_hip.h, "ray queries") ----
+    def trace_rays(self, scene, rays, options=None, out=None, with_stats=False):
+        """rt_trace_rays / rt_trace_rays_device: the closest hit of every ray.
+
+        Host variant: `rays` is a numpy array of RAY_DTYPE (or float32 of shape (n, 8): o, time, d, t_max); returns a RAYHIT_DTYPE array.
+        Device variant: `rays` is a contiguous float32 CUDA tensor of shape (n, 8); returns a float32 CUDA tensor of shape (n, 12) holding
+        the RtRayHit records (view the integer fields with .view(torch.int32), or RAYHIT_DTYPE after .cpu().numpy()). `out` receives the
+        hits when given (same kind and size); a refused call raises RtError and leaves it untouched. with_stats: also return the stats."""
+        st = A.RtStats()
+        opt = C.byref(options) if options is not None else None
+        if hasattr(rays, "data_ptr"):
+            import torch
+            if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
+                raise ValueError("device rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
+            n = rays.shape[0]
+            if out is None:
+                out = torch.empty((n, 12), dtype=torch.float32, device=rays.device)
+            if not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != 12 * n:
+                raise ValueError("out must be a contiguous float32 CUDA tensor of n * 12 elements")
+            if rays.device.index != self.device_id or out.device != rays.device:      # another GPU's pointer means nothing to this context's kernels
+                raise ValueError(f"rays and out must live on this context's device (cuda:{self.device_id})")
+            torch.cuda.synchronize(rays.device)           # the library's stream is not torch's
+            _check(lib().rt_trace_rays_device(self._h, scene._h, opt, C.c_void_p(rays.data_ptr() if n else None), n, C.c_void_p(out.data_ptr() if n else None),
+                                              C.byref(st)), self._h)
+            return (out, st.as_dict()) if with_stats else out
+        rays = np.asarray(rays)
+        if rays.dtype != RAY_DTYPE:
+            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+                raise ValueError("host rays must be a numpy array of RAY_DTYPE, or float32 of shape (n, 8)")
+            rays = np.ascontiguousarray(rays).view(RAY_DTYPE).reshape(-1)
+        rays = np.ascontiguousarray(rays).reshape(-1)
+        n = rays.shape[0]
+        if out is None:
+            out = np.empty(n, dtype=RAYHIT_DTYPE)
+        if not isinstance(out, np.ndarray) or out.dtype != RAYHIT_DTYPE or not out.flags.c_contiguous or out.size != n:
+            raise ValueError("out must be a C-contiguous numpy array of n RAYHIT_DTYPE records")
+        _check(lib().rt_trace_rays(self._h, scene._h, opt, C.c_void_p(rays.ctypes.data if n else None), n, C.c_void_p(out.ctypes.data if n else None),
+                                   C.byref(st)), self._h)
+        return (out, st.as_dict()) if with_stats else out
 
     # ---- denoising (include/rt_hip.h, "denoising"): device tensors only ----
     def denoise(self, rgb_sum, sq_sum, width, height, samples=0, counts=None, options=None, out=None):

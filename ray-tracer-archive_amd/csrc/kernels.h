@@ -178,6 +178,16 @@ struct SelectArgs {
 hipError_t launch_select(const SelectArgs& a, unsigned long long* masks, uint32_t* offsets, uint32_t* out, uint32_t* n_out, hipStream_t stream);
 hipError_t launch_write_color_counts(const float* rgb_sum, const uint32_t* counts, uint32_t n_pixels, uint8_t* rgb8, hipStream_t stream);
 hipError_t launch_write_color(const float* rgb_sum, uint32_t n_pixels, uint32_t spp, uint8_t* rgb8, hipStream_t stream);
+// ray queries (kernels.hip "ray queries"). RaySrcDev: the RtHittable record every primitive came from, by kind (scene_compile.hpp) — its own
+// block, not part of SceneDev: no render kernel's arguments change.
+struct RaySrcDev { const uint32_t* sphere; const uint32_t* moving; const uint32_t* rect; const uint32_t* tri; };
+// rays [first, first + n) of the list (RtRay records) into `pool`, spread over its queues; `counts` (zeroed by the caller) receives the queues'
+// sizes, invalid rays get their RtRayHit at once, counters[CTR_SEGMENTS] counts the rays stored. n <= kQueues * queue_cap, queue_cap % 512 == 0.
+hipError_t launch_rays_import(const void* rays, uint32_t first, uint32_t n, const PoolDev& pool, uint32_t queue_cap, uint32_t* counts, void* hits,
+                              unsigned long long* counters, hipStream_t stream);
+// after launch_extend: one RtRayHit per pool slot, at its ray's index (max_count: upper bound of the rays in one queue)
+hipError_t launch_rays_export(const LaunchCfg& cfg, const SceneDev& sc, const RaySrcDev& src, const PoolDev& pool, uint32_t queue_cap, uint32_t max_count,
+                              const uint32_t* counts, void* hits, hipStream_t stream);
 // multi-GPU root: gathered shard buffers -> full frame (rt_multi.cpp)
 hipError_t launch_untile_f32(const float* gathered, float* frame, uint32_t width, uint32_t height, uint32_t ts, uint32_t tiles_x, uint32_t world, uint64_t per_shard,
                              hipStream_t stream);

@@ -2157,6 +2157,150 @@ __global__ void __launch_bounds__(256) k_untile(const T* __restrict__ gathered, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// ray queries (rt_hip.h "ray queries"): caller's rays -> pool records -> k_extend -> RtRayHit records
+// ------------------------------------------------------------------------------------------------
+// k_rays_import: rays [first, first + n) of the caller's list become pool records — ray_o = (o, time), ray_d = (d, 0: the ray starts on
+// nothing), s0 = (t_max, 0, 0, the ray's index in the list), sd = 0 draws. Workgroup b (512 rays) feeds queue b mod kQueues, as k_generate's
+// first fill does; the slots come from the queue's size counter (zeroed by the host; one returning atomic per workgroup), so a queue stays
+// dense whatever is dropped. DROPPED here, never stored: a ray with a non-finite origin, direction or time, or whose |d|^2 is not a positive
+// normal f32 (the zero direction; a direction so small or so large that the walks' 1/|d|^2 would be inf or 0). Its hit record is written at
+// once — a miss with RT_RAYHIT_INVALID_RAY — so no walk ever starts on such a ray. A queue receives at most ceil(n / 512) / kQueues
+// workgroups of at most 512 rays; the host keeps n <= kQueues * queue_cap with queue_cap a multiple of 512, so a slot is < queue_cap (and a
+// ray whose slot were not is dropped as invalid rather than stored out of bounds).
+constexpr uint32_t kRaysImportThreads = 512;
+constexpr uint32_t kRayHitHit = 1u, kRayHitFrontFace = 2u, kRayHitInvalid = 4u;   // RT_RAYHIT_*
+DEVI bool query_ray_valid(Float4 ro, Float4 rdv) {
+    const float a = rdv.x * rdv.x + rdv.y * rdv.y + rdv.z * rdv.z;               // len2(d) as the walk forms it
+    const bool fin_o = fabsf(ro.x) < kInf && fabsf(ro.y) < kInf && fabsf(ro.z) < kInf && fabsf(ro.w) < kInf;
+    const bool fin_d = fabsf(rdv.x) < kInf && fabsf(rdv.y) < kInf && fabsf(rdv.z) < kInf;
+    return fin_o && fin_d && a >= 1.17549435e-38f && a < kInf;                   // (NaN fails every comparison)
+}
+// (element indices into the caller's lists are 64-bit: a list may hold up to 2^32 - 1 rays, and 2 * index or 3 * index does not fit 32 bits)
+DEVI void store_ray_miss(Float4* __restrict__ hits, uint32_t idx, uint32_t flags) {
+    hits += 3ull * idx;
+    hits[0] = Float4{kInf, __uint_as_float(0xFFFFFFFFu), __uint_as_float(0xFFFFFFFFu), __uint_as_float(flags)};
+    hits[1] = Float4{0.f, 0.f, 0.f, 0.f};
+    hits[2] = Float4{0.f, 0.f, 0.f, 0.f};
+}
+__global__ void __launch_bounds__(kRaysImportThreads) k_rays_import(const Float4* __restrict__ rays, uint32_t first, uint32_t n, PoolDev pool, uint32_t queue_cap,
+                                                                     uint32_t* __restrict__ counts, Float4* __restrict__ hits, unsigned long long* __restrict__ counters) {
+    __shared__ uint32_t s_scan[kRaysImportThreads / 64 + 1];
+    const uint32_t i = blockIdx.x * kRaysImportThreads + threadIdx.x, q = blockIdx.x & (kQueues - 1u);
+    Float4 ro = Float4{0.f, 0.f, 0.f, 0.f}, rdv = Float4{0.f, 0.f, 0.f, 0.f};
+    const bool mine = i < n;
+    if (mine) { const Float4* r = rays + 2ull * (first + i); ro = r[0]; rdv = r[1]; }
+    const bool valid = mine && query_ray_valid(ro, rdv);
+    const uint32_t slot = block_alloc(valid, counts + q * kQStride, s_scan);      // every thread of the workgroup calls it
+    const bool stored = valid && slot < queue_cap;
+    if (stored) {
+        const uint32_t at = q * queue_cap + slot;
+        pool.ray_o[at] = ro;
+        pool.ray_d[at] = Float4{rdv.x, rdv.y, rdv.z, __uint_as_float(0u)};
+        pool.s0[at] = Float4{rdv.w, 0.f, 0.f, __uint_as_float(first + i)};
+        pool.sd[at] = 0u;
+    }
+    if (mine && !stored) store_ray_miss(hits, first + i, kRayHitInvalid);
+    const uint64_t m = __ballot(stored);
+    if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(&counters[CTR_SEGMENTS], (unsigned long long)__popcll(m));
+}
+
+// k_rays_export: (ray, hit = (t, primitive)) of every pool slot -> one RtRayHit at the ray's index. The HitRecord is rebuilt with the
+// arithmetic of shade_segment's block "rebuild the HitRecord" — restated here, not shared, because that function's code must not move (its
+// register counts sit at occupancy boundaries; DESIGN.md section 2 has its miscompile) — with two differences: u, v of a sphere are always
+// computed, and a medium cannot occur (the host refuses such scenes). tests/test_gpu_rays.py::test_export_agrees_with_shade keeps the two in
+// step. The tables are read where the upload put them (HBM / L2): one pass over the pool, nothing staged.
+template <uint32_t FEAT>
+__global__ void __launch_bounds__(256) k_rays_export(SceneDev sc, RaySrcDev src, PoolDev pool, uint32_t queue_cap, const uint32_t* __restrict__ counts,
+                                                      Float4* __restrict__ hits) {
+    const uint32_t q = blockIdx.x & (kQueues - 1u), i = (blockIdx.x >> kQShift) * blockDim.x + threadIdx.x;
+    if (i >= min(counts[q * kQStride], queue_cap)) return;
+    const uint32_t at = q * queue_cap + i;
+    const Float4 ro = pool.ray_o[at], rdv = pool.ray_d[at], s0 = pool.s0[at];
+    const uint2 hit = pool.hit[at];
+    const uint32_t ray = __float_as_uint(s0.w);
+    const float t = __uint_as_float(hit.x), t_max = s0.x, tm = ro.w;
+    const bool limited = t_max > 0.f && t_max < kInf;                             // (t_max <= 0, +inf or NaN: no limit)
+    if (hit.y == rtd::HIT_NONE || (limited && t > t_max)) { store_ray_miss(hits, ray, 0u); return; }
+    const V3 o = v3(ro.x, ro.y, ro.z), d = v3(rdv.x, rdv.y, rdv.z);
+    // ---- rebuild the HitRecord (hittable.rs:11-19) from (ray, t, primitive): shade_segment's block ----
+    const uint32_t type = hit.y >> 28, idx = hit.y & rtd::LEAF_MAX_FIRST;
+    const uint32_t meta = type == rtd::LT_SPHERE ? sc.sphere_meta[idx]
+                        : ((FEAT & F_RECT) && type == rtd::LT_RECT) ? sc.rect_meta[idx]
+                        : ((FEAT & F_MOVING) && type == rtd::LT_MOVING) ? sc.moving_meta[idx]
+                        : ((FEAT & F_TRI) && type == rtd::LT_TRI) ? sc.tri_meta[idx] : 0u;
+    const uint32_t hittable = type == rtd::LT_SPHERE ? src.sphere[idx]
+                            : ((FEAT & F_RECT) && type == rtd::LT_RECT) ? src.rect[idx]
+                            : ((FEAT & F_MOVING) && type == rtd::LT_MOVING) ? src.moving[idx]
+                            : ((FEAT & F_TRI) && type == rtd::LT_TRI) ? src.tri[idx] : 0xFFFFFFFFu;
+    const uint32_t wrap = (FEAT & F_XFORM) ? (meta >> 22) : 0u;
+    rtd::Wrap W{};
+    if ((FEAT & F_XFORM) && wrap) W = sc.wraps[wrap];
+    const uint32_t xf = W.xform;
+    V3 ol = o, dl = d;
+    if ((FEAT & F_XFORM) && xf) xform_ray(sc.xforms[xf], o, d, ol, dl);
+    V3 p, n, outward; float hu = 0.f, hv = 0.f; bool ff;
+    if (type == rtd::LT_SPHERE) {
+        const Float4 sp = sc.spheres[idx];
+        p = ol + dl * t;                                            // sphere.rs:59
+        outward = (p - v3(sp.x, sp.y, sp.z)) / sp.w;                // :60
+        sphere_uv(outward, hu, hv);                                 // :62
+    } else if ((FEAT & F_RECT) && type == rtd::LT_RECT) {
+        const Float4 r0 = sc.rects[2 * idx], r1 = sc.rects[2 * idx + 1];
+        const int kaxis = (int)r1.y & 3; const int ia = kaxis == 0 ? 1 : 0, ib = kaxis == 2 ? 1 : 2;
+        p = ol + dl * t;                                            // aarect.rs:46
+        const float a = comp(p, ia), b = comp(p, ib);
+        hu = fdiv(a - r0.x, r0.y - r0.x); hv = fdiv(b - r0.z, r0.w - r0.z);   // :41-42
+        if (kaxis == 0) p.x = r1.x; else if (kaxis == 1) p.y = r1.x; else p.z = r1.x;   // on the plane exactly
+        outward = v3(kaxis == 0 ? 1.f : 0.f, kaxis == 1 ? 1.f : 0.f, kaxis == 2 ? 1.f : 0.f);
+    } else if ((FEAT & F_MOVING) && type == rtd::LT_MOVING) {
+        const Float4 m0 = sc.moving[3 * idx], m1 = sc.moving[3 * idx + 1], m2 = sc.moving[3 * idx + 2];
+        p = ol + dl * t;
+        outward = (p - moving_center(m0, m1, m2, tm)) / m0.w;       // moving_sphere.rs:58 (u,v not set: 0)
+    } else if ((FEAT & F_TRI) && type == rtd::LT_TRI) {
+        const V3 v0 = f4xyz(sc.tris[3 * idx]), v1 = f4xyz(sc.tris[3 * idx + 1]), v2 = f4xyz(sc.tris[3 * idx + 2]);
+        float tt, bu = 0.f, bv = 0.f;
+        tri_hit(ol, dl, v0, v1, v2, -kInf, kInf, tt, bu, bv);
+        hu = bu; hv = bv;
+        p = ol + dl * t;
+        outward = unit(cross(v1 - v0, v2 - v0));
+    } else { store_ray_miss(hits, ray, 0u); return; }               // a primitive kind this instance was not compiled for: cannot occur (pick_variant)
+    ff = dot(dl, outward) < 0.f;                                    // set_face_normal, hittable.rs:41-48
+    n = ff ? outward : -outward;
+    if ((FEAT & F_XFORM) && wrap) {
+        if (xf) p = xform_point_back(sc.xforms[xf], p);
+        // the wrappers from the innermost out; dk: the ray direction each wrapper hands to its child (hittable.rs:154-155)
+        V3 dk[rtd::MAX_WRAP_OPS + 1];
+        dk[0] = d;
+#pragma unroll
+        for (uint32_t k = 0; k < rtd::MAX_WRAP_OPS; ++k) {
+            const float sn = W.op[k].sin_t, cs = W.op[k].cos_t;
+            const V3 qv = dk[k];
+            dk[k + 1] = (k < W.n_ops && W.op[k].kind == rtd::WO_ROTATE_Y) ? v3(cs * qv.x - sn * qv.z, qv.y, sn * qv.x + cs * qv.z) : qv;
+        }
+#pragma unroll
+        for (int k = (int)rtd::MAX_WRAP_OPS - 1; k >= 0; --k) {
+            if ((uint32_t)k < W.n_ops) {
+                const uint32_t kind = W.op[k].kind;
+                if (kind == rtd::WO_FLIP_FACE) ff = !ff;                                   // hittable.rs:199
+                else {
+                    if (kind == rtd::WO_ROTATE_Y) {                                        // hittable.rs:169-170
+                        const float sn = W.op[k].sin_t, cs = W.op[k].cos_t;
+                        n = v3(cs * n.x + sn * n.z, n.y, -sn * n.x + cs * n.z);
+                    }
+                    ff = dot(dk[k + 1], n) < 0.f;                                          // hittable.rs:82-83 / 173
+                    n = ff ? n : -n;
+                }
+            }
+        }
+    }
+    // 48 bytes, three 16-byte stores
+    hits += 3ull * ray;
+    hits[0] = Float4{t, __uint_as_float(hittable), __uint_as_float(meta & rtd::META_MAT_MASK), __uint_as_float(kRayHitHit | (ff ? kRayHitFrontFace : 0u))};
+    hits[1] = Float4{p.x, p.y, p.z, hu};
+    hits[2] = Float4{n.x, n.y, n.z, hv};
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 static thread_local const char* g_launch_note = nullptr;
@@ -2367,6 +2511,26 @@ hipError_t launch_resolve_list(const RenderDev& rd, float* out, hipStream_t stre
     const uint32_t blocks = (rd.n_list + 255u) / 256u;
     if (blocks == 0u) return hipSuccess;
     hipLaunchKernelGGL(k_resolve_list, dim3(blocks), dim3(256), 0, stream, rd, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_rays_import(const void* rays, uint32_t first, uint32_t n, const PoolDev& pool, uint32_t queue_cap, uint32_t* counts, void* hits,
+                              unsigned long long* counters, hipStream_t stream) {
+    const uint32_t blocks = (n + kRaysImportThreads - 1u) / kRaysImportThreads;
+    if (blocks == 0u) return hipSuccess;
+    if ((uint64_t)n > (uint64_t)kQueues * queue_cap || (queue_cap & 511u) != 0u) return hipErrorInvalidValue;   // (k_rays_import: a slot is < queue_cap)
+    hipLaunchKernelGGL(k_rays_import, dim3(blocks), dim3(kRaysImportThreads), 0, stream, (const Float4*)rays, first, n, pool, queue_cap, counts, (Float4*)hits, counters);
+    return hipGetLastError();
+}
+
+hipError_t launch_rays_export(const LaunchCfg& cfg, const SceneDev& sc, const RaySrcDev& src, const PoolDev& pool, uint32_t queue_cap, uint32_t max_count,
+                              const uint32_t* counts, void* hits, hipStream_t stream) {
+    const uint32_t blocks = kQueues * ((std::min(max_count, queue_cap) + 255u) / 256u);   // max_count = upper bound of the rays in ONE queue
+    if (blocks == 0u) return hipSuccess;
+    const uint32_t v = pick_variant(cfg.features);
+#define RT_EXP(F) hipLaunchKernelGGL((k_rays_export<F>), dim3(blocks), dim3(256), 0, stream, sc, src, pool, queue_cap, counts, (Float4*)hits)
+    if (v == 0u) RT_EXP(0u); else if (v == kVariantMesh) RT_EXP(kVariantMesh); else if (v == kVariantBox) RT_EXP(kVariantBox); else RT_EXP(F_ALL);
+#undef RT_EXP
     return hipGetLastError();
 }
 

@@ -570,6 +570,7 @@ int rti::scene_image_upload(RtCtx* ctx, const SceneImage& im, RtScene** out_scen
     up(s->rects, cs.rects); up(s->rect_meta, cs.rect_meta); up(s->tris, cs.tris); up(s->tri_meta, cs.tri_meta); up(s->boxes, cs.boxes); up(s->media, cs.media);
     up(s->xforms, cs.xforms); up(s->wraps, cs.wraps); up(s->mat_a, cs.mat_a); up(s->mat_b, cs.mat_b); up(s->textures, cs.textures); up(s->perlins, cs.perlins);
     up(s->images, cs.images); up(s->image_bytes, cs.image_bytes); up(s->lights, cs.lights);
+    up(s->sphere_src, cs.sphere_src); up(s->moving_src, cs.moving_src); up(s->rect_src, cs.rect_src); up(s->tri_src, cs.tri_src);
     // a small scene whose shading tables are not staged in LDS: the material record of every sphere by SPHERE index (one dependent load fewer in
     // k_shade: book-1 waits ~700 cycles of a wave's ~20 000 for the material's record after the sphere's)
     std::vector<rtd::Float4> sphere_ma; std::vector<uint32_t> sphere_mb;
@@ -613,6 +614,7 @@ int rti::scene_image_upload(RtCtx* ctx, const SceneImage& im, RtScene** out_scen
     d.eb_rect_stride = im.eb_rect_stride; d.eb_rects = eb[0]; d.eb_moving = eb[1]; d.eb_xforms = eb[2]; d.eb_media = eb[3]; d.eb_boxes = eb[4];
     d.sb_perlin_only = im.perlin_only;
     d.sb_mat_a = sb[6]; d.sb_mat_b = sb[7]; d.sb_xforms = sb[8]; d.sb_wraps = sb[9]; d.sb_lights = sb[10]; d.sb_textures = sb[11];
+    s->src = rtk::RaySrcDev{(const uint32_t*)s->sphere_src.p, (const uint32_t*)s->moving_src.p, (const uint32_t*)s->rect_src.p, (const uint32_t*)s->tri_src.p};
     s->features = im.features;
     s->in_lds = im.in_lds; s->lds_bytes = lds_scene_bytes(cs);
     s->bg_mode = cs.background_mode; for (int i = 0; i < 3; ++i) s->bg[i] = cs.background[i];
@@ -651,7 +653,8 @@ int rt_scene_destroy(RtCtx* ctx, RtScene* s) {
     if (!s) return RT_OK;
     if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
     DevBuf* all[] = {&s->nodes, &s->spheres, &s->sphere_meta, &s->moving, &s->moving_meta, &s->rects, &s->rect_meta, &s->tris, &s->tri_meta, &s->boxes, &s->media,
-                     &s->xforms, &s->wraps, &s->mat_a, &s->mat_b, &s->textures, &s->perlins, &s->images, &s->image_bytes, &s->lights, &s->top_nodes, &s->shade_blob, &s->ext_blob, &s->wide, &s->sphere_mat_a, &s->sphere_mat_b};
+                     &s->xforms, &s->wraps, &s->mat_a, &s->mat_b, &s->textures, &s->perlins, &s->images, &s->image_bytes, &s->lights, &s->top_nodes, &s->shade_blob, &s->ext_blob, &s->wide, &s->sphere_mat_a, &s->sphere_mat_b,
+                     &s->sphere_src, &s->moving_src, &s->rect_src, &s->tri_src};
     for (DevBuf* b : all) b->release();
     delete s;
     return RT_OK;
@@ -1063,6 +1066,143 @@ int rt_render(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtPar
     if (!prm) return validate_params(ctx, prm);
     const RtPassOptions one = one_shot(prm);
     return rt_render_pass(ctx, scene, cam, prm, &one, rgb_sum_host, nullptr, stats);
+}
+
+// ---- ray queries (include/rt_hip.h): caller's rays through the traversal kernels of a render, one RtRayHit each ---------------------------
+static_assert(sizeof(RtRay) == 32 && sizeof(RtRayHit) == 48 && sizeof(RtRayQueryOptions) == 16, "ray query records: 32, 48 and 16 bytes");
+static int check_ray_query(RtCtx* ctx, const RtRayQueryOptions* o, uint64_t n_rays) {
+    if (o) {
+        if (o->struct_bytes < sizeof(RtRayQueryOptions) || o->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtRayQueryOptions.struct_bytes is not set (sizeof(RtRayQueryOptions))");
+        if (o->flags & ~(uint32_t)RT_FLAG_TIMING) return set_err(ctx, RT_ERR_INVALID, "RtRayQueryOptions.flags holds an unknown bit (known: RT_FLAG_TIMING)");
+    }
+    if (n_rays > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "n_rays must be < 2^32 (split the list)");
+    return RT_OK;
+}
+int rt_ray_query_check(const RtRayQueryOptions* options, uint64_t n_rays) { return check_ray_query(nullptr, options, n_rays); }
+
+// The chunk loop: import -> k_extend (the scene's own launch configuration, every layout) -> export, all on the context's stream; the host
+// waits once, at the end. A chunk's kernels read its queue sizes from device memory, so nothing comes back to the host in between.
+static int trace_rays_impl(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* opt, const void* d_rays, uint64_t n_rays, void* d_hits, RtStats* stats) {
+    using clk = std::chrono::steady_clock;
+    const auto t_begin = clk::now();
+    const bool timing = opt && (opt->flags & RT_FLAG_TIMING) != 0u;
+    // the pool, by the renderer's rule (render_impl): every ray in flight, up to 2^28 and to 70 % of the free memory; whole 512-ray groups per queue
+    const size_t rec[5] = {16, 16, 8, 16, 4};   // ray_o ray_d hit s0 sd
+    size_t slot_bytes = 0; for (size_t b : rec) slot_bytes += b;
+    uint32_t P = opt && opt->pool_slots ? opt->pool_slots : (1u << 28);
+    P = (uint32_t)std::min<uint64_t>(P, n_rays);
+    if (!(opt && opt->pool_slots)) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            size_t held = 0; for (int a = 0; a < 5; ++a) held += ctx->pool[0][a].bytes;
+            const size_t budget = (free_b + held) * 7 / 10;
+            while (P > (1u << 20) && (size_t)P * slot_bytes > budget) P >>= 1;
+        }
+    }
+    constexpr uint32_t kGrain = 512u * rtk::kQueues;
+    P = std::max<uint32_t>(kGrain, (uint32_t)std::min<uint64_t>(((uint64_t)P + kGrain - 1u) / kGrain * kGrain, 0xFFFFF000ull));
+    const uint32_t queue_cap = P / rtk::kQueues;
+    rtk::PoolDev pd{};
+    for (int a = 0; a < 5; ++a) HIP_TRY(ctx, ctx->pool[0][a].ensure((size_t)P * rec[a]));
+    pd.ray_o = (rtd::Float4*)ctx->pool[0][0].p; pd.ray_d = (rtd::Float4*)ctx->pool[0][1].p; pd.hit = (uint2*)ctx->pool[0][2].p;
+    pd.s0 = (rtd::Float4*)ctx->pool[0][3].p; pd.sd = (uint32_t*)ctx->pool[0][4].p; pd.s1 = nullptr;
+    // the render's counter block (render_impl): line 1 queue heads, line 2 the queues' sizes, line 3 what k_extend zeroes for a k_shade that never runs here
+    constexpr size_t kLine = 128, kQ = rtk::kQueues;
+    const size_t counter_bytes = 4 * kQ * kLine + sizeof(unsigned long long) * 16;
+    HIP_TRY(ctx, ctx->counters.ensure(counter_bytes));
+    char* cbase = (char*)ctx->counters.p;
+    uint32_t* c_head = (uint32_t*)(cbase + 1 * kQ * kLine);
+    uint32_t* c_count = (uint32_t*)(cbase + 2 * kQ * kLine);
+    uint32_t* c_other = (uint32_t*)(cbase + 3 * kQ * kLine);
+    unsigned long long* c64 = (unsigned long long*)(cbase + 4 * kQ * kLine);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, counter_bytes, ctx->stream));
+
+    rtk::RenderDev rd{};                     // a walk needs the queue geometry only; first_in_shade = 0: the record's time slot is the ray's time
+    rd.queue_cap = queue_cap; rd.q_lo = 0u; rd.q_n = rtk::kQueues; rd.q_shift = rtk::kQShift;
+    rd.div_nblocks = rtk::make_fastdiv(1u); rd.n_blocks = 1u;
+    rtk::LaunchCfg cfg{};
+    uint32_t extend_geometry[2] = {0u, 0u};
+    cfg.n_cu = (uint32_t)ctx->n_cu; cfg.extend_geometry = extend_geometry; cfg.features = scene->features; cfg.scene_in_lds = scene->in_lds;
+
+    size_t ev_used = 0;
+    auto next_event = [&](hipEvent_t& ev) -> hipError_t {
+        if (ev_used == ctx->events.size()) { hipEvent_t e; hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; ctx->events.push_back(e); }
+        ev = ctx->events[ev_used++];
+        return hipEventRecord(ev, ctx->stream);
+    };
+    struct Span { hipEvent_t a, b; int kind; };
+    std::vector<Span> spans;
+    uint32_t launched = 0u;
+    for (uint64_t first = 0; first < n_rays; first += P) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(P, n_rays - first);
+        hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr, ed = nullptr;
+        if (first != 0u) HIP_TRY(ctx, hipMemsetAsync(cbase, 0, 4 * kQ * kLine, ctx->stream));     // heads and sizes of the chunk before (the 64-bit statistics stay)
+        if (timing) HIP_TRY(ctx, next_event(ea));
+        LAUNCH_TRY(rtk::launch_rays_import(d_rays, (uint32_t)first, n, pd, queue_cap, c_count, d_hits, c64, ctx->stream));
+        if (timing) HIP_TRY(ctx, next_event(eb));
+        cfg.max_rays = n;
+        LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd, rd, c_count, c_head, c_other, c64, false, ctx->stream));
+        if (timing) HIP_TRY(ctx, next_event(ec));
+        // a queue holds at most its share of the chunk's 512-ray groups
+        const uint32_t per_queue = std::min<uint32_t>(queue_cap, ((n + 511u) / 512u + rtk::kQueues - 1u) / rtk::kQueues * 512u);
+        LAUNCH_TRY(rtk::launch_rays_export(cfg, scene->dev, scene->src, pd, queue_cap, per_queue, c_count, d_hits, ctx->stream));
+        if (timing) { HIP_TRY(ctx, next_event(ed)); spans.push_back({ea, eb, 2}); spans.push_back({eb, ec, 0}); spans.push_back({ec, ed, 2}); }
+        ++launched;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, c64, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) {
+        for (const Span& s : spans) {
+            float ms = 0.f; if (hipEventElapsedTime(&ms, s.a, s.b) != hipSuccess) continue;
+            if (s.kind == 0) stats->extend_ms += ms; else stats->other_ms += ms;
+        }
+        stats->samples = stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];
+        stats->debug[6] = extend_geometry[0]; stats->debug[7] = extend_geometry[1];
+        stats->iterations = launched; stats->extend_launches = launched; stats->pool_slots = P; stats->n_devices = 1u; stats->lds_top_nodes = scene->dev.n_top;
+        stats->scene_nodes = scene->n_nodes; stats->scene_prims = scene->n_prims; stats->scene_bytes = scene->bytes; stats->bvh_in_lds = scene->in_lds ? 1u : 0u;
+        stats->render_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
+    }
+    return RT_OK;
+}
+
+// the argument checks of both variants: a refused call has written nothing
+static int trace_rays_refuse(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const void* rays, uint64_t n_rays, const void* hits, bool device) {
+    if (!scene) return set_err(ctx, RT_ERR_INVALID, "scene is null");
+    const int v = check_ray_query(ctx, options, n_rays); if (v != RT_OK) return v;
+    if (scene->features & rtk::F_MEDIUM)
+        return set_err(ctx, RT_ERR_UNSUPPORTED, "ray queries: the scene holds a ConstantMedium, whose hit is a random draw keyed by a path; a bare ray has none");
+    if (n_rays != 0u && (!rays || !hits)) return set_err(ctx, RT_ERR_INVALID, "rays / hits is null");
+    if (device && (((uintptr_t)rays | (uintptr_t)hits) & 15u)) return set_err(ctx, RT_ERR_INVALID, "rays / hits must be 16-byte aligned");
+    return RT_OK;
+}
+
+int rt_trace_rays_device(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const void* rays_device, uint64_t n_rays, void* hits_device, RtStats* stats) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    const int v = trace_rays_refuse(ctx, scene, options, rays_device, n_rays, hits_device, true); if (v != RT_OK) return v;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n_rays == 0u) return RT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int r = trace_rays_impl(ctx, scene, options, rays_device, n_rays, hits_device, stats);
+    if (r != RT_OK) { const std::string keep = ctx->err; (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); ctx->err = keep; g_last_error = keep; }
+    return r;
+}
+
+int rt_trace_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const RtRay* rays_host, uint64_t n_rays, RtRayHit* hits_host, RtStats* stats) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    const int v = trace_rays_refuse(ctx, scene, options, rays_host, n_rays, hits_host, false); if (v != RT_OK) return v;   // (host buffers are copied: no alignment asked)
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n_rays == 0u) return RT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(ctx, ctx->rays_tmp.ensure((size_t)n_rays * sizeof(RtRay)));
+    HIP_TRY(ctx, ctx->hits_tmp.ensure((size_t)n_rays * sizeof(RtRayHit)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->rays_tmp.p, rays_host, (size_t)n_rays * sizeof(RtRay), hipMemcpyHostToDevice, ctx->stream));
+    const int r = rt_trace_rays_device(ctx, scene, options, ctx->rays_tmp.p, n_rays, ctx->hits_tmp.p, stats);
+    if (r != RT_OK) return r;
+    HIP_TRY(ctx, hipMemcpyAsync(hits_host, ctx->hits_tmp.p, (size_t)n_rays * sizeof(RtRayHit), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT_OK;
 }
 
 int rt_untile(const RtParams* p, const float* gathered, float* rgb_sum) { return untile_host<float>(p, gathered, rgb_sum); }

@@ -54,6 +54,7 @@ struct RtCtx {
     hipEvent_t ev_gather[2] = {nullptr, nullptr}; // brackets the exchange (RtStats.gather_ms); made at the first gather, kept
     rti::DevBuf list_map;                        // adaptive sampling: output slot -> list index of a list pass (rt_render_pass_pixels_device)
     rti::DevBuf sel_masks, sel_offsets, adaptive_word;   // rt_adaptive_select's wave ballots and their scan; the list check's verdict / the list's length
+    rti::OwnedDevBuf rays_tmp, hits_tmp;         // rt_trace_rays (host variant): the caller's rays and hits on their way to and from the device
     rti::OwnedDevBuf denoise_planes;             // rt_denoise_device: per-pixel mean and variance of the mean, three float2 planes (denoise.hip)
     uint32_t fail_renders = 0;                   // rt_test_fail_next_renders: renders still to fail (fault injection for the failure-path tests)
 };
@@ -61,7 +62,9 @@ struct RtCtx {
 struct RtScene {
     rti::DevBuf nodes, spheres, sphere_meta, moving, moving_meta, rects, rect_meta, tris, tri_meta, boxes, media, xforms, wraps, mat_a, mat_b, textures, perlins, images,
         image_bytes, lights, top_nodes, shade_blob, ext_blob, wide, sphere_mat_a, sphere_mat_b;
+    rti::DevBuf sphere_src, moving_src, rect_src, tri_src;   // ray queries: the RtHittable record of every primitive (no render kernel reads them)
     rtk::SceneDev dev{};
+    rtk::RaySrcDev src{};
     uint32_t features = 0; bool in_lds = false;
     uint32_t first_id = 0; float first_prim[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the ONE sphere or rect every walk tests first (hit id; centre + radius, or the rect's two records), first_id = 0: none or several
     int bg_mode = 0; float bg[3] = {0, 0, 0};

@@ -178,21 +178,21 @@ struct Compiler {
         out.nodes.push_back(n);
         out.nodes.back().skip = (uint32_t)out.nodes.size();
     }
-    uint32_t add_rect(int kaxis, double a0, double a1, double b0, double b1, double k, uint32_t meta) {
+    uint32_t add_rect(int kaxis, double a0, double a1, double b0, double b1, double k, uint32_t meta, int src) {
         out.rects.push_back(rtd::Float4{(float)a0, (float)a1, (float)b0, (float)b1});
         out.rects.push_back(rtd::Float4{(float)k, (float)kaxis, 0.f, 0.f});
-        out.rect_meta.push_back(meta);
+        out.rect_meta.push_back(meta); out.rect_src.push_back((uint32_t)src);
         return (uint32_t)out.rect_meta.size() - 1;
     }
     // boxes.rs:17-74 — the six sides in the reference's order
-    uint32_t add_box_rects(const double* p, uint32_t meta) {
+    uint32_t add_box_rects(const double* p, uint32_t meta, int src) {
         const double x0 = p[0], y0 = p[1], z0 = p[2], x1 = p[3], y1 = p[4], z1 = p[5];
-        const uint32_t first = add_rect(2, x0, x1, y0, y1, z1, meta);
-        add_rect(2, x0, x1, y0, y1, z0, meta);
-        add_rect(1, x0, x1, z0, z1, y1, meta);
-        add_rect(1, x0, x1, z0, z1, y0, meta);
-        add_rect(0, y0, y1, z0, z1, x1, meta);
-        add_rect(0, y0, y1, z0, z1, x0, meta);
+        const uint32_t first = add_rect(2, x0, x1, y0, y1, z1, meta, src);
+        add_rect(2, x0, x1, y0, y1, z0, meta, src);
+        add_rect(1, x0, x1, z0, z1, y1, meta, src);
+        add_rect(1, x0, x1, z0, z1, y0, meta, src);
+        add_rect(0, y0, y1, z0, z1, x1, meta, src);
+        add_rect(0, y0, y1, z0, z1, x0, meta, src);
         return first;
     }
 
@@ -228,20 +228,20 @@ struct Compiler {
         switch (h.kind) {
         case RT_HIT_SPHERE:
             out.spheres.push_back(rtd::Float4{(float)p[0], (float)p[1], (float)p[2], (float)p[3]});
-            out.sphere_meta.push_back(meta_for(h, ctx));
+            out.sphere_meta.push_back(meta_for(h, ctx)); out.sphere_src.push_back((uint32_t)id);
             if (!to_prologue) push_leaf_node(rtd::LT_SPHERE, (uint32_t)out.sphere_meta.size() - 1, 1);     // (else: emit_bvh's first_leaf names it)
             break;
         case RT_HIT_MOVING_SPHERE:
             out.moving.push_back(rtd::Float4{(float)p[0], (float)p[1], (float)p[2], (float)p[8]});
             out.moving.push_back(rtd::Float4{(float)p[3], (float)p[4], (float)p[5], (float)p[6]});
             out.moving.push_back(rtd::Float4{(float)p[7], 0.f, 0.f, 0.f});
-            out.moving_meta.push_back(meta_for(h, ctx));
+            out.moving_meta.push_back(meta_for(h, ctx)); out.moving_src.push_back((uint32_t)id);
             if (to_prologue) out.prologue.push_back(rtd::make_leaf(rtd::LT_MOVING, (uint32_t)out.moving_meta.size() - 1, 1));
             else push_leaf_node(rtd::LT_MOVING, (uint32_t)out.moving_meta.size() - 1, 1);
             break;
         case RT_HIT_XY_RECT: case RT_HIT_XZ_RECT: case RT_HIT_YZ_RECT: {
             const int kaxis = h.kind == RT_HIT_XY_RECT ? 2 : (h.kind == RT_HIT_XZ_RECT ? 1 : 0);
-            const uint32_t idx = add_rect(kaxis, p[0], p[1], p[2], p[3], p[4], meta_for(h, ctx));
+            const uint32_t idx = add_rect(kaxis, p[0], p[1], p[2], p[3], p[4], meta_for(h, ctx), id);
             if (!to_prologue) push_leaf_node(rtd::LT_RECT, idx, 1);                                        // (else: emit_bvh's first_leaf names it)
             break;
         }
@@ -249,13 +249,13 @@ struct Compiler {
             out.tris.push_back(rtd::Float4{(float)p[0], (float)p[1], (float)p[2], 0.f});
             out.tris.push_back(rtd::Float4{(float)p[3], (float)p[4], (float)p[5], 0.f});
             out.tris.push_back(rtd::Float4{(float)p[6], (float)p[7], (float)p[8], 0.f});
-            out.tri_meta.push_back(meta_for(h, ctx));
+            out.tri_meta.push_back(meta_for(h, ctx)); out.tri_src.push_back((uint32_t)id);
             push_leaf_node(rtd::LT_TRI, (uint32_t)out.tri_meta.size() - 1, 1);
             break;
         case RT_HIT_BOX: {
             // a primitive kind of its own for the walk: one 32-byte record (the six bounds + where its sides start in rects[]), tested in
             // straight-line code; the sides themselves stay rects — what a hit is shaded from, and what the hit id names
-            const uint32_t first = add_box_rects(p, meta_for(h, ctx));
+            const uint32_t first = add_box_rects(p, meta_for(h, ctx), id);
             uint32_t fbits = first; float ff; std::memcpy(&ff, &fbits, 4);
             out.boxes.push_back(rtd::Float4{(float)p[0], (float)p[3], (float)p[1], (float)p[4]});
             out.boxes.push_back(rtd::Float4{(float)p[2], (float)p[5], ff, 0.f});
@@ -416,10 +416,10 @@ struct Compiler {
         m.boundary_xform = intern_xform(c);
         if (b->kind == RT_HIT_SPHERE) {
             out.spheres.push_back(rtd::Float4{(float)b->p[0], (float)b->p[1], (float)b->p[2], (float)b->p[3]});
-            out.sphere_meta.push_back(0);
+            out.sphere_meta.push_back(0); out.sphere_src.push_back((uint32_t)inner);
             m.boundary_type = rtd::LT_SPHERE; m.boundary_first = (uint32_t)out.sphere_meta.size() - 1; m.boundary_count = 1;
         } else if (b->kind == RT_HIT_BOX) {
-            m.boundary_type = rtd::LT_RECT; m.boundary_first = add_box_rects(b->p, 0); m.boundary_count = 6;
+            m.boundary_type = rtd::LT_RECT; m.boundary_first = add_box_rects(b->p, 0, inner); m.boundary_count = 6;
         } else { out.error = "constant medium boundary must be a sphere or a box (optionally under Translate/RotateY)"; return; }
         if (h.p[0] == 0.0) { fail("constant medium with zero density"); return; }
         m.neg_inv_density = (float)(-1.0 / h.p[0]);   // constant_medium.rs:25

@@ -14,6 +14,9 @@ struct CompiledScene {
     std::vector<rtd::Float4> moving;   std::vector<uint32_t> moving_meta;    // 3 per primitive
     std::vector<rtd::Float4> rects;    std::vector<uint32_t> rect_meta;      // 2 per primitive
     std::vector<rtd::Float4> tris;     std::vector<uint32_t> tri_meta;       // 3 per primitive
+    // source ids: the RtHittable record each primitive came from (a Box's record for its six sides), one u32 per primitive and kind. Ray
+    // queries report them (rt_hip.h RtRayHit::hittable); no render kernel reads them.
+    std::vector<uint32_t> sphere_src, moving_src, rect_src, tri_src;
     std::vector<rtd::Float4> boxes;                                          // 2 per Box (device_types.h): bounds + index of its first side in rects
     std::vector<rtd::Medium> media;
     std::vector<rtd::Xform> xforms;                                          // [0] = identity

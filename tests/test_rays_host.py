@@ -1,0 +1,137 @@
+"""Ray queries without a GPU (include/rt_hip.h, "ray queries"): the struct mirrors against a compiled probe of the header,
+rt_ray_query_check's refusals, the source-id tables of the scene compiler as far as the host can see them, and — with the CPU checker
+alone — that the ray sets the GPU test compares are decidable enough."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rays as R  # noqa: E402
+
+
+def test_ray_structs_match_the_header(pkg, tmp_path):
+    A = pkg._abi
+    body = ""
+    for name in ("RtRay", "RtRayHit", "RtRayQueryOptions"):
+        body += f'printf("{name} %zu\\n", sizeof({name}));'
+        body += "".join(f'printf("{name}.{f} %zu\\n", offsetof({name}, {f}));' for f, _ in getattr(A, name)._fields_)
+    body += 'printf("flags %u %u %u\\n", (unsigned)RT_RAYHIT_HIT, (unsigned)RT_RAYHIT_FRONT_FACE, (unsigned)RT_RAYHIT_INVALID_RAY);'
+    src = tmp_path / "rq.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "rt_hip.h"\nint main(void){' + body + "return 0;}")
+    exe = tmp_path / "rq"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = dict(line.split(None, 1) for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    for name, size, dt in (("RtRay", 32, pkg.RAY_DTYPE), ("RtRayHit", 48, pkg.RAYHIT_DTYPE), ("RtRayQueryOptions", 16, None)):
+        T = getattr(A, name)
+        assert int(got[name]) == C.sizeof(T) == size, name
+        for f, _ in T._fields_:
+            assert int(got[f"{name}.{f}"]) == getattr(T, f).offset, (name, f)
+            if dt is not None:
+                assert dt.fields[f][1] == getattr(T, f).offset, (name, f)
+        if dt is not None:
+            assert dt.itemsize == size
+    assert got["flags"].split() == [str(A.RT_RAYHIT_HIT), str(A.RT_RAYHIT_FRONT_FACE), str(A.RT_RAYHIT_INVALID_RAY)] == ["1", "2", "4"]
+    assert A.RT_ABI_VERSION == 3 == pkg.lib().rt_abi_version()
+
+
+def test_ray_query_check(pkg):
+    A, lib = pkg._abi, pkg.lib()
+    assert lib.rt_ray_query_check(None, 0) == A.RT_OK
+    assert lib.rt_ray_query_check(None, (1 << 32) - 1) == A.RT_OK
+    good = pkg.ray_query_options(flags=A.RT_FLAG_TIMING, pool_slots=4096)
+    assert lib.rt_ray_query_check(C.byref(good), 1000) == A.RT_OK
+    pkg.ray_query_check(good, 5)
+
+    def opt(size=16, flags=0):
+        return A.RtRayQueryOptions(size, flags, 0, 0)
+    for o, n, word in ((opt(size=0), 1, b"struct_bytes"), (opt(size=8), 1, b"struct_bytes"), (opt(flags=1 << 9), 1, b"unknown"),
+                       (opt(flags=A.RT_FLAG_COUNTERS), 1, b"unknown"), (opt(), 1 << 32, b"2^32"), (None, 1 << 40, b"2^32")):
+        assert lib.rt_ray_query_check(C.byref(o) if o is not None else None, n) == A.RT_ERR_INVALID, word
+        assert word in lib.rt_last_error(None), (word, lib.rt_last_error(None))
+    with pytest.raises(pkg.RtError) as e:
+        pkg.ray_query_check(opt(flags=64), 1)
+    assert e.value.code == A.RT_ERR_INVALID
+    # without a context nothing is traced, and nothing is touched
+    assert lib.rt_trace_rays(None, None, None, None, 0, None, None) == A.RT_ERR_INVALID
+    assert lib.rt_trace_rays_device(None, None, None, None, 0, None, None) == A.RT_ERR_INVALID
+
+
+def test_scenes_cover_the_primitive_kinds(pkg):
+    """What the GPU test relies on: the six scenes hold, between them, every primitive kind and wrapper, stay small enough for a checker
+    that rebuilds its scene per ray, and none of them holds a medium (the refused scene does)."""
+    A = pkg._abi
+    kinds = set()
+    for name in R.SCENES:
+        b = R.build_scene(pkg, name)
+        info = pkg.compile_info(b.desc)
+        n = info["n_spheres"] + info["n_moving"] + info["n_rects"] + info["n_tris"]
+        assert 0 < n <= 520 and info["n_media"] == 0, (name, info)
+        kinds |= {b.desc.hittables[i].kind for i in range(b.desc.n_hittables)}
+    assert {A.RT_HIT_SPHERE, A.RT_HIT_MOVING_SPHERE, A.RT_HIT_XY_RECT, A.RT_HIT_XZ_RECT, A.RT_HIT_YZ_RECT, A.RT_HIT_TRIANGLE, A.RT_HIT_BOX,
+            A.RT_HIT_TRANSLATE, A.RT_HIT_ROTATE_Y, A.RT_HIT_FLIP_FACE, A.RT_HIT_BVH, A.RT_HIT_LIST} <= kinds
+    assert pkg.compile_info(R.medium_scene(pkg).desc)["n_media"] == 1
+
+
+@pytest.mark.parametrize("name", R.SCENES)
+def test_ray_sets_are_decidable(pkg, orc, name):
+    """At most 1 % of each set changes its answer under +-R ulps of its direction (rays.R_ULPS); every hit point lies on an object of the
+    description; the sets hold a few thousand f32 rays, camera and secondary, hits and misses."""
+    s = R.ray_set(pkg, orc, name)
+    rays, ref, und = s["rays"], s["ref"], s["undecidable"]
+    n = len(rays)
+    n_cam = R.GRID[0] * R.GRID[1]
+    print(f"{name}: {n} rays ({n_cam} camera), {int(ref['hit'].sum())} hits, {int(und.sum())} undecidable at R = {R.R_ULPS} ulps")
+    assert 1500 <= n <= 6000 and n > n_cam
+    assert rays.dtype == pkg.RAY_DTYPE and rays["o"].dtype == np.float32
+    assert ref["hit"].sum() > n // 4 and (~ref["hit"]).sum() > 0
+    assert und.mean() <= 0.01, f"{name}: {und.mean():.4f} of the rays are undecidable"
+    hit = ref["hit"] & ~und
+    assert s["on"][hit].any(axis=1).all(), f"{name}: a hit point lies on no object of the description"
+    # spheres: hits within 1e-3 of a pole (u is ill-conditioned there) stay below 1 % of the set
+    A = pkg._abi
+    kind = np.array([s["built"].desc.hittables[int(i)].kind for i in s["ids"]])
+    on_sphere = (s["on"] & (kind == A.RT_HIT_SPHERE)[None, :]).any(axis=1) & ref["hit"]
+    polar = on_sphere & ((ref["v"] < 1e-3) | (ref["v"] > 1.0 - 1e-3))
+    assert polar.mean() < 0.01
+    if name == "moving":
+        assert np.ptp(rays["time"]) > 0.5
+    if name == "earth":
+        assert np.ptp(ref["u"][on_sphere]) > 0.3 and np.ptp(ref["v"][on_sphere]) > 0.3
+
+
+def test_import_logic_keeps_malformed_rays_and_overfull_queues_out(pkg):
+    """A paper check of a COPY: k_rays_import's rules (csrc/kernels.hip) restated in numpy, made before any ray reached a persistent walk
+    kernel. It does not run the library (tests/test_gpu_rays.py does: test_edges for the validity rule, test_pool_rule for the pool), so
+    it shows that the rules as stated are sound, not that the kernel follows them: (a) its validity rule drops
+    every ray with a non-finite component, the zero direction and directions whose |d|^2 leaves the normal f32 range; (b) with the pool
+    rule of rt_trace_rays (P a multiple of 512 x 8, chunks of at most P rays, workgroup b of 512 rays feeding queue b mod 8) no queue can
+    be handed more rays than queue_cap, whatever the list length or pool_slots."""
+    f32 = np.float32
+
+    def valid(o, time, d):
+        with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+            o, d, time = np.asarray(o, f32), np.asarray(d, f32), f32(time)
+            a = f32(f32(f32(d[0] * d[0]) + f32(d[1] * d[1])) + f32(d[2] * d[2]))
+            fin = np.all(np.abs(o) < f32(np.inf)) and abs(time) < f32(np.inf) and np.all(np.abs(d) < f32(np.inf))
+            return bool(fin and a >= f32(1.17549435e-38) and a < f32(np.inf))
+    assert valid((0, 0, 0), 0.0, (0, 0, 1)) and valid((1e6, -3, 2), 0.5, (1e-3, 0, 0)) and valid((0, 0, 0), 0, (1e15, 1e15, 1e15))
+    for o, t, d in (((np.nan, 0, 0), 0, (0, 0, 1)), ((0, np.inf, 0), 0, (0, 0, 1)), ((0, 0, 0), np.nan, (0, 0, 1)), ((0, 0, 0), -np.inf, (0, 0, 1)),
+                    ((0, 0, 0), 0, (0, 0, 0)), ((0, 0, 0), 0, (-0.0, 0.0, -0.0)), ((0, 0, 0), 0, (np.nan, 1, 0)), ((0, 0, 0), 0, (1, -np.inf, 0)),
+                    ((0, 0, 0), 0, (1e-30, 0, 0)), ((0, 0, 0), 0, (1e-40, 1e-40, 0)), ((0, 0, 0), 0, (3e19, 3e19, 0)), ((0, 0, 0), 0, (3.4e38, 0, 0))):
+        assert not valid(o, t, d), (o, t, d)
+    Q, GRAIN = 8, 512 * 8
+    for n_rays in (1, 63, 512, 513, 4096, 4097, 10752, 960000, (1 << 28) + 5, (1 << 32) - 1):
+        for pool_slots in (0, 1, 511, 4096, 5000, 1 << 20):
+            P = min(pool_slots if pool_slots else 1 << 28, n_rays)
+            P = max(GRAIN, min(-(-P // GRAIN) * GRAIN, 0xFFFFF000))
+            cap = P // Q
+            assert cap % 512 == 0 and P % GRAIN == 0
+            for n in {min(P, n_rays), n_rays % P or min(P, n_rays)}:              # a full chunk and the last one
+                blocks = -(-n // 512)
+                per_queue = [len(range(q, blocks, Q)) * 512 for q in range(Q)]    # every workgroup stores at most 512 rays
+                assert max(per_queue) <= cap, (n_rays, pool_slots, n, per_queue, cap)
