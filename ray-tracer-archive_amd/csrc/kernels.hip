@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
+#include <type_traits>
 
 #include "device_types.h"
 #include "kernels.h"
@@ -47,26 +48,15 @@ DEVI V3 operator*(float t, V3 a) { return v3(a.x * t, a.y * t, a.z * t); }
 // Division and square root. The reference is f64; this path is f32 and everything below already differs from it by
 // rounding. The IEEE-exact f32 sequences (v_div_scale/fmas/fixup: 12 instructions; sqrtf: 15) buy nothing against
 // that reference, and the shading kernels are bound by VALU issue, so the hardware approximations are used:
-// v_rcp_f32, v_sqrt_f32, v_rsq_f32, 1 ulp each. x/0 and 0/0 keep their class (inf, NaN). -DRT_IEEE_DIV_SQRT restores
-// the exact sequences (tests/test_gpu_scenes.py compares the two builds' statistics, not bits).
-#ifdef RT_IEEE_DIV_SQRT
-DEVI float fdiv(float a, float b) { return a / b; }
-DEVI float fsqrt(float x) { return sqrtf(x); }
-DEVI V3 operator/(V3 a, float t) { return v3(a.x / t, a.y / t, a.z / t); }   // vec3.rs:181: component-wise divide
-#else
+// v_rcp_f32, v_sqrt_f32, v_rsq_f32, 1 ulp each. x/0 and 0/0 keep their class (inf, NaN).
 DEVI float fdiv(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 DEVI float fsqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
-DEVI V3 operator/(V3 a, float t) { const float r = __builtin_amdgcn_rcpf(t); return v3(a.x * r, a.y * r, a.z * r); }   // vec3.rs:181
-#endif
+DEVI V3 operator/(V3 a, float t) { const float r = __builtin_amdgcn_rcpf(t); return v3(a.x * r, a.y * r, a.z * r); }   // vec3.rs:181: component-wise divide
 DEVI float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 DEVI V3 cross(V3 u, V3 v) { return v3(u.y * v.z - u.z * v.y, -(u.x * v.z - u.z * v.x), u.x * v.y - u.y * v.x); }   // vec3.rs:68-76
 DEVI float len2(V3 a) { return dot(a, a); }
 DEVI float len(V3 a) { return fsqrt(len2(a)); }
-#ifdef RT_IEEE_DIV_SQRT
-DEVI V3 unit(V3 a) { return a / len(a); }                                   // vec3.rs:29-31
-#else
 DEVI V3 unit(V3 a) { const float r = __builtin_amdgcn_rsqf(len2(a)); return v3(a.x * r, a.y * r, a.z * r); }   // vec3.rs:29-31
-#endif
 DEVI V3 reflect(V3 v, V3 n) { return v - 2.0f * dot(v, n) * n; }            // vec3.rs:115-117
 DEVI V3 refract(V3 uv, V3 n, float eta) {                                    // vec3.rs:246-251
     float cos_theta = fminf(dot(-uv, n), 1.0f);
@@ -109,13 +99,7 @@ struct Rng {
 // sin/cos of 2*PI*x for x in [0,1): v_sin_f32 / v_cos_f32 take their argument in revolutions, so the
 // reference's `phi = 2*PI*r1; phi.cos()` (vec3.rs:258-260) is one hardware instruction each (abs. error
 // ~1e-6, far below the f32-vs-f64 differences already present); the libm path costs ~80 instructions.
-DEVI void sincos_2pi(float x, float& s, float& c) {
-#ifdef RT_LIBM_SINCOS
-    sincosf(2.0f * kPi * x, &s, &c);
-#else
-    s = __builtin_amdgcn_sinf(x); c = __builtin_amdgcn_cosf(x);
-#endif
-}
+DEVI void sincos_2pi(float x, float& s, float& c) { s = __builtin_amdgcn_sinf(x); c = __builtin_amdgcn_cosf(x); }
 DEVI V3 random_in_unit_sphere(Rng& g) {                                      // vec3.rs:78-86
     for (;;) {
         float a = g.range(-1.f, 1.f), b = g.range(-1.f, 1.f), c = g.range(-1.f, 1.f);
@@ -626,6 +610,9 @@ constexpr int kShadeBatch = 16;   // DRAIN: lanes on DONE that trigger a shading
 // 6 waves, and 210.5 ms at 8 with 44 B of scratch)
 // bytes of the record array of an LDS-resident scene as it is staged (kernels.h SceneDev::rec_unit)
 __host__ DEVI uint32_t lds_record_bytes(const SceneDev& sc) { return sc.n_records * (sc.rec_unit > 32u ? sc.rec_unit : 32u); }
+// TPB: the group size, used as the launch bound only (the body reads blockDim.x). The wavefront form of the LDS-staged modes is compiled for
+// 256, 512 and 1024 threads (launch_extend_c); the bound moves the register allocation and the schedule of the F_ALL and the Cornell
+// variant, so the copies are different programs and stay ("Kernel instances").
 template <int MODE, uint32_t FEAT, bool COUNT, uint32_t TPB, bool DRAIN, bool LIST>
 __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const uint32_t* __restrict__ count_ptr,
                                                  uint32_t* __restrict__ head, uint32_t* __restrict__ count_out_to_zero,
@@ -727,10 +714,6 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
             qb = v3((sc.grid_lo[0] - o.x) * inv.x, (sc.grid_lo[1] - o.y) * inv.y, (sc.grid_lo[2] - o.z) * inv.z);
         }
     };
-#ifdef RT_DEBUG_LONGWALK
-    uint32_t dbg_steps = 0u;
-#endif
-
 #ifdef RT_STAMPS
     unsigned long long st_refill = 0, st_node = 0, st_prim = 0, st_t0 = __builtin_amdgcn_s_memtime(), st_a, st_b;
     unsigned long long st_pass[6] = {0, 0, 0, 0, 0, 0}, st_lanes[6] = {0, 0, 0, 0, 0, 0};
@@ -928,24 +911,13 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
             // Aabb::hit (aabb.rs:31-55, interval carried across axes), on (centre, half extent): 4 packed ops for x and y,
             // one packed FMA + add/sub for z. min3/max3 ignore a NaN operand (0*inf), which keeps the box — conservative,
             // like the reference. A record without a box has h = inf; a self-loop record has h < 0 and both links on itself.
-#ifdef RT_PLAIN_VISIT
-            // the same arithmetic in plain v_fma_f32 / v_add_f32 (A/B against the packed form: VERDICT round 2, next #5)
-            const F2 tc = F2{fmaf(n0.x, sr.inv_xy.x, sr.noi_xy.x), fmaf(n0.y, sr.inv_xy.y, sr.noi_xy.y)};
-            const F2 th = F2{fmaf(n0.z, sr.ainv_xy.x, sr.e_xy.x), fmaf(n0.w, sr.ainv_xy.y, sr.e_xy.y)};
-            const F2 tz = F2{fmaf(n1.x, sr.inv_z.x, sr.noi_z.x), fmaf(n1.y, sr.inv_z.y, sr.noi_z.y)};
-            const F2 lo = F2{tc.x - th.x, tc.y - th.y}, hi = F2{tc.x + th.x, tc.y + th.y};
-#else
             const F2 tc = __builtin_elementwise_fma(F2{n0.x, n0.y}, sr.inv_xy, sr.noi_xy);   // (tcx, tcy)
             const F2 th = __builtin_elementwise_fma(F2{n0.z, n0.w}, sr.ainv_xy, sr.e_xy);      // (thx, thy), widened by the ray's own rounding
             const F2 tz = __builtin_elementwise_fma(F2{n1.x, n1.y}, sr.inv_z, sr.noi_z);      // (tcz, thz)
             const F2 lo = tc - th, hi = tc + th;
-#endif
             const float tnear = fmaxf(fmaxf(lo.x, lo.y), fmaxf(tz.x - tz.y, kTMin));
             const float tfar = fminf(fminf(hi.x, hi.y), fminf(tz.x + tz.y, tmax));
             if (COUNT) c_nodes += (node < special && n0.z < kInf) ? 1ull : 0ull;
-#ifdef RT_DEBUG_LONGWALK
-            if (COUNT) dbg_steps += node < special ? 1u : 0u;
-#endif
             node = tnear <= tfar ? __float_as_uint(n1.w) : __float_as_uint(n1.z);             // hit : skip
         }
         } else {
@@ -954,14 +926,10 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
 #pragma unroll
         for (int step = 0; step < kSteps; ++step) {
             const bool walk = pend == 0u;
-#ifdef RT_C16_LOAD_ALL
-            const uint4 w = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(nodes) + node);
-#else
             // only walking lanes load: a fully divergent 64-lane load occupies the CU's vector-memory pipe for about a cycle per lane, and
             // on the config-5 scene 60 % of the lane-loads were parked or idle lanes re-reading a record they do not use
             uint4 w = make_uint4(0u, 0xFFFFu, 0u, 0u);
             if (walk) w = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(nodes) + node);
-#endif
             const uint32_t lx = w.x & 0xFFFFu, ly = w.x >> 16, lz = w.y & 0xFFFFu, hx = w.y >> 16, hy = w.z & 0xFFFFu, hz = w.z >> 16;
             const float t0x = fmaf((float)lx, qa.x, qb.x), t1x = fmaf((float)hx, qa.x, qb.x);
             const float t0y = fmaf((float)ly, qa.y, qb.y), t1y = fmaf((float)hy, qa.y, qb.y);
@@ -972,9 +940,6 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
             const bool boxhit = nobox || tnear <= tfar;
             const bool leaf = (w.w >> 31) != 0u;
             if (COUNT) c_nodes += (walk && !nobox) ? 1ull : 0ull;
-#ifdef RT_DEBUG_LONGWALK
-            if (COUNT) dbg_steps += walk ? 1u : 0u;
-#endif
             const uint32_t next = (boxhit || leaf) ? node + 16u : w.w;  // a leaf's subtree is itself: its successor is the next record either way
             node = walk ? next : node;
             pend = (walk && boxhit && leaf) ? (w.w & 0x7FFFFFFFu) : pend;
@@ -983,16 +948,6 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
         // ---- events, outside the steps: lanes on a self-loop record ----
         if (!DRAIN && is_done()) {                                           // walked off the end: world.hit is done
             pool.hit[qbase + slot] = make_uint2(__float_as_uint(tmax), hit_prim);
-#ifdef RT_DEBUG_LONGWALK
-            if (COUNT && dbg_steps > 100000u) {
-                atomicAdd(&counters[CTR_DEBUG + 0], 1ull);
-                counters[CTR_DEBUG + 1] = ((unsigned long long)__float_as_uint(o.x) << 32) | __float_as_uint(o.y);
-                counters[CTR_DEBUG + 2] = ((unsigned long long)__float_as_uint(o.z) << 32) | __float_as_uint(d.x);
-                counters[CTR_DEBUG + 3] = ((unsigned long long)__float_as_uint(d.y) << 32) | __float_as_uint(d.z);
-                counters[CTR_DEBUG + 4] = ((unsigned long long)__float_as_uint(tmax) << 32) | from;
-            }
-            dbg_steps = 0u;
-#endif
             go_idle();
         }
         // leaf payload of a parked lane (0 for the others)
@@ -1018,11 +973,7 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
 #endif
         // ---- primitive pass: when enough lanes hold a leaf, or nobody can walk any further ----
         const uint64_t pm = __ballot(pl != 0u);
-#ifdef RT_SERVE_BEST
-        bool do_prims = pm != 0ull && ((int)__popcll(pm) >= kLeafBatch || __ballot(is_walking()) == 0ull);
-#else
         const bool do_prims = pm != 0ull && ((int)__popcll(pm) >= (FEAT == 0u ? kLeafBatchPlain : kLeafBatch) || __ballot(is_walking()) == 0ull);
-#endif
         // Scenes with four or more primitive kinds (book-2 final: spheres, a moving sphere, rects, media): a pass serves ONE
         // kind, the one most lanes wait with; the others stay parked and win a later pass. Every kind's code then runs with
         // as many lanes as the wave can give it instead of several kinds back to back with a handful of lanes each
@@ -1041,9 +992,6 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
                 const uint32_t c = (uint32_t)__popcll(__ballot(ty == k));
                 if (c > best) { best = c; serve = k; }
             }
-#ifdef RT_SERVE_BEST
-            do_prims = (int)best >= RT_SERVE_BEST || __ballot(is_walking()) == 0ull;
-#endif
         }
 #ifdef RT_STAMPS
         // passes and the lanes they serve, per kind (RT_STAMPS builds run without COUNT: its slots carry these)
@@ -1060,19 +1008,6 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
             const uint32_t type = pl >> 28, cnt = (pl >> 24) & 15u, first = pl & rtd::LEAF_MAX_FIRST;
             move_on();                                            // the record after the leaf, once its primitives are tested
             if (type == rtd::LT_SPHERE) {
-#ifdef RT_SPHERE_F64_ONLY
-                // two phases, so that the f64 refinement (several times the cost of the filter) runs once per SURVIVOR
-                // of the wave's slowest lane, not once per sphere of its largest leaf: first the f32 filter over the
-                // leaf, survivors as a bit mask (count <= 15); then the survivors in leaf order — the order in which
-                // HittableList::hit would shrink t_max
-                uint32_t surv = 0u;
-                for (uint32_t k = 0; k < cnt; ++k) {
-                    const float4 s = spheres[first + k];
-                    if (COUNT) c_prims[0]++;
-                    const uint32_t id = (rtd::LT_SPHERE << 28) | (first + k);
-                    if (id == from || !sphere_certain_miss(o, d, a, v3(s.x, s.y, s.z), s.w)) surv |= 1u << k;
-                }
-#else
                 // first the robust f32 test over the leaf in leaf order (the order in which HittableList::hit shrinks t_max); the few
                 // spheres it cannot decide (bit mask, count <= 15) get the f64 evaluation afterwards, together for the whole wave.
                 // A sphere decided later only ever lowers t_max further, so the closest hit is the same.
@@ -1086,7 +1021,6 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
                     if (r == 1) { tmax = t; hit_prim = id; }
                     surv |= (r == 2 ? 1u : 0u) << k;
                 }
-#endif
                 while (surv != 0u) {
                     const uint32_t k = (uint32_t)__builtin_ctz(surv);
                     surv &= surv - 1u;
@@ -1462,14 +1396,6 @@ DEVI void store_path(const PoolDev& p, uint32_t i, V3 o, V3 d, float tm, const P
 #define RT_SHADE_THREADS 256      // four waves share a workgroup's two barriers and its one atomic (512: book-1 k_shade 32.9 -> 31.8 ms, book-2 final 29.9 -> 28.4,
 #endif                            // Cornell 29.8 -> 29.1; 1024: 48 ms). Round 2 found no difference: its k_shade still drew work items from a counter per workgroup
 constexpr uint32_t kShadeThreads = RT_SHADE_THREADS;
-#ifndef RT_SHADE_WAVE_ALLOC
-#define RT_SHADE_WAVE_ALLOC 0     // tuning builds (with RT_QUEUES >= 32): every wave allocates for itself — measured, no gain
-#endif
-constexpr bool kShadeWaveAlloc = RT_SHADE_WAVE_ALLOC != 0;
-#ifndef RT_SHADE_GROUP_NEW
-#define RT_SHADE_GROUP_NEW 1
-#endif
-constexpr bool kShadeGroupNew = RT_SHADE_GROUP_NEW != 0;
 DEVI uint32_t block_alloc(bool flag, uint32_t* counter, uint32_t* s_scan) {
     const uint32_t wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const uint64_t m = __ballot(flag);
@@ -1698,10 +1624,6 @@ DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& 
                             unsigned long long& c_light_rect, unsigned long long& c_light_sphere) {
     bool finished = false, time_zero = false;
     L = v3(0.f, 0.f, 0.f);          // radiance of this sample: set by the terminal event only
-#ifdef RT_DEBUG_WORK
-    if (s.work == RT_DEBUG_WORK) printf("work %u depth %u o %.9g %.9g %.9g d %.9g %.9g %.9g tm %.9g hit t %.9g prim %08x T %g %g %g rng %llx from %08x\n", s.work, depth, o.x, o.y, o.z,
-                                        d.x, d.y, d.z, tm, __uint_as_float(hit.x), hit.y, s.T.x, s.T.y, s.T.z, (unsigned long long)g.s, s.from);
-#endif
     if (hit.y == rtd::HIT_NONE) {
         // main.rs:74-76: the miss returns the background
         V3 bg = v3(rd.bg[0], rd.bg[1], rd.bg[2]);
@@ -1879,9 +1801,6 @@ DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& 
         }
     }
 
-#ifdef RT_DEBUG_WORK
-    if (s.work == RT_DEBUG_WORK) printf("   exit: finished %d o %.9g %.9g %.9g d %.9g %.9g %.9g tm %.9g from %08x\n", (int)finished, o.x, o.y, o.z, d.x, d.y, d.z, tm, s.from);
-#endif
     return (finished ? SH_FINISHED : 0u) | (time_zero ? SH_TIME_ZERO : 0u);
 }
 
@@ -2022,17 +1941,10 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
             const uint32_t cy = (uint32_t)fminf(fmaxf((o.y - sc.grid_lo[1]) * fast_rcp(sc.grid_scale[1]) * k4, 0.f), 3.f);
             const uint32_t cz = (uint32_t)fminf(fmaxf((o.z - sc.grid_lo[2]) * fast_rcp(sc.grid_scale[2]) * k4, 0.f), 3.f);
             dst = block_alloc_sorted(alive, alive ? ((oct << 6) | (cz << 4) | (cy << 2) | cx) : 0u, count_out, s_bins);
-        } else if (kShadeWaveAlloc) {
-            // every wave takes its survivors' slots by itself: no barrier, no wave waiting for the slowest of its workgroup. One returning
-            // atomic per wave is eight times the atomics of one per workgroup: needs RT_QUEUES = 32 counters or more
-            const uint64_t m = __ballot(alive);
-            uint32_t base = 0u;
-            if ((threadIdx.x & 63u) == 0u && m != 0ull) base = atomicAdd(count_out, (uint32_t)__popcll(m));
-            dst = first_lane_u32(base) + lane_rank(m);
         } else {
             // the paths that go on first, the new camera rays behind them: the waves of k_extend that take the latter walk the same boxes
             // together (book-1 k_extend -1.2 ms), and it costs the scan nothing
-            dst = kShadeGroupNew ? block_alloc_two(alive && !began, alive && began, count_out, s_scan) : block_alloc(alive, count_out, s_scan);
+            dst = block_alloc_two(alive && !began, alive && began, count_out, s_scan);
         }
         SSTAMP(4);
         if (rd.first_in_shade != 0u && alive) tm = first_sphere_hit(rd, o, d, s.from);
@@ -2319,80 +2231,6 @@ template <class K> static hipError_t check_no_static_lds(K kernel) {
     }
     return hipSuccess;
 }
-// Persistent grid of k_extend = what is resident at once. Registers and the LDS copy of the scene both
-// limit it; a scene whose LDS copy is large (book-2 final: 65 KB; the 64 KB top of a tree that does not fit) allows two workgroups
-// per CU, and then larger workgroups keep more waves. The runtime's occupancy query decides between the sizes compiled per mode.
-template <int MODE, uint32_t FEAT, bool COUNT, uint32_t TPB>
-static hipError_t launch_extend_g(uint32_t n_groups, size_t lds_bytes, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
-                                  uint32_t* head, uint32_t* cz, unsigned long long* counters, hipStream_t stream) {
-    hipLaunchKernelGGL((k_extend<MODE, FEAT, COUNT, TPB, false, false>), dim3(n_groups), dim3(TPB), lds_bytes, stream, sc, pool, count_ptr, head, cz, counters, rd);
-    return hipGetLastError();
-}
-// the drain form: one lane per path of the pool (upper bound max_count; the kernel reads the real count), 256-thread groups
-template <int MODE, uint32_t FEAT, bool COUNT, bool LIST>
-static hipError_t launch_drain_c(const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, uint32_t max_count, const uint32_t* count_ptr, uint32_t* head, uint32_t* cz,
-                                 unsigned long long* counters, hipStream_t stream) {
-    const size_t lds_bytes = MODE == M_LDS ? ((size_t)lds_record_bytes(sc) + (size_t)sc.n_spheres * 16u + sc.ext_blob_bytes) : MODE == M_TOP ? (size_t)sc.n_top * 32u : 0u;
-    constexpr uint32_t T = kExtendThreads;
-    static thread_local bool checked = false;
-    if (!checked) { const hipError_t e = check_no_static_lds(k_extend<MODE, FEAT, COUNT, T, true, LIST>); if (e != hipSuccess) return e; checked = true; }
-    // max_count = upper bound of the paths in ONE queue
-    hipLaunchKernelGGL((k_extend<MODE, FEAT, COUNT, T, true, LIST>), dim3(rd.q_n * ((max_count + T - 1u) / T)), dim3(T), lds_bytes, stream, sc, pool, count_ptr, head, cz, counters, rd);
-    return hipGetLastError();
-}
-template <int MODE, uint32_t FEAT, bool COUNT>
-static hipError_t launch_extend_c(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
-                                  uint32_t* head, uint32_t* cz, unsigned long long* counters, hipStream_t stream) {
-    const size_t lds_bytes = MODE == M_LDS ? ((size_t)lds_record_bytes(sc) + (size_t)sc.n_spheres * 16u + sc.ext_blob_bytes) : MODE == M_TOP ? (size_t)sc.n_top * 32u : 0u;
-    constexpr bool kNoLds = MODE == M_HBM || MODE == M_C16;
-    // workgroup sizes compiled for this mode: 256 threads always; 512 and 1024 where an LDS copy limits the groups per CU (a
-    // 100 KB scene allows ONE group per CU: only a 1024-thread group then keeps 16 waves on it)
-    constexpr uint32_t T0 = kExtendThreads, T1 = kNoLds ? T0 : 2u * T0, T2 = kNoLds ? T0 : 4u * T0;
-    static thread_local size_t cached_lds = ~(size_t)0; static thread_local int nb[3] = {0, 0, 0}; static thread_local int pick = 0;
-    if (cached_lds != lds_bytes) {
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[0], k_extend<MODE, FEAT, COUNT, T0, false, false>, (int)T0, lds_bytes);
-        if (e != hipSuccess) return e;
-        nb[1] = nb[2] = 0;
-        e = check_no_static_lds(k_extend<MODE, FEAT, COUNT, T0, false, false>);
-        if (e != hipSuccess) return e;
-        if (!kNoLds) {
-            e = check_no_static_lds(k_extend<MODE, FEAT, COUNT, T1, false, false>);
-            if (e == hipSuccess) e = check_no_static_lds(k_extend<MODE, FEAT, COUNT, T2, false, false>);
-            if (e != hipSuccess) return e;
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[1], k_extend<MODE, FEAT, COUNT, T1, false, false>, (int)T1, lds_bytes);
-            if (e != hipSuccess) return e;
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[2], k_extend<MODE, FEAT, COUNT, T2, false, false>, (int)T2, lds_bytes);
-            if (e != hipSuccess) return e;
-        }
-#ifdef RT_EXTEND_PER_CU_MAX
-        nb[0] = std::min(nb[0], RT_EXTEND_PER_CU_MAX); nb[1] = std::min(nb[1], RT_EXTEND_PER_CU_MAX / 2); nb[2] = std::min(nb[2], RT_EXTEND_PER_CU_MAX / 4);   // tuning builds only
-#endif
-        // most resident waves wins; ties go to the smaller group (its waves leave the staging barrier sooner)
-        pick = 0;
-        if (2 * nb[1] > nb[0]) pick = 1;
-        if (4 * nb[2] > std::max(nb[0], 2 * nb[1])) pick = 2;
-        if (nb[pick] < 1) { if (lds_bytes > 160u * 1024u) return hipErrorInvalidValue; nb[pick] = 1; }
-        cached_lds = lds_bytes;
-    }
-    if (cfg.extend_geometry) { cfg.extend_geometry[0] = (uint32_t)(pick == 0 ? T0 : pick == 1 ? T1 : T2); cfg.extend_geometry[1] = (uint32_t)nb[pick]; }
-    // the resident set, or fewer workgroups when the queue is short (the host's upper bound of it): a wave needs 64 rays to be worth
-    // starting, and every workgroup started stages the scene and reads the queue size — the floor of the launches of a render's tail
-    const uint32_t tpb = pick == 0 ? T0 : pick == 1 ? T1 : T2;
-    const uint32_t per_cu = std::max<uint32_t>(1u, (uint32_t)nb[pick]);
-    uint32_t groups = std::min<uint32_t>(cfg.n_cu * per_cu, std::max<uint32_t>(1u, (cfg.max_rays + tpb - 1u) / tpb));
-    const uint32_t gq = std::max<uint32_t>(1u, rd.q_n * 64u / tpb);     // workgroups that make up q_n waves: every queue gets the same number of waves
-    groups = (groups + gq - 1u) / gq * gq;
-    if (!kNoLds && pick == 2) return launch_extend_g<MODE, FEAT, COUNT, T2>(groups, lds_bytes, sc, pool, rd, count_ptr, head, cz, counters, stream);
-    if (!kNoLds && pick == 1) return launch_extend_g<MODE, FEAT, COUNT, T1>(groups, lds_bytes, sc, pool, rd, count_ptr, head, cz, counters, stream);
-    return launch_extend_g<MODE, FEAT, COUNT, T0>(groups, lds_bytes, sc, pool, rd, count_ptr, head, cz, counters, stream);
-}
-template <int MODE, uint32_t FEAT>
-static hipError_t launch_extend_t(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
-                                  uint32_t* head, uint32_t* cz, unsigned long long* counters, bool count, hipStream_t stream) {
-    return count ? launch_extend_c<MODE, FEAT, true>(cfg, sc, pool, rd, count_ptr, head, cz, counters, stream)
-                 : launch_extend_c<MODE, FEAT, false>(cfg, sc, pool, rd, count_ptr, head, cz, counters, stream);
-}
-
 // Kernel variants are compiled for a few feature sets; a scene runs on the smallest one that covers it.
 //   0                              static spheres, Lambertian/Metal/Dielectric (book 1)
 //   F_RECT | F_TRI                 + rects and triangles, no wrappers/media/textures/lights (BASELINE config 5)
@@ -2405,14 +2243,92 @@ static uint32_t pick_variant(uint32_t need) {
     if ((need & ~kVariantBox) == 0u) return kVariantBox;
     return F_ALL;
 }
+// Run-time switches -> template arguments, here and nowhere else: each helper calls `f`, a generic lambda, with a std::integral_constant
+// that names the case; the launchers below nest them and read the values back with decltype(x)::value.
+template <class F> static auto with_variant(uint32_t features, F&& f) {
+    const uint32_t v = pick_variant(features);
+    if (v == 0u) return f(std::integral_constant<uint32_t, 0u>{});
+    if (v == kVariantMesh) return f(std::integral_constant<uint32_t, kVariantMesh>{});
+    if (v == kVariantBox) return f(std::integral_constant<uint32_t, kVariantBox>{});
+    return f(std::integral_constant<uint32_t, F_ALL>{});
+}
+// where the walk finds its records (k_extend MODE)
+template <class F> static auto with_mode(const LaunchCfg& cfg, const SceneDev& sc, F&& f) {
+    if (cfg.scene_in_lds) return f(std::integral_constant<int, M_LDS>{});
+    if (sc.nodes16) return f(std::integral_constant<int, M_C16>{});
+    if (sc.n_top != 0u) return f(std::integral_constant<int, M_TOP>{});
+    return f(std::integral_constant<int, M_HBM>{});
+}
+template <class F> static auto with_flag(bool b, F&& f) {
+    if (b) return f(std::true_type{});
+    return f(std::false_type{});
+}
+
+// bytes of LDS a workgroup of k_extend stages: the whole scene, the top of its tree, or nothing
+template <int MODE> static size_t staged_bytes(const SceneDev& sc) {
+    return MODE == M_LDS ? ((size_t)lds_record_bytes(sc) + (size_t)sc.n_spheres * 16u + sc.ext_blob_bytes) : MODE == M_TOP ? (size_t)sc.n_top * 32u : 0u;
+}
+// the drain form: one lane per path of the pool (upper bound max_count; the kernel reads the real count), 256-thread groups
+template <int MODE, uint32_t FEAT, bool COUNT, bool LIST>
+static hipError_t launch_drain_c(const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, uint32_t max_count, const uint32_t* count_ptr, uint32_t* head, uint32_t* cz,
+                                 unsigned long long* counters, hipStream_t stream) {
+    constexpr uint32_t T = kExtendThreads;
+    const auto kernel = k_extend<MODE, FEAT, COUNT, T, true, LIST>;
+    static thread_local bool checked = false;
+    if (!checked) { const hipError_t e = check_no_static_lds(kernel); if (e != hipSuccess) return e; checked = true; }
+    // max_count = upper bound of the paths in ONE queue
+    hipLaunchKernelGGL(kernel, dim3(rd.q_n * ((max_count + T - 1u) / T)), dim3(T), staged_bytes<MODE>(sc), stream, sc, pool, count_ptr, head, cz, counters, rd);
+    return hipGetLastError();
+}
+// Persistent grid of k_extend = what is resident at once. Registers and the LDS copy of the scene both
+// limit it; a scene whose LDS copy is large (book-2 final: 65 KB; the 64 KB top of a tree that does not fit) allows two workgroups
+// per CU, and then larger workgroups keep more waves. The runtime's occupancy query decides between the sizes compiled per mode.
+template <int MODE, uint32_t FEAT, bool COUNT>
+static hipError_t launch_extend_c(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
+                                  uint32_t* head, uint32_t* cz, unsigned long long* counters, hipStream_t stream) {
+    const size_t lds_bytes = staged_bytes<MODE>(sc);
+    constexpr bool kNoLds = MODE == M_HBM || MODE == M_C16;
+    // workgroup sizes compiled for this mode: 256 threads always; 512 and 1024 where an LDS copy limits the groups per CU (a
+    // 100 KB scene allows ONE group per CU: only a 1024-thread group then keeps 16 waves on it)
+    constexpr uint32_t T0 = kExtendThreads, T1 = kNoLds ? T0 : 2u * T0, T2 = kNoLds ? T0 : 4u * T0;
+    const uint32_t sizes[3] = {T0, T1, T2};
+    const auto k0 = k_extend<MODE, FEAT, COUNT, T0, false, false>;
+    const decltype(k0) kernels[3] = {k0, k_extend<MODE, FEAT, COUNT, T1, false, false>, k_extend<MODE, FEAT, COUNT, T2, false, false>};
+    static thread_local size_t cached_lds = ~(size_t)0; static thread_local int nb[3] = {0, 0, 0}; static thread_local int pick = 0;
+    if (cached_lds != lds_bytes) {
+        nb[1] = nb[2] = 0;
+        for (int k = 0; k < (kNoLds ? 1 : 3); ++k) {
+            hipError_t e = check_no_static_lds(kernels[k]);
+            if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[k], kernels[k], (int)sizes[k], lds_bytes);
+            if (e != hipSuccess) return e;
+        }
+        // most resident waves wins; ties go to the smaller group (its waves leave the staging barrier sooner)
+        pick = 0;
+        if (2 * nb[1] > nb[0]) pick = 1;
+        if (4 * nb[2] > std::max(nb[0], 2 * nb[1])) pick = 2;
+        if (nb[pick] < 1) { if (lds_bytes > 160u * 1024u) return hipErrorInvalidValue; nb[pick] = 1; }
+        cached_lds = lds_bytes;
+    }
+    const uint32_t tpb = sizes[pick];
+    if (cfg.extend_geometry) { cfg.extend_geometry[0] = tpb; cfg.extend_geometry[1] = (uint32_t)nb[pick]; }
+    // the resident set, or fewer workgroups when the queue is short (the host's upper bound of it): a wave needs 64 rays to be worth
+    // starting, and every workgroup started stages the scene and reads the queue size — the floor of the launches of a render's tail
+    const uint32_t per_cu = std::max<uint32_t>(1u, (uint32_t)nb[pick]);
+    uint32_t groups = std::min<uint32_t>(cfg.n_cu * per_cu, std::max<uint32_t>(1u, (cfg.max_rays + tpb - 1u) / tpb));
+    const uint32_t gq = std::max<uint32_t>(1u, rd.q_n * 64u / tpb);     // workgroups that make up q_n waves: every queue gets the same number of waves
+    groups = (groups + gq - 1u) / gq * gq;
+    hipLaunchKernelGGL(kernels[pick], dim3(groups), dim3(tpb), lds_bytes, stream, sc, pool, count_ptr, head, cz, counters, rd);
+    return hipGetLastError();
+}
 
 // the 8-lanes-per-ray walk: a persistent grid of 256-thread groups, every wave holding 8 rays at a time
 template <uint32_t FEAT, bool COUNT>
 static hipError_t launch_extend_wide_c(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
                                        uint32_t* head, uint32_t* cz, unsigned long long* counters, hipStream_t stream) {
+    const auto kernel = k_extend_wide<FEAT, COUNT>;
     static thread_local int per_cu = 0;
     if (per_cu == 0) {
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_extend_wide<FEAT, COUNT>, 256, 0);
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0);
         if (e != hipSuccess) return e;
         per_cu = std::max(per_cu, 1);
     }
@@ -2421,60 +2337,25 @@ static hipError_t launch_extend_wide_c(const LaunchCfg& cfg, const SceneDev& sc,
     uint32_t groups = std::min<uint32_t>(cfg.n_cu * (uint32_t)per_cu, std::max<uint32_t>(1u, (cfg.max_rays + 31u) / 32u));
     const uint32_t gq = std::max<uint32_t>(1u, rd.q_n * 64u / 256u);   // 4 waves a group: a multiple of q_n waves
     groups = (groups + gq - 1u) / gq * gq;
-    hipLaunchKernelGGL((k_extend_wide<FEAT, COUNT>), dim3(groups), dim3(256), 0, stream, sc, pool, count_ptr, head, cz, counters, rd);
+    hipLaunchKernelGGL(kernel, dim3(groups), dim3(256), 0, stream, sc, pool, count_ptr, head, cz, counters, rd);
     return hipGetLastError();
 }
 
 hipError_t launch_extend(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
                          uint32_t* head, uint32_t* cz, unsigned long long* counters, bool count, hipStream_t stream) {
     if (cfg.max_rays == 0u) return hipSuccess;
-    const uint32_t v = pick_variant(cfg.features);
-    if (sc.wide != nullptr) {
-        if (v == 0u) return count ? launch_extend_wide_c<0u, true>(cfg, sc, pool, rd, count_ptr, head, cz, counters, stream)
-                                  : launch_extend_wide_c<0u, false>(cfg, sc, pool, rd, count_ptr, head, cz, counters, stream);
-        return count ? launch_extend_wide_c<kVariantMesh, true>(cfg, sc, pool, rd, count_ptr, head, cz, counters, stream)
-                     : launch_extend_wide_c<kVariantMesh, false>(cfg, sc, pool, rd, count_ptr, head, cz, counters, stream);
-    }
-#define RT_EXT(M, F) launch_extend_t<M, F>(cfg, sc, pool, rd, count_ptr, head, cz, counters, count, stream)
-#define RT_EXT_V(M) (v == 0u ? RT_EXT(M, 0u) : v == kVariantMesh ? RT_EXT(M, kVariantMesh) : v == kVariantBox ? RT_EXT(M, kVariantBox) : RT_EXT(M, F_ALL))
-    if (cfg.scene_in_lds) return RT_EXT_V(M_LDS);
-    if (sc.nodes16) return RT_EXT_V(M_C16);
-    if (sc.n_top != 0u) return RT_EXT_V(M_TOP);
-    return RT_EXT_V(M_HBM);
-#undef RT_EXT_V
-#undef RT_EXT
+    // the wide walk exists for the sphere-only and the mesh variant (rt_api.cpp builds the wide tree for no other scene)
+    if (sc.wide != nullptr) return with_flag(pick_variant(cfg.features) == 0u, [&](auto plain) { return with_flag(count, [&](auto cnt) {
+        return launch_extend_wide_c<decltype(plain)::value ? 0u : kVariantMesh, decltype(cnt)::value>(cfg, sc, pool, rd, count_ptr, head, cz, counters, stream); }); });
+    return with_mode(cfg, sc, [&](auto mode) { return with_variant(cfg.features, [&](auto feat) { return with_flag(count, [&](auto cnt) {
+        return launch_extend_c<decltype(mode)::value, decltype(feat)::value, decltype(cnt)::value>(cfg, sc, pool, rd, count_ptr, head, cz, counters, stream); }); }); });
 }
 
 hipError_t launch_drain(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, uint32_t max_count, const uint32_t* count_ptr,
                         uint32_t* head, uint32_t* cz, unsigned long long* counters, bool count, hipStream_t stream) {
     if (max_count == 0u) return hipSuccess;
-    const uint32_t v = pick_variant(cfg.features);
-#define RT_DRN_L(M, F, L) (count ? launch_drain_c<M, F, true, L>(sc, pool, rd, max_count, count_ptr, head, cz, counters, stream) \
-                                 : launch_drain_c<M, F, false, L>(sc, pool, rd, max_count, count_ptr, head, cz, counters, stream))
-#define RT_DRN(M, F) (rd.n_list != 0u ? RT_DRN_L(M, F, true) : RT_DRN_L(M, F, false))
-#define RT_DRN_V(M) (v == 0u ? RT_DRN(M, 0u) : v == kVariantMesh ? RT_DRN(M, kVariantMesh) : v == kVariantBox ? RT_DRN(M, kVariantBox) : RT_DRN(M, F_ALL))
-    if (cfg.scene_in_lds) return RT_DRN_V(M_LDS);
-    if (sc.nodes16) return RT_DRN_V(M_C16);
-    if (sc.n_top != 0u) return RT_DRN_V(M_TOP);
-    return RT_DRN_V(M_HBM);
-#undef RT_DRN_V
-#undef RT_DRN
-#undef RT_DRN_L
-}
-
-template <uint32_t FEAT, bool LIST>
-static void launch_shade_l(uint32_t blocks, const SceneDev& sc, const PoolDev& in, const PoolDev& out, const RenderDev& rd, const uint32_t* count_in,
-                           uint32_t* count_out, uint32_t* hz, unsigned long long* counters, bool count,
-                           hipStream_t stream) {
-    if (count) hipLaunchKernelGGL((k_shade<FEAT, true, LIST>), dim3(blocks), dim3(kShadeThreads), sc.shade_blob_bytes, stream, sc, in, out, rd, count_in, count_out, hz, counters);
-    else hipLaunchKernelGGL((k_shade<FEAT, false, LIST>), dim3(blocks), dim3(kShadeThreads), sc.shade_blob_bytes, stream, sc, in, out, rd, count_in, count_out, hz, counters);
-}
-template <uint32_t FEAT>
-static void launch_shade_t(uint32_t blocks, const SceneDev& sc, const PoolDev& in, const PoolDev& out, const RenderDev& rd, const uint32_t* count_in,
-                           uint32_t* count_out, uint32_t* hz, unsigned long long* counters, bool count,
-                           hipStream_t stream) {
-    if (rd.n_list != 0u) launch_shade_l<FEAT, true>(blocks, sc, in, out, rd, count_in, count_out, hz, counters, count, stream);
-    else launch_shade_l<FEAT, false>(blocks, sc, in, out, rd, count_in, count_out, hz, counters, count, stream);
+    return with_mode(cfg, sc, [&](auto mode) { return with_variant(cfg.features, [&](auto feat) { return with_flag(count, [&](auto cnt) { return with_flag(rd.n_list != 0u, [&](auto list) {
+        return launch_drain_c<decltype(mode)::value, decltype(feat)::value, decltype(cnt)::value, decltype(list)::value>(sc, pool, rd, max_count, count_ptr, head, cz, counters, stream); }); }); }); });
 }
 
 hipError_t launch_shade(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& in, const PoolDev& out, const RenderDev& rd, uint32_t max_count,
@@ -2482,19 +2363,16 @@ hipError_t launch_shade(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev&
                         hipStream_t stream) {
     const uint32_t blocks = rd.q_n * ((max_count + kShadeThreads - 1u) / kShadeThreads);   // max_count = upper bound of the paths in ONE queue
     if (blocks == 0u) return hipSuccess;
-    const uint32_t v = pick_variant(cfg.features);
-    if (v == 0u) launch_shade_t<0u>(blocks, sc, in, out, rd, count_in, count_out, hz, counters, count, stream);
-    else if (v == kVariantMesh) launch_shade_t<kVariantMesh>(blocks, sc, in, out, rd, count_in, count_out, hz, counters, count, stream);
-    else if (v == kVariantBox) launch_shade_t<kVariantBox>(blocks, sc, in, out, rd, count_in, count_out, hz, counters, count, stream);
-    else launch_shade_t<F_ALL>(blocks, sc, in, out, rd, count_in, count_out, hz, counters, count, stream);
+    with_variant(cfg.features, [&](auto feat) { with_flag(count, [&](auto cnt) { with_flag(rd.n_list != 0u, [&](auto list) {
+        hipLaunchKernelGGL((k_shade<decltype(feat)::value, decltype(cnt)::value, decltype(list)::value>), dim3(blocks), dim3(kShadeThreads), sc.shade_blob_bytes, stream,
+                           sc, in, out, rd, count_in, count_out, hz, counters); }); }); });
     return hipGetLastError();
 }
 
 hipError_t launch_generate(const PoolDev& pool, const RenderDev& rd, uint32_t n_init, uint32_t* out_count, hipStream_t stream) {
     const uint32_t blocks = (n_init + kShadeThreads - 1u) / kShadeThreads;
     if (blocks == 0u) return hipSuccess;
-    if (rd.n_list != 0u) hipLaunchKernelGGL(k_generate<true>, dim3(blocks), dim3(kShadeThreads), 0, stream, pool, rd, n_init, out_count);
-    else hipLaunchKernelGGL(k_generate<false>, dim3(blocks), dim3(kShadeThreads), 0, stream, pool, rd, n_init, out_count);
+    with_flag(rd.n_list != 0u, [&](auto list) { hipLaunchKernelGGL(k_generate<decltype(list)::value>, dim3(blocks), dim3(kShadeThreads), 0, stream, pool, rd, n_init, out_count); });
     return hipGetLastError();
 }
 
@@ -2527,10 +2405,8 @@ hipError_t launch_rays_export(const LaunchCfg& cfg, const SceneDev& sc, const Ra
                               const uint32_t* counts, void* hits, hipStream_t stream) {
     const uint32_t blocks = kQueues * ((std::min(max_count, queue_cap) + 255u) / 256u);   // max_count = upper bound of the rays in ONE queue
     if (blocks == 0u) return hipSuccess;
-    const uint32_t v = pick_variant(cfg.features);
-#define RT_EXP(F) hipLaunchKernelGGL((k_rays_export<F>), dim3(blocks), dim3(256), 0, stream, sc, src, pool, queue_cap, counts, (Float4*)hits)
-    if (v == 0u) RT_EXP(0u); else if (v == kVariantMesh) RT_EXP(kVariantMesh); else if (v == kVariantBox) RT_EXP(kVariantBox); else RT_EXP(F_ALL);
-#undef RT_EXP
+    with_variant(cfg.features, [&](auto feat) {
+        hipLaunchKernelGGL((k_rays_export<decltype(feat)::value>), dim3(blocks), dim3(256), 0, stream, sc, src, pool, queue_cap, counts, (Float4*)hits); });
     return hipGetLastError();
 }
 

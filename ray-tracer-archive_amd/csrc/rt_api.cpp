@@ -761,10 +761,6 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     }
     HIP_TRY(ctx, ctx->blocksum.ensure((size_t)total_items * 16));
     rd.blocksum = (rtd::Float4*)ctx->blocksum.p;
-#ifdef RT_DEBUG_POISON
-    // diagnostic build (scripts/sweep.py "poison"): the per-item sums filled with NaN first, so an item no kernel ever finished shows up in the frame
-    HIP_TRY(ctx, hipMemsetAsync(ctx->blocksum.p, 0xFF, (size_t)total_items * 16, ctx->stream));
-#endif
     HIP_TRY(ctx, ctx->tile_prefix.ensure(prefix.size() * 4));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->tile_prefix.p, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // `prefix` is a stack vector

@@ -1,6 +1,16 @@
 #!/bin/bash
-# usage: scripts/isa.sh <mangled-prefix>   -> /tmp/kern.s with that kernel's ISA
-cd /root/repo/ray-tracer-archive_amd/csrc && hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-atomic-optimizer-strategy=None -S --cuda-device-only kernels.hip -o /tmp/kernels.s 2>&1 | grep -E "error" 
-n=$(grep -n "^$1.*:" /tmp/kernels.s | head -1 | cut -d: -f1)
-awk -v n=$n 'NR>=n' /tmp/kernels.s | awk '{print} /s_endpgm/{exit}' > /tmp/kern.s
-wc -l /tmp/kern.s
+# usage: scripts/isa.sh [-o dump.s] [mangled-prefix]
+#   the ISA of every kernel of kernels.hip, compiled with build.py's code-generation flags -> dump.s (default /tmp/kernels.s);
+#   with a mangled prefix, that kernel's ISA -> /tmp/kern.s as well.
+# The sources are the ones of the checkout this script lies in, so two checkouts are compared by running each one's script and
+# handing the two dumps to scripts/isa_diff.py; scripts/isa_regs.py lists a dump's register figures.
+set -eu
+src="$(cd "$(dirname "${BASH_SOURCE[0]}")/../ray-tracer-archive_amd/csrc" && pwd)"
+out=/tmp/kernels.s
+if [ "${1:-}" = "-o" ]; then out="$2"; shift 2; fi
+hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-atomic-optimizer-strategy=None -S --cuda-device-only "$src/kernels.hip" -o "$out"
+if [ -n "${1:-}" ]; then
+    n=$(grep -n "^$1.*:" "$out" | head -1 | cut -d: -f1)
+    awk -v n="$n" 'NR>=n' "$out" | awk '{print} /s_endpgm/{exit}' > /tmp/kern.s
+    wc -l /tmp/kern.s
+fi

@@ -7,19 +7,13 @@ VARIANTS = {
     "base": [],
     "sh1024": ["RT_SHADE_THREADS=1024"],
     "sh256": ["RT_SHADE_THREADS=256"],
-    "dbgwork": ["RT_DEBUG_WORK=3000u"],
     "b1r1s1": ["RT_LEAF_BATCH=1", "RT_REFILL_MIN=1", "RT_STEPS=1"],
     "b64": ["RT_LEAF_BATCH=64"],
-    "f64only": ["RT_SPHERE_F64_ONLY=1"],
     "tol6": ["RT_SPHERE_TOL=1e-6f"],
     "tol4": ["RT_SPHERE_TOL=1e-4f"],
-    "libm": ["RT_LIBM_SINCOS=1"],
     "stamps": ["RT_STAMPS=1"],
-    "poison": ["RT_DEBUG_POISON=1"],     # per-item sums NaN-filled before every render: an item no kernel finished shows in the frame
     "sk9": ["RT_SERVE_KINDS_MIN=9u"], "sk9b32": ["RT_SERVE_KINDS_MIN=9u", "RT_LEAF_BATCH=32"], "sk9b16": ["RT_SERVE_KINDS_MIN=9u", "RT_LEAF_BATCH=16"],
-    "c16all": ["RT_C16_LOAD_ALL=1"],
     "sw7": ["RT_SHADE_WAVES=7"], "sw5": ["RT_SHADE_WAVES=5"], "sw6": ["RT_SHADE_WAVES=6"], "sw8": ["RT_SHADE_WAVES=8"],
-    "sb16": ["RT_SERVE_BEST=16"], "sb24": ["RT_SERVE_BEST=24"], "sb32": ["RT_SERVE_BEST=32"], "sb40": ["RT_SERVE_BEST=40"], "sb48": ["RT_SERVE_BEST=48"],
     "b32r24": ["RT_LEAF_BATCH=32"], "b40": ["RT_LEAF_BATCH=40"], "b48": ["RT_LEAF_BATCH=48"],
     "r1": ["RT_REFILL_MIN=1"],
     "r8": ["RT_REFILL_MIN=8"],
@@ -29,7 +23,6 @@ VARIANTS = {
     "t512": ["RT_EXTEND_THREADS=512"],
     "t1024": ["RT_EXTEND_THREADS=1024"],
     "c128": ["RT_CHUNK=128"],
-    "longwalk": ["RT_DEBUG_LONGWALK=1"],
     "c256": ["RT_CHUNK=256"],
     "b16r16": ["RT_LEAF_BATCH=16", "RT_REFILL_MIN=16"],
     "c512": ["RT_CHUNK=512"],
@@ -48,16 +41,6 @@ VARIANTS = {
     "b24": ["RT_LEAF_BATCH=24"],
     "b32": ["RT_LEAF_BATCH=32"],
     "b1": ["RT_LEAF_BATCH=1"],
-    "bs0": ["RT_BLOCK_SHIFT=0"],
-    "bs1": ["RT_BLOCK_SHIFT=1"],
-    "bs2": ["RT_BLOCK_SHIFT=2"],
-    "bs3": ["RT_BLOCK_SHIFT=3"],
-    "bs5": ["RT_BLOCK_SHIFT=5"],
-    "o6": ["RT_EXTEND_PER_CU_MAX=6"],
-    "o5": ["RT_EXTEND_PER_CU_MAX=5"],
-    "o4": ["RT_EXTEND_PER_CU_MAX=4"],
-    "o3": ["RT_EXTEND_PER_CU_MAX=3"],
-    "o2": ["RT_EXTEND_PER_CU_MAX=2"],
 }
 if sys.argv[1] == "build":
     import importlib.util
