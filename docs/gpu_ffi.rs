@@ -148,6 +148,12 @@ pub struct RtRayHit {
 pub const RT_RAYHIT_HIT: u32 = 1; pub const RT_RAYHIT_FRONT_FACE: u32 = 2; pub const RT_RAYHIT_INVALID_RAY: u32 = 4;
 #[repr(C)] #[derive(Clone, Copy, Default, Debug)]
 pub struct RtRayQueryOptions { pub struct_bytes: u32, pub flags: u32, pub pool_slots: u32, pub _pad: u32 }
+// first-hit features (rt_render_features_device): per-slot sums of albedo, normal, depth and the hit count of the render's own camera rays
+pub const RT_FEATURES_ACCUMULATE: u32 = 1;
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtFeatureOptions { pub struct_bytes: u32, pub flags: u32, pub first_sample: u32, pub pool_slots: u32 }
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct RtFeatureBuffers { pub albedo_sum: *mut c_void, pub normal_sum: *mut c_void, pub depth_sum: *mut c_void, pub hits: *mut c_void }
 pub const RT_DENOISE_MAX_WINDOW_RADIUS: u32 = 16;
 pub const RT_DENOISE_MAX_PATCH_RADIUS: u32 = 4;
 
@@ -233,6 +239,11 @@ extern "C" {
                                 hits_device: *mut c_void, stats: *mut RtStats) -> c_int;
     pub fn rt_trace_rays(ctx: *mut RtCtx, scene: *const RtScene, options: *const RtRayQueryOptions, rays_host: *const RtRay, n_rays: u64,
                          hits_host: *mut RtRayHit, stats: *mut RtStats) -> c_int;
+    /// host only: validates a feature pass (params, options)
+    pub fn rt_features_check(params: *const RtParams, options: *const RtFeatureOptions) -> c_int;
+    /// first-hit feature sums of samples [first_sample, first_sample + samples_per_pixel) into the caller's device planes (null = not wanted)
+    pub fn rt_render_features_device(ctx: *mut RtCtx, scene: *const RtScene, cam: *const RtCamera, params: *const RtParams,
+                                     options: *const RtFeatureOptions, buffers: *const RtFeatureBuffers, stats: *mut RtStats) -> c_int;
     pub fn rt_untile(params: *const RtParams, gathered: *const f32, rgb_sum: *mut f32) -> c_int;
     /// write_color (main.rs:141-169) on the device
     pub fn rt_resolve_device(ctx: *mut RtCtx, rgb_sum_device: *const c_void, width: u32, height: u32,

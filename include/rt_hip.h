@@ -464,6 +464,54 @@ int rt_trace_rays_device(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptio
 int rt_trace_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options /* NULL = defaults */, const RtRay* rays_host, uint64_t n_rays,
                   RtRayHit* hits_host, RtStats* stats);
 
+/* ---- first-hit features: albedo, normal and depth of the render's own camera rays ----------------------------------------------------------
+ *
+ * What a feature-guided filter or an external denoiser starts from: per-pixel SUMS, over a range of samples, of the first hit's colour,
+ * normal and distance, for exactly the primary rays a render of the same (scene, camera, params) traces.
+ *   - WHICH RAYS. For every output slot of the rgb_sum layout (the full frame, or this shard's tiles back to back: tile_size, shard_index
+ *     and shard_count are honoured; clipped slots of edge tiles are never written) and every sample s of
+ *     [first_sample, first_sample + params->samples_per_pixel): the primary ray the render traces for (seed, pixel, s) — the device function
+ *     a render calls, with the same draws in the same order from the path's stream (jitter, lens offset, time). Not a restatement of it.
+ *   - PER SAMPLE, from world.hit(ray, 0.001, inf) (main.rs:74):
+ *       albedo  the first hit's colour: texture.value(u, v, p) for a Lambertian, albedo for a Metal, (1, 1, 1) for a Dielectric; for a
+ *               DiffuseLight what `emitted` returns toward this ray (its colour on the front face, 0 on the back); on a miss the
+ *               background radiance of the ray (constant, or the sky gradient);
+ *       normal  the HitRecord normal as rt_trace_rays reports it: world space, after set_face_normal and the wrapper replay; 0 on a miss;
+ *       depth   t * |d| in f32; 0 on a miss;
+ *       hits    1 when the ray hit something.
+ *   - FOLDING. Every plane holds per-slot sums, folded sequentially in sample order in f32 (hits: u32) from 0 — or, under
+ *     RT_FEATURES_ACCUMULATE, from the value already in the plane. Hence passes over [0, a) and [a, N), the second accumulating, leave the
+ *     bits of one pass over [0, N). No float atomics: a slot's result is a function of (scene, layout, camera, seed, width, height, pixel,
+ *     sample range) alone — not of pool_slots, the chunking, the shard the pixel fell in or the call count.
+ *   - Means are the caller's: albedo_sum / samples; normal_sum and depth_sum over `hits` (a miss adds 0 to both).
+ *   - RtParams: max_depth and nan_policy are not read. Of flags, RT_FLAG_TIMING is honoured, RT_FLAG_SAMPLE_BLOCKS is accepted without
+ *     effect (features fold per sample), RT_FLAG_COUNTERS and RT_FLAG_FUSED are RT_ERR_INVALID. RtParams.pool_slots is not read
+ *     (RtFeatureOptions.pool_slots caps the rays in flight; 0 = the renderer's rule, as for ray queries; longer passes run in chunks).
+ *   - REFUSED, with the reason in rt_last_error and nothing written: params rt_render refuses; struct_bytes < sizeof(RtFeatureOptions); an
+ *     unknown bit in flags; first_sample + samples_per_pixel >= 2^32; all four pointers NULL; a pointer that is not 16-byte aligned. A scene
+ *     that holds a ConstantMedium is RT_ERR_UNSUPPORTED: the limit of ray queries, and as deliberate. No pixel-list variant, no multi-GPU
+ *     entry point, no host-memory variant (callers copy the planes).
+ *   - RtStats: samples = segments = rays traced; render_ms; with RT_FLAG_TIMING also extend_ms (the traversal kernels) and other_ms (the
+ *     kernels that make the rays, write the per-ray records and fold them; debug[0], [1], [2]: the three of them apart, in microseconds).
+ *     The call blocks until done. */
+enum { RT_FEATURES_ACCUMULATE = 1u };
+typedef struct RtFeatureOptions {
+    uint32_t struct_bytes;    /* sizeof(RtFeatureOptions) as the caller compiled it (the struct may grow at its end) */
+    uint32_t flags;           /* RT_FEATURES_ACCUMULATE; an unknown bit is RT_ERR_INVALID */
+    uint32_t first_sample;    /* absolute index of the first sample of this pass */
+    uint32_t pool_slots;      /* rays in flight; 0 = the renderer's rule */
+} RtFeatureOptions;
+typedef struct RtFeatureBuffers {   /* device memory the caller owns; any pointer may be NULL = not wanted; 16-byte aligned */
+    void* albedo_sum;         /* 3 f32 per output slot, the layout of rgb_sum (rt_output_floats floats) */
+    void* normal_sum;         /* 3 f32 per slot */
+    void* depth_sum;          /* 1 f32 per slot */
+    void* hits;               /* 1 u32 per slot: samples of the pass range whose primary ray hit something */
+} RtFeatureBuffers;
+/* Host only, no device: validates (params, options) and reports the reason through rt_last_error. */
+int rt_features_check(const RtParams* params, const RtFeatureOptions* options);
+int rt_render_features_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* params, const RtFeatureOptions* options,
+                              const RtFeatureBuffers* buffers, RtStats* stats);
+
 /* Host-side helper: scatter `shard_count` gathered shard buffers (each rt_output_floats long,
    in shard order) into a full-frame rgb_sum. */
 int rt_untile(const RtParams* params, const float* gathered, float* rgb_sum);

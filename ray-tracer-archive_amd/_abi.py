@@ -19,6 +19,7 @@ RT_PASS_ACCUMULATE = 1
 RT_COMM_ID_BYTES = 128
 RT_DENOISE_MAX_WINDOW_RADIUS, RT_DENOISE_MAX_PATCH_RADIUS = 16, 4
 RT_RAYHIT_HIT, RT_RAYHIT_FRONT_FACE, RT_RAYHIT_INVALID_RAY = 1, 2, 4
+RT_FEATURES_ACCUMULATE = 1
 # RtUploadOptions.layout_flags
 (RT_LAYOUT_LISTS_AS_REFERENCE, RT_LAYOUT_LISTS_CULLED, RT_LAYOUT_NO_MEMBER_BOXES, RT_LAYOUT_MEMBER_BOXES, RT_LAYOUT_CHILD_ORDER_AS_REFERENCE,
  RT_LAYOUT_SCENE_IN_HBM, RT_LAYOUT_NODES_32B, RT_LAYOUT_NO_SHADE_TABLES_IN_LDS, RT_LAYOUT_NO_EXTEND_TABLES_IN_LDS, RT_LAYOUT_WIDE_NODES) = (1 << k for k in range(10))
@@ -131,6 +132,14 @@ class RtRayQueryOptions(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32), ("pool_slots", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class RtFeatureOptions(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32), ("first_sample", C.c_uint32), ("pool_slots", C.c_uint32)]
+
+
+class RtFeatureBuffers(C.Structure):
+    _fields_ = [("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p), ("depth_sum", C.c_void_p), ("hits", C.c_void_p)]
+
+
 class RtWideInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("n_leaf_entries", C.c_uint64), ("n_inner_entries", C.c_uint64), ("n_prims", C.c_uint64),
                 ("depth", C.c_uint32), ("_pad", C.c_uint32), ("mean_children", C.c_double), ("mean_leaf_members", C.c_double)]
@@ -146,7 +155,8 @@ RT_HIP_SYMBOLS = ["rt_ctx_create", "rt_ctx_destroy", "rt_scene_upload", "rt_scen
                   "rt_pass_check", "rt_render_pass", "rt_render_pass_device",
                   "rt_adaptive_check", "rt_adaptive_select", "rt_render_pass_pixels_device", "rt_resolve_counts_device",
                   "rt_denoise_check", "rt_denoise_device",
-                  "rt_ray_query_check", "rt_trace_rays_device", "rt_trace_rays"]
+                  "rt_ray_query_check", "rt_trace_rays_device", "rt_trace_rays",
+                  "rt_features_check", "rt_render_features_device"]
 RT_HOST_SYMBOLS = ["rt_host_scene_create", "rt_host_scene_desc", "rt_host_scene_camera", "rt_host_scene_destroy", "rt_host_camera_new",
                    "rt_host_write_color", "rt_host_tonemap", "rt_host_write_png", "rt_host_write_jpeg", "rt_host_write_image"]
 
@@ -207,6 +217,10 @@ def declare(lib):
     lib.rt_trace_rays_device.argtypes = [vp, vp, P(RtRayQueryOptions), vp, u64, vp, P(RtStats)]
     lib.rt_trace_rays.restype = i32
     lib.rt_trace_rays.argtypes = [vp, vp, P(RtRayQueryOptions), vp, u64, vp, P(RtStats)]
+    lib.rt_features_check.restype = i32
+    lib.rt_features_check.argtypes = [P(RtParams), P(RtFeatureOptions)]
+    lib.rt_render_features_device.restype = i32
+    lib.rt_render_features_device.argtypes = [vp, vp, P(RtCamera), P(RtParams), P(RtFeatureOptions), P(RtFeatureBuffers), P(RtStats)]
     lib.rt_untile.restype = i32
     lib.rt_untile.argtypes = [P(RtParams), P(C.c_float), P(C.c_float)]
     lib.rt_resolve_device.restype = i32

@@ -241,6 +241,13 @@ class Adaptive:
             cnt = torch.from_numpy(np.ascontiguousarray(self.counts()).view(np.int32).reshape(-1)).to(dev)
         return denoise_frame(self.ctx, rgb, sq, p.width, p.height, self.samples_per_item, counts=cnt, rgb8=rgb8, **opts)
 
+    def features(self, samples):
+        """First-hit features of this frame's camera rays (rt_render_features_device), from a pass of its own of `samples` samples per pixel
+        — uniform, independent of the radiance samples held: (albedo (H, W, 3), normal (H, W, 3), depth (H, W), hit fraction (H, W)), f32
+        means; normal and depth over the samples that hit. A sharded frame is untiled first."""
+        from .features import feature_means
+        return feature_means(self.ctx, self.scene, self.cam, self.params, samples)
+
     # ---- checkpoints ----
     def save(self, path):
         """An .npz checkpoint: sums, counts, samples_done, frame_samples, the options, the RtParams fields, the camera and the scene."""

@@ -89,6 +89,17 @@ def ray_query_check(options=None, n_rays=0):
     _check(lib().rt_ray_query_check(C.byref(options) if options is not None else None, n_rays))
 
 
+def feature_options(first_sample=0, accumulate=False, pool_slots=0, flags=None):
+    """RtFeatureOptions (include/rt_hip.h, "first-hit features"); flags overrides the accumulate bit when given."""
+    f = (A.RT_FEATURES_ACCUMULATE if accumulate else 0) if flags is None else int(flags)
+    return A.RtFeatureOptions(C.sizeof(A.RtFeatureOptions), f, int(first_sample), int(pool_slots))
+
+
+def features_check(params, options):
+    """rt_features_check (host only): raises RtError (RT_ERR_INVALID, with the reason) for a feature pass the contract refuses."""
+    _check(lib().rt_features_check(C.byref(params), C.byref(options) if options is not None else None))
+
+
 def _check_device(a, b, n, what, float_):
     """a (and b, unless None) are contiguous CUDA tensors of n elements (n None: any), float32 or a 32-bit integer type."""
     import torch
@@ -436,6 +447,37 @@ class Context:
         _check(lib().rt_trace_rays(self._h, scene._h, opt, C.c_void_p(rays.ctypes.data if n else None), n, C.c_void_p(out.ctypes.data if n else None),
                                    C.byref(st)), self._h)
         return (out, st.as_dict()) if with_stats else out
+
+    # ---- first-hit features (include/rt_hip.h, "first-hit features"): device tensors only ----
+    def render_features(self, scene, cam, params, first_sample=0, accumulate=False, albedo=None, normal=None, depth=None, hits=None, pool_slots=0,
+                        with_stats=False):
+        """rt_render_features_device: per-slot sums of the first hit's albedo, normal and depth, and the number of hits, over samples
+        first_sample .. first_sample + params.samples_per_pixel - 1 of the render's own camera rays.
+
+        albedo / normal: float32 CUDA tensors of 3 * slots elements (slots = output_floats(params) // 3), depth: float32 of slots, hits: a
+        32-bit integer tensor of slots. Only the planes given are written; with none given all four are made (zero-filled, so clipped slots
+        of a sharded layout read 0). accumulate: the fold starts from the planes' values. Returns (albedo, normal, depth, hits), None for a
+        plane not wanted, and the stats too with with_stats. A refused call raises RtError and leaves the planes untouched."""
+        import torch
+        slots = output_floats(params) // 3
+        if albedo is None and normal is None and depth is None and hits is None:
+            if accumulate:
+                raise ValueError("an accumulating feature pass needs the planes to add into")
+            dev = torch.device("cuda", self.device_id)
+            albedo, normal = torch.zeros(3 * slots, dtype=torch.float32, device=dev), torch.zeros(3 * slots, dtype=torch.float32, device=dev)
+            depth, hits = torch.zeros(slots, dtype=torch.float32, device=dev), torch.zeros(slots, dtype=torch.int32, device=dev)
+        _check_device(albedo, normal, n=3 * slots, what="albedo / normal", float_=True)
+        _check_device(depth, None, n=slots, what="depth", float_=True)
+        _check_device(hits, None, n=slots, what="hits", float_=False)
+        planes = (albedo, normal, depth, hits)
+        if any(t is not None and t.device.index != self.device_id for t in planes):      # another GPU's pointer means nothing to this context's kernels
+            raise ValueError(f"feature planes must live on this context's device (cuda:{self.device_id})")
+        opt = feature_options(first_sample, accumulate, pool_slots)
+        buf = A.RtFeatureBuffers(*[t.data_ptr() if t is not None else None for t in planes])
+        st = A.RtStats()
+        torch.cuda.synchronize(torch.device("cuda", self.device_id))        # the library's stream is not torch's
+        _check(lib().rt_render_features_device(self._h, scene._h, C.byref(cam), C.byref(params), C.byref(opt), C.byref(buf), C.byref(st)), self._h)
+        return planes + (st.as_dict(),) if with_stats else planes
 
     # ---- denoising (include/rt_hip.h, "denoising"): device tensors only ----
     def denoise(self, rgb_sum, sq_sum, width, height, samples=0, counts=None, options=None, out=None):

@@ -188,6 +188,22 @@ hipError_t launch_rays_import(const void* rays, uint32_t first, uint32_t n, cons
 // after launch_extend: one RtRayHit per pool slot, at its ray's index (max_count: upper bound of the rays in one queue)
 hipError_t launch_rays_export(const LaunchCfg& cfg, const SceneDev& sc, const RaySrcDev& src, const PoolDev& pool, uint32_t queue_cap, uint32_t max_count,
                               const uint32_t* counts, void* hits, hipStream_t stream);
+// first-hit features (kernels.hip "first-hit features"). FeatDev: one chunk of a feature pass — samples [k0, k0 + nk) of the pass, of output
+// slots [slot0, slot0 + ns) — and where its results go; its own block, like RaySrcDev. Ray r = k * ns + s of the chunk is sample
+// first_sample + k0 + k of slot slot0 + s; its 32-byte record is rec[2 r], rec[2 r + 1].
+struct FeatDev {
+    uint32_t first_sample, k0, nk, slot0, ns; FastDiv div_ns;
+    uint32_t accumulate;        // the fold starts from the planes' values instead of 0
+    rtd::Float4* rec;           // [2 * ns * nk], owned by the context
+    float* albedo; float* normal; float* depth; uint32_t* hits;   // the caller's planes, nullptr = not wanted
+};
+// the chunk's camera rays (RenderDev: camera, frame, tiling, seed, queue geometry) into `pool`; `counts` (zeroed by the caller) receives the queues'
+// sizes, counters[CTR_SEGMENTS] counts the rays. ns * nk <= kQueues * rd.queue_cap, rd.queue_cap % 512 == 0.
+hipError_t launch_features_import(const RenderDev& rd, const FeatDev& fd, const PoolDev& pool, uint32_t* counts, unsigned long long* counters, hipStream_t stream);
+// after launch_extend: one feature record per pool slot (max_count: upper bound of the rays in one queue); then the per-slot fold into the planes
+hipError_t launch_features_export(const LaunchCfg& cfg, const SceneDev& sc, const RenderDev& rd, const FeatDev& fd, const PoolDev& pool, uint32_t max_count,
+                                  const uint32_t* counts, hipStream_t stream);
+hipError_t launch_features_fold(const RenderDev& rd, const FeatDev& fd, hipStream_t stream);
 // multi-GPU root: gathered shard buffers -> full frame (rt_multi.cpp)
 hipError_t launch_untile_f32(const float* gathered, float* frame, uint32_t width, uint32_t height, uint32_t ts, uint32_t tiles_x, uint32_t world, uint64_t per_shard,
                              hipStream_t stream);

@@ -2213,6 +2213,186 @@ __global__ void __launch_bounds__(256) k_rays_export(SceneDev sc, RaySrcDev src,
 }
 
 // ------------------------------------------------------------------------------------------------
+// first-hit features (rt_hip.h "first-hit features"): the render's own camera rays -> pool records -> k_extend -> per-ray feature
+// records -> per-pixel sums
+// ------------------------------------------------------------------------------------------------
+// The HitRecord of (ray, t, primitive) as a function: k_rays_export's block "rebuild the HitRecord" above, statement for statement (u, v always
+// computed, no medium). k_rays_export keeps its own copy: calling this function from it moved its register figures in all four instances
+// (23/36/62/72 VGPRs -> 19/37/58/64), and the figures of the existing kernels are pinned. The identity test of
+// tests/test_gpu_features.py and the yardstick tests, whose expected values come from k_rays_export, keep the two in step. false: a primitive
+// kind this instance was not compiled for — cannot occur (pick_variant).
+struct HitRec { V3 p, n; float u, v; bool ff; uint32_t meta; };
+template <uint32_t FEAT>
+DEVI bool rebuild_hit(const SceneDev& sc, V3 o, V3 d, float tm, float t, uint32_t prim, HitRec& h) {
+    const uint32_t type = prim >> 28, idx = prim & rtd::LEAF_MAX_FIRST;
+    const uint32_t meta = type == rtd::LT_SPHERE ? sc.sphere_meta[idx]
+                        : ((FEAT & F_RECT) && type == rtd::LT_RECT) ? sc.rect_meta[idx]
+                        : ((FEAT & F_MOVING) && type == rtd::LT_MOVING) ? sc.moving_meta[idx]
+                        : ((FEAT & F_TRI) && type == rtd::LT_TRI) ? sc.tri_meta[idx] : 0u;
+    const uint32_t wrap = (FEAT & F_XFORM) ? (meta >> 22) : 0u;
+    rtd::Wrap W{};
+    if ((FEAT & F_XFORM) && wrap) W = sc.wraps[wrap];
+    const uint32_t xf = W.xform;
+    V3 ol = o, dl = d;
+    if ((FEAT & F_XFORM) && xf) xform_ray(sc.xforms[xf], o, d, ol, dl);
+    V3 p, n, outward; float hu = 0.f, hv = 0.f; bool ff;
+    if (type == rtd::LT_SPHERE) {
+        const Float4 sp = sc.spheres[idx];
+        p = ol + dl * t;                                            // sphere.rs:59
+        outward = (p - v3(sp.x, sp.y, sp.z)) / sp.w;                // :60
+        sphere_uv(outward, hu, hv);                                 // :62
+    } else if ((FEAT & F_RECT) && type == rtd::LT_RECT) {
+        const Float4 r0 = sc.rects[2 * idx], r1 = sc.rects[2 * idx + 1];
+        const int kaxis = (int)r1.y & 3; const int ia = kaxis == 0 ? 1 : 0, ib = kaxis == 2 ? 1 : 2;
+        p = ol + dl * t;                                            // aarect.rs:46
+        const float a = comp(p, ia), b = comp(p, ib);
+        hu = fdiv(a - r0.x, r0.y - r0.x); hv = fdiv(b - r0.z, r0.w - r0.z);   // :41-42
+        if (kaxis == 0) p.x = r1.x; else if (kaxis == 1) p.y = r1.x; else p.z = r1.x;   // on the plane exactly
+        outward = v3(kaxis == 0 ? 1.f : 0.f, kaxis == 1 ? 1.f : 0.f, kaxis == 2 ? 1.f : 0.f);
+    } else if ((FEAT & F_MOVING) && type == rtd::LT_MOVING) {
+        const Float4 m0 = sc.moving[3 * idx], m1 = sc.moving[3 * idx + 1], m2 = sc.moving[3 * idx + 2];
+        p = ol + dl * t;
+        outward = (p - moving_center(m0, m1, m2, tm)) / m0.w;       // moving_sphere.rs:58 (u,v not set: 0)
+    } else if ((FEAT & F_TRI) && type == rtd::LT_TRI) {
+        const V3 v0 = f4xyz(sc.tris[3 * idx]), v1 = f4xyz(sc.tris[3 * idx + 1]), v2 = f4xyz(sc.tris[3 * idx + 2]);
+        float tt, bu = 0.f, bv = 0.f;
+        tri_hit(ol, dl, v0, v1, v2, -kInf, kInf, tt, bu, bv);
+        hu = bu; hv = bv;
+        p = ol + dl * t;
+        outward = unit(cross(v1 - v0, v2 - v0));
+    } else return false;
+    ff = dot(dl, outward) < 0.f;                                    // set_face_normal, hittable.rs:41-48
+    n = ff ? outward : -outward;
+    if ((FEAT & F_XFORM) && wrap) {
+        if (xf) p = xform_point_back(sc.xforms[xf], p);
+        // the wrappers from the innermost out; dk: the ray direction each wrapper hands to its child (hittable.rs:154-155)
+        V3 dk[rtd::MAX_WRAP_OPS + 1];
+        dk[0] = d;
+#pragma unroll
+        for (uint32_t k = 0; k < rtd::MAX_WRAP_OPS; ++k) {
+            const float sn = W.op[k].sin_t, cs = W.op[k].cos_t;
+            const V3 qv = dk[k];
+            dk[k + 1] = (k < W.n_ops && W.op[k].kind == rtd::WO_ROTATE_Y) ? v3(cs * qv.x - sn * qv.z, qv.y, sn * qv.x + cs * qv.z) : qv;
+        }
+#pragma unroll
+        for (int k = (int)rtd::MAX_WRAP_OPS - 1; k >= 0; --k) {
+            if ((uint32_t)k < W.n_ops) {
+                const uint32_t kind = W.op[k].kind;
+                if (kind == rtd::WO_FLIP_FACE) ff = !ff;                                   // hittable.rs:199
+                else {
+                    if (kind == rtd::WO_ROTATE_Y) {                                        // hittable.rs:169-170
+                        const float sn = W.op[k].sin_t, cs = W.op[k].cos_t;
+                        n = v3(cs * n.x + sn * n.z, n.y, -sn * n.x + cs * n.z);
+                    }
+                    ff = dot(dk[k + 1], n) < 0.f;                                          // hittable.rs:82-83 / 173
+                    n = ff ? n : -n;
+                }
+            }
+        }
+    }
+    h.p = p; h.n = n; h.u = hu; h.v = hv; h.ff = ff; h.meta = meta;
+    return true;
+}
+
+// A chunk = samples [k0, k0 + nk) of output slots [slot0, slot0 + ns): ray r = k * ns + s of the chunk is sample k0 + k of slot slot0 + s, so
+// that a wave of the import makes the rays of 64 neighbouring pixels and the fold reads its records coalesced.
+// k_features_import: lane r makes that ray with new_camera_ray — the function k_generate and k_shade call, so the ray is the render's, bit for
+// bit — and writes the pool record k_rays_import writes (s0.w = r; sd = 0; the ray starts on nothing). Workgroup b feeds queue b mod kQueues;
+// slots from the queue's size counter. A clipped slot of an edge tile makes no ray. The host keeps ns * nk <= kQueues * queue_cap.
+__global__ void __launch_bounds__(kRaysImportThreads) k_features_import(RenderDev rd, FeatDev fd, PoolDev pool, uint32_t* __restrict__ counts,
+                                                                         unsigned long long* __restrict__ counters) {
+    __shared__ uint32_t s_scan[kRaysImportThreads / 64 + 1];
+    const uint32_t r = blockIdx.x * kRaysImportThreads + threadIdx.x, q = blockIdx.x & (kQueues - 1u);
+    const uint32_t k = fdivu(r, fd.div_ns), s = r - k * fd.ns;
+    uint32_t x = 0u, y = 0u;
+    if (k < fd.nk) slot_pixel(rd, fd.slot0 + s, x, y);
+    const bool valid = k < fd.nk && x < rd.width && y < rd.height;
+    V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f); float tm = 0.f;
+    if (valid) { Rng g; new_camera_ray(rd, x, y, fd.first_sample + fd.k0 + k, g, o, d, tm); }
+    const uint32_t slot = block_alloc(valid, counts + q * kQStride, s_scan);      // every thread of the workgroup calls it
+    const bool stored = valid && slot < rd.queue_cap;
+    if (stored) {
+        const uint32_t at = q * rd.queue_cap + slot;
+        pool.ray_o[at] = Float4{o.x, o.y, o.z, tm};
+        pool.ray_d[at] = Float4{d.x, d.y, d.z, __uint_as_float(0u)};
+        pool.s0[at] = Float4{0.f, 0.f, 0.f, __uint_as_float(r)};
+        pool.sd[at] = 0u;
+    }
+    const uint64_t m = __ballot(stored);
+    if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(&counters[CTR_SEGMENTS], (unsigned long long)__popcll(m));
+}
+
+// k_features_export: (ray, hit) of every pool slot -> the ray's feature record, 32 bytes at its index in the chunk: (albedo.rgb, depth),
+// (normal.xyz, hit ? 1 : 0). Albedo: what the render's first shading step multiplies or returns — texture.value(u, v, p) of a Lambertian, the
+// albedo of a Metal, 1 for a Dielectric (mat_a holds it: scene_compile.cpp), `emitted` of a DiffuseLight (its colour on the front face, 0 on the back: shade_segment's rule),
+// the background on a miss.
+template <uint32_t FEAT>
+__global__ void __launch_bounds__(256) k_features_export(SceneDev sc, RenderDev rd, FeatDev fd, PoolDev pool, const uint32_t* __restrict__ counts) {
+    const uint32_t q = blockIdx.x & (kQueues - 1u), i = (blockIdx.x >> kQShift) * blockDim.x + threadIdx.x;
+    if (i >= min(counts[q * kQStride], rd.queue_cap)) return;
+    const uint32_t at = q * rd.queue_cap + i;
+    const Float4 ro = pool.ray_o[at], rdv = pool.ray_d[at];
+    const uint2 hit = pool.hit[at];
+    const uint32_t r = __float_as_uint(pool.s0[at].w);
+    if (r >= fd.ns * fd.nk) return;                                               // (cannot occur: the import wrote it)
+    const V3 o = v3(ro.x, ro.y, ro.z), d = v3(rdv.x, rdv.y, rdv.z);
+    Float4* rec = fd.rec + 2ull * r;
+    HitRec h;
+    if (hit.y == rtd::HIT_NONE || !rebuild_hit<FEAT>(sc, o, d, ro.w, __uint_as_float(hit.x), hit.y, h)) {
+        V3 bg = v3(rd.bg[0], rd.bg[1], rd.bg[2]);                                 // main.rs:74-76, as shade_segment forms it
+        if (rd.bg_mode == RT_BG_SKY_GRADIENT_K) {
+            const V3 ud = unit(d);
+            const float t = 0.5f * (ud.y + 1.0f);
+            bg = (1.0f - t) * v3(1.f, 1.f, 1.f) + t * bg;
+        }
+        rec[0] = Float4{bg.x, bg.y, bg.z, 0.f};
+        rec[1] = Float4{0.f, 0.f, 0.f, __uint_as_float(0u)};
+        return;
+    }
+    const uint32_t type = hit.y >> 28, idx = hit.y & rtd::LEAF_MAX_FIRST, mat = h.meta & rtd::META_MAT_MASK;
+    Float4 ma; uint32_t mb;
+    if (type == rtd::LT_SPHERE && sc.sphere_mat_a != nullptr) { ma = sc.sphere_mat_a[idx]; mb = sc.sphere_mat_b[idx]; }
+    else { ma = sc.mat_a[mat]; mb = sc.mat_b[mat]; }
+    const uint32_t kind = mb & 15u, tex = mb >> 4;
+    V3 colour = v3(ma.x, ma.y, ma.z);
+    if ((FEAT & F_TEX) && tex != rtd::TEX_INLINE && kind != rtd::MK_METAL && kind != rtd::MK_DIELECTRIC) colour = texture_value(sc, tex, h.u, h.v, h.p);
+    if (kind == rtd::MK_DIFFUSE_LIGHT && !h.ff) colour = v3(0.f, 0.f, 0.f);        // material.rs:184-190
+    rec[0] = Float4{colour.x, colour.y, colour.z, __uint_as_float(hit.x) * len(d)};
+    rec[1] = Float4{h.n.x, h.n.y, h.n.z, __uint_as_float(1u)};
+}
+
+// k_features_fold: one thread per slot of the chunk adds the slot's nk records, in sample order, in f32, into the wanted planes — from the
+// value already there when fd.accumulate is set (RT_FEATURES_ACCUMULATE, or a later sample range of the same call), else from 0. No atomics:
+// passes over [0, a) and [a, N) leave the bits of one pass over [0, N). Clipped slots are never written.
+__global__ void __launch_bounds__(256) k_features_fold(RenderDev rd, FeatDev fd) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= fd.ns) return;
+    const uint32_t slot = fd.slot0 + s;
+    uint32_t x, y; slot_pixel(rd, slot, x, y);
+    if (x >= rd.width || y >= rd.height) return;
+    float* pa = fd.albedo ? fd.albedo + 3ull * slot : nullptr;
+    float* pn = fd.normal ? fd.normal + 3ull * slot : nullptr;
+    float* pd = fd.depth ? fd.depth + slot : nullptr;
+    uint32_t* ph = fd.hits ? fd.hits + slot : nullptr;
+    V3 a = v3(0.f, 0.f, 0.f), n = v3(0.f, 0.f, 0.f); float dep = 0.f; uint32_t nh = 0u;
+    if (fd.accumulate != 0u) {
+        if (pa) a = v3(pa[0], pa[1], pa[2]);
+        if (pn) n = v3(pn[0], pn[1], pn[2]);
+        if (pd) dep = *pd;
+        if (ph) nh = *ph;
+    }
+    for (uint32_t k = 0; k < fd.nk; ++k) {
+        const Float4* rec = fd.rec + 2ull * ((uint64_t)k * fd.ns + s);
+        const Float4 r0 = rec[0], r1 = rec[1];
+        a = a + v3(r0.x, r0.y, r0.z); n = n + v3(r1.x, r1.y, r1.z); dep += r0.w; nh += __float_as_uint(r1.w);
+    }
+    if (pa) { pa[0] = a.x; pa[1] = a.y; pa[2] = a.z; }
+    if (pn) { pn[0] = n.x; pn[1] = n.y; pn[2] = n.z; }
+    if (pd) *pd = dep;
+    if (ph) *ph = nh;
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 static thread_local const char* g_launch_note = nullptr;
@@ -2407,6 +2587,31 @@ hipError_t launch_rays_export(const LaunchCfg& cfg, const SceneDev& sc, const Ra
     if (blocks == 0u) return hipSuccess;
     with_variant(cfg.features, [&](auto feat) {
         hipLaunchKernelGGL((k_rays_export<decltype(feat)::value>), dim3(blocks), dim3(256), 0, stream, sc, src, pool, queue_cap, counts, (Float4*)hits); });
+    return hipGetLastError();
+}
+
+hipError_t launch_features_import(const RenderDev& rd, const FeatDev& fd, const PoolDev& pool, uint32_t* counts, unsigned long long* counters, hipStream_t stream) {
+    const uint64_t n = (uint64_t)fd.ns * fd.nk;
+    if (n == 0u) return hipSuccess;
+    if (n > (uint64_t)kQueues * rd.queue_cap || (rd.queue_cap & 511u) != 0u) return hipErrorInvalidValue;   // (k_features_import: a slot is < queue_cap)
+    const uint32_t blocks = (uint32_t)((n + kRaysImportThreads - 1u) / kRaysImportThreads);
+    hipLaunchKernelGGL(k_features_import, dim3(blocks), dim3(kRaysImportThreads), 0, stream, rd, fd, pool, counts, counters);
+    return hipGetLastError();
+}
+
+hipError_t launch_features_export(const LaunchCfg& cfg, const SceneDev& sc, const RenderDev& rd, const FeatDev& fd, const PoolDev& pool, uint32_t max_count,
+                                  const uint32_t* counts, hipStream_t stream) {
+    const uint32_t blocks = kQueues * ((std::min(max_count, rd.queue_cap) + 255u) / 256u);   // max_count = upper bound of the rays in ONE queue
+    if (blocks == 0u) return hipSuccess;
+    with_variant(cfg.features, [&](auto feat) {
+        hipLaunchKernelGGL((k_features_export<decltype(feat)::value>), dim3(blocks), dim3(256), 0, stream, sc, rd, fd, pool, counts); });
+    return hipGetLastError();
+}
+
+hipError_t launch_features_fold(const RenderDev& rd, const FeatDev& fd, hipStream_t stream) {
+    const uint32_t blocks = (fd.ns + 255u) / 256u;
+    if (blocks == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_features_fold, dim3(blocks), dim3(256), 0, stream, rd, fd);
     return hipGetLastError();
 }
 

@@ -1201,6 +1201,150 @@ int rt_trace_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* opt
     return RT_OK;
 }
 
+// ---- first-hit features (include/rt_hip.h): albedo, normal and depth of the render's own camera rays, as per-pixel sums ---------------------
+static_assert(sizeof(RtFeatureOptions) == 16 && sizeof(RtFeatureBuffers) == 4 * sizeof(void*), "feature records: 16 bytes and four pointers");
+static int check_features(RtCtx* ctx, const RtParams* p, const RtFeatureOptions* o) {
+    const int v = validate_params(ctx, p); if (v != RT_OK) return v;
+    if (!o) return set_err(ctx, RT_ERR_INVALID, "feature options are null");
+    if (o->struct_bytes < sizeof(RtFeatureOptions) || o->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtFeatureOptions.struct_bytes is not set (sizeof(RtFeatureOptions))");
+    if (o->flags & ~(uint32_t)RT_FEATURES_ACCUMULATE) return set_err(ctx, RT_ERR_INVALID, "RtFeatureOptions.flags holds an unknown bit (known: RT_FEATURES_ACCUMULATE)");
+    if ((uint64_t)o->first_sample + p->samples_per_pixel > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "first_sample + samples_per_pixel must be < 2^32");
+    if (p->flags & (RT_FLAG_COUNTERS | RT_FLAG_FUSED)) return set_err(ctx, RT_ERR_INVALID, "a feature pass takes neither RT_FLAG_COUNTERS nor RT_FLAG_FUSED");
+    return RT_OK;
+}
+int rt_features_check(const RtParams* params, const RtFeatureOptions* options) { return check_features(nullptr, params, options); }
+
+// The chunk loop, modelled on trace_rays_impl: import (the camera rays of a chunk) -> k_extend (the scene's own launch configuration) ->
+// export (one feature record per ray) -> fold (per-slot sums), all on the context's stream; the host waits once, at the end. A chunk holds
+// the whole sample run of as many slots as the pool has room for; only a pass with more samples per pixel than pool slots is cut along the
+// samples too, its later parts folding on from the planes — the same additions in the same order, so the cut does not show.
+static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* opt, const RtFeatureBuffers* out, RtStats* stats) {
+    using clk = std::chrono::steady_clock;
+    const auto t_begin = clk::now();
+    const bool timing = (prm->flags & RT_FLAG_TIMING) != 0u;
+    Tiling tl; make_tiling(*prm, tl);
+    const uint32_t sc = prm->shard_count <= 1u ? 1u : prm->shard_count, si = prm->shard_count <= 1u ? 0u : prm->shard_index;
+    // camera, frame and tiling as render_impl sets them: what new_camera_ray and slot_pixel read
+    rtk::RenderDev rd{};
+    auto cp3 = [](float* d, const RtVec3& v) { d[0] = (float)v.x; d[1] = (float)v.y; d[2] = (float)v.z; };
+    cp3(rd.cam_origin, cam->origin); cp3(rd.cam_llc, cam->lower_left_corner); cp3(rd.cam_horizontal, cam->horizontal); cp3(rd.cam_vertical, cam->vertical);
+    cp3(rd.cam_u, cam->u); cp3(rd.cam_v, cam->v);
+    rd.cam_lens_radius = (float)cam->lens_radius; rd.cam_time0 = (float)cam->time0; rd.cam_time1 = (float)cam->time1;
+    rd.width = prm->width; rd.height = prm->height; rd.seed = prm->seed;
+    rd.bg_mode = scene->bg_mode; for (int i = 0; i < 3; ++i) rd.bg[i] = scene->bg[i];
+    rd.tile_size = tl.ts; rd.tiles_x = tl.tiles_x; rd.tiles_y = tl.tiles_y; rd.shard_index = si; rd.shard_count = sc; rd.n_local_tiles = tl.n_local;
+    rd.div_width = rtk::make_fastdiv(prm->width); rd.div_ts = rtk::make_fastdiv(tl.ts); rd.div_ts2 = rtk::make_fastdiv(tl.ts * tl.ts); rd.div_tiles_x = rtk::make_fastdiv(tl.tiles_x);
+    rd.div_nblocks = rtk::make_fastdiv(1u); rd.n_blocks = 1u;                 // (a walk needs the queue geometry only; first_in_shade = 0: the record's time slot is the ray's time)
+    const uint64_t n_slots = sc <= 1u ? (uint64_t)prm->width * prm->height : (uint64_t)tl.n_local * tl.ts * tl.ts;
+    if (n_slots == 0u) return RT_OK;
+    if (n_slots > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "more than 2^32 - 1 output slots in one shard (shard the image further)");
+    const uint64_t spp = prm->samples_per_pixel, n_rays = n_slots * spp;
+
+    // the pool, by the renderer's rule (trace_rays_impl), plus 32 bytes of feature record per ray in flight
+    const size_t rec[5] = {16, 16, 8, 16, 4};   // ray_o ray_d hit s0 sd
+    size_t slot_bytes = 32; for (size_t b : rec) slot_bytes += b;
+    uint32_t P = opt->pool_slots ? opt->pool_slots : (1u << 28);
+    P = (uint32_t)std::min<uint64_t>(P, n_rays);
+    if (!opt->pool_slots) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            size_t held = ctx->feature_rec.bytes; for (int a = 0; a < 5; ++a) held += ctx->pool[0][a].bytes;
+            const size_t budget = (free_b + held) * 7 / 10;
+            while (P > (1u << 20) && (size_t)P * slot_bytes > budget) P >>= 1;
+        }
+    }
+    constexpr uint32_t kGrain = 512u * rtk::kQueues;
+    P = std::max<uint32_t>(kGrain, (uint32_t)std::min<uint64_t>(((uint64_t)P + kGrain - 1u) / kGrain * kGrain, 0xFFFFF000ull));
+    rd.queue_cap = P / rtk::kQueues; rd.q_lo = 0u; rd.q_n = rtk::kQueues; rd.q_shift = rtk::kQShift;
+    rtk::PoolDev pd{};
+    for (int a = 0; a < 5; ++a) HIP_TRY(ctx, ctx->pool[0][a].ensure((size_t)P * rec[a]));
+    HIP_TRY(ctx, ctx->feature_rec.ensure((size_t)P * 32u));
+    pd.ray_o = (rtd::Float4*)ctx->pool[0][0].p; pd.ray_d = (rtd::Float4*)ctx->pool[0][1].p; pd.hit = (uint2*)ctx->pool[0][2].p;
+    pd.s0 = (rtd::Float4*)ctx->pool[0][3].p; pd.sd = (uint32_t*)ctx->pool[0][4].p; pd.s1 = nullptr;
+    // the render's counter block (render_impl): line 1 queue heads, line 2 the queues' sizes, line 3 what k_extend zeroes for a k_shade that never runs here
+    constexpr size_t kLine = 128, kQ = rtk::kQueues;
+    const size_t counter_bytes = 4 * kQ * kLine + sizeof(unsigned long long) * 16;
+    HIP_TRY(ctx, ctx->counters.ensure(counter_bytes));
+    char* cbase = (char*)ctx->counters.p;
+    uint32_t* c_head = (uint32_t*)(cbase + 1 * kQ * kLine);
+    uint32_t* c_count = (uint32_t*)(cbase + 2 * kQ * kLine);
+    uint32_t* c_other = (uint32_t*)(cbase + 3 * kQ * kLine);
+    unsigned long long* c64 = (unsigned long long*)(cbase + 4 * kQ * kLine);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, counter_bytes, ctx->stream));
+
+    rtk::LaunchCfg cfg{};
+    uint32_t extend_geometry[2] = {0u, 0u};
+    cfg.n_cu = (uint32_t)ctx->n_cu; cfg.extend_geometry = extend_geometry; cfg.features = scene->features; cfg.scene_in_lds = scene->in_lds;
+    rtk::FeatDev fd{};
+    fd.first_sample = opt->first_sample; fd.rec = (rtd::Float4*)ctx->feature_rec.p;
+    fd.albedo = (float*)out->albedo_sum; fd.normal = (float*)out->normal_sum; fd.depth = (float*)out->depth_sum; fd.hits = (uint32_t*)out->hits;
+
+    size_t ev_used = 0;
+    auto next_event = [&](hipEvent_t& ev) -> hipError_t {
+        if (ev_used == ctx->events.size()) { hipEvent_t e; hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; ctx->events.push_back(e); }
+        ev = ctx->events[ev_used++];
+        return hipEventRecord(ev, ctx->stream);
+    };
+    struct Span { hipEvent_t a, b; int kind; };
+    std::vector<Span> spans;
+    uint32_t launched = 0u;
+    const uint32_t nk_max = (uint32_t)std::min<uint64_t>(spp, P), ns_max = P / nk_max;      // samples and slots of a chunk: nk * ns <= P
+    for (uint64_t k0 = 0; k0 < spp; k0 += nk_max) {
+        fd.k0 = (uint32_t)k0; fd.nk = (uint32_t)std::min<uint64_t>(nk_max, spp - k0);
+        fd.accumulate = (opt->flags & RT_FEATURES_ACCUMULATE) != 0u || k0 != 0u ? 1u : 0u;
+        for (uint64_t slot0 = 0; slot0 < n_slots; slot0 += ns_max) {
+            fd.slot0 = (uint32_t)slot0; fd.ns = (uint32_t)std::min<uint64_t>(ns_max, n_slots - slot0); fd.div_ns = rtk::make_fastdiv(fd.ns);
+            const uint32_t n = fd.ns * fd.nk;
+            hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr, ed = nullptr, ee = nullptr;
+            if (launched != 0u) HIP_TRY(ctx, hipMemsetAsync(cbase, 0, 4 * kQ * kLine, ctx->stream));     // heads and sizes of the chunk before (the 64-bit statistics stay)
+            if (timing) HIP_TRY(ctx, next_event(ea));
+            LAUNCH_TRY(rtk::launch_features_import(rd, fd, pd, c_count, c64, ctx->stream));
+            if (timing) HIP_TRY(ctx, next_event(eb));
+            cfg.max_rays = n;
+            LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd, rd, c_count, c_head, c_other, c64, false, ctx->stream));
+            if (timing) HIP_TRY(ctx, next_event(ec));
+            // a queue holds at most its share of the chunk's 512-ray groups
+            const uint32_t per_queue = std::min<uint32_t>(rd.queue_cap, ((n + 511u) / 512u + rtk::kQueues - 1u) / rtk::kQueues * 512u);
+            LAUNCH_TRY(rtk::launch_features_export(cfg, scene->dev, rd, fd, pd, per_queue, c_count, ctx->stream));
+            if (timing) HIP_TRY(ctx, next_event(ed));
+            LAUNCH_TRY(rtk::launch_features_fold(rd, fd, ctx->stream));
+            if (timing) { HIP_TRY(ctx, next_event(ee)); spans.push_back({ea, eb, 1}); spans.push_back({eb, ec, 0}); spans.push_back({ec, ed, 2}); spans.push_back({ed, ee, 3}); }
+            ++launched;
+        }
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, c64, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) {
+        double part_ms[4] = {0.0, 0.0, 0.0, 0.0};                     // extend, import, export, fold
+        for (const Span& s : spans) { float ms = 0.f; if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) part_ms[s.kind] += ms; }
+        stats->extend_ms = part_ms[0]; stats->other_ms = part_ms[1] + part_ms[2] + part_ms[3];
+        for (int k = 0; k < 3; ++k) stats->debug[k] = (uint64_t)(part_ms[k + 1] * 1000.0 + 0.5);     // microseconds of the import, export and fold kernels
+        stats->samples = stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];
+        stats->debug[6] = extend_geometry[0]; stats->debug[7] = extend_geometry[1];
+        stats->iterations = launched; stats->extend_launches = launched; stats->pool_slots = P; stats->n_devices = 1u; stats->lds_top_nodes = scene->dev.n_top;
+        stats->scene_nodes = scene->n_nodes; stats->scene_prims = scene->n_prims; stats->scene_bytes = scene->bytes; stats->bvh_in_lds = scene->in_lds ? 1u : 0u;
+        stats->render_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
+    }
+    return RT_OK;
+}
+
+int rt_render_features_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* options, const RtFeatureBuffers* buffers,
+                              RtStats* stats) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    if (!scene || !cam) return set_err(ctx, RT_ERR_INVALID, "scene / cam is null");
+    const int v = check_features(ctx, prm, options); if (v != RT_OK) return v;
+    if (scene->features & rtk::F_MEDIUM)
+        return set_err(ctx, RT_ERR_UNSUPPORTED, "first-hit features: the scene holds a ConstantMedium (the limit of ray queries: its hit is a draw of the path's medium stream)");
+    if (!buffers || (!buffers->albedo_sum && !buffers->normal_sum && !buffers->depth_sum && !buffers->hits)) return set_err(ctx, RT_ERR_INVALID, "no feature buffer is wanted (all four pointers are null)");
+    if (((uintptr_t)buffers->albedo_sum | (uintptr_t)buffers->normal_sum | (uintptr_t)buffers->depth_sum | (uintptr_t)buffers->hits) & 15u)
+        return set_err(ctx, RT_ERR_INVALID, "feature buffers must be 16-byte aligned");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int r = features_impl(ctx, scene, cam, prm, options, buffers, stats);
+    if (r != RT_OK) { const std::string keep = ctx->err; (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); ctx->err = keep; g_last_error = keep; }
+    return r;
+}
+
 int rt_untile(const RtParams* p, const float* gathered, float* rgb_sum) { return untile_host<float>(p, gathered, rgb_sum); }
 int rt_untile_rgb8(const RtParams* p, const uint8_t* gathered, uint8_t* rgb8) { return untile_host<uint8_t>(p, gathered, rgb8); }
 

@@ -55,6 +55,7 @@ struct RtCtx {
     rti::DevBuf list_map;                        // adaptive sampling: output slot -> list index of a list pass (rt_render_pass_pixels_device)
     rti::DevBuf sel_masks, sel_offsets, adaptive_word;   // rt_adaptive_select's wave ballots and their scan; the list check's verdict / the list's length
     rti::OwnedDevBuf rays_tmp, hits_tmp;         // rt_trace_rays (host variant): the caller's rays and hits on their way to and from the device
+    rti::OwnedDevBuf feature_rec;                // rt_render_features_device: the per-ray feature records of a chunk between export and fold (kernels.h FeatDev)
     rti::OwnedDevBuf denoise_planes;             // rt_denoise_device: per-pixel mean and variance of the mean, three float2 planes (denoise.hip)
     uint32_t fail_renders = 0;                   // rt_test_fail_next_renders: renders still to fail (fault injection for the failure-path tests)
 };

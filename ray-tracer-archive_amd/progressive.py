@@ -202,6 +202,13 @@ class Progressive:
         sq = torch.from_numpy(np.ascontiguousarray(self.sq_sum()).reshape(-1)).to(dev)
         return denoise_frame(self.ctx, rgb, sq, p.width, p.height, self.samples_per_item, counts=torch.from_numpy(cnt.reshape(-1)).to(dev), rgb8=rgb8, **opts)
 
+    def features(self, samples):
+        """First-hit features of this frame's camera rays (rt_render_features_device), from a pass of its own of `samples` samples per pixel
+        — uniform, independent of the radiance samples held: (albedo (H, W, 3), normal (H, W, 3), depth (H, W), hit fraction (H, W)), f32
+        means; normal and depth over the samples that hit. A sharded frame is untiled first."""
+        from .features import feature_means
+        return feature_means(self.ctx, self.scene, self.cam, self.params, samples)
+
     def save(self, path):
         """An .npz checkpoint: the sums, samples_done, frame_samples, the RtParams fields, the camera and the scene fingerprint."""
         z = dict(version=np.int64(CHECKPOINT_VERSION), samples_done=np.int64(self.samples_done), frame_samples=np.int64(self.frame_samples),
