@@ -137,6 +137,14 @@ pub struct RtDenoiseOptions {
     pub struct_bytes: u32, pub window_radius: u32, pub patch_radius: u32, pub samples_per_item: u32,
     pub strength: f64, pub alpha: f64, pub eps: f64,
 }
+// guided denoising (rt_denoise_guided_device): full-frame feature planes of rt_render_features_device; a sigma left 0 takes its default
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct RtDenoiseGuide {
+    pub struct_bytes: u32, pub feature_samples: u32,
+    pub albedo_sum: *const c_void, pub normal_sum: *const c_void, pub depth_sum: *const c_void, pub hits: *const c_void,
+    pub sigma_albedo: f64, pub sigma_normal: f64, pub sigma_depth: f64,
+}
+pub const RT_DENOISE_GUIDED_MAX_WINDOW_RADIUS: u32 = 10;
 // ray queries: the closest hit of caller-supplied rays (rt_trace_rays); t_max <= 0 or +inf = no limit
 #[repr(C)] #[derive(Clone, Copy, Default, Debug)]
 pub struct RtRay { pub o: [f32; 3], pub time: f32, pub d: [f32; 3], pub t_max: f32 }
@@ -232,6 +240,12 @@ extern "C" {
     /// filtered MEAN radiance (width * height * 3 f32) from rgb_sum, sq_sum and the sample count; counts_device null = uniform `samples`
     pub fn rt_denoise_device(ctx: *mut RtCtx, options: *const RtDenoiseOptions, width: u32, height: u32, rgb_sum_device: *const c_void,
                              sq_sum_device: *const c_void, samples: u32, counts_device: *const c_void, mean_out_device: *mut c_void) -> c_int;
+    /// host only: validates a frame size, denoise options (null = defaults; window_radius <= 10 here) and a guide
+    pub fn rt_denoise_guided_check(width: u32, height: u32, options: *const RtDenoiseOptions, guide: *const RtDenoiseGuide) -> c_int;
+    /// rt_denoise_device with the weights joined with albedo, normal and log depth of the first hit (binary16 guide records)
+    pub fn rt_denoise_guided_device(ctx: *mut RtCtx, options: *const RtDenoiseOptions, guide: *const RtDenoiseGuide, width: u32, height: u32,
+                                    rgb_sum_device: *const c_void, sq_sum_device: *const c_void, samples: u32, counts_device: *const c_void,
+                                    mean_out_device: *mut c_void) -> c_int;
     /// host only: validates ray-query options (null = defaults) and a ray count
     pub fn rt_ray_query_check(options: *const RtRayQueryOptions, n_rays: u64) -> c_int;
     /// closest hits of n_rays RtRay records in device memory, one RtRayHit each (device memory, 16-byte aligned)

@@ -420,6 +420,51 @@ int rt_denoise_check(uint32_t width, uint32_t height, const RtDenoiseOptions* op
 int rt_denoise_device(RtCtx* ctx, const RtDenoiseOptions* options /* NULL = defaults */, uint32_t width, uint32_t height, const void* rgb_sum_device,
                       const void* sq_sum_device, uint32_t samples, const void* counts_device /* NULL = uniform `samples` */, void* mean_out_device);
 
+/* ---- denoising, guided: the same filter with its weights joined with first-hit features ----------------------------------------------------
+ *
+ * rt_denoise_device's inputs plus full-frame feature planes as rt_render_features_device writes them with shard_count <= 1: albedo_sum and
+ * normal_sum (3 f32 per pixel), depth_sum (1 f32), hits (1 u32), folded over feature_samples = n_f >= 1 samples per pixel (uniform,
+ * independent of the radiance counts). The sample variance cannot tell a noisy pixel from a texture or geometry edge at low counts; the
+ * features, nearly noise-free, can.
+ * COLOUR PART: u, v, validity and the patch distance d(p,q) are exactly those above; PREPARE and FILTER do not change.
+ * GUIDE, per pixel, computed in f64, rounded to f32, then to IEEE binary16 (round to nearest even) and clamped to +-65504; h = hits:
+ *     A_c = albedo_sum_c / n_f / sigma_albedo        c = 0..2
+ *     N_c = normal_sum_c / n_f / sigma_normal        c = 0..2; over ALL samples, not over the hits: a pixel partly on the background has
+ *                                                    a shorter mean normal, so coverage is part of the guide
+ *     Z   = ln(max(depth_sum / h, 1e-30)) / sigma_depth   when h > 0, else 0 (log depth: a plain difference is a relative depth difference)
+ *     g(p,q) = the sum over the 7 components of (F_p - F_q)^2, formed in f32 from the binary16 values; pointwise, no patch
+ *     w(p,q) = exp(-(max(d(p,q), 0) + g(p,q)))       (w(p,p) = 1)
+ *     out[p] = sum_q w(p,q) u[q] / sum_q w(p,q)      accumulated as differences from u[p]: a constant frame returns bit for bit
+ * A plane pointer that is NULL makes its components 0. depth_sum requires hits. All three guide planes NULL is RT_ERR_INVALID (that
+ * filter is rt_denoise_device). A pixel is additionally INVALID when one of its feature sums is not finite or hits > n_f; invalid pixels
+ * behave as above: copied through, nobody's neighbour, no patch tap.
+ * Sigmas: a field left 0 takes its default (sigma_albedo 0.2, sigma_normal 0.5, sigma_depth 0.2: the best triple of the grid measured in
+ * DESIGN.md §10); a negative, NaN, infinite or -0.0 value, or one whose f32 reciprocal is not finite and positive, is RT_ERR_INVALID.
+ * Caps: patch_radius <= 4 as above; window_radius <= RT_DENOISE_GUIDED_MAX_WINDOW_RADIUS = 10, refused above: the guide records of the
+ * tile plus an r halo are staged in LDS beside the colour planes (at r 10, f 4: 60 x 60 x 24 B + 52 x 52 x 16 B + 23,040 B of box-sum
+ * buffers = 152,704 B of 163,840 B), and the binary16 records are what makes them fit.
+ * Determinism: the result is a function of the inputs and options alone — not of where tiles fall or of the call count; no atomics, every
+ * pixel folds in one fixed order. mean_out must not be one of the inputs, the feature planes included; the inputs are never written. */
+#define RT_DENOISE_GUIDED_MAX_WINDOW_RADIUS 10
+typedef struct RtDenoiseGuide {
+    uint32_t struct_bytes;      /* sizeof(RtDenoiseGuide) as the caller compiled it (the struct may grow at its end) */
+    uint32_t feature_samples;   /* n_f >= 1: the samples per pixel the planes were folded over */
+    const void* albedo_sum;     /* device, width * height * 3 f32; NULL = not used */
+    const void* normal_sum;     /* device, width * height * 3 f32; NULL = not used */
+    const void* depth_sum;      /* device, width * height f32; NULL = not used; needs hits */
+    const void* hits;           /* device, width * height u32; NULL = none */
+    double sigma_albedo;        /* 0 = 0.2 */
+    double sigma_normal;        /* 0 = 0.5 */
+    double sigma_depth;         /* 0 = 0.2 */
+} RtDenoiseGuide;
+/* Host only, no device: validates (width, height, options; NULL = defaults, guide) and reports the reason through rt_last_error. The plane
+   pointers are only tested against NULL. */
+int rt_denoise_guided_check(uint32_t width, uint32_t height, const RtDenoiseOptions* options, const RtDenoiseGuide* guide);
+/* Three kernels on the context's stream; blocks until done. A refused call writes nothing. */
+int rt_denoise_guided_device(RtCtx* ctx, const RtDenoiseOptions* options /* NULL = defaults */, const RtDenoiseGuide* guide, uint32_t width, uint32_t height,
+                             const void* rgb_sum_device, const void* sq_sum_device, uint32_t samples, const void* counts_device /* NULL = uniform `samples` */,
+                             void* mean_out_device);
+
 /* ---- ray queries: the closest hit of caller-supplied rays ----------------------------------------------------------------------------------
  *
  * hits[i] is the HitRecord that `world.hit(ray_i, 0.001, inf)` returns (main.rs:74, hittable.rs:11-19) for the uploaded scene: t, p, the

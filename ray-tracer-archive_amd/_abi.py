@@ -18,6 +18,7 @@ RT_OUT_RGB_SUM_F32, RT_OUT_RGB8 = 0, 1
 RT_PASS_ACCUMULATE = 1
 RT_COMM_ID_BYTES = 128
 RT_DENOISE_MAX_WINDOW_RADIUS, RT_DENOISE_MAX_PATCH_RADIUS = 16, 4
+RT_DENOISE_GUIDED_MAX_WINDOW_RADIUS = 10
 RT_RAYHIT_HIT, RT_RAYHIT_FRONT_FACE, RT_RAYHIT_INVALID_RAY = 1, 2, 4
 RT_FEATURES_ACCUMULATE = 1
 # RtUploadOptions.layout_flags
@@ -119,6 +120,11 @@ class RtDenoiseOptions(C.Structure):
                 ("strength", C.c_double), ("alpha", C.c_double), ("eps", C.c_double)]
 
 
+class RtDenoiseGuide(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("feature_samples", C.c_uint32), ("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p),
+                ("depth_sum", C.c_void_p), ("hits", C.c_void_p), ("sigma_albedo", C.c_double), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double)]
+
+
 class RtRay(C.Structure):
     _fields_ = [("o", C.c_float * 3), ("time", C.c_float), ("d", C.c_float * 3), ("t_max", C.c_float)]
 
@@ -154,7 +160,7 @@ RT_HIP_SYMBOLS = ["rt_ctx_create", "rt_ctx_destroy", "rt_scene_upload", "rt_scen
                   "rt_runtime_libraries", "rt_test_fail_next_renders", "rt_test_device_workers", "rt_scene_compile_info_ex", "rt_scene_compile_dump_ex", "rt_scene_wide_layout_check",
                   "rt_pass_check", "rt_render_pass", "rt_render_pass_device",
                   "rt_adaptive_check", "rt_adaptive_select", "rt_render_pass_pixels_device", "rt_resolve_counts_device",
-                  "rt_denoise_check", "rt_denoise_device",
+                  "rt_denoise_check", "rt_denoise_device", "rt_denoise_guided_check", "rt_denoise_guided_device",
                   "rt_ray_query_check", "rt_trace_rays_device", "rt_trace_rays",
                   "rt_features_check", "rt_render_features_device"]
 RT_HOST_SYMBOLS = ["rt_host_scene_create", "rt_host_scene_desc", "rt_host_scene_camera", "rt_host_scene_destroy", "rt_host_camera_new",
@@ -211,6 +217,10 @@ def declare(lib):
     lib.rt_denoise_check.argtypes = [u32, u32, P(RtDenoiseOptions)]
     lib.rt_denoise_device.restype = i32
     lib.rt_denoise_device.argtypes = [vp, P(RtDenoiseOptions), u32, u32, vp, vp, u32, vp, vp]
+    lib.rt_denoise_guided_check.restype = i32
+    lib.rt_denoise_guided_check.argtypes = [u32, u32, P(RtDenoiseOptions), P(RtDenoiseGuide)]
+    lib.rt_denoise_guided_device.restype = i32
+    lib.rt_denoise_guided_device.argtypes = [vp, P(RtDenoiseOptions), P(RtDenoiseGuide), u32, u32, vp, vp, u32, vp, vp]
     lib.rt_ray_query_check.restype = i32
     lib.rt_ray_query_check.argtypes = [P(RtRayQueryOptions), u64]
     lib.rt_trace_rays_device.restype = i32

@@ -74,6 +74,19 @@ def denoise_check(width, height, options=None):
     _check(lib().rt_denoise_check(width, height, C.byref(options) if options is not None else None))
 
 
+def denoise_guide(feature_samples, albedo=None, normal=None, depth=None, hits=None, sigma_albedo=0.0, sigma_normal=0.0, sigma_depth=0.0):
+    """RtDenoiseGuide (include/rt_hip.h, "denoising, guided"): the feature planes of rt_render_features_device — CUDA tensors, raw device
+    addresses, or None for a plane not used — folded over feature_samples samples per pixel; a sigma left 0 takes its default."""
+    ptr = lambda t: None if t is None else int(t) if isinstance(t, int) else t.data_ptr()
+    return A.RtDenoiseGuide(C.sizeof(A.RtDenoiseGuide), int(feature_samples), ptr(albedo), ptr(normal), ptr(depth), ptr(hits),
+                            float(sigma_albedo), float(sigma_normal), float(sigma_depth))
+
+
+def denoise_guided_check(width, height, options, guide):
+    """rt_denoise_guided_check (host only): raises RtError (RT_ERR_INVALID, with the reason) for what the guided filter refuses."""
+    _check(lib().rt_denoise_guided_check(width, height, C.byref(options) if options is not None else None, C.byref(guide) if guide is not None else None))
+
+
 # numpy views of RtRay / RtRayHit (include/rt_hip.h, "ray queries"): 32 and 48 bytes, field for field
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("time", np.float32), ("d", np.float32, 3), ("t_max", np.float32)])
 RAYHIT_DTYPE = np.dtype([("t", np.float32), ("hittable", np.int32), ("material", np.int32), ("flags", np.uint32),
@@ -496,6 +509,31 @@ class Context:
         _check(lib().rt_denoise_device(self._h, C.byref(options) if options is not None else None, width, height, C.c_void_p(rgb_sum.data_ptr()),
                                        C.c_void_p(sq_sum.data_ptr()), int(samples), C.c_void_p(counts.data_ptr()) if counts is not None else None,
                                        C.c_void_p(out.data_ptr())), self._h)
+        return out
+
+    def denoise_guided(self, rgb_sum, sq_sum, width, height, feature_samples, albedo=None, normal=None, depth=None, hits=None, samples=0, counts=None,
+                       options=None, sigma_albedo=0.0, sigma_normal=0.0, sigma_depth=0.0, out=None):
+        """rt_denoise_guided_device: Context.denoise with the weights joined with full-frame feature planes (render_features with
+        shard_count <= 1: albedo / normal float32 of width * height * 3, depth float32 and hits 32-bit integers of width * height; None =
+        not used) folded over feature_samples samples. Returns `out`; a refused call raises RtError and leaves `out` untouched."""
+        import torch
+        n = 3 * width * height
+        _check_device(rgb_sum, sq_sum, n=n, what="rgb_sum / sq_sum", float_=True)
+        if counts is not None:
+            _check_device(counts, None, n=width * height, what="counts", float_=False)
+        _check_device(albedo, normal, n=n, what="albedo / normal", float_=True)
+        _check_device(depth, None, n=width * height, what="depth", float_=True)
+        _check_device(hits, None, n=width * height, what="hits", float_=False)
+        if any(t is not None and t.device != rgb_sum.device for t in (albedo, normal, depth, hits, counts, sq_sum)):
+            raise ValueError("the sums, the counts and the feature planes must live on one device")
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=rgb_sum.device)
+        _check_device(out, None, n=n, what="out", float_=True)
+        guide = denoise_guide(feature_samples, albedo, normal, depth, hits, sigma_albedo, sigma_normal, sigma_depth)
+        torch.cuda.synchronize(rgb_sum.device)        # the library's stream is not torch's
+        _check(lib().rt_denoise_guided_device(self._h, C.byref(options) if options is not None else None, C.byref(guide), width, height,
+                                              C.c_void_p(rgb_sum.data_ptr()), C.c_void_p(sq_sum.data_ptr()), int(samples),
+                                              C.c_void_p(counts.data_ptr()) if counts is not None else None, C.c_void_p(out.data_ptr())), self._h)
         return out
 
     # ---- one process per GPU: RCCL communicator on this context (rt_multi.cpp) ----

@@ -5,6 +5,10 @@
 //                   window offset: the pointwise term on the tile plus an f halo, its patch sum as a separable box sum through LDS, the
 //                   weight, and the sums of w and w (u[q] - u[p]) in registers. No atomics; every pixel's sums are folded in one fixed
 //                   order (window rows, then columns; patch taps ascending), so the result does not depend on where tiles fall.
+//   k_nlm_guide_prepare / k_nlm_guided<F> : the guided filter (rt_hip.h, "denoising, guided"): per pixel one 16-byte record of 7 binary16
+//                   guide components; k_nlm's loop with the records of the tile plus an r halo staged beside the planes and
+//                   g(p,q) added to the patch distance in step (C). k_nlm and nlm_window are pinned (text and ISA), so the guided loop
+//                   is a second function beside them, not a flag in them.
 // The entry points live here, not in rt_api.cpp: nothing the render path is built from changes with this file.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -232,6 +236,244 @@ int nlm_options(RtCtx* ctx, uint32_t width, uint32_t height, const RtDenoiseOpti
     return RT_OK;
 }
 
+
+// ---- guided: the weights joined with first-hit features (rt_hip.h, "denoising, guided") ------------------------------------------------------
+constexpr int kMaxWindowGuided = 10;   // RT_DENOISE_GUIDED_MAX_WINDOW_RADIUS (static_assert below)
+
+struct GuideArgs {
+    const float* albedo; const float* normal; const float* depth; const uint32_t* hits;   // any may be null (depth needs hits)
+    uint32_t n_f;
+    double sigma_albedo, sigma_normal, sigma_depth;
+};
+
+// f64 -> f32 -> binary16 (v_cvt_f16_f32, round to nearest even), clamped to +-65504. The clamp is made on the f32 value: every f32 in
+// (65504, 65520) rounds to 65504 and everything from 65520 on to inf, which the clamp brings back to 65504, so the two orders agree.
+__device__ inline uint32_t guide_half(double x) {
+    const float f = fminf(fmaxf((float)x, -65504.f), 65504.f);
+    return (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)f);
+}
+
+// One thread per pixel, f64: the pixel's guide record (A0 A1 A2 N0 N1 N2 Z 0 as binary16). A pixel the guide makes invalid is marked in
+// the colour planes k_nlm_prepare left (v0 = -1), so staging the tile sees one kind of invalid pixel; its record is 0.
+__global__ void __launch_bounds__(256) k_nlm_guide_prepare(GuideArgs g, uint32_t n_pixels, uint4* __restrict__ rec, float2* __restrict__ planes) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pixels) return;
+    const double nf = (double)g.n_f;
+    double F[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    bool valid = true;
+    for (int c = 0; c < 3; ++c) {
+        if (g.albedo) { const double s = (double)g.albedo[(uint64_t)p * 3u + c]; valid = valid && isfinite(s); F[c] = s / nf / g.sigma_albedo; }
+        if (g.normal) { const double s = (double)g.normal[(uint64_t)p * 3u + c]; valid = valid && isfinite(s); F[3 + c] = s / nf / g.sigma_normal; }
+    }
+    const uint32_t h = g.hits ? g.hits[p] : 0u;
+    if (h > g.n_f) valid = false;
+    if (g.depth) {
+        const double s = (double)g.depth[p];
+        valid = valid && isfinite(s);
+        if (h > 0u) F[6] = log(fmax(s / (double)h, 1e-30)) / g.sigma_depth;
+    }
+    uint4 r = make_uint4(0u, 0u, 0u, 0u);
+    if (valid) {
+        r.x = guide_half(F[0]) | (guide_half(F[1]) << 16); r.y = guide_half(F[2]) | (guide_half(F[3]) << 16);
+        r.z = guide_half(F[4]) | (guide_half(F[5]) << 16); r.w = guide_half(F[6]);
+    } else {
+        planes[(uint64_t)n_pixels + p].y = -1.f;
+        planes[2ull * n_pixels + p] = make_float2(0.f, 0.f);
+    }
+    rec[p] = r;
+}
+
+__device__ inline float half_lo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xFFFFu)); }
+__device__ inline float half_hi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+__device__ inline void guide_unpack(const uint4& r, float f[7]) {
+    f[0] = half_lo(r.x); f[1] = half_hi(r.x); f[2] = half_lo(r.y); f[3] = half_hi(r.y); f[4] = half_lo(r.z); f[5] = half_hi(r.z); f[6] = half_lo(r.w);
+}
+
+// nlm_window with the guide: steps (A) and (B) are nlm_window's; step (C) reads the partner's record (one ds_read_b128; a wave's 64 records
+// are two rows of 32 contiguous 16-byte slots: no bank conflict) and adds g(p,q) to max(d, 0). G: (kTile + 2 r)^2 records, this thread's at gp.
+template <int F, bool MASKED>
+__device__ inline void nlm_guided_window(const NlmArgs& a, const float2* P0, const float2* P1, const float2* P2, const uint4* G, float* bT, float* bH, float* bTM,
+                                         float* bHM, int EW, int GW, bool p_valid, int ep, int gp, float up0, float up1, float up2, float& sw, float& s0,
+                                         float& s1, float& s2) {
+    constexpr int AW = kTile + 2 * F, AH = kTile + 2 * F, TAPS = 2 * F + 1;
+    const int tid = (int)threadIdx.x, r = a.r;
+    const int px = tid & (kTile - 1), py = tid / kTile;
+    int ae[2]; bool a_on[2], a_valid[2]; float ua[2][3], va[2][3];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int i = tid + s * kThreads;
+        a_on[s] = i < AW * AH;
+        const int ay = a_on[s] ? i / AW : 0, ax = a_on[s] ? i - ay * AW : 0;
+        ae[s] = (ay + r) * EW + ax + r;
+        const float2 q0 = P0[ae[s]], q1 = P1[ae[s]], q2 = P2[ae[s]];
+        ua[s][0] = q0.x; ua[s][1] = q0.y; ua[s][2] = q1.x; va[s][0] = q1.y; va[s][1] = q2.x; va[s][2] = q2.y;
+        a_valid[s] = a_on[s] && q1.y >= 0.f;
+    }
+    float fp[7];
+    guide_unpack(G[gp], fp);
+    const float inv_all = __builtin_amdgcn_rcpf((float)(3 * TAPS * TAPS));
+    for (int dy = -r; dy <= r; ++dy) {
+        for (int dx = -r; dx <= r; ++dx) {
+            const int off = dy * EW + dx;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                if (!a_on[s]) continue;
+                const int e = ae[s] + off;
+                const float2 q0 = P0[e], q1 = P1[e], q2 = P2[e];
+                const bool part = a_valid[s] && q1.y >= 0.f;
+                const float t = nlm_term(ua[s][0], va[s][0], q0.x, q1.y, a.k2, a.alpha, a.eps) + nlm_term(ua[s][1], va[s][1], q0.y, q2.x, a.k2, a.alpha, a.eps) +
+                                nlm_term(ua[s][2], va[s][2], q1.x, q2.y, a.k2, a.alpha, a.eps);
+                bT[tid + s * kThreads] = part ? t : 0.f;
+                if (MASKED) bTM[tid + s * kThreads] = part ? 1.f : 0.f;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const int j = tid + s * kThreads;
+                if (j >= AH * kTile) continue;
+                const int row = j / kTile, x = j & (kTile - 1);
+                const float* src = bT + row * AW + x;
+                float h = src[0];
+#pragma unroll
+                for (int t = 1; t < TAPS; ++t) h += src[t];
+                bH[j] = h;
+                if (MASKED) {
+                    const float* srm = bTM + row * AW + x;
+                    float hm = srm[0];
+#pragma unroll
+                    for (int t = 1; t < TAPS; ++t) hm += srm[t];
+                    bHM[j] = hm;
+                }
+            }
+            __syncthreads();
+            const float* col = bH + py * kTile + px;
+            float D = col[0];
+#pragma unroll
+            for (int t = 1; t < TAPS; ++t) D += col[t * kTile];
+            float inv = inv_all;
+            if (MASKED) {
+                const float* cm = bHM + py * kTile + px;
+                float cnt = cm[0];
+#pragma unroll
+                for (int t = 1; t < TAPS; ++t) cnt += cm[t * kTile];
+                inv = __builtin_amdgcn_rcpf(3.f * fmaxf(cnt, 1.f));
+            }
+            const float2 q0 = P0[ep + off], q1 = P1[ep + off];
+            const uint4 gq = G[gp + dy * GW + dx];
+            if (p_valid && q1.y >= 0.f) {
+                float fq[7];
+                guide_unpack(gq, fq);
+                float g = 0.f;
+#pragma unroll
+                for (int c = 0; c < 7; ++c) { const float d = fp[c] - fq[c]; g = fmaf(d, d, g); }
+                const float w = __expf(-(fmaxf(D * inv, 0.f) + g));
+                sw += w;
+                s0 = fmaf(w, q0.x - up0, s0);
+                s1 = fmaf(w, q0.y - up1, s1);
+                s2 = fmaf(w, q1.x - up2, s2);
+            }
+        }
+    }
+}
+
+template <int F>
+__global__ void __launch_bounds__(kThreads) k_nlm_guided(NlmArgs a, const uint4* __restrict__ guide) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int AW = kTile + 2 * F, AH = kTile + 2 * F;
+    const int halo = a.r + F, EW = kTile + 2 * halo, EH = EW, GW = kTile + 2 * a.r, tid = (int)threadIdx.x;
+    float2* P0 = (float2*)smem; float2* P1 = P0 + EW * EH; float2* P2 = P1 + EW * EH;
+    uint4* G = (uint4*)(P2 + EW * EH);            // EW is even: 24 EW^2 is a multiple of 16
+    float* bT = (float*)(G + GW * GW); float* bH = bT + AW * AH; float* bTM = bH + AH * kTile; float* bHM = bTM + AW * AH;
+    const int x0 = (int)blockIdx.x * kTile, y0 = (int)blockIdx.y * kTile, W = (int)a.width, H = (int)a.height;
+    const uint64_t n_px = (uint64_t)a.width * a.height;
+    int any_invalid = 0;
+    for (int i = tid; i < EW * EH; i += kThreads) {
+        const int ey = i / EW, ex = i - ey * EW, gx = x0 - halo + ex, gy = y0 - halo + ey;
+        float2 p0 = make_float2(0.f, 0.f), p1 = make_float2(0.f, -1.f), p2 = make_float2(0.f, 0.f);
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const uint64_t g = (uint64_t)gy * a.width + (uint32_t)gx;
+            p0 = a.planes[g]; p1 = a.planes[n_px + g]; p2 = a.planes[2ull * n_px + g];
+        }
+        P0[i] = p0; P1[i] = p1; P2[i] = p2;
+        any_invalid |= p1.y < 0.f ? 1 : 0;
+    }
+    for (int i = tid; i < GW * GW; i += kThreads) {
+        const int ey = i / GW, ex = i - ey * GW, gx = x0 - a.r + ex, gy = y0 - a.r + ey;
+        uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) rec = guide[(uint64_t)gy * a.width + (uint32_t)gx];
+        G[i] = rec;
+    }
+    const int masked = __syncthreads_or(any_invalid);
+    const int px = tid & (kTile - 1), py = tid / kTile, ep = (py + halo) * EW + px + halo, gp = (py + a.r) * GW + px + a.r;
+    const float2 c0 = P0[ep], c1 = P1[ep];
+    const bool p_valid = c1.y >= 0.f;
+    float sw = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    if (masked) nlm_guided_window<F, true>(a, P0, P1, P2, G, bT, bH, bTM, bHM, EW, GW, p_valid, ep, gp, c0.x, c0.y, c1.x, sw, s0, s1, s2);
+    else nlm_guided_window<F, false>(a, P0, P1, P2, G, bT, bH, bTM, bHM, EW, GW, p_valid, ep, gp, c0.x, c0.y, c1.x, sw, s0, s1, s2);
+    const int gx = x0 + px, gy = y0 + py;
+    if (gx >= W || gy >= H) return;
+    float o0 = c0.x, o1 = c0.y, o2 = c1.x;            // an invalid pixel is copied through
+    if (p_valid) { o0 += s0 / sw; o1 += s1 / sw; o2 += s2 / sw; }   // sw >= 1: the pixel's own weight
+    float* o = a.out + ((uint64_t)gy * a.width + (uint32_t)gx) * 3u;
+    o[0] = o0; o[1] = o1; o[2] = o2;
+}
+
+size_t nlm_guided_lds_bytes(int r, int f) {
+    const size_t gw = (size_t)(kTile + 2 * r);
+    return nlm_lds_bytes(r, f) + gw * gw * sizeof(uint4);
+}
+// at the caps (r 10, f 4): 60^2 x 24 B of colour planes + 52^2 x 16 B of guide records + 23,040 B of box-sum buffers = 152,704 B
+static_assert((kTile + 2 * (kMaxWindowGuided + kMaxPatch)) * (kTile + 2 * (kMaxWindowGuided + kMaxPatch)) * 24 +
+                      (kTile + 2 * kMaxWindowGuided) * (kTile + 2 * kMaxWindowGuided) * 16 +
+                      2 * ((kTile + 2 * kMaxPatch) * (kTile + 2 * kMaxPatch) + (kTile + 2 * kMaxPatch) * kTile) * 4 == 152704 &&
+                      152704 <= 160 * 1024,
+              "colour planes, guide records and box-sum buffers must fit the 160 KiB LDS at the guided caps");
+static_assert(kMaxWindowGuided == RT_DENOISE_GUIDED_MAX_WINDOW_RADIUS && sizeof(uint4) == 16, "cap as the header states it; 16-byte records");
+
+template <int F>
+hipError_t launch_nlm_guided_f(const NlmArgs& a, const uint4* guide, hipStream_t stream) {
+    const size_t lds = nlm_guided_lds_bytes(a.r, F);
+    hipError_t e = hipFuncSetAttribute((const void*)k_nlm_guided<F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_nlm_guided<F>, dim3((a.width + kTile - 1) / kTile, (a.height + kTile - 1) / kTile), dim3(kThreads), lds, stream, a, guide);
+    return hipGetLastError();
+}
+
+hipError_t launch_nlm_guided(const NlmArgs& a, const uint4* guide, int f, hipStream_t stream) {
+    switch (f) {
+        case 1: return launch_nlm_guided_f<1>(a, guide, stream);
+        case 2: return launch_nlm_guided_f<2>(a, guide, stream);
+        case 3: return launch_nlm_guided_f<3>(a, guide, stream);
+        case 4: return launch_nlm_guided_f<4>(a, guide, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+// a sigma with its default filled in; false for a value the contract refuses
+bool guide_sigma(double given, double dflt, double& out) {
+    if (!(std::isfinite(given) && given >= 0.0) || std::signbit(given)) return false;
+    out = given != 0.0 ? given : dflt;
+    const float inv = 1.f / (float)out;
+    return std::isfinite(inv) && inv > 0.f;
+}
+
+// options (window cap of the guided path included) and the guide with its defaults filled in; RT_ERR_INVALID with the reason otherwise
+int nlm_guided_options(RtCtx* ctx, uint32_t width, uint32_t height, const RtDenoiseOptions* o, const RtDenoiseGuide* g, NlmOptions& out, GuideArgs& ga) {
+    using rti::set_err;
+    const int v = nlm_options(ctx, width, height, o, out); if (v != RT_OK) return v;
+    if (out.r > kMaxWindowGuided) return set_err(ctx, RT_ERR_INVALID, "RtDenoiseOptions.window_radius is above RT_DENOISE_GUIDED_MAX_WINDOW_RADIUS (10): the guide records of a larger halo do not fit the LDS beside the colour planes");
+    if (!g) return set_err(ctx, RT_ERR_INVALID, "denoise: guide is null (the filter without a guide is rt_denoise_device)");
+    if (g->struct_bytes < sizeof(RtDenoiseGuide) || g->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtDenoiseGuide.struct_bytes is not set (sizeof(RtDenoiseGuide))");
+    if (g->feature_samples == 0u) return set_err(ctx, RT_ERR_INVALID, "RtDenoiseGuide.feature_samples must be >= 1");
+    if (!g->albedo_sum && !g->normal_sum && !g->depth_sum) return set_err(ctx, RT_ERR_INVALID, "RtDenoiseGuide: albedo_sum, normal_sum and depth_sum are all null (the filter without a guide is rt_denoise_device)");
+    if (g->depth_sum && !g->hits) return set_err(ctx, RT_ERR_INVALID, "RtDenoiseGuide.depth_sum needs hits (the depth is a mean over the samples that hit)");
+    ga = GuideArgs{(const float*)g->albedo_sum, (const float*)g->normal_sum, (const float*)g->depth_sum, (const uint32_t*)g->hits, g->feature_samples, 0.0, 0.0, 0.0};
+    if (!guide_sigma(g->sigma_albedo, 0.2, ga.sigma_albedo)) return set_err(ctx, RT_ERR_INVALID, "RtDenoiseGuide.sigma_albedo must be finite and > 0 with a finite f32 reciprocal (0 = the default)");
+    if (!guide_sigma(g->sigma_normal, 0.5, ga.sigma_normal)) return set_err(ctx, RT_ERR_INVALID, "RtDenoiseGuide.sigma_normal must be finite and > 0 with a finite f32 reciprocal (0 = the default)");
+    if (!guide_sigma(g->sigma_depth, 0.2, ga.sigma_depth)) return set_err(ctx, RT_ERR_INVALID, "RtDenoiseGuide.sigma_depth must be finite and > 0 with a finite f32 reciprocal (0 = the default)");
+    return RT_OK;
+}
+
 }  // namespace
 
 }  // namespace rtk
@@ -260,6 +502,39 @@ int rt_denoise_device(RtCtx* ctx, const RtDenoiseOptions* options, uint32_t widt
     a.planes = (const float2*)ctx->denoise_planes.p; a.out = (float*)mean_out_device; a.width = width; a.height = height; a.r = o.r;
     a.k2 = (float)(o.strength * o.strength); a.alpha = (float)o.alpha; a.eps = (float)o.eps;
     HIP_TRY(ctx, rtk::launch_nlm(a, o.f, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_denoise_guided_check(uint32_t width, uint32_t height, const RtDenoiseOptions* options, const RtDenoiseGuide* guide) {
+    rtk::NlmOptions o; rtk::GuideArgs g;
+    return rtk::nlm_guided_options(nullptr, width, height, options, guide, o, g);
+}
+
+int rt_denoise_guided_device(RtCtx* ctx, const RtDenoiseOptions* options, const RtDenoiseGuide* guide, uint32_t width, uint32_t height, const void* rgb_sum_device,
+                             const void* sq_sum_device, uint32_t samples, const void* counts_device, void* mean_out_device) {
+    using rti::set_err;
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    if (!rgb_sum_device || !sq_sum_device || !mean_out_device) return set_err(ctx, RT_ERR_INVALID, "denoise: rgb_sum / sq_sum / mean_out is null");
+    rtk::NlmOptions o; rtk::GuideArgs g;
+    const int v = rtk::nlm_guided_options(ctx, width, height, options, guide, o, g); if (v != RT_OK) return v;
+    for (const void* in : {rgb_sum_device, sq_sum_device, counts_device, (const void*)g.albedo, (const void*)g.normal, (const void*)g.depth, (const void*)g.hits})
+        if (in && in == mean_out_device) return set_err(ctx, RT_ERR_INVALID, "denoise: mean_out must not be an input buffer (the feature planes included)");
+    if (!counts_device && samples == 0u) return set_err(ctx, RT_ERR_INVALID, "denoise: samples must be >= 1 when there is no counts buffer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t n_pixels = width * height;
+    HIP_TRY(ctx, ctx->denoise_planes.ensure((size_t)n_pixels * 3u * sizeof(float2)));
+    HIP_TRY(ctx, ctx->denoise_guide.ensure((size_t)n_pixels * sizeof(uint4)));
+    hipLaunchKernelGGL(rtk::k_nlm_prepare, dim3((n_pixels + 255u) / 256u), dim3(256), 0, ctx->stream, (const float*)rgb_sum_device, (const float*)sq_sum_device,
+                       (const uint32_t*)counts_device, samples, o.m, n_pixels, (float2*)ctx->denoise_planes.p);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(rtk::k_nlm_guide_prepare, dim3((n_pixels + 255u) / 256u), dim3(256), 0, ctx->stream, g, n_pixels, (uint4*)ctx->denoise_guide.p,
+                       (float2*)ctx->denoise_planes.p);
+    HIP_TRY(ctx, hipGetLastError());
+    rtk::NlmArgs a{};
+    a.planes = (const float2*)ctx->denoise_planes.p; a.out = (float*)mean_out_device; a.width = width; a.height = height; a.r = o.r;
+    a.k2 = (float)(o.strength * o.strength); a.alpha = (float)o.alpha; a.eps = (float)o.eps;
+    HIP_TRY(ctx, rtk::launch_nlm_guided(a, (const uint4*)ctx->denoise_guide.p, o.f, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }

@@ -1,12 +1,14 @@
 """Denoising of low-sample frames: non-local means over the sample variance (include/rt_hip.h, "denoising").
 
 nlm_reference restates the filter in numpy — the prepare step in f64 rounded to f32, the filter step in f64 from those f32 planes — and is
-what the device kernels (csrc/denoise.hip, f32) are tested against. denoise_frame is the device path behind Progressive.denoised() and
-Adaptive.denoised().
+what the device kernels (csrc/denoise.hip, f32) are tested against. nlm_guided_reference is the same filter with its weights joined with
+first-hit features ("denoising, guided"): guide_prepare makes the binary16 guide components, the filter step is nlm_reference's own.
+denoise_frame is the device path behind Progressive.denoised() and Adaptive.denoised(); render_guide makes the feature pass they join in.
 """
 import numpy as np
 
 DEFAULTS = dict(window_radius=10, patch_radius=3, strength=0.45, alpha=1.0, eps=1e-10)
+GUIDE_DEFAULTS = dict(sigma_albedo=0.2, sigma_normal=0.5, sigma_depth=0.2)      # the library's (include/rt_hip.h; measured: DESIGN.md, "Denoising")
 
 
 def _options(opts):
@@ -42,17 +44,19 @@ def nlm_prepare(rgb_sum, sq_sum, counts_or_n, m):
     return u, v, valid
 
 
-def nlm_reference(rgb_sum, sq_sum, counts_or_n, m, **opts):
-    """The filter of include/rt_hip.h restated: the filtered mean radiance, f64 (H, W, 3). opts: window_radius, patch_radius, strength,
-    alpha, eps (0 or absent: the default). Every sum is taken directly, term by term, in f64."""
+def _filter(u32, v32, valid, opts, guide=None):
+    """The filter step in f64 from the prepared f32 planes; guide: (H, W, 7) binary16 components whose squared distance joins the patch
+    distance, or None. Every sum is taken directly, term by term; the output is u[p] + sum w (u[q] - u[p]) / sum w."""
     r, f, kk, alpha, eps = _options(opts)
-    u32, v32, valid = nlm_prepare(rgb_sum, sq_sum, counts_or_n, m)
     H, W = valid.shape
     pad = r + f
     u = np.zeros((H + 2 * pad, W + 2 * pad, 3)); v = np.zeros_like(u); ok = np.zeros((H + 2 * pad, W + 2 * pad), dtype=bool)
     u[pad:pad + H, pad:pad + W] = u32; v[pad:pad + H, pad:pad + W] = v32; ok[pad:pad + H, pad:pad + W] = valid
     u = np.where(ok[..., None], u, 0.0)          # an invalid pixel's u may be non-finite: it takes part in nothing
     Ha, Wa = H + 2 * f, W + 2 * f                  # the pixels p + o
+    if guide is not None:
+        G = np.zeros((H + 2 * pad, W + 2 * pad, guide.shape[2]))
+        G[pad:pad + H, pad:pad + W] = np.where(valid[..., None], guide.astype(np.float64), 0.0)
 
     def shifted(a, dy, dx, h, w, margin):
         return a[margin + dy:margin + dy + h, margin + dx:margin + dx + w]
@@ -76,20 +80,104 @@ def nlm_reference(rgb_sum, sq_sum, counts_or_n, m, **opts):
                 uq, okq = shifted(u, dy, dx, H, W, pad), shifted(ok, dy, dx, H, W, pad)
                 pair = okp & okq
                 d = D / np.maximum(3.0 * cnt, 1.0)
-                w = np.where(pair, np.exp(-np.maximum(d, 0.0)), 0.0)
+                if guide is None:
+                    w = np.where(pair, np.exp(-np.maximum(d, 0.0)), 0.0)
+                else:
+                    g = ((shifted(G, 0, 0, H, W, pad) - shifted(G, dy, dx, H, W, pad)) ** 2).sum(axis=2)
+                    w = np.where(pair, np.exp(-(np.maximum(d, 0.0) + g)), 0.0)
                 sw += w
-                swu += w[..., None] * uq
-        out = swu / np.where(sw > 0, sw, 1.0)[..., None]
+                swu += w[..., None] * (uq - up)
+        out = up + swu / np.where(sw > 0, sw, 1.0)[..., None]          # summed as differences from u[p], as the kernels do: a constant frame is exact
     return np.where(valid[..., None], out, u32.astype(np.float64))
 
 
-def denoise_frame(ctx, rgb_sum, sq_sum, width, height, samples_per_item, samples=0, counts=None, rgb8=False, **opts):
-    """rt_denoise_device on full-frame device tensors; the f32 mean (H, W, 3) on the host, or with rgb8 its write_color bytes
-    (rt_resolve_device with one sample per pixel: the library's only tone map)."""
+def nlm_reference(rgb_sum, sq_sum, counts_or_n, m, **opts):
+    """The filter of include/rt_hip.h restated: the filtered mean radiance, f64 (H, W, 3). opts: window_radius, patch_radius, strength,
+    alpha, eps (0 or absent: the default). Every sum is taken directly, term by term, in f64."""
+    u32, v32, valid = nlm_prepare(rgb_sum, sq_sum, counts_or_n, m)
+    return _filter(u32, v32, valid, opts)
+
+
+def guide_prepare(feature_samples, albedo_sum=None, normal_sum=None, depth_sum=None, hits=None, sigma_albedo=0.0, sigma_normal=0.0, sigma_depth=0.0):
+    """The guide of include/rt_hip.h ("denoising, guided"): (F, valid) — F (H, W, 7) binary16, the components A0 A1 A2 N0 N1 N2 Z computed
+    in f64, rounded to f32, then to binary16 (round to nearest even) and clamped to +-65504; a plane that is None gives 0. valid (H, W):
+    every given feature sum is finite and hits <= feature_samples. albedo_sum / normal_sum: (H, W, 3), depth_sum / hits: (H, W)."""
+    n_f = int(feature_samples)
+    if n_f < 1:
+        raise ValueError("feature_samples must be >= 1")
+    if albedo_sum is None and normal_sum is None and depth_sum is None:
+        raise ValueError("a guide needs one of albedo_sum, normal_sum, depth_sum (the filter without a guide is nlm_reference)")
+    if depth_sum is not None and hits is None:
+        raise ValueError("depth_sum needs hits")
+    sig = [float(s) if s else GUIDE_DEFAULTS[k] for k, s in (("sigma_albedo", sigma_albedo), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth))]
+    first = next(p for p in (albedo_sum, normal_sum, depth_sum) if p is not None)
+    H, W = np.shape(first)[:2]
+    F = np.zeros((H, W, 7))
+    valid = np.ones((H, W), dtype=bool)
+    with np.errstate(all="ignore"):
+        for plane, at, sigma in ((albedo_sum, 0, sig[0]), (normal_sum, 3, sig[1])):
+            if plane is not None:
+                s = np.asarray(plane, dtype=np.float32).reshape(H, W, 3).astype(np.float64)
+                valid &= np.isfinite(s).all(axis=2)
+                F[..., at:at + 3] = s / float(n_f) / sigma
+        h = np.asarray(hits).reshape(H, W).astype(np.int64) if hits is not None else np.zeros((H, W), dtype=np.int64)
+        valid &= h <= n_f
+        if depth_sum is not None:
+            s = np.asarray(depth_sum, dtype=np.float32).reshape(H, W).astype(np.float64)
+            valid &= np.isfinite(s)
+            F[..., 6] = np.where(h > 0, np.log(np.maximum(s / np.maximum(h, 1), 1e-30)) / sig[2], 0.0)
+        F16 = np.clip(F.astype(np.float32).astype(np.float16), np.float16(-65504), np.float16(65504))
+    F16[~valid] = 0
+    return F16, valid
+
+
+def nlm_guided_reference(rgb_sum, sq_sum, counts_or_n, m, feature_samples, albedo_sum=None, normal_sum=None, depth_sum=None, hits=None,
+                         sigma_albedo=0.0, sigma_normal=0.0, sigma_depth=0.0, **opts):
+    """The guided filter of include/rt_hip.h restated: nlm_reference with g(p,q), the squared distance of the binary16 guide components,
+    added to max(d, 0) in the weight; f64 (H, W, 3). A pixel the guide makes invalid is invalid for the colour part too."""
+    u32, v32, valid = nlm_prepare(rgb_sum, sq_sum, counts_or_n, m)
+    F, ok = guide_prepare(feature_samples, albedo_sum, normal_sum, depth_sum, hits, sigma_albedo, sigma_normal, sigma_depth)
+    if ok.shape != valid.shape:
+        raise ValueError("the feature planes have another size than the frame")
+    valid = valid & ok
+    v32 = v32.copy(); v32[~valid] = 0.0
+    return _filter(u32, v32, valid, opts, guide=F)
+
+
+def render_guide(ctx, scene, cam, params, feature_samples, sigma_albedo=0.0, sigma_normal=0.0, sigma_depth=0.0):
+    """A feature pass of `feature_samples` samples per pixel over the frame's camera rays (Context.render_features, device tensors) as
+    the `guide` of denoise_frame: full-frame planes; a sharded frame's planes are untiled as its sums are, the other shards' pixels 0."""
+    import torch
+    from . import _abi as A
+    prm = A.RtParams.from_buffer_copy(params)
+    prm.samples_per_pixel = int(feature_samples)
+    prm.flags &= A.RT_FLAG_TIMING | A.RT_FLAG_SAMPLE_BLOCKS      # (a feature pass refuses the counter and the fused-kernel diagnostics)
+    planes = ctx.render_features(scene, cam, prm)
+    if prm.shard_count > 1:
+        from .adaptive import slot_pixels
+        x, y, ok = slot_pixels(prm)
+        full = []
+        for t, ch in zip(planes, (3, 3, 1, 1)):
+            a = t.cpu().numpy().reshape(-1, ch)
+            f = np.zeros((prm.height, prm.width, ch), dtype=a.dtype)
+            f[y[ok], x[ok]] = a[ok]
+            full.append(torch.from_numpy(f.reshape(-1)).to(t.device))
+        planes = tuple(full)
+    return dict(feature_samples=int(feature_samples), albedo=planes[0], normal=planes[1], depth=planes[2], hits=planes[3],
+                sigma_albedo=sigma_albedo, sigma_normal=sigma_normal, sigma_depth=sigma_depth)
+
+
+def denoise_frame(ctx, rgb_sum, sq_sum, width, height, samples_per_item, samples=0, counts=None, rgb8=False, guide=None, **opts):
+    """rt_denoise_device on full-frame device tensors — with `guide` (Context.denoise_guided's feature arguments, as render_guide
+    returns them) rt_denoise_guided_device; the f32 mean (H, W, 3) on the host, or with rgb8 its write_color bytes (rt_resolve_device
+    with one sample per pixel: the library's only tone map)."""
     import torch
     from .api import denoise_options
     o = denoise_options(samples_per_item=samples_per_item, **opts)
-    out = ctx.denoise(rgb_sum, sq_sum, width, height, samples=samples, counts=counts, options=o)
+    if guide is None:
+        out = ctx.denoise(rgb_sum, sq_sum, width, height, samples=samples, counts=counts, options=o)
+    else:
+        out = ctx.denoise_guided(rgb_sum, sq_sum, width, height, samples=samples, counts=counts, options=o, **guide)
     if not rgb8:
         return out.cpu().numpy().reshape(height, width, 3)
     b = torch.empty(height * width * 3, dtype=torch.uint8, device=out.device)
