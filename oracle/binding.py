@@ -51,6 +51,9 @@ def lib():
         L.orc_render.argtypes = [vp, vp, vp, C.POINTER(OrcOpts), f64p, C.POINTER(OrcStats)]
         L.orc_render_samples.restype = C.c_int
         L.orc_render_samples.argtypes = [vp, vp, vp, C.POINTER(OrcOpts), f64p, f64p, C.POINTER(OrcStats)]
+        u32p = C.POINTER(C.c_uint32)
+        L.orc_render_paths.restype = C.c_int
+        L.orc_render_paths.argtypes = [vp, vp, vp, C.POINTER(OrcOpts), C.c_int32, C.POINTER(C.c_int32), f64p, f64p, u32p, u32p, u32p, f64p, f64p, C.POINTER(OrcStats)]
         L.orc_render_crops.restype = C.c_int
         L.orc_render_crops.argtypes = [vp, vp, vp, C.POINTER(OrcOpts), C.c_int32, C.POINTER(C.c_int32), f64p, C.POINTER(OrcStats)]
         L.orc_render_reference_shaped.restype = C.c_int
@@ -110,6 +113,39 @@ def render(desc, cam, params, precision=64, n_threads=1, rect=None, count=False,
     if rc != 0:
         raise RuntimeError("oracle: " + L.orc_last_error().decode())
     return (out, st.as_dict(), ps) if per_sample else (out, st.as_dict())
+
+
+# Path records (orc_render_paths). EVENTS: name -> bit of the event mask, in the order of oracle.cpp's EV_* enum.
+EVENT_NAMES = ["lambertian_cosine_only", "lambertian_light_xz_rect", "lambertian_light_sphere", "lambertian_mixture_cosine", "metal",
+               "dielectric_refract", "dielectric_reflect_schlick", "dielectric_reflect_cannot_refract", "dielectric_back_face", "isotropic",
+               "medium_scattered", "medium_passed", "tex_solid", "tex_checker", "tex_noise", "tex_image", "tex_empty_image",
+               "hit_sphere", "hit_moving_sphere", "hit_rect", "hit_triangle", "hit_box_side", "under_translate", "under_rotate_y", "under_flip_face",
+               "lens_offset", "time"]
+EVENTS = {n: 1 << k for k, n in enumerate(EVENT_NAMES)}
+TERM_MISS, TERM_EMITTER_FRONT, TERM_EMITTER_BACK, TERM_DEPTH, TERM_NONFINITE = range(5)
+
+
+def render_paths(desc, cam, params, precision=64, n_threads=1, rect=None, count=False, r_ulps=0, signs=(1, 1, 1)):
+    """render(..., per_sample=True) with every sample's path record. Returns a dict: radiance float64 (h,w,spp,3), segments, terminal,
+    events uint32 (h,w,spp), margin and tmin_margin float64 (h,w,spp), rgb_sum (H,W,3), stats. r_ulps > 0: every traced ray's direction is rounded to
+    f32 and moved by signs[c] * r_ulps f32 ulps per component."""
+    L = lib()
+    H, W, spp = params.height, params.width, params.samples_per_pixel
+    x0, y0, x1, y1 = rect if rect else (0, 0, W, H)
+    opts = OrcOpts(precision, n_threads, x0, y0, x1, y1, 1 if count else 0, 0)
+    out = np.zeros((H, W, 3), dtype=np.float64)
+    shape = (y1 - y0, x1 - x0, spp)
+    ps = np.zeros(shape + (3,), dtype=np.float64)
+    seg, term, ev = (np.zeros(shape, dtype=np.uint32) for _ in range(3))
+    margin, tmin = np.zeros(shape, dtype=np.float64), np.zeros(shape, dtype=np.float64)
+    st = OrcStats()
+    f64p, u32p = C.POINTER(C.c_double), C.POINTER(C.c_uint32)
+    rc = L.orc_render_paths(C.byref(desc), C.byref(cam), C.byref(params), C.byref(opts), int(r_ulps), (C.c_int32 * 3)(*[int(v) for v in signs]),
+                            out.ctypes.data_as(f64p), ps.ctypes.data_as(f64p), seg.ctypes.data_as(u32p), term.ctypes.data_as(u32p), ev.ctypes.data_as(u32p),
+                            margin.ctypes.data_as(f64p), tmin.ctypes.data_as(f64p), C.byref(st))
+    if rc != 0:
+        raise RuntimeError("oracle: " + L.orc_last_error().decode())
+    return dict(radiance=ps, segments=seg, terminal=term, events=ev, margin=margin, tmin_margin=tmin, rgb_sum=out, stats=st.as_dict())
 
 
 def render_crops(desc, cam, params, rects, precision=64, n_threads=1, count=False):

@@ -8,6 +8,9 @@
 //     or output images of its own.  What pins this file instead are the analytic known-answer
 //     tests derived from the reference source (tests/test_oracle_kat.py) and
 //     distribution-level checks (furnace test, f32-vs-f64 converged means).
+//     The DEVICE, in turn, is pinned to this file sample by sample: orc_render_paths records every sample's path (segments, how
+//     it ended, which branches it took, how closely its thresholds were decided), with an option to perturb every traced ray —
+//     tests/paths.py builds the decidability rule and tests/test_gpu_paths.py the comparison from it.
 //
 // It follows the reference file by file — every function cites the lines it restates — with the
 // same object model (virtual Hittable / Material / Texture / Pdf, recursive ray_color), templated
@@ -18,6 +21,7 @@
 //   - BVHNode::construct sorts the sub-range [start,end) (bvh.rs:108 sorts the whole vector, a bug
 //     that loses objects) and a span-1 node tests its object once (bvh.rs:96-98 tests it twice);
 //   - Aabb::hit carries the interval across axes (aabb.rs:48-49 shadows it per axis);
+//   - Sphere / MovingSphere::bounding_box use |radius| (sphere.rs:66-73 turns the box of a negative-radius sphere inside out);
 //   - ConstantMedium and Isotropic are restated from the commented-out code
 //     (constant_medium.rs:31-71, material.rs:193-220) under the live scatter signature; the
 //     medium's free-path draw is keyed by (path, segment, medium) instead of taken from the
@@ -76,6 +80,26 @@ struct Counters {
 };
 enum { PT_SPHERE = 0, PT_MOVING = 1, PT_RECT = 2, PT_TRI = 3, PT_MEDIUM = 4, PT_INSTANCE = 5 };
 
+// Path records (orc_render_paths): which branch every segment of a path took, how it ended, and how closely its random-number
+// thresholds were decided. Filled only where Ctx::path / Rng::margin are set; null on every other entry point, whose arithmetic they
+// do not touch.
+enum : uint32_t {
+    EV_LAMB_COSINE_ONLY = 1u << 0, EV_LAMB_LIGHT_XZRECT = 1u << 1, EV_LAMB_LIGHT_SPHERE = 1u << 2, EV_LAMB_MIX_COSINE = 1u << 3,
+    EV_METAL = 1u << 4, EV_DIEL_REFRACT = 1u << 5, EV_DIEL_REFLECT_SCHLICK = 1u << 6, EV_DIEL_REFLECT_TIR = 1u << 7, EV_DIEL_BACK_FACE = 1u << 8,
+    EV_ISOTROPIC = 1u << 9, EV_MEDIUM_SCATTERED = 1u << 10, EV_MEDIUM_PASSED = 1u << 11,
+    EV_TEX_SOLID = 1u << 12, EV_TEX_CHECKER = 1u << 13, EV_TEX_NOISE = 1u << 14, EV_TEX_IMAGE = 1u << 15, EV_TEX_EMPTY_IMAGE = 1u << 16,
+    EV_HIT_SPHERE = 1u << 17, EV_HIT_MOVING = 1u << 18, EV_HIT_RECT = 1u << 19, EV_HIT_TRI = 1u << 20, EV_HIT_BOX_SIDE = 1u << 21,
+    EV_UNDER_TRANSLATE = 1u << 22, EV_UNDER_ROTATE_Y = 1u << 23, EV_UNDER_FLIP_FACE = 1u << 24, EV_LENS = 1u << 25, EV_TIME = 1u << 26
+};
+enum : uint32_t { TERM_MISS = 0, TERM_EMITTER_FRONT = 1, TERM_EMITTER_BACK = 2, TERM_DEPTH = 3, TERM_NONFINITE = 4 };
+struct PathRec {
+    uint32_t events = 0, terminal = TERM_MISS;
+    double margin = std::numeric_limits<double>::infinity();   // smallest distance by which a random-number threshold was decided
+    double tmin_margin = std::numeric_limits<double>::infinity();   // smallest |root - t_min| * |d . n| of a primitive test: how far along the
+                                                                    // normal the ray's origin would have to move to carry a root across t_min
+    int r_ulps = 0; int sign[3] = {1, 1, 1};                   // perturbation of every traced ray's direction (0: none)
+};
+
 template <class R> struct Uni;  // u64 -> uniform [0,1)
 template <> struct Uni<double> { static double cv(uint64_t z) { return (double)(z >> 11) * (1.0 / 9007199254740992.0); } };
 template <> struct Uni<float>  { static float  cv(uint64_t z) { return (float)(z >> 40) * (1.0f / 16777216.0f); } };
@@ -84,6 +108,10 @@ template <class R> struct Rng {
     uint64_t state = 0, base = 0;
     uint32_t segment = 0;  // index of the world.hit call on this path (for medium draws)
     Counters* cnt = nullptr;
+    double* margin = nullptr;   // PathRec::margin of the path this stream belongs to, or null
+    double* tmin = nullptr;     // PathRec::tmin_margin, or null
+    void decided_by(double d) { if (margin && d < *margin) *margin = d; }
+    void root_at(double root, double t_min, double d_dot_n) { if (tmin) { double m = std::fabs(root - t_min) * std::fabs(d_dot_n); if (m < *tmin) *tmin = m; } }
     uint64_t next64() { state += GAMMA; if (cnt) cnt->draws++; return fin(state); }
     R random_double() { return Uni<R>::cv(next64()); }                                    // rt_weekend.rs:8-11
     R random_double_range(R lo, R hi) { return lo + (hi - lo) * random_double(); }        // rt_weekend.rs:13-15
@@ -133,12 +161,18 @@ template <class R> Vec3<R> random_vec_range(Rng<R>& g, R lo, R hi) {            
     return Vec3<R>(a, b, c);
 }
 template <class R> Vec3<R> random_in_unit_sphere(Rng<R>& g) {                                                                   // vec3.rs:78-86
-    for (;;) { Vec3<R> p = random_vec_range(g, (R)-1, (R)1); if (p.length_squared() >= (R)1) continue; return p; }
+    for (;;) {
+        Vec3<R> p = random_vec_range(g, (R)-1, (R)1);
+        g.decided_by(std::fabs((double)p.length_squared() - 1.0));
+        if (p.length_squared() >= (R)1) continue;
+        return p;
+    }
 }
 template <class R> Vec3<R> random_in_unit_disk(Rng<R>& g) {                                                                     // vec3.rs:101-113
     for (;;) {
         R a = g.random_double_range((R)-1, (R)1), b = g.random_double_range((R)-1, (R)1);
         Vec3<R> p(a, b, 0);
+        g.decided_by(std::fabs((double)p.length_squared() - 1.0));
         if (p.length_squared() >= (R)1) continue;
         return p;
     }
@@ -227,18 +261,19 @@ template <class R> struct Aabb {
 // ------------------------------------------------------------------------------------------------
 template <class R> struct Texture {
     virtual ~Texture() {}
-    virtual Vec3<R> value(R u, R v, const Vec3<R>& p) const = 0;   // texture.rs:7-9
+    virtual Vec3<R> value(R u, R v, const Vec3<R>& p, uint32_t* ev = nullptr) const = 0;   // texture.rs:7-9 (ev: a path record's event mask, or null)
 };
 template <class R> struct SolidColor : Texture<R> {               // texture.rs:34-38
     Vec3<R> c;
     explicit SolidColor(const Vec3<R>& c_) : c(c_) {}
-    Vec3<R> value(R, R, const Vec3<R>&) const override { return c; }
+    Vec3<R> value(R, R, const Vec3<R>&, uint32_t* ev) const override { if (ev) *ev |= EV_TEX_SOLID; return c; }
 };
 template <class R> struct CheckerTexture : Texture<R> {           // texture.rs:60-69
     std::shared_ptr<Texture<R>> even, odd;
-    Vec3<R> value(R u, R v, const Vec3<R>& p) const override {
+    Vec3<R> value(R u, R v, const Vec3<R>& p, uint32_t* ev) const override {
+        if (ev) *ev |= EV_TEX_CHECKER;
         R sines = std::sin((R)10 * p.x()) * std::sin((R)10 * p.y()) * std::sin((R)10 * p.z());
-        return sines < (R)0 ? odd->value(u, v, p) : even->value(u, v, p);
+        return sines < (R)0 ? odd->value(u, v, p, ev) : even->value(u, v, p, ev);
     }
 };
 template <class R> struct Perlin {                                 // perlin.rs
@@ -284,14 +319,16 @@ template <class R> struct Perlin {                                 // perlin.rs
 };
 template <class R> struct NoiseTexture : Texture<R> {             // texture.rs:90-96
     std::shared_ptr<Perlin<R>> noise; R scale = 1;
-    Vec3<R> value(R, R, const Vec3<R>& p) const override {
+    Vec3<R> value(R, R, const Vec3<R>& p, uint32_t* ev) const override {
+        if (ev) *ev |= EV_TEX_NOISE;
         return Vec3<R>(1, 1, 1) * (R)0.5 * ((R)1 + std::sin(scale * p.z() + (R)10 * noise->turb(p)));
     }
 };
 template <class R> static R clamp(R x, R lo, R hi) { return x < lo ? lo : (x > hi ? hi : x); }   // rt_weekend.rs:21-29
 template <class R> struct ImageTexture : Texture<R> {             // texture.rs:117-140
     std::vector<uint8_t> data; uint32_t width = 0, height = 0;
-    Vec3<R> value(R u, R v, const Vec3<R>&) const override {
+    Vec3<R> value(R u, R v, const Vec3<R>&, uint32_t* ev) const override {
+        if (ev) *ev |= data.empty() ? EV_TEX_EMPTY_IMAGE : EV_TEX_IMAGE;
         if (data.empty()) return Vec3<R>(0, 1, 1);
         u = clamp(u, (R)0, (R)1);
         v = (R)1 - clamp(v, (R)0, (R)1);
@@ -310,6 +347,7 @@ template <class R> struct ImageTexture : Texture<R> {             // texture.rs:
 template <class R> struct Material;
 template <class R> struct HitRecord {                             // hittable.rs:11-19
     Vec3<R> p, normal; const Material<R>* mat_ptr = nullptr; R t = 0, u = 0, v = 0; bool front_face = false;
+    uint32_t tags = 0;   // EV_HIT_* of the primitive, EV_UNDER_* of the wrappers above it, EV_MEDIUM_SCATTERED (path records only)
     void set_face_normal(const Ray<R>& r, const Vec3<R>& outward_normal) {   // hittable.rs:41-48
         front_face = dot(r.dir, outward_normal) < (R)0;
         normal = front_face ? outward_normal : -outward_normal;
@@ -317,7 +355,11 @@ template <class R> struct HitRecord {                             // hittable.rs
 };
 
 // What the reference reads from thread-local state: the RNG; plus our counters.
-template <class R> struct Ctx { Rng<R>* rng; Counters* cnt; int order; };
+template <class R> struct Ctx {
+    Rng<R>* rng; Counters* cnt; int order; PathRec* path;   // path: null unless a path record is being filled
+    void ev(uint32_t bits) { if (path) path->events |= bits; }
+    uint32_t* evp() { return path ? &path->events : nullptr; }
+};
 
 template <class R> struct Hittable {                              // hittable.rs:51-60
     virtual ~Hittable() {}
@@ -354,7 +396,8 @@ template <class R> struct MixturePdf : Pdf<R> {                   // pdf.rs:59-8
         return (R)0.5 * p[0]->value(direction, cx) + (R)0.5 * p[1]->value(direction, cx);
     }
     Vec3<R> generate(Ctx<R>& cx) const override {
-        if (cx.rng->random_double() < (R)0.5) return p[0]->generate(cx);
+        if (cx.rng->random_double() < (R)0.5) return p[0]->generate(cx);   // (f32 and f64 uniforms share their top bit: no margin)
+        cx.ev(EV_LAMB_MIX_COSINE);
         return p[1]->generate(cx);
     }
 };
@@ -365,14 +408,14 @@ template <class R> struct ScatterRecord {                         // material.rs
 template <class R> struct Material {                              // material.rs:11-21
     virtual ~Material() {}
     virtual bool scatter(const Ray<R>&, const HitRecord<R>&, ScatterRecord<R>&, Ctx<R>&) const { return false; }
-    virtual Vec3<R> emitted(const Ray<R>&, const HitRecord<R>&, R, R, const Vec3<R>&) const { return Vec3<R>(0, 0, 0); }
+    virtual Vec3<R> emitted(const Ray<R>&, const HitRecord<R>&, R, R, const Vec3<R>&, Ctx<R>&) const { return Vec3<R>(0, 0, 0); }
     virtual R scattering_pdf(const Ray<R>&, const HitRecord<R>&, const Ray<R>&) const { return 0; }
 };
 template <class R> struct Lambertian : Material<R> {              // material.rs:47-72
     std::shared_ptr<Texture<R>> albedo;
-    bool scatter(const Ray<R>&, const HitRecord<R>& rec, ScatterRecord<R>& srec, Ctx<R>&) const override {
+    bool scatter(const Ray<R>&, const HitRecord<R>& rec, ScatterRecord<R>& srec, Ctx<R>& cx) const override {
         srec.is_specular = false;
-        srec.attenuation = albedo->value(rec.u, rec.v, rec.p);
+        srec.attenuation = albedo->value(rec.u, rec.v, rec.p, cx.evp());
         srec.pdf_ptr = std::make_shared<CosinePdf<R>>(rec.normal);
         return true;
     }
@@ -384,6 +427,7 @@ template <class R> struct Lambertian : Material<R> {              // material.rs
 template <class R> struct Metal : Material<R> {                   // material.rs:95-108
     Vec3<R> albedo; R fuzz = 0;
     bool scatter(const Ray<R>& r_in, const HitRecord<R>& rec, ScatterRecord<R>& srec, Ctx<R>& cx) const override {
+        cx.ev(EV_METAL);
         Vec3<R> reflected = reflect(r_in.dir.unit(), rec.normal);
         // random_in_unit_sphere() is drawn even when fuzz == 0; the ray's time is 0.0, not r_in.time()
         srec.specular_ray = Ray<R>(rec.p, reflected + fuzz * random_in_unit_sphere(*cx.rng), (R)0);
@@ -411,17 +455,23 @@ template <class R> struct Dielectric : Material<R> {              // material.rs
         R sin_theta = std::sqrt((R)1 - cos_theta * cos_theta);
         bool cannot_refract = refraction_ratio * sin_theta > (R)1;
         // `||` short-circuits: no draw on total internal reflection (material.rs:146-147)
-        Vec3<R> direction = (cannot_refract || reflectance(cos_theta, refraction_ratio) > cx.rng->random_double())
-                                ? reflect(unit_direction, rec.normal)
-                                : refract(unit_direction, rec.normal, refraction_ratio);
+        bool reflects = cannot_refract;
+        if (!rec.front_face) cx.ev(EV_DIEL_BACK_FACE);
+        if (!cannot_refract) {
+            const R refl = reflectance(cos_theta, refraction_ratio), draw = cx.rng->random_double();
+            cx.rng->decided_by(std::fabs((double)refl - (double)draw));
+            reflects = refl > draw;
+        }
+        cx.ev(cannot_refract ? EV_DIEL_REFLECT_TIR : (reflects ? EV_DIEL_REFLECT_SCHLICK : EV_DIEL_REFRACT));
+        Vec3<R> direction = reflects ? reflect(unit_direction, rec.normal) : refract(unit_direction, rec.normal, refraction_ratio);
         srec.specular_ray = Ray<R>(rec.p, direction, r_in.tm);
         return true;
     }
 };
 template <class R> struct DiffuseLight : Material<R> {            // material.rs:174-191
     std::shared_ptr<Texture<R>> emit;
-    Vec3<R> emitted(const Ray<R>&, const HitRecord<R>& rec, R u, R v, const Vec3<R>& p) const override {
-        return rec.front_face ? emit->value(u, v, p) : Vec3<R>(0, 0, 0);
+    Vec3<R> emitted(const Ray<R>&, const HitRecord<R>& rec, R u, R v, const Vec3<R>& p, Ctx<R>& cx) const override {
+        return rec.front_face ? emit->value(u, v, p, cx.evp()) : Vec3<R>(0, 0, 0);
     }
 };
 // material.rs:193-220 is commented out and written against the pre-book-3 signature
@@ -430,8 +480,9 @@ template <class R> struct DiffuseLight : Material<R> {            // material.rs
 template <class R> struct Isotropic : Material<R> {
     std::shared_ptr<Texture<R>> albedo;
     bool scatter(const Ray<R>& r_in, const HitRecord<R>& rec, ScatterRecord<R>& srec, Ctx<R>& cx) const override {
+        cx.ev(EV_ISOTROPIC);
         srec.specular_ray = Ray<R>(rec.p, random_in_unit_sphere(*cx.rng), r_in.tm);   // material.rs:216
-        srec.attenuation = albedo->value(rec.u, rec.v, rec.p);                       // material.rs:217
+        srec.attenuation = albedo->value(rec.u, rec.v, rec.p, cx.evp());                     // material.rs:217
         srec.is_specular = true;
         srec.pdf_ptr = nullptr;
         return true;
@@ -457,8 +508,10 @@ template <class R> struct Sphere : Hittable<R> {
         if (det < (R)0) return false;
         R sqrtd = std::sqrt(det);
         R root = (-half_b - sqrtd) / a;
+        if (cx.rng->tmin) cx.rng->root_at(root, t_min, dot(r.dir, (r.at(root) - center) / radius));
         if (root < t_min || t_max < root) {
             root = (-half_b + sqrtd) / a;
+            if (cx.rng->tmin) cx.rng->root_at(root, t_min, dot(r.dir, (r.at(root) - center) / radius));
             if (root < t_min || t_max < root) return false;
         }
         rec.t = root;
@@ -467,10 +520,15 @@ template <class R> struct Sphere : Hittable<R> {
         rec.set_face_normal(r, outward_normal);
         get_sphere_uv(outward_normal, rec.u, rec.v);
         rec.mat_ptr = mat_ptr;
+        rec.tags = EV_HIT_SPHERE;
         return true;
     }
     bool bounding_box(R, R, Aabb<R>& out) const override {        // sphere.rs:66-73
-        out = Aabb<R>(center - Vec3<R>(radius, radius, radius), center + Vec3<R>(radius, radius, radius));
+        // sphere.rs:66-73 forms centre -+ radius with the signed radius: the inner sphere of a hollow glass ball (radius < 0) gets a box
+        // turned inside out, and whether a ray then finds it depends on which boxes the tree happens to pair it with. |radius| here (and
+        // in MovingSphere): the BVH stays a pure accelerator, as with F6.
+        const R ar = std::fabs(radius);
+        out = Aabb<R>(center - Vec3<R>(ar, ar, ar), center + Vec3<R>(ar, ar, ar));
         return true;
     }
     R pdf_value(const Vec3<R>& o, const Vec3<R>& v, Ctx<R>& cx) const override {   // sphere.rs:75-84
@@ -484,6 +542,7 @@ template <class R> struct Sphere : Hittable<R> {
         Vec3<R> direction = center - o;
         R distance_sq = direction.length_squared();
         Onb<R> uvw = Onb<R>::build_from_w(direction);
+        cx.ev(EV_LAMB_LIGHT_SPHERE);
         return uvw.local(random_to_sphere(*cx.rng, radius, distance_sq));
     }
 };
@@ -502,8 +561,10 @@ template <class R> struct MovingSphere : Hittable<R> {
         if (det < (R)0) return false;
         R sqrtd = std::sqrt(det);
         R root = (-half_b - sqrtd) / a;
+        if (cx.rng->tmin) cx.rng->root_at(root, t_min, dot(r.dir, (r.at(root) - center(r.tm)) / radius));
         if (root < t_min || t_max < root) {
             root = (-half_b + sqrtd) / a;
+            if (cx.rng->tmin) cx.rng->root_at(root, t_min, dot(r.dir, (r.at(root) - center(r.tm)) / radius));
             if (root < t_min || t_max < root) return false;
         }
         rec.t = root;
@@ -513,10 +574,11 @@ template <class R> struct MovingSphere : Hittable<R> {
         // u,v are NOT set by the reference (stale temp_rec values, hittable_list.rs:40-48); defined as 0.
         rec.u = 0; rec.v = 0;
         rec.mat_ptr = mat_ptr;
+        rec.tags = EV_HIT_MOVING;
         return true;
     }
     bool bounding_box(R t0, R t1, Aabb<R>& out) const override {  // :67-78
-        Vec3<R> rv(radius, radius, radius);
+        Vec3<R> rv(std::fabs(radius), std::fabs(radius), std::fabs(radius));
         Aabb<R> b0(center(t0) - rv, center(t0) + rv), b1(center(t1) - rv, center(t1) + rv);
         out = Aabb<R>::surrounding_box(b0, b1);
         return true;
@@ -525,12 +587,16 @@ template <class R> struct MovingSphere : Hittable<R> {
 
 // aarect.rs — one class, axis = the constant axis (2: XyRect, 1: XzRect, 0: YzRect)
 template <class R> struct AARect : Hittable<R> {
-    int kaxis = 2; R a0 = 0, a1 = 0, b0 = 0, b1 = 0, k = 0; const Material<R>* mp = nullptr;
+    int kaxis = 2; R a0 = 0, a1 = 0, b0 = 0, b1 = 0, k = 0; const Material<R>* mp = nullptr; bool box_side = false;
     void axes(int& ia, int& ib) const { if (kaxis == 2) { ia = 0; ib = 1; } else if (kaxis == 1) { ia = 0; ib = 2; } else { ia = 1; ib = 2; } }
     bool hit(const Ray<R>& r, R t_min, R t_max, HitRecord<R>& rec, Ctx<R>& cx) const override {   // aarect.rs:31-48, 81-98, 150-167
         if (cx.cnt) cx.cnt->prim_tests[PT_RECT]++;
         int ia, ib; axes(ia, ib);
         R t = (k - r.orig.e[kaxis]) / r.dir.e[kaxis];
+        if (cx.rng->tmin && std::isfinite(t)) {
+            const R pa = r.orig.e[ia] + t * r.dir.e[ia], pb = r.orig.e[ib] + t * r.dir.e[ib];
+            if (!(pa < a0 || pa > a1 || pb < b0 || pb > b1)) cx.rng->root_at(t, t_min, r.dir.e[kaxis]);
+        }
         if (t < t_min || t > t_max) return false;
         if (!std::isfinite(t)) return false;   // measure-zero hazard (SURVEY §8a'): never accept t = inf/NaN
         R a = r.orig.e[ia] + t * r.dir.e[ia];
@@ -542,6 +608,7 @@ template <class R> struct AARect : Hittable<R> {
         Vec3<R> n(0, 0, 0); n.e[kaxis] = 1;
         rec.set_face_normal(r, n);
         rec.mat_ptr = mp;
+        rec.tags = box_side ? EV_HIT_BOX_SIDE : EV_HIT_RECT;
         rec.p = r.at(t);
         return true;
     }
@@ -565,6 +632,7 @@ template <class R> struct AARect : Hittable<R> {
     }
     Vec3<R> random(const Vec3<R>& origin, Ctx<R>& cx) const override {
         if (kaxis != 1) return Vec3<R>(1, 0, 0);
+        cx.ev(EV_LAMB_LIGHT_XZRECT);
         R rx = cx.rng->random_double_range(a0, a1);
         R rz = cx.rng->random_double_range(b0, b1);
         return Vec3<R>(rx, k, rz) - origin;
@@ -590,11 +658,13 @@ template <class R> struct Triangle : Hittable<R> {
         R v = dot(r.dir, qv) * inv;
         if (v < (R)0 || u + v > (R)1) return false;
         R t = dot(e2, qv) * inv;
+        if (cx.rng->tmin && std::isfinite(t)) cx.rng->root_at(t, t_min, dot(r.dir, cross(e1, e2).unit()));
         if (t < t_min || t > t_max || !std::isfinite(t)) return false;
         rec.t = t; rec.u = u; rec.v = v;
         rec.p = r.at(t);
         rec.set_face_normal(r, cross(e1, e2).unit());
         rec.mat_ptr = mp;
+        rec.tags = EV_HIT_TRI;
         return true;
     }
     bool bounding_box(R, R, Aabb<R>& out) const override {
@@ -647,7 +717,7 @@ template <class R> struct BoxObj : Hittable<R> {
     BoxObj(const Vec3<R>& p0, const Vec3<R>& p1, const Material<R>* m) : box_min(p0), box_max(p1) {
         auto add = [&](int kaxis, R a0, R a1, R b0, R b1, R k) {
             auto q = std::make_unique<AARect<R>>();
-            q->kaxis = kaxis; q->a0 = a0; q->a1 = a1; q->b0 = b0; q->b1 = b1; q->k = k; q->mp = m;
+            q->kaxis = kaxis; q->a0 = a0; q->a1 = a1; q->b0 = b0; q->b1 = b1; q->k = k; q->mp = m; q->box_side = true;
             sides.objects.push_back(q.get()); own.push_back(std::move(q));
         };
         add(2, p0.x(), p1.x(), p0.y(), p1.y(), p1.z());
@@ -671,6 +741,7 @@ template <class R> struct Translate : Hittable<R> {
         rec.p += offset;
         Vec3<R> norm = rec.normal;
         rec.set_face_normal(moved_r, norm);   // normal already opposes the ray => front_face forced true
+        rec.tags |= EV_UNDER_TRANSLATE;
         return true;
     }
     bool bounding_box(R t0, R t1, Aabb<R>& out) const override {
@@ -716,6 +787,7 @@ template <class R> struct RotateY : Hittable<R> {
         normal.e[2] = -sin_theta * rec.normal.e[0] + cos_theta * rec.normal.e[2];
         rec.p = p;
         rec.set_face_normal(rotated_r, normal);
+        rec.tags |= EV_UNDER_ROTATE_Y;
         return true;
     }
     bool bounding_box(R, R, Aabb<R>& out) const override { out = bbox; return hasbox; }
@@ -726,6 +798,7 @@ template <class R> struct FlipFace : Hittable<R> {
     bool hit(const Ray<R>& r, R t_min, R t_max, HitRecord<R>& rec, Ctx<R>& cx) const override {
         if (!ptr->hit(r, t_min, t_max, rec, cx)) return false;
         rec.front_face = !rec.front_face;   // the flag only; the normal is untouched (:199)
+        rec.tags |= EV_UNDER_FLIP_FACE;
         return true;
     }
     bool bounding_box(R t0, R t1, Aabb<R>& out) const override { return ptr->bounding_box(t0, t1, out); }
@@ -739,9 +812,10 @@ template <class R> struct ConstantMedium : Hittable<R> {
         HitRecord<R> rec1, rec2;
         R inf = std::numeric_limits<R>::infinity();
         Counters* saved = cx.cnt; cx.cnt = nullptr;   // the two boundary probes are part of this one medium test
+        double* saved_tmin = cx.rng->tmin; cx.rng->tmin = nullptr;   // (and their t_min is not the path's)
         bool h1 = boundary->hit(r, -inf, inf, rec1, cx);
         bool h2 = h1 && boundary->hit(r, rec1.t + (R)0.0001, inf, rec2, cx);
-        cx.cnt = saved;
+        cx.cnt = saved; cx.rng->tmin = saved_tmin;
         if (!h1 || !h2) return false;
         if (rec1.t < t_min) rec1.t = t_min;
         if (rec2.t > t_max) rec2.t = t_max;
@@ -753,13 +827,15 @@ template <class R> struct ConstantMedium : Hittable<R> {
         // traversal; this restatement keys the draw by (path, segment, medium) instead.
         R xi = Uni<R>::cv(medium_bits(cx.rng->base, cx.rng->segment, medium_id));
         R hit_distance = neg_inv_density * std::log(xi);
-        if (hit_distance > distance_inside_boundary) return false;
+        cx.rng->decided_by(std::fabs((double)hit_distance - (double)distance_inside_boundary) / (double)distance_inside_boundary);
+        if (hit_distance > distance_inside_boundary) { cx.ev(EV_MEDIUM_PASSED); return false; }
         rec.t = rec1.t + hit_distance / ray_length;
         rec.p = r.at(rec.t);
         rec.normal = Vec3<R>(1, 0, 0);
         rec.front_face = true;
         rec.u = 0; rec.v = 0;
         rec.mat_ptr = phase_function;
+        rec.tags = EV_MEDIUM_SCATTERED;
         return true;
     }
     bool bounding_box(R t0, R t1, Aabb<R>& out) const override { return boundary->bounding_box(t0, t1, out); }
@@ -967,16 +1043,35 @@ template <class R> Vec3<R> background_color(const Scene<R>& sc, const Ray<R>& r)
     return sc.background;
 }
 
-template <class R> Vec3<R> ray_color(const Ray<R>& r, const Scene<R>& sc, int depth, Ctx<R>& cx) {
+// A path record's perturbation: the direction rounded to f32 and moved by +-r_ulps f32 ulps per component (tests/rays.py does the same to
+// a single ray) — what an f32 kernel's rounding can do to every ray of a path, not only to the first.
+template <class R> Ray<R> perturbed(const Ray<R>& r, const PathRec& pr) {
+    Ray<R> q = r;
+    for (int c = 0; c < 3; ++c) {
+        const float f = (float)r.dir.e[c], a = std::fabs(f);
+        const float step = (float)pr.r_ulps * (std::nextafter(a, std::numeric_limits<float>::infinity()) - a);
+        q.dir.e[c] = (R)(f + (float)pr.sign[c] * step);
+    }
+    return q;
+}
+
+template <class R> Vec3<R> ray_color(const Ray<R>& r_in, const Scene<R>& sc, int depth, Ctx<R>& cx) {
     HitRecord<R> rec;
-    if (depth <= 0) return Vec3<R>();                                                        // main.rs:71-73
+    if (depth <= 0) { if (cx.path) cx.path->terminal = TERM_DEPTH; return Vec3<R>(); }       // main.rs:71-73
+    Ray<R> moved;
+    if (cx.path && cx.path->r_ulps > 0) moved = perturbed(r_in, *cx.path);
+    const Ray<R>& r = (cx.path && cx.path->r_ulps > 0) ? moved : r_in;
     if (cx.cnt) cx.cnt->segments++;
     bool h = sc.world->hit(r, (R)0.001, std::numeric_limits<R>::infinity(), rec, cx);        // main.rs:74
     cx.rng->segment++;
-    if (!h) return background_color(sc, r);                                                  // main.rs:75
+    if (!h) { if (cx.path) cx.path->terminal = TERM_MISS; return background_color(sc, r); }  // main.rs:75
+    cx.ev(rec.tags);
     ScatterRecord<R> srec;
-    Vec3<R> emitted = rec.mat_ptr->emitted(r, rec, rec.u, rec.v, rec.p);                     // main.rs:80-84
-    if (!rec.mat_ptr->scatter(r, rec, srec, cx)) return emitted;                             // main.rs:85-87
+    Vec3<R> emitted = rec.mat_ptr->emitted(r, rec, rec.u, rec.v, rec.p, cx);                 // main.rs:80-84
+    if (!rec.mat_ptr->scatter(r, rec, srec, cx)) {                                           // main.rs:85-87
+        if (cx.path) cx.path->terminal = rec.front_face ? TERM_EMITTER_FRONT : TERM_EMITTER_BACK;
+        return emitted;
+    }
     if (srec.is_specular) return srec.attenuation * ray_color(srec.specular_ray, sc, depth - 1, cx);   // main.rs:89-92
     Ray<R> scattered; R pdf_val;
     if (sc.lights) {
@@ -987,6 +1082,7 @@ template <class R> Vec3<R> ray_color(const Ray<R>& r, const Scene<R>& sc, int de
     } else {
         // no lights list: the reference's estimator would divide by zero (hittable_list.rs:74,82);
         // book-1/2 behaviour = sample the material's own CosinePdf (main.rs:119-121, commented)
+        cx.ev(EV_LAMB_COSINE_ONLY);
         scattered = Ray<R>(rec.p, srec.pdf_ptr->generate(cx), r.tm);
         pdf_val = srec.pdf_ptr->value(scattered.dir, cx);
     }
@@ -1047,9 +1143,12 @@ static Camera<R> camera_from(const RtCamera* cam_d) {
 
 // The sample loop main.rs:731-784 over the pixel rectangle [x0,x1) x [y0,y1). `compact`: rgb_sum holds the rectangle
 // only (row-major, (y1-y0) x (x1-x0) x 3) instead of the whole H x W frame.
+// Where orc_render_paths wants its per-sample records: arrays of [n_pixels_in_rect][spp], and the perturbation of every traced ray.
+struct PathOut { uint32_t* segments; uint32_t* terminal; uint32_t* events; double* margin; double* tmin_margin; int r_ulps; int sign[3]; };
+
 template <class R>
 static int render_rect(const Scene<R>& sc, const Camera<R>& cam, const RtParams* prm, int nt, bool count, int x0, int y0, int x1, int y1, bool compact,
-                       double* rgb_sum, OrcStats* st, double* per_sample /* optional: [n_pixels_in_rect][spp][3] */) {
+                       double* rgb_sum, OrcStats* st, double* per_sample /* optional: [n_pixels_in_rect][spp][3] */, const PathOut* po = nullptr) {
     const uint32_t W = prm->width, H = prm->height, spp = prm->samples_per_pixel;
     if (x0 < 0 || y0 < 0 || x1 > (int)W || y1 > (int)H || x1 <= x0 || y1 <= y0) { g_err = "bad rectangle"; return -1; }
     nt = std::max(1, nt);
@@ -1064,7 +1163,11 @@ static int render_rect(const Scene<R>& sc, const Camera<R>& cam, const RtParams*
                 const uint64_t pixel_index = (uint64_t)y * W + (uint64_t)x;
                 for (uint32_t s = 0; s < spp; ++s) {
                     Rng<R> g; g.base = path_base(prm->seed, pixel_index, s); g.state = g.base; g.segment = 0; g.cnt = count ? &cnt : nullptr;
-                    Ctx<R> cx{&g, count ? &cnt : nullptr, 0};
+                    PathRec pr;
+                    if (po) { pr.r_ulps = po->r_ulps; pr.sign[0] = po->sign[0]; pr.sign[1] = po->sign[1]; pr.sign[2] = po->sign[2]; g.margin = &pr.margin; g.tmin = &pr.tmin_margin; }
+                    Ctx<R> cx{&g, count ? &cnt : nullptr, 0, po ? &pr : nullptr};
+                    if (cam.lens_radius > (R)0) cx.ev(EV_LENS);
+                    if (cam.time0 < cam.time1) cx.ev(EV_TIME);
                     R ju = g.random_double(), jv = g.random_double();
                     R u = ((R)x + ju) / (R)(W - 1);                         // main.rs:752
                     R v = ((R)j + jv) / (R)(H - 1);                         // main.rs:753
@@ -1078,6 +1181,10 @@ static int render_rect(const Scene<R>& sc, const Camera<R>& cam, const RtParams*
                     if (per_sample) {
                         size_t pi = (size_t)(y - y0) * (size_t)(x1 - x0) + (size_t)(x - x0);
                         double* o = per_sample + (pi * spp + s) * 3; o[0] = cd[0]; o[1] = cd[1]; o[2] = cd[2];
+                    }
+                    if (po) {
+                        size_t k = ((size_t)(y - y0) * (size_t)(x1 - x0) + (size_t)(x - x0)) * spp + s;
+                        po->segments[k] = g.segment; po->terminal[k] = finite ? pr.terminal : TERM_NONFINITE; po->events[k] = pr.events; po->margin[k] = pr.margin; po->tmin_margin[k] = pr.tmin_margin;
                     }
                 }
                 double* o = compact ? rgb_sum + ((size_t)(y - y0) * (size_t)(x1 - x0) + (size_t)(x - x0)) * 3 : rgb_sum + ((size_t)y * W + x) * 3;
@@ -1100,13 +1207,13 @@ static int render_rect(const Scene<R>& sc, const Camera<R>& cam, const RtParams*
 
 template <class R>
 static int render_t(const RtSceneDesc* desc, const RtCamera* cam_d, const RtParams* prm, const OrcOpts* opt, double* rgb_sum, OrcStats* st,
-                    double* per_sample) {
+                    double* per_sample, const PathOut* po = nullptr) {
     Scene<R> sc;
     if (!sc.load(*desc)) { g_err = "scene: " + sc.error; return -1; }
     const Camera<R> cam = camera_from<R>(cam_d);
     int x0 = opt->x0, y0 = opt->y0, x1 = opt->x1, y1 = opt->y1;
     if (x1 <= x0 || y1 <= y0) { x0 = 0; y0 = 0; x1 = (int)prm->width; y1 = (int)prm->height; }
-    return render_rect<R>(sc, cam, prm, opt->n_threads, opt->count != 0, x0, y0, x1, y1, false, rgb_sum, st, per_sample);
+    return render_rect<R>(sc, cam, prm, opt->n_threads, opt->count != 0, x0, y0, x1, y1, false, rgb_sum, st, per_sample, po);
 }
 
 // The reference's own driver shape, main.rs:730-778: ONE PIXEL AT A TIME, `thread_num` threads spawned per pixel, each tracing
@@ -1134,7 +1241,7 @@ static int render_reference_shaped(const Scene<R>& sc, const Camera<R>& cam, con
                     for (uint32_t q = 0; q < k; ++q) {
                         const uint32_t s = (uint32_t)t * k + q;
                         Rng<R> g; g.base = path_base(prm->seed, pixel_index, s); g.state = g.base; g.segment = 0; g.cnt = nullptr;
-                        Ctx<R> cx{&g, nullptr, 0};
+                        Ctx<R> cx{&g, nullptr, 0, nullptr};
                         R ju = g.random_double(), jv = g.random_double();
                         R u = ((R)x + ju) / (R)(W - 1), v = ((R)j + jv) / (R)(H - 1);
                         Ray<R> r = cam.get_ray(u, v, g);
@@ -1196,6 +1303,25 @@ int orc_render_samples(const RtSceneDesc* desc, const RtCamera* cam, const RtPar
     return orc::render_t<double>(desc, cam, prm, opt, rgb_sum, st, per_sample);
 }
 
+/* orc_render_samples, and for every sample the record of its path: the number of world.hit calls, how it ended (0 miss -> background,
+ * 1 emitter seen from the front, 2 from the back, 3 depth exhausted, 4 non-finite: the radiance is scrubbed under RT_NAN_PER_SAMPLE), the
+ * mask of the branches it took (the EV_* bits above; oracle/binding.py names them) and the smallest margin by which one of its
+ * random-number thresholds was decided: | |p|^2 - 1 | of every rejection test, |reflectance - draw|, |free path - distance| / distance.
+ * tmin_margin: the smallest |root - t_min| * |d . n| over the primitive tests of the path (n the unit normal at that root): the distance by
+ * which the ray's origin would have to move along the normal to carry that root across t_min (a medium's boundary probes left out).
+ * r_ulps > 0 rounds the direction of every ray the path traces to f32 and moves it by sign[c] * r_ulps f32 ulps per component.
+ * Arrays of [pixels in rect][spp]; radiance is f64 at either precision. */
+int orc_render_paths(const RtSceneDesc* desc, const RtCamera* cam, const RtParams* prm, const OrcOpts* opt, int32_t r_ulps, const int32_t* sign3, double* rgb_sum,
+                     double* per_sample, uint32_t* segments, uint32_t* terminal, uint32_t* events, double* margin, double* tmin_margin, OrcStats* st) {
+    if (!desc || !cam || !prm || !opt || !rgb_sum || !per_sample || !segments || !terminal || !events || !margin || !tmin_margin || (r_ulps > 0 && !sign3) || r_ulps < 0) {
+        g_err = "null argument"; return -1;
+    }
+    orc::PathOut po{segments, terminal, events, margin, tmin_margin, r_ulps, {1, 1, 1}};
+    if (r_ulps > 0) for (int c = 0; c < 3; ++c) po.sign[c] = sign3[c] < 0 ? -1 : 1;
+    if (opt->precision == 32) return orc::render_t<float>(desc, cam, prm, opt, rgb_sum, st, per_sample, &po);
+    return orc::render_t<double>(desc, cam, prm, opt, rgb_sum, st, per_sample, &po);
+}
+
 /* n_rects rectangles (x0, y0, x1, y1 each) of one frame, scene built once; out = the rectangles back to back (compact). */
 int orc_render_crops(const RtSceneDesc* desc, const RtCamera* cam, const RtParams* prm, const OrcOpts* opt, int32_t n_rects, const int32_t* rects, double* out,
                      OrcStats* stats) {
@@ -1240,7 +1366,7 @@ void orc_camera_new(const double* lookfrom, const double* lookat, const double* 
 /* sphere.rs:41-65 — out = t, p[3], normal[3], u, v, front_face */
 int orc_sphere_hit(const double* center, double radius, const double* o, const double* d, double tm, double t_min, double t_max, double* out10) {
     orc::Sphere<double> s; s.center = VD(center[0], center[1], center[2]); s.radius = radius;
-    orc::Rng<double> g; orc::Ctx<double> cx{&g, nullptr, 0};
+    orc::Rng<double> g; orc::Ctx<double> cx{&g, nullptr, 0, nullptr};
     orc::HitRecord<double> rec;
     if (!s.hit(orc::Ray<double>(VD(o[0], o[1], o[2]), VD(d[0], d[1], d[2]), tm), t_min, t_max, rec, cx)) return 0;
     out10[0] = rec.t; for (int i = 0; i < 3; ++i) { out10[1 + i] = rec.p.e[i]; out10[4 + i] = rec.normal.e[i]; }
@@ -1249,13 +1375,13 @@ int orc_sphere_hit(const double* center, double radius, const double* o, const d
 }
 double orc_sphere_pdf_value(const double* center, double radius, const double* o, const double* v) {
     orc::Sphere<double> s; s.center = VD(center[0], center[1], center[2]); s.radius = radius;
-    orc::Rng<double> g; orc::Ctx<double> cx{&g, nullptr, 0};
+    orc::Rng<double> g; orc::Ctx<double> cx{&g, nullptr, 0, nullptr};
     return s.pdf_value(VD(o[0], o[1], o[2]), VD(v[0], v[1], v[2]), cx);
 }
 /* aarect.rs — kaxis 2/1/0 = Xy/Xz/Yz; out as orc_sphere_hit */
 int orc_rect_hit(int kaxis, const double* abk5, const double* o, const double* d, double t_min, double t_max, double* out10) {
     orc::AARect<double> q; q.kaxis = kaxis; q.a0 = abk5[0]; q.a1 = abk5[1]; q.b0 = abk5[2]; q.b1 = abk5[3]; q.k = abk5[4];
-    orc::Rng<double> g; orc::Ctx<double> cx{&g, nullptr, 0};
+    orc::Rng<double> g; orc::Ctx<double> cx{&g, nullptr, 0, nullptr};
     orc::HitRecord<double> rec;
     if (!q.hit(orc::Ray<double>(VD(o[0], o[1], o[2]), VD(d[0], d[1], d[2]), 0), t_min, t_max, rec, cx)) return 0;
     out10[0] = rec.t; for (int i = 0; i < 3; ++i) { out10[1 + i] = rec.p.e[i]; out10[4 + i] = rec.normal.e[i]; }
@@ -1264,7 +1390,7 @@ int orc_rect_hit(int kaxis, const double* abk5, const double* o, const double* d
 }
 double orc_xzrect_pdf_value(const double* abk5, const double* o, const double* v) {
     orc::AARect<double> q; q.kaxis = 1; q.a0 = abk5[0]; q.a1 = abk5[1]; q.b0 = abk5[2]; q.b1 = abk5[3]; q.k = abk5[4];
-    orc::Rng<double> g; orc::Ctx<double> cx{&g, nullptr, 0};
+    orc::Rng<double> g; orc::Ctx<double> cx{&g, nullptr, 0, nullptr};
     return q.pdf_value(VD(o[0], o[1], o[2]), VD(v[0], v[1], v[2]), cx);
 }
 void orc_onb_build_from_w(const double* n, double* out9) {
@@ -1288,7 +1414,7 @@ int orc_aabb_hit(const double* mn, const double* mx, const double* o, const doub
 int orc_world_hit(const RtSceneDesc* desc, const double* o, const double* d, double tm, double t_min, double t_max, double* out10) {
     orc::Scene<double> sc;
     if (!sc.load(*desc)) { g_err = "scene: " + sc.error; return -1; }
-    orc::Rng<double> g; orc::Ctx<double> cx{&g, nullptr, 0};
+    orc::Rng<double> g; orc::Ctx<double> cx{&g, nullptr, 0, nullptr};
     orc::HitRecord<double> rec;
     if (!sc.world->hit(orc::Ray<double>(VD(o[0], o[1], o[2]), VD(d[0], d[1], d[2]), tm), t_min, t_max, rec, cx)) return 0;
     out10[0] = rec.t; for (int i = 0; i < 3; ++i) { out10[1 + i] = rec.p.e[i]; out10[4 + i] = rec.normal.e[i]; }

@@ -1734,7 +1734,8 @@ DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& 
 
         if (kind == rtd::MK_DIFFUSE_LIGHT) {
             // emitted (material.rs:184-190); default scatter returns false -> main.rs:85-87
-            if (ff) L = s.T * colour;
+            // (the back emits nothing — but a throughput that is already non-finite, 0/0 of a pdf upstream, stays so: main.rs:130-138 multiplies it in)
+            L = ff ? s.T * colour : s.T * 0.f;
             finished = true;
         } else {
             if (kind == rtd::MK_LAMBERTIAN) {
@@ -1797,7 +1798,7 @@ DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& 
                 o = p; d = dir;
             }
             depth++;
-            if (depth >= rd.max_depth) finished = true;                     // main.rs:71-73: the next call returns 0
+            if (depth >= rd.max_depth) { finished = true; L = s.T * 0.f; }  // main.rs:71-73: the next call returns 0 (times the throughput: NaN stays NaN)
         }
     }
 

@@ -69,9 +69,11 @@ struct Compiler {
         if (depth > 128) return fail("graph too deep (cycle?)");
         const double* p = h->p;
         switch (h->kind) {
-        case RT_HIT_SPHERE: for (int i = 0; i < 3; ++i) { b.mn[i] = p[i] - p[3]; b.mx[i] = p[i] + p[3]; } return true;            // sphere.rs:66-73
+        // sphere.rs:66-73 with |radius|: the signed radius turns the box of a hollow ball's inner sphere (radius < 0) inside out, and which
+        // rays then find it depends on the tree's shape — the reference's own tree and each device layout's differ. (Same for MovingSphere.)
+        case RT_HIT_SPHERE: for (int i = 0; i < 3; ++i) { b.mn[i] = p[i] - std::fabs(p[3]); b.mx[i] = p[i] + std::fabs(p[3]); } return true;
         case RT_HIT_MOVING_SPHERE: {                                                                                                   // moving_sphere.rs:67-78
-            Box3 b0, b1; const double r = p[8];
+            Box3 b0, b1; const double r = std::fabs(p[8]);
             for (int i = 0; i < 3; ++i) {
                 const double c0 = p[i] + ((t0 - p[6]) / (p[7] - p[6])) * (p[3 + i] - p[i]);
                 const double c1 = p[i] + ((t1 - p[6]) / (p[7] - p[6])) * (p[3 + i] - p[i]);
