@@ -145,6 +145,15 @@ pub struct RtDenoiseGuide {
     pub sigma_albedo: f64, pub sigma_normal: f64, pub sigma_depth: f64,
 }
 pub const RT_DENOISE_GUIDED_MAX_WINDOW_RADIUS: u32 = 10;
+// guided denoising with feature variances (rt_denoise_guided_moments_device): the planes of rt_render_feature_moments_device; 0 = default
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct RtDenoiseGuideMoments {
+    pub struct_bytes: u32, pub feature_samples: u32,
+    pub albedo_sum: *const c_void, pub normal_sum: *const c_void, pub depth_sum: *const c_void, pub hits: *const c_void,
+    pub albedo_sq_sum: *const c_void, pub normal_sq_sum: *const c_void, pub depth_sq_sum: *const c_void,
+    pub sigma_albedo: f64, pub sigma_normal: f64, pub sigma_depth: f64, pub variance_strength: f64,
+}
+pub const RT_DENOISE_GUIDED_MOMENTS_MAX_WINDOW_RADIUS: u32 = 8;
 // ray queries: the closest hit of caller-supplied rays (rt_trace_rays); t_max <= 0 or +inf = no limit
 #[repr(C)] #[derive(Clone, Copy, Default, Debug)]
 pub struct RtRay { pub o: [f32; 3], pub time: f32, pub d: [f32; 3], pub t_max: f32 }
@@ -162,6 +171,13 @@ pub const RT_FEATURES_ACCUMULATE: u32 = 1;
 pub struct RtFeatureOptions { pub struct_bytes: u32, pub flags: u32, pub first_sample: u32, pub pool_slots: u32 }
 #[repr(C)] #[derive(Clone, Copy, Debug)]
 pub struct RtFeatureBuffers { pub albedo_sum: *mut c_void, pub normal_sum: *mut c_void, pub depth_sum: *mut c_void, pub hits: *mut c_void }
+// the same pass with the per-slot sums of squares beside the sums (rt_render_feature_moments_device)
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct RtFeatureMomentBuffers {
+    pub struct_bytes: u32, pub _pad: u32,
+    pub albedo_sum: *mut c_void, pub normal_sum: *mut c_void, pub depth_sum: *mut c_void, pub hits: *mut c_void,
+    pub albedo_sq_sum: *mut c_void, pub normal_sq_sum: *mut c_void, pub depth_sq_sum: *mut c_void,
+}
 pub const RT_DENOISE_MAX_WINDOW_RADIUS: u32 = 16;
 pub const RT_DENOISE_MAX_PATCH_RADIUS: u32 = 4;
 
@@ -246,6 +262,12 @@ extern "C" {
     pub fn rt_denoise_guided_device(ctx: *mut RtCtx, options: *const RtDenoiseOptions, guide: *const RtDenoiseGuide, width: u32, height: u32,
                                     rgb_sum_device: *const c_void, sq_sum_device: *const c_void, samples: u32, counts_device: *const c_void,
                                     mean_out_device: *mut c_void) -> c_int;
+    /// host only: validates the options and the guide of the variance-guided filter (window_radius 0 = 8, at most 8; feature_samples >= 2)
+    pub fn rt_denoise_guided_moments_check(width: u32, height: u32, options: *const RtDenoiseOptions, guide: *const RtDenoiseGuideMoments) -> c_int;
+    /// rt_denoise_guided_device with the feature distance variance-cancelled and variance-normalised from the features' second moments
+    pub fn rt_denoise_guided_moments_device(ctx: *mut RtCtx, options: *const RtDenoiseOptions, guide: *const RtDenoiseGuideMoments, width: u32, height: u32,
+                                            rgb_sum_device: *const c_void, sq_sum_device: *const c_void, samples: u32, counts_device: *const c_void,
+                                            mean_out_device: *mut c_void) -> c_int;
     /// host only: validates ray-query options (null = defaults) and a ray count
     pub fn rt_ray_query_check(options: *const RtRayQueryOptions, n_rays: u64) -> c_int;
     /// closest hits of n_rays RtRay records in device memory, one RtRayHit each (device memory, 16-byte aligned)
@@ -258,6 +280,11 @@ extern "C" {
     /// first-hit feature sums of samples [first_sample, first_sample + samples_per_pixel) into the caller's device planes (null = not wanted)
     pub fn rt_render_features_device(ctx: *mut RtCtx, scene: *const RtScene, cam: *const RtCamera, params: *const RtParams,
                                      options: *const RtFeatureOptions, buffers: *const RtFeatureBuffers, stats: *mut RtStats) -> c_int;
+    /// host only: validates a feature pass with second moments (params, options, the buffers' struct_bytes)
+    pub fn rt_feature_moments_check(params: *const RtParams, options: *const RtFeatureOptions, buffers: *const RtFeatureMomentBuffers) -> c_int;
+    /// rt_render_features_device plus the per-slot sums of squares of albedo, normal and depth
+    pub fn rt_render_feature_moments_device(ctx: *mut RtCtx, scene: *const RtScene, cam: *const RtCamera, params: *const RtParams,
+                                            options: *const RtFeatureOptions, buffers: *const RtFeatureMomentBuffers, stats: *mut RtStats) -> c_int;
     pub fn rt_untile(params: *const RtParams, gathered: *const f32, rgb_sum: *mut f32) -> c_int;
     /// write_color (main.rs:141-169) on the device
     pub fn rt_resolve_device(ctx: *mut RtCtx, rgb_sum_device: *const c_void, width: u32, height: u32,

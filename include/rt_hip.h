@@ -465,6 +465,68 @@ int rt_denoise_guided_device(RtCtx* ctx, const RtDenoiseOptions* options /* NULL
                              const void* rgb_sum_device, const void* sq_sum_device, uint32_t samples, const void* counts_device /* NULL = uniform `samples` */,
                              void* mean_out_device);
 
+/* ---- denoising, guided with feature variances: g(p,q) variance-cancelled and variance-normalised ----------------------------------------------
+ *
+ * rt_denoise_guided_device's inputs plus the SQUARED sums of the features as rt_render_feature_moments_device writes them with
+ * shard_count <= 1: albedo_sq_sum and normal_sq_sum (3 f32 per pixel), depth_sq_sum (1 f32), over the same n_f >= 2 samples. At a few
+ * samples per pixel the features are themselves noisy where a pixel sees several surfaces (small spheres, silhouettes, light edges); the
+ * plain squared distance of the guided filter then separates pixels the patch distance would rightly average. Here the feature distance
+ * takes the form the colour distance already has (Rousselle, Knaus, Zwicker 2012, 2013): the expected squared difference of two noisy
+ * means is subtracted, and what is left is damped where the features are uncertain.
+ * COLOUR PART: u, v, validity and the patch distance d(p,q) are exactly those of rt_denoise_device.
+ * GUIDE, per pixel, in f64; h = hits, S a sum, Q its squared sum:
+ *     var(S, Q) = max(Q - S^2 / n_f, 0) / (n_f (n_f - 1))          the variance of the mean over ALL n_f samples
+ *     a_c = albedo_sum_c / n_f     n_c = normal_sum_c / n_f     md = max(depth_sum / h, 1e-30)     z = ln(md) when h > 0, else 0
+ *     VA = sum_c var(albedo_sum_c, albedo_sq_sum_c)     VN = sum_c var(normal_sum_c, normal_sq_sum_c)
+ *     VZ = var(depth_sum, depth_sq_sum) (n_f / h)^2 / md^2 when h > 0, else 0       the delta method on the log; over all samples, so partial
+ *                                                                                   coverage inflates it and the guide weakens on silhouettes
+ *   The record holds TEN components, each over its group's sigma: A_c = a_c / sigma_albedo, N_c = n_c / sigma_normal, Z = z / sigma_depth and
+ *   the standard errors sA = sqrt(VA) / sigma_albedo, sN = sqrt(VN) / sigma_normal, sZ = sqrt(VZ) / sigma_depth (roots: a variance of 1e-8
+ *   is below binary16's range, its root is not). Each goes f64 -> f32 -> binary16 (round to nearest even), clamped to +-65504.
+ * FILTER, in f32 from the binary16 values, with V_j = s_j^2 and kappa = variance_strength:
+ *     g(p,q) = sum over j in {A, N, Z} of  max(|F_j,p - F_j,q|^2 - (V_j,p + min(V_j,p, V_j,q)), 0) / (1 + kappa (V_j,p + V_j,q))
+ *     w(p,q) = exp(-(max(d(p,q), 0) + g(p,q)))       (w(p,p) = 1)     |.|^2 over the group's components
+ *     out[p] = sum_q w(p,q) u[q] / sum_q w(p,q)      accumulated as differences from u[p]: a constant frame returns bit for bit
+ * A sum plane that is NULL zeroes its group (components and variance); a squared plane that is NULL zeroes its group's variance — with all
+ * three NULL, g is rt_denoise_guided_device's. depth_sum requires hits. All three sum planes NULL is RT_ERR_INVALID. A pixel is
+ * additionally INVALID when a given feature sum or squared sum is not finite or hits > n_f; invalid pixels behave as above.
+ * Defaults: a field left 0 takes its default — sigma_albedo 0.01, sigma_normal 0.025, sigma_depth 0.01, variance_strength 64: the best point
+ * of the grid measured in DESIGN.md §10 (scripts/cpu_guided_moments.py) — and a negative, NaN, infinite or -0.0 value, a sigma whose f32
+ * reciprocal is not finite and positive, or a variance_strength that is not finite in f32 is RT_ERR_INVALID. feature_samples < 2 is
+ * RT_ERR_INVALID (no variance).
+ * Caps: patch_radius <= 4; window_radius <= RT_DENOISE_GUIDED_MOMENTS_MAX_WINDOW_RADIUS = 8, refused above, and for THIS entry point
+ * window_radius 0 means 8: per pixel of the tile plus an r halo the LDS holds the 16-byte record and an 8-byte one (sA, sN, sZ, 0) beside
+ * the colour planes (at r 8, f 4: 56 x 56 x 24 B + 48 x 48 x 24 B + 23,040 B = 153,600 B of 163,840 B; r 9 does not fit).
+ * Determinism and aliasing: as rt_denoise_guided_device — a function of the inputs and options alone; mean_out must not be one of the
+ * inputs (rgb_sum, sq_sum, counts, the four sum planes, hits among them, and the three squared planes); the inputs are never written. */
+#define RT_DENOISE_GUIDED_MOMENTS_MAX_WINDOW_RADIUS 8
+#define RT_DENOISE_MOMENTS_SIGMA_ALBEDO 0.01
+#define RT_DENOISE_MOMENTS_SIGMA_NORMAL 0.025
+#define RT_DENOISE_MOMENTS_SIGMA_DEPTH 0.01
+#define RT_DENOISE_MOMENTS_VARIANCE_STRENGTH 64.0
+typedef struct RtDenoiseGuideMoments {
+    uint32_t struct_bytes;      /* sizeof(RtDenoiseGuideMoments) as the caller compiled it (the struct may grow at its end) */
+    uint32_t feature_samples;   /* n_f >= 2: the samples per pixel the planes were folded over */
+    const void* albedo_sum;     /* device, width * height * 3 f32; NULL = not used */
+    const void* normal_sum;     /* device, width * height * 3 f32; NULL = not used */
+    const void* depth_sum;      /* device, width * height f32; NULL = not used; needs hits */
+    const void* hits;           /* device, width * height u32; NULL = none */
+    const void* albedo_sq_sum;  /* device, width * height * 3 f32; NULL = variance 0 */
+    const void* normal_sq_sum;  /* device, width * height * 3 f32; NULL = variance 0 */
+    const void* depth_sq_sum;   /* device, width * height f32; NULL = variance 0 */
+    double sigma_albedo;        /* 0 = RT_DENOISE_MOMENTS_SIGMA_ALBEDO */
+    double sigma_normal;        /* 0 = RT_DENOISE_MOMENTS_SIGMA_NORMAL */
+    double sigma_depth;         /* 0 = RT_DENOISE_MOMENTS_SIGMA_DEPTH */
+    double variance_strength;   /* kappa; 0 = RT_DENOISE_MOMENTS_VARIANCE_STRENGTH */
+} RtDenoiseGuideMoments;
+/* Host only, no device: validates (width, height, options; NULL = defaults, guide) and reports the reason through rt_last_error. The plane
+   pointers are only tested against NULL. */
+int rt_denoise_guided_moments_check(uint32_t width, uint32_t height, const RtDenoiseOptions* options, const RtDenoiseGuideMoments* guide);
+/* Three kernels on the context's stream; blocks until done. A refused call writes nothing. */
+int rt_denoise_guided_moments_device(RtCtx* ctx, const RtDenoiseOptions* options /* NULL = defaults */, const RtDenoiseGuideMoments* guide, uint32_t width,
+                                     uint32_t height, const void* rgb_sum_device, const void* sq_sum_device, uint32_t samples,
+                                     const void* counts_device /* NULL = uniform `samples` */, void* mean_out_device);
+
 /* ---- ray queries: the closest hit of caller-supplied rays ----------------------------------------------------------------------------------
  *
  * hits[i] is the HitRecord that `world.hit(ray_i, 0.001, inf)` returns (main.rs:74, hittable.rs:11-19) for the uploaded scene: t, p, the
@@ -556,6 +618,34 @@ typedef struct RtFeatureBuffers {   /* device memory the caller owns; any pointe
 int rt_features_check(const RtParams* params, const RtFeatureOptions* options);
 int rt_render_features_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* params, const RtFeatureOptions* options,
                               const RtFeatureBuffers* buffers, RtStats* stats);
+
+/* ---- first-hit features, second moments: the same pass with per-slot sums of squares -------------------------------------------------------
+ *
+ * Everything stated for rt_render_features_device holds — rays, samples, slots, sharding, chunking, refusals — and the four sum planes
+ * written here are bit for bit the ones it writes. Beside them, per output slot, three optional planes: albedo_sq_sum (3 f32),
+ * normal_sq_sum (3 f32) and depth_sq_sum (1 f32), each the sum over the pass's samples of the SQUARE of that sample's value: the square is
+ * formed in f32 (x * x, rounded, then added; never fused), a miss adds 0 to normal and depth. Folded sequentially in sample order in f32
+ * from 0 — or, under RT_FEATURES_ACCUMULATE, from the value already in the plane — so passes over [0, a) and [a, N), the second
+ * accumulating, leave the bits of one pass over [0, N), for the sums and the squares alike; and neither depends on pool_slots, the
+ * chunking or the shard. What a variance-normalised guide needs (rt_denoise_guided_moments_device): the variance of a feature's mean over
+ * n samples is max(Q - S^2 / n, 0) / (n (n - 1)).
+ * Any pointer may be NULL = not wanted; all seven NULL, a pointer that is not 16-byte aligned, or struct_bytes <
+ * sizeof(RtFeatureMomentBuffers) is RT_ERR_INVALID and nothing is written. RtStats as for rt_render_features_device. */
+typedef struct RtFeatureMomentBuffers {   /* device memory the caller owns; any pointer may be NULL = not wanted; 16-byte aligned */
+    uint32_t struct_bytes;    /* sizeof(RtFeatureMomentBuffers) as the caller compiled it (the struct may grow at its end) */
+    uint32_t _pad;
+    void* albedo_sum;         /* as RtFeatureBuffers */
+    void* normal_sum;
+    void* depth_sum;
+    void* hits;
+    void* albedo_sq_sum;      /* 3 f32 per slot */
+    void* normal_sq_sum;      /* 3 f32 per slot */
+    void* depth_sq_sum;       /* 1 f32 per slot */
+} RtFeatureMomentBuffers;
+/* Host only, no device: validates (params, options, buffers' struct_bytes) and reports the reason through rt_last_error. */
+int rt_feature_moments_check(const RtParams* params, const RtFeatureOptions* options, const RtFeatureMomentBuffers* buffers);
+int rt_render_feature_moments_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* params, const RtFeatureOptions* options,
+                                     const RtFeatureMomentBuffers* buffers, RtStats* stats);
 
 /* Host-side helper: scatter `shard_count` gathered shard buffers (each rt_output_floats long,
    in shard order) into a full-frame rgb_sum. */

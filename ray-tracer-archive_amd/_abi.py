@@ -19,6 +19,8 @@ RT_PASS_ACCUMULATE = 1
 RT_COMM_ID_BYTES = 128
 RT_DENOISE_MAX_WINDOW_RADIUS, RT_DENOISE_MAX_PATCH_RADIUS = 16, 4
 RT_DENOISE_GUIDED_MAX_WINDOW_RADIUS = 10
+RT_DENOISE_GUIDED_MOMENTS_MAX_WINDOW_RADIUS = 8
+RT_DENOISE_MOMENTS_SIGMA_ALBEDO, RT_DENOISE_MOMENTS_SIGMA_NORMAL, RT_DENOISE_MOMENTS_SIGMA_DEPTH, RT_DENOISE_MOMENTS_VARIANCE_STRENGTH = 0.01, 0.025, 0.01, 64.0
 RT_RAYHIT_HIT, RT_RAYHIT_FRONT_FACE, RT_RAYHIT_INVALID_RAY = 1, 2, 4
 RT_FEATURES_ACCUMULATE = 1
 # RtUploadOptions.layout_flags
@@ -125,6 +127,12 @@ class RtDenoiseGuide(C.Structure):
                 ("depth_sum", C.c_void_p), ("hits", C.c_void_p), ("sigma_albedo", C.c_double), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double)]
 
 
+class RtDenoiseGuideMoments(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("feature_samples", C.c_uint32), ("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p),
+                ("depth_sum", C.c_void_p), ("hits", C.c_void_p), ("albedo_sq_sum", C.c_void_p), ("normal_sq_sum", C.c_void_p), ("depth_sq_sum", C.c_void_p),
+                ("sigma_albedo", C.c_double), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double), ("variance_strength", C.c_double)]
+
+
 class RtRay(C.Structure):
     _fields_ = [("o", C.c_float * 3), ("time", C.c_float), ("d", C.c_float * 3), ("t_max", C.c_float)]
 
@@ -146,6 +154,11 @@ class RtFeatureBuffers(C.Structure):
     _fields_ = [("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p), ("depth_sum", C.c_void_p), ("hits", C.c_void_p)]
 
 
+class RtFeatureMomentBuffers(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("_pad", C.c_uint32), ("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p), ("depth_sum", C.c_void_p),
+                ("hits", C.c_void_p), ("albedo_sq_sum", C.c_void_p), ("normal_sq_sum", C.c_void_p), ("depth_sq_sum", C.c_void_p)]
+
+
 class RtWideInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("n_leaf_entries", C.c_uint64), ("n_inner_entries", C.c_uint64), ("n_prims", C.c_uint64),
                 ("depth", C.c_uint32), ("_pad", C.c_uint32), ("mean_children", C.c_double), ("mean_leaf_members", C.c_double)]
@@ -162,7 +175,8 @@ RT_HIP_SYMBOLS = ["rt_ctx_create", "rt_ctx_destroy", "rt_scene_upload", "rt_scen
                   "rt_adaptive_check", "rt_adaptive_select", "rt_render_pass_pixels_device", "rt_resolve_counts_device",
                   "rt_denoise_check", "rt_denoise_device", "rt_denoise_guided_check", "rt_denoise_guided_device",
                   "rt_ray_query_check", "rt_trace_rays_device", "rt_trace_rays",
-                  "rt_features_check", "rt_render_features_device"]
+                  "rt_features_check", "rt_render_features_device",
+                  "rt_feature_moments_check", "rt_render_feature_moments_device", "rt_denoise_guided_moments_check", "rt_denoise_guided_moments_device"]
 RT_HOST_SYMBOLS = ["rt_host_scene_create", "rt_host_scene_desc", "rt_host_scene_camera", "rt_host_scene_destroy", "rt_host_camera_new",
                    "rt_host_write_color", "rt_host_tonemap", "rt_host_write_png", "rt_host_write_jpeg", "rt_host_write_image"]
 
@@ -231,6 +245,14 @@ def declare(lib):
     lib.rt_features_check.argtypes = [P(RtParams), P(RtFeatureOptions)]
     lib.rt_render_features_device.restype = i32
     lib.rt_render_features_device.argtypes = [vp, vp, P(RtCamera), P(RtParams), P(RtFeatureOptions), P(RtFeatureBuffers), P(RtStats)]
+    lib.rt_feature_moments_check.restype = i32
+    lib.rt_feature_moments_check.argtypes = [P(RtParams), P(RtFeatureOptions), P(RtFeatureMomentBuffers)]
+    lib.rt_render_feature_moments_device.restype = i32
+    lib.rt_render_feature_moments_device.argtypes = [vp, vp, P(RtCamera), P(RtParams), P(RtFeatureOptions), P(RtFeatureMomentBuffers), P(RtStats)]
+    lib.rt_denoise_guided_moments_check.restype = i32
+    lib.rt_denoise_guided_moments_check.argtypes = [u32, u32, P(RtDenoiseOptions), P(RtDenoiseGuideMoments)]
+    lib.rt_denoise_guided_moments_device.restype = i32
+    lib.rt_denoise_guided_moments_device.argtypes = [vp, P(RtDenoiseOptions), P(RtDenoiseGuideMoments), u32, u32, vp, vp, u32, vp, vp]
     lib.rt_untile.restype = i32
     lib.rt_untile.argtypes = [P(RtParams), P(C.c_float), P(C.c_float)]
     lib.rt_resolve_device.restype = i32

@@ -87,6 +87,21 @@ def denoise_guided_check(width, height, options, guide):
     _check(lib().rt_denoise_guided_check(width, height, C.byref(options) if options is not None else None, C.byref(guide) if guide is not None else None))
 
 
+def denoise_guide_moments(feature_samples, albedo=None, normal=None, depth=None, hits=None, albedo_sq=None, normal_sq=None, depth_sq=None,
+                          sigma_albedo=0.0, sigma_normal=0.0, sigma_depth=0.0, variance_strength=0.0):
+    """RtDenoiseGuideMoments (include/rt_hip.h, "denoising, guided with feature variances"): the planes of rt_render_feature_moments_device
+    — CUDA tensors, raw device addresses, or None — folded over feature_samples >= 2 samples per pixel; a sigma or the variance strength
+    left 0 takes its default."""
+    ptr = lambda t: None if t is None else int(t) if isinstance(t, int) else t.data_ptr()
+    return A.RtDenoiseGuideMoments(C.sizeof(A.RtDenoiseGuideMoments), int(feature_samples), ptr(albedo), ptr(normal), ptr(depth), ptr(hits), ptr(albedo_sq),
+                                   ptr(normal_sq), ptr(depth_sq), float(sigma_albedo), float(sigma_normal), float(sigma_depth), float(variance_strength))
+
+
+def denoise_guided_moments_check(width, height, options, guide):
+    """rt_denoise_guided_moments_check (host only): raises RtError (RT_ERR_INVALID, with the reason) for what the variance-guided filter refuses."""
+    _check(lib().rt_denoise_guided_moments_check(width, height, C.byref(options) if options is not None else None, C.byref(guide) if guide is not None else None))
+
+
 # numpy views of RtRay / RtRayHit (include/rt_hip.h, "ray queries"): 32 and 48 bytes, field for field
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("time", np.float32), ("d", np.float32, 3), ("t_max", np.float32)])
 RAYHIT_DTYPE = np.dtype([("t", np.float32), ("hittable", np.int32), ("material", np.int32), ("flags", np.uint32),
@@ -111,6 +126,17 @@ def feature_options(first_sample=0, accumulate=False, pool_slots=0, flags=None):
 def features_check(params, options):
     """rt_features_check (host only): raises RtError (RT_ERR_INVALID, with the reason) for a feature pass the contract refuses."""
     _check(lib().rt_features_check(C.byref(params), C.byref(options) if options is not None else None))
+
+
+def feature_moment_buffers(albedo=None, normal=None, depth=None, hits=None, albedo_sq=None, normal_sq=None, depth_sq=None):
+    """RtFeatureMomentBuffers (include/rt_hip.h, "first-hit features, second moments"): CUDA tensors, raw device addresses, or None."""
+    ptr = lambda t: None if t is None else int(t) if isinstance(t, int) else t.data_ptr()
+    return A.RtFeatureMomentBuffers(C.sizeof(A.RtFeatureMomentBuffers), 0, ptr(albedo), ptr(normal), ptr(depth), ptr(hits), ptr(albedo_sq), ptr(normal_sq), ptr(depth_sq))
+
+
+def feature_moments_check(params, options, buffers):
+    """rt_feature_moments_check (host only): raises RtError (RT_ERR_INVALID, with the reason) for a pass with second moments the contract refuses."""
+    _check(lib().rt_feature_moments_check(C.byref(params), C.byref(options) if options is not None else None, C.byref(buffers) if buffers is not None else None))
 
 
 def _check_device(a, b, n, what, float_):
@@ -492,6 +518,34 @@ class Context:
         _check(lib().rt_render_features_device(self._h, scene._h, C.byref(cam), C.byref(params), C.byref(opt), C.byref(buf), C.byref(st)), self._h)
         return planes + (st.as_dict(),) if with_stats else planes
 
+    def render_feature_moments(self, scene, cam, params, first_sample=0, accumulate=False, albedo=None, normal=None, depth=None, hits=None, albedo_sq=None,
+                               normal_sq=None, depth_sq=None, pool_slots=0, with_stats=False):
+        """rt_render_feature_moments_device: render_features with the per-slot sums of squares beside the sums — albedo_sq / normal_sq
+        float32 of 3 * slots elements, depth_sq float32 of slots. Only the planes given are written; with none given all seven are made
+        (zero-filled). Returns (albedo, normal, depth, hits, albedo_sq, normal_sq, depth_sq), None for a plane not wanted, and the stats
+        too with with_stats. A refused call raises RtError and leaves the planes untouched."""
+        import torch
+        slots = output_floats(params) // 3
+        planes = (albedo, normal, depth, hits, albedo_sq, normal_sq, depth_sq)
+        if all(t is None for t in planes):
+            if accumulate:
+                raise ValueError("an accumulating feature pass needs the planes to add into")
+            dev = torch.device("cuda", self.device_id)
+            planes = tuple(torch.zeros(n * slots, dtype=torch.int32 if i == 3 else torch.float32, device=dev) for i, n in enumerate((3, 3, 1, 1, 3, 3, 1)))
+        albedo, normal, depth, hits, albedo_sq, normal_sq, depth_sq = planes
+        _check_device(albedo, normal, n=3 * slots, what="albedo / normal", float_=True)
+        _check_device(albedo_sq, normal_sq, n=3 * slots, what="albedo_sq / normal_sq", float_=True)
+        _check_device(depth, depth_sq, n=slots, what="depth / depth_sq", float_=True)
+        _check_device(hits, None, n=slots, what="hits", float_=False)
+        if any(t is not None and t.device.index != self.device_id for t in planes):      # another GPU's pointer means nothing to this context's kernels
+            raise ValueError(f"feature planes must live on this context's device (cuda:{self.device_id})")
+        opt = feature_options(first_sample, accumulate, pool_slots)
+        buf = feature_moment_buffers(*planes)
+        st = A.RtStats()
+        torch.cuda.synchronize(torch.device("cuda", self.device_id))        # the library's stream is not torch's
+        _check(lib().rt_render_feature_moments_device(self._h, scene._h, C.byref(cam), C.byref(params), C.byref(opt), C.byref(buf), C.byref(st)), self._h)
+        return planes + (st.as_dict(),) if with_stats else planes
+
     # ---- denoising (include/rt_hip.h, "denoising"): device tensors only ----
     def denoise(self, rgb_sum, sq_sum, width, height, samples=0, counts=None, options=None, out=None):
         """rt_denoise_device: the filtered MEAN radiance of a full frame from its sums (float32 CUDA tensors of width * height * 3
@@ -534,6 +588,35 @@ class Context:
         _check(lib().rt_denoise_guided_device(self._h, C.byref(options) if options is not None else None, C.byref(guide), width, height,
                                               C.c_void_p(rgb_sum.data_ptr()), C.c_void_p(sq_sum.data_ptr()), int(samples),
                                               C.c_void_p(counts.data_ptr()) if counts is not None else None, C.c_void_p(out.data_ptr())), self._h)
+        return out
+
+    def denoise_guided_moments(self, rgb_sum, sq_sum, width, height, feature_samples, albedo=None, normal=None, depth=None, hits=None, albedo_sq=None,
+                               normal_sq=None, depth_sq=None, samples=0, counts=None, options=None, sigma_albedo=0.0, sigma_normal=0.0, sigma_depth=0.0,
+                               variance_strength=0.0, out=None):
+        """rt_denoise_guided_moments_device: Context.denoise_guided with the feature distance variance-cancelled and variance-normalised
+        from the squared sums of render_feature_moments (albedo_sq / normal_sq float32 of width * height * 3, depth_sq float32 of
+        width * height; None = that group's variance is 0), feature_samples >= 2. window_radius 0 means 8 here, at most 8. Returns `out`;
+        a refused call raises RtError and leaves `out` untouched."""
+        import torch
+        n = 3 * width * height
+        _check_device(rgb_sum, sq_sum, n=n, what="rgb_sum / sq_sum", float_=True)
+        if counts is not None:
+            _check_device(counts, None, n=width * height, what="counts", float_=False)
+        _check_device(albedo, normal, n=n, what="albedo / normal", float_=True)
+        _check_device(albedo_sq, normal_sq, n=n, what="albedo_sq / normal_sq", float_=True)
+        _check_device(depth, depth_sq, n=width * height, what="depth / depth_sq", float_=True)
+        _check_device(hits, None, n=width * height, what="hits", float_=False)
+        if any(t is not None and t.device != rgb_sum.device for t in (albedo, normal, depth, hits, albedo_sq, normal_sq, depth_sq, counts, sq_sum)):
+            raise ValueError("the sums, the counts and the feature planes must live on one device")
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=rgb_sum.device)
+        _check_device(out, None, n=n, what="out", float_=True)
+        guide = denoise_guide_moments(feature_samples, albedo, normal, depth, hits, albedo_sq, normal_sq, depth_sq, sigma_albedo, sigma_normal, sigma_depth,
+                                      variance_strength)
+        torch.cuda.synchronize(rgb_sum.device)        # the library's stream is not torch's
+        _check(lib().rt_denoise_guided_moments_device(self._h, C.byref(options) if options is not None else None, C.byref(guide), width, height,
+                                                      C.c_void_p(rgb_sum.data_ptr()), C.c_void_p(sq_sum.data_ptr()), int(samples),
+                                                      C.c_void_p(counts.data_ptr()) if counts is not None else None, C.c_void_p(out.data_ptr())), self._h)
         return out
 
     # ---- one process per GPU: RCCL communicator on this context (rt_multi.cpp) ----

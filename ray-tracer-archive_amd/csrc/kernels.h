@@ -204,6 +204,10 @@ hipError_t launch_features_import(const RenderDev& rd, const FeatDev& fd, const 
 hipError_t launch_features_export(const LaunchCfg& cfg, const SceneDev& sc, const RenderDev& rd, const FeatDev& fd, const PoolDev& pool, uint32_t max_count,
                                   const uint32_t* counts, hipStream_t stream);
 hipError_t launch_features_fold(const RenderDev& rd, const FeatDev& fd, hipStream_t stream);
+// the fold with second moments (rt_hip.h "first-hit features, second moments"): the caller's squared-sum planes, nullptr = not wanted. Its
+// own block beside FeatDev, so that the kernels which take FeatDev alone keep their arguments.
+struct FeatMomDev { float* albedo_sq; float* normal_sq; float* depth_sq; };
+hipError_t launch_features_fold_moments(const RenderDev& rd, const FeatDev& fd, const FeatMomDev& fm, hipStream_t stream);
 // multi-GPU root: gathered shard buffers -> full frame (rt_multi.cpp)
 hipError_t launch_untile_f32(const float* gathered, float* frame, uint32_t width, uint32_t height, uint32_t ts, uint32_t tiles_x, uint32_t world, uint64_t per_shard,
                              hipStream_t stream);

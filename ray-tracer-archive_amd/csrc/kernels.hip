@@ -2393,6 +2393,47 @@ __global__ void __launch_bounds__(256) k_features_fold(RenderDev rd, FeatDev fd)
     if (ph) *ph = nh;
 }
 
+// k_features_fold_moments: k_features_fold with the second moments beside the sums (rt_hip.h, "first-hit features, second moments"): per
+// record the square of each value is formed in f32 (x * x: the build contracts nothing) and added, in sample order, into the wanted squared
+// planes. The sums take k_features_fold's additions in its order, so the four sum planes are its bits. Same records; nothing new per ray.
+__global__ void __launch_bounds__(256) k_features_fold_moments(RenderDev rd, FeatDev fd, FeatMomDev fm) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= fd.ns) return;
+    const uint32_t slot = fd.slot0 + s;
+    uint32_t x, y; slot_pixel(rd, slot, x, y);
+    if (x >= rd.width || y >= rd.height) return;
+    float* pa = fd.albedo ? fd.albedo + 3ull * slot : nullptr;
+    float* pn = fd.normal ? fd.normal + 3ull * slot : nullptr;
+    float* pd = fd.depth ? fd.depth + slot : nullptr;
+    uint32_t* ph = fd.hits ? fd.hits + slot : nullptr;
+    float* qa = fm.albedo_sq ? fm.albedo_sq + 3ull * slot : nullptr;
+    float* qn = fm.normal_sq ? fm.normal_sq + 3ull * slot : nullptr;
+    float* qd = fm.depth_sq ? fm.depth_sq + slot : nullptr;
+    V3 a = v3(0.f, 0.f, 0.f), n = v3(0.f, 0.f, 0.f), a2 = v3(0.f, 0.f, 0.f), n2 = v3(0.f, 0.f, 0.f); float dep = 0.f, dep2 = 0.f; uint32_t nh = 0u;
+    if (fd.accumulate != 0u) {
+        if (pa) a = v3(pa[0], pa[1], pa[2]);
+        if (pn) n = v3(pn[0], pn[1], pn[2]);
+        if (pd) dep = *pd;
+        if (ph) nh = *ph;
+        if (qa) a2 = v3(qa[0], qa[1], qa[2]);
+        if (qn) n2 = v3(qn[0], qn[1], qn[2]);
+        if (qd) dep2 = *qd;
+    }
+    for (uint32_t k = 0; k < fd.nk; ++k) {
+        const Float4* rec = fd.rec + 2ull * ((uint64_t)k * fd.ns + s);
+        const Float4 r0 = rec[0], r1 = rec[1];
+        a = a + v3(r0.x, r0.y, r0.z); n = n + v3(r1.x, r1.y, r1.z); dep += r0.w; nh += __float_as_uint(r1.w);
+        a2 = a2 + v3(r0.x * r0.x, r0.y * r0.y, r0.z * r0.z); n2 = n2 + v3(r1.x * r1.x, r1.y * r1.y, r1.z * r1.z); dep2 += r0.w * r0.w;
+    }
+    if (pa) { pa[0] = a.x; pa[1] = a.y; pa[2] = a.z; }
+    if (pn) { pn[0] = n.x; pn[1] = n.y; pn[2] = n.z; }
+    if (pd) *pd = dep;
+    if (ph) *ph = nh;
+    if (qa) { qa[0] = a2.x; qa[1] = a2.y; qa[2] = a2.z; }
+    if (qn) { qn[0] = n2.x; qn[1] = n2.y; qn[2] = n2.z; }
+    if (qd) *qd = dep2;
+}
+
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
@@ -2613,6 +2654,13 @@ hipError_t launch_features_fold(const RenderDev& rd, const FeatDev& fd, hipStrea
     const uint32_t blocks = (fd.ns + 255u) / 256u;
     if (blocks == 0u) return hipSuccess;
     hipLaunchKernelGGL(k_features_fold, dim3(blocks), dim3(256), 0, stream, rd, fd);
+    return hipGetLastError();
+}
+
+hipError_t launch_features_fold_moments(const RenderDev& rd, const FeatDev& fd, const FeatMomDev& fm, hipStream_t stream) {
+    const uint32_t blocks = (fd.ns + 255u) / 256u;
+    if (blocks == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_features_fold_moments, dim3(blocks), dim3(256), 0, stream, rd, fd, fm);
     return hipGetLastError();
 }
 

@@ -1218,7 +1218,8 @@ int rt_features_check(const RtParams* params, const RtFeatureOptions* options) {
 // export (one feature record per ray) -> fold (per-slot sums), all on the context's stream; the host waits once, at the end. A chunk holds
 // the whole sample run of as many slots as the pool has room for; only a pass with more samples per pixel than pool slots is cut along the
 // samples too, its later parts folding on from the planes — the same additions in the same order, so the cut does not show.
-static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* opt, const RtFeatureBuffers* out, RtStats* stats) {
+static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* opt, const RtFeatureBuffers* out, RtStats* stats,
+                         const rtk::FeatMomDev* moments = nullptr) {      // moments: the squared-sum planes of rt_render_feature_moments_device; the fold is then k_features_fold_moments
     using clk = std::chrono::steady_clock;
     const auto t_begin = clk::now();
     const bool timing = (prm->flags & RT_FLAG_TIMING) != 0u;
@@ -1307,7 +1308,8 @@ static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, 
             const uint32_t per_queue = std::min<uint32_t>(rd.queue_cap, ((n + 511u) / 512u + rtk::kQueues - 1u) / rtk::kQueues * 512u);
             LAUNCH_TRY(rtk::launch_features_export(cfg, scene->dev, rd, fd, pd, per_queue, c_count, ctx->stream));
             if (timing) HIP_TRY(ctx, next_event(ed));
-            LAUNCH_TRY(rtk::launch_features_fold(rd, fd, ctx->stream));
+            if (moments) LAUNCH_TRY(rtk::launch_features_fold_moments(rd, fd, *moments, ctx->stream));
+            else LAUNCH_TRY(rtk::launch_features_fold(rd, fd, ctx->stream));
             if (timing) { HIP_TRY(ctx, next_event(ee)); spans.push_back({ea, eb, 1}); spans.push_back({eb, ec, 0}); spans.push_back({ec, ed, 2}); spans.push_back({ed, ee, 3}); }
             ++launched;
         }
@@ -1341,6 +1343,38 @@ int rt_render_features_device(RtCtx* ctx, const RtScene* scene, const RtCamera* 
     if (stats) std::memset(stats, 0, sizeof(*stats));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int r = features_impl(ctx, scene, cam, prm, options, buffers, stats);
+    if (r != RT_OK) { const std::string keep = ctx->err; (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); ctx->err = keep; g_last_error = keep; }
+    return r;
+}
+
+// ---- first-hit features, second moments (include/rt_hip.h): the same pass, with the per-slot sums of squares beside the sums ---------------
+static_assert(sizeof(RtFeatureMomentBuffers) == 8 * sizeof(void*), "feature moment buffers: struct_bytes (padded) and seven pointers");
+int rt_feature_moments_check(const RtParams* params, const RtFeatureOptions* options, const RtFeatureMomentBuffers* buffers) {
+    const int v = check_features(nullptr, params, options); if (v != RT_OK) return v;
+    if (!buffers) return set_err(nullptr, RT_ERR_INVALID, "feature moment buffers are null");
+    if (buffers->struct_bytes < sizeof(RtFeatureMomentBuffers) || buffers->struct_bytes > 4096u) return set_err(nullptr, RT_ERR_INVALID, "RtFeatureMomentBuffers.struct_bytes is not set (sizeof(RtFeatureMomentBuffers))");
+    return RT_OK;
+}
+
+int rt_render_feature_moments_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* options,
+                                     const RtFeatureMomentBuffers* b, RtStats* stats) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    if (!scene || !cam) return set_err(ctx, RT_ERR_INVALID, "scene / cam is null");
+    const int v = check_features(ctx, prm, options); if (v != RT_OK) return v;
+    if (scene->features & rtk::F_MEDIUM)
+        return set_err(ctx, RT_ERR_UNSUPPORTED, "first-hit features: the scene holds a ConstantMedium (the limit of ray queries: its hit is a draw of the path's medium stream)");
+    if (!b) return set_err(ctx, RT_ERR_INVALID, "feature moment buffers are null");
+    if (b->struct_bytes < sizeof(RtFeatureMomentBuffers) || b->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtFeatureMomentBuffers.struct_bytes is not set (sizeof(RtFeatureMomentBuffers))");
+    if (!b->albedo_sum && !b->normal_sum && !b->depth_sum && !b->hits && !b->albedo_sq_sum && !b->normal_sq_sum && !b->depth_sq_sum)
+        return set_err(ctx, RT_ERR_INVALID, "no feature buffer is wanted (all seven pointers are null)");
+    if (((uintptr_t)b->albedo_sum | (uintptr_t)b->normal_sum | (uintptr_t)b->depth_sum | (uintptr_t)b->hits | (uintptr_t)b->albedo_sq_sum | (uintptr_t)b->normal_sq_sum |
+         (uintptr_t)b->depth_sq_sum) & 15u)
+        return set_err(ctx, RT_ERR_INVALID, "feature buffers must be 16-byte aligned");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const RtFeatureBuffers sums{b->albedo_sum, b->normal_sum, b->depth_sum, b->hits};
+    const rtk::FeatMomDev fm{(float*)b->albedo_sq_sum, (float*)b->normal_sq_sum, (float*)b->depth_sq_sum};
+    const int r = features_impl(ctx, scene, cam, prm, options, &sums, stats, &fm);
     if (r != RT_OK) { const std::string keep = ctx->err; (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); ctx->err = keep; g_last_error = keep; }
     return r;
 }

@@ -57,7 +57,8 @@ struct RtCtx {
     rti::OwnedDevBuf rays_tmp, hits_tmp;         // rt_trace_rays (host variant): the caller's rays and hits on their way to and from the device
     rti::OwnedDevBuf feature_rec;                // rt_render_features_device: the per-ray feature records of a chunk between export and fold (kernels.h FeatDev)
     rti::OwnedDevBuf denoise_planes;             // rt_denoise_device: per-pixel mean and variance of the mean, three float2 planes (denoise.hip)
-    rti::OwnedDevBuf denoise_guide;              // rt_denoise_guided_device: per pixel one 16-byte record of 8 binary16 guide components (denoise.hip)
+    rti::OwnedDevBuf denoise_guide;              // rt_denoise_guided_device: per pixel one 16-byte record of 8 binary16 guide components (denoise.hip);
+                                                 // rt_denoise_guided_moments_device: those, then per pixel one 8-byte record of the standard errors
     uint32_t fail_renders = 0;                   // rt_test_fail_next_renders: renders still to fail (fault injection for the failure-path tests)
 };
 

@@ -181,13 +181,18 @@ class Progressive:
         self.ctx.resolve_device(src.data_ptr(), p.width, p.height, self.samples_done, out.data_ptr())
         return out.cpu().numpy().reshape(p.height, p.width, 3)
 
-    def denoised(self, rgb8=False, feature_samples=0, sigma_albedo=0.0, sigma_normal=0.0, sigma_depth=0.0, **opts):
+    def denoised(self, rgb8=False, feature_samples=0, sigma_albedo=0.0, sigma_normal=0.0, sigma_depth=0.0, feature_variance=False, variance_strength=0.0, **opts):
         """The frame so far filtered by rt_denoise_device (non-local means over the sample variance; opts: denoise_options fields, the
         frame's samples per work item is filled in): the mean radiance, f32 (H, W, 3), or its write_color bytes with rgb8=True. A
         sharded frame is untiled first: the other shards' pixels hold no sums and come out as they are, 0.
         feature_samples = N > 0: a feature pass of N samples per pixel is rendered (Context.render_features) and the weights are joined
-        with it (rt_denoise_guided_device; the sigmas: RtDenoiseGuide, 0 = the default). 0: the plain filter."""
+        with it (rt_denoise_guided_device; the sigmas: RtDenoiseGuide, 0 = the default). 0: the plain filter.
+        feature_variance=True with feature_samples = N >= 2: the pass keeps the features' second moments (Context.render_feature_moments)
+        and the filter is rt_denoise_guided_moments_device (sigmas and variance_strength: RtDenoiseGuideMoments, 0 = the default;
+        window_radius 0 = 8, at most 8)."""
         from .denoise import denoise_frame, render_guide
+        if feature_variance and int(feature_samples) < 2:
+            raise ValueError("feature_variance needs feature_samples >= 2")
         if self.samples_done == 0:
             raise ValueError("no samples rendered yet")
         if self._sq is None:
@@ -195,7 +200,8 @@ class Progressive:
         import torch
         p, dev = self.params, self._rgb.device
         if feature_samples:
-            opts["guide"] = render_guide(self.ctx, self.scene, self.cam, p, feature_samples, sigma_albedo, sigma_normal, sigma_depth)
+            opts["guide"] = render_guide(self.ctx, self.scene, self.cam, p, feature_samples, sigma_albedo, sigma_normal, sigma_depth, moments=bool(feature_variance),
+                                         variance_strength=variance_strength)
         if p.shard_count <= 1:
             return denoise_frame(self.ctx, self._rgb, self._sq, p.width, p.height, self.samples_per_item, samples=self.samples_done, rgb8=rgb8, **opts)
         from .adaptive import slot_pixels
