@@ -275,6 +275,11 @@ extern "C" {
                                 hits_device: *mut c_void, stats: *mut RtStats) -> c_int;
     pub fn rt_trace_rays(ctx: *mut RtCtx, scene: *const RtScene, options: *const RtRayQueryOptions, rays_host: *const RtRay, n_rays: u64,
                          hits_host: *mut RtRayHit, stats: *mut RtStats) -> c_int;
+    /// occlusion: one byte per ray (RT_RAYHIT_HIT when anything is hit in [0.001, t_max], RT_RAYHIT_INVALID_RAY for a ray never traced)
+    pub fn rt_occluded_rays_device(ctx: *mut RtCtx, scene: *const RtScene, options: *const RtRayQueryOptions, rays_device: *const c_void, n_rays: u64,
+                                   occluded_device: *mut c_void, stats: *mut RtStats) -> c_int;
+    pub fn rt_occluded_rays(ctx: *mut RtCtx, scene: *const RtScene, options: *const RtRayQueryOptions, rays_host: *const RtRay, n_rays: u64,
+                            occluded_host: *mut u8, stats: *mut RtStats) -> c_int;
     /// host only: validates a feature pass (params, options)
     pub fn rt_features_check(params: *const RtParams, options: *const RtFeatureOptions) -> c_int;
     /// first-hit feature sums of samples [first_sample, first_sample + samples_per_pixel) into the caller's device planes (null = not wanted)

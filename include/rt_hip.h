@@ -546,7 +546,7 @@ int rt_denoise_guided_moments_device(RtCtx* ctx, const RtDenoiseOptions* options
  *     about 1.1e-19) or overflows (|d| above about 1.8e19), for which the walk's 1 / |d|^2 would be inf or 0.
  *   - A scene that holds a ConstantMedium is RT_ERR_UNSUPPORTED and nothing is written: a medium's hit is a random draw keyed by (path,
  *     segment, medium) and a bare ray has no path. A deliberate limit. Every query ray starts on nothing (there is no "the primitive this
- *     ray leaves" input), there is no any-hit mode and no multi-GPU entry point.
+ *     ray leaves" input) and there is no multi-GPU entry point. "Is anything hit at all?" is rt_occluded_rays below.
  *   - Options: an unknown bit in flags (known: RT_FLAG_TIMING), struct_bytes < sizeof(RtRayQueryOptions) or n_rays >= 2^32 is
  *     RT_ERR_INVALID with the reason in rt_last_error, and nothing is written. n_rays == 0 is a no-op. pool_slots caps the rays in flight
  *     (0 = the renderer's rule: all of them, up to 2^28 and to 70 % of the free device memory); longer lists run in chunks.
@@ -570,6 +570,33 @@ int rt_trace_rays_device(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptio
                          void* hits_device, RtStats* stats);
 int rt_trace_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options /* NULL = defaults */, const RtRay* rays_host, uint64_t n_rays,
                   RtRayHit* hits_host, RtStats* stats);
+
+/* ---- occlusion queries: any-hit rays that stop at the first blocker -------------------------------------------------------------------------
+ *
+ * One byte per ray: occluded[i] is RT_RAYHIT_HIT (1) when some primitive of the scene is hit at a t with 0.001 <= t <= t_max, both ends
+ * inclusive as in the primitive tests, and 0 otherwise — shadow rays, ambient occlusion, line of sight, visibility baking. The answer:
+ * occluded[i] == RT_RAYHIT_HIT exactly when rt_trace_rays on the same scene and layout reports a hit for ray i. What it saves is work:
+ * the walk starts with the ray's own t_max as its interval, so boxes beyond the target are culled from the first node on; it stops at
+ * the first primitive it accepts; and no HitRecord is rebuilt or written.
+ *   - The rays are the RtRay records of rt_trace_rays (32 bytes; 16-byte aligned in device memory for the *_device variant); the output is
+ *     n_rays bytes and needs no alignment. t_max <= 0, +inf or NaN means no limit; t_min stays the renderer's 0.001.
+ *   - An INVALID ray — the rule is rt_trace_rays' own: a non-finite origin, direction or time, or |d|^2 not a positive normal f32 — is never
+ *     traced and gets RT_RAYHIT_INVALID_RAY (4). No other bit is ever set.
+ *   - RtRayQueryOptions is read as rt_trace_rays reads it and rt_ray_query_check validates it: an unknown bit in flags (known:
+ *     RT_FLAG_TIMING), a short struct_bytes, n_rays >= 2^32, or a NULL rays or output pointer with n_rays > 0 is RT_ERR_INVALID with the
+ *     reason in rt_last_error, and nothing is written. n_rays == 0 is a no-op. pool_slots and chunking follow rt_trace_rays' pool rule.
+ *   - A scene that holds a ConstantMedium is RT_ERR_UNSUPPORTED and nothing is written: the limit of rt_trace_rays, for its reason. Every
+ *     query ray starts on nothing; there is no multi-GPU entry point.
+ *   - Every RT_LAYOUT_* answers. A scene uploaded with RT_LAYOUT_WIDE_NODES is answered through its closest-hit 8-wide walk: the same
+ *     bytes, without the early exit (that walk is the measured-slower option and has no any-hit version).
+ *   - Determinism: occluded[i] is a function of (scene, layout, ray i) alone — not of the chunk size, of the ray's place in the list, or of
+ *     the host / device variant — and the same call gives the same bytes every time.
+ *   - RtStats: samples = segments = n_rays minus the invalid ones; render_ms; with RT_FLAG_TIMING also extend_ms (the traversal kernels)
+ *     and other_ms (the two kernels that read the rays and write the bytes). Both variants block until done. */
+int rt_occluded_rays_device(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options /* NULL = defaults */, const void* rays_device, uint64_t n_rays,
+                            void* occluded_device /* n_rays bytes */, RtStats* stats);
+int rt_occluded_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options /* NULL = defaults */, const RtRay* rays_host, uint64_t n_rays,
+                     uint8_t* occluded_host, RtStats* stats);
 
 /* ---- first-hit features: albedo, normal and depth of the render's own camera rays ----------------------------------------------------------
  *

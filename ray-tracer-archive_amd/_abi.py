@@ -174,7 +174,7 @@ RT_HIP_SYMBOLS = ["rt_ctx_create", "rt_ctx_destroy", "rt_scene_upload", "rt_scen
                   "rt_pass_check", "rt_render_pass", "rt_render_pass_device",
                   "rt_adaptive_check", "rt_adaptive_select", "rt_render_pass_pixels_device", "rt_resolve_counts_device",
                   "rt_denoise_check", "rt_denoise_device", "rt_denoise_guided_check", "rt_denoise_guided_device",
-                  "rt_ray_query_check", "rt_trace_rays_device", "rt_trace_rays",
+                  "rt_ray_query_check", "rt_trace_rays_device", "rt_trace_rays", "rt_occluded_rays_device", "rt_occluded_rays",
                   "rt_features_check", "rt_render_features_device",
                   "rt_feature_moments_check", "rt_render_feature_moments_device", "rt_denoise_guided_moments_check", "rt_denoise_guided_moments_device"]
 RT_HOST_SYMBOLS = ["rt_host_scene_create", "rt_host_scene_desc", "rt_host_scene_camera", "rt_host_scene_destroy", "rt_host_camera_new",
@@ -241,6 +241,10 @@ def declare(lib):
     lib.rt_trace_rays_device.argtypes = [vp, vp, P(RtRayQueryOptions), vp, u64, vp, P(RtStats)]
     lib.rt_trace_rays.restype = i32
     lib.rt_trace_rays.argtypes = [vp, vp, P(RtRayQueryOptions), vp, u64, vp, P(RtStats)]
+    lib.rt_occluded_rays_device.restype = i32
+    lib.rt_occluded_rays_device.argtypes = [vp, vp, P(RtRayQueryOptions), vp, u64, vp, P(RtStats)]
+    lib.rt_occluded_rays.restype = i32
+    lib.rt_occluded_rays.argtypes = [vp, vp, P(RtRayQueryOptions), vp, u64, vp, P(RtStats)]
     lib.rt_features_check.restype = i32
     lib.rt_features_check.argtypes = [P(RtParams), P(RtFeatureOptions)]
     lib.rt_render_features_device.restype = i32

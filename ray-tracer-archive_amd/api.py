@@ -487,6 +487,45 @@ class Context:
                                    C.byref(st)), self._h)
         return (out, st.as_dict()) if with_stats else out
 
+    def occluded(self, scene, rays, options=None, out=None, with_stats=False):
+        """rt_occluded_rays / rt_occluded_rays_device: one byte per ray — RT_RAYHIT_HIT (1) when anything is hit in [0.001, t_max], else 0;
+        RT_RAYHIT_INVALID_RAY (4) for a ray that is never traced. Exactly the hit / miss of trace_rays, for less work.
+
+        `rays` as for trace_rays: a numpy array of RAY_DTYPE or float32 of shape (n, 8) (host variant, returns a uint8 numpy array of length
+        n), or a contiguous float32 CUDA tensor of shape (n, 8) (device variant, returns a uint8 CUDA tensor of length n). `out` receives
+        the bytes when given (same kind, n elements); a refused call raises RtError and leaves it untouched. with_stats: also the stats."""
+        st = A.RtStats()
+        opt = C.byref(options) if options is not None else None
+        if hasattr(rays, "data_ptr"):
+            import torch
+            if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
+                raise ValueError("device rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
+            n = rays.shape[0]
+            if out is None:
+                out = torch.empty((n,), dtype=torch.uint8, device=rays.device)
+            if not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != n:
+                raise ValueError("out must be a contiguous uint8 CUDA tensor of n elements")
+            if rays.device.index != self.device_id or out.device != rays.device:
+                raise ValueError(f"rays and out must live on this context's device (cuda:{self.device_id})")
+            torch.cuda.synchronize(rays.device)           # the library's stream is not torch's
+            _check(lib().rt_occluded_rays_device(self._h, scene._h, opt, C.c_void_p(rays.data_ptr() if n else None), n, C.c_void_p(out.data_ptr() if n else None),
+                                                 C.byref(st)), self._h)
+            return (out, st.as_dict()) if with_stats else out
+        rays = np.asarray(rays)
+        if rays.dtype != RAY_DTYPE:
+            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+                raise ValueError("host rays must be a numpy array of RAY_DTYPE, or float32 of shape (n, 8)")
+            rays = np.ascontiguousarray(rays).view(RAY_DTYPE).reshape(-1)
+        rays = np.ascontiguousarray(rays).reshape(-1)
+        n = rays.shape[0]
+        if out is None:
+            out = np.empty(n, dtype=np.uint8)
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or out.size != n:
+            raise ValueError("out must be a C-contiguous numpy array of n uint8")
+        _check(lib().rt_occluded_rays(self._h, scene._h, opt, C.c_void_p(rays.ctypes.data if n else None), n, C.c_void_p(out.ctypes.data if n else None),
+                                      C.byref(st)), self._h)
+        return (out, st.as_dict()) if with_stats else out
+
     # ---- first-hit features (include/rt_hip.h, "first-hit features"): device tensors only ----
     def render_features(self, scene, cam, params, first_sample=0, accumulate=False, albedo=None, normal=None, depth=None, hits=None, pool_slots=0,
                         with_stats=False):

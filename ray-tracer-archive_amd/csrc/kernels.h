@@ -188,6 +188,15 @@ hipError_t launch_rays_import(const void* rays, uint32_t first, uint32_t n, cons
 // after launch_extend: one RtRayHit per pool slot, at its ray's index (max_count: upper bound of the rays in one queue)
 hipError_t launch_rays_export(const LaunchCfg& cfg, const SceneDev& sc, const RaySrcDev& src, const PoolDev& pool, uint32_t queue_cap, uint32_t max_count,
                               const uint32_t* counts, void* hits, hipStream_t stream);
+// occlusion queries (kernels.hip "occlusion queries"): the import writes RT_RAYHIT_INVALID_RAY into the byte of a dropped ray; limit_in_d =
+// !extend_any_is_closest(scene): the record carries the ray's limit where the any-hit walk reads it. launch_extend_any: the any-hit k_extend, or
+// the closest-hit k_extend_wide for a scene uploaded with the 8-wide tree; the export writes 0 / RT_RAYHIT_HIT at every stored ray's index.
+bool extend_any_is_closest(const SceneDev& sc);
+hipError_t launch_occluded_import(const void* rays, uint32_t first, uint32_t n, const PoolDev& pool, uint32_t queue_cap, uint32_t* counts, void* occluded,
+                                  unsigned long long* counters, bool limit_in_d, hipStream_t stream);
+hipError_t launch_extend_any(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
+                             uint32_t* head, uint32_t* count_out_to_zero, unsigned long long* counters, hipStream_t stream);
+hipError_t launch_occluded_export(const PoolDev& pool, uint32_t queue_cap, uint32_t max_count, const uint32_t* counts, void* occluded, hipStream_t stream);
 // first-hit features (kernels.hip "first-hit features"). FeatDev: one chunk of a feature pass — samples [k0, k0 + nk) of the pass, of output
 // slots [slot0, slot0 + ns) — and where its results go; its own block, like RaySrcDev. Ray r = k * ns + s of the chunk is sample
 // first_sample + k0 + k of slot slot0 + s; its 32-byte record is rec[2 r], rec[2 r + 1].

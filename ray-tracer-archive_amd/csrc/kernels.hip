@@ -613,10 +613,18 @@ __host__ DEVI uint32_t lds_record_bytes(const SceneDev& sc) { return sc.n_record
 // TPB: the group size, used as the launch bound only (the body reads blockDim.x). The wavefront form of the LDS-staged modes is compiled for
 // 256, 512 and 1024 threads (launch_extend_c); the bound moves the register allocation and the schedule of the F_ALL and the Cornell
 // variant, so the copies are different programs and stay ("Kernel instances").
-template <int MODE, uint32_t FEAT, bool COUNT, uint32_t TPB, bool DRAIN, bool LIST>
+//
+// ANYHIT: the occlusion walk of a ray query (rt_hip.h rt_occluded_rays): "is anything hit in [t_min, t_max]?". Three differences, all
+// `if constexpr`, so that every ANYHIT = false instance is the program it was: (1) a walk begins with the ray's own limit as t_max — the
+// record's ray_d.w carries it (k_occluded_import; such a ray starts on nothing, so `from` is 0) — and boxes beyond the target are culled
+// from the first node on; (2) a lane that holds a hit after the prologue or after a primitive pass stores it and retires at once, also
+// inside a Translate / RotateY instance: no record is rebuilt, so nothing has to be switched back; (3) nothing else: pool.hit gets the
+// same (t, primitive) pair, of which k_occluded_export reads "is there one". Queries only: no counters, no drain, no pixel list.
+template <int MODE, uint32_t FEAT, bool COUNT, uint32_t TPB, bool DRAIN, bool LIST, bool ANYHIT = false>
 __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const uint32_t* __restrict__ count_ptr,
                                                  uint32_t* __restrict__ head, uint32_t* __restrict__ count_out_to_zero,
                                                  unsigned long long* __restrict__ counters, RenderDev rd) {
+    static_assert(!ANYHIT || (!COUNT && !DRAIN && !LIST && (FEAT & F_MEDIUM) == 0u), "the any-hit walk serves ray queries: no counters, drain, list or media");
     extern __shared__ float4 lds[];
     constexpr bool LDS = MODE == M_LDS, TOP = MODE == M_TOP, C16 = MODE == M_C16;
     constexpr int kSteps = FEAT == F_ALL ? kStepsAll : kStepsPlain;
@@ -849,6 +857,7 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
                     slot = w_next + rank;
                     o = v3(ox, oy, oz); d = v3(dx, dy, dz); tm = ot;
                     from = __float_as_uint(dfrom);            // primitive this ray starts on (0: camera / medium)
+                    if constexpr (ANYHIT) from = 0u;          // (the slot holds the ray's limit instead)
                     if (C16) set_grid_ray(); else set_slab_ray(o, d, sr);
                     a = len2(d);
                     if (FEAT & F_XFORM) { ow = o; dw = d; }
@@ -861,6 +870,12 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
                         const uint32_t smp = pool.s1 != nullptr ? __float_as_uint(pool.s1[qbase + slot].w) : rd.first_sample + (item - pixel * rd.n_blocks);
                         mkey = path_base(rd.seed, (uint64_t)pixel, smp);
                     }
+                    if constexpr (ANYHIT) {
+                        // the interval is the ray's own (k_occluded_import: +inf for "no limit"); a prologue member that is hit ends the walk
+                        tmax = dfrom; hit_prim = rtd::HIT_NONE; go_root();
+                        prologue();
+                        if (hit_prim != rtd::HIT_NONE) { pool.hit[qbase + slot] = make_uint2(__float_as_uint(tmax), hit_prim); go_idle(); }
+                    } else
                     if (rd.first_in_shade != 0u) {
                         // the sphere every walk tests first was tested where this ray was made: its t came in the record's time slot
                         tmax = ot; tm = 0.f; hit_prim = ot < kInf ? rd.first_id : rtd::HIT_NONE;
@@ -1077,6 +1092,10 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
                 if (COUNT) c_prims[4]++;
                 const V3 mo = (FEAT & F_XFORM) ? ow : o, md = (FEAT & F_XFORM) ? dw : d;
                 if (medium_hit(sc, m, mo, md, kTMin, tmax, xi, t)) { tmax = t; hit_prim = (rtd::LT_MEDIUM << 28) | first; }
+            }
+            if constexpr (ANYHIT) {
+                // the first primitive accepted answers the query: store it and take the next ray
+                if (hit_prim != rtd::HIT_NONE) { pool.hit[qbase + slot] = make_uint2(__float_as_uint(tmax), hit_prim); go_idle(); }
             }
         }
 #ifdef RT_STAMPS
@@ -2213,6 +2232,50 @@ __global__ void __launch_bounds__(256) k_rays_export(SceneDev sc, RaySrcDev src,
     hits[2] = Float4{n.x, n.y, n.z, hv};
 }
 
+// ---- occlusion queries (rt_hip.h rt_occluded_rays): the same rays -> pool records -> the any-hit k_extend -> one byte per ray ----
+// k_occluded_import: k_rays_import's twin (same validity rule, same slots, same counter) with two differences: a dropped ray gets its BYTE,
+// RT_RAYHIT_INVALID_RAY, and with limit_in_d the record's ray_d.w — "the primitive this ray starts on", 0 for every query ray — carries
+// the ray's limit as the any-hit walk wants it (+inf for t_max <= 0, +inf or NaN), so that the walk's refill finds it in the words it
+// prefetches anyway. Without limit_in_d (scenes walked by k_extend_wide, closest hit) the slot stays 0. s0.x keeps the caller's t_max.
+__global__ void __launch_bounds__(kRaysImportThreads) k_occluded_import(const Float4* __restrict__ rays, uint32_t first, uint32_t n, PoolDev pool, uint32_t queue_cap,
+                                                                         uint32_t* __restrict__ counts, uint8_t* __restrict__ occluded,
+                                                                         unsigned long long* __restrict__ counters, uint32_t limit_in_d) {
+    __shared__ uint32_t s_scan[kRaysImportThreads / 64 + 1];
+    const uint32_t i = blockIdx.x * kRaysImportThreads + threadIdx.x, q = blockIdx.x & (kQueues - 1u);
+    Float4 ro = Float4{0.f, 0.f, 0.f, 0.f}, rdv = Float4{0.f, 0.f, 0.f, 0.f};
+    const bool mine = i < n;
+    if (mine) { const Float4* r = rays + 2ull * (first + i); ro = r[0]; rdv = r[1]; }
+    const bool valid = mine && query_ray_valid(ro, rdv);
+    const uint32_t slot = block_alloc(valid, counts + q * kQStride, s_scan);      // every thread of the workgroup calls it
+    const bool stored = valid && slot < queue_cap;
+    if (stored) {
+        const uint32_t at = q * queue_cap + slot;
+        const float limit = (rdv.w > 0.f && rdv.w < kInf) ? rdv.w : kInf;         // (NaN fails both comparisons: no limit)
+        pool.ray_o[at] = ro;
+        pool.ray_d[at] = Float4{rdv.x, rdv.y, rdv.z, limit_in_d != 0u ? limit : __uint_as_float(0u)};
+        pool.s0[at] = Float4{rdv.w, 0.f, 0.f, __uint_as_float(first + i)};
+        pool.sd[at] = 0u;
+    }
+    if (mine && !stored) occluded[(uint64_t)first + i] = (uint8_t)kRayHitInvalid;
+    const uint64_t m = __ballot(stored);
+    if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(&counters[CTR_SEGMENTS], (unsigned long long)__popcll(m));
+}
+
+// k_occluded_export: pool.hit of every slot -> the byte at its ray's index, by k_rays_export's own rule for "a hit": a primitive, and a t
+// not beyond the ray's limit. After the any-hit walk the second half always holds (the walk accepted nothing beyond the limit); after
+// k_extend_wide it is the comparison k_rays_export makes. No FEAT variants: nothing of the HitRecord is rebuilt.
+__global__ void __launch_bounds__(256) k_occluded_export(PoolDev pool, uint32_t queue_cap, const uint32_t* __restrict__ counts, uint8_t* __restrict__ occluded) {
+    const uint32_t q = blockIdx.x & (kQueues - 1u), i = (blockIdx.x >> kQShift) * blockDim.x + threadIdx.x;
+    if (i >= min(counts[q * kQStride], queue_cap)) return;
+    const uint32_t at = q * queue_cap + i;
+    const Float4 s0 = pool.s0[at];
+    const uint2 hit = pool.hit[at];
+    const float t = __uint_as_float(hit.x), t_max = s0.x;
+    const bool limited = t_max > 0.f && t_max < kInf;                             // (t_max <= 0, +inf or NaN: no limit)
+    const bool miss = hit.y == rtd::HIT_NONE || (limited && t > t_max);
+    occluded[__float_as_uint(s0.w)] = miss ? (uint8_t)0u : (uint8_t)kRayHitHit;
+}
+
 // ------------------------------------------------------------------------------------------------
 // first-hit features (rt_hip.h "first-hit features"): the render's own camera rays -> pool records -> k_extend -> per-ray feature
 // records -> per-pixel sums
@@ -2505,42 +2568,49 @@ static hipError_t launch_drain_c(const SceneDev& sc, const PoolDev& pool, const 
 // Persistent grid of k_extend = what is resident at once. Registers and the LDS copy of the scene both
 // limit it; a scene whose LDS copy is large (book-2 final: 65 KB; the 64 KB top of a tree that does not fit) allows two workgroups
 // per CU, and then larger workgroups keep more waves. The runtime's occupancy query decides between the sizes compiled per mode.
-template <int MODE, uint32_t FEAT, bool COUNT>
-static hipError_t launch_extend_c(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
-                                  uint32_t* head, uint32_t* cz, unsigned long long* counters, hipStream_t stream) {
-    const size_t lds_bytes = staged_bytes<MODE>(sc);
-    constexpr bool kNoLds = MODE == M_HBM || MODE == M_C16;
-    // workgroup sizes compiled for this mode: 256 threads always; 512 and 1024 where an LDS copy limits the groups per CU (a
+// (shared with the any-hit walk, launch_extend_any_c: `kernels` are the programs for 256, 512 and 1024 threads — three copies, or one
+// program compiled for the largest group; `g` is the caller's cache of the choice, one per template instance and thread)
+struct GroupPick { size_t cached_lds = ~(size_t)0; int nb[3] = {0, 0, 0}; int pick = 0; };
+template <class K>
+static hipError_t launch_extend_sized(GroupPick& g, const K (&kernels)[3], bool no_lds, size_t lds_bytes, const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool,
+                                      const RenderDev& rd, const uint32_t* count_ptr, uint32_t* head, uint32_t* cz, unsigned long long* counters, hipStream_t stream) {
+    // workgroup sizes for this mode: 256 threads always; 512 and 1024 where an LDS copy limits the groups per CU (a
     // 100 KB scene allows ONE group per CU: only a 1024-thread group then keeps 16 waves on it)
-    constexpr uint32_t T0 = kExtendThreads, T1 = kNoLds ? T0 : 2u * T0, T2 = kNoLds ? T0 : 4u * T0;
-    const uint32_t sizes[3] = {T0, T1, T2};
-    const auto k0 = k_extend<MODE, FEAT, COUNT, T0, false, false>;
-    const decltype(k0) kernels[3] = {k0, k_extend<MODE, FEAT, COUNT, T1, false, false>, k_extend<MODE, FEAT, COUNT, T2, false, false>};
-    static thread_local size_t cached_lds = ~(size_t)0; static thread_local int nb[3] = {0, 0, 0}; static thread_local int pick = 0;
-    if (cached_lds != lds_bytes) {
-        nb[1] = nb[2] = 0;
-        for (int k = 0; k < (kNoLds ? 1 : 3); ++k) {
+    const uint32_t T0 = kExtendThreads, sizes[3] = {T0, no_lds ? T0 : 2u * T0, no_lds ? T0 : 4u * T0};
+    if (g.cached_lds != lds_bytes) {
+        g.nb[1] = g.nb[2] = 0;
+        for (int k = 0; k < (no_lds ? 1 : 3); ++k) {
             hipError_t e = check_no_static_lds(kernels[k]);
-            if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[k], kernels[k], (int)sizes[k], lds_bytes);
+            if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&g.nb[k], kernels[k], (int)sizes[k], lds_bytes);
             if (e != hipSuccess) return e;
         }
         // most resident waves wins; ties go to the smaller group (its waves leave the staging barrier sooner)
-        pick = 0;
-        if (2 * nb[1] > nb[0]) pick = 1;
-        if (4 * nb[2] > std::max(nb[0], 2 * nb[1])) pick = 2;
-        if (nb[pick] < 1) { if (lds_bytes > 160u * 1024u) return hipErrorInvalidValue; nb[pick] = 1; }
-        cached_lds = lds_bytes;
+        g.pick = 0;
+        if (2 * g.nb[1] > g.nb[0]) g.pick = 1;
+        if (4 * g.nb[2] > std::max(g.nb[0], 2 * g.nb[1])) g.pick = 2;
+        if (g.nb[g.pick] < 1) { if (lds_bytes > 160u * 1024u) return hipErrorInvalidValue; g.nb[g.pick] = 1; }
+        g.cached_lds = lds_bytes;
     }
-    const uint32_t tpb = sizes[pick];
-    if (cfg.extend_geometry) { cfg.extend_geometry[0] = tpb; cfg.extend_geometry[1] = (uint32_t)nb[pick]; }
+    const uint32_t tpb = sizes[g.pick];
+    if (cfg.extend_geometry) { cfg.extend_geometry[0] = tpb; cfg.extend_geometry[1] = (uint32_t)g.nb[g.pick]; }
     // the resident set, or fewer workgroups when the queue is short (the host's upper bound of it): a wave needs 64 rays to be worth
     // starting, and every workgroup started stages the scene and reads the queue size — the floor of the launches of a render's tail
-    const uint32_t per_cu = std::max<uint32_t>(1u, (uint32_t)nb[pick]);
+    const uint32_t per_cu = std::max<uint32_t>(1u, (uint32_t)g.nb[g.pick]);
     uint32_t groups = std::min<uint32_t>(cfg.n_cu * per_cu, std::max<uint32_t>(1u, (cfg.max_rays + tpb - 1u) / tpb));
     const uint32_t gq = std::max<uint32_t>(1u, rd.q_n * 64u / tpb);     // workgroups that make up q_n waves: every queue gets the same number of waves
     groups = (groups + gq - 1u) / gq * gq;
-    hipLaunchKernelGGL(kernels[pick], dim3(groups), dim3(tpb), lds_bytes, stream, sc, pool, count_ptr, head, cz, counters, rd);
+    hipLaunchKernelGGL(kernels[g.pick], dim3(groups), dim3(tpb), lds_bytes, stream, sc, pool, count_ptr, head, cz, counters, rd);
     return hipGetLastError();
+}
+template <int MODE, uint32_t FEAT, bool COUNT>
+static hipError_t launch_extend_c(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
+                                  uint32_t* head, uint32_t* cz, unsigned long long* counters, hipStream_t stream) {
+    constexpr bool kNoLds = MODE == M_HBM || MODE == M_C16;
+    constexpr uint32_t T0 = kExtendThreads, T1 = kNoLds ? T0 : 2u * T0, T2 = kNoLds ? T0 : 4u * T0;
+    const auto k0 = k_extend<MODE, FEAT, COUNT, T0, false, false>;
+    const decltype(k0) kernels[3] = {k0, k_extend<MODE, FEAT, COUNT, T1, false, false>, k_extend<MODE, FEAT, COUNT, T2, false, false>};
+    static thread_local GroupPick g;
+    return launch_extend_sized(g, kernels, kNoLds, staged_bytes<MODE>(sc), cfg, sc, pool, rd, count_ptr, head, cz, counters, stream);
 }
 
 // the 8-lanes-per-ray walk: a persistent grid of 256-thread groups, every wave holding 8 rays at a time
@@ -2629,6 +2699,50 @@ hipError_t launch_rays_export(const LaunchCfg& cfg, const SceneDev& sc, const Ra
     if (blocks == 0u) return hipSuccess;
     with_variant(cfg.features, [&](auto feat) {
         hipLaunchKernelGGL((k_rays_export<decltype(feat)::value>), dim3(blocks), dim3(256), 0, stream, sc, src, pool, queue_cap, counts, (Float4*)hits); });
+    return hipGetLastError();
+}
+
+// The any-hit walk: ONE instance per (mode, variant), compiled for the largest group its mode may need (the bound only caps the registers at
+// 128, which every ANYHIT instance is below: DESIGN.md section 11); the occupancy query picks the launched size among 256, 512 and 1024
+// as launch_extend_c does among its three instances (launch_extend_sized serves both).
+constexpr uint32_t kVariantAnyAll = F_ALL & ~F_MEDIUM;
+template <int MODE, uint32_t FEAT>
+static hipError_t launch_extend_any_c(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
+                                      uint32_t* head, uint32_t* cz, unsigned long long* counters, hipStream_t stream) {
+    constexpr bool kNoLds = MODE == M_HBM || MODE == M_C16;
+    const auto k = k_extend<MODE, FEAT, false, kNoLds ? kExtendThreads : 4u * kExtendThreads, false, false, true>;
+    const decltype(k) kernels[3] = {k, k, k};
+    static thread_local GroupPick g;
+    return launch_extend_sized(g, kernels, kNoLds, staged_bytes<MODE>(sc), cfg, sc, pool, rd, count_ptr, head, cz, counters, stream);
+}
+
+bool extend_any_is_closest(const SceneDev& sc) { return sc.wide != nullptr; }
+
+hipError_t launch_extend_any(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
+                             uint32_t* head, uint32_t* cz, unsigned long long* counters, hipStream_t stream) {
+    if (cfg.max_rays == 0u) return hipSuccess;
+    if (cfg.features & F_MEDIUM) return hipErrorInvalidValue;            // (the host refuses such scenes before anything is launched)
+    // a scene uploaded with the 8-wide tree is answered by its closest-hit walk: same answer, no early exit
+    if (extend_any_is_closest(sc)) return launch_extend(cfg, sc, pool, rd, count_ptr, head, cz, counters, false, stream);
+    return with_mode(cfg, sc, [&](auto mode) { return with_variant(cfg.features, [&](auto feat) {
+        constexpr uint32_t F = decltype(feat)::value == F_ALL ? kVariantAnyAll : decltype(feat)::value;
+        return launch_extend_any_c<decltype(mode)::value, F>(cfg, sc, pool, rd, count_ptr, head, cz, counters, stream); }); });
+}
+
+hipError_t launch_occluded_import(const void* rays, uint32_t first, uint32_t n, const PoolDev& pool, uint32_t queue_cap, uint32_t* counts, void* occluded,
+                                  unsigned long long* counters, bool limit_in_d, hipStream_t stream) {
+    const uint32_t blocks = (n + kRaysImportThreads - 1u) / kRaysImportThreads;
+    if (blocks == 0u) return hipSuccess;
+    if ((uint64_t)n > (uint64_t)kQueues * queue_cap || (queue_cap & 511u) != 0u) return hipErrorInvalidValue;   // (k_occluded_import: a slot is < queue_cap)
+    hipLaunchKernelGGL(k_occluded_import, dim3(blocks), dim3(kRaysImportThreads), 0, stream, (const Float4*)rays, first, n, pool, queue_cap, counts, (uint8_t*)occluded,
+                       counters, limit_in_d ? 1u : 0u);
+    return hipGetLastError();
+}
+
+hipError_t launch_occluded_export(const PoolDev& pool, uint32_t queue_cap, uint32_t max_count, const uint32_t* counts, void* occluded, hipStream_t stream) {
+    const uint32_t blocks = kQueues * ((std::min(max_count, queue_cap) + 255u) / 256u);   // max_count = upper bound of the rays in ONE queue
+    if (blocks == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_occluded_export, dim3(blocks), dim3(256), 0, stream, pool, queue_cap, counts, (uint8_t*)occluded);
     return hipGetLastError();
 }
 

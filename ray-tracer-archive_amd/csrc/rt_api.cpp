@@ -1078,7 +1078,10 @@ int rt_ray_query_check(const RtRayQueryOptions* options, uint64_t n_rays) { retu
 
 // The chunk loop: import -> k_extend (the scene's own launch configuration, every layout) -> export, all on the context's stream; the host
 // waits once, at the end. A chunk's kernels read its queue sizes from device memory, so nothing comes back to the host in between.
-static int trace_rays_impl(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* opt, const void* d_rays, uint64_t n_rays, void* d_hits, RtStats* stats) {
+// any_hit (rt_occluded_rays): the same loop with the occlusion kernels — its own import, the any-hit walk, the byte export; d_hits is then
+// the caller's n_rays bytes.
+static int trace_rays_impl(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* opt, const void* d_rays, uint64_t n_rays, void* d_hits, RtStats* stats,
+                           bool any_hit = false) {
     using clk = std::chrono::steady_clock;
     const auto t_begin = clk::now();
     const bool timing = opt && (opt->flags & RT_FLAG_TIMING) != 0u;
@@ -1134,14 +1137,17 @@ static int trace_rays_impl(RtCtx* ctx, const RtScene* scene, const RtRayQueryOpt
         hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr, ed = nullptr;
         if (first != 0u) HIP_TRY(ctx, hipMemsetAsync(cbase, 0, 4 * kQ * kLine, ctx->stream));     // heads and sizes of the chunk before (the 64-bit statistics stay)
         if (timing) HIP_TRY(ctx, next_event(ea));
-        LAUNCH_TRY(rtk::launch_rays_import(d_rays, (uint32_t)first, n, pd, queue_cap, c_count, d_hits, c64, ctx->stream));
+        if (any_hit) LAUNCH_TRY(rtk::launch_occluded_import(d_rays, (uint32_t)first, n, pd, queue_cap, c_count, d_hits, c64, !rtk::extend_any_is_closest(scene->dev), ctx->stream));
+        else LAUNCH_TRY(rtk::launch_rays_import(d_rays, (uint32_t)first, n, pd, queue_cap, c_count, d_hits, c64, ctx->stream));
         if (timing) HIP_TRY(ctx, next_event(eb));
         cfg.max_rays = n;
-        LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd, rd, c_count, c_head, c_other, c64, false, ctx->stream));
+        if (any_hit) LAUNCH_TRY(rtk::launch_extend_any(cfg, scene->dev, pd, rd, c_count, c_head, c_other, c64, ctx->stream));
+        else LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd, rd, c_count, c_head, c_other, c64, false, ctx->stream));
         if (timing) HIP_TRY(ctx, next_event(ec));
         // a queue holds at most its share of the chunk's 512-ray groups
         const uint32_t per_queue = std::min<uint32_t>(queue_cap, ((n + 511u) / 512u + rtk::kQueues - 1u) / rtk::kQueues * 512u);
-        LAUNCH_TRY(rtk::launch_rays_export(cfg, scene->dev, scene->src, pd, queue_cap, per_queue, c_count, d_hits, ctx->stream));
+        if (any_hit) LAUNCH_TRY(rtk::launch_occluded_export(pd, queue_cap, per_queue, c_count, d_hits, ctx->stream));
+        else LAUNCH_TRY(rtk::launch_rays_export(cfg, scene->dev, scene->src, pd, queue_cap, per_queue, c_count, d_hits, ctx->stream));
         if (timing) { HIP_TRY(ctx, next_event(ed)); spans.push_back({ea, eb, 2}); spans.push_back({eb, ec, 0}); spans.push_back({ec, ed, 2}); }
         ++launched;
     }
@@ -1161,14 +1167,16 @@ static int trace_rays_impl(RtCtx* ctx, const RtScene* scene, const RtRayQueryOpt
     return RT_OK;
 }
 
-// the argument checks of both variants: a refused call has written nothing
-static int trace_rays_refuse(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const void* rays, uint64_t n_rays, const void* hits, bool device) {
+// the argument checks of both variants: a refused call has written nothing. out_align: the alignment a device output needs (RtRayHit
+// records: 16; the bytes of an occlusion query: 1)
+static int trace_rays_refuse(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const void* rays, uint64_t n_rays, const void* out, bool device,
+                             uintptr_t out_align = 16u) {
     if (!scene) return set_err(ctx, RT_ERR_INVALID, "scene is null");
     const int v = check_ray_query(ctx, options, n_rays); if (v != RT_OK) return v;
     if (scene->features & rtk::F_MEDIUM)
         return set_err(ctx, RT_ERR_UNSUPPORTED, "ray queries: the scene holds a ConstantMedium, whose hit is a random draw keyed by a path; a bare ray has none");
-    if (n_rays != 0u && (!rays || !hits)) return set_err(ctx, RT_ERR_INVALID, "rays / hits is null");
-    if (device && (((uintptr_t)rays | (uintptr_t)hits) & 15u)) return set_err(ctx, RT_ERR_INVALID, "rays / hits must be 16-byte aligned");
+    if (n_rays != 0u && (!rays || !out)) return set_err(ctx, RT_ERR_INVALID, "rays / hits is null");
+    if (device && ((((uintptr_t)rays) & 15u) | (((uintptr_t)out) & (out_align - 1u)))) return set_err(ctx, RT_ERR_INVALID, "rays / hits must be 16-byte aligned");
     return RT_OK;
 }
 
@@ -1196,6 +1204,36 @@ int rt_trace_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* opt
     const int r = rt_trace_rays_device(ctx, scene, options, ctx->rays_tmp.p, n_rays, ctx->hits_tmp.p, stats);
     if (r != RT_OK) return r;
     HIP_TRY(ctx, hipMemcpyAsync(hits_host, ctx->hits_tmp.p, (size_t)n_rays * sizeof(RtRayHit), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT_OK;
+}
+
+// occlusion queries: the two entry points above with the any-hit kernels and one byte per ray
+int rt_occluded_rays_device(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const void* rays_device, uint64_t n_rays, void* occluded_device, RtStats* stats) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    const int v = trace_rays_refuse(ctx, scene, options, rays_device, n_rays, occluded_device, true, 1u); if (v != RT_OK) return v;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n_rays == 0u) return RT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int r = trace_rays_impl(ctx, scene, options, rays_device, n_rays, occluded_device, stats, true);
+    if (r != RT_OK) { const std::string keep = ctx->err; (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); ctx->err = keep; g_last_error = keep; }
+    return r;
+}
+
+int rt_occluded_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const RtRay* rays_host, uint64_t n_rays, uint8_t* occluded_host, RtStats* stats) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    const int v = trace_rays_refuse(ctx, scene, options, rays_host, n_rays, occluded_host, false, 1u); if (v != RT_OK) return v;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n_rays == 0u) return RT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(ctx, ctx->rays_tmp.ensure((size_t)n_rays * sizeof(RtRay)));
+    HIP_TRY(ctx, ctx->hits_tmp.ensure((size_t)n_rays));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->rays_tmp.p, rays_host, (size_t)n_rays * sizeof(RtRay), hipMemcpyHostToDevice, ctx->stream));
+    const int r = rt_occluded_rays_device(ctx, scene, options, ctx->rays_tmp.p, n_rays, ctx->hits_tmp.p, stats);
+    if (r != RT_OK) return r;
+    HIP_TRY(ctx, hipMemcpyAsync(occluded_host, ctx->hits_tmp.p, (size_t)n_rays, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return RT_OK;

@@ -4,7 +4,8 @@ A kernel's text is what stands between its label and its .Lfunc_end; comments, s
 stripped, every instruction and label is kept. Register figures that match are not enough: the scheduler's occupancy target follows
 the flat work-group size and can reorder instructions without moving a register count.
 Kernels are matched by name. A k_extend of `after` without a group size among its template arguments (<MODE, FEAT, COUNT, DRAIN, LIST>) is
-compared with the copy of `before` that was compiled for the largest group (<MODE, FEAT, COUNT, TPB, DRAIN, LIST>)."""
+compared with the copy of `before` that was compiled for the largest group (<MODE, FEAT, COUNT, TPB, DRAIN, LIST>); one with a seventh
+argument `false` (<..., LIST, ANYHIT = false>) with the six-argument instance of `before`."""
 import re, subprocess, sys
 
 
@@ -59,6 +60,9 @@ if sys.argv[1] == '--copies':
     print(f"{same + diff} smaller-group copies compared with their largest-group copy: {same} identical, {diff} differ")
 else:
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    # a k_extend of `after` with a seventh template argument `false` (ANYHIT, defaulted: added after `before` was taken) is the instance
+    # `before` lists with six
+    b = {(n[:-len(', false>')] + '>' if re.fullmatch(r'rtk::k_extend<([^,]*, ){6}false>', n) else n): v for n, v in b.items()}
     by_key = merged(a)
     same = diff = 0
     used = set()
