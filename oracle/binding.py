@@ -82,6 +82,8 @@ def lib():
         L.orc_aabb_hit.argtypes = [f64p, f64p, f64p, f64p, C.c_double, C.c_double, C.c_int]
         L.orc_world_hit.restype = C.c_int
         L.orc_world_hit.argtypes = [vp, f64p, f64p, C.c_double, C.c_double, C.c_double, f64p]
+        L.orc_world_hit_many.restype = C.c_int
+        L.orc_world_hit_many.argtypes = [vp, C.c_uint64, f64p, f64p, f64p, C.c_double, f64p, C.c_double, C.c_int, f64p, C.POINTER(C.c_uint8)]
         L.orc_texture_value.restype = C.c_int
         L.orc_texture_value.argtypes = [vp, C.c_int, C.c_double, C.c_double, f64p, f64p]
         L.orc_rng_stream.restype = None
@@ -207,6 +209,30 @@ def world_hit(desc, o, d, tm=0.0, t_min=0.001, t_max=float("inf")):
     if n < 0:
         raise RuntimeError("oracle: " + lib().orc_last_error().decode())
     return hit_out(n, buf)
+
+
+def world_hit_many(desc, o, d, tm, t_min=0.001, t_max=float("inf"), precision=64):
+    """world.hit for n rays with one scene build: o, d (n, 3), tm (n,), t_max a scalar or (n,). Returns (hit bool (n,), rec float64 (n, 10):
+    t, p, normal, u, v, front_face as orc_world_hit writes them; rows of misses are 0). precision 64 gives world_hit's bits; 32 runs the
+    checker's f32 instance."""
+    o, d = np.ascontiguousarray(o, dtype=np.float64).reshape(-1, 3), np.ascontiguousarray(d, dtype=np.float64).reshape(-1, 3)
+    n = len(o)
+    tm = np.ascontiguousarray(np.broadcast_to(np.asarray(tm, dtype=np.float64), (n,)))
+    if d.shape != o.shape:
+        raise ValueError("o and d must both be (n, 3)")
+    per_ray = None
+    if np.ndim(t_max) != 0:
+        per_ray = np.ascontiguousarray(t_max, dtype=np.float64).reshape(-1)
+        if len(per_ray) != n:
+            raise ValueError("t_max must be a scalar or hold one value per ray")
+    rec, hit = np.zeros((n, 10), dtype=np.float64), np.zeros(n, dtype=np.uint8)
+    f64p = C.POINTER(C.c_double)
+    rc = lib().orc_world_hit_many(C.byref(desc), n, o.ctypes.data_as(f64p), d.ctypes.data_as(f64p), tm.ctypes.data_as(f64p), float(t_min),
+                                  per_ray.ctypes.data_as(f64p) if per_ray is not None else None, float(t_max) if per_ray is None else 0.0, int(precision),
+                                  rec.ctypes.data_as(f64p), hit.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != 0:
+        raise RuntimeError("oracle: " + lib().orc_last_error().decode())
+    return hit != 0, rec
 
 
 def rng_stream(seed, pixel_index, sample_index, n):

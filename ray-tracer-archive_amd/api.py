@@ -215,10 +215,10 @@ def comm_unique_id():
     return bytes(buf)
 
 
-def compile_info(desc, layout_flags=0):
-    """rt_scene_compile_info[_ex]: what the scene compiler makes of a graph (host only)."""
+def compile_info(desc, layout_flags=0, **more):
+    """rt_scene_compile_info[_ex]: what the scene compiler makes of a graph (host only); `more` as for upload_options."""
     info = A.RtCompileInfo()
-    opt = upload_options(layout_flags)
+    opt = upload_options(layout_flags, **more)
     _check(lib().rt_scene_compile_info_ex(C.byref(desc), C.byref(opt), C.byref(info)))
     out = {n: getattr(info, n) for n, _ in info._fields_ if n not in ("first", "_pad")}
     out["first"] = [int(info.first[k]) for k in range(info.n_first)]
@@ -232,10 +232,10 @@ def wide_layout_check(desc):
     return {n: getattr(info, n) for n, _ in info._fields_ if not n.startswith("_")}
 
 
-def compile_dump(desc, layout_flags=0):
-    """rt_scene_compile_dump[_ex]: (nodes structured array, spheres (n,4) f32, sphere_meta u32)."""
-    info = compile_info(desc, layout_flags)
-    opt = upload_options(layout_flags)
+def compile_dump(desc, layout_flags=0, **more):
+    """rt_scene_compile_dump[_ex]: (nodes structured array, spheres (n,4) f32, sphere_meta u32); `more` as for upload_options."""
+    info = compile_info(desc, layout_flags, **more)
+    opt = upload_options(layout_flags, **more)
     node_t = np.dtype([("mn", np.float32, 3), ("skip", np.uint32), ("mx", np.float32, 3), ("leaf", np.uint32)])
     nodes = np.zeros(info["n_nodes"], dtype=node_t)
     n_s = max(1, info["n_spheres"] + info["n_media"])   # media boundaries add private spheres

@@ -1,6 +1,8 @@
-"""Ray sets for the ray-query tests (tests/test_rays_host.py, tests/test_gpu_rays.py): six small scenes, and per scene a fixed list of
-f32 rays — pixel-centre camera rays plus one generation of secondary rays from the CPU checker's hit points in seeded random directions —
-with the checker's f64 answer for every ray, which rays are DECIDABLE, and which object every hit lies on.
+"""Ray sets for the ray-query tests (tests/test_rays_host.py, tests/test_gpu_rays.py, tests/test_gpu_occlusion.py): six small scenes that
+fit LDS, and per scene a fixed list of f32 rays — pixel-centre camera rays plus one generation of secondary rays from the CPU checker's
+hit points in seeded random directions — with the checker's f64 answer for every ray, which rays are DECIDABLE, and which object every
+hit lies on. And one scene that does not fit LDS (`field`, with `field_sah`: tests/test_gpu_rays_hbm.py), its set made the same way, the
+uploads it is walked through (field_matrix) and the checker's own f32 figures that bound the device there (MEASURED_F32_CHECKER).
 
 A ray is undecidable when the checker's answer changes under a perturbation of its direction by +-R f32 ulps per component (8 fixed sign
 patterns): hit <-> miss, t moving by more than 1e-3 * max(1, t), or front_face flipping. Such a ray grazes a silhouette or an edge; an f32
@@ -21,7 +23,10 @@ R_ULPS = 64
 SIGNS = [(1, 1, 1), (1, 1, -1), (1, -1, 1), (1, -1, -1), (-1, 1, 1), (-1, 1, -1), (-1, -1, 1), (-1, -1, -1)]
 SCENES = ["book1", "cornell", "mesh", "moving", "rotated_sphere", "earth"]
 STATIC_SCENES = ["book1", "cornell", "mesh", "rotated_sphere", "earth"]
-GRID = (48, 32)          # camera rays per scene: pixel centres of a 48 x 32 frame (+ as many secondary rays as they have hits)
+# the ray set of scenes that do not fit LDS (tests/test_gpu_rays_hbm.py): one geometry, the reference's BVH builder and the SAH one
+HBM_SCENES = ["field", "field_sah"]
+FIELD_SPHERES, FIELD_GRID, FIELD_SEED, FIELD_BOX_RAYS = 1250, 23, 20250317, 64
+GRID = (48, 32)         # camera rays per scene: pixel centres of a 48 x 32 frame (+ as many secondary rays as they have hits)
 
 
 def earth_image():
@@ -35,8 +40,101 @@ class Built:
         self.desc, self.cam, self.keep, self.extent = desc, cam, keep, extent
 
 
+def field_scene(pkg, builder):
+    """A static BVH that does not fit LDS (a few thousand records, more than the default LDS top of 1024 and at most the 4096 a top can hold):
+    FIELD_SPHERES spheres over a height field of FIELD_GRID^2 x 2 triangles, one Box, one ground rect. No two surfaces meet — spheres
+    are placed by rejection, 0.05 apart and outside the box's footprint; the height field lies between the rect and everything else —
+    so no ray finds two primitives at one t, the one way layouts may differ (include/rt_hip.h, the layout section)."""
+    rng = np.random.default_rng(FIELD_SEED)
+    b = pkg.SceneBuilder(background=(0.5, 0.7, 1.0), background_mode=pkg._abi.RT_BG_SKY_GRADIENT, bvh_builder=builder)
+    mats = [b.lambertian((0.7, 0.3, 0.3)), b.metal((0.8, 0.8, 0.8), 0.1), b.dielectric(1.5)]
+    centres, radii = np.zeros((FIELD_SPHERES, 3)), np.zeros(FIELD_SPHERES)
+    k = 0
+    while k < FIELD_SPHERES:
+        c = np.array([rng.uniform(-12.0, 12.0), rng.uniform(0.5, 3.5), rng.uniform(-12.0, 12.0)])
+        r = rng.uniform(0.2, 0.4)
+        if abs(c[0]) < 1.6 and abs(c[2]) < 1.6:
+            continue
+        if k and (np.linalg.norm(centres[:k] - c, axis=1) < radii[:k] + r + 0.05).any():
+            continue
+        centres[k], radii[k] = c, r
+        k += 1
+    ids = [b.sphere(centres[i], float(radii[i]), mats[i % 3]) for i in range(FIELD_SPHERES)]
+    n = FIELD_GRID
+    h = rng.uniform(-1.0, -0.2, (n + 1, n + 1))
+    P = lambda i, j: (-12.0 + 24.0 * i / n, float(h[i, j]), -12.0 + 24.0 * j / n)
+    tri_mats = [b.lambertian((0.3, 0.6, 0.3)), b.metal((0.7, 0.7, 0.9), 0.2)]
+    for i in range(n):
+        for j in range(n):
+            ids.append(b.triangle(P(i, j), P(i + 1, j), P(i, j + 1), tri_mats[(i + j) & 1]))
+            ids.append(b.triangle(P(i + 1, j), P(i + 1, j + 1), P(i, j + 1), tri_mats[(i + j + 1) & 1]))
+    ids.append(b.box((-1.0, 0.0, -1.0), (1.0, 2.0, 1.0), b.lambertian((0.8, 0.7, 0.2))))
+    ids.append(b.xz_rect(-14, 14, -14, 14, -1.25, b.lambertian((0.5, 0.5, 0.5))))
+    desc = b.desc(b.bvh(ids))
+    cam = pkg.camera_new((14.0, 5.0, 16.0), (0.0, 0.5, 0.0), (0, 1, 0), 40.0, 1.5, 0.0, 10.0, 0.0, 0.0)
+    return Built(desc, cam, b, 14.0)
+
+
+def field_matrix(A):
+    """The uploads of tests/test_gpu_rays_hbm.py: case -> (scene, layout flags, the other RtUploadOptions fields). None of them fits LDS
+    (tests/test_rays_host.py::test_field_does_not_fit_lds), but `collapse_4`: leaf_collapse = 4 folds the tree to ~1,600 records, which do;
+    `collapse_4_hbm` is the same upload kept out of LDS by flag."""
+    m = {"c16": (0, {}), "c16_one_order": (A.RT_LAYOUT_CHILD_ORDER_AS_REFERENCE, {})}
+    for k in range(1, 8):
+        m[f"c16_axes_{k}"] = (0, dict(octant_axes=k))
+    for k in (1, 2, 3, 7, 100, 0, 4096):
+        m[f"top_{k or 1024}"] = (A.RT_LAYOUT_NODES_32B, dict(lds_top_records=k))
+    m["top_one_order"] = (A.RT_LAYOUT_NODES_32B | A.RT_LAYOUT_CHILD_ORDER_AS_REFERENCE, dict(lds_top_records=7))
+    m["member_boxes"] = (A.RT_LAYOUT_MEMBER_BOXES, {})
+    m["lists_as_reference"] = (A.RT_LAYOUT_LISTS_AS_REFERENCE, {})
+    m["lists_as_reference_top_7"] = (A.RT_LAYOUT_LISTS_AS_REFERENCE | A.RT_LAYOUT_NODES_32B, dict(lds_top_records=7))
+    m["park_cost"] = (0, dict(list_park_cost=2.0))
+    m["wide"] = (A.RT_LAYOUT_WIDE_NODES, {})
+    m["collapse_4"] = (0, dict(leaf_collapse=4))
+    m["collapse_4_hbm"] = (A.RT_LAYOUT_SCENE_IN_HBM, dict(leaf_collapse=4))
+    out = {k: ("field",) + v for k, v in m.items()}
+    for k in ("c16", "top_1024", "wide"):
+        out[k + "_sah"] = ("field_sah",) + m[k]
+    return out
+
+
+FITS_LDS = ("collapse_4",)          # the cases of field_matrix whose flags make the scene fit LDS
+
+
+def top_rule(skip, max_top):
+    """Records of the top of the tree a NODES_32B upload keeps in LDS (RtStats.lds_top_nodes), restated from the skip links of the
+    compiled records: depth = the number of enclosing subtrees [i, skip_i); the top is every record above the deepest cut that holds at
+    most max_top records — or nothing, when the first level alone exceeds max_top or the whole tree fits."""
+    n, ends, per_depth = len(skip), [], []
+    for i in range(n):
+        while ends and ends[-1] <= i:
+            ends.pop()
+        if len(ends) == len(per_depth):
+            per_depth.append(0)
+        per_depth[len(ends)] += 1
+        if skip[i] > i + 1:
+            ends.append(int(skip[i]))
+    total = 0
+    for count in per_depth:
+        if total + count > max_top:
+            break
+        total += count
+    return total if 0 < total < n else 0
+
+
+def field_box_rays(rng):
+    """FIELD_BOX_RAYS primary rays at the Box of field_scene, from seeded points above the spheres towards seeded points inside the box.
+    The camera's own rays reach the box on a handful of pixels (it stands behind 14 units of spheres: 1 to 10 hits over 40 scene seeds);
+    these make it a kind the set covers. They get their secondary rays like every other primary ray."""
+    o = np.stack([rng.uniform(-4.0, 4.0, FIELD_BOX_RAYS), rng.uniform(4.5, 7.0, FIELD_BOX_RAYS), rng.uniform(-4.0, 4.0, FIELD_BOX_RAYS)], axis=1)
+    to = np.stack([rng.uniform(-0.9, 0.9, FIELD_BOX_RAYS), rng.uniform(0.1, 1.9, FIELD_BOX_RAYS), rng.uniform(-0.9, 0.9, FIELD_BOX_RAYS)], axis=1)
+    return make_rays(o, to - o, np.zeros(FIELD_BOX_RAYS))
+
+
 def build_scene(pkg, name):
     A = pkg._abi
+    if name in HBM_SCENES:
+        return field_scene(pkg, A.RT_BVH_SAH if name == "field_sah" else A.RT_BVH_REFERENCE)
     if name == "book1":
         hs = pkg.HostScene("book1", 1)
         # (the book's camera looks at the origin, which is the north pole of the r = 1000 ground sphere: u is ill-conditioned within 3 units
@@ -115,8 +213,17 @@ def camera_rays(cam, width, height, rng):
     return make_rays(np.broadcast_to(org, d.shape), d, tm)
 
 
-def ask(orc, desc, rays):
-    """The checker's world.hit for every ray, as arrays: hit (bool), t, p, n, u, v, ff."""
+def ask(orc, desc, rays, precision=64):
+    """The checker's world.hit for every ray, as arrays: hit (bool), t, p, n, u, v, ff. One batch call: the scene is built once."""
+    hit, rec = orc.world_hit_many(desc, rays["o"], rays["d"], rays["time"], 0.001, float("inf"), precision)
+    miss = ~hit
+    out = dict(hit=hit, t=rec[:, 0].copy(), p=rec[:, 1:4].copy(), n=rec[:, 4:7].copy(), u=rec[:, 7].copy(), v=rec[:, 8].copy(), ff=rec[:, 9] != 0.0)
+    out["t"][miss] = np.inf
+    return out
+
+
+def ask_per_ray(orc, desc, rays):
+    """ask() through the per-ray entry orc_world_hit, which builds the scene for every ray: what the batch entry is held to, bit for bit."""
     n = len(rays)
     out = dict(hit=np.zeros(n, bool), t=np.full(n, np.inf), p=np.zeros((n, 3)), n=np.zeros((n, 3)), u=np.zeros(n), v=np.zeros(n), ff=np.zeros(n, bool))
     L = orc.lib()
@@ -219,6 +326,40 @@ def objects_at(pkg, desc, p, tm, extent):
     return np.array([i for i, _, _ in prims]), dist <= 1e-7 * max(1.0, extent)
 
 
+def deviations(pkg, s, k, t, p, n, u, v):
+    """Worst deviation from the set's f64 answers on the rays k, in the definitions of tests/test_gpu_rays.py: dict(t = relative |dt|,
+    p = |dp| / extent, n = |dn|, uv = |d(u, v)| with u modulo 1 and sphere hits within 1e-3 of a pole left out, ta = |dt| / max(1, t))
+    and the rays that set each figure. t, p, n, u, v: the answers under test for the whole set."""
+    A = pkg._abi
+    built, ref, ids, on = s["built"], s["ref"], s["ids"], s["on"]
+    f = lambda a: np.asarray(a)[k].astype(np.float64)
+    dt = np.abs(f(t) - ref["t"][k])
+    kind = np.array([built.desc.hittables[int(h)].kind for h in ids])
+    polar = (on[k] & (kind == A.RT_HIT_SPHERE)[None, :]).any(axis=1) & ((ref["v"][k] < 1e-3) | (ref["v"][k] > 1.0 - 1e-3))
+    du = np.abs(f(u) - ref["u"][k]); du = np.minimum(du, 1.0 - du)
+    dv = np.abs(f(v) - ref["v"][k])
+    each = dict(t=dt / ref["t"][k], p=np.linalg.norm(f(p) - ref["p"][k], axis=1) / built.extent, n=np.linalg.norm(f(n) - ref["n"][k], axis=1),
+                uv=np.where(polar, 0.0, np.maximum(du, dv)), ta=dt / np.maximum(1.0, ref["t"][k]))
+    return {q: float(e.max()) for q, e in each.items()}, {q: int(k[int(e.argmax())]) for q, e in each.items()}
+
+
+# The checker against itself: its f32 instance (Scene<float>) against its f64 answers on the decidable rays both hit, in deviations()'s
+# definitions, measured on a CPU (tests/test_rays_host.py::test_field_f32_checker_figures measures them again and holds them to this
+# table). What plain f32 arithmetic costs on this set; the device is allowed 2 x each figure (tests/test_gpu_rays_hbm.py), the factor of
+# tests/test_gpu_paths.py. Nothing here comes from a GPU.
+MEASURED_F32_CHECKER = {
+    "field": dict(t=1.451e-2, p=2.312e-4, n=8.155e-3, uv=4.650e-3, ta=1.595e-4),
+}
+
+
+def f32_checker_figures(pkg, orc, name):
+    s = ray_set(pkg, orc, name)
+    a = ask(orc, s["built"].desc, s["rays"], precision=32)
+    k = np.flatnonzero(~s["undecidable"] & s["ref"]["hit"] & a["hit"])
+    worst, at = deviations(pkg, s, k, a["t"], a["p"], a["n"], a["u"], a["v"])
+    return worst, at, a
+
+
 _cache = {}
 
 
@@ -227,8 +368,13 @@ def ray_set(pkg, orc, name):
     if name in _cache:
         return _cache[name]
     built = build_scene(pkg, name)
-    rng = np.random.default_rng(7 + SCENES.index(name))
+    if name == "field_sah":                                   # the geometry of "field": the checker's answers do not depend on the device's builder
+        _cache[name] = dict(ray_set(pkg, orc, "field"), built=built)
+        return _cache[name]
+    rng = np.random.default_rng(7 + (SCENES + HBM_SCENES).index(name))
     prim = camera_rays(built.cam, GRID[0], GRID[1], rng)
+    if name == "field":
+        prim = np.concatenate([prim, field_box_rays(rng)])
     first = ask(orc, built.desc, prim)
     k = np.flatnonzero(first["hit"])
     dirs = rng.normal(size=(len(k), 3)); dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)

@@ -50,6 +50,7 @@ def test_occlusion_agrees_with_the_checker_and_the_closest_hit(pkg, orc, gpu, na
     try:
         occ, st = occluded_device(gpu, scene, rays, with_stats=True)
         assert st["segments"] == st["samples"] == len(rays)
+        assert layout != "hbm_32b" or st["lds_top_nodes"] == 0      # M_HBM, not the top layout (tests/test_gpu_rays_hbm.py)
         assert np.isin(occ, (0, A.RT_RAYHIT_HIT)).all()
         dec = ~und
         wrong = dec & ((occ == A.RT_RAYHIT_HIT) != ref["hit"])

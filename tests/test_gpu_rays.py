@@ -56,6 +56,7 @@ def test_rays_agree_with_the_checker(pkg, orc, gpu, name, layout):
     hits, st = trace_device(pkg, gpu, scene, rays, with_stats=True)
     scene.close()
     assert st["segments"] == st["samples"] == len(rays)
+    assert layout != "hbm_32b" or st["lds_top_nodes"] == 0      # fewer records than a top holds: M_HBM. The top layout is tests/test_gpu_rays_hbm.py's
     g_hit, g_ff = (hits["flags"] & A.RT_RAYHIT_HIT) != 0, (hits["flags"] & A.RT_RAYHIT_FRONT_FACE) != 0
     assert ((hits["flags"] & ~np.uint32(3)) == 0).all()
     dec = ~und

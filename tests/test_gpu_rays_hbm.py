@@ -1,0 +1,204 @@
+"""The walks of a scene that does NOT fit LDS, ray by ray (tests/rays.py, scene `field`: ~3,700 records, more than the default LDS top of
+1024 and at most the 4096 a top can hold): every upload of rays.field_matrix — compressed records per direction octant (every choice
+of octant axes), 32-byte records with a top of 1 .. 1024 records in LDS (k_extend's M_TOP) or none (M_HBM), member boxes, the
+reference's lists, a park cost, the 8-wide tree, collapsed leaves — against the f64 CPU checker, against the device's own closest hit
+through the any-hit walk, and bit for bit against each other; and one small render through the top layouts and the three carriers.
+
+The scene's surfaces are disjoint, so no ray finds two primitives at one t: the one way layouts may differ (include/rt_hip.h, the layout
+section) is absent, and what the header promises is equality of the records, not closeness.
+
+Tolerance of t, p, n, u, v: 2 x rays.MEASURED_F32_CHECKER["field"], the CPU checker's f32 instance against its f64 answers on this set —
+the factor and the rule of tests/test_gpu_paths.py. Nothing in it comes from the device, whose own worst figures are recorded
+(record_metric) and tabled in DESIGN.md section 11."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rays as R  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+CASES = ["c16", "c16_one_order"] + [f"c16_axes_{k}" for k in range(1, 8)] + [f"top_{k}" for k in (1, 2, 3, 7, 100, 1024, 4096)] + \
+        ["top_one_order", "member_boxes", "lists_as_reference", "lists_as_reference_top_7", "park_cost", "wide", "collapse_4", "collapse_4_hbm",
+         "c16_sah", "top_1024_sah", "wide_sah"]
+TOPS = [f"top_{k}" for k in (1, 2, 3, 7, 100, 1024, 4096)]
+NOT_BINARY = ("wide", "wide_sah", "collapse_4", "collapse_4_hbm")
+BASE = "c16_one_order"
+
+_results = {}
+
+
+def to_device(rays):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(rays).view(np.float32).reshape(-1, 8).copy()).cuda()
+
+
+def run_case(pkg, orc, gpu, case):
+    """One upload per case: the closest hits with their stats, and the any-hit bytes for the three limits of (c). Kept per process."""
+    if case in _results:
+        return _results[case]
+    A = pkg._abi
+    name, flags, more = R.field_matrix(A)[case]
+    s = R.ray_set(pkg, orc, name)
+    rays = s["rays"]
+    f32 = np.float32
+    scene = gpu.upload(s["built"].desc, flags, **more)
+    try:
+        out, st = gpu.trace_rays(scene, to_device(rays), with_stats=True)
+        hits = out.cpu().numpy().reshape(-1).view(pkg.RAYHIT_DTYPE)
+        hit = (hits["flags"] & A.RT_RAYHIT_HIT) != 0
+        occ = {}
+        for label, limit in (("none", np.zeros(len(rays), f32)), ("t", np.where(hit, hits["t"], f32(1.0)).astype(f32)),
+                             ("below", np.where(hit, np.nextafter(hits["t"], f32(0.0)), f32(1.0)).astype(f32))):
+            q = rays.copy()
+            q["t_max"] = limit
+            o, ost = gpu.occluded(scene, to_device(q), with_stats=True)
+            occ[label] = o.cpu().numpy()
+            assert ost["bvh_in_lds"] == st["bvh_in_lds"] and ost["lds_top_nodes"] == st["lds_top_nodes"] and ost["segments"] == len(rays)
+    finally:
+        scene.close()
+    _results[case] = dict(set=s, flags=flags, more=more, hits=hits, stats=st, occ=occ)
+    return _results[case]
+
+
+def test_the_matrix_is_the_one_of_rays_py(pkg):
+    assert sorted(CASES) == sorted(R.field_matrix(pkg._abi))
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_field_rays(pkg, orc, gpu, case):
+    from conftest import record_metric
+    A = pkg._abi
+    r = run_case(pkg, orc, gpu, case)
+    s, hits, st, flags, more = r["set"], r["hits"], r["stats"], r["flags"], r["more"]
+    built, rays, ref, und = s["built"], s["rays"], s["ref"], s["undecidable"]
+    assert st["segments"] == st["samples"] == len(rays)
+    # ---- (a) which kernel ran ----
+    want_top = 0
+    if flags & A.RT_LAYOUT_NODES_32B:
+        skip = pkg.compile_dump(built.desc, flags, **more)[0]["skip"]
+        want_top = R.top_rule(skip, min(more.get("lds_top_records", 0) or 1024, 4096))
+    print(f"{case}: bvh_in_lds {st['bvh_in_lds']}, lds_top_nodes {st['lds_top_nodes']} (the depth-cut rule gives {want_top}), {st['scene_nodes']} records")
+    record_metric(config="rays_hbm_kernel", case=case, bvh_in_lds=int(st["bvh_in_lds"]), lds_top_nodes=int(st["lds_top_nodes"]), top_rule=int(want_top),
+                  scene_nodes=int(st["scene_nodes"]))
+    assert st["bvh_in_lds"] == (1 if case in R.FITS_LDS else 0)
+    assert st["lds_top_nodes"] == want_top
+    if case in ("top_7", "top_100", "top_1024", "top_1024_sah", "top_one_order", "lists_as_reference_top_7"):
+        assert st["lds_top_nodes"] > 0, "this case is meant to run M_TOP"
+    if case == "top_4096":
+        assert st["lds_top_nodes"] == 0, "the whole tree fits a top of 4096 records: M_HBM"
+    # ---- (b) against the checker, on decidable rays ----
+    g_hit, g_ff = (hits["flags"] & A.RT_RAYHIT_HIT) != 0, (hits["flags"] & A.RT_RAYHIT_FRONT_FACE) != 0
+    assert ((hits["flags"] & ~np.uint32(3)) == 0).all()
+    dec = ~und
+    print(f"{case}: {len(rays)} rays, {int(und.sum())} undecidable (left out), {int((g_hit & dec).sum())} hits compared")
+    wrong = dec & (g_hit != ref["hit"])
+    assert not wrong.any(), f"hit/miss differs on decidable rays {np.flatnonzero(wrong)[:8]}"
+    both = dec & g_hit
+    wrong = both & (g_ff != ref["ff"])
+    assert not wrong.any(), f"front_face differs on decidable rays {np.flatnonzero(wrong)[:8]}"
+    miss = ~g_hit
+    assert np.isposinf(hits["t"][miss]).all() and (hits["hittable"][miss] == -1).all() and (hits["material"][miss] == -1).all()
+    assert (hits["flags"][miss] == 0).all() and not hits["p"][miss].any() and not hits["n"][miss].any() and not hits["u"][miss].any() and not hits["v"][miss].any()
+    ids, on = s["ids"], s["on"]
+    col = np.full(built.desc.n_hittables, -1)
+    col[ids] = np.arange(len(ids))
+    k = np.flatnonzero(both)
+    h = hits["hittable"][k]
+    assert ((h >= 0) & (h < len(col))).all() and (col[h] >= 0).all(), "a hittable that is not a primitive record"
+    off = k[~on[k, col[h]]]
+    assert len(off) == 0, f"rays {off[:8]}: the checker's hit point does not lie on the reported hittable {hits['hittable'][off[:8]]}"
+    mat = np.array([built.desc.hittables[int(i)].material for i in h])
+    assert (hits["material"][k] == mat).all(), f"material differs on rays {k[hits['material'][k] != mat][:8]}"
+    worst, at = R.deviations(pkg, s, k, hits["t"], hits["p"], hits["n"], hits["u"], hits["v"])
+    bound = {q: 2.0 * v for q, v in R.MEASURED_F32_CHECKER["field"].items()}
+    print(f"{case}: worst rel|dt| {worst['t']:.3e}  |dp|/extent {worst['p']:.3e}  |dn| {worst['n']:.3e}  |d(u,v)| {worst['uv']:.3e}  |dt|/max(1,t) {worst['ta']:.3e}"
+          f"  at rays {at}")
+    record_metric(config="rays_hbm", case=case, dta=worst["ta"], dt=worst["t"], dp=worst["p"], dn=worst["n"], duv=worst["uv"], undecidable=int(und.sum()),
+                  rays=len(rays))
+    for q in bound:
+        assert worst[q] <= bound[q], (q, worst[q], bound[q], at[q])
+    # ---- (c) the any-hit walk on the same upload against the closest hit, exactly ----
+    want = np.where(g_hit, A.RT_RAYHIT_HIT, 0).astype(np.uint8)
+    occ = r["occ"]
+    assert (occ["none"] == want).all(), f"no limit: differs from the closest hit at {np.flatnonzero(occ['none'] != want)[:8]}"
+    assert (occ["t"] == want).all(), f"t_max = t bit for bit: differs at {np.flatnonzero(occ['t'] != want)[:8]}"
+    assert not occ["below"].any(), f"t_max = nextafter(t, 0) (misses: 1.0): occluded at {np.flatnonzero(occ['below'])[:8]}"
+
+
+def describe(pkg, s, a, b, i):
+    d = s["built"].desc
+    on = s["ids"][s["on"][i]]
+    return (f"ray {i}: t {a['t'][i]!r} / {b['t'][i]!r}, hittable {a['hittable'][i]} / {b['hittable'][i]} "
+            f"(kinds {d.hittables[max(int(a['hittable'][i]), 0)].kind} / {d.hittables[max(int(b['hittable'][i]), 0)].kind}), flags {a['flags'][i]} / {b['flags'][i]}, "
+            f"checker t {s['ref']['t'][i]!r} on hittables {on.tolist()}")
+
+
+def test_the_matrix_bit_for_bit(pkg, orc, gpu):
+    """(d) On decidable rays every binary walk — and the 8-wide walk, which calls the same primitive functions — returns the RtRayHit bytes
+    of c16_one_order, whatever the records, their order, their memory or the BVH builder; the top_k cases (same records, same order, another
+    memory) equal each other on ALL rays; collapsed leaves give the same hittable and the same t bits."""
+    from conftest import record_metric
+    base = run_case(pkg, orc, gpu, BASE)
+    s = base["set"]
+    dec = ~s["undecidable"]
+    differing = {}
+    for case in CASES:
+        got = run_case(pkg, orc, gpu, case)["hits"]
+        if case in ("collapse_4", "collapse_4_hbm"):
+            bad = dec & ((got["hittable"] != base["hits"]["hittable"]) | (got["t"].view(np.uint32) != base["hits"]["t"].view(np.uint32)))
+        else:
+            bad = dec & (got.view(np.uint8).reshape(len(got), -1) != base["hits"].view(np.uint8).reshape(len(got), -1)).any(axis=1)
+        differing[case] = np.flatnonzero(bad)
+        if bad.any():
+            print(f"{case} against {BASE}: " + "; ".join(describe(pkg, s, got, base["hits"], int(i)) for i in differing[case][:4]))
+    total = int(sum(len(v) for v in differing.values()))
+    print(f"decidable rays that differ from {BASE}, over {len(CASES)} uploads: {total}  {({c: len(v) for c, v in differing.items() if len(v)})}")
+    record_metric(config="rays_hbm_matrix", uploads=len(CASES), decidable_rays_differing=total)
+    first = run_case(pkg, orc, gpu, TOPS[0])["hits"]
+    for case in TOPS[1:]:
+        got = run_case(pkg, orc, gpu, case)["hits"]
+        assert got.tobytes() == first.tobytes(), f"{case} differs from {TOPS[0]} on rays {np.flatnonzero((got.view(np.uint8).reshape(len(got), -1) != first.view(np.uint8).reshape(len(got), -1)).any(axis=1))[:8]}"
+    assert total == 0, {c: v[:8].tolist() for c, v in differing.items() if len(v)}
+
+
+def test_field_render_through_the_top_layouts(pkg, orc, gpu):
+    """A render of the same scene (32 x 24, 4 spp, depth 8): the frame and the segment count are the same bytes whether the top in LDS holds
+    7, 63, 1023 records or none (M_TOP against M_HBM); with a top of 7 the wavefront loop run to the end (tail_paths = 1), the drain
+    hand-over (the default: M_TOP with DRAIN) and the fused kernel give one frame; and against the default compressed layout fewer than
+    2e-3 of the pixels differ, the share tests/test_gpu_scenes.py allows between layouts."""
+    A = pkg._abi
+    built = R.ray_set(pkg, orc, "field")["built"]
+    W, H, SPP = 32, 24, 4
+    prm = lambda **kw: pkg.make_params(W, H, SPP, max_depth=8, seed=20240917, **kw)
+    frames = {}
+    for top in (7, 100, 0, 4096):
+        scene = gpu.upload(built.desc, A.RT_LAYOUT_NODES_32B, lds_top_records=top)
+        try:
+            img, st = gpu.render(scene, built.cam, prm())
+            assert st["bvh_in_lds"] == 0 and (st["lds_top_nodes"] > 0) == (top != 4096), (top, st["lds_top_nodes"])
+            assert st["samples"] == W * H * SPP and np.isfinite(img).all()
+            frames[top] = (img, st["segments"])
+            if top == 7:
+                assert st["drain_paths"] > 0                         # the default: the drain kernel carried the paths, in M_TOP
+                loop, sl = gpu.render(scene, built.cam, prm(tail_paths=1))
+                assert sl["drain_paths"] == 0 and sl["lds_top_nodes"] == st["lds_top_nodes"]
+                fused, sf = gpu.render(scene, built.cam, prm(flags=A.RT_FLAG_FUSED, tail_paths=1))
+                assert sf["drain_paths"] > 0
+                assert loop.tobytes() == img.tobytes() == fused.tobytes() and sl["segments"] == st["segments"] == sf["segments"]
+        finally:
+            scene.close()
+    for top in (100, 0, 4096):
+        assert frames[top][0].tobytes() == frames[7][0].tobytes() and frames[top][1] == frames[7][1], top
+    scene = gpu.upload(built.desc)
+    try:
+        c16, st = gpu.render(scene, built.cam, prm())
+        assert st["bvh_in_lds"] == 0 and st["lds_top_nodes"] == 0
+    finally:
+        scene.close()
+    share = float((np.abs(c16 - frames[7][0]).max(axis=2) > 0).mean())
+    print(f"pixels that differ between top_7 and the default compressed layout: {share:.4f}; segments {frames[7][1]} / {st['segments']}")
+    assert share < 2e-3

@@ -135,3 +135,116 @@ def test_import_logic_keeps_malformed_rays_and_overfull_queues_out(pkg):
                 blocks = -(-n // 512)
                 per_queue = [len(range(q, blocks, Q)) * 512 for q in range(Q)]    # every workgroup stores at most 512 rays
                 assert max(per_queue) <= cap, (n_rays, pool_slots, n, per_queue, cap)
+
+
+# ---- the batch entry of the checker, and the ray set of a scene that does not fit LDS (tests/test_gpu_rays_hbm.py) ----------------------
+@pytest.mark.parametrize("name", ["mesh", "moving"])
+def test_batch_world_hit_equals_the_per_ray_entry(pkg, orc, name):
+    """orc_world_hit_many at precision 64 is orc_world_hit's code path with the scene built once: the same bits for every ray, hits and
+    misses, with the limit as a scalar and per ray; and a limit below the hit turns it into a miss in both."""
+    s = R.ray_set(pkg, orc, name)
+    rays, desc = s["rays"], s["built"].desc
+    batch, single = R.ask(orc, desc, rays), R.ask_per_ray(orc, desc, rays)
+    assert batch["hit"].any() and (~batch["hit"]).any()
+    for k in single:
+        assert batch[k].dtype == single[k].dtype and batch[k].tobytes() == single[k].tobytes(), k
+    o, d, tm = rays["o"].astype(np.float64), rays["d"].astype(np.float64), rays["time"].astype(np.float64)
+    limit = np.where(batch["hit"], batch["t"] * np.where(np.arange(len(rays)) & 1, 0.5, 1.5), 1.0)
+    hit, rec = orc.world_hit_many(desc, o, d, tm, 0.001, limit)
+    for i in range(0, len(rays), 7):
+        one = orc.world_hit(desc, o[i], d[i], tm[i], 0.001, limit[i])
+        assert (one is not None) == bool(hit[i]), i
+        if one is not None:
+            assert (one["t"],) + one["p"] + one["normal"] + (one["u"], one["v"], float(one["front_face"])) == tuple(rec[i]), i
+    assert (hit[batch["hit"]] == ((np.arange(len(rays)) & 1) == 0)[batch["hit"]]).all()
+    # precision 32 is the checker's f32 instance: every number it reports is an f32, and it is not the f64 answer rounded
+    h32, r32 = orc.world_hit_many(desc, o, d, tm, precision=32)
+    both = h32 & batch["hit"]
+    assert both.sum() > len(rays) // 4 and (r32 == r32.astype(np.float32)).all()
+    assert (r32[both, 0] != batch["t"][both].astype(np.float32)).any()
+    with pytest.raises(RuntimeError):
+        orc.world_hit_many(desc, o, d, tm, precision=16)
+
+
+def field_configs(pkg):
+    A = pkg._abi
+    return [(case, scene, flags, more) for case, (scene, flags, more) in R.field_matrix(A).items()]
+
+
+def test_field_does_not_fit_lds(pkg):
+    """What tests/test_gpu_rays_hbm.py relies on, for both builders and every upload of its matrix: the scene does not fit LDS, and it
+    compiles to more records than the default LDS top holds (1024: the top is partial, M_TOP) and at most the 4096 a top can hold
+    (lds_top_records = 4096 keeps no top: M_HBM). The one exception is named: leaf_collapse = 4 folds the tree below the LDS budget."""
+    A = pkg._abi
+    built = {name: R.build_scene(pkg, name) for name in R.HBM_SCENES}
+    for case, scene, flags, more in field_configs(pkg):
+        info = pkg.compile_info(built[scene].desc, flags & ~A.RT_LAYOUT_SCENE_IN_HBM, **more)
+        print(f"{case}: {info['n_nodes']} records, fits_lds = {info['fits_lds']}, n_first = {info['n_first']}")
+        if case in R.FITS_LDS or case == "collapse_4_hbm":
+            assert info["fits_lds"] == 1 and info["n_nodes"] > 1024, (case, info)
+            continue
+        assert info["fits_lds"] == 0 and 1024 < info["n_nodes"] <= 4096, (case, info)
+        assert info["n_media"] == 0 and info["n_moving"] == 0 and info["n_spheres"] == R.FIELD_SPHERES and info["n_tris"] == 2 * R.FIELD_GRID ** 2
+        # the ground rect is tested when a walk begins (the first_leaf twin) unless the lists are the reference's or the walk is 8-wide
+        assert info["n_first"] == (0 if flags & (A.RT_LAYOUT_LISTS_AS_REFERENCE | A.RT_LAYOUT_WIDE_NODES) else 1), (case, info)
+    # members without boxes make a smaller tree, which fits: that layout is the existing ray tests' (tests/test_gpu_rays.py)
+    for scene in R.HBM_SCENES:
+        assert pkg.compile_info(built[scene].desc, A.RT_LAYOUT_REFERENCE_COUNTERS)["fits_lds"] == 1
+        assert pkg.wide_layout_check(built[scene].desc)["depth"] >= 3
+
+
+def test_field_top_layouts(pkg):
+    """The top layouts the GPU test uploads, built and verified on the host (rt_scene_top_layout_check: one address space over both
+    memories, every skip link landing where the plain array's does): the number of top records is the depth-cut rule restated in
+    rays.top_rule, > 0 for tops of 7, 100 and 1024 records and 0 for 4096 (the whole tree fits: M_HBM)."""
+    L = pkg.lib()
+    for name in R.HBM_SCENES:
+        desc = R.build_scene(pkg, name).desc
+        skip = pkg.compile_dump(desc, pkg._abi.RT_LAYOUT_NODES_32B)[0]["skip"]
+        for max_top in (1, 2, 3, 7, 100, 1024, 4096):
+            n = C.c_uint64(0)
+            assert L.rt_scene_top_layout_check(C.byref(desc), max_top, C.byref(n)) == pkg._abi.RT_OK, L.rt_last_error(None)
+            assert n.value == R.top_rule(skip, max_top) <= max_top, (name, max_top, n.value)
+            assert (n.value > 0) == (max_top in (7, 100, 1024)) or max_top in (1, 2, 3), (name, max_top, n.value)
+            print(f"{name}: top of at most {max_top} records holds {n.value}")
+
+
+def test_field_ray_set(pkg, orc):
+    """The field set is decidable enough (rays.py's cap of 1 %), spread over every direction octant — the compressed layout keeps one
+    record array per octant — and over every primitive kind of the scene; every hit lies on exactly one primitive (no two surfaces
+    meet), and field_sah shares the rays and the answers."""
+    A = pkg._abi
+    s = R.ray_set(pkg, orc, "field")
+    rays, ref, und = s["rays"], s["ref"], s["undecidable"]
+    print(f"field: {len(rays)} rays, {int(ref['hit'].sum())} hits, {int(und.sum())} undecidable at R = {R.R_ULPS} ulps")
+    assert 2000 <= len(rays) <= 4000 and rays.dtype == pkg.RAY_DTYPE
+    assert und.mean() <= 0.01, f"{und.mean():.4f} of the rays are undecidable"
+    dec = ~und
+    d = rays["d"]
+    octant = (d[:, 0] < 0) * 1 + (d[:, 1] < 0) * 2 + (d[:, 2] < 0) * 4
+    per_octant = np.bincount(octant[dec], minlength=8)
+    print("decidable rays per direction octant:", per_octant.tolist())
+    assert per_octant.min() >= 50
+    hit = ref["hit"] & dec
+    assert (s["on"][hit].sum(axis=1) == 1).all(), "a hit point lies on no primitive, or on two"
+    kind = np.array([s["built"].desc.hittables[int(i)].kind for i in s["ids"]])
+    for k in (A.RT_HIT_SPHERE, A.RT_HIT_TRIANGLE, A.RT_HIT_BOX, A.RT_HIT_XZ_RECT):
+        n = int((s["on"][:, kind == k].any(axis=1) & hit).sum())
+        print(f"hits on primitives of kind {k}: {n}")
+        assert n >= 20, k
+    assert (~ref["hit"] & dec).sum() >= 100
+    t = R.ray_set(pkg, orc, "field_sah")
+    assert t["rays"] is rays and t["ref"] is ref and t["built"].desc.bvh_builder == A.RT_BVH_SAH and s["built"].desc.bvh_builder == A.RT_BVH_REFERENCE
+
+
+def test_field_f32_checker_figures(pkg, orc):
+    """rays.MEASURED_F32_CHECKER["field"], which bounds the device (x 2), is what the checker's f32 instance measures against its f64
+    answers here — within 1 % (libm builds differ in the last place) — and the two instances agree on hit / miss and front_face for every
+    decidable ray."""
+    worst, at, a = R.f32_checker_figures(pkg, orc, "field")
+    s = R.ray_set(pkg, orc, "field")
+    dec = ~s["undecidable"]
+    print("f32 checker against f64 checker:", {k: f"{v:.3e} (ray {at[k]})" for k, v in worst.items()})
+    assert not (dec & (a["hit"] != s["ref"]["hit"])).any() and not (dec & a["hit"] & (a["ff"] != s["ref"]["ff"])).any()
+    for k, v in R.MEASURED_F32_CHECKER["field"].items():
+        assert abs(worst[k] - v) <= 0.01 * v, (k, worst[k], v)
