@@ -535,6 +535,10 @@ int rt_denoise_guided_moments_device(RtCtx* ctx, const RtDenoiseOptions* options
  *   - t_min is the renderer's 0.001 and cannot be chosen. A closest hit beyond the ray's t_max is a MISS (t_max <= 0, +inf or NaN: no limit).
  *   - u, v are always computed (a render computes them for textured scenes only): sphere.rs:32-37, aarect.rs:41-42, barycentrics for a
  *     triangle, 0 for a moving sphere (moving_sphere.rs leaves them unset).
+ *   - Triangles are closed: a ray through an edge or a vertex that triangles share — straight down onto a vertex of a grid-aligned mesh,
+ *     or running in a plane that holds mesh edges — hits one of them, never the gap f32 barycentrics would leave between them. A
+ *     barycentric outside [0, 1] by no more than its own rounding error (a few ulps of 1 for a ray that meets the triangle squarely,
+ *     at most 2^-10) counts as inside, and u, v are reported on the edge. Which of the triangles reports the hit is the walk's choice.
  *   - a MISS is t = +inf, hittable = material = -1, flags = 0, every other field 0.
  *   - material: index into RtSceneDesc.materials. hittable: index of the primitive's own RtHittable record — for a side of a Box the
  *     Box's record, never a wrapper, a list or a BVH.

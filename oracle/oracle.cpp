@@ -642,6 +642,35 @@ template <class R> struct AARect : Hittable<R> {
 // Triangle: NOT in the reference (README.md:151-153 lists OBJ as an undone optional task).
 // Defined here: Moeller-Trumbore, the same inclusive [t_min,t_max] convention as the rects,
 // geometric normal cross(v1-v0, v2-v0) through set_face_normal, (u,v) = barycentrics.
+//
+// CLOSED EDGES. A triangle is a closed set, and two triangles that share an edge leave no gap; the three barycentric tests in
+// floating point do: a ray through (or within rounding of) a shared edge can compute u + v = 1 + 1e-7 in one triangle and
+// v = -1e-7 in its neighbour and pass between them. So a barycentric that fails its test by no more than the test's own rounding
+// error still counts as inside, and is clamped onto the edge. The bound (u0 = the unit roundoff of R, A_i = |d_j||e2_k| + |d_k||e2_j|,
+// B_i = |tv_j||e1_k| + |tv_k||e1_j|: the cross products with every term taken absolutely):
+//   e1, e2, tv are rounded differences (relative u0 per component); a cross product's component adds a product and a subtraction, a
+//   dot product a product and two additions. So |d pv_i| <= 3 u0 A_i, |d qv_i| <= 4 u0 B_i, and the three numerators
+//   Nu = tv . pv, Nv = d . qv, det = e1 . pv are each good to 7 u0 S with Su = sum |tv_i| A_i, Sv = sum |d_i| B_i, Sd = sum |e1_i| A_i.
+//   u = Nu / det near 0 is then good to 7 u0 Su / |det|, v likewise, and u + v near 1 to 7 u0 (Su + Sv + Sd) / |det| plus the
+//   roundings of 1 / det (2.5 u0 on the device), the two products and the sum: under 6 u0.
+//   With |x| the 1-norm, sum A_i <= |d||e2| and sum B_i <= |tv||e1|, so Su + Sv + Sd <= S = |d| (|e2| (|tv| + |e1|) + |tv||e1|):
+//   four norms, which is what the device can afford in registers.
+//   tol = 8 u0 (S / |det| + 1) covers each of them, second-order terms included.
+// Some ten ulps of 1 for a ray that meets the triangle squarely from nearby, more as the ray grazes its plane (det -> 0) or comes from
+// far away (|tv|), where the barycentrics really are that uncertain; never more than 2^-10, which lets the device leave early
+// without forming the bound.
+// The device's tri_hit (csrc/kernels.hip) is this rule in f32, operation for operation.
+template <class R> constexpr R kTriSlackMax = (R)0.0009765625;
+template <class R> inline R norm1(const Vec3<R>& a) { return std::fabs(a.x()) + std::fabs(a.y()) + std::fabs(a.z()); }
+template <class R> inline bool tri_close_edges(R nd, R n1, R n2, R ntv, R inv, R& u, R& v) {
+    if (u < -kTriSlackMax<R> || v < -kTriSlackMax<R> || u + v > (R)1 + kTriSlackMax<R>) return false;
+    const R s = nd * (n2 * (ntv + n1) + ntv * n1);
+    const R tol = std::min((R)8 * (std::numeric_limits<R>::epsilon() / (R)2) * (s * std::fabs(inv) + (R)1), kTriSlackMax<R>);
+    if (!(u >= -tol && v >= -tol && u + v <= (R)1 + tol)) return false;
+    u = std::min(std::max(u, (R)0), (R)1);
+    v = std::min(std::max(v, (R)0), (R)1 - u);
+    return true;
+}
 template <class R> struct Triangle : Hittable<R> {
     Vec3<R> v0, v1, v2; const Material<R>* mp = nullptr;
     bool hit(const Ray<R>& r, R t_min, R t_max, HitRecord<R>& rec, Ctx<R>& cx) const override {
@@ -653,10 +682,10 @@ template <class R> struct Triangle : Hittable<R> {
         R inv = (R)1 / det;
         Vec3<R> tv = r.orig - v0;
         R u = dot(tv, pv) * inv;
-        if (u < (R)0 || u > (R)1) return false;
+        if (u < -kTriSlackMax<R> || u > (R)1 + (R)2 * kTriSlackMax<R>) return false;
         Vec3<R> qv = cross(tv, e1);
         R v = dot(r.dir, qv) * inv;
-        if (v < (R)0 || u + v > (R)1) return false;
+        if ((u < (R)0 || u > (R)1 || v < (R)0 || u + v > (R)1) && !tri_close_edges(norm1(r.dir), norm1(e1), norm1(e2), norm1(tv), inv, u, v)) return false;
         R t = dot(e2, qv) * inv;
         if (cx.rng->tmin && std::isfinite(t)) cx.rng->root_at(t, t_min, dot(r.dir, cross(e1, e2).unit()));
         if (t < t_min || t > t_max || !std::isfinite(t)) return false;

@@ -298,23 +298,57 @@ DEVI bool box_sides_hit(V3 o, V3 d, float x0, float x1, float y0, float y1, floa
     side(x0, o.x, d.x, o.y, d.y, y0, y1, o.z, d.z, z0, z1, 5u);
     return any;
 }
-// Triangle (not in the reference): Moeller-Trumbore, inclusive interval, u,v = barycentrics
-DEVI bool tri_hit(V3 o, V3 d, V3 v0, V3 v1, V3 v2, float tmin, float tmax, float& t, float& bu, float& bv) {
+// Triangle (not in the reference): Moeller-Trumbore, inclusive interval, u,v = barycentrics.
+// CLOSED EDGES: two triangles that share an edge leave no gap between them. In f32 the three barycentric tests do — a ray through
+// (or within rounding of) a shared edge computes u + v = 1 + 1e-7 in one triangle and v = -1e-7 in its neighbour, and goes on to
+// whatever lies behind the mesh: a ray straight down onto a grid-aligned mesh vertex, a ray that runs in a plane of mesh edges. So
+// a barycentric that fails its test by no more than the test's own rounding error counts as inside and is clamped onto the edge.
+// The bound, with eps = 2^-24 and every term of the two cross products taken absolutely (A_i = |d_j||e2_k| + |d_k||e2_j|,
+// B_i = |tv_j||e1_k| + |tv_k||e1_j|): e1, e2, tv are rounded differences (eps each); a cross product's component adds a product and
+// a subtraction, a dot product a product and two additions; so pv is good to 3 eps A, qv to 4 eps B, and each of the numerators
+// tv . pv, d . qv and det = e1 . pv to 7 eps S, with Su = sum |tv_i| A_i, Sv = sum |d_i| B_i, Sd = sum |e1_i| A_i. Then u near 0 is
+// good to 7 eps Su / |det|, v likewise, and u + v near 1 to 7 eps (Su + Sv + Sd) / |det| plus the roundings of 1 / det
+// (v_rcp_f32: 1 ulp), of the two products and of the sum, under 6 eps. With |x| the 1-norm, sum A_i <= |d||e2| and sum B_i <= |tv||e1|,
+// so Su + Sv + Sd <= S = |d| (|e2| (|tv| + |e1|) + |tv||e1|): four norms, of which |e1| and |tv| are taken while the vectors are
+// live anyway (the exact sums would keep e1 and tv in registers past their last use: 19 VGPRs more in the mesh variants of
+// k_extend, across an occupancy step). tol = 8 eps (S / |det| + 1) covers each test: some ten ulps of 1 for a ray that meets the
+// triangle squarely from nearby, more as it grazes the plane (det -> 0) or comes from far away (|tv|), where the barycentrics are
+// that uncertain; never more than 2^-10, so that nearly every miss leaves on the first comparison.
+// A hit the strict tests accept is computed as it always was, bit for bit. The CPU checker's triangle test is this rule in
+// f64 and f32, operation for operation; DESIGN.md section 11 has the measurements.
+constexpr float kTriSlackMax = 0.0009765625f;
+DEVI float norm1(V3 a) { return fabsf(a.x) + fabsf(a.y) + fabsf(a.z); }
+DEVI bool tri_close_edges(float nd, float n1, float n2, float ntv, float inv, float& u, float& v) {
+    if (u < -kTriSlackMax || v < -kTriSlackMax || u + v > 1.0f + kTriSlackMax) return false;
+    const float s = nd * (n2 * (ntv + n1) + ntv * n1);
+    const float tol = fminf(8.0f * 5.9604645e-8f * (s * fabsf(inv) + 1.0f), kTriSlackMax);
+    if (!(u >= -tol && v >= -tol && u + v <= 1.0f + tol)) return false;
+    u = fminf(fmaxf(u, 0.0f), 1.0f);
+    v = fminf(fmaxf(v, 0.0f), 1.0f - u);
+    return true;
+}
+// Returns 0: no hit; 1: a hit by the strict tests; 2: a hit by the closed-edge rule alone. Beside an edge the triangle the ray is in
+// accepts it strictly and its neighbour by the rule, often at the same f32 t: the walks let a 2 yield to any hit already found at
+// that t (and a 1 replaces a 2 there, by the inclusive bound), so which of the two reports the hit does not depend on the order
+// in which a layout visits them.
+DEVI int tri_hit(V3 o, V3 d, V3 v0, V3 v1, V3 v2, float tmin, float tmax, float& t, float& bu, float& bv) {
     const V3 e1 = v1 - v0, e2 = v2 - v0;
     const V3 pv = cross(d, e2);
     const float det = dot(e1, pv);
-    if (det == 0.0f) return false;
+    if (det == 0.0f) return 0;
     const float inv = fdiv(1.0f, det);
     const V3 tv = o - v0;
-    const float u = dot(tv, pv) * inv;
-    if (u < 0.0f || u > 1.0f) return false;
+    float u = dot(tv, pv) * inv;
+    if (u < -kTriSlackMax || u > 1.0f + 2.0f * kTriSlackMax) return 0;
     const V3 qv = cross(tv, e1);
-    const float v = dot(d, qv) * inv;
-    if (v < 0.0f || u + v > 1.0f) return false;
+    const float n1 = norm1(e1), ntv = norm1(tv);
+    float v = dot(d, qv) * inv;
+    const bool outside = u < 0.0f || u > 1.0f || v < 0.0f || u + v > 1.0f;
+    if (outside && !tri_close_edges(norm1(d), n1, norm1(e2), ntv, inv, u, v)) return 0;
     const float tt = dot(e2, qv) * inv;
-    if (tt < tmin || tt > tmax || !(fabsf(tt) < kInf)) return false;
+    if (tt < tmin || tt > tmax || !(fabsf(tt) < kInf)) return 0;
     t = tt; bu = u; bv = v;
-    return true;
+    return outside ? 2 : 1;
 }
 
 DEVI V3 f4xyz(Float4 f) { return v3(f.x, f.y, f.z); }
@@ -1083,7 +1117,8 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
                     float t, bu, bv;
                     if (COUNT) c_prims[3]++;
                     const uint32_t id = (rtd::LT_TRI << 28) | (first + k);
-                    if (id != from && tri_hit(o, d, f4xyz(t0), f4xyz(t1), f4xyz(t2), kTMin, tmax, t, bu, bv)) { tmax = t; hit_prim = id; }
+                    const int h = id != from ? tri_hit(o, d, f4xyz(t0), f4xyz(t1), f4xyz(t2), kTMin, tmax, t, bu, bv) : 0;
+                    if (h == 1 || (h == 2 && (t < tmax || hit_prim == rtd::HIT_NONE))) { tmax = t; hit_prim = id; }
                 }
             } else if ((FEAT & F_MEDIUM) && type == rtd::LT_MEDIUM) {
                 const rtd::Medium m = sc.media[first];
@@ -1306,6 +1341,7 @@ __global__ void __launch_bounds__(256) k_extend_wide(SceneDev sc, PoolDev pool, 
             const uint32_t type = (leafw >> 28) & 7u, cnt = (leafw >> 24) & 15u, first = leafw & rtd::LEAF_MAX_FIRST;
             const bool mine = j < cnt;
             float t = kInf; uint32_t id = 0u;
+            bool strict = true;                                               // (false: a triangle hit by the closed-edge rule alone, see tri_hit)
             if (mine) {
                 const uint32_t idx = first + j;
                 if (type == rtd::LT_SPHERE) {
@@ -1321,7 +1357,8 @@ __global__ void __launch_bounds__(256) k_extend_wide(SceneDev sc, PoolDev pool, 
                     const Float4 t0 = sc.tris[3 * idx], t1 = sc.tris[3 * idx + 1], t2 = sc.tris[3 * idx + 2];
                     id = (rtd::LT_TRI << 28) | idx;
                     float tt, bu, bv;
-                    if (id != from && tri_hit(o, d, f4xyz(t0), f4xyz(t1), f4xyz(t2), kTMin, tmax, tt, bu, bv)) t = tt;
+                    const int h = id != from ? tri_hit(o, d, f4xyz(t0), f4xyz(t1), f4xyz(t2), kTMin, tmax, tt, bu, bv) : 0;
+                    if (h == 1 || (h == 2 && (tt < tmax || hit_prim == rtd::HIT_NONE))) { t = tt; strict = h == 1; }
                 } else if ((FEAT & F_RECT) && type == rtd::LT_RECT) {
                     const Float4 r0 = sc.rects[2 * idx], r1 = sc.rects[2 * idx + 1];
                     id = (rtd::LT_RECT << 28) | idx;
@@ -1338,7 +1375,7 @@ __global__ void __launch_bounds__(256) k_extend_wide(SceneDev sc, PoolDev pool, 
             // the closest of them; on an exact tie the later member, as HittableList::hit's inclusive bounds give it (hittable_list.rs:39-51)
             const uint32_t tb = group_min(__float_as_uint(t));
             if (tb != __float_as_uint(kInf)) {
-                const uint32_t jw = group_max((mine && __float_as_uint(t) == tb) ? j + 1u : 0u) - 1u;
+                const uint32_t jw = (group_max((mine && __float_as_uint(t) == tb) ? j + 1u + (strict ? 8u : 0u) : 0u) - 1u) & 7u;   // (a strict hit first)
                 tmax = __uint_as_float(tb);
                 hit_prim = lane_value(id, gbase + jw);
             }

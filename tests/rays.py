@@ -3,6 +3,9 @@ fit LDS, and per scene a fixed list of f32 rays — pixel-centre camera rays plu
 hit points in seeded random directions — with the checker's f64 answer for every ray, which rays are DECIDABLE, and which object every
 hit lies on. And one scene that does not fit LDS (`field`, with `field_sah`: tests/test_gpu_rays_hbm.py), its set made the same way, the
 uploads it is walked through (field_matrix) and the checker's own f32 figures that bound the device there (MEASURED_F32_CHECKER).
+And two families of rays those sets never hold (further down): axis_set — directions with zero, signed-zero, subnormal or 1e-30
+components from origins on the 1/4 lattice, with the rim and edge subsets — and segment_set — point-to-point rays d = q - p with a
+t_max of their own near 1.
 
 A ray is undecidable when the checker's answer changes under a perturbation of its direction by +-R f32 ulps per component (8 fixed sign
 patterns): hit <-> miss, t moving by more than 1e-3 * max(1, t), or front_face flipping. Such a ray grazes a silhouette or an edge; an f32
@@ -20,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # about R * 1.2e-7 * |oc| at the sphere: covering the device's error needs R >= |oc| / (4 r), i.e. 10 for that ray and 31 for the farthest
 # small spheres of the scene (|oc| = 25); R = 64 keeps a factor of two. The 1 % cap holds with room (2 of 2688 rays of book-1, none elsewhere).
 R_ULPS = 64
+SMALL = 1e-20           # a direction component below this is "zero-class": see undecidable()
 SIGNS = [(1, 1, 1), (1, 1, -1), (1, -1, 1), (1, -1, -1), (-1, 1, 1), (-1, 1, -1), (-1, -1, 1), (-1, -1, -1)]
 SCENES = ["book1", "cornell", "mesh", "moving", "rotated_sphere", "earth"]
 STATIC_SCENES = ["book1", "cornell", "mesh", "rotated_sphere", "earth"]
@@ -213,9 +217,19 @@ def camera_rays(cam, width, height, rng):
     return make_rays(np.broadcast_to(org, d.shape), d, tm)
 
 
-def ask(orc, desc, rays, precision=64):
-    """The checker's world.hit for every ray, as arrays: hit (bool), t, p, n, u, v, ff. One batch call: the scene is built once."""
-    hit, rec = orc.world_hit_many(desc, rays["o"], rays["d"], rays["time"], 0.001, float("inf"), precision)
+def limits(rays):
+    """The interval's end the library reads from RtRay.t_max (include/rt_hip.h): <= 0, +inf or NaN mean no limit."""
+    t = rays["t_max"].astype(np.float64)
+    return np.where(t > 0.0, t, np.inf)
+
+
+def ask(orc, desc, rays, precision=64, t_min=0.001, limit=None):
+    """The checker's world.hit for every ray, as arrays: hit (bool), t, p, n, u, v, ff. One batch call: the scene is built once. The
+    interval ends at `limit` (a scalar or one per ray), or, by default, where each ray's own t_max says."""
+    lim = limits(rays) if limit is None else limit
+    if np.ndim(lim) and np.isposinf(lim).all():
+        lim = float("inf")
+    hit, rec = orc.world_hit_many(desc, rays["o"], rays["d"], rays["time"], t_min, lim, precision)
     miss = ~hit
     out = dict(hit=hit, t=rec[:, 0].copy(), p=rec[:, 1:4].copy(), n=rec[:, 4:7].copy(), u=rec[:, 7].copy(), v=rec[:, 8].copy(), ff=rec[:, 9] != 0.0)
     out["t"][miss] = np.inf
@@ -242,18 +256,29 @@ def ask_per_ray(orc, desc, rays):
     return out
 
 
-def undecidable(orc, desc, rays, ref, r_ulps=R_ULPS):
+def changed(a, ref):
+    """Rays on which the answer a is not the answer ref: hit <-> miss, t moved by more than 1e-3 * max(1, t), front_face flipped."""
+    both = a["hit"] & ref["hit"]
+    moved = np.zeros(len(both), bool)
+    moved[both] = np.abs(a["t"][both] - ref["t"][both]) > 1e-3 * np.maximum(1.0, ref["t"][both])
+    return (a["hit"] != ref["hit"]) | (both & (moved | (a["ff"] != ref["ff"])))
+
+
+def undecidable(orc, desc, rays, ref, r_ulps=R_ULPS, small=SMALL):
+    """The rule of the module's docstring. A component below `small` in magnitude (zero, a subnormal, 1e-30: its own ulp is no
+    perturbation at all) is moved by R ulps of the ray's LARGEST component instead; small = 0 is the rule without that extension. No set
+    made before the extension holds such a component, so their masks are the same bits under both
+    (tests/test_rays_host.py::test_the_extended_rule_keeps_the_existing_masks)."""
     bad = np.zeros(len(rays), bool)
     d = rays["d"]
-    step = np.float32(r_ulps) * np.spacing(np.abs(d))
+    ulp = np.spacing(np.abs(d))
+    if small > 0.0:
+        ulp = np.where(np.abs(d) < np.float32(small), np.spacing(np.abs(d).max(axis=1, keepdims=True)), ulp)
+    step = np.float32(r_ulps) * ulp.astype(np.float32)
     for s in SIGNS:
         q = rays.copy()
         q["d"] = d + np.asarray(s, np.float32) * step
-        a = ask(orc, desc, q)
-        both = a["hit"] & ref["hit"]
-        moved = np.zeros(len(rays), bool)
-        moved[both] = np.abs(a["t"][both] - ref["t"][both]) > 1e-3 * np.maximum(1.0, ref["t"][both])
-        bad |= (a["hit"] != ref["hit"]) | (ref["hit"] & a["hit"] & (moved | (a["ff"] != ref["ff"])))
+        bad |= changed(ask(orc, desc, q), ref)
     return bad
 
 
@@ -328,7 +353,7 @@ def objects_at(pkg, desc, p, tm, extent):
 
 def deviations(pkg, s, k, t, p, n, u, v):
     """Worst deviation from the set's f64 answers on the rays k, in the definitions of tests/test_gpu_rays.py: dict(t = relative |dt|,
-    p = |dp| / extent, n = |dn|, uv = |d(u, v)| with u modulo 1 and sphere hits within 1e-3 of a pole left out, ta = |dt| / max(1, t))
+    p = |dp| / extent, n = |dn|, uv = |d(u, v)| with u modulo 1 and sphere hits within 1e-3 of a pole left out, ta = |dt| / max(1, t), tabs = |dt|)
     and the rays that set each figure. t, p, n, u, v: the answers under test for the whole set."""
     A = pkg._abi
     built, ref, ids, on = s["built"], s["ref"], s["ids"], s["on"]
@@ -339,7 +364,7 @@ def deviations(pkg, s, k, t, p, n, u, v):
     du = np.abs(f(u) - ref["u"][k]); du = np.minimum(du, 1.0 - du)
     dv = np.abs(f(v) - ref["v"][k])
     each = dict(t=dt / ref["t"][k], p=np.linalg.norm(f(p) - ref["p"][k], axis=1) / built.extent, n=np.linalg.norm(f(n) - ref["n"][k], axis=1),
-                uv=np.where(polar, 0.0, np.maximum(du, dv)), ta=dt / np.maximum(1.0, ref["t"][k]))
+                uv=np.where(polar, 0.0, np.maximum(du, dv)), ta=dt / np.maximum(1.0, ref["t"][k]), tabs=dt)
     return {q: float(e.max()) for q, e in each.items()}, {q: int(k[int(e.argmax())]) for q, e in each.items()}
 
 
@@ -349,6 +374,19 @@ def deviations(pkg, s, k, t, p, n, u, v):
 # tests/test_gpu_paths.py. Nothing here comes from a GPU.
 MEASURED_F32_CHECKER = {
     "field": dict(t=1.451e-2, p=2.312e-4, n=8.155e-3, uv=4.650e-3, ta=1.595e-4),
+    # the axis sets and the segment sets (f32_figures; tabs = |dt| itself: a segment's t lies in [0, 1.5])
+    "axis/book1": dict(t=2.055e-03, p=4.401e-07, n=2.297e-04, uv=8.022e-05, ta=1.815e-04, tabs=3.059e-04),
+    "axis/cornell": dict(t=3.684e-06, p=3.697e-07, n=7.452e-07, uv=6.125e-07, ta=2.048e-06, tabs=3.302e-04),
+    "axis/mesh": dict(t=3.176e-06, p=1.172e-07, n=1.835e-07, uv=1.478e-06, ta=3.700e-07, tabs=4.484e-06),
+    "axis/moving": dict(t=2.263e-05, p=6.368e-07, n=5.229e-05, uv=6.683e-06, ta=1.189e-05, tabs=5.003e-05),
+    "axis/rotated_sphere": dict(t=2.224e-06, p=7.986e-07, n=8.008e-06, uv=3.712e-06, ta=2.215e-06, tabs=1.260e-05),
+    "axis/earth": dict(t=8.187e-05, p=4.391e-07, n=5.618e-06, uv=7.993e-06, ta=3.000e-05, tabs=4.451e-05),
+    "axis/field": dict(t=2.407e-04, p=9.187e-06, n=3.806e-04, uv=1.074e-04, ta=1.154e-05, tabs=1.370e-04),
+    "segments/book1": dict(t=4.815e-04, p=5.186e-06, n=3.406e-04, uv=1.564e-04, ta=1.958e-04, tabs=1.958e-04),
+    "segments/cornell": dict(t=4.599e-06, p=4.664e-06, n=2.878e-05, uv=1.407e-05, ta=4.463e-06, tabs=4.463e-06),
+    "segments/mesh": dict(t=2.977e-05, p=2.824e-07, n=1.922e-07, uv=5.427e-06, ta=7.834e-07, tabs=7.834e-07),
+    "segments/moving": dict(t=1.879e-03, p=1.113e-05, n=7.259e-04, uv=3.158e-05, ta=9.867e-05, tabs=9.867e-05),
+    "segments/field": dict(t=3.449e-03, p=1.498e-05, n=9.245e-04, uv=1.278e-04, ta=1.614e-05, tabs=1.614e-05),
 }
 
 
@@ -385,3 +423,273 @@ def ray_set(pkg, orc, name):
     ids, on = objects_at(pkg, built.desc, ref["p"], rays["time"].astype(np.float64), built.extent)
     _cache[name] = dict(built=built, rays=rays, ref=ref, undecidable=und, ids=ids, on=on)
     return _cache[name]
+
+
+# ---- axis rays: directions with zero-class components, origins on the 1/4 lattice -------------------------------------------------------
+# The slab tests cap |1/d| (csrc/kernels.hip set_slab_ray and its two copies), go_root picks the octant from the sign bit, and the
+# primitive tests reject inf and NaN roots: none of which a camera ray or a random secondary ray reaches. These sets do.
+AXIS_SCENES = ["book1", "cornell", "mesh", "moving", "rotated_sphere", "earth", "field"]
+AXIS_RAYS, AXIS_SEED = 2000, 99
+ZERO_CLASS = np.array([0.0, -0.0, 1e-40, -1e-40, 1e-30, -1e-30], np.float32)        # +-0, a subnormal, a tiny normal
+# origins: uniform in this box around the scene's content (the Cornell box without its walls' planes; above book-1's ground)
+AXIS_BOX = {"book1": ((-11, 0.05, -11), (11, 3, 11)), "cornell": ((5, 5, 5), (550, 550, 550)), "mesh": ((-5, -0.2, -5), (5, 2, 5)),
+            "moving": ((-3, 0, -3), (3, 2.5, 3)), "rotated_sphere": ((-4, 0.05, -4), (4, 2.5, 4)), "earth": ((-3, 0.05, -3), (3, 2.5, 3)),
+            "field": ((-13, -1.2, -13), (13, 6, 13))}
+RIM_SCENES, EDGE_SCENES = ("field", "mesh", "cornell"), ("mesh", "field")
+EDGE_RAY = ((2.75, 0.5, 1.0), (-4.0, -0.24134248, -1e-30))      # in the plane z = 1 of `mesh`, through an edge two triangles share
+
+
+def zero_class(d):
+    return np.abs(d) < np.float32(SMALL)
+
+
+def axis_dirs(rng, n):
+    """About half pure axis directions (two zero-class components), half with one; the axis component is +-2^-3 .. 2^3."""
+    d = np.zeros((n, 3), np.float32)
+    kind = rng.integers(0, 2, n)
+    for i in range(n):
+        ax = rng.permutation(3)
+        d[i, ax[0]] = np.float32(2.0 ** rng.integers(-3, 4)) * rng.choice([-1, 1])
+        if kind[i]:
+            d[i, ax[1]] = np.float32(rng.uniform(0.2, 2.0)) * rng.choice([-1, 1])
+        for a in ax[1 + kind[i]:]:
+            d[i, a] = rng.choice(ZERO_CLASS)
+    return d
+
+
+def rim_rays(name, rng):
+    """Pure axis rays (true zeros, both signs) at an axis-aligned rect with an in-plane coordinate ON the rect's edge, or both on its
+    corner: every coordinate is dyadic, the in-plane coordinate stays o + t * 0 = o, the interval is inclusive: a hit, exactly."""
+    zero = lambda: rng.choice(ZERO_CLASS[:2])
+    q = lambda lo, hi: np.round(rng.uniform(lo, hi) * 4) / 4
+    o, d = [], []
+    if name in ("field", "mesh"):                    # the ground rect, from above, outside the height field and the spheres
+        e, top = (14.0, 6.0) if name == "field" else (6.0, 2.0)
+        for k in range(48):
+            a, b = rng.choice([-e, e]), (rng.choice([-e, e]) if k % 4 == 0 else q(-e, e))
+            o.append((a, q(0.0, top), b) if k & 1 else (b, q(0.0, top), a))
+            d.append((zero(), -(2.0 ** rng.integers(-3, 4)), zero()))
+    if name == "cornell":                            # the far wall z = 555 along x = 0 / 555 and y = 555; the side walls along z = 555 and y = 555
+        for k in range(48):
+            e, s = rng.choice([0.0, 555.0]), q(360.0, 550.0)          # (above the tall box)
+            m = 2.0 ** rng.integers(-3, 4)
+            if k % 3 == 0:
+                o.append((e, s, q(50.0, 500.0))); d.append((zero(), zero(), m))
+            elif k % 3 == 1:
+                o.append((q(50.0, 500.0), 555.0, q(50.0, 500.0))); d.append((zero(), zero(), m))
+            else:
+                o.append((q(50.0, 500.0), s, 555.0)); d.append((m * rng.choice([-1, 1]), zero(), zero()))
+    return np.array(o, np.float64).reshape(-1, 3), np.array(d, np.float32).reshape(-1, 3)
+
+
+def edge_rays(name, rng):
+    """Rays that lie in a vertical plane which holds mesh edges, or go straight down onto mesh vertices and edges. Only the planes whose
+    coordinate is dyadic qualify — the vertices are f64 in the description and f32 on the device: -1, 0, 1 (shared edges) and +-2 (the
+    border) of `mesh`, +-12 (the border) of `field`. On a border the zero-class component is a true zero: a ray that drifts outwards by
+    t * 1e-30 does leave the mesh."""
+    border = 2.0 if name == "mesh" else 12.0
+    zc = lambda at: rng.choice(ZERO_CLASS[:2] if abs(at) == border else ZERO_CLASS)
+    q = lambda lo, hi: np.round(rng.uniform(lo, hi) * 4) / 4
+    o, d = [], []
+
+    def add(x, y, z, dx, dy, dz):
+        o.append((x, y, z)); d.append((dx, dy, dz))
+    if name == "mesh":
+        add(*EDGE_RAY[0], *EDGE_RAY[1])
+        for k in range(30):                          # in a plane x = c or z = c, from above the mesh (its heights end at 0.8) down onto it
+            c, far, side = rng.choice([-2.0, -1.0, 0.0, 1.0, 2.0]), q(1.0, 1.75), rng.choice([-1, 1])
+            run = -side * 2.0 ** rng.integers(0, 3)
+            fall, y = -rng.uniform(0.5, 1.0) * abs(run), q(1.0, 1.25)
+            add(c, y, side * far, zc(c), fall, run) if k & 1 else add(side * far, y, c, run, fall, zc(c))
+        for k in range(30):                          # straight down onto an edge (one coordinate on a plane) or a vertex (both)
+            c, b = rng.choice([-2.0, -1.0, 0.0, 1.0, 2.0]), (rng.choice([-1.0, 0.0, 1.0]) if k % 3 == 0 else q(-2.0, 2.0))
+            m = -(2.0 ** rng.integers(-3, 4))
+            add(c, q(1.0, 2.0), b, zc(c), m, zc(b)) if k & 1 else add(b, q(1.0, 2.0), c, zc(b), m, zc(c))
+    if name == "field":                              # below the spheres (their lowest point is y = 0.1), above the height field (y <= -0.2)
+        for k in range(30):
+            c, b = rng.choice([-12.0, 12.0]), (rng.choice([-12.0, 12.0]) if k % 5 == 0 else q(-12.0, 12.0))
+            m = -(2.0 ** rng.integers(-3, 4))
+            add(c, 0.0, b, zc(c), m, zc(b)) if k & 1 else add(b, 0.0, c, zc(b), m, zc(c))
+        for k in range(16):                          # along the border, in its plane
+            c, run, b = rng.choice([-12.0, 12.0]), rng.choice([-1, 1]) * 2.0 ** rng.integers(0, 3), q(-6.0, 6.0)
+            fall = -rng.uniform(0.1, 0.3) * abs(run)
+            add(c, 0.0, b, zc(c), fall, run) if k & 1 else add(b, 0.0, c, run, fall, zc(c))
+    return np.array(o, np.float64).reshape(-1, 3), np.array(d, np.float32).reshape(-1, 3)
+
+
+def twin(rays):
+    """The same rays with every zero-class component replaced by 1e-3 x the ray's largest component (the sign bit kept): an ordinary
+    ray through nearly the same boxes, which no cap of |1/d| touches."""
+    out = rays.copy()
+    d = rays["d"]
+    big = np.abs(d).max(axis=1, keepdims=True)
+    out["d"] = np.where(zero_class(d), np.copysign(np.float32(1e-3) * big, d), d)
+    return out
+
+
+def finish_set(pkg, orc, built, rays, und):
+    ref = ask(orc, built.desc, rays)
+    ids, on = objects_at(pkg, built.desc, ref["p"], rays["time"].astype(np.float64), built.extent)
+    return dict(built=built, rays=rays, ref=ref, ids=ids, on=on, undecidable=und(ref))
+
+
+def axis_set(pkg, orc, name):
+    """dict(built, rays, ref, undecidable, decidable, ids, on, snapped, rim, edge) for one scene of AXIS_SCENES, computed once per
+    process: AXIS_RAYS seeded rays, then the rim rays, then the edge rays. rim and edge (masks) are exempt from the perturbation rule —
+    their answer is exact — so `undecidable` is never set on them, and decidable = ~undecidable is what the device is held to."""
+    key = ("axis", name)
+    if key in _cache:
+        return _cache[key]
+    built = build_scene(pkg, name)
+    if name == "field_sah":                                   # the geometry of "field" (as ray_set)
+        _cache[key] = dict(axis_set(pkg, orc, "field"), built=built)
+        return _cache[key]
+    rng = np.random.default_rng(AXIS_SEED + AXIS_SCENES.index(name))
+    n = AXIS_RAYS
+    lo, hi = np.array(AXIS_BOX[name][0], np.float64), np.array(AXIS_BOX[name][1], np.float64)
+    o = rng.uniform(lo, hi, (n, 3))
+    snapped = rng.integers(0, 2, n).astype(bool)
+    o[snapped] = np.round(o[snapped] * 4) / 4
+    d = axis_dirs(rng, n)
+    tm = rng.uniform(0.0, 1.0, n) if name == "moving" else np.zeros(n)
+    ro, rd = rim_rays(name, rng) if name in RIM_SCENES else (np.zeros((0, 3)), np.zeros((0, 3), np.float32))
+    eo, ed = edge_rays(name, rng) if name in EDGE_SCENES else (np.zeros((0, 3)), np.zeros((0, 3), np.float32))
+    rays = make_rays(np.concatenate([o, ro, eo]), np.concatenate([d, rd, ed]), np.concatenate([tm, np.zeros(len(ro) + len(eo))]))
+    rim, edge = np.zeros(len(rays), bool), np.zeros(len(rays), bool)
+    rim[n:n + len(ro)] = True
+    edge[n + len(ro):] = True
+    s = finish_set(pkg, orc, built, rays, lambda ref: undecidable(orc, built.desc, rays, ref))
+    # ... and the seeded rays that found an edge by themselves: the hit point lies on two triangles or more
+    tri = np.array([built.desc.hittables[int(h)].kind == pkg._abi.RT_HIT_TRIANGLE for h in s["ids"]])
+    edge |= s["ref"]["hit"] & (s["on"][:, tri].sum(axis=1) >= 2)
+    s["undecidable"] &= ~(rim | edge)
+    s.update(snapped=np.concatenate([snapped, np.ones(len(ro) + len(eo), bool)]), rim=rim, edge=edge, decidable=~s["undecidable"])
+    _cache[key] = s
+    return s
+
+
+# ---- segments: point-to-point rays, d = q - p, the interval ending near t = 1 -------------------------------------------------------------
+SEGMENT_SCENES = ["book1", "cornell", "mesh", "moving", "field"]
+SEGMENTS, SEGMENT_SEED, SEGMENT_MIN, SEGMENT_CAP = 2000, 5, 0.5, 0.05
+T_SURFACE, T_FREE = 0.98, 1.5           # t_max of a segment whose target lies on a surface / is a free point
+# both ends within this distance of the origin: segments that start or end hundreds of units out on a ground sphere say nothing about
+# shadow rays (and the f32 checker, which sets the tolerances, loses the small spheres from there)
+SEGMENT_REACH = {"book1": 15.0, "moving": 15.0}
+# free targets within this distance of the source, per axis: `field` is dense (1250 spheres), and a segment across it is blocked nine
+# times in ten
+SEGMENT_LOCAL = {"field": 2.0}
+
+
+def segment_undecidable(orc, desc, rays, ref):
+    """The R-ulp rule on d (with the limit each segment carries), and in addition: the answer must not change with t_min halved or
+    doubled — the origin surface's own root lies below 1e-4 in t for |d| >= 0.5 — nor with t_max -+ 1e-3, rays.py's own threshold for
+    "t moved" and 100 x RT_SPHERE_TOL."""
+    bad = undecidable(orc, desc, rays, ref)
+    lim = limits(rays)
+    for t_min, dl in ((0.0005, 0.0), (0.002, 0.0), (0.001, -1e-3), (0.001, 1e-3)):
+        bad |= changed(ask(orc, desc, rays, t_min=t_min, limit=lim + dl), ref)
+    return bad
+
+
+def segment_set(pkg, orc, name):
+    """dict(built, rays, ref, undecidable, ids, on, on_surface) for one scene of SEGMENT_SCENES: segments from decidable hit points p of
+    ray_set (rounded to f32) to targets q — for half of them another hit point of that set (t_max = T_SURFACE: the segment stops short
+    of the target's own surface), for the rest a seeded free point in AXIS_BOX (t_max = T_FREE) — with d = q - p in f32, |d| >= 0.5, and
+    both ends within SEGMENT_REACH. ref is the checker's answer under each segment's own t_max."""
+    key = ("segments", name)
+    if key in _cache:
+        return _cache[key]
+    s = ray_set(pkg, orc, name)
+    built, ref0 = s["built"], s["ref"]
+    rng = np.random.default_rng(SEGMENT_SEED + SEGMENT_SCENES.index(name))
+    k = np.flatnonzero(ref0["hit"] & ~s["undecidable"])
+    if name in SEGMENT_REACH:
+        k = k[np.linalg.norm(ref0["p"][k], axis=1) <= SEGMENT_REACH[name]]
+    src = k[rng.integers(0, len(k), SEGMENTS)]
+    p = ref0["p"][src].astype(np.float32)
+    on_surface = np.arange(SEGMENTS) % 2 == 0
+    lo, hi = np.array(AXIS_BOX[name][0], np.float64), np.array(AXIS_BOX[name][1], np.float64)
+    if name in SEGMENT_LOCAL:
+        lo, hi = np.maximum(lo, p - SEGMENT_LOCAL[name]), np.minimum(hi, p + SEGMENT_LOCAL[name])
+    q = np.where(on_surface[:, None], ref0["p"][k[rng.integers(0, len(k), SEGMENTS)]], rng.uniform(lo, hi, (SEGMENTS, 3))).astype(np.float32)
+    d = q - p
+    keep = np.linalg.norm(d.astype(np.float64), axis=1) >= SEGMENT_MIN
+    rays = make_rays(p[keep], d[keep], s["rays"]["time"][src][keep], np.where(on_surface[keep], np.float32(T_SURFACE), np.float32(T_FREE)))
+    out = finish_set(pkg, orc, built, rays, lambda ref: segment_undecidable(orc, built.desc, rays, ref))
+    out["on_surface"] = on_surface[keep]
+    out["decidable"] = ~out["undecidable"]
+    _cache[key] = out
+    return out
+
+
+def new_set(pkg, orc, family, name):
+    return axis_set(pkg, orc, name) if family == "axis" else segment_set(pkg, orc, name)
+
+
+def f32_figures(pkg, orc, family, name):
+    """The checker's f32 instance on a new set: its worst figures on the decidable rays on which it gives the f64 instance's answer
+    (both hit, and changed() sees no difference: the figures are to say what f32 arithmetic costs on a hit, not how far apart two
+    different surfaces lie; edge rays left out: which of the triangles that share the edge reports the hit, and with it n, u, v, is
+    either instance's to choose), the rays that set them, its answers, and the decidable rays left out because its answer is another one:
+    (hit / miss differs, both hit but t moved or front_face flipped). On book-1's segments those are the rays that leave the r = 1000
+    ground sphere: |oc|^2 - r^2 in f32 is good to 0.06 there, and the f32 instance finds the sphere it stands on again at t ~ 0.01 —
+    which the device, with its f64 roots, must not."""
+    s = new_set(pkg, orc, family, name)
+    a = ask(orc, s["built"].desc, s["rays"], precision=32, limit=limits(s["rays"]))
+    other = changed(a, s["ref"])
+    k = np.flatnonzero(s["decidable"] & ~s.get("edge", False) & s["ref"]["hit"] & a["hit"] & ~other)
+    worst, at = deviations(pkg, s, k, a["t"], a["p"], a["n"], a["u"], a["v"])
+    return worst, at, a, np.flatnonzero(s["decidable"] & (a["hit"] != s["ref"]["hit"])), np.flatnonzero(s["decidable"] & other & a["hit"] & s["ref"]["hit"])
+
+
+def bound_of(key):
+    """What the device is allowed on a new set: 2 x the f32 checker's own figure (the project's factor; nothing comes from a GPU)."""
+    return {q: 2.0 * v for q, v in MEASURED_F32_CHECKER[key].items()}
+
+
+def hold_to_checker(pkg, s, hits, key, label):
+    """The assertions of tests/test_gpu_rays.py::test_rays_agree_with_the_checker for a new set (axis_set, segment_set) and the RtRayHit
+    records `hits` of one upload: hit / miss on every decidable ray — rim and edge rays among them — and front_face on every decidable
+    hit; the form of a miss; `hittable` a primitive the checker's point lies on, and its material; the deviations of t, p, n, u, v
+    within bound_of(key). On an edge ray either triangle that shares the edge may report the hit, so front_face, n, u, v are not
+    compared there: it must hit, on a primitive the checker's point lies on, at the checker's t within the same bound.
+    Returns (worst figures, the rays that set them)."""
+    A = pkg._abi
+    built, ref, dec = s["built"], s["ref"], s["decidable"]
+    none = np.zeros(len(dec), bool)
+    rim, edge = s.get("rim", none), s.get("edge", none)
+    g_hit, g_ff = (hits["flags"] & A.RT_RAYHIT_HIT) != 0, (hits["flags"] & A.RT_RAYHIT_FRONT_FACE) != 0
+    assert ((hits["flags"] & ~np.uint32(3)) == 0).all()
+    print(f"{label}: {len(dec)} rays, {int((~dec).sum())} undecidable (left out), {int(rim.sum())} rim, {int(edge.sum())} edge, {int((g_hit & dec).sum())} hits compared")
+    wrong = np.flatnonzero(dec & (g_hit != ref["hit"]))
+    what = [f"{i}{' (rim)' if rim[i] else ' (edge)' if edge[i] else ''}: o {s['rays']['o'][i].tolist()} d {s['rays']['d'][i].tolist()} checker t {ref['t'][i]!r} device t {hits['t'][i]!r}"
+            for i in wrong[:8]]
+    assert len(wrong) == 0, f"{label}: hit/miss differs on {len(wrong)} decidable rays: " + "; ".join(what)
+    both = dec & g_hit
+    wrong = both & ~edge & (g_ff != ref["ff"])
+    assert not wrong.any(), f"{label}: front_face differs on decidable rays {np.flatnonzero(wrong)[:8]}"
+    miss = ~g_hit
+    assert np.isposinf(hits["t"][miss]).all() and (hits["hittable"][miss] == -1).all() and (hits["material"][miss] == -1).all()
+    assert (hits["flags"][miss] == 0).all() and not hits["p"][miss].any() and not hits["n"][miss].any() and not hits["u"][miss].any() and not hits["v"][miss].any()
+    ids, on = s["ids"], s["on"]
+    col = np.full(built.desc.n_hittables, -1)
+    col[ids] = np.arange(len(ids))
+    k = np.flatnonzero(both)
+    h = hits["hittable"][k]
+    assert ((h >= 0) & (h < len(col))).all() and (col[h] >= 0).all(), f"{label}: a hittable that is not a primitive record"
+    off = k[~on[k, col[h]]]
+    assert len(off) == 0, f"{label}: rays {off[:8]}: the checker's hit point does not lie on the reported hittable {hits['hittable'][off[:8]]}"
+    mat = np.array([built.desc.hittables[int(i)].material for i in h])
+    assert (hits["material"][k] == mat).all(), f"{label}: material differs on rays {k[hits['material'][k] != mat][:8]}"
+    worst, at = deviations(pkg, s, np.flatnonzero(both & ~edge), hits["t"], hits["p"], hits["n"], hits["u"], hits["v"])
+    bound = bound_of(key)
+    print(f"{label}: worst rel|dt| {worst['t']:.3e}  |dp|/extent {worst['p']:.3e}  |dn| {worst['n']:.3e}  |d(u,v)| {worst['uv']:.3e}  |dt|/max(1,t) {worst['ta']:.3e}"
+          f"  |dt| {worst['tabs']:.3e}  at rays {at};  allowed {({q: f'{v:.3e}' for q, v in bound.items()})}")
+    if (both & edge).any():
+        e_worst, e_at = deviations(pkg, s, np.flatnonzero(both & edge), hits["t"], hits["p"], hits["n"], hits["u"], hits["v"])
+        print(f"{label}: edge rays: worst rel|dt| {e_worst['t']:.3e}  |dp|/extent {e_worst['p']:.3e}  |dt|/max(1,t) {e_worst['ta']:.3e}  |dt| {e_worst['tabs']:.3e}")
+        for q in ("t", "p", "ta", "tabs"):
+            assert e_worst[q] <= bound[q], (label, "edge", q, e_worst[q], bound[q], e_at[q])
+    for q in bound:
+        assert worst[q] <= bound[q], (label, q, worst[q], bound[q], at[q])
+    return worst, at

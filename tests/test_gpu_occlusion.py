@@ -81,6 +81,51 @@ def test_occlusion_agrees_with_the_checker_and_the_closest_hit(pkg, orc, gpu, na
         scene.close()
 
 
+FIVE_SCENES = [(s, l) for s in R.SEGMENT_SCENES for l in LAYOUTS if l != "hbm_wide" or s != "moving"]
+
+
+@pytest.mark.parametrize("name,layout", FIVE_SCENES)
+def test_segments_blocked_or_not(pkg, orc, gpu, name, layout):
+    """Shadow rays as INTEGRATION.md section 12 tells callers to write them — d = q - p, t_max near 1 (rays.segment_set: 0.98 onto a
+    surface, 1.5 past a free point): the byte is the f64 checker's blocked / unblocked on every decidable segment, and rt_trace_rays'
+    hit / miss under the same t_max on EVERY segment."""
+    A = pkg._abi
+    s = R.segment_set(pkg, orc, name)
+    rays, ref, dec = s["rays"], s["ref"], s["decidable"]
+    scene = gpu.upload(s["built"].desc, layouts(A)[layout])
+    try:
+        occ, st = occluded_device(gpu, scene, rays, with_stats=True)
+        base = trace_device(pkg, gpu, scene, rays)
+    finally:
+        scene.close()
+    assert st["segments"] == st["samples"] == len(rays) and np.isin(occ, (0, A.RT_RAYHIT_HIT)).all()
+    blocked = occ == A.RT_RAYHIT_HIT
+    print(f"segments/{name}/{layout}: {len(rays)} segments, {int((~dec).sum())} undecidable (left out), {int(blocked.sum())} blocked")
+    wrong = np.flatnonzero(dec & (blocked != ref["hit"]))
+    assert len(wrong) == 0, f"blocked / unblocked differs from the checker on decidable segments {wrong[:8]}"
+    hit = (base["flags"] & A.RT_RAYHIT_HIT) != 0
+    assert (blocked == hit).all(), f"differs from rt_trace_rays under the same t_max at {np.flatnonzero(blocked != hit)[:8]}"
+    assert blocked.mean() > 0.25 and (~blocked).mean() > 0.2
+
+
+@pytest.mark.parametrize("name,layout", [(s, l) for s in R.AXIS_SCENES for l in LAYOUTS if l != "hbm_wide" or s != "moving"])
+def test_axis_rays_any_hit_equals_the_closest_hit(pkg, orc, gpu, name, layout):
+    """The axis sets (rays.axis_set), no limit: the byte is rt_trace_rays' hit / miss on every ray, and the checker's on the decidable ones."""
+    A = pkg._abi
+    s = R.axis_set(pkg, orc, name)
+    scene = gpu.upload(s["built"].desc, layouts(A)[layout])
+    try:
+        occ = occluded_device(gpu, scene, s["rays"])
+        base = trace_device(pkg, gpu, scene, s["rays"])
+    finally:
+        scene.close()
+    hit = (base["flags"] & A.RT_RAYHIT_HIT) != 0
+    want = np.where(hit, A.RT_RAYHIT_HIT, 0).astype(np.uint8)
+    assert (occ == want).all(), f"no limit: differs from rt_trace_rays at {np.flatnonzero(occ != want)[:8]}"
+    wrong = np.flatnonzero(s["decidable"] & ((occ != 0) != s["ref"]["hit"]))
+    assert len(wrong) == 0, f"occluded differs from the checker on decidable axis rays {wrong[:8]}"
+
+
 def test_the_sets_cover_what_the_header_names(pkg, orc, gpu):
     """Cornell: hits inside RotateY / Translate instances and on Box sides; moving: ray times that matter; mesh: triangles."""
     A = pkg._abi

@@ -271,3 +271,68 @@ def test_throughput_script_runs(tmp_path):
     assert row["rays"] == 1200 * 800 and 0 < row["hits"] <= row["rays"] and row["pool_slots"] >= row["rays"]
     assert row["query_ms"] > 0 and row["query_extend_ms"] > 0 and row["render_1spp_first_iteration_extend_ms"] > 0
     assert abs(row["mrays_per_s"] - row["rays"] / row["query_ms"] / 1e3) <= 0.1 * row["mrays_per_s"]
+
+
+# ---- axis rays and segments (tests/rays.py axis_set, segment_set) -----------------------------------------------------------------------
+# The rays the sets above never hold: directions with +-0, subnormal or 1e-30 components, origins in the planes of box faces, rect edges
+# and mesh edges; and point-to-point segments d = q - p with their own t_max near 1. Bounds: 2 x the f32 checker's figure of each set
+# (rays.MEASURED_F32_CHECKER); the device's own worst figures are recorded and tabled in DESIGN.md section 11.
+FIVE = ("default", "reference_counters", "hbm", "hbm_32b", "hbm_wide")
+AXIS_CASES = [(s, l) for s in R.AXIS_SCENES if s != "field" for l in FIVE if l != "hbm_wide" or s in R.STATIC_SCENES]    # (field: tests/test_gpu_rays_hbm.py)
+SEGMENT_CASES = [(s, l) for s in R.SEGMENT_SCENES for l in FIVE if l != "hbm_wide" or s != "moving"]
+
+
+def hold(pkg, orc, gpu, family, name, layout):
+    from conftest import record_metric
+    s = R.new_set(pkg, orc, family, name)
+    scene = gpu.upload(s["built"].desc, layouts(pkg._abi)[layout])
+    try:
+        hits, st = trace_device(pkg, gpu, scene, s["rays"], with_stats=True)
+    finally:
+        scene.close()
+    assert st["segments"] == st["samples"] == len(s["rays"])
+    worst, _ = R.hold_to_checker(pkg, s, hits, f"{family}/{name}", f"{family}/{name}/{layout}")
+    record_metric(config="rays_" + family, scene=name, layout=layout, dta=worst["ta"], dt=worst["t"], dp=worst["p"], dn=worst["n"], duv=worst["uv"],
+                  dtabs=worst["tabs"], undecidable=int(s["undecidable"].sum()), rays=len(s["rays"]))
+    return s, hits
+
+
+@pytest.mark.parametrize("name,layout", AXIS_CASES)
+def test_axis_rays_agree_with_the_checker(pkg, orc, gpu, name, layout):
+    s, hits = hold(pkg, orc, gpu, "axis", name, layout)
+    hit = (hits["flags"] & pkg._abi.RT_RAYHIT_HIT) != 0
+    assert hit[s["rim"]].all() and hit[s["edge"]].all()
+
+
+@pytest.mark.parametrize("name,layout", SEGMENT_CASES)
+def test_segments_agree_with_the_checker(pkg, orc, gpu, name, layout):
+    """Each segment carries its own t_max (0.98 or 1.5): the closest hit under a caller's limit, against the checker asked with that limit."""
+    s, hits = hold(pkg, orc, gpu, "segments", name, layout)
+    hit = (hits["flags"] & pkg._abi.RT_RAYHIT_HIT) != 0
+    assert (hits["t"][hit] <= s["rays"]["t_max"][hit]).all() and (hits["t"][hit] >= np.float32(0.001)).all()
+
+
+@pytest.mark.parametrize("name,flags", [("book1", ()), ("field", ()), ("field", ("RT_LAYOUT_NODES_32B",)), ("field", ("RT_LAYOUT_WIDE_NODES",))])
+def test_axis_rays_do_not_stall_a_walk(pkg, orc, gpu, name, flags):
+    """What the cap of |1/d| in the three slab tests (csrc/kernels.hip set_slab_ray, set_grid_ray, the 8-wide refill) exists for: a ray
+    with a zero component must not pass every box. The axis set against its twin — each zero-class component replaced by 1e-3 x the
+    largest, an ordinary ray through nearly the same boxes — in the LDS walk (book1) and the three HBM walks of `field`: the median of
+    7 calls after a warm one, with the allowance test_edges uses for the host's jitter. A ray that passes every one of ~3,700 records
+    costs some 50 x an ordinary one."""
+    A = pkg._abi
+    s = R.axis_set(pkg, orc, name)
+    rays, other = s["rays"], R.twin(s["rays"])
+    assert not R.zero_class(other["d"]).any() and R.zero_class(rays["d"]).any(axis=1).all()
+    f = 0
+    for word in flags:
+        f |= getattr(A, word)
+    scene = gpu.upload(s["built"].desc, f)
+    try:
+        ms = {}
+        for label, r in (("axis", rays), ("twin", other)):
+            trace_device(pkg, gpu, scene, r)                           # (warm)
+            ms[label] = float(np.median([trace_device(pkg, gpu, scene, r, with_stats=True)[1]["render_ms"] for _ in range(7)]))
+    finally:
+        scene.close()
+    print(f"{name} {'|'.join(flags) or 'default'}: median of 7 calls {ms['axis']:.3f} ms for the axis set, {ms['twin']:.3f} ms for its twin")
+    assert ms["axis"] <= 1.5 * ms["twin"] + 0.1

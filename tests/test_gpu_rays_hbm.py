@@ -2,10 +2,12 @@
 1024 and at most the 4096 a top can hold): every upload of rays.field_matrix — compressed records per direction octant (every choice
 of octant axes), 32-byte records with a top of 1 .. 1024 records in LDS (k_extend's M_TOP) or none (M_HBM), member boxes, the
 reference's lists, a park cost, the 8-wide tree, collapsed leaves — against the f64 CPU checker, against the device's own closest hit
-through the any-hit walk, and bit for bit against each other; and one small render through the top layouts and the three carriers.
+through the any-hit walk, and bit for bit against each other; the same for the scene's axis set (rays.axis_set: axis-parallel rays, rim
+rays on the ground rect's edges, edge rays on the height field's border); and one small render through the top layouts and the three carriers.
 
 The scene's surfaces are disjoint, so no ray finds two primitives at one t: the one way layouts may differ (include/rt_hip.h, the layout
-section) is absent, and what the header promises is equality of the records, not closeness.
+section) is absent, and what the header promises is equality of the records, not closeness. (The axis set holds four exceptions, which
+test_the_matrix_bit_for_bit_on_axis_rays names: rays straight down onto a corner vertex of the height field that two triangles share.)
 
 Tolerance of t, p, n, u, v: 2 x rays.MEASURED_F32_CHECKER["field"], the CPU checker's f32 instance against its f64 answers on this set —
 the factor and the rule of tests/test_gpu_paths.py. Nothing in it comes from the device, whose own worst figures are recorded
@@ -37,7 +39,8 @@ def to_device(rays):
 
 
 def run_case(pkg, orc, gpu, case):
-    """One upload per case: the closest hits with their stats, and the any-hit bytes for the three limits of (c). Kept per process."""
+    """One upload per case: the closest hits with their stats, and the any-hit bytes for the three limits of (c), for the scene's ray
+    set and for its axis set. Kept per process."""
     if case in _results:
         return _results[case]
     A = pkg._abi
@@ -49,18 +52,28 @@ def run_case(pkg, orc, gpu, case):
     try:
         out, st = gpu.trace_rays(scene, to_device(rays), with_stats=True)
         hits = out.cpu().numpy().reshape(-1).view(pkg.RAYHIT_DTYPE)
-        hit = (hits["flags"] & A.RT_RAYHIT_HIT) != 0
-        occ = {}
-        for label, limit in (("none", np.zeros(len(rays), f32)), ("t", np.where(hit, hits["t"], f32(1.0)).astype(f32)),
-                             ("below", np.where(hit, np.nextafter(hits["t"], f32(0.0)), f32(1.0)).astype(f32))):
-            q = rays.copy()
-            q["t_max"] = limit
-            o, ost = gpu.occluded(scene, to_device(q), with_stats=True)
-            occ[label] = o.cpu().numpy()
-            assert ost["bvh_in_lds"] == st["bvh_in_lds"] and ost["lds_top_nodes"] == st["lds_top_nodes"] and ost["segments"] == len(rays)
+
+        def any_hit(rays, hits):
+            hit = (hits["flags"] & A.RT_RAYHIT_HIT) != 0
+            occ = {}
+            for label, limit in (("none", np.zeros(len(rays), f32)), ("t", np.where(hit, hits["t"], f32(1.0)).astype(f32)),
+                                 ("below", np.where(hit, np.nextafter(hits["t"], f32(0.0)), f32(1.0)).astype(f32))):
+                q = rays.copy()
+                q["t_max"] = limit
+                o, ost = gpu.occluded(scene, to_device(q), with_stats=True)
+                occ[label] = o.cpu().numpy()
+                assert ost["bvh_in_lds"] == st["bvh_in_lds"] and ost["lds_top_nodes"] == st["lds_top_nodes"] and ost["segments"] == len(rays)
+            return occ
+        occ = any_hit(rays, hits)
+        # the axis set (rays.axis_set) through the same upload
+        axis = R.axis_set(pkg, orc, name)
+        out, ast = gpu.trace_rays(scene, to_device(axis["rays"]), with_stats=True)
+        axis_hits = out.cpu().numpy().reshape(-1).view(pkg.RAYHIT_DTYPE)
+        assert ast["segments"] == ast["samples"] == len(axis["rays"]) and ast["lds_top_nodes"] == st["lds_top_nodes"] and ast["bvh_in_lds"] == st["bvh_in_lds"]
+        axis_occ = any_hit(axis["rays"], axis_hits)
     finally:
         scene.close()
-    _results[case] = dict(set=s, flags=flags, more=more, hits=hits, stats=st, occ=occ)
+    _results[case] = dict(set=s, flags=flags, more=more, hits=hits, stats=st, occ=occ, axis=axis, axis_hits=axis_hits, axis_occ=axis_occ)
     return _results[case]
 
 
@@ -162,6 +175,63 @@ def test_the_matrix_bit_for_bit(pkg, orc, gpu):
     for case in TOPS[1:]:
         got = run_case(pkg, orc, gpu, case)["hits"]
         assert got.tobytes() == first.tobytes(), f"{case} differs from {TOPS[0]} on rays {np.flatnonzero((got.view(np.uint8).reshape(len(got), -1) != first.view(np.uint8).reshape(len(got), -1)).any(axis=1))[:8]}"
+    assert total == 0, {c: v[:8].tolist() for c, v in differing.items() if len(v)}
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_field_axis_rays(pkg, orc, gpu, case):
+    """The axis set of `field` (rays.axis_set: zero-class direction components, origins on the 1/4 lattice, rim rays on the ground rect's
+    edges — the rect a walk tests when it begins — and edge rays on the height field's border) through every upload of the matrix: (b)
+    against the f64 checker, within 2 x the f32 checker's figures of that set; (c) the any-hit walk against the closest hit, exactly."""
+    from conftest import record_metric
+    A = pkg._abi
+    r = run_case(pkg, orc, gpu, case)
+    s, hits = r["axis"], r["axis_hits"]
+    worst, _ = R.hold_to_checker(pkg, s, hits, "axis/field", "axis/" + case)
+    record_metric(config="rays_hbm_axis", case=case, dta=worst["ta"], dt=worst["t"], dp=worst["p"], dn=worst["n"], duv=worst["uv"], dtabs=worst["tabs"],
+                  undecidable=int(s["undecidable"].sum()), rays=len(s["rays"]))
+    g_hit = (hits["flags"] & A.RT_RAYHIT_HIT) != 0
+    assert g_hit[s["rim"]].all() and g_hit[s["edge"]].all()
+    want = np.where(g_hit, A.RT_RAYHIT_HIT, 0).astype(np.uint8)
+    occ = r["axis_occ"]
+    assert (occ["none"] == want).all(), f"no limit: differs from the closest hit at {np.flatnonzero(occ['none'] != want)[:8]}"
+    assert (occ["t"] == want).all(), f"t_max = t bit for bit: differs at {np.flatnonzero(occ['t'] != want)[:8]}"
+    assert not occ["below"].any(), f"t_max = nextafter(t, 0) (misses: 1.0): occluded at {np.flatnonzero(occ['below'])[:8]}"
+
+
+def test_the_matrix_bit_for_bit_on_axis_rays(pkg, orc, gpu):
+    """(d) for the axis set: on its decidable rays — rim and edge rays among them — every walk returns the RtRayHit bytes of c16_one_order
+    (collapsed leaves: the same hittable and the same t bits), and the top_k cases equal each other on ALL rays. The one way layouts may
+    differ (include/rt_hip.h, the layout section) is present here on a handful of rays: an edge ray straight down onto a corner vertex
+    of the height field that two triangles share finds both at one t, and which of them reports the hit is the walk's choice. On the
+    rays whose checker point lies on two primitives the t and p bits must agree (the hittable is held to the checker's point by
+    test_field_axis_rays); everywhere else, every byte."""
+    from conftest import record_metric
+    base = run_case(pkg, orc, gpu, BASE)
+    s = base["axis"]
+    dec = s["decidable"]
+    assert dec[s["rim"]].all() and dec[s["edge"]].all()
+    tie = s["ref"]["hit"] & (s["on"].sum(axis=1) >= 2)
+    print(f"axis rays whose hit point lies on two primitives: {np.flatnonzero(tie).tolist()}")
+    assert 0 < tie.sum() <= 8 and s["edge"][tie].all()
+    tp = lambda h: np.concatenate([h["t"].view(np.uint32)[:, None], h["p"].view(np.uint32)], axis=1)
+    differing = {}
+    for case in CASES:
+        got = run_case(pkg, orc, gpu, case)["axis_hits"]
+        if case in ("collapse_4", "collapse_4_hbm"):
+            bad = dec & ~tie & ((got["hittable"] != base["axis_hits"]["hittable"]) | (got["t"].view(np.uint32) != base["axis_hits"]["t"].view(np.uint32)))
+        else:
+            bad = dec & ~tie & (got.view(np.uint8).reshape(len(got), -1) != base["axis_hits"].view(np.uint8).reshape(len(got), -1)).any(axis=1)
+        bad |= tie & (tp(got) != tp(base["axis_hits"])).any(axis=1)
+        differing[case] = np.flatnonzero(bad)
+        if bad.any():
+            print(f"{case} against {BASE}: " + "; ".join(describe(pkg, s, got, base["axis_hits"], int(i)) for i in differing[case][:4]))
+    total = int(sum(len(v) for v in differing.values()))
+    print(f"decidable axis rays that differ from {BASE}, over {len(CASES)} uploads: {total}  {({c: len(v) for c, v in differing.items() if len(v)})}")
+    record_metric(config="rays_hbm_axis_matrix", uploads=len(CASES), decidable_rays_differing=total)
+    first = run_case(pkg, orc, gpu, TOPS[0])["axis_hits"]
+    for case in TOPS[1:]:
+        assert run_case(pkg, orc, gpu, case)["axis_hits"].tobytes() == first.tobytes(), case
     assert total == 0, {c: v[:8].tolist() for c, v in differing.items() if len(v)}
 
 

@@ -248,3 +248,112 @@ def test_field_f32_checker_figures(pkg, orc):
     assert not (dec & (a["hit"] != s["ref"]["hit"])).any() and not (dec & a["hit"] & (a["ff"] != s["ref"]["ff"])).any()
     for k, v in R.MEASURED_F32_CHECKER["field"].items():
         assert abs(worst[k] - v) <= 0.01 * v, (k, worst[k], v)
+
+
+# ---- axis rays and segments (rays.axis_set, rays.segment_set): what tests/test_gpu_rays.py, _hbm.py and _occlusion.py rely on ------------
+@pytest.mark.parametrize("name", R.SCENES + ["field"])
+def test_the_extended_rule_keeps_the_existing_masks(pkg, orc, name):
+    """rays.undecidable moves a direction component below 1e-20 by R ulps of the ray's largest component. Each existing set's mask is
+    the same bits with and without the extension (a few camera rays hold such a component: those of a camera that looks along an axis)."""
+    s = R.ray_set(pkg, orc, name)
+    print(f"{name}: {int(R.zero_class(s['rays']['d']).any(axis=1).sum())} rays with a zero-class direction component")
+    old = R.undecidable(orc, s["built"].desc, s["rays"], s["ref"], small=0.0)
+    assert old.dtype == s["undecidable"].dtype and old.tobytes() == s["undecidable"].tobytes()
+
+
+@pytest.mark.parametrize("name", R.AXIS_SCENES)
+def test_axis_sets(pkg, orc, name):
+    """About 2000 seeded rays per scene, half with two zero-class direction components and half with one, every zero-class value and
+    every axis among them, about half of the origins on the 1/4 lattice; at most 1 % undecidable under the extended rule; no ray whose
+    checker t is NaN (an origin in a rect's plane with d parallel to it: the reference's own 0 / 0); and the two named subsets: rim rays
+    hit a rect, edge rays hit a triangle, in the f64 checker and in its f32 instance alike."""
+    A = pkg._abi
+    s = R.axis_set(pkg, orc, name)
+    rays, ref, und, rim, edge = s["rays"], s["ref"], s["undecidable"], s["rim"], s["edge"]
+    d = rays["d"]
+    zc = R.zero_class(d)
+    n_zero = zc.sum(axis=1)
+    print(f"axis/{name}: {len(rays)} rays, {int(ref['hit'].sum())} hits, {int(und.sum())} undecidable at R = {R.R_ULPS} ulps (extended rule), "
+          f"{int(rim.sum())} rim, {int(edge.sum())} edge, {int(s['snapped'].sum())} origins on the 1/4 lattice")
+    assert R.AXIS_RAYS <= len(rays) <= R.AXIS_RAYS + 200 and rays.dtype == pkg.RAY_DTYPE
+    assert und.mean() <= 0.01, f"{name}: {und.mean():.4f} of the axis rays are undecidable"
+    assert not (und & (rim | edge)).any() and (s["decidable"] == ~und).all()
+    assert not np.isnan(ref["t"]).any() and not np.isnan(ref["p"]).any()
+    assert ref["hit"].sum() > len(rays) // 8 and (~ref["hit"]).sum() > len(rays) // 8
+    assert set(np.unique(n_zero)) == {1, 2} and 0.4 < (n_zero == 2).mean() < 0.6
+    bits = d.view(np.uint32)[zc]
+    assert set(np.unique(bits)) == set(R.ZERO_CLASS.view(np.uint32).tolist()), "every zero-class value occurs: +-0, +-1e-40, +-1e-30"
+    for axis in range(3):
+        pure = (n_zero == 2) & ~zc[:, axis]
+        assert (pure & (d[:, axis] > 0)).sum() >= 50 and (pure & (d[:, axis] < 0)).sum() >= 50, axis
+    mag = np.abs(d[~zc & (n_zero == 2)[:, None]])
+    assert mag.min() == 0.125 and mag.max() == 8.0
+    assert 0.4 < s["snapped"][:R.AXIS_RAYS].mean() < 0.6
+    assert (rays["o"][s["snapped"]] * 4 == np.round(rays["o"][s["snapped"]] * 4)).all()
+    if name == "moving":
+        assert np.ptp(rays["time"]) > 0.5
+    hit = ref["hit"] & ~und
+    assert s["on"][hit].any(axis=1).all(), f"{name}: a hit point lies on no object of the description"
+    kind = np.array([s["built"].desc.hittables[int(i)].kind for i in s["ids"]])
+    f32 = R.ask(orc, s["built"].desc, rays, precision=32)
+    assert rim.any() == (name in R.RIM_SCENES) and rim.sum() <= 64 and edge[R.AXIS_RAYS:].any() == (name in R.EDGE_SCENES)
+    if rim.any():
+        rect = np.isin(kind, (A.RT_HIT_XY_RECT, A.RT_HIT_XZ_RECT, A.RT_HIT_YZ_RECT))
+        assert (n_zero[rim] == 2).all() and (d[rim][zc[rim]] == 0.0).all()
+        assert ref["hit"][rim].all() and f32["hit"][rim].all() and s["on"][rim][:, rect].any(axis=1).all()
+    if edge.any():
+        tri = kind == A.RT_HIT_TRIANGLE
+        assert ref["hit"][edge].all() and s["on"][edge][:, tri].any(axis=1).all(), "an edge ray that does not hit a triangle"
+        assert f32["hit"][edge].all() and (np.abs(f32["t"][edge] - ref["t"][edge]) <= 1e-3).all(), "the f32 instance leaks through an edge"
+        assert name != "mesh" or (s["on"][edge][:, tri].sum(axis=1) >= 2).sum() >= 20      # (field: the border, which one triangle owns)
+    if name == "mesh":
+        i = R.AXIS_RAYS + int(rim.sum())
+        assert edge[i] and tuple(rays["o"][i]) == R.EDGE_RAY[0] and tuple(rays["d"][i]) == tuple(np.float32(R.EDGE_RAY[1]))
+        assert abs(ref["t"][i] - 0.2451517) < 1e-6
+
+
+@pytest.mark.parametrize("name", R.SEGMENT_SCENES)
+def test_segment_sets(pkg, orc, name):
+    """About 2000 segments d = q - p per scene with |d| >= 0.5, half of them ending on a surface (t_max = 0.98) and half at a free point
+    (1.5); at most 5 % undecidable (R ulps on d, t_min halved and doubled, t_max -+ 1e-3); blocked and unblocked each more than a quarter."""
+    s = R.segment_set(pkg, orc, name)
+    rays, ref, und = s["rays"], s["ref"], s["undecidable"]
+    length = np.linalg.norm(rays["d"].astype(np.float64), axis=1)
+    print(f"segments/{name}: {len(rays)} segments, |d| {length.min():.2f} .. {length.max():.1f}, {int(ref['hit'].sum())} blocked, "
+          f"{int(und.sum())} undecidable ({und.mean():.4f})")
+    assert 0.9 * R.SEGMENTS <= len(rays) <= R.SEGMENTS and rays.dtype == pkg.RAY_DTYPE and length.min() >= R.SEGMENT_MIN
+    assert und.mean() <= R.SEGMENT_CAP, f"{name}: {und.mean():.4f} of the segments are undecidable"
+    assert set(np.unique(rays["t_max"])) == {np.float32(R.T_SURFACE), np.float32(R.T_FREE)}
+    assert (rays["t_max"] == np.float32(R.T_SURFACE)).tolist() == s["on_surface"].tolist() and 0.45 < s["on_surface"].mean() < 0.55
+    assert ref["hit"].mean() > 0.25 and (~ref["hit"]).mean() > 0.25
+    assert (ref["t"][ref["hit"]] <= R.T_FREE).all() and not np.isnan(ref["t"]).any()
+    hit = ref["hit"] & ~und
+    assert s["on"][hit].any(axis=1).all(), f"{name}: a hit point lies on no object of the description"
+    if name in R.SEGMENT_REACH:
+        o = rays["o"].astype(np.float64)
+        assert np.linalg.norm(o, axis=1).max() <= R.SEGMENT_REACH[name] + 1e-3
+        assert np.linalg.norm((o + rays["d"])[s["on_surface"]], axis=1).max() <= R.SEGMENT_REACH[name] + 1e-3
+    if name == "moving":
+        assert np.ptp(rays["time"]) > 0.5
+
+
+def test_segment_lengths_span_two_decades(pkg, orc):
+    length = np.concatenate([np.linalg.norm(R.segment_set(pkg, orc, n)["rays"]["d"].astype(np.float64), axis=1) for n in R.SEGMENT_SCENES])
+    print(f"|d| over the segment sets: {length.min():.2f} .. {length.max():.1f}")
+    assert length.max() >= 100.0 * length.min()
+
+
+@pytest.mark.parametrize("key", [f"axis/{n}" for n in R.AXIS_SCENES] + [f"segments/{n}" for n in R.SEGMENT_SCENES])
+def test_new_sets_f32_checker_figures(pkg, orc, key):
+    """rays.MEASURED_F32_CHECKER[key], which bounds the device (x 2), is what the checker's f32 instance measures against its f64 answers
+    here, within 1 % (libm builds differ in the last place). Reported, not asserted — the judge of the device is the f64 checker alone —
+    is on how many decidable rays the f32 instance gives another answer; but they are few, so that the figures speak for the set."""
+    family, name = key.split("/")
+    worst, at, a, differs, other = R.f32_figures(pkg, orc, family, name)
+    s = R.new_set(pkg, orc, family, name)
+    print(f"{key}: f32 checker against f64 checker:", {k: f"{v:.3e} (ray {at[k]})" for k, v in worst.items()})
+    print(f"{key}: on {len(differs)} decidable rays the f32 checker's hit / miss is not the f64 checker's; on {len(other)} both hit, elsewhere")
+    assert len(differs) + len(other) <= 0.02 * len(s["rays"])
+    assert set(R.MEASURED_F32_CHECKER[key]) == set(worst)
+    for k, v in R.MEASURED_F32_CHECKER[key].items():
+        assert abs(worst[k] - v) <= 0.01 * v, (k, worst[k], v)
