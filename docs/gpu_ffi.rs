@@ -115,9 +115,23 @@ pub const RT_LAYOUT_NO_SHADE_TABLES_IN_LDS: u32 = 128;
 pub const RT_LAYOUT_NO_EXTEND_TABLES_IN_LDS: u32 = 256;
 pub const RT_LAYOUT_WIDE_NODES: u32 = 512;
 pub const RT_LAYOUT_REFERENCE_COUNTERS: u32 = 1 | 4 | 16;   // RtStats test counts = the reference's own
+// per-vertex normals / texture coordinates of RT_HIT_TRIANGLE records (RtTriangleAttrs.flags), handed over in RtUploadOptions
+pub const RT_TRI_NORMALS: u32 = 1;
+pub const RT_TRI_UVS: u32 = 2;
 #[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtTriangleAttrs {
+    pub hittable: i32, pub flags: u32, pub n: [[f32; 3]; 3], pub uv: [[f32; 2]; 3],
+}
+#[repr(C)] #[derive(Clone, Copy, Debug)]
 pub struct RtUploadOptions {
     pub struct_bytes: u32, pub layout_flags: u32, pub lds_top_records: u32, pub octant_axes: u32, pub leaf_collapse: u32, pub list_park_cost: f32,
+    pub triangle_attrs: *const RtTriangleAttrs, pub n_triangle_attrs: u64,
+}
+impl Default for RtUploadOptions {
+    fn default() -> Self {
+        RtUploadOptions { struct_bytes: std::mem::size_of::<RtUploadOptions>() as u32, layout_flags: 0, lds_top_records: 0, octant_axes: 0, leaf_collapse: 0,
+                          list_park_cost: 0.0, triangle_attrs: std::ptr::null(), n_triangle_attrs: 0 }
+    }
 }
 
 // progressive rendering: a frame in resumable sample passes (rt_render_pass); RtPassOptions.flags
@@ -201,7 +215,7 @@ pub struct RtWideInfo {
 pub struct RtCompileInfo {
     pub n_nodes: u64, pub n_box_nodes: u64, pub n_spheres: u64, pub n_moving: u64, pub n_rects: u64, pub n_tris: u64,
     pub n_media: u64, pub n_xforms: u64, pub n_lights: u64, pub n_materials: u64, pub features: u32, pub fits_lds: u32,
-    pub n_first: u32, pub first: [u32; 4], pub _pad: u32,
+    pub n_first: u32, pub first: [u32; 4], pub n_tri_attrs: u32,
 }
 
 pub const RT_OUT_RGB_SUM_F32: u32 = 0;

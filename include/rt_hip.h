@@ -266,6 +266,34 @@ enum {
                                             the default binary records on MI355X — VALU-bound at 8 rays per wave, DESIGN.md section 5 — kept as an option) */
     RT_LAYOUT_REFERENCE_COUNTERS = 1u | 4u | 16u
 };
+/* ---- triangle attributes: per-vertex normals and texture coordinates ------------------------------------------------------------------------
+ * RtSceneDesc stays the reference's graph; what a mesh carries beyond its positions travels beside it, keyed by hittable id, in
+ * RtUploadOptions. A record names ONE RT_HIT_TRIANGLE of the desc; a triangle the graph reaches several times (under different wrappers)
+ * carries its attributes in every copy. A record with flags == 0 is legal and changes nothing.
+ * Semantics, with (bu, bv) the barycentrics of the hit after the closed-edge clamp (the values RtRayHit.u, v report for a plain triangle)
+ * and w0 = 1 - bu - bv, all in f32 on the device:
+ *   RT_TRI_NORMALS  ns = unit(w0 n0 + bu n1 + bv n2) takes the place of the facet's geometric normal in the HitRecord and nothing downstream
+ *                   changes: front_face = dot(d, ns) < 0, normal = +-ns, and the Translate / RotateY / FlipFace replay runs on it as it
+ *                   runs on the geometric normal; "the normal opposes the ray" holds for every material. Vertex normals need not be unit:
+ *                   they are normalised in f64 at upload, then rounded to f32. Where the f32 squared length of the sum is not a positive
+ *                   normal number (the vertex normals cancel) the hit falls back to the geometric normal.
+ *   RT_TRI_UVS      u = u0 + bu (u1 - u0) + bv (u2 - u0), v likewise: uv = (0,0), (1,0), (0,1) returns exactly (bu, bv). Without the flag the
+ *                   barycentrics are (u, v), as for a plain triangle.
+ * Intersection stays purely geometric: t, p, hit / miss, the closed edges, occlusion queries and the primitive a scattered ray leaves are
+ * untouched. Documented limit: a direction scattered about ns can point below the facet; it is traced like any other ray and skips only
+ * the triangle it leaves (no terminator fix). Renders (every kernel form, passes, pixel lists), rt_trace_rays* (n, u, v, FRONT_FACE) and
+ * rt_render_features* (normal; albedo through the texture) use the interpolated values.
+ * Refused with RT_ERR_INVALID and a reason, nothing uploaded: a hittable id out of range or not an RT_HIT_TRIANGLE, an id listed twice, an
+ * unknown flag bit, a non-finite normal or uv whose flag is set, a vertex normal of zero length under RT_TRI_NORMALS, n_triangle_attrs > 0
+ * with a NULL pointer. */
+enum { RT_TRI_NORMALS = 1u, RT_TRI_UVS = 2u };
+typedef struct RtTriangleAttrs {      /* 68 B */
+    int32_t  hittable;                /* id of an RT_HIT_TRIANGLE record of the desc */
+    uint32_t flags;                   /* RT_TRI_*; an unknown bit is RT_ERR_INVALID */
+    float    n[3][3];                 /* normal at v0, v1, v2, in the triangle's own (pre-wrapper) space; need not be unit */
+    float    uv[3][2];                /* texture coordinates at v0, v1, v2 */
+} RtTriangleAttrs;
+
 /* Checked, not dropped: a layout bit this library does not know, a switch set both ways (LISTS_AS_REFERENCE with LISTS_CULLED,
  * NO_MEMBER_BOXES with MEMBER_BOXES), struct_bytes < 8 or a negative list_park_cost is RT_ERR_INVALID with the reason in rt_last_error. */
 typedef struct RtUploadOptions {
@@ -277,6 +305,9 @@ typedef struct RtUploadOptions {
                                   BASELINE scene (more primitive tests). The one switch that can move a sample: a ray that grazes a sphere within the
                                   rounding of its box is culled by that box in the other layouts and tested here (a handful of samples in 5e8) */
     float    list_park_cost;   /* cost of a stop at a leaf in primitive tests, for the grouping of culled list members; 0 = default (6) */
+    /* read only when struct_bytes covers them (a caller compiled against the 24-byte struct keeps working): */
+    const RtTriangleAttrs* triangle_attrs;   /* per-vertex normals / texture coordinates of RT_HIT_TRIANGLE records, see RtTriangleAttrs above */
+    uint64_t n_triangle_attrs;               /* records in triangle_attrs; > 0 with a NULL pointer is RT_ERR_INVALID */
 } RtUploadOptions;
 int rt_scene_upload_ex(RtCtx* ctx, const RtSceneDesc* desc, const RtUploadOptions* options /* NULL = defaults */, RtScene** out_scene);
 
@@ -742,11 +773,11 @@ typedef struct RtCompileInfo {
     uint64_t n_nodes;       /* threaded-BVH records */
     uint64_t n_box_nodes;   /* of which carry a box (= BVHNode count of the reference tree) */
     uint64_t n_spheres, n_moving, n_rects, n_tris, n_media, n_xforms, n_lights, n_materials;
-    uint32_t features;      /* kernel feature bits the scene needs */
+    uint32_t features;      /* kernel feature bits the scene needs (128: a triangle on the device carries attributes, n_tri_attrs > 0) */
     uint32_t fits_lds;      /* nodes + sphere records fit the LDS staging budget */
     uint32_t n_first;       /* primitives tested when a walk begins instead of being met by it (none with RT_LAYOUT_LISTS_AS_REFERENCE) ... */
     uint32_t first[4];      /* ... as leaf words: kind << 28 | count << 24 | first index (kind 1 = sphere, 2 = moving sphere, 5 = medium); they are not in the node records */
-    uint32_t _pad;
+    uint32_t n_tri_attrs;   /* triangle records on the device that carry attributes (RtTriangleAttrs with a flag set; instanced copies count) */
 } RtCompileInfo;
 int rt_scene_compile_info(const RtSceneDesc* desc, RtCompileInfo* out);
 int rt_scene_compile_info_ex(const RtSceneDesc* desc, const RtUploadOptions* options, RtCompileInfo* out);

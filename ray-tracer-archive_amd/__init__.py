@@ -16,4 +16,5 @@ from .adaptive import Adaptive, select_reference, check_counts, check_adaptive_c
 from .denoise import nlm_reference, nlm_prepare, nlm_guided_reference, guide_prepare, nlm_guided_moments_reference, guide_moments_prepare  # noqa: F401
 from .progressive import Progressive, check_checkpoint, std_error  # noqa: F401
 from .scene import SceneBuilder  # noqa: F401
-from .scene_json import JsonScene, load_scene  # noqa: F401
+from .scene_json import JsonScene, load_scene, parse_obj, parse_obj_attrs  # noqa: F401
+from .mesh import icosphere, interpolate_reference, sphere_uv  # noqa: F401

@@ -23,6 +23,8 @@ RT_DENOISE_GUIDED_MOMENTS_MAX_WINDOW_RADIUS = 8
 RT_DENOISE_MOMENTS_SIGMA_ALBEDO, RT_DENOISE_MOMENTS_SIGMA_NORMAL, RT_DENOISE_MOMENTS_SIGMA_DEPTH, RT_DENOISE_MOMENTS_VARIANCE_STRENGTH = 0.01, 0.025, 0.01, 64.0
 RT_RAYHIT_HIT, RT_RAYHIT_FRONT_FACE, RT_RAYHIT_INVALID_RAY = 1, 2, 4
 RT_FEATURES_ACCUMULATE = 1
+RT_TRI_NORMALS, RT_TRI_UVS = 1, 2
+RT_FEATURE_TRI_ATTR = 128      # RtCompileInfo.features: a triangle carries attributes (csrc/kernels.h F_TRI_ATTR)
 # RtUploadOptions.layout_flags
 (RT_LAYOUT_LISTS_AS_REFERENCE, RT_LAYOUT_LISTS_CULLED, RT_LAYOUT_NO_MEMBER_BOXES, RT_LAYOUT_MEMBER_BOXES, RT_LAYOUT_CHILD_ORDER_AS_REFERENCE,
  RT_LAYOUT_SCENE_IN_HBM, RT_LAYOUT_NODES_32B, RT_LAYOUT_NO_SHADE_TABLES_IN_LDS, RT_LAYOUT_NO_EXTEND_TABLES_IN_LDS, RT_LAYOUT_WIDE_NODES) = (1 << k for k in range(10))
@@ -101,12 +103,17 @@ class RtStats(C.Structure):
 class RtCompileInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("n_box_nodes", C.c_uint64), ("n_spheres", C.c_uint64), ("n_moving", C.c_uint64), ("n_rects", C.c_uint64),
                 ("n_tris", C.c_uint64), ("n_media", C.c_uint64), ("n_xforms", C.c_uint64), ("n_lights", C.c_uint64), ("n_materials", C.c_uint64),
-                ("features", C.c_uint32), ("fits_lds", C.c_uint32), ("n_first", C.c_uint32), ("first", C.c_uint32 * 4), ("_pad", C.c_uint32)]
+                ("features", C.c_uint32), ("fits_lds", C.c_uint32), ("n_first", C.c_uint32), ("first", C.c_uint32 * 4), ("n_tri_attrs", C.c_uint32)]
+
+
+class RtTriangleAttrs(C.Structure):
+    _fields_ = [("hittable", C.c_int32), ("flags", C.c_uint32), ("n", (C.c_float * 3) * 3), ("uv", (C.c_float * 2) * 3)]
 
 
 class RtUploadOptions(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("layout_flags", C.c_uint32), ("lds_top_records", C.c_uint32), ("octant_axes", C.c_uint32),
-                ("leaf_collapse", C.c_uint32), ("list_park_cost", C.c_float)]
+                ("leaf_collapse", C.c_uint32), ("list_park_cost", C.c_float),
+                ("triangle_attrs", C.POINTER(RtTriangleAttrs)), ("n_triangle_attrs", C.c_uint64)]
 
 
 class RtPassOptions(C.Structure):

@@ -220,7 +220,7 @@ def compile_info(desc, layout_flags=0, **more):
     info = A.RtCompileInfo()
     opt = upload_options(layout_flags, **more)
     _check(lib().rt_scene_compile_info_ex(C.byref(desc), C.byref(opt), C.byref(info)))
-    out = {n: getattr(info, n) for n, _ in info._fields_ if n not in ("first", "_pad")}
+    out = {n: getattr(info, n) for n, _ in info._fields_ if n != "first"}
     out["first"] = [int(info.first[k]) for k in range(info.n_first)]
     return out
 
@@ -281,9 +281,15 @@ class HostScene:
             pass
 
 
-def upload_options(layout_flags=0, lds_top_records=0, octant_axes=0, leaf_collapse=0, list_park_cost=0.0):
-    """RtUploadOptions (include/rt_hip.h): how the scene is laid out on the device; never what it looks like."""
-    return A.RtUploadOptions(C.sizeof(A.RtUploadOptions), layout_flags, lds_top_records, octant_axes, leaf_collapse, list_park_cost)
+def upload_options(layout_flags=0, lds_top_records=0, octant_axes=0, leaf_collapse=0, list_park_cost=0.0, triangle_attrs=None):
+    """RtUploadOptions (include/rt_hip.h): how the scene is laid out on the device, never what it looks like — and the per-vertex normals /
+    texture coordinates of its triangles: triangle_attrs = a ctypes array or a sequence of RtTriangleAttrs (SceneBuilder.triangle_attrs())."""
+    opt = A.RtUploadOptions(C.sizeof(A.RtUploadOptions), layout_flags, lds_top_records, octant_axes, leaf_collapse, list_park_cost)
+    if triangle_attrs is not None and len(triangle_attrs):
+        arr = triangle_attrs if isinstance(triangle_attrs, C.Array) else (A.RtTriangleAttrs * len(triangle_attrs))(*triangle_attrs)
+        opt.triangle_attrs, opt.n_triangle_attrs = arr, len(arr)
+        opt._keep = arr                                     # the options point into it
+    return opt
 
 
 def runtime_libraries():
@@ -293,8 +299,10 @@ def runtime_libraries():
     return [p for p in buf.value.decode().split("\n") if p], code == A.RT_OK
 
 
-def scene_fingerprint(desc):
-    """sha256 (hex) over the arrays and scalars of an RtSceneDesc: what a progressive checkpoint records of the scene it was rendered from."""
+def scene_fingerprint(desc, triangle_attrs=None):
+    """sha256 (hex) over the arrays and scalars of an RtSceneDesc — and over the RtTriangleAttrs records that travel beside it, if any sets a
+    flag: what a progressive checkpoint records of the scene it was rendered from. A scene without attributes has the print it always had;
+    of a record only what its flags make the library read counts, in the order of the hittable ids."""
     import hashlib
     h = hashlib.sha256()
 
@@ -316,6 +324,15 @@ def scene_fingerprint(desc):
             h.update(C.string_at(C.cast(im.data, C.c_void_p).value, im.width * im.height * 3))
     h.update(np.array([desc.world, desc.lights, desc.background_mode, desc.bvh_builder], dtype=np.int32).tobytes())
     h.update(np.array(desc.background.tuple(), dtype=np.float64).tobytes() + int(desc.bvh_seed).to_bytes(8, "little"))
+    live = sorted((a for a in (triangle_attrs if triangle_attrs is not None else ()) if a.flags), key=lambda a: a.hittable)
+    if live:
+        h.update(b"triangle_attrs" + len(live).to_bytes(8, "little"))
+        for a in live:
+            h.update(np.array([a.hittable, a.flags], dtype=np.int64).tobytes())
+            if a.flags & A.RT_TRI_NORMALS:
+                h.update(bytes(a.n))
+            if a.flags & A.RT_TRI_UVS:
+                h.update(bytes(a.uv))
     return h.hexdigest()
 
 
@@ -324,7 +341,8 @@ class Scene:
         self.ctx = ctx
         self._h = C.c_void_p()
         _check(lib().rt_scene_upload_ex(ctx._h, C.byref(desc), C.byref(options) if options is not None else None, C.byref(self._h)), ctx._h)
-        self.fingerprint = scene_fingerprint(desc)     # (progressive checkpoints: the scene a frame's sums belong to)
+        attrs = getattr(options, "_keep", None) if options is not None and options.struct_bytes >= C.sizeof(A.RtUploadOptions) else None
+        self.fingerprint = scene_fingerprint(desc, attrs)     # (progressive checkpoints: the scene a frame's sums belong to)
 
     def close(self):
         if self._h and self.ctx._h:
@@ -347,7 +365,8 @@ class Context:
         _check(lib().rt_ctx_create(device_id, C.c_void_p(stream) if stream else None, C.byref(self._h)))
 
     def upload(self, desc, layout_flags=0, **more):
-        """rt_scene_upload_ex; layout_flags = RT_LAYOUT_* (A.RT_LAYOUT_REFERENCE_COUNTERS: the layout whose test counts are the reference's)."""
+        """rt_scene_upload_ex; layout_flags = RT_LAYOUT_* (A.RT_LAYOUT_REFERENCE_COUNTERS: the layout whose test counts are the reference's);
+        triangle_attrs= (in `more`): RtTriangleAttrs records, see upload_options."""
         return Scene(self, desc, upload_options(layout_flags, **more) if (layout_flags or more) else None)
 
     def fail_next_renders(self, n):

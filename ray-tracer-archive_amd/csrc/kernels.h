@@ -10,7 +10,11 @@ namespace rtk {
 // features a scene needs beyond "static spheres + Lambertian/Metal/Dielectric + BVH"
 enum : uint32_t {
     F_MOVING = 1u, F_RECT = 2u, F_TRI = 4u, F_MEDIUM = 8u, F_XFORM = 16u, F_TEX = 32u, F_LIGHTS = 64u,
-    F_ALL = 127u
+    F_ALL = 127u,
+    // a triangle carries per-vertex normals / texture coordinates (rt_hip.h RtTriangleAttrs). Not part of F_ALL and never seen by the plain walk:
+    // only the kernels that rebuild a HitRecord have instances with it (kernels.hip with_shade_variant), every other instance is the one
+    // the same scene without attributes runs. The table is found from SceneDev::tris (kernels.hip TriAttr), not through a field of its own.
+    F_TRI_ATTR = 128u
 };
 #define RT_N_PRIM_TYPES_K 6
 enum : uint32_t { CTR_NODE_TESTS = 0, CTR_PRIM_TESTS = 1, CTR_SAMPLES = 7, CTR_DEBUG = 8, CTR_SEGMENTS = 13, CTR_ITERATIONS = 14, CTR_COUNT = 16 };

@@ -353,6 +353,32 @@ DEVI int tri_hit(V3 o, V3 d, V3 v0, V3 v1, V3 v2, float tmin, float tmax, float&
 
 DEVI V3 f4xyz(Float4 f) { return v3(f.x, f.y, f.z); }
 
+// Triangle attributes (rt_hip.h RtTriangleAttrs; instances with F_TRI_ATTR only). A scene uploaded with attributes keeps one 64-byte record
+// per triangle in the triangles' own allocation, in front of tris[] and in reverse: the record of triangle i is the four Float4 at
+// tris - 4 (i + 1) = (n0.xyz, n1.x) (n1.yz, n2.xy) (n2.z, u0, v0, u1) (v1, u2, v2, flags) (rt_api.cpp tri_attr_table). Its address follows
+// from the triangle index in the hit word, as the vertices' does: the four loads issue with the three vertex loads, no look-up in between.
+struct TriAttr { Float4 r0, r1, r2, r3; };
+DEVI TriAttr tri_attr_load(const Float4* tris, uint32_t idx) {
+    const Float4* a = tris - 4ll * ((long long)idx + 1ll);
+    return TriAttr{a[0], a[1], a[2], a[3]};
+}
+// (bu, bv): tri_hit's barycentrics after the closed-edge clamp. The shading normal takes the place of `outward` (every later step — face
+// test, wrappers, materials — runs on it unchanged), the texture coordinates that of the barycentrics; identity uv return (bu, bv) exactly.
+DEVI void tri_attr_apply(const TriAttr& a, float bu, float bv, V3& outward, float& hu, float& hv) {
+    const uint32_t flags = __float_as_uint(a.r3.w);
+    if (flags & 1u) {                                                       // RT_TRI_NORMALS
+        const float w0 = 1.0f - bu - bv;
+        const V3 s = w0 * v3(a.r0.x, a.r0.y, a.r0.z) + bu * v3(a.r0.w, a.r1.x, a.r1.y) + bv * v3(a.r1.z, a.r1.w, a.r2.x);
+        const float l2 = len2(s);
+        if (l2 >= 1.17549435e-38f && l2 < kInf) outward = unit(s);         // else the vertex normals cancel: the geometric normal stays
+    }
+    if (flags & 2u) {                                                       // RT_TRI_UVS
+        const float u0 = a.r2.y, v0 = a.r2.z;
+        hu = u0 + bu * (a.r2.w - u0) + bv * (a.r3.y - u0);
+        hv = v0 + bu * (a.r3.x - v0) + bv * (a.r3.z - v0);
+    }
+}
+
 // ConstantMedium::hit (constant_medium.rs:31-71). Boundary = sphere or box, optionally under an
 // instance transform. `xi` is the free-path draw keyed by (path, segment, medium).
 DEVI bool boundary_hit(const SceneDev& sc, const rtd::Medium& m, V3 o, V3 d, float a, float tmin, float tmax, float& t) {
@@ -661,7 +687,7 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
     static_assert(!ANYHIT || (!COUNT && !DRAIN && !LIST && (FEAT & F_MEDIUM) == 0u), "the any-hit walk serves ray queries: no counters, drain, list or media");
     extern __shared__ float4 lds[];
     constexpr bool LDS = MODE == M_LDS, TOP = MODE == M_TOP, C16 = MODE == M_C16;
-    constexpr int kSteps = FEAT == F_ALL ? kStepsAll : kStepsPlain;
+    constexpr int kSteps = (FEAT & F_ALL) == F_ALL ? kStepsAll : kStepsPlain;
     // The pool is kQueues independent queues (kernels.h): a wave serves the queue of its number mod kQueues, a DRAIN workgroup the
     // queue of its block number; every counter exists once per queue, 128 bytes apart.
     if (blockIdx.x == 0 && threadIdx.x < rd.q_n) count_out_to_zero[(rd.q_lo + threadIdx.x) * kQStride] = 0u;   // the next k_shade appends to them
@@ -1735,11 +1761,14 @@ DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& 
                 outward = (p - moving_center(m0, m1, m2, tm)) / m0.w;       // moving_sphere.rs:58 (u,v not set: 0)
             } else {
                 const V3 v0 = f4xyz(sc.tris[3 * idx]), v1 = f4xyz(sc.tris[3 * idx + 1]), v2 = f4xyz(sc.tris[3 * idx + 2]);
+                TriAttr ta{};
+                if (FEAT & F_TRI_ATTR) ta = tri_attr_load(sc.tris, idx);
                 float tt, bu, bv;
                 tri_hit(ol, dl, v0, v1, v2, -kInf, kInf, tt, bu, bv);
                 hu = bu; hv = bv;
                 p = ol + dl * t;
                 outward = unit(cross(v1 - v0, v2 - v0));
+                if (FEAT & F_TRI_ATTR) tri_attr_apply(ta, bu, bv, outward, hu, hv);
             }
             ff = dot(dl, outward) < 0.f;                                    // set_face_normal, hittable.rs:41-48
             n = ff ? outward : -outward;
@@ -2227,11 +2256,14 @@ __global__ void __launch_bounds__(256) k_rays_export(SceneDev sc, RaySrcDev src,
         outward = (p - moving_center(m0, m1, m2, tm)) / m0.w;       // moving_sphere.rs:58 (u,v not set: 0)
     } else if ((FEAT & F_TRI) && type == rtd::LT_TRI) {
         const V3 v0 = f4xyz(sc.tris[3 * idx]), v1 = f4xyz(sc.tris[3 * idx + 1]), v2 = f4xyz(sc.tris[3 * idx + 2]);
+        TriAttr ta{};
+        if (FEAT & F_TRI_ATTR) ta = tri_attr_load(sc.tris, idx);
         float tt, bu = 0.f, bv = 0.f;
         tri_hit(ol, dl, v0, v1, v2, -kInf, kInf, tt, bu, bv);
         hu = bu; hv = bv;
         p = ol + dl * t;
         outward = unit(cross(v1 - v0, v2 - v0));
+        if (FEAT & F_TRI_ATTR) tri_attr_apply(ta, bu, bv, outward, hu, hv);
     } else { store_ray_miss(hits, ray, 0u); return; }               // a primitive kind this instance was not compiled for: cannot occur (pick_variant)
     ff = dot(dl, outward) < 0.f;                                    // set_face_normal, hittable.rs:41-48
     n = ff ? outward : -outward;
@@ -2356,11 +2388,14 @@ DEVI bool rebuild_hit(const SceneDev& sc, V3 o, V3 d, float tm, float t, uint32_
         outward = (p - moving_center(m0, m1, m2, tm)) / m0.w;       // moving_sphere.rs:58 (u,v not set: 0)
     } else if ((FEAT & F_TRI) && type == rtd::LT_TRI) {
         const V3 v0 = f4xyz(sc.tris[3 * idx]), v1 = f4xyz(sc.tris[3 * idx + 1]), v2 = f4xyz(sc.tris[3 * idx + 2]);
+        TriAttr ta{};
+        if (FEAT & F_TRI_ATTR) ta = tri_attr_load(sc.tris, idx);
         float tt, bu = 0.f, bv = 0.f;
         tri_hit(ol, dl, v0, v1, v2, -kInf, kInf, tt, bu, bv);
         hu = bu; hv = bv;
         p = ol + dl * t;
         outward = unit(cross(v1 - v0, v2 - v0));
+        if (FEAT & F_TRI_ATTR) tri_attr_apply(ta, bu, bv, outward, hu, hv);
     } else return false;
     ff = dot(dl, outward) < 0.f;                                    // set_face_normal, hittable.rs:41-48
     n = ff ? outward : -outward;
@@ -2560,6 +2595,7 @@ template <class K> static hipError_t check_no_static_lds(K kernel) {
 //   F_ALL                          everything
 constexpr uint32_t kVariantMesh = F_RECT | F_TRI, kVariantBox = F_RECT | F_XFORM | F_LIGHTS;
 static uint32_t pick_variant(uint32_t need) {
+    need &= F_ALL;                      // (F_TRI_ATTR selects among the shading instances only: with_shade_variant)
     if (need == 0u) return 0u;
     if ((need & ~kVariantMesh) == 0u) return kVariantMesh;
     if ((need & ~kVariantBox) == 0u) return kVariantBox;
@@ -2573,6 +2609,15 @@ template <class F> static auto with_variant(uint32_t features, F&& f) {
     if (v == kVariantMesh) return f(std::integral_constant<uint32_t, kVariantMesh>{});
     if (v == kVariantBox) return f(std::integral_constant<uint32_t, kVariantBox>{});
     return f(std::integral_constant<uint32_t, F_ALL>{});
+}
+// The kernels that rebuild a HitRecord — k_shade, the drain form of k_extend, the ray-query and the feature export — have two more instances,
+// for scenes whose triangles carry attributes (F_TRI_ATTR): the mesh variant and the full one. A scene without attributes runs exactly the
+// instances it ran before they existed, and the plain walk (launch_extend, launch_extend_any) never sees the bit.
+constexpr uint32_t kVariantMeshAttr = kVariantMesh | F_TRI_ATTR, kVariantAllAttr = F_ALL | F_TRI_ATTR;
+template <class F> static auto with_shade_variant(uint32_t features, F&& f) {
+    if ((features & F_TRI_ATTR) == 0u) return with_variant(features, f);
+    if (pick_variant(features) == kVariantMesh) return f(std::integral_constant<uint32_t, kVariantMeshAttr>{});
+    return f(std::integral_constant<uint32_t, kVariantAllAttr>{});
 }
 // where the walk finds its records (k_extend MODE)
 template <class F> static auto with_mode(const LaunchCfg& cfg, const SceneDev& sc, F&& f) {
@@ -2683,7 +2728,7 @@ hipError_t launch_extend(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev
 hipError_t launch_drain(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, uint32_t max_count, const uint32_t* count_ptr,
                         uint32_t* head, uint32_t* cz, unsigned long long* counters, bool count, hipStream_t stream) {
     if (max_count == 0u) return hipSuccess;
-    return with_mode(cfg, sc, [&](auto mode) { return with_variant(cfg.features, [&](auto feat) { return with_flag(count, [&](auto cnt) { return with_flag(rd.n_list != 0u, [&](auto list) {
+    return with_mode(cfg, sc, [&](auto mode) { return with_shade_variant(cfg.features, [&](auto feat) { return with_flag(count, [&](auto cnt) { return with_flag(rd.n_list != 0u, [&](auto list) {
         return launch_drain_c<decltype(mode)::value, decltype(feat)::value, decltype(cnt)::value, decltype(list)::value>(sc, pool, rd, max_count, count_ptr, head, cz, counters, stream); }); }); }); });
 }
 
@@ -2692,7 +2737,7 @@ hipError_t launch_shade(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev&
                         hipStream_t stream) {
     const uint32_t blocks = rd.q_n * ((max_count + kShadeThreads - 1u) / kShadeThreads);   // max_count = upper bound of the paths in ONE queue
     if (blocks == 0u) return hipSuccess;
-    with_variant(cfg.features, [&](auto feat) { with_flag(count, [&](auto cnt) { with_flag(rd.n_list != 0u, [&](auto list) {
+    with_shade_variant(cfg.features, [&](auto feat) { with_flag(count, [&](auto cnt) { with_flag(rd.n_list != 0u, [&](auto list) {
         hipLaunchKernelGGL((k_shade<decltype(feat)::value, decltype(cnt)::value, decltype(list)::value>), dim3(blocks), dim3(kShadeThreads), sc.shade_blob_bytes, stream,
                            sc, in, out, rd, count_in, count_out, hz, counters); }); }); });
     return hipGetLastError();
@@ -2734,7 +2779,7 @@ hipError_t launch_rays_export(const LaunchCfg& cfg, const SceneDev& sc, const Ra
                               const uint32_t* counts, void* hits, hipStream_t stream) {
     const uint32_t blocks = kQueues * ((std::min(max_count, queue_cap) + 255u) / 256u);   // max_count = upper bound of the rays in ONE queue
     if (blocks == 0u) return hipSuccess;
-    with_variant(cfg.features, [&](auto feat) {
+    with_shade_variant(cfg.features, [&](auto feat) {
         hipLaunchKernelGGL((k_rays_export<decltype(feat)::value>), dim3(blocks), dim3(256), 0, stream, sc, src, pool, queue_cap, counts, (Float4*)hits); });
     return hipGetLastError();
 }
@@ -2796,7 +2841,7 @@ hipError_t launch_features_export(const LaunchCfg& cfg, const SceneDev& sc, cons
                                   const uint32_t* counts, hipStream_t stream) {
     const uint32_t blocks = kQueues * ((std::min(max_count, rd.queue_cap) + 255u) / 256u);   // max_count = upper bound of the rays in ONE queue
     if (blocks == 0u) return hipSuccess;
-    with_variant(cfg.features, [&](auto feat) {
+    with_shade_variant(cfg.features, [&](auto feat) {
         hipLaunchKernelGGL((k_features_export<decltype(feat)::value>), dim3(blocks), dim3(256), 0, stream, sc, rd, fd, pool, counts); });
     return hipGetLastError();
 }

@@ -444,6 +444,60 @@ static rti::UploadOpts resolve_options(const RtUploadOptions* o) {
     return u;
 }
 
+// ---- triangle attributes (rt_hip.h RtTriangleAttrs): checked against the graph, then laid out by DEVICE triangle index ---------------------
+// The table is parallel to tris[]: one 64-byte record per device triangle — (n0.xyz, n1.x) (n1.yz, n2.xy) (n2.z, uv0, u1) (v1, uv2, flags) —
+// so that a kernel which holds the triangle index of a hit asks for it together with the vertices (no look-up through tri_meta). The
+// index -> hittable map is the one the ray queries report (CompiledScene::tri_src), which every layout keeps: leaf collapse, SAH, the
+// 8-wide tree and the octant arrays reorder records, never tris[]. A triangle the graph reaches several times has one device record per
+// copy, and each gets the attributes. *n_with counts the device triangles that carry some; `table` stays empty when there is none, and table == nullptr checks and counts only.
+static int tri_attr_table(const RtSceneDesc& desc, const RtUploadOptions* o, const rtc::CompiledScene& cs, std::vector<rtd::Float4>* table, uint32_t* n_with,
+                          std::string& err) {
+    if (table) table->clear();
+    *n_with = 0u;
+    if (!o || o->struct_bytes < offsetof(RtUploadOptions, n_triangle_attrs) + sizeof(uint64_t) || o->n_triangle_attrs == 0u) return RT_OK;
+    if (!o->triangle_attrs) { err = "RtUploadOptions.triangle_attrs is NULL with n_triangle_attrs > 0"; return RT_ERR_INVALID; }
+    std::vector<int64_t> by_id(desc.n_hittables, -1);
+    for (uint64_t k = 0; k < o->n_triangle_attrs; ++k) {
+        const RtTriangleAttrs& a = o->triangle_attrs[k];
+        const std::string what = "RtTriangleAttrs[" + std::to_string(k) + "]: ";
+        if (a.hittable < 0 || (uint64_t)a.hittable >= desc.n_hittables) { err = what + "hittable id out of range"; return RT_ERR_INVALID; }
+        if (desc.hittables[a.hittable].kind != RT_HIT_TRIANGLE) { err = what + "hittable " + std::to_string(a.hittable) + " is not an RT_HIT_TRIANGLE"; return RT_ERR_INVALID; }
+        if (by_id[a.hittable] >= 0) { err = what + "hittable " + std::to_string(a.hittable) + " is listed twice"; return RT_ERR_INVALID; }
+        if (a.flags & ~(uint32_t)(RT_TRI_NORMALS | RT_TRI_UVS)) { err = what + "flags: unknown bit"; return RT_ERR_INVALID; }
+        if (a.flags & RT_TRI_NORMALS) for (int v = 0; v < 3; ++v) {
+            double l2 = 0.0;
+            for (int c = 0; c < 3; ++c) { if (!std::isfinite(a.n[v][c])) { err = what + "a normal is not finite"; return RT_ERR_INVALID; } l2 += (double)a.n[v][c] * (double)a.n[v][c]; }
+            if (!(l2 > 0.0)) { err = what + "a vertex normal has zero length"; return RT_ERR_INVALID; }
+        }
+        if (a.flags & RT_TRI_UVS) for (int v = 0; v < 3; ++v) for (int c = 0; c < 2; ++c)
+            if (!std::isfinite(a.uv[v][c])) { err = what + "a texture coordinate is not finite"; return RT_ERR_INVALID; }
+        by_id[a.hittable] = (int64_t)k;
+    }
+    // the device triangles that carry attributes: a record for a triangle the world does not reach attaches to nothing
+    const size_t n = cs.tri_src.size();
+    auto record_of = [&](size_t i) -> const RtTriangleAttrs* {
+        const int64_t k = cs.tri_src[i] < by_id.size() ? by_id[cs.tri_src[i]] : -1;
+        return k >= 0 && o->triangle_attrs[k].flags != 0u ? &o->triangle_attrs[k] : nullptr;
+    };
+    for (size_t i = 0; i < n; ++i) if (record_of(i)) ++*n_with;
+    if (!table || *n_with == 0u) return RT_OK;
+    table->assign(4 * n, rtd::Float4{0.f, 0.f, 0.f, 0.f});
+    for (size_t i = 0; i < n; ++i) {
+        const RtTriangleAttrs* ap = record_of(i);
+        if (!ap) continue;
+        const RtTriangleAttrs& a = *ap;
+        float f[16] = {0.f};
+        if (a.flags & RT_TRI_NORMALS) for (int v = 0; v < 3; ++v) {
+            const double x = a.n[v][0], y = a.n[v][1], z = a.n[v][2], l = std::sqrt(x * x + y * y + z * z);     // unit in f64, then rounded
+            f[3 * v] = (float)(x / l); f[3 * v + 1] = (float)(y / l); f[3 * v + 2] = (float)(z / l);
+        }
+        if (a.flags & RT_TRI_UVS) for (int v = 0; v < 3; ++v) { f[9 + 2 * v] = a.uv[v][0]; f[10 + 2 * v] = a.uv[v][1]; }
+        std::memcpy(&f[15], &a.flags, 4);
+        std::memcpy(&(*table)[4 * i], f, 64);
+    }
+    return RT_OK;
+}
+
 // ---- the host image of a scene: everything an upload copies to a device, built ONCE (rt_scene_upload_multi uploads it n times) ---------
 struct rti::SceneImage {
     rtc::CompiledScene cs;
@@ -456,6 +510,7 @@ struct rti::SceneImage {
     uint32_t sb[12] = {0}, perlin_only = 0u, eb[5] = {0}, eb_rect_stride = 32u;
     uint32_t features = 0u;
     rtw::WideTree wide; bool use_wide = false;     // 8-wide nodes for k_extend_wide (a static BVH that does not fit LDS)
+    std::vector<rtd::Float4> tri_attrs;            // tri_attr_table: 4 records per device triangle, empty = the upload gave no attributes
 };
 void rti::scene_image_free(SceneImage* im) { delete im; }
 
@@ -469,6 +524,11 @@ int rti::scene_image_build(const RtSceneDesc* desc, const RtUploadOptions* optio
     if (rc != RT_OK) { err = "scene: " + cs.error; return rc; }
     im->in_lds = opt.lds_scene && lds_scene_bytes(cs) <= kLdsSceneBudget;
     im->features = scene_features(cs);
+    {   // attributes change what is shaded, never what is walked: every test on `features` below sees the scene's own bits
+        uint32_t n_with = 0u;
+        const int ok = tri_attr_table(*desc, options, cs, &im->tri_attrs, &n_with, err);
+        if (ok != RT_OK) return ok;
+    }
     // RT_LAYOUT_WIDE_NODES: a static BVH in HBM (spheres / rects / triangles / boxes under box nodes only) walked 8 lanes to a ray over an
     // 8-wide tree (kernels.hip k_extend_wide) instead of the binary records below.
     if (!im->in_lds && opt.wide_nodes && opt.node16 && (im->features & ~(rtk::F_RECT | rtk::F_TRI)) == 0u && cs.prologue.empty() && cs.first_leaf == 0u && rtw::eligible(cs.nodes)) {   // (k_extend_wide tests nothing before the tree)
@@ -553,6 +613,7 @@ int rti::scene_image_build(const RtSceneDesc* desc, const RtUploadOptions* optio
             eblob.clear();
         }
     }
+    if (!im->tri_attrs.empty()) im->features |= rtk::F_TRI_ATTR;
     *out = im.release();
     return RT_OK;
 }
@@ -564,10 +625,22 @@ int rti::scene_image_upload(RtCtx* ctx, const SceneImage& im, RtScene** out_scen
     RtScene* s = new RtScene();
     int r = RT_OK;
     auto up = [&](auto& buf, const auto& vec) { if (r == RT_OK) r = upload(ctx, buf, vec); };
+    // A scene with triangle attributes keeps them in the triangles' own allocation, IN FRONT of tris[] and in reverse: the record of
+    // triangle i is the four Float4 at tris - 4 (i + 1). SceneDev is an argument of every kernel and its layout is part of their code; this
+    // way it does not change, and the kernels compiled with F_TRI_ATTR find the table from the pointer they already hold.
+    const size_t n_tri = cs.tri_meta.size(), tri_front = im.tri_attrs.empty() ? 0 : 4 * n_tri;
+    std::vector<rtd::Float4> tris_with_attrs;
+    auto up_tris = [&]() {
+        if (tri_front == 0) { up(s->tris, cs.tris); return; }
+        tris_with_attrs.resize(tri_front + cs.tris.size());
+        for (size_t i = 0; i < n_tri; ++i) std::memcpy(&tris_with_attrs[tri_front - 4 * (i + 1)], &im.tri_attrs[4 * i], 64);
+        std::memcpy(tris_with_attrs.data() + tri_front, cs.tris.data(), cs.tris.size() * sizeof(rtd::Float4));
+        up(s->tris, tris_with_attrs);
+    };
     if (im.top) up(s->top_nodes, im.dn.top);
     if (im.c16) up(s->nodes, im.n16); else up(s->nodes, im.dn.main);
     up(s->spheres, cs.spheres); up(s->sphere_meta, cs.sphere_meta); up(s->moving, cs.moving); up(s->moving_meta, cs.moving_meta);
-    up(s->rects, cs.rects); up(s->rect_meta, cs.rect_meta); up(s->tris, cs.tris); up(s->tri_meta, cs.tri_meta); up(s->boxes, cs.boxes); up(s->media, cs.media);
+    up(s->rects, cs.rects); up(s->rect_meta, cs.rect_meta); up_tris(); up(s->tri_meta, cs.tri_meta); up(s->boxes, cs.boxes); up(s->media, cs.media);
     up(s->xforms, cs.xforms); up(s->wraps, cs.wraps); up(s->mat_a, cs.mat_a); up(s->mat_b, cs.mat_b); up(s->textures, cs.textures); up(s->perlins, cs.perlins);
     up(s->images, cs.images); up(s->image_bytes, cs.image_bytes); up(s->lights, cs.lights);
     up(s->sphere_src, cs.sphere_src); up(s->moving_src, cs.moving_src); up(s->rect_src, cs.rect_src); up(s->tri_src, cs.tri_src);
@@ -602,7 +675,7 @@ int rti::scene_image_upload(RtCtx* ctx, const SceneImage& im, RtScene** out_scen
     if (!sphere_ma.empty()) { d.sphere_mat_a = (const rtd::Float4*)s->sphere_mat_a.p; d.sphere_mat_b = (const uint32_t*)s->sphere_mat_b.p; }
     d.moving = (const rtd::Float4*)s->moving.p; d.moving_meta = (const uint32_t*)s->moving_meta.p;
     d.rects = (const rtd::Float4*)s->rects.p; d.rect_meta = (const uint32_t*)s->rect_meta.p;
-    d.tris = (const rtd::Float4*)s->tris.p; d.tri_meta = (const uint32_t*)s->tri_meta.p; d.boxes = (const rtd::Float4*)s->boxes.p;
+    d.tris = (const rtd::Float4*)s->tris.p + tri_front; d.tri_meta = (const uint32_t*)s->tri_meta.p; d.boxes = (const rtd::Float4*)s->boxes.p;
     d.media = (const rtd::Medium*)s->media.p; d.xforms = (const rtd::Xform*)s->xforms.p; d.wraps = (const rtd::Wrap*)s->wraps.p;
     d.mat_a = (const rtd::Float4*)s->mat_a.p; d.mat_b = (const uint32_t*)s->mat_b.p;
     d.textures = (const rtd::Texture*)s->textures.p; d.perlins = (const rtd::PerlinTable*)s->perlins.p;
@@ -630,7 +703,7 @@ int rti::scene_image_upload(RtCtx* ctx, const SceneImage& im, RtScene** out_scen
     }
     s->n_nodes = cs.nodes.size();
     s->n_prims = cs.sphere_meta.size() + cs.moving_meta.size() + cs.rect_meta.size() + cs.tri_meta.size() + cs.media.size();
-    s->bytes = cs.nodes.size() * 32 + cs.spheres.size() * 16 + cs.moving.size() * 16 + cs.rects.size() * 16 + cs.tris.size() * 16 +
+    s->bytes = cs.nodes.size() * 32 + cs.spheres.size() * 16 + cs.moving.size() * 16 + cs.rects.size() * 16 + (cs.tris.size() + tri_front) * 16 +
                4 * (cs.sphere_meta.size() + cs.moving_meta.size() + cs.rect_meta.size() + cs.tri_meta.size());
     *out_scene = s;
     return RT_OK;
@@ -1431,11 +1504,17 @@ int rt_scene_compile_info_ex(const RtSceneDesc* desc, const RtUploadOptions* opt
     out->n_rects = cs.rect_meta.size(); out->n_tris = cs.tri_meta.size(); out->n_media = cs.media.size(); out->n_xforms = cs.xforms.size();
     out->n_lights = cs.lights.size(); out->n_materials = cs.mat_b.size();
     out->features = scene_features(cs);
+    {
+        std::string why;
+        const int ok = tri_attr_table(*desc, options, cs, nullptr, &out->n_tri_attrs, why);
+        if (ok != RT_OK) return set_err(nullptr, ok, why);
+        if (out->n_tri_attrs != 0u) out->features |= rtk::F_TRI_ATTR;
+    }
     out->fits_lds = lds_scene_bytes(cs) <= kLdsSceneBudget ? 1u : 0u;
     {   // what a walk tests before it enters the tree: the root list's every-ray members, then the root BVH's scene-sized spheres
         std::vector<uint32_t> first = cs.prologue;
         if (cs.first_leaf != 0u) first.push_back(cs.first_leaf);
-        out->n_first = (uint32_t)std::min<size_t>(first.size(), 4); out->_pad = 0u;
+        out->n_first = (uint32_t)std::min<size_t>(first.size(), 4);
         for (uint32_t k = 0; k < 4u; ++k) out->first[k] = k < first.size() ? first[k] : 0u;
     }
     return RT_OK;
@@ -1493,6 +1572,7 @@ int rt_scene_compile_dump_ex(const RtSceneDesc* desc, const RtUploadOptions* opt
     rtc::CompiledScene cs;
     const int rc = rtc::compile_scene(*desc, resolve_options(options).compile, cs);
     if (rc != RT_OK) return set_err(nullptr, rc, "scene: " + cs.error);
+    { uint32_t n_with; std::string why; const int ok = tri_attr_table(*desc, options, cs, nullptr, &n_with, why); if (ok != RT_OK) return set_err(nullptr, ok, why); }
     if ((nodes && cap_nodes < cs.nodes.size()) || ((spheres || sphere_meta) && cap_spheres < cs.sphere_meta.size())) return set_err(nullptr, RT_ERR_INVALID, "capacity too small");
     if (nodes) std::memcpy(nodes, cs.nodes.data(), cs.nodes.size() * sizeof(rtd::Node));
     if (spheres) std::memcpy(spheres, cs.spheres.data(), cs.spheres.size() * sizeof(rtd::Float4));

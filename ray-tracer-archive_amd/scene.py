@@ -13,6 +13,7 @@ class SceneBuilder:
     def __init__(self, background=(0.0, 0.0, 0.0), background_mode=A.RT_BG_CONSTANT, bvh_seed=1, bvh_builder=A.RT_BVH_REFERENCE):
         self.hittables, self.children, self.materials, self.textures, self.perlins, self.images = [], [], [], [], [], []
         self._image_arrays = []
+        self.tri_attrs = []          # RtTriangleAttrs of the triangles built with normals / uvs
         self.background, self.background_mode, self.bvh_seed, self.bvh_builder = background, background_mode, bvh_seed, bvh_builder
         self._keep = None
 
@@ -102,8 +103,23 @@ class SceneBuilder:
     def yz_rect(self, y0, y1, z0, z1, k, mat):
         return self._hit(A.RT_HIT_YZ_RECT, mat, p=[y0, y1, z0, z1, k])
 
-    def triangle(self, v0, v1, v2, mat):
-        return self._hit(A.RT_HIT_TRIANGLE, mat, p=list(v0) + list(v1) + list(v2))
+    def triangle(self, v0, v1, v2, mat, normals=None, uvs=None):
+        """normals: three vectors at v0, v1, v2 (need not be unit); uvs: three (u, v) pairs. Either one makes an RtTriangleAttrs record, which
+        travels beside the desc: hand triangle_attrs() to upload / compile_info as `triangle_attrs=`."""
+        hid = self._hit(A.RT_HIT_TRIANGLE, mat, p=list(v0) + list(v1) + list(v2))
+        if normals is not None or uvs is not None:
+            a = A.RtTriangleAttrs(hid, (A.RT_TRI_NORMALS if normals is not None else 0) | (A.RT_TRI_UVS if uvs is not None else 0))
+            for v in range(3):
+                for c in range(3):
+                    a.n[v][c] = float(normals[v][c]) if normals is not None else 0.0
+                for c in range(2):
+                    a.uv[v][c] = float(uvs[v][c]) if uvs is not None else 0.0
+            self.tri_attrs.append(a)
+        return hid
+
+    def triangle_attrs(self):
+        """The RtTriangleAttrs array of the triangles built with normals / uvs (None when there is none)."""
+        return (A.RtTriangleAttrs * len(self.tri_attrs))(*self.tri_attrs) if self.tri_attrs else None
 
     def box(self, p0, p1, mat):
         return self._hit(A.RT_HIT_BOX, mat, p=list(p0) + list(p1))

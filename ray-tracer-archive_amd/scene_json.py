@@ -19,16 +19,18 @@ SceneBuilder calls — nothing here touches the device.
                     "block": {"box": [[0, 0, 0], [165, 330, 165]], "material": "wall"},
                     "tall":  {"translate": ["turned", [265, 0, 295]]}, "turned": {"rotate_y": ["block", 15]},
                     "fog":   {"constant_medium": ["ball", 0.01], "material": "smoke"},
-                    "mesh":  {"obj": "bunny.obj", "material": "steel", "scale": 1.0, "offset": [0, 0, 0]}},
+                    "mesh":  {"obj": "bunny.obj", "material": "steel", "scale": 1.0, "offset": [0, 0, 0], "smooth": true, "textured": false}},
       "world":  {"list": ["floor", "tall", "fog"]},  # or {"bvh": [...]} = BVHNode::construct2 over the members
       "lights": ["lamp_rect", "ball"],              # optional: XzRect / Sphere objects (main.rs:669-686)
       "bvh": {"seed": 1, "builder": "reference"}    # or "sah"
     }
 
 Hittable kinds: sphere [center, radius]; moving_sphere [c0, c1, t0, t1, radius]; xy_rect / xz_rect /
-yz_rect [a0, a1, b0, b1, k]; triangle [v0, v1, v2]; box [p0, p1]; translate [child, offset]; rotate_y
+yz_rect [a0, a1, b0, b1, k]; triangle [v0, v1, v2] (+ "normals": [n0, n1, n2], "uvs": [[u, v] x 3]: RtTriangleAttrs); box [p0, p1]; translate [child, offset]; rotate_y
 [child, degrees]; flip_face child; constant_medium [boundary, density] (+ "material": an isotropic);
-list [...]; bvh [...]; obj "file.obj" (triangles of a Wavefront OBJ, in a BVH).
+list [...]; bvh [...]; obj "file.obj" (triangles of a Wavefront OBJ, in a BVH; "smooth": true shades with the file's vn,
+"textured": true maps textures through its vt — faces that name none stay flat / keep their barycentrics). A scene with such attributes
+hands JsonScene.triangle_attrs to upload(..., triangle_attrs=).
 Errors raise ValueError with the offending key.
 """
 import json
@@ -71,8 +73,54 @@ def parse_obj(path):
     return np.asarray(tris, dtype=np.float64).reshape(-1, 3, 3)
 
 
+def parse_obj_attrs(path):
+    """parse_obj with the attributes a face's corners name: (tris (n, 3, 3), vn (n, 3, 3), vt (n, 3, 2), has_vn (n,), has_vt (n,)). A face
+    written v/vt/vn, v//vn or v/vt gives its triangles the `vn` / `vt` records it indexes (fans and negative indices as for `v`); has_vn /
+    has_vt say whether EVERY corner of the face named one, rows without are 0."""
+    verts, norms, texs = [], [], []
+    tris, vn, vt, has_vn, has_vt = [], [], [], [], []
+
+    def pick(w, table, what, ln):
+        i = int(w)
+        i = i - 1 if i > 0 else len(table) + i
+        if not 0 <= i < len(table):
+            raise ValueError(f"{path}:{ln}: {what} index {w} out of range")
+        return i
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            t = line.split()
+            if not t or t[0].startswith("#"):
+                continue
+            if t[0] in ("v", "vn"):
+                if len(t) < 4:
+                    raise ValueError(f"{path}:{ln}: {t[0]} needs three coordinates")
+                (verts if t[0] == "v" else norms).append([float(t[1]), float(t[2]), float(t[3])])
+            elif t[0] == "vt":
+                if len(t) < 3:
+                    raise ValueError(f"{path}:{ln}: vt needs two coordinates")
+                texs.append([float(t[1]), float(t[2])])
+            elif t[0] == "f":
+                corners = []
+                for w in t[1:]:
+                    part = w.split("/") + ["", ""]
+                    corners.append((verts[pick(part[0], verts, "face", ln)],
+                                    texs[pick(part[1], texs, "vt", ln)] if part[1] else None,
+                                    norms[pick(part[2], norms, "vn", ln)] if part[2] else None))
+                all_t, all_n = all(c[1] is not None for c in corners), all(c[2] is not None for c in corners)
+                for k in range(1, len(corners) - 1):
+                    tri = (corners[0], corners[k], corners[k + 1])
+                    tris.append([c[0] for c in tri])
+                    vt.append([c[1] if all_t else [0.0, 0.0] for c in tri])
+                    vn.append([c[2] if all_n else [0.0, 0.0, 0.0] for c in tri])
+                    has_vt.append(all_t)
+                    has_vn.append(all_n)
+    return (np.asarray(tris, dtype=np.float64).reshape(-1, 3, 3), np.asarray(vn, dtype=np.float64).reshape(-1, 3, 3),
+            np.asarray(vt, dtype=np.float64).reshape(-1, 3, 2), np.asarray(has_vn, dtype=bool), np.asarray(has_vt, dtype=bool))
+
+
 class JsonScene:
-    """desc (RtSceneDesc), camera(aspect) -> RtCamera; keeps the arrays the desc points into alive."""
+    """desc (RtSceneDesc), camera(aspect) -> RtCamera, triangle_attrs (the RtTriangleAttrs array to hand to upload as triangle_attrs=, or
+    None); keeps the arrays the desc points into alive."""
 
     def __init__(self, doc, base_dir="."):
         if isinstance(doc, (str, bytes)):
@@ -98,6 +146,7 @@ class JsonScene:
         if doc.get("lights"):
             lights = self.b.hittable_list([self._object(n) for n in doc["lights"]])
         self.desc = self.b.desc(world, lights)
+        self.triangle_attrs = self.b.triangle_attrs()
 
     # ---- textures / materials ----
     def _colour_texture(self, v, what):
@@ -203,7 +252,13 @@ class JsonScene:
             hid = getattr(b, k)(*[float(x) for x in args(k, 5)], mat())
         elif "triangle" in o:
             v0, v1, v2 = args("triangle", 3)
-            hid = b.triangle(_vec3(v0, w), _vec3(v1, w), _vec3(v2, w), mat())
+            nrm = [_vec3(x, f"{w}.normals") for x in args("normals", 3)] if "normals" in o else None
+            uvs = None
+            if "uvs" in o:
+                uvs = args("uvs", 3)
+                if not all(isinstance(x, (list, tuple)) and len(x) == 2 and all(isinstance(c, (int, float)) for c in x) for x in uvs):
+                    raise ValueError(f"{w}.uvs: expected three [u, v] pairs")
+            hid = b.triangle(_vec3(v0, w), _vec3(v1, w), _vec3(v2, w), mat(), normals=nrm, uvs=uvs)
         elif "box" in o:
             p0, p1 = args("box", 2)
             hid = b.box(_vec3(p0, w), _vec3(p1, w), mat())
@@ -224,11 +279,20 @@ class JsonScene:
         elif "list" in o or "bvh" in o:
             hid = self._group(o, w)
         elif "obj" in o:
-            tris = parse_obj(os.path.join(self.base_dir, o["obj"])) * float(o.get("scale", 1.0)) + np.asarray(_vec3(o.get("offset", [0, 0, 0]), w))
+            scale, smooth, textured = float(o.get("scale", 1.0)), bool(o.get("smooth", False)), bool(o.get("textured", False))
+            tris, vn, vt, has_vn, has_vt = parse_obj_attrs(os.path.join(self.base_dir, o["obj"]))
+            tris = tris * scale + np.asarray(_vec3(o.get("offset", [0, 0, 0]), w))
             if len(tris) == 0:
                 raise ValueError(f"{w}.obj: no faces")
+            if smooth and not has_vn.any():
+                raise ValueError(f"{w}.smooth: the OBJ names no vn on any face")
+            if textured and not has_vt.any():
+                raise ValueError(f"{w}.textured: the OBJ names no vt on any face")
+            if smooth and scale < 0.0:
+                raise ValueError(f"{w}.smooth: a negative scale turns the mesh inside out under its normals")
             m = mat()
-            hid = b.bvh([b.triangle(list(t[0]), list(t[1]), list(t[2]), m) for t in tris])
+            hid = b.bvh([b.triangle(list(t[0]), list(t[1]), list(t[2]), m, normals=vn[k] if smooth and has_vn[k] else None,
+                                    uvs=vt[k] if textured and has_vt[k] else None) for k, t in enumerate(tris)])
         else:
             raise ValueError(f"{w}: unknown hittable kind")
         self._busy.discard(name)

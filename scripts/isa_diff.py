@@ -62,7 +62,8 @@ else:
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
     # a k_extend of `after` with a seventh template argument `false` (ANYHIT, defaulted: added after `before` was taken) is the instance
     # `before` lists with six
-    b = {(n[:-len(', false>')] + '>' if re.fullmatch(r'rtk::k_extend<([^,]*, ){6}false>', n) else n): v for n, v in b.items()}
+    # (only where `before` does not list the seven-argument name itself: two dumps taken after ANYHIT was added match by name)
+    b = {(n[:-len(', false>')] + '>' if n not in a and re.fullmatch(r'rtk::k_extend<([^,]*, ){6}false>', n) else n): v for n, v in b.items()}
     by_key = merged(a)
     same = diff = 0
     used = set()
