@@ -97,14 +97,16 @@ struct ListPass { const uint32_t* list; uint32_t n; uint32_t* counts; };
 static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions& pass, void* d_out, void* d_sq, RtStats* stats,
                        const ListPass* lp);
 
-// A render that fails half way (a HIP error, out of memory) must not leave work or recorded events in flight on the
-// caller's stream: drain it before the error goes back.
+// A call that fails half way (a HIP error, out of memory) must not leave work or recorded events in flight on the caller's stream:
+// drain it and clear the sticky error before the code goes back, with the message of the failure, not of the drain.
+static int drain_on_failure(RtCtx* ctx, int r) {
+    if (r != RT_OK) { const std::string keep = ctx->err; (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); ctx->err = keep; g_last_error = keep; }
+    return r;
+}
 static int render_pass_checked(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions& pass, void* d_out, void* d_sq,
                                RtStats* stats, const ListPass* lp = nullptr) {
     if (ctx->fail_renders != 0u) { --ctx->fail_renders; return set_err(ctx, RT_ERR_DEVICE, "injected failure (rt_test_fail_next_renders)"); }
-    const int r = render_impl(ctx, scene, cam, prm, pass, d_out, d_sq, stats, lp);
-    if (r != RT_OK) { const std::string keep = ctx->err; (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); ctx->err = keep; g_last_error = keep; }
-    return r;
+    return drain_on_failure(ctx, render_impl(ctx, scene, cam, prm, pass, d_out, d_sq, stats, lp));
 }
 // the whole frame as one pass that overwrites: what rt_render computes
 static RtPassOptions one_shot(const RtParams* prm) { return RtPassOptions{(uint32_t)sizeof(RtPassOptions), 0u, 0u, prm->samples_per_pixel}; }
@@ -175,18 +177,14 @@ int rt_ctx_destroy(RtCtx* ctx) {
     if (!ctx) return RT_OK;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (auto& pl : ctx->pool) for (auto& b : pl) b.release();
-    comm_release(ctx);
-    ctx->blocksum.release(); ctx->counters.release(); ctx->out_tmp.release(); ctx->sq_tmp.release(); ctx->tile_prefix.release(); ctx->shard_tmp.release();
-    ctx->list_map.release(); ctx->sel_masks.release(); ctx->sel_offsets.release(); ctx->adaptive_word.release();
+    comm_release(ctx);   // before the memory its exchanges use goes
     for (hipEvent_t ev : ctx->events) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->ev_gather) if (ev) (void)hipEventDestroy(ev);
     if (ctx->h_count) (void)hipHostFree(ctx->h_count);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->h_words) (void)hipHostFree(ctx->h_words);
-    ctx->comm_words.release();
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;   // every device buffer of the context frees itself here (DevBuf); hipFree needs no stream, and the device is still current
     return RT_OK;
 }
 
@@ -725,10 +723,6 @@ int rt_scene_upload(RtCtx* ctx, const RtSceneDesc* desc, RtScene** out_scene) { 
 int rt_scene_destroy(RtCtx* ctx, RtScene* s) {
     if (!s) return RT_OK;
     if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
-    DevBuf* all[] = {&s->nodes, &s->spheres, &s->sphere_meta, &s->moving, &s->moving_meta, &s->rects, &s->rect_meta, &s->tris, &s->tri_meta, &s->boxes, &s->media,
-                     &s->xforms, &s->wraps, &s->mat_a, &s->mat_b, &s->textures, &s->perlins, &s->images, &s->image_bytes, &s->lights, &s->top_nodes, &s->shade_blob, &s->ext_blob, &s->wide, &s->sphere_mat_a, &s->sphere_mat_b,
-                     &s->sphere_src, &s->moving_src, &s->rect_src, &s->tri_src};
-    for (DevBuf* b : all) b->release();
     delete s;
     return RT_OK;
 }
@@ -749,22 +743,106 @@ int rt_output_floats(const RtParams* p, uint64_t* out_n) {
         if (e_ != hipSuccess) return set_err(ctx, RT_ERR_DEVICE, std::string(rtk::launch_note() ? rtk::launch_note() : #call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions& pass, void* d_out, void* d_sq, RtStats* stats,
-                       const ListPass* lp) {
-    using clk = std::chrono::steady_clock;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    Tiling tl; make_tiling(*prm, tl);
-    const uint32_t sc = prm->shard_count <= 1u ? 1u : prm->shard_count, si = prm->shard_count <= 1u ? 0u : prm->shard_index;
+// ---- what the launch paths below (render_impl, trace_rays_impl, features_impl) decide in one place each --------------------------------
+
+// The path pool's arrays, bytes per slot: ray_o ray_d hit s0 sd, and s1 = (acc, sample) for items of several samples (kernels.h PoolDev).
+// A caller names how many of them it uses: 5, or all 6.
+constexpr size_t kPoolRec[6] = {16, 16, 8, 16, 4, 16};
+static size_t pool_slot_bytes(int n_arrays) { size_t b = 0; for (int a = 0; a < n_arrays; ++a) b += kPoolRec[a]; return b; }
+static size_t pool_held_bytes(const RtCtx* ctx, int k, int n_arrays) { size_t b = 0; for (int a = 0; a < n_arrays; ++a) b += ctx->pool[k][a].bytes; return b; }
+// the first n_arrays arrays of pool k, grown to P slots
+static int pool_bind(RtCtx* ctx, int k, uint32_t P, int n_arrays, rtk::PoolDev& pd) {
+    DevBuf* b = ctx->pool[k];
+    for (int a = 0; a < n_arrays; ++a) HIP_TRY(ctx, b[a].ensure((size_t)P * kPoolRec[a]));
+    pd = rtk::PoolDev{(rtd::Float4*)b[0].p, (rtd::Float4*)b[1].p, (uint2*)b[2].p, (rtd::Float4*)b[3].p, (uint32_t*)b[4].p, n_arrays > 5 ? (rtd::Float4*)b[5].p : nullptr};
+    return RT_OK;
+}
+// Pool size: as many slots as there are items, up to `asked`; unasked (0) up to 2^28, halved while above 2^20 slots and larger than 70 %
+// of the device memory the pool may take — what is free and what the buffers about to be resized hold already (`held`) — less `set_aside`.
+static uint32_t pool_size(uint32_t asked, uint64_t items, size_t slot_bytes, size_t held, size_t set_aside) {
+    uint32_t P = (uint32_t)std::min<uint64_t>(asked ? asked : (1u << 28), items);
+    size_t free_b = 0, total_b = 0;
+    if (!asked && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+        const size_t avail = (free_b + held) * 7 / 10, budget = avail > set_aside ? avail - set_aside : 0;
+        while (P > (1u << 20) && (size_t)P * slot_bytes > budget) P >>= 1;
+    }
+    return P;
+}
+// kQueues queues of queue_cap slots, filled 512 at a time in turn (k_generate, the imports): a pool is a multiple of 512 * kQueues slots
+static uint32_t pool_grain(uint32_t P) {
+    constexpr uint32_t kGrain = 512u * rtk::kQueues;
+    return std::max<uint32_t>(kGrain, (uint32_t)std::min<uint64_t>(((uint64_t)P + kGrain - 1u) / kGrain * kGrain, 0xFFFFF000ull));
+}
+
+// The context's counter block. Every counter the workgroups hit with atomics has a 128-byte line of its own, one per queue: four groups of
+// kQueues lines, then the 16 64-bit statistics (kernels.h CTR_*). Group 0 is unused since round 3 (it held the queues' next-work-item
+// counters; a path now finds its next item by itself, kernels.h RenderDev::lineage), group 1 holds the queue heads, groups 2 and 3 the
+// sizes of the two pools. A chunk loop has one pool: count[0] is its queues' sizes, count[1] what k_extend zeroes for a k_shade that never runs.
+struct CounterBlock {
+    static constexpr size_t kLine = 128, kGroup = rtk::kQueues * kLine, kQueueLines = 4 * kGroup, kStats = sizeof(unsigned long long) * rtk::CTR_COUNT;
+    static_assert(rtk::kQStride * sizeof(uint32_t) == kLine, "queue counters are one line apart");
+    char* base = nullptr; hipStream_t stream = nullptr;
+    uint32_t* head = nullptr; uint32_t* count[2] = {nullptr, nullptr}; unsigned long long* c64 = nullptr;
+    hipError_t ensure(RtCtx* ctx) {
+        const hipError_t e = ctx->counters.ensure(kQueueLines + kStats);
+        if (e != hipSuccess) return e;
+        base = (char*)ctx->counters.p; stream = ctx->stream;
+        head = (uint32_t*)(base + 1 * kGroup); count[0] = (uint32_t*)(base + 2 * kGroup); count[1] = (uint32_t*)(base + 3 * kGroup);
+        c64 = (unsigned long long*)(base + kQueueLines);
+        return hipSuccess;
+    }
+    hipError_t zero_all() const { return hipMemsetAsync(base, 0, kQueueLines + kStats, stream); }
+    hipError_t zero_queue_lines() const { return hipMemsetAsync(base, 0, kQueueLines, stream); }   // between chunks: heads and sizes go, the statistics stay
+    hipError_t read_stats(RtCtx* ctx) const { return hipMemcpyAsync(ctx->h_counters, c64, kStats, hipMemcpyDeviceToHost, stream); }
+};
+
+// Device times of a call's kernels: events on the context's stream (the context keeps them for the next call), spans between two of them
+// with a kind of the caller's choosing, and after the call's final synchronise the milliseconds of every kind.
+struct StreamTimer {
+    RtCtx* ctx; size_t used = 0;
+    struct Span { hipEvent_t a, b; int kind; };
+    std::vector<Span> spans;
+    hipError_t mark(hipEvent_t& ev) {
+        if (used == ctx->events.size()) { hipEvent_t e; hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; ctx->events.push_back(e); }
+        ev = ctx->events[used++];
+        return hipEventRecord(ev, ctx->stream);
+    }
+    void span(hipEvent_t a, hipEvent_t b, int kind) { spans.push_back({a, b, kind}); }
+    void sum(double* ms_by_kind) const { for (const Span& s : spans) { float ms = 0.f; if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) ms_by_kind[s.kind] += ms; } }
+};
+
+// the part of RtStats that the scene and the launch configuration decide, the same after every kind of call
+static void scene_stats(RtStats* stats, const RtScene* scene, const uint32_t extend_geometry[2]) {
+    stats->debug[6] = extend_geometry[0]; stats->debug[7] = extend_geometry[1];   // k_extend: threads per workgroup, resident workgroups per CU
+    stats->n_devices = 1u; stats->lds_top_nodes = scene->dev.n_top;
+    stats->scene_nodes = scene->n_nodes; stats->scene_prims = scene->n_prims; stats->scene_bytes = scene->bytes; stats->bvh_in_lds = scene->in_lds ? 1u : 0u;
+}
+
+// camera, frame, seed, background and tiling: what new_camera_ray and the slot <-> pixel decodes of every kernel read (kernels.h RenderDev)
+static rtk::RenderDev frame_render_dev(const RtScene* scene, const RtCamera* cam, const RtParams* prm, const Tiling& tl) {
     rtk::RenderDev rd{};
     auto cp3 = [](float* d, const RtVec3& v) { d[0] = (float)v.x; d[1] = (float)v.y; d[2] = (float)v.z; };
     cp3(rd.cam_origin, cam->origin); cp3(rd.cam_llc, cam->lower_left_corner); cp3(rd.cam_horizontal, cam->horizontal); cp3(rd.cam_vertical, cam->vertical);
     cp3(rd.cam_u, cam->u); cp3(rd.cam_v, cam->v);
     rd.cam_lens_radius = (float)cam->lens_radius; rd.cam_time0 = (float)cam->time0; rd.cam_time1 = (float)cam->time1;
+    rd.width = prm->width; rd.height = prm->height; rd.seed = prm->seed;
+    rd.bg_mode = scene->bg_mode; for (int i = 0; i < 3; ++i) rd.bg[i] = scene->bg[i];
+    rd.tile_size = tl.ts; rd.tiles_x = tl.tiles_x; rd.tiles_y = tl.tiles_y; rd.n_local_tiles = tl.n_local;
+    rd.shard_count = prm->shard_count <= 1u ? 1u : prm->shard_count; rd.shard_index = prm->shard_count <= 1u ? 0u : prm->shard_index;
+    rd.div_width = rtk::make_fastdiv(prm->width); rd.div_ts = rtk::make_fastdiv(tl.ts); rd.div_ts2 = rtk::make_fastdiv(tl.ts * tl.ts); rd.div_tiles_x = rtk::make_fastdiv(tl.tiles_x);
+    return rd;
+}
+
+static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions& pass, void* d_out, void* d_sq, RtStats* stats,
+                       const ListPass* lp) {
+    using clk = std::chrono::steady_clock;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Tiling tl; make_tiling(*prm, tl);
+    rtk::RenderDev rd = frame_render_dev(scene, cam, prm, tl);
+    const uint32_t sc = rd.shard_count, si = rd.shard_index;
     // a pass renders samples first_sample .. first_sample + samples_per_pixel - 1: rd.spp is its END (absolute), n_blocks its items per pixel
-    rd.width = prm->width; rd.height = prm->height; rd.spp = pass.first_sample + prm->samples_per_pixel; rd.max_depth = prm->max_depth; rd.seed = prm->seed;
+    rd.spp = pass.first_sample + prm->samples_per_pixel; rd.max_depth = prm->max_depth; rd.nan_policy = prm->nan_policy;
     rd.first_sample = pass.first_sample; rd.accumulate = (pass.flags & RT_PASS_ACCUMULATE) ? 1u : 0u; rd.sq_sum = (float*)d_sq;
-    rd.nan_policy = prm->nan_policy; rd.bg_mode = scene->bg_mode; for (int i = 0; i < 3; ++i) rd.bg[i] = scene->bg[i];
-    rd.tile_size = tl.ts; rd.tiles_x = tl.tiles_x; rd.tiles_y = tl.tiles_y; rd.shard_index = si; rd.shard_count = sc;
     // in-image pixels per local tile (edge tiles are clipped) -> prefix table
     std::vector<uint32_t> prefix(tl.n_local + 1, 0u);
     uint64_t valid_pixels = 0;
@@ -781,11 +859,9 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     const uint64_t total_items = (lp ? (uint64_t)lp->n : valid_pixels) * rd.n_blocks;
     if (total_items >= kMaxItems) return set_err(ctx, RT_ERR_INVALID, "too many work items for one shard (image too large)");
     rd.total_items = (uint32_t)total_items;
-    rd.n_local_tiles = tl.n_local;
     {   // launch-invariant divisors of the item -> (tile, pixel, sample) decode, and how far clipped edge tiles can move a tile index
         const uint64_t ts2 = (uint64_t)tl.ts * tl.ts, item_tile = ts2 * rd.n_blocks;
-        rd.div_nblocks = rtk::make_fastdiv(rd.n_blocks); rd.div_width = rtk::make_fastdiv(prm->width); rd.div_ts = rtk::make_fastdiv(tl.ts); rd.div_shards = rtk::make_fastdiv(sc);
-        rd.div_ts2 = rtk::make_fastdiv((uint32_t)ts2); rd.div_tiles_x = rtk::make_fastdiv(tl.tiles_x); rd.div_sq_row = rtk::make_fastdiv(std::max(1u, tl.ts >> 3));
+        rd.div_nblocks = rtk::make_fastdiv(rd.n_blocks); rd.div_shards = rtk::make_fastdiv(sc); rd.div_sq_row = rtk::make_fastdiv(std::max(1u, tl.ts >> 3));
         const bool fits = item_tile <= 0xFFFFFFFFull;
         rd.div_item_tile = rtk::make_fastdiv(fits ? (uint32_t)item_tile : 0xFFFFFFFFu);
         const uint64_t clipped = (uint64_t)tl.n_local * ts2 - valid_pixels;
@@ -805,33 +881,18 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
 
     // Pool: as many paths in flight as there are work items, up to 2^28 (45 GB for the two pools) and to what the
     // device has free. Launches then carry hundreds of millions of rays: few launches, short tails.
-    const size_t rec[6] = {16, 16, 8, 16, 4, block_shift ? (size_t)16 : (size_t)0};   // ray_o ray_d hit s0 sd [s1 = acc, sample]
-    size_t slot_bytes = 0; for (int a = 0; a < 6; ++a) slot_bytes += 2 * rec[a];
-    uint32_t P = prm->pool_slots ? prm->pool_slots : (1u << 28);
-    P = (uint32_t)std::min<uint64_t>(P, total_items);
-    if (!prm->pool_slots) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            size_t held = ctx->blocksum.bytes; for (int k = 0; k < 2; ++k) for (int a = 0; a < 6; ++a) held += ctx->pool[k][a].bytes;
-            const size_t avail = free_b + held, need_sum = (size_t)total_items * 16;
-            const size_t budget = avail * 7 / 10 > need_sum ? avail * 7 / 10 - need_sum : 0;
-            while (P > (1u << 20) && (size_t)P * slot_bytes > budget) P >>= 1;
-        }
-    }
+    // Both pools and blocksum count as held; blocksum (16 bytes per item, whatever the pool's size) is set aside.
+    const int n_arrays = block_shift ? 6 : 5;
+    uint32_t P = pool_size(prm->pool_slots, total_items, 2 * pool_slot_bytes(n_arrays), ctx->blocksum.bytes + pool_held_bytes(ctx, 0, 6) + pool_held_bytes(ctx, 1, 6),
+                            (size_t)total_items * 16);
     // Every slot of the first fill owns a LINEAGE of work items — w, w + P, w + 2P, ... — which its path works through one after the other
     // (kernels.h RenderDev::lineage). So that all lineages are equally long (and the pool stays full until the last generation), P is
     // not the cap itself but total / k for the smallest k that fits the cap: 480 M items under a cap of 2^28 run as 2 x 240 M.
     if (!prm->pool_slots && P < total_items) { const uint64_t k = (total_items + P - 1u) / P; P = (uint32_t)((total_items + k - 1u) / k); }
-    // kQueues queues of queue_cap slots, filled 512 at a time in turn (k_generate): P is a multiple of 512 * kQueues
-    constexpr uint32_t kGrain = 512u * rtk::kQueues;
-    P = std::max<uint32_t>(kGrain, (uint32_t)std::min<uint64_t>(((uint64_t)P + kGrain - 1u) / kGrain * kGrain, 0xFFFFF000ull));
+    P = pool_grain(P);
     rd.queue_cap = P / rtk::kQueues;
     rtk::PoolDev pd[2];
-    for (int k = 0; k < 2; ++k) {
-        for (int a = 0; a < 6; ++a) if (rec[a]) HIP_TRY(ctx, ctx->pool[k][a].ensure((size_t)P * rec[a]));
-        pd[k].ray_o = (rtd::Float4*)ctx->pool[k][0].p; pd[k].ray_d = (rtd::Float4*)ctx->pool[k][1].p; pd[k].hit = (uint2*)ctx->pool[k][2].p;
-        pd[k].s0 = (rtd::Float4*)ctx->pool[k][3].p; pd[k].sd = (uint32_t*)ctx->pool[k][4].p; pd[k].s1 = rec[5] ? (rtd::Float4*)ctx->pool[k][5].p : nullptr;
-    }
+    for (int k = 0; k < 2; ++k) { const int r = pool_bind(ctx, k, P, n_arrays, pd[k]); if (r != RT_OK) return r; }
     HIP_TRY(ctx, ctx->blocksum.ensure((size_t)total_items * 16));
     rd.blocksum = (rtd::Float4*)ctx->blocksum.p;
     HIP_TRY(ctx, ctx->tile_prefix.ensure(prefix.size() * 4));
@@ -843,43 +904,27 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
         HIP_TRY(ctx, rtk::launch_list_map(lp->list, lp->n, (uint32_t*)ctx->list_map.p, ctx->stream));
         rd.list = lp->list; rd.n_list = lp->n; rd.list_map = (const uint32_t*)ctx->list_map.p; rd.div_list = rtk::make_fastdiv(lp->n); rd.counts = lp->counts;
     }
-    // counters, one 128-byte line each (they are hit by atomics from every workgroup):
-    // line 0 unused since round 3 (it held the queues' next-work-item counters; a path now finds its next item by itself, kernels.h RenderDev::lineage),
-    // line 1 queue head, lines 2,3 pool counts; 64-bit statistics from line 4
-    // (four counters per queue: next work item, queue head, size of either pool; each on a line of its own)
-    constexpr size_t kLine = 128, kQ = rtk::kQueues;
-    static_assert(rtk::kQStride * sizeof(uint32_t) == kLine, "queue counters are one line apart");
-    HIP_TRY(ctx, ctx->counters.ensure(4 * kQ * kLine + sizeof(unsigned long long) * 16));
-    char* cbase = (char*)ctx->counters.p;
-    uint32_t* c_head = (uint32_t*)(cbase + 1 * kQ * kLine);
-    uint32_t* c_count[2] = {(uint32_t*)(cbase + 2 * kQ * kLine), (uint32_t*)(cbase + 3 * kQ * kLine)};
-    unsigned long long* c64 = (unsigned long long*)(cbase + 4 * kQ * kLine);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, 4 * kQ * kLine + sizeof(unsigned long long) * 16, ctx->stream));
+    CounterBlock cb;
+    HIP_TRY(ctx, cb.ensure(ctx));
+    HIP_TRY(ctx, cb.zero_all());
 
     const bool counting = (prm->flags & RT_FLAG_COUNTERS) != 0, timing = (prm->flags & RT_FLAG_TIMING) != 0;
     rtk::LaunchCfg cfg{};
     uint32_t extend_geometry[2] = {0u, 0u};
     cfg.n_cu = (uint32_t)ctx->n_cu; cfg.extend_geometry = extend_geometry; cfg.features = scene->features; cfg.scene_in_lds = scene->in_lds;
 
-    size_t ev_used = 0;
-    auto next_event = [&](hipEvent_t& ev) -> hipError_t {
-        if (ev_used == ctx->events.size()) { hipEvent_t e; hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; ctx->events.push_back(e); }
-        ev = ctx->events[ev_used++];
-        return hipEventRecord(ev, ctx->stream);
-    };
-    struct Span { hipEvent_t a, b; int kind; };
-    std::vector<Span> spans;
+    StreamTimer tm{ctx};
 
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timing) HIP_TRY(ctx, next_event(e0));
+    if (timing) HIP_TRY(ctx, tm.mark(e0));
     const uint32_t n_init = (uint32_t)std::min<uint64_t>(P, total_items);
     rd.n_init = n_init; rd.lineage = P;
     rd.q_lo = 0u; rd.q_n = rtk::kQueues; rd.q_shift = rtk::kQShift;
     // the ground sphere tested where a ray is made (kernels.h RenderDev::first_in_shade): a scene without motion, one such sphere, no counting
     rd.first_in_shade = scene->first_id != 0u && rtk::can_test_first_in_shade(scene->features) && !counting ? 1u : 0u;
     rd.first_id = scene->first_id; for (int k = 0; k < 8; ++k) rd.first_prim[k] = scene->first_prim[k];
-    HIP_TRY(ctx, rtk::launch_generate(pd[0], rd, n_init, c_count[0], ctx->stream));
-    if (timing) { HIP_TRY(ctx, next_event(e1)); spans.push_back({e0, e1, 2}); }
+    HIP_TRY(ctx, rtk::launch_generate(pd[0], rd, n_init, cb.count[0], ctx->stream));
+    if (timing) { HIP_TRY(ctx, tm.mark(e1)); tm.span(e0, e1, 2); }
     // The host never waits for an iteration it has just enqueued: the kernels read the pool size from device memory and size-check
     // themselves, so the host only needs (a) an UPPER BOUND of the pool size to size k_shade's grid and (b) to learn that it has
     // reached 0. After every iteration the size is copied to a pinned ring slot behind an event; before enqueuing the next
@@ -919,45 +964,44 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
         if (live == 0u) break;
         if ((uint64_t)live * rtk::kQueues <= drain_at) {
             hipEvent_t ea = nullptr, eb = nullptr;
-            if (timing) HIP_TRY(ctx, next_event(ea));
-            LAUNCH_TRY(rtk::launch_drain(cfg, scene->dev, pd[cur], rd, live, c_count[cur], c_head, c_count[1 - cur], c64, counting, ctx->stream));
-            if (timing) { HIP_TRY(ctx, next_event(eb)); spans.push_back({ea, eb, 3}); }
+            if (timing) HIP_TRY(ctx, tm.mark(ea));
+            LAUNCH_TRY(rtk::launch_drain(cfg, scene->dev, pd[cur], rd, live, cb.count[cur], cb.head, cb.count[1 - cur], cb.c64, counting, ctx->stream));
+            if (timing) { HIP_TRY(ctx, tm.mark(eb)); tm.span(ea, eb, 3); }
             drained = live * rtk::kQueues;
             break;
         }
         hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr;
-        if (timing) HIP_TRY(ctx, next_event(ea));
+        if (timing) HIP_TRY(ctx, tm.mark(ea));
         cfg.max_rays = (uint32_t)std::min<uint64_t>((uint64_t)live * rtk::kQueues, 0xFFFFFFFFull);
-        LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd[cur], rd, c_count[cur], c_head, c_count[1 - cur], c64, counting, ctx->stream));
-        if (timing) HIP_TRY(ctx, next_event(eb));
-        HIP_TRY(ctx, rtk::launch_shade(cfg, scene->dev, pd[cur], pd[1 - cur], rd, live, c_count[cur], c_count[1 - cur], c_head, c64, counting, ctx->stream));
-        if (timing) { HIP_TRY(ctx, next_event(ec)); spans.push_back({ea, eb, 0}); spans.push_back({eb, ec, 1}); }
+        LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd[cur], rd, cb.count[cur], cb.head, cb.count[1 - cur], cb.c64, counting, ctx->stream));
+        if (timing) HIP_TRY(ctx, tm.mark(eb));
+        HIP_TRY(ctx, rtk::launch_shade(cfg, scene->dev, pd[cur], pd[1 - cur], rd, live, cb.count[cur], cb.count[1 - cur], cb.head, cb.c64, counting, ctx->stream));
+        if (timing) { HIP_TRY(ctx, tm.mark(ec)); tm.span(ea, eb, 0); tm.span(eb, ec, 1); }
         cur = 1 - cur;
         const uint32_t ring = launched % kRing;
-        HIP_TRY(ctx, hipMemcpy2DAsync(ctx->h_count + ring * rtk::kQueues, sizeof(uint32_t), c_count[cur], kLine, sizeof(uint32_t), rtk::kQueues, hipMemcpyDeviceToHost,
+        HIP_TRY(ctx, hipMemcpy2DAsync(ctx->h_count + ring * rtk::kQueues, sizeof(uint32_t), cb.count[cur], CounterBlock::kLine, sizeof(uint32_t), rtk::kQueues, hipMemcpyDeviceToHost,
                                       ctx->stream));   // the kQueues pool sizes, one per line
         hipEvent_t ev = nullptr;
-        HIP_TRY(ctx, next_event(ev));
+        HIP_TRY(ctx, tm.mark(ev));
         pending.push_back({ev, ring});
         if (++launched > 100000000u) return set_err(ctx, RT_ERR_DEVICE, "render loop did not terminate");
     }
     hipEvent_t r0 = nullptr, r1 = nullptr;
-    if (timing) HIP_TRY(ctx, next_event(r0));
+    if (timing) HIP_TRY(ctx, tm.mark(r0));
     if (sc > 1 && !rd.accumulate && !lp) {   // clipped pixels of edge tiles stay 0 (an accumulating pass finds them 0 from its first pass; a list pass writes listed slots only)
         HIP_TRY(ctx, hipMemsetAsync(d_out, 0, (size_t)tl.n_local * tl.ts * tl.ts * 3 * sizeof(float), ctx->stream));
         if (d_sq) HIP_TRY(ctx, hipMemsetAsync(d_sq, 0, (size_t)tl.n_local * tl.ts * tl.ts * 3 * sizeof(float), ctx->stream));
     }
     if (lp) HIP_TRY(ctx, rtk::launch_resolve_list(rd, (float*)d_out, ctx->stream));
     else HIP_TRY(ctx, rtk::launch_resolve(rd, (float*)d_out, (uint32_t)valid_pixels, ctx->stream));
-    if (timing) { HIP_TRY(ctx, next_event(r1)); spans.push_back({r0, r1, 2}); }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, c64, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (timing) { HIP_TRY(ctx, tm.mark(r1)); tm.span(r0, r1, 2); }
+    HIP_TRY(ctx, cb.read_stats(ctx));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (stats) {
         stats->render_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
-        for (const Span& s : spans) {
-            float ms = 0.f; if (hipEventElapsedTime(&ms, s.a, s.b) != hipSuccess) continue;
-            if (s.kind == 0) stats->extend_ms += ms; else if (s.kind == 1) stats->shade_ms += ms; else if (s.kind == 3) stats->drain_ms += ms; else stats->other_ms += ms;
-        }
+        double part_ms[4] = {0.0, 0.0, 0.0, 0.0};                     // extend, shade, generate and resolve, drain
+        tm.sum(part_ms);
+        stats->extend_ms = part_ms[0]; stats->shade_ms = part_ms[1]; stats->other_ms = part_ms[2]; stats->drain_ms = part_ms[3];
         stats->samples = (lp ? (uint64_t)lp->n : valid_pixels) * prm->samples_per_pixel;
         stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];
 #if defined(RT_STAMPS) || defined(RT_SHADE_STAMPS)
@@ -973,10 +1017,9 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
 #ifdef RT_STAMPS
         stats->debug[5] = ctx->h_counters[rtk::CTR_SAMPLES];       // node steps of all waves (scripts/gpu_stamps.py)
 #endif
-        stats->debug[6] = extend_geometry[0]; stats->debug[7] = extend_geometry[1];   // k_extend: threads per workgroup, resident workgroups per CU
         stats->iterations = (uint32_t)ctx->h_counters[rtk::CTR_ITERATIONS]; stats->extend_launches = launched; stats->shade_launches = launched; stats->pool_slots = P;
-        stats->n_devices = 1u; stats->lds_top_nodes = scene->dev.n_top; stats->drain_paths = drained;
-        stats->scene_nodes = scene->n_nodes; stats->scene_prims = scene->n_prims; stats->scene_bytes = scene->bytes; stats->bvh_in_lds = scene->in_lds ? 1u : 0u;
+        stats->drain_paths = drained;
+        scene_stats(stats, scene, extend_geometry);
     }
     return RT_OK;
 }
@@ -1154,40 +1197,18 @@ int rt_ray_query_check(const RtRayQueryOptions* options, uint64_t n_rays) { retu
 // any_hit (rt_occluded_rays): the same loop with the occlusion kernels — its own import, the any-hit walk, the byte export; d_hits is then
 // the caller's n_rays bytes.
 static int trace_rays_impl(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* opt, const void* d_rays, uint64_t n_rays, void* d_hits, RtStats* stats,
-                           bool any_hit = false) {
+                           bool any_hit) {
     using clk = std::chrono::steady_clock;
     const auto t_begin = clk::now();
     const bool timing = opt && (opt->flags & RT_FLAG_TIMING) != 0u;
-    // the pool, by the renderer's rule (render_impl): every ray in flight, up to 2^28 and to 70 % of the free memory; whole 512-ray groups per queue
-    const size_t rec[5] = {16, 16, 8, 16, 4};   // ray_o ray_d hit s0 sd
-    size_t slot_bytes = 0; for (size_t b : rec) slot_bytes += b;
-    uint32_t P = opt && opt->pool_slots ? opt->pool_slots : (1u << 28);
-    P = (uint32_t)std::min<uint64_t>(P, n_rays);
-    if (!(opt && opt->pool_slots)) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            size_t held = 0; for (int a = 0; a < 5; ++a) held += ctx->pool[0][a].bytes;
-            const size_t budget = (free_b + held) * 7 / 10;
-            while (P > (1u << 20) && (size_t)P * slot_bytes > budget) P >>= 1;
-        }
-    }
-    constexpr uint32_t kGrain = 512u * rtk::kQueues;
-    P = std::max<uint32_t>(kGrain, (uint32_t)std::min<uint64_t>(((uint64_t)P + kGrain - 1u) / kGrain * kGrain, 0xFFFFF000ull));
+    // one pool, every ray in flight
+    const uint32_t P = pool_grain(pool_size(opt ? opt->pool_slots : 0u, n_rays, pool_slot_bytes(5), pool_held_bytes(ctx, 0, 5), 0));
     const uint32_t queue_cap = P / rtk::kQueues;
     rtk::PoolDev pd{};
-    for (int a = 0; a < 5; ++a) HIP_TRY(ctx, ctx->pool[0][a].ensure((size_t)P * rec[a]));
-    pd.ray_o = (rtd::Float4*)ctx->pool[0][0].p; pd.ray_d = (rtd::Float4*)ctx->pool[0][1].p; pd.hit = (uint2*)ctx->pool[0][2].p;
-    pd.s0 = (rtd::Float4*)ctx->pool[0][3].p; pd.sd = (uint32_t*)ctx->pool[0][4].p; pd.s1 = nullptr;
-    // the render's counter block (render_impl): line 1 queue heads, line 2 the queues' sizes, line 3 what k_extend zeroes for a k_shade that never runs here
-    constexpr size_t kLine = 128, kQ = rtk::kQueues;
-    const size_t counter_bytes = 4 * kQ * kLine + sizeof(unsigned long long) * 16;
-    HIP_TRY(ctx, ctx->counters.ensure(counter_bytes));
-    char* cbase = (char*)ctx->counters.p;
-    uint32_t* c_head = (uint32_t*)(cbase + 1 * kQ * kLine);
-    uint32_t* c_count = (uint32_t*)(cbase + 2 * kQ * kLine);
-    uint32_t* c_other = (uint32_t*)(cbase + 3 * kQ * kLine);
-    unsigned long long* c64 = (unsigned long long*)(cbase + 4 * kQ * kLine);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, counter_bytes, ctx->stream));
+    { const int r = pool_bind(ctx, 0, P, 5, pd); if (r != RT_OK) return r; }
+    CounterBlock cb;   // one pool: count[0] the queues' sizes, count[1] what k_extend zeroes for a k_shade that never runs here
+    HIP_TRY(ctx, cb.ensure(ctx));
+    HIP_TRY(ctx, cb.zero_all());
 
     rtk::RenderDev rd{};                     // a walk needs the queue geometry only; first_in_shade = 0: the record's time slot is the ray's time
     rd.queue_cap = queue_cap; rd.q_lo = 0u; rd.q_n = rtk::kQueues; rd.q_shift = rtk::kQShift;
@@ -1196,54 +1217,48 @@ static int trace_rays_impl(RtCtx* ctx, const RtScene* scene, const RtRayQueryOpt
     uint32_t extend_geometry[2] = {0u, 0u};
     cfg.n_cu = (uint32_t)ctx->n_cu; cfg.extend_geometry = extend_geometry; cfg.features = scene->features; cfg.scene_in_lds = scene->in_lds;
 
-    size_t ev_used = 0;
-    auto next_event = [&](hipEvent_t& ev) -> hipError_t {
-        if (ev_used == ctx->events.size()) { hipEvent_t e; hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; ctx->events.push_back(e); }
-        ev = ctx->events[ev_used++];
-        return hipEventRecord(ev, ctx->stream);
-    };
-    struct Span { hipEvent_t a, b; int kind; };
-    std::vector<Span> spans;
+    StreamTimer tm{ctx};
     uint32_t launched = 0u;
     for (uint64_t first = 0; first < n_rays; first += P) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(P, n_rays - first);
         hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr, ed = nullptr;
-        if (first != 0u) HIP_TRY(ctx, hipMemsetAsync(cbase, 0, 4 * kQ * kLine, ctx->stream));     // heads and sizes of the chunk before (the 64-bit statistics stay)
-        if (timing) HIP_TRY(ctx, next_event(ea));
-        if (any_hit) LAUNCH_TRY(rtk::launch_occluded_import(d_rays, (uint32_t)first, n, pd, queue_cap, c_count, d_hits, c64, !rtk::extend_any_is_closest(scene->dev), ctx->stream));
-        else LAUNCH_TRY(rtk::launch_rays_import(d_rays, (uint32_t)first, n, pd, queue_cap, c_count, d_hits, c64, ctx->stream));
-        if (timing) HIP_TRY(ctx, next_event(eb));
+        if (first != 0u) HIP_TRY(ctx, cb.zero_queue_lines());
+        if (timing) HIP_TRY(ctx, tm.mark(ea));
+        if (any_hit) LAUNCH_TRY(rtk::launch_occluded_import(d_rays, (uint32_t)first, n, pd, queue_cap, cb.count[0], d_hits, cb.c64, !rtk::extend_any_is_closest(scene->dev), ctx->stream));
+        else LAUNCH_TRY(rtk::launch_rays_import(d_rays, (uint32_t)first, n, pd, queue_cap, cb.count[0], d_hits, cb.c64, ctx->stream));
+        if (timing) HIP_TRY(ctx, tm.mark(eb));
         cfg.max_rays = n;
-        if (any_hit) LAUNCH_TRY(rtk::launch_extend_any(cfg, scene->dev, pd, rd, c_count, c_head, c_other, c64, ctx->stream));
-        else LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd, rd, c_count, c_head, c_other, c64, false, ctx->stream));
-        if (timing) HIP_TRY(ctx, next_event(ec));
+        if (any_hit) LAUNCH_TRY(rtk::launch_extend_any(cfg, scene->dev, pd, rd, cb.count[0], cb.head, cb.count[1], cb.c64, ctx->stream));
+        else LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd, rd, cb.count[0], cb.head, cb.count[1], cb.c64, false, ctx->stream));
+        if (timing) HIP_TRY(ctx, tm.mark(ec));
         // a queue holds at most its share of the chunk's 512-ray groups
         const uint32_t per_queue = std::min<uint32_t>(queue_cap, ((n + 511u) / 512u + rtk::kQueues - 1u) / rtk::kQueues * 512u);
-        if (any_hit) LAUNCH_TRY(rtk::launch_occluded_export(pd, queue_cap, per_queue, c_count, d_hits, ctx->stream));
-        else LAUNCH_TRY(rtk::launch_rays_export(cfg, scene->dev, scene->src, pd, queue_cap, per_queue, c_count, d_hits, ctx->stream));
-        if (timing) { HIP_TRY(ctx, next_event(ed)); spans.push_back({ea, eb, 2}); spans.push_back({eb, ec, 0}); spans.push_back({ec, ed, 2}); }
+        if (any_hit) LAUNCH_TRY(rtk::launch_occluded_export(pd, queue_cap, per_queue, cb.count[0], d_hits, ctx->stream));
+        else LAUNCH_TRY(rtk::launch_rays_export(cfg, scene->dev, scene->src, pd, queue_cap, per_queue, cb.count[0], d_hits, ctx->stream));
+        if (timing) { HIP_TRY(ctx, tm.mark(ed)); tm.span(ea, eb, 1); tm.span(eb, ec, 0); tm.span(ec, ed, 1); }
         ++launched;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, c64, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, cb.read_stats(ctx));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (stats) {
-        for (const Span& s : spans) {
-            float ms = 0.f; if (hipEventElapsedTime(&ms, s.a, s.b) != hipSuccess) continue;
-            if (s.kind == 0) stats->extend_ms += ms; else stats->other_ms += ms;
-        }
+        double part_ms[2] = {0.0, 0.0};                               // extend, import and export
+        tm.sum(part_ms);
+        stats->extend_ms = part_ms[0]; stats->other_ms = part_ms[1];
         stats->samples = stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];
-        stats->debug[6] = extend_geometry[0]; stats->debug[7] = extend_geometry[1];
-        stats->iterations = launched; stats->extend_launches = launched; stats->pool_slots = P; stats->n_devices = 1u; stats->lds_top_nodes = scene->dev.n_top;
-        stats->scene_nodes = scene->n_nodes; stats->scene_prims = scene->n_prims; stats->scene_bytes = scene->bytes; stats->bvh_in_lds = scene->in_lds ? 1u : 0u;
+        stats->iterations = launched; stats->extend_launches = launched; stats->pool_slots = P;
+        scene_stats(stats, scene, extend_geometry);
         stats->render_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
     }
     return RT_OK;
 }
 
-// the argument checks of both variants: a refused call has written nothing. out_align: the alignment a device output needs (RtRayHit
-// records: 16; the bytes of an occlusion query: 1)
+// The two kinds of query differ in the kernels (trace_rays_impl any_hit) and in what a ray's result is: an RtRayHit record, or one byte.
+struct RayQueryKind { bool any_hit; size_t out_bytes; uintptr_t out_align; };
+constexpr RayQueryKind kClosestHit{false, sizeof(RtRayHit), 16u}, kOcclusion{true, 1u, 1u};
+
+// the argument checks of both variants: a refused call has written nothing. out_align: the alignment a device output needs
 static int trace_rays_refuse(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const void* rays, uint64_t n_rays, const void* out, bool device,
-                             uintptr_t out_align = 16u) {
+                             uintptr_t out_align) {
     if (!scene) return set_err(ctx, RT_ERR_INVALID, "scene is null");
     const int v = check_ray_query(ctx, options, n_rays); if (v != RT_OK) return v;
     if (scene->features & rtk::F_MEDIUM)
@@ -1253,63 +1268,47 @@ static int trace_rays_refuse(RtCtx* ctx, const RtScene* scene, const RtRayQueryO
     return RT_OK;
 }
 
-int rt_trace_rays_device(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const void* rays_device, uint64_t n_rays, void* hits_device, RtStats* stats) {
+static int ray_query_device(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const void* rays_device, uint64_t n_rays, void* out_device, RtStats* stats,
+                            const RayQueryKind& kind) {
     if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
-    const int v = trace_rays_refuse(ctx, scene, options, rays_device, n_rays, hits_device, true); if (v != RT_OK) return v;
+    const int v = trace_rays_refuse(ctx, scene, options, rays_device, n_rays, out_device, true, kind.out_align); if (v != RT_OK) return v;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (n_rays == 0u) return RT_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int r = trace_rays_impl(ctx, scene, options, rays_device, n_rays, hits_device, stats);
-    if (r != RT_OK) { const std::string keep = ctx->err; (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); ctx->err = keep; g_last_error = keep; }
-    return r;
+    return drain_on_failure(ctx, trace_rays_impl(ctx, scene, options, rays_device, n_rays, out_device, stats, kind.any_hit));
 }
-
-int rt_trace_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const RtRay* rays_host, uint64_t n_rays, RtRayHit* hits_host, RtStats* stats) {
+// the host variant: the rays staged in, the device variant on the context's own buffers, the results staged out; render_ms covers all of it
+static int ray_query_host(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const RtRay* rays_host, uint64_t n_rays, void* out_host, RtStats* stats,
+                          const RayQueryKind& kind) {
     if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
-    const int v = trace_rays_refuse(ctx, scene, options, rays_host, n_rays, hits_host, false); if (v != RT_OK) return v;   // (host buffers are copied: no alignment asked)
+    const int v = trace_rays_refuse(ctx, scene, options, rays_host, n_rays, out_host, false, kind.out_align); if (v != RT_OK) return v;   // (host buffers are copied: no alignment asked)
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (n_rays == 0u) return RT_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(ctx, ctx->rays_tmp.ensure((size_t)n_rays * sizeof(RtRay)));
-    HIP_TRY(ctx, ctx->hits_tmp.ensure((size_t)n_rays * sizeof(RtRayHit)));
+    HIP_TRY(ctx, ctx->hits_tmp.ensure((size_t)n_rays * kind.out_bytes));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->rays_tmp.p, rays_host, (size_t)n_rays * sizeof(RtRay), hipMemcpyHostToDevice, ctx->stream));
-    const int r = rt_trace_rays_device(ctx, scene, options, ctx->rays_tmp.p, n_rays, ctx->hits_tmp.p, stats);
+    const int r = ray_query_device(ctx, scene, options, ctx->rays_tmp.p, n_rays, ctx->hits_tmp.p, stats, kind);
     if (r != RT_OK) return r;
-    HIP_TRY(ctx, hipMemcpyAsync(hits_host, ctx->hits_tmp.p, (size_t)n_rays * sizeof(RtRayHit), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_host, ctx->hits_tmp.p, (size_t)n_rays * kind.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return RT_OK;
 }
 
+int rt_trace_rays_device(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const void* rays_device, uint64_t n_rays, void* hits_device, RtStats* stats) {
+    return ray_query_device(ctx, scene, options, rays_device, n_rays, hits_device, stats, kClosestHit);
+}
+int rt_trace_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const RtRay* rays_host, uint64_t n_rays, RtRayHit* hits_host, RtStats* stats) {
+    return ray_query_host(ctx, scene, options, rays_host, n_rays, hits_host, stats, kClosestHit);
+}
 // occlusion queries: the two entry points above with the any-hit kernels and one byte per ray
 int rt_occluded_rays_device(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const void* rays_device, uint64_t n_rays, void* occluded_device, RtStats* stats) {
-    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
-    const int v = trace_rays_refuse(ctx, scene, options, rays_device, n_rays, occluded_device, true, 1u); if (v != RT_OK) return v;
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n_rays == 0u) return RT_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int r = trace_rays_impl(ctx, scene, options, rays_device, n_rays, occluded_device, stats, true);
-    if (r != RT_OK) { const std::string keep = ctx->err; (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); ctx->err = keep; g_last_error = keep; }
-    return r;
+    return ray_query_device(ctx, scene, options, rays_device, n_rays, occluded_device, stats, kOcclusion);
 }
-
 int rt_occluded_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const RtRay* rays_host, uint64_t n_rays, uint8_t* occluded_host, RtStats* stats) {
-    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
-    const int v = trace_rays_refuse(ctx, scene, options, rays_host, n_rays, occluded_host, false, 1u); if (v != RT_OK) return v;
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n_rays == 0u) return RT_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(ctx, ctx->rays_tmp.ensure((size_t)n_rays * sizeof(RtRay)));
-    HIP_TRY(ctx, ctx->hits_tmp.ensure((size_t)n_rays));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->rays_tmp.p, rays_host, (size_t)n_rays * sizeof(RtRay), hipMemcpyHostToDevice, ctx->stream));
-    const int r = rt_occluded_rays_device(ctx, scene, options, ctx->rays_tmp.p, n_rays, ctx->hits_tmp.p, stats);
-    if (r != RT_OK) return r;
-    HIP_TRY(ctx, hipMemcpyAsync(occluded_host, ctx->hits_tmp.p, (size_t)n_rays, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return RT_OK;
+    return ray_query_host(ctx, scene, options, rays_host, n_rays, occluded_host, stats, kOcclusion);
 }
 
 // ---- first-hit features (include/rt_hip.h): albedo, normal and depth of the render's own camera rays, as per-pixel sums ---------------------
@@ -1330,59 +1329,27 @@ int rt_features_check(const RtParams* params, const RtFeatureOptions* options) {
 // the whole sample run of as many slots as the pool has room for; only a pass with more samples per pixel than pool slots is cut along the
 // samples too, its later parts folding on from the planes — the same additions in the same order, so the cut does not show.
 static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* opt, const RtFeatureBuffers* out, RtStats* stats,
-                         const rtk::FeatMomDev* moments = nullptr) {      // moments: the squared-sum planes of rt_render_feature_moments_device; the fold is then k_features_fold_moments
+                         const rtk::FeatMomDev* moments) {                // moments: the squared-sum planes of rt_render_feature_moments_device; the fold is then k_features_fold_moments
     using clk = std::chrono::steady_clock;
     const auto t_begin = clk::now();
     const bool timing = (prm->flags & RT_FLAG_TIMING) != 0u;
     Tiling tl; make_tiling(*prm, tl);
-    const uint32_t sc = prm->shard_count <= 1u ? 1u : prm->shard_count, si = prm->shard_count <= 1u ? 0u : prm->shard_index;
-    // camera, frame and tiling as render_impl sets them: what new_camera_ray and slot_pixel read
-    rtk::RenderDev rd{};
-    auto cp3 = [](float* d, const RtVec3& v) { d[0] = (float)v.x; d[1] = (float)v.y; d[2] = (float)v.z; };
-    cp3(rd.cam_origin, cam->origin); cp3(rd.cam_llc, cam->lower_left_corner); cp3(rd.cam_horizontal, cam->horizontal); cp3(rd.cam_vertical, cam->vertical);
-    cp3(rd.cam_u, cam->u); cp3(rd.cam_v, cam->v);
-    rd.cam_lens_radius = (float)cam->lens_radius; rd.cam_time0 = (float)cam->time0; rd.cam_time1 = (float)cam->time1;
-    rd.width = prm->width; rd.height = prm->height; rd.seed = prm->seed;
-    rd.bg_mode = scene->bg_mode; for (int i = 0; i < 3; ++i) rd.bg[i] = scene->bg[i];
-    rd.tile_size = tl.ts; rd.tiles_x = tl.tiles_x; rd.tiles_y = tl.tiles_y; rd.shard_index = si; rd.shard_count = sc; rd.n_local_tiles = tl.n_local;
-    rd.div_width = rtk::make_fastdiv(prm->width); rd.div_ts = rtk::make_fastdiv(tl.ts); rd.div_ts2 = rtk::make_fastdiv(tl.ts * tl.ts); rd.div_tiles_x = rtk::make_fastdiv(tl.tiles_x);
+    rtk::RenderDev rd = frame_render_dev(scene, cam, prm, tl);
     rd.div_nblocks = rtk::make_fastdiv(1u); rd.n_blocks = 1u;                 // (a walk needs the queue geometry only; first_in_shade = 0: the record's time slot is the ray's time)
-    const uint64_t n_slots = sc <= 1u ? (uint64_t)prm->width * prm->height : (uint64_t)tl.n_local * tl.ts * tl.ts;
+    const uint64_t n_slots = rd.shard_count <= 1u ? (uint64_t)prm->width * prm->height : (uint64_t)tl.n_local * tl.ts * tl.ts;
     if (n_slots == 0u) return RT_OK;
     if (n_slots > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "more than 2^32 - 1 output slots in one shard (shard the image further)");
     const uint64_t spp = prm->samples_per_pixel, n_rays = n_slots * spp;
 
-    // the pool, by the renderer's rule (trace_rays_impl), plus 32 bytes of feature record per ray in flight
-    const size_t rec[5] = {16, 16, 8, 16, 4};   // ray_o ray_d hit s0 sd
-    size_t slot_bytes = 32; for (size_t b : rec) slot_bytes += b;
-    uint32_t P = opt->pool_slots ? opt->pool_slots : (1u << 28);
-    P = (uint32_t)std::min<uint64_t>(P, n_rays);
-    if (!opt->pool_slots) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            size_t held = ctx->feature_rec.bytes; for (int a = 0; a < 5; ++a) held += ctx->pool[0][a].bytes;
-            const size_t budget = (free_b + held) * 7 / 10;
-            while (P > (1u << 20) && (size_t)P * slot_bytes > budget) P >>= 1;
-        }
-    }
-    constexpr uint32_t kGrain = 512u * rtk::kQueues;
-    P = std::max<uint32_t>(kGrain, (uint32_t)std::min<uint64_t>(((uint64_t)P + kGrain - 1u) / kGrain * kGrain, 0xFFFFF000ull));
+    // one pool, every ray in flight, plus 32 bytes of feature record per slot
+    const uint32_t P = pool_grain(pool_size(opt->pool_slots, n_rays, pool_slot_bytes(5) + 32, pool_held_bytes(ctx, 0, 5) + ctx->feature_rec.bytes, 0));
     rd.queue_cap = P / rtk::kQueues; rd.q_lo = 0u; rd.q_n = rtk::kQueues; rd.q_shift = rtk::kQShift;
     rtk::PoolDev pd{};
-    for (int a = 0; a < 5; ++a) HIP_TRY(ctx, ctx->pool[0][a].ensure((size_t)P * rec[a]));
+    { const int r = pool_bind(ctx, 0, P, 5, pd); if (r != RT_OK) return r; }
     HIP_TRY(ctx, ctx->feature_rec.ensure((size_t)P * 32u));
-    pd.ray_o = (rtd::Float4*)ctx->pool[0][0].p; pd.ray_d = (rtd::Float4*)ctx->pool[0][1].p; pd.hit = (uint2*)ctx->pool[0][2].p;
-    pd.s0 = (rtd::Float4*)ctx->pool[0][3].p; pd.sd = (uint32_t*)ctx->pool[0][4].p; pd.s1 = nullptr;
-    // the render's counter block (render_impl): line 1 queue heads, line 2 the queues' sizes, line 3 what k_extend zeroes for a k_shade that never runs here
-    constexpr size_t kLine = 128, kQ = rtk::kQueues;
-    const size_t counter_bytes = 4 * kQ * kLine + sizeof(unsigned long long) * 16;
-    HIP_TRY(ctx, ctx->counters.ensure(counter_bytes));
-    char* cbase = (char*)ctx->counters.p;
-    uint32_t* c_head = (uint32_t*)(cbase + 1 * kQ * kLine);
-    uint32_t* c_count = (uint32_t*)(cbase + 2 * kQ * kLine);
-    uint32_t* c_other = (uint32_t*)(cbase + 3 * kQ * kLine);
-    unsigned long long* c64 = (unsigned long long*)(cbase + 4 * kQ * kLine);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, counter_bytes, ctx->stream));
+    CounterBlock cb;   // one pool: count[0] the queues' sizes, count[1] what k_extend zeroes for a k_shade that never runs here
+    HIP_TRY(ctx, cb.ensure(ctx));
+    HIP_TRY(ctx, cb.zero_all());
 
     rtk::LaunchCfg cfg{};
     uint32_t extend_geometry[2] = {0u, 0u};
@@ -1391,14 +1358,7 @@ static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, 
     fd.first_sample = opt->first_sample; fd.rec = (rtd::Float4*)ctx->feature_rec.p;
     fd.albedo = (float*)out->albedo_sum; fd.normal = (float*)out->normal_sum; fd.depth = (float*)out->depth_sum; fd.hits = (uint32_t*)out->hits;
 
-    size_t ev_used = 0;
-    auto next_event = [&](hipEvent_t& ev) -> hipError_t {
-        if (ev_used == ctx->events.size()) { hipEvent_t e; hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; ctx->events.push_back(e); }
-        ev = ctx->events[ev_used++];
-        return hipEventRecord(ev, ctx->stream);
-    };
-    struct Span { hipEvent_t a, b; int kind; };
-    std::vector<Span> spans;
+    StreamTimer tm{ctx};
     uint32_t launched = 0u;
     const uint32_t nk_max = (uint32_t)std::min<uint64_t>(spp, P), ns_max = P / nk_max;      // samples and slots of a chunk: nk * ns <= P
     for (uint64_t k0 = 0; k0 < spp; k0 += nk_max) {
@@ -1408,54 +1368,63 @@ static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, 
             fd.slot0 = (uint32_t)slot0; fd.ns = (uint32_t)std::min<uint64_t>(ns_max, n_slots - slot0); fd.div_ns = rtk::make_fastdiv(fd.ns);
             const uint32_t n = fd.ns * fd.nk;
             hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr, ed = nullptr, ee = nullptr;
-            if (launched != 0u) HIP_TRY(ctx, hipMemsetAsync(cbase, 0, 4 * kQ * kLine, ctx->stream));     // heads and sizes of the chunk before (the 64-bit statistics stay)
-            if (timing) HIP_TRY(ctx, next_event(ea));
-            LAUNCH_TRY(rtk::launch_features_import(rd, fd, pd, c_count, c64, ctx->stream));
-            if (timing) HIP_TRY(ctx, next_event(eb));
+            if (launched != 0u) HIP_TRY(ctx, cb.zero_queue_lines());
+            if (timing) HIP_TRY(ctx, tm.mark(ea));
+            LAUNCH_TRY(rtk::launch_features_import(rd, fd, pd, cb.count[0], cb.c64, ctx->stream));
+            if (timing) HIP_TRY(ctx, tm.mark(eb));
             cfg.max_rays = n;
-            LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd, rd, c_count, c_head, c_other, c64, false, ctx->stream));
-            if (timing) HIP_TRY(ctx, next_event(ec));
+            LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd, rd, cb.count[0], cb.head, cb.count[1], cb.c64, false, ctx->stream));
+            if (timing) HIP_TRY(ctx, tm.mark(ec));
             // a queue holds at most its share of the chunk's 512-ray groups
             const uint32_t per_queue = std::min<uint32_t>(rd.queue_cap, ((n + 511u) / 512u + rtk::kQueues - 1u) / rtk::kQueues * 512u);
-            LAUNCH_TRY(rtk::launch_features_export(cfg, scene->dev, rd, fd, pd, per_queue, c_count, ctx->stream));
-            if (timing) HIP_TRY(ctx, next_event(ed));
+            LAUNCH_TRY(rtk::launch_features_export(cfg, scene->dev, rd, fd, pd, per_queue, cb.count[0], ctx->stream));
+            if (timing) HIP_TRY(ctx, tm.mark(ed));
             if (moments) LAUNCH_TRY(rtk::launch_features_fold_moments(rd, fd, *moments, ctx->stream));
             else LAUNCH_TRY(rtk::launch_features_fold(rd, fd, ctx->stream));
-            if (timing) { HIP_TRY(ctx, next_event(ee)); spans.push_back({ea, eb, 1}); spans.push_back({eb, ec, 0}); spans.push_back({ec, ed, 2}); spans.push_back({ed, ee, 3}); }
+            if (timing) { HIP_TRY(ctx, tm.mark(ee)); tm.span(ea, eb, 1); tm.span(eb, ec, 0); tm.span(ec, ed, 2); tm.span(ed, ee, 3); }
             ++launched;
         }
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, c64, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, cb.read_stats(ctx));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (stats) {
         double part_ms[4] = {0.0, 0.0, 0.0, 0.0};                     // extend, import, export, fold
-        for (const Span& s : spans) { float ms = 0.f; if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) part_ms[s.kind] += ms; }
+        tm.sum(part_ms);
         stats->extend_ms = part_ms[0]; stats->other_ms = part_ms[1] + part_ms[2] + part_ms[3];
         for (int k = 0; k < 3; ++k) stats->debug[k] = (uint64_t)(part_ms[k + 1] * 1000.0 + 0.5);     // microseconds of the import, export and fold kernels
         stats->samples = stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];
-        stats->debug[6] = extend_geometry[0]; stats->debug[7] = extend_geometry[1];
-        stats->iterations = launched; stats->extend_launches = launched; stats->pool_slots = P; stats->n_devices = 1u; stats->lds_top_nodes = scene->dev.n_top;
-        stats->scene_nodes = scene->n_nodes; stats->scene_prims = scene->n_prims; stats->scene_bytes = scene->bytes; stats->bvh_in_lds = scene->in_lds ? 1u : 0u;
+        stats->iterations = launched; stats->extend_launches = launched; stats->pool_slots = P;
+        scene_stats(stats, scene, extend_geometry);
         stats->render_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
     }
     return RT_OK;
 }
 
-int rt_render_features_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* options, const RtFeatureBuffers* buffers,
-                              RtStats* stats) {
+// What both feature entry points check, in two parts because the moments variant checks its own record in between: the call (a refused
+// call has written nothing), then the caller's planes — one wanted at least, each 16-byte aligned.
+static int features_refuse(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* options) {
     if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
     if (!scene || !cam) return set_err(ctx, RT_ERR_INVALID, "scene / cam is null");
     const int v = check_features(ctx, prm, options); if (v != RT_OK) return v;
     if (scene->features & rtk::F_MEDIUM)
         return set_err(ctx, RT_ERR_UNSUPPORTED, "first-hit features: the scene holds a ConstantMedium (the limit of ray queries: its hit is a draw of the path's medium stream)");
-    if (!buffers || (!buffers->albedo_sum && !buffers->normal_sum && !buffers->depth_sum && !buffers->hits)) return set_err(ctx, RT_ERR_INVALID, "no feature buffer is wanted (all four pointers are null)");
-    if (((uintptr_t)buffers->albedo_sum | (uintptr_t)buffers->normal_sum | (uintptr_t)buffers->depth_sum | (uintptr_t)buffers->hits) & 15u)
-        return set_err(ctx, RT_ERR_INVALID, "feature buffers must be 16-byte aligned");
+    return RT_OK;
+}
+static int feature_planes_refuse(RtCtx* ctx, std::initializer_list<const void*> planes, const char* none_wanted) {
+    uintptr_t any = 0; for (const void* p : planes) any |= (uintptr_t)p;
+    if (!any) return set_err(ctx, RT_ERR_INVALID, none_wanted);
+    if (any & 15u) return set_err(ctx, RT_ERR_INVALID, "feature buffers must be 16-byte aligned");
+    return RT_OK;
+}
+
+int rt_render_features_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* options, const RtFeatureBuffers* buffers,
+                              RtStats* stats) {
+    const int v = features_refuse(ctx, scene, cam, prm, options); if (v != RT_OK) return v;
+    const RtFeatureBuffers none{nullptr, nullptr, nullptr, nullptr}, &b = buffers ? *buffers : none;
+    const int w = feature_planes_refuse(ctx, {b.albedo_sum, b.normal_sum, b.depth_sum, b.hits}, "no feature buffer is wanted (all four pointers are null)"); if (w != RT_OK) return w;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int r = features_impl(ctx, scene, cam, prm, options, buffers, stats);
-    if (r != RT_OK) { const std::string keep = ctx->err; (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); ctx->err = keep; g_last_error = keep; }
-    return r;
+    return drain_on_failure(ctx, features_impl(ctx, scene, cam, prm, options, buffers, stats, nullptr));
 }
 
 // ---- first-hit features, second moments (include/rt_hip.h): the same pass, with the per-slot sums of squares beside the sums ---------------
@@ -1469,25 +1438,16 @@ int rt_feature_moments_check(const RtParams* params, const RtFeatureOptions* opt
 
 int rt_render_feature_moments_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* options,
                                      const RtFeatureMomentBuffers* b, RtStats* stats) {
-    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
-    if (!scene || !cam) return set_err(ctx, RT_ERR_INVALID, "scene / cam is null");
-    const int v = check_features(ctx, prm, options); if (v != RT_OK) return v;
-    if (scene->features & rtk::F_MEDIUM)
-        return set_err(ctx, RT_ERR_UNSUPPORTED, "first-hit features: the scene holds a ConstantMedium (the limit of ray queries: its hit is a draw of the path's medium stream)");
+    const int v = features_refuse(ctx, scene, cam, prm, options); if (v != RT_OK) return v;
     if (!b) return set_err(ctx, RT_ERR_INVALID, "feature moment buffers are null");
     if (b->struct_bytes < sizeof(RtFeatureMomentBuffers) || b->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtFeatureMomentBuffers.struct_bytes is not set (sizeof(RtFeatureMomentBuffers))");
-    if (!b->albedo_sum && !b->normal_sum && !b->depth_sum && !b->hits && !b->albedo_sq_sum && !b->normal_sq_sum && !b->depth_sq_sum)
-        return set_err(ctx, RT_ERR_INVALID, "no feature buffer is wanted (all seven pointers are null)");
-    if (((uintptr_t)b->albedo_sum | (uintptr_t)b->normal_sum | (uintptr_t)b->depth_sum | (uintptr_t)b->hits | (uintptr_t)b->albedo_sq_sum | (uintptr_t)b->normal_sq_sum |
-         (uintptr_t)b->depth_sq_sum) & 15u)
-        return set_err(ctx, RT_ERR_INVALID, "feature buffers must be 16-byte aligned");
+    const int w = feature_planes_refuse(ctx, {b->albedo_sum, b->normal_sum, b->depth_sum, b->hits, b->albedo_sq_sum, b->normal_sq_sum, b->depth_sq_sum},
+                                        "no feature buffer is wanted (all seven pointers are null)"); if (w != RT_OK) return w;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const RtFeatureBuffers sums{b->albedo_sum, b->normal_sum, b->depth_sum, b->hits};
     const rtk::FeatMomDev fm{(float*)b->albedo_sq_sum, (float*)b->normal_sq_sum, (float*)b->depth_sq_sum};
-    const int r = features_impl(ctx, scene, cam, prm, options, &sums, stats, &fm);
-    if (r != RT_OK) { const std::string keep = ctx->err; (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); ctx->err = keep; g_last_error = keep; }
-    return r;
+    return drain_on_failure(ctx, features_impl(ctx, scene, cam, prm, options, &sums, stats, &fm));
 }
 
 int rt_untile(const RtParams* p, const float* gathered, float* rgb_sum) { return untile_host<float>(p, gathered, rgb_sum); }

@@ -13,8 +13,14 @@ namespace rti {
 
 extern thread_local std::string g_last_error;
 
+// A grow-only device allocation that frees itself with its owner: a context, a scene or a scope, each destroyed with its device
+// current. Never copied, and never in static storage (its hipFree would then run at process exit, after the runtime).
 struct DevBuf {
     void* p = nullptr; size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
     hipError_t ensure(size_t n) {
         if (n <= bytes && p) return hipSuccess;
         if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
@@ -23,14 +29,6 @@ struct DevBuf {
         if (e == hipSuccess) bytes = n;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-};
-// a DevBuf that frees itself with its owner (rt_ctx_destroy deletes the context with its device current)
-struct OwnedDevBuf : DevBuf {
-    OwnedDevBuf() = default;
-    OwnedDevBuf(const OwnedDevBuf&) = delete;
-    OwnedDevBuf& operator=(const OwnedDevBuf&) = delete;
-    ~OwnedDevBuf() { release(); }
 };
 
 }  // namespace rti
@@ -54,10 +52,10 @@ struct RtCtx {
     hipEvent_t ev_gather[2] = {nullptr, nullptr}; // brackets the exchange (RtStats.gather_ms); made at the first gather, kept
     rti::DevBuf list_map;                        // adaptive sampling: output slot -> list index of a list pass (rt_render_pass_pixels_device)
     rti::DevBuf sel_masks, sel_offsets, adaptive_word;   // rt_adaptive_select's wave ballots and their scan; the list check's verdict / the list's length
-    rti::OwnedDevBuf rays_tmp, hits_tmp;         // rt_trace_rays (host variant): the caller's rays and hits on their way to and from the device
-    rti::OwnedDevBuf feature_rec;                // rt_render_features_device: the per-ray feature records of a chunk between export and fold (kernels.h FeatDev)
-    rti::OwnedDevBuf denoise_planes;             // rt_denoise_device: per-pixel mean and variance of the mean, three float2 planes (denoise.hip)
-    rti::OwnedDevBuf denoise_guide;              // rt_denoise_guided_device: per pixel one 16-byte record of 8 binary16 guide components (denoise.hip);
+    rti::DevBuf rays_tmp, hits_tmp;              // rt_trace_rays (host variant): the caller's rays and hits on their way to and from the device
+    rti::DevBuf feature_rec;                     // rt_render_features_device: the per-ray feature records of a chunk between export and fold (kernels.h FeatDev)
+    rti::DevBuf denoise_planes;                  // rt_denoise_device: per-pixel mean and variance of the mean, three float2 planes (denoise.hip)
+    rti::DevBuf denoise_guide;                   // rt_denoise_guided_device: per pixel one 16-byte record of 8 binary16 guide components (denoise.hip);
                                                  // rt_denoise_guided_moments_device: those, then per pixel one 8-byte record of the standard errors
     uint32_t fail_renders = 0;                   // rt_test_fail_next_renders: renders still to fail (fault injection for the failure-path tests)
 };

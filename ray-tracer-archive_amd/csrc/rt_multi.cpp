@@ -403,7 +403,6 @@ int rt_comm_selftest(RtCtx* ctx) {
     for (size_t i = 0; i < n; ++i) src[i] = (uint8_t)((i * 2654435761u) >> 13);
     DevBuf a, b;
     HIP_TRY(ctx, a.ensure(n)); HIP_TRY(ctx, b.ensure(n));
-    struct Free { DevBuf &x, &y; ~Free() { x.release(); y.release(); } } fr{a, b};
     HIP_TRY(ctx, hipMemcpyAsync(a.p, src.data(), n, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(b.p, 0, n, ctx->stream));
     NCCL_TRY(ctx, R->GroupStart());
@@ -443,9 +442,10 @@ const char* rt_last_error_multi(const RtMultiCtx* m) { return m ? m->err.c_str()
 int rt_ctx_destroy_multi(RtMultiCtx* m) {
     if (!m) return RT_OK;
     m->workers.stop();
-    if (!m->ctx.empty() && m->ctx[0]) { (void)hipSetDevice(m->ctx[0]->device); m->frame.release(); if (m->host_pinned) (void)hipHostFree(m->host_pinned); }
+    const int root = !m->ctx.empty() && m->ctx[0] ? m->ctx[0]->device : -1;
     for (RtCtx* c : m->ctx) rt_ctx_destroy(c);
-    delete m;
+    if (root >= 0) { (void)hipSetDevice(root); if (m->host_pinned) (void)hipHostFree(m->host_pinned); }
+    delete m;   // m->frame frees itself here, with the root device current and every stream that used it drained
     return RT_OK;
 }
 
