@@ -77,9 +77,10 @@ pub const RT_BG_SKY_GRADIENT: i32 = 1;   // book-1 sky (not in the reference)
 pub const RT_BVH_REFERENCE: i32 = 0;     // BVHNode::construct as intended (bvh.rs:77-130)
 pub const RT_BVH_SAH: i32 = 1;           // binned SAH: same picture, fewer node visits
 
+pub const RT_SCENE_LIGHTS_ALL_SHAPES: u32 = 1;   // RtSceneDesc.scene_flags: rects of any orientation, triangles, boxes and wrapped members are sampled as lights
 #[repr(C)]
 pub struct RtSceneDesc {
-    pub abi_version: u32, pub _pad0: u32,
+    pub abi_version: u32, pub scene_flags: u32,
     pub hittables: *const RtHittable, pub n_hittables: u64,
     pub children: *const i32, pub n_children: u64,
     pub materials: *const RtMaterial, pub n_materials: u64,
@@ -218,6 +219,14 @@ pub struct RtCompileInfo {
     pub n_first: u32, pub first: [u32; 4], pub n_tri_attrs: u32,
 }
 
+pub const RT_LIGHTQ_DIRECTION_GIVEN: u32 = 1;    // RtLightQuery.flags: evaluate the pdf of the caller's d, draw nothing
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtLightQuery { pub p: [f32; 3], pub flags: u32, pub rng_state: u64, pub d: [f32; 3], pub _pad: f32 }       // 40 B
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtLightSample { pub d: [f32; 3], pub pdf: f32, pub light: i32, pub n_draws: u32 }                           // 24 B
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtLightQueryOptions { pub struct_bytes: u32, pub flags: u32 }
+
 pub const RT_OUT_RGB_SUM_F32: u32 = 0;
 pub const RT_OUT_RGB8: u32 = 1;
 pub const RT_COMM_ID_BYTES: usize = 128;
@@ -294,6 +303,11 @@ extern "C" {
                                    occluded_device: *mut c_void, stats: *mut RtStats) -> c_int;
     pub fn rt_occluded_rays(ctx: *mut RtCtx, scene: *const RtScene, options: *const RtRayQueryOptions, rays_host: *const RtRay, n_rays: u64,
                             occluded_host: *mut u8, stats: *mut RtStats) -> c_int;
+    /// the scene's own light sampler: one RtLightSample per RtLightQuery (device memory, 8-byte aligned); lights = -1 is RT_ERR_UNSUPPORTED
+    pub fn rt_sample_lights_device(ctx: *mut RtCtx, scene: *const RtScene, options: *const RtLightQueryOptions, queries_device: *const c_void, n: u64,
+                                   results_device: *mut c_void, stats: *mut RtStats) -> c_int;
+    pub fn rt_sample_lights(ctx: *mut RtCtx, scene: *const RtScene, options: *const RtLightQueryOptions, queries_host: *const RtLightQuery, n: u64,
+                            results_host: *mut RtLightSample, stats: *mut RtStats) -> c_int;
     /// host only: validates a feature pass (params, options)
     pub fn rt_features_check(params: *const RtParams, options: *const RtFeatureOptions) -> c_int;
     /// first-hit feature sums of samples [first_sample, first_sample + samples_per_pixel) into the caller's device planes (null = not wanted)

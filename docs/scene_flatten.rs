@@ -87,7 +87,7 @@ impl SceneBuilder {
     /// (main.rs:669-684) or -1 for the book-1/2 integrator; `background` = main.rs:692.
     pub fn desc(&self, world: i32, lights: i32, background_mode: i32, background: crate::vec3::Vec3, bvh_seed: u64) -> RtSceneDesc {
         RtSceneDesc {
-            abi_version: RT_ABI_VERSION, _pad0: 0,
+            abi_version: RT_ABI_VERSION, scene_flags: 0,   // the reference's lights: XzRect and Sphere (RT_SCENE_LIGHTS_ALL_SHAPES samples every shape)
             hittables: self.hittables.as_ptr(), n_hittables: self.hittables.len() as u64,
             children: self.children.as_ptr(), n_children: self.children.len() as u64,
             materials: self.materials.as_ptr(), n_materials: self.materials.len() as u64,

@@ -144,9 +144,30 @@ typedef enum RtBvhBuilder {
                               node visits on large scenes; SURVEY.md 8(f) rank 1 */
 } RtBvhBuilder;
 
+/* ---- RtSceneDesc.scene_flags --------------------------------------------------------------------------------------------------------------
+ * RT_SCENE_LIGHTS_ALL_SHAPES: every member of the lights list is sampled as a light. The reference implements pdf_value / random for XzRect
+ * and Sphere only (aarect.rs:107-125, sphere.rs:75-90); every other member takes the trait defaults (pdf 0, direction (1,0,0):
+ * hittable.rs:54-59), which is what the library does with the flag clear, bit for bit. With the flag set a member may be
+ *   - an XY, XZ or YZ rect: two draws, range(a0, a1) then range(b0, b1), the point on the plane; pdf = t^2 |v|^2 / (|cos| area);
+ *   - a triangle: two draws r1 then r2, s = sqrt(r1), the point (1 - s) v0 + s (1 - r2) v1 + s r2 v2; pdf = t^2 |v|^2 / (|cos| area) with
+ *     the hit test the walk uses (closed edges);
+ *   - a box: one next64() % 6 pick of a side in boxes.rs order (z1 z0 y1 y0 x1 x0), then that rect's two draws; pdf_value = 1/6 of the sum
+ *     over the sides the ray meets (the list rule, hittable_list.rs:73-84, applied to the box's own sides);
+ *   - a sphere, as ever;
+ *   - any chain of up to 6 Translate / RotateY / FlipFace above one of these: the chain is composed into one rigid map at upload, the pdf
+ *     is evaluated in the member's own space (a rigid map keeps it), a drawn direction is rotated back; FlipFace changes nothing.
+ * Anything else in the lights list — a moving sphere, a medium, a nested list, a BVH, a rect or triangle of zero area, a deeper chain — is
+ * RT_ERR_INVALID with the reason, and nothing is uploaded. The list semantics stay the reference's: the pick is next64() % n, uniform over
+ * the members whatever their size, and the list's pdf is the mean of the members' pdfs, occluded or not.
+ * LIMIT: the cost is linear in the number of lights per Lambertian bounce (every member's pdf is evaluated for every scattered ray); an
+ * emissive mesh of thousands of triangles is slow. There is no light BVH and no area-weighted pick.
+ * RtStats.prim_tests counts the light tests with their kind: triangles in the triangle slot, rects and boxes (six each) in the rect slot,
+ * spheres in the sphere slot. A list of bare XZ rects and spheres runs the same kernels and uploads the same bytes with the flag as without. */
+enum { RT_SCENE_LIGHTS_ALL_SHAPES = 1u };
+
 typedef struct RtSceneDesc {
     uint32_t abi_version;   /* RT_ABI_VERSION */
-    uint32_t _pad0;
+    uint32_t scene_flags;   /* RT_SCENE_*; an unknown bit is RT_ERR_INVALID. 0 = the reference's behaviour */
     const RtHittable* hittables;  uint64_t n_hittables;
     const int32_t*    children;   uint64_t n_children;
     const RtMaterial* materials;  uint64_t n_materials;
@@ -633,6 +654,36 @@ int rt_occluded_rays_device(RtCtx* ctx, const RtScene* scene, const RtRayQueryOp
 int rt_occluded_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options /* NULL = defaults */, const RtRay* rays_host, uint64_t n_rays,
                      uint8_t* occluded_host, RtStats* stats);
 
+/* ---- light-sample queries: the scene's own light sampler, query by query -------------------------------------------------------------------
+ *
+ * What a host that does its own direct lighting needs beside rt_occluded_rays: the directions of its shadow rays drawn from the scene's
+ * lights list, and their pdf. results[i] is what the Lambertian branch of a render computes for its light half at the point p, by the same
+ * device functions (not a restatement):
+ *   - the device seeds the path generator with (rng_state, 0 draws); ONE pick k = next64() % n_lights (hittable_list.rs:81-84), then the
+ *     picked member's `random` from p (RtSceneDesc.scene_flags has the draw orders): d = the direction (not normalised: the vector from p
+ *     to the sampled point for a rect, triangle or box), light = k, n_draws = the draws consumed (pick included);
+ *   - pdf = the list's pdf_value at (p, d): the mean over ALL members of each member's pdf (hittable_list.rs:73-80), 0 for a member the
+ *     ray misses. Occlusion is not looked at.
+ *   - RT_LIGHTQ_DIRECTION_GIVEN in a query's flags: nothing is drawn; pdf is evaluated for the caller's d, light = -1, n_draws = 0 and d
+ *     is copied through. For the d of a drawn result this returns the drawn result's pdf, bit for bit.
+ * Works with RT_SCENE_LIGHTS_ALL_SHAPES set or clear (clear: the reference's kinds, LK_DEFAULT members included). A scene with lights = -1
+ * is RT_ERR_UNSUPPORTED. An unknown bit in RtLightQueryOptions.flags (known: RT_FLAG_TIMING), struct_bytes < sizeof(RtLightQueryOptions),
+ * n >= 2^32, or a NULL queries / results pointer with n > 0 is RT_ERR_INVALID; device buffers must be 8-byte aligned; a refused call
+ * writes nothing. n == 0 is a no-op. An unknown bit in a QUERY's flags is ignored. One kernel on the context's stream, one lane per
+ * query, no pool; results[i] is a function of (scene, query i) alone. RtStats: samples = n; render_ms; with RT_FLAG_TIMING other_ms =
+ * the kernel. Both variants block until done. */
+enum { RT_LIGHTQ_DIRECTION_GIVEN = 1u };
+typedef struct RtLightQuery  { float p[3]; uint32_t flags; uint64_t rng_state; float d[3]; float _pad; } RtLightQuery;      /* 40 B */
+typedef struct RtLightSample { float d[3]; float pdf; int32_t light; uint32_t n_draws; } RtLightSample;                      /* 24 B */
+typedef struct RtLightQueryOptions {
+    uint32_t struct_bytes;    /* sizeof(RtLightQueryOptions) as the caller compiled it (the struct may grow at its end) */
+    uint32_t flags;           /* RT_FLAG_TIMING; an unknown bit is RT_ERR_INVALID */
+} RtLightQueryOptions;
+int rt_sample_lights_device(RtCtx* ctx, const RtScene* scene, const RtLightQueryOptions* options /* NULL = defaults */, const void* queries_device, uint64_t n,
+                            void* results_device, RtStats* stats);
+int rt_sample_lights(RtCtx* ctx, const RtScene* scene, const RtLightQueryOptions* options /* NULL = defaults */, const RtLightQuery* queries_host, uint64_t n,
+                     RtLightSample* results_host, RtStats* stats);
+
 /* ---- first-hit features: albedo, normal and depth of the render's own camera rays ----------------------------------------------------------
  *
  * What a feature-guided filter or an external denoiser starts from: per-pixel SUMS, over a range of samples, of the first hit's colour,
@@ -773,7 +824,8 @@ typedef struct RtCompileInfo {
     uint64_t n_nodes;       /* threaded-BVH records */
     uint64_t n_box_nodes;   /* of which carry a box (= BVHNode count of the reference tree) */
     uint64_t n_spheres, n_moving, n_rects, n_tris, n_media, n_xforms, n_lights, n_materials;
-    uint32_t features;      /* kernel feature bits the scene needs (128: a triangle on the device carries attributes, n_tri_attrs > 0) */
+    uint32_t features;      /* kernel feature bits the scene needs (128: a triangle on the device carries attributes, n_tri_attrs > 0;
+                               256: RT_SCENE_LIGHTS_ALL_SHAPES and a light that is not a bare XZ rect or sphere) */
     uint32_t fits_lds;      /* nodes + sphere records fit the LDS staging budget */
     uint32_t n_first;       /* primitives tested when a walk begins instead of being met by it (none with RT_LAYOUT_LISTS_AS_REFERENCE) ... */
     uint32_t first[4];      /* ... as leaf words: kind << 28 | count << 24 | first index (kind 1 = sphere, 2 = moving sphere, 5 = medium); they are not in the node records */

@@ -9,7 +9,7 @@ from . import _abi  # noqa: F401
 from .api import (Context, Scene, HostScene, RtError, camera_new, lib, lib_path, tonemap, write_color, write_png, write_image, untile,
                   output_floats, make_params, compile_info, compile_dump, MultiContext, MultiScene, comm_unique_id, untile_rgb8, wide_layout_check, runtime_libraries, upload_options,
                   pass_check, scene_fingerprint, adaptive_check, adaptive_options, denoise_check, denoise_options, denoise_guide, denoise_guided_check,
-                  RAY_DTYPE, RAYHIT_DTYPE, ray_query_check, ray_query_options, feature_options, features_check,
+                  RAY_DTYPE, RAYHIT_DTYPE, LIGHTQUERY_DTYPE, LIGHTSAMPLE_DTYPE, ray_query_check, ray_query_options, feature_options, features_check,
                   denoise_guide_moments, denoise_guided_moments_check, feature_moment_buffers, feature_moments_check)  # noqa: F401
 from .features import feature_means  # noqa: F401
 from .adaptive import Adaptive, select_reference, check_counts, check_adaptive_checkpoint, slot_pixels  # noqa: F401
@@ -18,3 +18,4 @@ from .progressive import Progressive, check_checkpoint, std_error  # noqa: F401
 from .scene import SceneBuilder  # noqa: F401
 from .scene_json import JsonScene, load_scene, parse_obj, parse_obj_attrs  # noqa: F401
 from .mesh import icosphere, interpolate_reference, sphere_uv  # noqa: F401
+from .lights import light_reference, solid_angle_triangle  # noqa: F401

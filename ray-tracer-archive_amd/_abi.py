@@ -25,6 +25,9 @@ RT_RAYHIT_HIT, RT_RAYHIT_FRONT_FACE, RT_RAYHIT_INVALID_RAY = 1, 2, 4
 RT_FEATURES_ACCUMULATE = 1
 RT_TRI_NORMALS, RT_TRI_UVS = 1, 2
 RT_FEATURE_TRI_ATTR = 128      # RtCompileInfo.features: a triangle carries attributes (csrc/kernels.h F_TRI_ATTR)
+RT_FEATURE_LIGHTS_EXT = 256    # RtCompileInfo.features: the lights table holds extended records (csrc/kernels.h F_LIGHTS_EXT)
+RT_SCENE_LIGHTS_ALL_SHAPES = 1  # RtSceneDesc.scene_flags
+RT_LIGHTQ_DIRECTION_GIVEN = 1   # RtLightQuery.flags
 # RtUploadOptions.layout_flags
 (RT_LAYOUT_LISTS_AS_REFERENCE, RT_LAYOUT_LISTS_CULLED, RT_LAYOUT_NO_MEMBER_BOXES, RT_LAYOUT_MEMBER_BOXES, RT_LAYOUT_CHILD_ORDER_AS_REFERENCE,
  RT_LAYOUT_SCENE_IN_HBM, RT_LAYOUT_NODES_32B, RT_LAYOUT_NO_SHADE_TABLES_IN_LDS, RT_LAYOUT_NO_EXTEND_TABLES_IN_LDS, RT_LAYOUT_WIDE_NODES) = (1 << k for k in range(10))
@@ -64,7 +67,7 @@ class RtHittable(C.Structure):
 
 
 class RtSceneDesc(C.Structure):
-    _fields_ = [("abi_version", C.c_uint32), ("_pad0", C.c_uint32),
+    _fields_ = [("abi_version", C.c_uint32), ("scene_flags", C.c_uint32),
                 ("hittables", C.POINTER(RtHittable)), ("n_hittables", C.c_uint64),
                 ("children", C.POINTER(C.c_int32)), ("n_children", C.c_uint64),
                 ("materials", C.POINTER(RtMaterial)), ("n_materials", C.c_uint64),
@@ -153,6 +156,18 @@ class RtRayQueryOptions(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32), ("pool_slots", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class RtLightQuery(C.Structure):
+    _fields_ = [("p", C.c_float * 3), ("flags", C.c_uint32), ("rng_state", C.c_uint64), ("d", C.c_float * 3), ("_pad", C.c_float)]
+
+
+class RtLightSample(C.Structure):
+    _fields_ = [("d", C.c_float * 3), ("pdf", C.c_float), ("light", C.c_int32), ("n_draws", C.c_uint32)]
+
+
+class RtLightQueryOptions(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class RtFeatureOptions(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32), ("first_sample", C.c_uint32), ("pool_slots", C.c_uint32)]
 
@@ -182,6 +197,7 @@ RT_HIP_SYMBOLS = ["rt_ctx_create", "rt_ctx_destroy", "rt_scene_upload", "rt_scen
                   "rt_adaptive_check", "rt_adaptive_select", "rt_render_pass_pixels_device", "rt_resolve_counts_device",
                   "rt_denoise_check", "rt_denoise_device", "rt_denoise_guided_check", "rt_denoise_guided_device",
                   "rt_ray_query_check", "rt_trace_rays_device", "rt_trace_rays", "rt_occluded_rays_device", "rt_occluded_rays",
+                  "rt_sample_lights_device", "rt_sample_lights",
                   "rt_features_check", "rt_render_features_device",
                   "rt_feature_moments_check", "rt_render_feature_moments_device", "rt_denoise_guided_moments_check", "rt_denoise_guided_moments_device"]
 RT_HOST_SYMBOLS = ["rt_host_scene_create", "rt_host_scene_desc", "rt_host_scene_camera", "rt_host_scene_destroy", "rt_host_camera_new",
@@ -252,6 +268,10 @@ def declare(lib):
     lib.rt_occluded_rays_device.argtypes = [vp, vp, P(RtRayQueryOptions), vp, u64, vp, P(RtStats)]
     lib.rt_occluded_rays.restype = i32
     lib.rt_occluded_rays.argtypes = [vp, vp, P(RtRayQueryOptions), vp, u64, vp, P(RtStats)]
+    lib.rt_sample_lights_device.restype = i32
+    lib.rt_sample_lights_device.argtypes = [vp, vp, P(RtLightQueryOptions), vp, u64, vp, P(RtStats)]
+    lib.rt_sample_lights.restype = i32
+    lib.rt_sample_lights.argtypes = [vp, vp, P(RtLightQueryOptions), vp, u64, vp, P(RtStats)]
     lib.rt_features_check.restype = i32
     lib.rt_features_check.argtypes = [P(RtParams), P(RtFeatureOptions)]
     lib.rt_render_features_device.restype = i32

@@ -106,6 +106,9 @@ def denoise_guided_moments_check(width, height, options, guide):
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("time", np.float32), ("d", np.float32, 3), ("t_max", np.float32)])
 RAYHIT_DTYPE = np.dtype([("t", np.float32), ("hittable", np.int32), ("material", np.int32), ("flags", np.uint32),
                          ("p", np.float32, 3), ("u", np.float32), ("n", np.float32, 3), ("v", np.float32)])
+# ... and of RtLightQuery / RtLightSample ("light-sample queries"): 40 and 24 bytes
+LIGHTQUERY_DTYPE = np.dtype([("p", np.float32, 3), ("flags", np.uint32), ("rng_state", np.uint64), ("d", np.float32, 3), ("_pad", np.float32)])
+LIGHTSAMPLE_DTYPE = np.dtype([("d", np.float32, 3), ("pdf", np.float32), ("light", np.int32), ("n_draws", np.uint32)])
 
 
 def ray_query_options(flags=0, pool_slots=0):
@@ -324,6 +327,8 @@ def scene_fingerprint(desc, triangle_attrs=None):
             h.update(C.string_at(C.cast(im.data, C.c_void_p).value, im.width * im.height * 3))
     h.update(np.array([desc.world, desc.lights, desc.background_mode, desc.bvh_builder], dtype=np.int32).tobytes())
     h.update(np.array(desc.background.tuple(), dtype=np.float64).tobytes() + int(desc.bvh_seed).to_bytes(8, "little"))
+    if desc.scene_flags:                                     # (a scene without flags has the print it always had)
+        h.update(b"scene_flags" + int(desc.scene_flags).to_bytes(4, "little"))
     live = sorted((a for a in (triangle_attrs if triangle_attrs is not None else ()) if a.flags), key=lambda a: a.hittable)
     if live:
         h.update(b"triangle_attrs" + len(live).to_bytes(8, "little"))
@@ -544,6 +549,39 @@ class Context:
         _check(lib().rt_occluded_rays(self._h, scene._h, opt, C.c_void_p(rays.ctypes.data if n else None), n, C.c_void_p(out.ctypes.data if n else None),
                                       C.byref(st)), self._h)
         return (out, st.as_dict()) if with_stats else out
+
+    # ---- light-sample queries (include/rt_hip.h, "light-sample queries") ----
+    def _light_queries(self, scene, q, with_stats):
+        st = A.RtStats()
+        n = q.shape[0]
+        out = np.empty(n, dtype=LIGHTSAMPLE_DTYPE)
+        _check(lib().rt_sample_lights(self._h, scene._h, None, C.c_void_p(q.ctypes.data if n else None), n, C.c_void_p(out.ctypes.data if n else None),
+                                      C.byref(st)), self._h)
+        return (out, st.as_dict()) if with_stats else out
+
+    def sample_lights(self, scene, points, states, with_stats=False):
+        """rt_sample_lights: for every point (float32, shape (n, 3)) and generator state (uint64, n) one pick of the scene's lights list, the
+        picked member's draw and the list's pdf of the drawn direction — what a Lambertian bounce of a render does for its light half, by the
+        same device functions. Returns a LIGHTSAMPLE_DTYPE array: d (not normalised), pdf, light (the member's index), n_draws."""
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        states = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1)
+        if states.shape[0] != points.shape[0]:
+            raise ValueError("one generator state per point")
+        q = np.zeros(points.shape[0], dtype=LIGHTQUERY_DTYPE)
+        q["p"], q["rng_state"] = points, states
+        return self._light_queries(scene, q, with_stats)
+
+    def light_pdf(self, scene, points, dirs, with_stats=False):
+        """rt_sample_lights with RT_LIGHTQ_DIRECTION_GIVEN: the lights list's pdf_value at (point, direction), nothing drawn. Returns the pdfs
+        (float32, n)."""
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        if dirs.shape[0] != points.shape[0]:
+            raise ValueError("one direction per point")
+        q = np.zeros(points.shape[0], dtype=LIGHTQUERY_DTYPE)
+        q["p"], q["d"], q["flags"] = points, dirs, A.RT_LIGHTQ_DIRECTION_GIVEN
+        r = self._light_queries(scene, q, with_stats)
+        return (r[0]["pdf"].copy(), r[1]) if with_stats else r["pdf"].copy()
 
     # ---- first-hit features (include/rt_hip.h, "first-hit features"): device tensors only ----
     def render_features(self, scene, cam, params, first_sample=0, accumulate=False, albedo=None, normal=None, depth=None, hits=None, pool_slots=0,

@@ -132,5 +132,17 @@ struct Image { uint64_t offset; uint32_t width, height; };   // offset into the 
 // ---- lights (main.rs:669-686; only XzRect and Sphere implement pdf_value/random) ---------------------
 enum LightKind : uint32_t { LK_DEFAULT = 0, LK_XZRECT = 1, LK_SPHERE = 2 };
 struct Light { uint32_t kind; float p[5]; uint32_t _pad[2]; };   // rect: a0,a1,b0,b1,k   sphere: c.xyz, r
+// RT_SCENE_LIGHTS_ALL_SHAPES with a member that is not a bare XzRect or Sphere (kernels.h F_LIGHTS_EXT): the lights table then holds one
+// 96-byte LightX per member INSTEAD of the 32-byte records (three Light slots each, so the table's bytes, its place in the shade blob and
+// SceneDev stay what they are; only the instances compiled with F_LIGHTS_EXT read it this way). A scene without the bit keeps the records above.
+enum LightXKind : uint32_t { LX_RECT = 1, LX_SPHERE = 2, LX_TRI = 3, LX_BOX = 4 };
+struct LightX {
+    uint32_t kind;
+    uint32_t has_xform;      // 1: the member sits under Translate / RotateY wrappers, composed into xf (world -> the member's own space)
+    uint32_t _pad[2];
+    float p[12];             // rect: a0 a1 b0 b1 k kaxis(0 = Yz, 1 = Xz, 2 = Xy)   sphere: c.xyz r   triangle: v0 v1 v2   box: x0 x1 y0 y1 z0 z1
+    Xform xf;
+};
+static_assert(sizeof(Light) == 32 && sizeof(LightX) == 3 * sizeof(Light), "an extended light record takes three slots of the lights table");
 
 }  // namespace rtd

@@ -642,7 +642,7 @@ enum : int { M_HBM = 0, M_LDS = 1, M_TOP = 2, M_C16 = 3 };
 struct PathState;
 enum : uint32_t { SH_FINISHED = 1u, SH_TIME_ZERO = 2u };
 template <uint32_t FEAT> DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& d, float tm, PathState& s, Rng& g, uint32_t& depth, uint2 hit, V3& L,
-                                                     unsigned long long& c_light_rect, unsigned long long& c_light_sphere);
+                                                     unsigned long long& c_light_rect, unsigned long long& c_light_sphere, unsigned long long& c_light_tri);
 DEVI bool finish_sample(const RenderDev& rd, PathState& s, Rng& g, uint32_t& depth, V3 L, V3& o, V3& d, float& tm);
 template <bool LIST> DEVI void start_item(const RenderDev& rd, uint32_t work, PathState& s, Rng& g, V3& o, V3& d, float& tm);
 // L, the radiance of the sample in flight, is not part of the state: `emitted` is non-zero only for
@@ -843,7 +843,7 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
     };
     // ---- DRAIN: the lane's path, for its whole life ----
     PathState ps{}; Rng g; g.s = 0; g.n = 0; uint32_t depth = 0;
-    unsigned long long c_segments = 0, c_samples = 0, c_light_rect = 0, c_light_sphere = 0;
+    unsigned long long c_segments = 0, c_samples = 0, c_light_rect = 0, c_light_sphere = 0, c_light_tri = 0;
     const bool with_acc = rd.block_shift != 0u;
     // the root list's every-ray members (SceneDev::prologue), for a lane whose walk begins: world space, t_max = inf
     auto prologue = [&]() {
@@ -1172,7 +1172,7 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
                 if (lane_done) {
                     c_segments++;
                     V3 so = (FEAT & F_XFORM) ? ow : o, sd = (FEAT & F_XFORM) ? dw : d, L;
-                    const uint32_t sh = shade_segment<FEAT>(sc, rd, so, sd, tm, ps, g, depth, make_uint2(__float_as_uint(tmax), hit_prim), L, c_light_rect, c_light_sphere);
+                    const uint32_t sh = shade_segment<FEAT>(sc, rd, so, sd, tm, ps, g, depth, make_uint2(__float_as_uint(tmax), hit_prim), L, c_light_rect, c_light_sphere, c_light_tri);
                     if (sh & SH_TIME_ZERO) tm = 0.0f;
                     if (sh & SH_FINISHED) {
                         if (COUNT) c_samples++;
@@ -1204,12 +1204,14 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
         for (int off = 32; off > 0; off >>= 1) {
             c_segments += __shfl_down(c_segments, off);
             if (COUNT) { c_samples += __shfl_down(c_samples, off); c_light_rect += __shfl_down(c_light_rect, off); c_light_sphere += __shfl_down(c_light_sphere, off); }
+            if constexpr (COUNT && (FEAT & F_LIGHTS_EXT) != 0u) c_light_tri += __shfl_down(c_light_tri, off);
         }
         if (lane == 0u) {
             if (c_segments) atomicAdd(&counters[CTR_SEGMENTS], c_segments);
             if (COUNT && c_samples) atomicAdd(&counters[CTR_SAMPLES], c_samples);
             if (COUNT && c_light_rect) atomicAdd(&counters[CTR_PRIM_TESTS + 2], c_light_rect);
             if (COUNT && c_light_sphere) atomicAdd(&counters[CTR_PRIM_TESTS + 0], c_light_sphere);
+            if constexpr (COUNT && (FEAT & F_LIGHTS_EXT) != 0u) { if (c_light_tri) atomicAdd(&counters[CTR_PRIM_TESTS + 3], c_light_tri); }
         }
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&counters[CTR_ITERATIONS], 1ull);
     }
@@ -1683,6 +1685,110 @@ DEVI V3 light_random(const rtd::Light& l, V3 o, Rng& g) {
     }
     return v3(1.f, 0.f, 0.f);                                                  // hittable.rs:57-59
 }
+// RT_SCENE_LIGHTS_ALL_SHAPES (rt_hip.h; instances with F_LIGHTS_EXT only): the lights table holds rtd::LightX records. A member's pdf is
+// evaluated in its own space (o, v moved there by the composed wrapper chain: a rigid map keeps solid angles), a drawn direction is rotated back.
+DEVI float rectx_pdf_value(V3 o, V3 v, float a0, float a1, float b0, float b1, float k, int kaxis) {   // aarect.rs:107-117 for every orientation
+    float t, ha, hb;
+    if (!rect_hit(o, v, Float4{a0, a1, b0, b1}, Float4{k, (float)kaxis, 0.f, 0.f}, kTMin, kInf, t, ha, hb)) return 0.f;
+    const float area = (a1 - a0) * (b1 - b0);
+    const float distance_squared = t * t * len2(v);
+    const float cosine = fabsf(fdiv(comp(v, kaxis), len(v)));
+    return fdiv(fdiv(distance_squared, cosine), area);
+}
+DEVI V3 rectx_random(V3 o, float a0, float a1, float b0, float b1, float k, int kaxis, Rng& g) {        // aarect.rs:118-125
+    const float ra = g.range(a0, a1);
+    const float rb = g.range(b0, b1);
+    return (kaxis == 0 ? v3(k, ra, rb) : kaxis == 1 ? v3(ra, k, rb) : v3(ra, rb, k)) - o;
+}
+// the six sides of a box in boxes.rs order (z1 z0 y1 y0 x1 x0), p = x0 x1 y0 y1 z0 z1
+DEVI void box_side(const float* p, uint32_t s, float& a0, float& a1, float& b0, float& b1, float& k, int& kaxis) {
+    kaxis = s < 2u ? 2 : (s < 4u ? 1 : 0);
+    a0 = s < 4u ? p[0] : p[2]; a1 = s < 4u ? p[1] : p[3];
+    b0 = s < 2u ? p[2] : p[4]; b1 = s < 2u ? p[3] : p[5];
+    k = s == 0u ? p[5] : s == 1u ? p[4] : s == 2u ? p[3] : s == 3u ? p[2] : s == 4u ? p[1] : p[0];
+}
+DEVI float lightx_pdf_value(const rtd::LightX& l, V3 o, V3 v, unsigned long long& c_rect, unsigned long long& c_sphere, unsigned long long& c_tri) {
+    if (l.has_xform) { V3 ol, vl; xform_ray(l.xf, o, v, ol, vl); o = ol; v = vl; }
+    if (l.kind == rtd::LX_RECT) { c_rect++; return rectx_pdf_value(o, v, l.p[0], l.p[1], l.p[2], l.p[3], l.p[4], (int)l.p[5]); }
+    if (l.kind == rtd::LX_TRI) {
+        c_tri++;
+        const V3 v0 = v3(l.p[0], l.p[1], l.p[2]), v1 = v3(l.p[3], l.p[4], l.p[5]), v2 = v3(l.p[6], l.p[7], l.p[8]);
+        float t, bu, bv;
+        if (tri_hit(o, v, v0, v1, v2, kTMin, kInf, t, bu, bv) == 0) return 0.f;
+        const V3 nn = cross(v1 - v0, v2 - v0);
+        const float ln = len(nn);
+        const float distance_squared = t * t * len2(v);
+        const float cosine = fabsf(fdiv(dot(v, nn), len(v) * ln));
+        return fdiv(fdiv(distance_squared, cosine), 0.5f * ln);
+    }
+    if (l.kind == rtd::LX_BOX) {                                               // the list rule (hittable_list.rs:73-80) over the box's own sides
+        c_rect += 6ull;
+        float sum = 0.f;
+#pragma unroll
+        for (uint32_t s = 0; s < 6u; ++s) {
+            float a0, a1, b0, b1, k; int kaxis;
+            box_side(l.p, s, a0, a1, b0, b1, k, kaxis);
+            sum += (1.0f / 6.0f) * rectx_pdf_value(o, v, a0, a1, b0, b1, k, kaxis);
+        }
+        return sum;
+    }
+    c_sphere++;                                                                // sphere.rs:75-84, as light_pdf_value
+    const V3 c = v3(l.p[0], l.p[1], l.p[2]); const float r = l.p[3];
+    float t;
+    const float a = len2(v);
+    if (sphere_certain_miss(o, v, a, c, r) || !sphere_roots(o, v, a, c, r, kTMin, kInf, t)) return 0.f;
+    const float cos_theta_max = fsqrt(1.f - fdiv(r * r, len2(c - o)));
+    const float solid_angle = 2.f * kPi * (1.f - cos_theta_max);
+    return fdiv(1.f, solid_angle);
+}
+DEVI V3 lightx_random(const rtd::LightX& l, V3 o, Rng& g) {
+    if (l.has_xform) { V3 ol, dl; xform_ray(l.xf, o, v3(0.f, 0.f, 0.f), ol, dl); o = ol; }
+    V3 dir;
+    if (l.kind == rtd::LX_RECT) dir = rectx_random(o, l.p[0], l.p[1], l.p[2], l.p[3], l.p[4], (int)l.p[5], g);
+    else if (l.kind == rtd::LX_TRI) {
+        const float r1 = g.rnd(), r2 = g.rnd();
+        const float s = fsqrt(r1);
+        const V3 v0 = v3(l.p[0], l.p[1], l.p[2]), v1 = v3(l.p[3], l.p[4], l.p[5]), v2 = v3(l.p[6], l.p[7], l.p[8]);
+        dir = ((1.0f - s) * v0 + (s * (1.0f - r2)) * v1 + (s * r2) * v2) - o;
+    } else if (l.kind == rtd::LX_BOX) {
+        const uint32_t s = (uint32_t)(g.next64() % 6ull);                     // hittable_list.rs:81-84 over the sides
+        float a0, a1, b0, b1, k; int kaxis;
+        box_side(l.p, s, a0, a1, b0, b1, k, kaxis);
+        dir = rectx_random(o, a0, a1, b0, b1, k, kaxis, g);
+    } else {                                                                   // sphere.rs:85-90, as light_random
+        const V3 direction = v3(l.p[0], l.p[1], l.p[2]) - o;
+        const Onb uvw = onb_from_w(direction);
+        dir = onb_local(uvw, random_to_sphere(g, l.p[3], len2(direction)));
+    }
+    return l.has_xform ? xform_normal_back(l.xf, dir) : dir;
+}
+// HittableList::random and pdf_value over the scene's lights (hittable_list.rs:73-84): what the light-sample query (k_sample_lights) calls, and
+// the Lambertian branch of shade_segment in the instances with F_LIGHTS_EXT. The instances without the bit keep the same statements in line
+// (over the same light_random / light_pdf_value): written as calls, their loop came out of hipcc with its exit test inverted, and the
+// instruction text of the existing instances is pinned.
+template <uint32_t FEAT>
+DEVI V3 lights_random(const SceneDev& sc, V3 p, Rng& g, uint32_t& k) {
+    k = (uint32_t)(g.next64() % (uint64_t)sc.n_lights);   // hittable_list.rs:81-84
+    if constexpr ((FEAT & F_LIGHTS_EXT) != 0u) return lightx_random(reinterpret_cast<const rtd::LightX*>(sc.lights)[k], p, g);
+    else return light_random(sc.lights[k], p, g);
+}
+template <uint32_t FEAT>
+DEVI float lights_pdf_value(const SceneDev& sc, V3 p, V3 dir, unsigned long long& c_light_rect, unsigned long long& c_light_sphere, unsigned long long& c_light_tri) {
+    const float weight = 1.0f / (float)sc.n_lights;
+    float lsum = 0.f;
+    if constexpr ((FEAT & F_LIGHTS_EXT) != 0u) {
+        for (uint32_t k = 0; k < sc.n_lights; ++k) {
+            const rtd::LightX l = reinterpret_cast<const rtd::LightX*>(sc.lights)[k];
+            lsum += weight * lightx_pdf_value(l, p, dir, c_light_rect, c_light_sphere, c_light_tri);
+        }
+    } else {
+        for (uint32_t k = 0; k < sc.n_lights; ++k) {
+            const rtd::Light l = sc.lights[k];
+            lsum += weight * light_pdf_value(l, p, dir, l.kind == rtd::LK_XZRECT ? c_light_rect : c_light_sphere);
+        }
+    }
+    return lsum;
+}
 
 // ------------------------------------------------------------------------------------------------
 // k_shade
@@ -1703,7 +1809,7 @@ DEVI void sphere_uv(V3 p, float& u, float& v) {                                /
 // scenes with glass and moving spheres; tests/test_gpu_scenes.py::test_time_survives_a_glass_bounce keeps watch.)
 template <uint32_t FEAT>
 DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& d, const float tm, PathState& s, Rng& g, uint32_t& depth, uint2 hit, V3& L,
-                            unsigned long long& c_light_rect, unsigned long long& c_light_sphere) {
+                            unsigned long long& c_light_rect, unsigned long long& c_light_sphere, unsigned long long& c_light_tri) {
     bool finished = false, time_zero = false;
     L = v3(0.f, 0.f, 0.f);          // radiance of this sample: set by the terminal event only
     if (hit.y == rtd::HIT_NONE) {
@@ -1830,16 +1936,24 @@ DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& 
                 float pdf_val;
                 if ((FEAT & F_LIGHTS) && sc.n_lights) {
                     // MixturePdf::generate (pdf.rs:73-79) over HittablePdf(lights) and the cosine pdf
+                    float lsum = 0.f;
+                    if constexpr ((FEAT & F_LIGHTS_EXT) != 0u) {             // extended light records: the list functions the light-sample query calls too
+                        if (g.rnd() < 0.5f) {
+                            uint32_t k;
+                            dir = lights_random<FEAT>(sc, p, g, k);
+                        } else dir = onb_local(uvw, random_cosine_direction(g));
+                        lsum = lights_pdf_value<FEAT>(sc, p, dir, c_light_rect, c_light_sphere, c_light_tri);
+                    } else {
                     if (g.rnd() < 0.5f) {
                         const uint32_t k = (uint32_t)(g.next64() % (uint64_t)sc.n_lights);   // hittable_list.rs:81-84
                         dir = light_random(sc.lights[k], p, g);
                     } else dir = onb_local(uvw, random_cosine_direction(g));
                     // MixturePdf::value (pdf.rs:70-72)
                     const float weight = 1.0f / (float)sc.n_lights;
-                    float lsum = 0.f;
                     for (uint32_t k = 0; k < sc.n_lights; ++k) {
                         const rtd::Light l = sc.lights[k];
                         lsum += weight * light_pdf_value(l, p, dir, l.kind == rtd::LK_XZRECT ? c_light_rect : c_light_sphere);
+                    }
                     }
                     const float cosine = dot(unit(dir), uvw.w);
                     const float cpdf = cosine <= 0.f ? 0.f : cosine * kInvPi;   // pdf.rs:24-31
@@ -1974,7 +2088,7 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
     bool alive = i < count_in;
     const bool with_acc = rd.block_shift != 0u;
     PathState s{}; V3 o = v3(0, 0, 0), d = v3(0, 0, 1); float tm = 0.f;
-    unsigned long long c_samples = 0, c_light_rect = 0, c_light_sphere = 0;
+    unsigned long long c_samples = 0, c_light_rect = 0, c_light_sphere = 0, c_light_tri = 0;
     Rng g; g.s = 0; g.n = 0u; uint32_t depth = 0u;
     bool began = false;                // this thread's path has just begun a new work item (a camera ray)
     if (alive) {
@@ -1989,7 +2103,7 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
         SSTAMP(2);
         depth = sd & 0xFFu;
         g = path_rng(rd, s.work, with_acc, stored, sd >> 8, s.sample);     // the stream is a function of (pixel, sample): only the draw count travels
-        const uint32_t sh = shade_segment<FEAT>(sc, rd, o, d, tm, s, g, depth, hit, L, c_light_rect, c_light_sphere);
+        const uint32_t sh = shade_segment<FEAT>(sc, rd, o, d, tm, s, g, depth, hit, L, c_light_rect, c_light_sphere, c_light_tri);
         const bool finished = (sh & SH_FINISHED) != 0u;
         if (sh & SH_TIME_ZERO) tm = 0.0f;
 
@@ -2049,10 +2163,12 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
 #endif
     if (COUNT) {
         for (int off = 32; off > 0; off >>= 1) { c_samples += __shfl_down(c_samples, off); c_light_rect += __shfl_down(c_light_rect, off); c_light_sphere += __shfl_down(c_light_sphere, off); }
+        if constexpr ((FEAT & F_LIGHTS_EXT) != 0u) for (int off = 32; off > 0; off >>= 1) c_light_tri += __shfl_down(c_light_tri, off);
         if ((threadIdx.x & 63u) == 0u) {
             if (c_samples) atomicAdd(&counters[CTR_SAMPLES], c_samples);
             if (c_light_rect) atomicAdd(&counters[CTR_PRIM_TESTS + 2], c_light_rect);
             if (c_light_sphere) atomicAdd(&counters[CTR_PRIM_TESTS + 0], c_light_sphere);
+            if constexpr ((FEAT & F_LIGHTS_EXT) != 0u) { if (c_light_tri) atomicAdd(&counters[CTR_PRIM_TESTS + 3], c_light_tri); }
         }
     }
 }
@@ -2345,6 +2461,35 @@ __global__ void __launch_bounds__(256) k_occluded_export(PoolDev pool, uint32_t 
     occluded[__float_as_uint(s0.w)] = miss ? (uint8_t)0u : (uint8_t)kRayHitHit;
 }
 
+// ---- light-sample queries (rt_hip.h rt_sample_lights): the light half of shade_segment's Lambertian branch, one lane per query ----
+// Records as rt_hip.h declares them (RtLightQuery 40 B, RtLightSample 24 B). The generator is seeded (rng_state, 0 draws); the pick, the draw
+// and the list's pdf are lights_random / lights_pdf_value, the functions shade_segment calls. The tables are read where the upload put
+// them (no LDS staging: a query kernel is a few loads per lane). EXT: the scene's lights table holds rtd::LightX records (F_LIGHTS_EXT).
+struct LightQueryDev { float p[3]; uint32_t flags; uint64_t rng_state; float d[3]; float _pad; };
+struct LightSampleDev { float d[3]; float pdf; int32_t light; uint32_t n_draws; };
+static_assert(sizeof(LightQueryDev) == 40 && sizeof(LightSampleDev) == 24, "light query records: 40 and 24 bytes");
+constexpr uint32_t kLightQDirectionGiven = 1u;
+template <bool EXT>
+__global__ void __launch_bounds__(256) k_sample_lights(SceneDev sc, const LightQueryDev* __restrict__ queries, LightSampleDev* __restrict__ results, uint32_t n) {
+    constexpr uint32_t FEAT = F_LIGHTS | (EXT ? F_LIGHTS_EXT : 0u);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const LightQueryDev q = queries[i];
+    const V3 p = v3(q.p[0], q.p[1], q.p[2]);
+    V3 dir = v3(q.d[0], q.d[1], q.d[2]);
+    LightSampleDev r; r.light = -1; r.n_draws = 0u;
+    if ((q.flags & kLightQDirectionGiven) == 0u) {
+        Rng g; g.s = q.rng_state; g.n = 0u;
+        uint32_t k;
+        dir = lights_random<FEAT>(sc, p, g, k);
+        r.light = (int32_t)k; r.n_draws = g.n;
+    }
+    unsigned long long c0 = 0, c1 = 0, c2 = 0;
+    r.pdf = lights_pdf_value<FEAT>(sc, p, dir, c0, c1, c2);
+    r.d[0] = dir.x; r.d[1] = dir.y; r.d[2] = dir.z;
+    results[i] = r;
+}
+
 // ------------------------------------------------------------------------------------------------
 // first-hit features (rt_hip.h "first-hit features"): the render's own camera rays -> pool records -> k_extend -> per-ray feature
 // records -> per-pixel sums
@@ -2614,10 +2759,19 @@ template <class F> static auto with_variant(uint32_t features, F&& f) {
 // for scenes whose triangles carry attributes (F_TRI_ATTR): the mesh variant and the full one. A scene without attributes runs exactly the
 // instances it ran before they existed, and the plain walk (launch_extend, launch_extend_any) never sees the bit.
 constexpr uint32_t kVariantMeshAttr = kVariantMesh | F_TRI_ATTR, kVariantAllAttr = F_ALL | F_TRI_ATTR;
-template <class F> static auto with_shade_variant(uint32_t features, F&& f) {
+template <class F> static auto with_record_variant(uint32_t features, F&& f) {
     if ((features & F_TRI_ATTR) == 0u) return with_variant(features, f);
     if (pick_variant(features) == kVariantMesh) return f(std::integral_constant<uint32_t, kVariantMeshAttr>{});
     return f(std::integral_constant<uint32_t, kVariantAllAttr>{});
+}
+// ... and k_shade and the drain / fused form of k_extend two more for scenes whose lights table holds extended records (F_LIGHTS_EXT: RT_SCENE_LIGHTS_ALL_SHAPES
+// with a member that is not a bare XzRect or Sphere): the full variant, without and with triangle attributes. The ray-query and feature-export kernels
+// sample no light and never see the bit (with_record_variant).
+constexpr uint32_t kVariantAllLx = F_ALL | F_LIGHTS_EXT, kVariantAllAttrLx = F_ALL | F_TRI_ATTR | F_LIGHTS_EXT;
+template <class F> static auto with_shade_variant(uint32_t features, F&& f) {
+    if ((features & F_LIGHTS_EXT) == 0u) return with_record_variant(features, f);
+    if ((features & F_TRI_ATTR) == 0u) return f(std::integral_constant<uint32_t, kVariantAllLx>{});
+    return f(std::integral_constant<uint32_t, kVariantAllAttrLx>{});
 }
 // where the walk finds its records (k_extend MODE)
 template <class F> static auto with_mode(const LaunchCfg& cfg, const SceneDev& sc, F&& f) {
@@ -2779,7 +2933,7 @@ hipError_t launch_rays_export(const LaunchCfg& cfg, const SceneDev& sc, const Ra
                               const uint32_t* counts, void* hits, hipStream_t stream) {
     const uint32_t blocks = kQueues * ((std::min(max_count, queue_cap) + 255u) / 256u);   // max_count = upper bound of the rays in ONE queue
     if (blocks == 0u) return hipSuccess;
-    with_shade_variant(cfg.features, [&](auto feat) {
+    with_record_variant(cfg.features, [&](auto feat) {
         hipLaunchKernelGGL((k_rays_export<decltype(feat)::value>), dim3(blocks), dim3(256), 0, stream, sc, src, pool, queue_cap, counts, (Float4*)hits); });
     return hipGetLastError();
 }
@@ -2828,6 +2982,15 @@ hipError_t launch_occluded_export(const PoolDev& pool, uint32_t queue_cap, uint3
     return hipGetLastError();
 }
 
+hipError_t launch_sample_lights(const SceneDev& sc, bool ext, const void* queries, void* results, uint32_t n, hipStream_t stream) {
+    const uint32_t blocks = (n + 255u) / 256u;
+    if (blocks == 0u) return hipSuccess;
+    if (sc.n_lights == 0u) return hipErrorInvalidValue;                  // (the host refuses a scene without lights before anything is launched)
+    with_flag(ext, [&](auto e) {
+        hipLaunchKernelGGL(k_sample_lights<decltype(e)::value>, dim3(blocks), dim3(256), 0, stream, sc, (const LightQueryDev*)queries, (LightSampleDev*)results, n); });
+    return hipGetLastError();
+}
+
 hipError_t launch_features_import(const RenderDev& rd, const FeatDev& fd, const PoolDev& pool, uint32_t* counts, unsigned long long* counters, hipStream_t stream) {
     const uint64_t n = (uint64_t)fd.ns * fd.nk;
     if (n == 0u) return hipSuccess;
@@ -2841,7 +3004,7 @@ hipError_t launch_features_export(const LaunchCfg& cfg, const SceneDev& sc, cons
                                   const uint32_t* counts, hipStream_t stream) {
     const uint32_t blocks = kQueues * ((std::min(max_count, rd.queue_cap) + 255u) / 256u);   // max_count = upper bound of the rays in ONE queue
     if (blocks == 0u) return hipSuccess;
-    with_shade_variant(cfg.features, [&](auto feat) {
+    with_record_variant(cfg.features, [&](auto feat) {
         hipLaunchKernelGGL((k_features_export<decltype(feat)::value>), dim3(blocks), dim3(256), 0, stream, sc, rd, fd, pool, counts); });
     return hipGetLastError();
 }

@@ -45,6 +45,7 @@ static uint32_t scene_features(const rtc::CompiledScene& cs) {
     if (cs.xforms.size() > 1 || cs.wraps.size() > 1) f |= rtk::F_XFORM;
     for (uint32_t mb : cs.mat_b) { const uint32_t kind = mb & 15u; if ((mb >> 4) != rtd::TEX_INLINE && kind != rtd::MK_METAL && kind != rtd::MK_DIELECTRIC) f |= rtk::F_TEX; }
     if (cs.has_lights) f |= rtk::F_LIGHTS;
+    if (cs.lights_ext) f |= rtk::F_LIGHTS_EXT;
     return f;
 }
 
@@ -678,7 +679,7 @@ int rti::scene_image_upload(RtCtx* ctx, const SceneImage& im, RtScene** out_scen
     d.mat_a = (const rtd::Float4*)s->mat_a.p; d.mat_b = (const uint32_t*)s->mat_b.p;
     d.textures = (const rtd::Texture*)s->textures.p; d.perlins = (const rtd::PerlinTable*)s->perlins.p;
     d.images = (const rtd::Image*)s->images.p; d.image_bytes = (const uint8_t*)s->image_bytes.p;
-    d.lights = (const rtd::Light*)s->lights.p; d.n_lights = (uint32_t)cs.lights.size();
+    d.lights = (const rtd::Light*)s->lights.p; d.n_lights = cs.n_lights;
     d.shade_blob = im.blob.empty() ? nullptr : (const rtd::Float4*)s->shade_blob.p; d.shade_blob_bytes = (uint32_t)im.blob.size();
     d.sb_spheres = sb[0]; d.sb_sphere_meta = sb[1]; d.sb_rects = sb[2]; d.sb_rect_meta = sb[3]; d.sb_moving = sb[4]; d.sb_moving_meta = sb[5];
     d.ext_blob = im.eblob.empty() ? nullptr : (const rtd::Float4*)s->ext_blob.p; d.ext_blob_bytes = (uint32_t)im.eblob.size();
@@ -1311,6 +1312,70 @@ int rt_occluded_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* 
     return ray_query_host(ctx, scene, options, rays_host, n_rays, occluded_host, stats, kOcclusion);
 }
 
+// ---- light-sample queries (include/rt_hip.h): the scene's own light sampler, one RtLightSample per RtLightQuery ---------------------------------
+// One kernel, one lane per query, no pool and no counters: the launch, timing and failure rules of the other query paths (the context's
+// stream, StreamTimer under RT_FLAG_TIMING, drain_on_failure, one wait at the end).
+static_assert(sizeof(RtLightQuery) == 40 && sizeof(RtLightSample) == 24 && sizeof(RtLightQueryOptions) == 8, "light query records: 40, 24 and 8 bytes");
+static int light_query_refuse(RtCtx* ctx, const RtScene* scene, const RtLightQueryOptions* o, const void* queries, uint64_t n, const void* results, bool device) {
+    if (!scene) return set_err(ctx, RT_ERR_INVALID, "scene is null");
+    if (o) {
+        if (o->struct_bytes < sizeof(RtLightQueryOptions) || o->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtLightQueryOptions.struct_bytes is not set (sizeof(RtLightQueryOptions))");
+        if (o->flags & ~(uint32_t)RT_FLAG_TIMING) return set_err(ctx, RT_ERR_INVALID, "RtLightQueryOptions.flags holds an unknown bit (known: RT_FLAG_TIMING)");
+    }
+    if (n > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "n must be < 2^32 (split the list)");
+    if ((scene->features & rtk::F_LIGHTS) == 0u || scene->dev.n_lights == 0u)
+        return set_err(ctx, RT_ERR_UNSUPPORTED, "light-sample queries: the scene was uploaded without a lights list (RtSceneDesc.lights = -1)");
+    if (n != 0u && (!queries || !results)) return set_err(ctx, RT_ERR_INVALID, "queries / results is null");
+    if (device && ((((uintptr_t)queries) | ((uintptr_t)results)) & 7u)) return set_err(ctx, RT_ERR_INVALID, "queries / results must be 8-byte aligned");
+    return RT_OK;
+}
+static int sample_lights_impl(RtCtx* ctx, const RtScene* scene, const RtLightQueryOptions* opt, const void* d_queries, uint64_t n, void* d_results, RtStats* stats) {
+    using clk = std::chrono::steady_clock;
+    const auto t_begin = clk::now();
+    const bool timing = opt && (opt->flags & RT_FLAG_TIMING) != 0u;
+    StreamTimer tm{ctx};
+    hipEvent_t ea = nullptr, eb = nullptr;
+    if (timing) HIP_TRY(ctx, tm.mark(ea));
+    LAUNCH_TRY(rtk::launch_sample_lights(scene->dev, (scene->features & rtk::F_LIGHTS_EXT) != 0u, d_queries, d_results, (uint32_t)n, ctx->stream));
+    if (timing) { HIP_TRY(ctx, tm.mark(eb)); tm.span(ea, eb, 1); }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) {
+        double part_ms[2] = {0.0, 0.0};
+        tm.sum(part_ms);
+        stats->other_ms = part_ms[1];
+        stats->samples = n;
+        const uint32_t none[2] = {0u, 0u};
+        scene_stats(stats, scene, none);
+        stats->render_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
+    }
+    return RT_OK;
+}
+int rt_sample_lights_device(RtCtx* ctx, const RtScene* scene, const RtLightQueryOptions* options, const void* queries_device, uint64_t n, void* results_device, RtStats* stats) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    const int v = light_query_refuse(ctx, scene, options, queries_device, n, results_device, true); if (v != RT_OK) return v;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n == 0u) return RT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return drain_on_failure(ctx, sample_lights_impl(ctx, scene, options, queries_device, n, results_device, stats));
+}
+int rt_sample_lights(RtCtx* ctx, const RtScene* scene, const RtLightQueryOptions* options, const RtLightQuery* queries_host, uint64_t n, RtLightSample* results_host, RtStats* stats) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    const int v = light_query_refuse(ctx, scene, options, queries_host, n, results_host, false); if (v != RT_OK) return v;   // (host buffers are copied: no alignment asked)
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n == 0u) return RT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(ctx, ctx->rays_tmp.ensure((size_t)n * sizeof(RtLightQuery)));
+    HIP_TRY(ctx, ctx->hits_tmp.ensure((size_t)n * sizeof(RtLightSample)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->rays_tmp.p, queries_host, (size_t)n * sizeof(RtLightQuery), hipMemcpyHostToDevice, ctx->stream));
+    const int r = rt_sample_lights_device(ctx, scene, options, ctx->rays_tmp.p, n, ctx->hits_tmp.p, stats);
+    if (r != RT_OK) return r;
+    HIP_TRY(ctx, hipMemcpyAsync(results_host, ctx->hits_tmp.p, (size_t)n * sizeof(RtLightSample), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT_OK;
+}
+
 // ---- first-hit features (include/rt_hip.h): albedo, normal and depth of the render's own camera rays, as per-pixel sums ---------------------
 static_assert(sizeof(RtFeatureOptions) == 16 && sizeof(RtFeatureBuffers) == 4 * sizeof(void*), "feature records: 16 bytes and four pointers");
 static int check_features(RtCtx* ctx, const RtParams* p, const RtFeatureOptions* o) {
@@ -1462,7 +1527,7 @@ int rt_scene_compile_info_ex(const RtSceneDesc* desc, const RtUploadOptions* opt
     if (rc != RT_OK) return set_err(nullptr, rc, "scene: " + cs.error);
     out->n_nodes = cs.nodes.size(); out->n_box_nodes = cs.n_box_nodes; out->n_spheres = cs.sphere_meta.size(); out->n_moving = cs.moving_meta.size();
     out->n_rects = cs.rect_meta.size(); out->n_tris = cs.tri_meta.size(); out->n_media = cs.media.size(); out->n_xforms = cs.xforms.size();
-    out->n_lights = cs.lights.size(); out->n_materials = cs.mat_b.size();
+    out->n_lights = cs.n_lights; out->n_materials = cs.mat_b.size();
     out->features = scene_features(cs);
     {
         std::string why;

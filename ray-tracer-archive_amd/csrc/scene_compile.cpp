@@ -804,6 +804,8 @@ struct Compiler {
             }
         } else ids.push_back(d.lights);
         if (ids.empty()) { fail("empty lights list (the reference divides by its length, hittable_list.rs:74,82)"); return; }
+        out.n_lights = (uint32_t)ids.size();
+        if (d.scene_flags & RT_SCENE_LIGHTS_ALL_SHAPES) { compile_lights_all_shapes(ids); return; }
         for (int id : ids) {
             const RtHittable* h = H(id); if (!h) return;
             rtd::Light l{};
@@ -813,6 +815,62 @@ struct Compiler {
             out.lights.push_back(l);
         }
     }
+
+    // RT_SCENE_LIGHTS_ALL_SHAPES (rt_hip.h): every member is a rect, a triangle, a box or a sphere under at most MAX_WRAP_OPS wrappers, or the
+    // scene is refused. A list of bare XzRects and Spheres keeps the records (and the kernels) of a scene without the flag.
+    void compile_lights_all_shapes(const std::vector<int>& ids) {
+        std::vector<rtd::LightX> xs;
+        bool ext = false;
+        for (size_t k = 0; k < ids.size(); ++k) {
+            const std::string who = "lights list member " + std::to_string(k) + ": ";
+            Chain c;
+            const int inner = unwrap(ids[k], c); if (inner < 0) return;
+            const RtHittable* h = H(inner); if (!h) return;
+            if (c.ops.size() > rtd::MAX_WRAP_OPS) { fail(who + "a chain of more than 6 Translate/RotateY/FlipFace wrappers"); return; }
+            const double* p = h->p;
+            rtd::LightX x{};
+            switch (h->kind) {
+            case RT_HIT_XY_RECT: case RT_HIT_XZ_RECT: case RT_HIT_YZ_RECT:
+                if (!((p[1] - p[0]) * (p[3] - p[2]) != 0.0)) { fail(who + "a rect of zero area cannot be sampled"); return; }
+                x.kind = rtd::LX_RECT; for (int i = 0; i < 5; ++i) x.p[i] = (float)p[i];
+                x.p[5] = h->kind == RT_HIT_XY_RECT ? 2.f : (h->kind == RT_HIT_XZ_RECT ? 1.f : 0.f);
+                break;
+            case RT_HIT_TRIANGLE: {
+                const double e1[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]}, e2[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
+                const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+                if (!(n[0] * n[0] + n[1] * n[1] + n[2] * n[2] > 0.0)) { fail(who + "a triangle of zero area cannot be sampled"); return; }
+                x.kind = rtd::LX_TRI; for (int i = 0; i < 9; ++i) x.p[i] = (float)p[i];
+                break;
+            }
+            case RT_HIT_BOX:
+                for (int a = 0; a < 3; ++a) if (!(p[3 + a] - p[a] != 0.0)) { fail(who + "a box with sides of zero area cannot be sampled"); return; }
+                x.kind = rtd::LX_BOX; for (int a = 0; a < 3; ++a) { x.p[2 * a] = (float)p[a]; x.p[2 * a + 1] = (float)p[3 + a]; }
+                break;
+            case RT_HIT_SPHERE: x.kind = rtd::LX_SPHERE; for (int i = 0; i < 4; ++i) x.p[i] = (float)p[i]; break;
+            case RT_HIT_MOVING_SPHERE: fail(who + "a moving sphere cannot be sampled as a light"); return;
+            case RT_HIT_CONSTANT_MEDIUM: fail(who + "a constant medium cannot be sampled as a light"); return;
+            case RT_HIT_LIST: fail(who + "a nested list cannot be sampled as a light (list its members)"); return;
+            case RT_HIT_BVH: fail(who + "a BVH cannot be sampled as a light (list its members)"); return;
+            default: fail(who + "unknown hittable kind"); return;
+            }
+            x.has_xform = c.identity ? 0u : 1u;
+            x.xf = rtd::Xform{(float)std::sin(c.theta), (float)std::cos(c.theta), {(float)c.off[0], (float)c.off[1], (float)c.off[2]}, {0.f, 0.f, 0.f}};
+            if (!(c.ops.empty() && (h->kind == RT_HIT_XZ_RECT || h->kind == RT_HIT_SPHERE))) ext = true;
+            xs.push_back(x);
+        }
+        if (!ext) {   // the reference's own kinds: the records of a scene without the flag, byte for byte
+            for (const rtd::LightX& x : xs) {
+                rtd::Light l{};
+                l.kind = x.kind == rtd::LX_RECT ? rtd::LK_XZRECT : rtd::LK_SPHERE;
+                for (int i = 0; i < 5; ++i) l.p[i] = x.kind == rtd::LX_RECT || i < 4 ? x.p[i] : 0.f;
+                out.lights.push_back(l);
+            }
+            return;
+        }
+        out.lights_ext = true;
+        out.lights.resize(3 * xs.size());
+        std::memcpy(out.lights.data(), xs.data(), xs.size() * sizeof(rtd::LightX));
+    }
 };
 
 }  // namespace
@@ -820,6 +878,7 @@ struct Compiler {
 int compile_scene(const RtSceneDesc& desc, const CompileOptions& opt, CompiledScene& out) {
     out = CompiledScene();
     if (desc.abi_version != RT_ABI_VERSION) { out.error = "RtSceneDesc.abi_version mismatch"; return RT_ERR_INVALID; }
+    if (desc.scene_flags & ~(uint32_t)RT_SCENE_LIGHTS_ALL_SHAPES) { out.error = "RtSceneDesc.scene_flags holds an unknown bit (known: RT_SCENE_LIGHTS_ALL_SHAPES)"; return RT_ERR_INVALID; }
     if (!desc.hittables || desc.n_hittables == 0) { out.error = "scene has no hittables"; return RT_ERR_INVALID; }
     if ((desc.n_children && !desc.children) || (desc.n_materials && !desc.materials) || (desc.n_textures && !desc.textures) ||
         (desc.n_perlins && !desc.perlins) || (desc.n_images && !desc.images)) { out.error = "null array with non-zero count"; return RT_ERR_INVALID; }

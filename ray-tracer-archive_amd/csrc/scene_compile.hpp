@@ -25,7 +25,9 @@ struct CompiledScene {
     std::vector<rtd::Texture> textures;
     std::vector<rtd::PerlinTable> perlins;
     std::vector<rtd::Image> images;    std::vector<uint8_t> image_bytes;
-    std::vector<rtd::Light> lights;
+    std::vector<rtd::Light> lights;                                          // one record per light — or, lights_ext, one rtd::LightX in three slots each
+    uint32_t n_lights = 0;                                                   // members of the lights list
+    bool lights_ext = false;                                                 // RT_SCENE_LIGHTS_ALL_SHAPES and a member that is not a bare XzRect / Sphere
     uint32_t first_leaf = 0;                                                 // leaf word of the spheres a walk tests before it enters the tree (emit_bvh: spheres as large as the scene), 0: none
     std::vector<uint32_t> prologue;                                          // leaf payloads of the root list's every-ray members (scene_compile.cpp: prologue_member)
     int background_mode = 0; float background[3] = {0, 0, 0};
