@@ -115,6 +115,7 @@ pub const RT_LAYOUT_NODES_32B: u32 = 64;
 pub const RT_LAYOUT_NO_SHADE_TABLES_IN_LDS: u32 = 128;
 pub const RT_LAYOUT_NO_EXTEND_TABLES_IN_LDS: u32 = 256;
 pub const RT_LAYOUT_WIDE_NODES: u32 = 512;
+pub const RT_LAYOUT_ALL_BOX_NODES: u32 = 1024;
 pub const RT_LAYOUT_REFERENCE_COUNTERS: u32 = 1 | 4 | 16;   // RtStats test counts = the reference's own
 // per-vertex normals / texture coordinates of RT_HIT_TRIANGLE records (RtTriangleAttrs.flags), handed over in RtUploadOptions
 pub const RT_TRI_NORMALS: u32 = 1;

@@ -285,6 +285,9 @@ enum {
     RT_LAYOUT_NO_EXTEND_TABLES_IN_LDS = 256u,
     RT_LAYOUT_WIDE_NODES = 512u,         /* static BVH in HBM: walk an 8-wide tree, 8 lanes to a ray, one 128-byte node per visit (measured slower than
                                             the default binary records on MI355X — VALU-bound at 8 rays per wave, DESIGN.md section 5 — kept as an option) */
+    RT_LAYOUT_ALL_BOX_NODES = 1024u,     /* keep every box record of the tree (default, in a scene staged in LDS: an inner box that most rays which reach it pass anyway
+                                            is left out and its children take its place — fewer box tests, the same leaves in the same order; off by itself under
+                                            LISTS_AS_REFERENCE, NO_MEMBER_BOXES, SCENE_IN_HBM and WIDE_NODES) */
     RT_LAYOUT_REFERENCE_COUNTERS = 1u | 4u | 16u
 };
 /* ---- triangle attributes: per-vertex normals and texture coordinates ------------------------------------------------------------------------

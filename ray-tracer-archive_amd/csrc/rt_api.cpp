@@ -392,10 +392,7 @@ static bool device_nodes16(const std::vector<rtd::Node>& nodes, std::vector<rtd:
     out[n] = end; out[n + 1] = end;
     return true;
 }
-static size_t lds_scene_bytes(const rtc::CompiledScene& cs) {
-    size_t twins = 0; for (const rtd::Node& nd : cs.nodes) if (nd.leaf != 0u) ++twins;
-    return (cs.nodes.size() + 2 + twins) * 32 + cs.spheres.size() * 16;
-}
+using rtc::lds_scene_bytes;
 
 // ---- layout options: RtUploadOptions of the ABI, resolved once per upload (the library reads no environment variable for them) -----------
 struct rti::UploadOpts {
@@ -408,7 +405,8 @@ static int check_options(const RtUploadOptions* options, std::string& err) {
     if (options) {
         // a host built against a newer header must hear that this library does not know a switch, not have it dropped
         constexpr uint32_t kKnown = RT_LAYOUT_LISTS_AS_REFERENCE | RT_LAYOUT_LISTS_CULLED | RT_LAYOUT_NO_MEMBER_BOXES | RT_LAYOUT_MEMBER_BOXES | RT_LAYOUT_CHILD_ORDER_AS_REFERENCE |
-                                    RT_LAYOUT_SCENE_IN_HBM | RT_LAYOUT_NODES_32B | RT_LAYOUT_NO_SHADE_TABLES_IN_LDS | RT_LAYOUT_NO_EXTEND_TABLES_IN_LDS | RT_LAYOUT_WIDE_NODES;
+                                    RT_LAYOUT_SCENE_IN_HBM | RT_LAYOUT_NODES_32B | RT_LAYOUT_NO_SHADE_TABLES_IN_LDS | RT_LAYOUT_NO_EXTEND_TABLES_IN_LDS | RT_LAYOUT_WIDE_NODES |
+                                    RT_LAYOUT_ALL_BOX_NODES;
         if (options->struct_bytes < 8u || options->struct_bytes > 4096u) { err = "RtUploadOptions.struct_bytes is not set (sizeof(RtUploadOptions))"; return RT_ERR_INVALID; }
         const uint32_t f = options->layout_flags;
         if (f & ~kKnown) { err = "RtUploadOptions.layout_flags: unknown bit"; return RT_ERR_INVALID; }
@@ -422,8 +420,12 @@ static int check_options(const RtUploadOptions* options, std::string& err) {
 
 static rti::UploadOpts resolve_options(const RtUploadOptions* o) {
     rti::UploadOpts u;
+    u.compile.elide_within_lds_bytes = kLdsSceneBudget;
     if (o && o->struct_bytes >= 8u) {
         const uint32_t f = o->layout_flags;
+        // box records are elided in the layout a scene staged in LDS gets by default only: the reference's counts (LISTS_AS_REFERENCE,
+        // NO_MEMBER_BOXES) are compared record by record, and the walks from HBM (octant orders, the 8-wide tree) rely on binary nodes
+        if (f & (RT_LAYOUT_ALL_BOX_NODES | RT_LAYOUT_LISTS_AS_REFERENCE | RT_LAYOUT_NO_MEMBER_BOXES | RT_LAYOUT_SCENE_IN_HBM | RT_LAYOUT_WIDE_NODES)) u.compile.elide_within_lds_bytes = 0;
         if (f & RT_LAYOUT_LISTS_AS_REFERENCE) { u.compile.cull_lists = 0; u.compile.big_spheres_first = false; }   // "nothing tested at the start of a walk"
         else if (f & RT_LAYOUT_LISTS_CULLED) u.compile.cull_lists = 1;
         if (f & RT_LAYOUT_NO_MEMBER_BOXES) u.compile.member_boxes = 0; else if (f & RT_LAYOUT_MEMBER_BOXES) u.compile.member_boxes = 1;

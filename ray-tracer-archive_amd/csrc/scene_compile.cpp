@@ -732,6 +732,90 @@ struct Compiler {
         src.swap(dst);
     }
 
+    // ---- a scene walked from LDS: inner box records that cost more box tests than they save are left out ----
+    // The reference's builder splits at the median of a random axis, so many an inner box is almost as large as its parent's: a ray that
+    // entered the parent enters it with probability p > 1/2, the record costs one test and saves its children's with probability 1 - p.
+    // Leaving it out splices its children into its parent's sequence: every link to it goes to the next record (its first child), the
+    // children's own skip links already lead past their subtrees. The leaves keep their order, so the primitives are tested in the same
+    // order, t_max takes the same values and ties resolve the same way; only box tests go away (a node visit of k_extend is at its
+    // instruction floor, DESIGN 9.1: what moves the kernel is fewer visits).
+    // Model: a kept boxed record costs P(entered) of its nearest kept boxed ancestor (1 without one), P(entered Z) = min(1, A(Z) / A(R)) with
+    // A the half area and R the outermost boxed record above Z. The kept set that minimises the sum, exactly: bottom-up over (record,
+    // nearest kept ancestor) — keep the record, or hand its children to that ancestor; a tie keeps it. No constant to tune, no camera.
+    // A record that carries a leaf word, has no box (or no finite one), or has a child without one always stays.
+    void elide_box_nodes() {
+        std::vector<rtd::Node>& src = out.nodes;
+        const size_t n = src.size();
+        auto sub_end = [&](size_t i) { return std::min<size_t>(std::max<size_t>(src[i].skip, i + 1), n); };
+        auto boxed = [&](size_t i) { for (int a = 0; a < 3; ++a) if (!std::isfinite(src[i].mn[a]) || !std::isfinite(src[i].mx[a])) return false; return true; };
+        auto area = [&](size_t i) { const rtd::Node& b = src[i]; return half_area(Box3{{b.mn[0], b.mn[1], b.mn[2]}, {b.mx[0], b.mx[1], b.mx[2]}}); };
+        // cost[i][k]: the cheapest subtree of i, i included, when its nearest kept ancestor is the k-th record of its chain of ancestors
+        // (k = 0: none, k = 1: the top of its tree, ..., k = depth: its parent); splice[i][k]: whether that is reached without i.
+        // chain / p_chain: the ancestors of the record being solved and P(entered) of each (p_chain[0] = 1: no box above).
+        std::vector<std::vector<double>> cost(n);
+        std::vector<std::vector<char>> splice(n);
+        std::vector<size_t> chain; std::vector<double> p_chain{1.0};
+        // top_area: A(R) of the tree i lies in, < 0 when i is the top of one
+        auto solve = [&](auto& self, size_t i, double top_area) -> void {
+            const size_t depth = chain.size(), end = sub_end(i);
+            if (!boxed(i)) {
+                // no box test. A record made by push_leaf_node has no children; a box record with a NaN or an overflowed corner (the device
+                // passes such an axis always, rt_api.cpp node_boxes) has: it stays, and each child is the top of a tree of its own
+                double below = 0.0;
+                chain.push_back(i); p_chain.push_back(1.0);
+                for (size_t c = i + 1; c < end; c = sub_end(c)) { self(self, c, -1.0); below += cost[c][depth + 1]; }
+                chain.pop_back(); p_chain.pop_back();
+                cost[i].assign(depth + 1, below); splice[i].assign(depth + 1, 0);
+                return;
+            }
+            const double a_top = top_area < 0.0 ? area(i) : top_area;
+            chain.push_back(i); p_chain.push_back(a_top > 0.0 ? std::min(1.0, area(i) / a_top) : 1.0);
+            std::vector<double> handed(depth + 1, 0.0);                       // the children under each ancestor of i
+            double kept = 0.0; size_t kids = 0, bare = 0;                      // the children under i
+            for (size_t c = i + 1; c < end; c = sub_end(c), ++kids) {
+                self(self, c, a_top);
+                if (!boxed(c)) ++bare;
+                kept += cost[c][depth + 1];
+                for (size_t k = 0; k <= depth; ++k) handed[k] += cost[c][k];
+            }
+            chain.pop_back(); p_chain.pop_back();
+            // a child without a box (a medium, a moving sphere, the records that enter and leave an instance) has no other cull than i: without
+            // i every ray that reaches i's parent would stop at it, and "only box tests go away" would no longer hold
+            const bool candidate = src[i].leaf == 0u && kids != 0 && bare == 0;
+            cost[i].resize(depth + 1); splice[i].resize(depth + 1);
+            for (size_t k = 0; k <= depth; ++k) {
+                const double keep = p_chain[k] + kept;
+                splice[i][k] = candidate && handed[k] < keep;                  // a tie keeps the record
+                cost[i][k] = splice[i][k] ? handed[k] : keep;
+            }
+        };
+        for (size_t i = 0; i < n; i = sub_end(i)) solve(solve, i, -1.0);
+        // top-down: the ancestor a record ends up under decides whether it stays
+        std::vector<char> gone(n, 0);
+        std::vector<size_t> under(n, 0), ends;
+        uint64_t removed = 0;
+        for (size_t i = 0; i < n; ++i) {
+            while (!ends.empty() && ends.back() <= i) ends.pop_back();
+            const size_t depth = ends.size(), end = sub_end(i);
+            gone[i] = splice[i][under[i]];
+            removed += gone[i] ? 1u : 0u;
+            for (size_t c = i + 1; c < end; c = sub_end(c)) under[c] = gone[i] ? under[i] : depth + 1;
+            if (end > i + 1) ends.push_back(end);
+        }
+        if (removed == 0) return;
+        std::vector<rtd::Node> dst; dst.reserve(n - removed);
+        std::vector<uint32_t> map(n + 1);
+        for (size_t i = 0; i < n; ++i) {
+            map[i] = (uint32_t)dst.size();                                     // a link to a removed record goes to the next kept one: its first child
+            if (!gone[i]) dst.push_back(src[i]);
+        }
+        map[n] = (uint32_t)dst.size();
+        remap(dst, map, (uint32_t)dst.size());
+        for (size_t i = 0; i < dst.size(); ++i) if (nobox(dst[i])) dst[i].skip = (uint32_t)i + 1;
+        src.swap(dst);
+        out.n_box_nodes -= std::min<uint64_t>(out.n_box_nodes, removed);
+    }
+
     // ---- materials, textures, lights ----
     void compile_materials() {
         for (uint64_t i = 0; i < d.n_textures; ++i) {
@@ -904,6 +988,7 @@ int compile_scene(const RtSceneDesc& desc, const CompileOptions& opt, CompiledSc
     c.merge_runs();
     c.fold_box_leaf();
     if (opt.leaf_collapse > 1) c.collapse_small_subtrees(opt.leaf_collapse);
+    if (opt.elide_within_lds_bytes != 0 && lds_scene_bytes(out) <= opt.elide_within_lds_bytes) c.elide_box_nodes();   // "fits" is decided before the pass
     c.compile_lights();
     if (!c.ok()) return RT_ERR_INVALID;
     out.background_mode = desc.background_mode;

@@ -44,7 +44,15 @@ struct CompileOptions {
     double park_cost = 6.0;     // a stop of the walk at a leaf, in primitive tests (grouping of culled list members)
     uint32_t leaf_collapse = 0; // a box node whose subtree is <= n primitives of one kind becomes a leaf (0/1: off)
     bool big_spheres_first = true;  // a sphere of the root BVH whose box is most of the scene (a ground sphere) is tested when a walk begins, not met by it
+    size_t elide_within_lds_bytes = 0;  // a scene whose lds_scene_bytes() is within this budget BEFORE the pass loses the inner box records that cost more tests than they
+                                        // save (scene_compile.cpp elide_box_nodes); 0: every box record stays (scenes walked from HBM keep binary nodes)
 };
+
+// What a workgroup stages of a scene that is walked from LDS: the records, the two closing ones, a park twin per leaf, the sphere data.
+inline size_t lds_scene_bytes(const CompiledScene& cs) {
+    size_t twins = 0; for (const rtd::Node& nd : cs.nodes) if (nd.leaf != 0u) ++twins;
+    return (cs.nodes.size() + 2 + twins) * 32 + cs.spheres.size() * 16;
+}
 
 // Returns RT_OK or a negative RtStatus; `out.error` explains.
 int compile_scene(const RtSceneDesc& desc, const CompileOptions& opt, CompiledScene& out);
