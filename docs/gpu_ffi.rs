@@ -78,6 +78,7 @@ pub const RT_BVH_REFERENCE: i32 = 0;     // BVHNode::construct as intended (bvh.
 pub const RT_BVH_SAH: i32 = 1;           // binned SAH: same picture, fewer node visits
 
 pub const RT_SCENE_LIGHTS_ALL_SHAPES: u32 = 1;   // RtSceneDesc.scene_flags: rects of any orientation, triangles, boxes and wrapped members are sampled as lights
+pub const RT_SCENE_LIGHTS_MANY: u32 = 4;         // RtSceneDesc.scene_flags, with RT_SCENE_LIGHTS_ALL_SHAPES: area-weighted pick, the list's pdf through a light tree
 #[repr(C)]
 pub struct RtSceneDesc {
     pub abi_version: u32, pub scene_flags: u32,
@@ -221,6 +222,7 @@ pub struct RtCompileInfo {
 }
 
 pub const RT_LIGHTQ_DIRECTION_GIVEN: u32 = 1;    // RtLightQuery.flags: evaluate the pdf of the caller's d, draw nothing
+pub const RT_LIGHTQ_LINEAR: u32 = 2;             // RtLightQuery.flags: a scene with a light tree evaluates the pdf by the plain loop over its table
 #[repr(C)] #[derive(Clone, Copy, Default, Debug)]
 pub struct RtLightQuery { pub p: [f32; 3], pub flags: u32, pub rng_state: u64, pub d: [f32; 3], pub _pad: f32 }       // 40 B
 #[repr(C)] #[derive(Clone, Copy, Default, Debug)]
@@ -358,6 +360,9 @@ extern "C" {
     pub fn rt_scene_compile_info_ex(desc: *const RtSceneDesc, options: *const RtUploadOptions, out: *mut RtCompileInfo) -> c_int;
     pub fn rt_scene_compile_dump_ex(desc: *const RtSceneDesc, options: *const RtUploadOptions, nodes: *mut c_void, cap_nodes: u64,
                                     spheres: *mut f32, sphere_meta: *mut u32, cap_spheres: u64) -> c_int;
+    /// host only: the light tree of an RT_SCENE_LIGHTS_MANY scene (32-byte records), slot -> member, p and cdf by member; any output may be null
+    pub fn rt_scene_light_tree_dump(desc: *const RtSceneDesc, nodes: *mut c_void, cap_nodes: u64, slot_member: *mut u32, p: *mut f32, cdf: *mut f32,
+                                    cap_lights: u64, out_n_lights: *mut u64, out_n_nodes: *mut u64) -> c_int;
     pub fn rt_scene_wide_layout_check(desc: *const RtSceneDesc, out: *mut RtWideInfo) -> c_int;
     pub fn rt_scene_top_layout_check(desc: *const RtSceneDesc, max_top: u32, out_n_top: *mut u64) -> c_int;
     pub fn rt_scene_compile_dump(desc: *const RtSceneDesc, nodes: *mut c_void, cap_nodes: u64, spheres: *mut f32,

@@ -159,11 +159,28 @@ typedef enum RtBvhBuilder {
  * Anything else in the lights list — a moving sphere, a medium, a nested list, a BVH, a rect or triangle of zero area, a deeper chain — is
  * RT_ERR_INVALID with the reason, and nothing is uploaded. The list semantics stay the reference's: the pick is next64() % n, uniform over
  * the members whatever their size, and the list's pdf is the mean of the members' pdfs, occluded or not.
- * LIMIT: the cost is linear in the number of lights per Lambertian bounce (every member's pdf is evaluated for every scattered ray); an
- * emissive mesh of thousands of triangles is slow. There is no light BVH and no area-weighted pick.
+ * LIMIT (of RT_SCENE_LIGHTS_ALL_SHAPES alone): the cost is linear in the number of lights per Lambertian bounce (every member's pdf is
+ * evaluated for every scattered ray) and the pick ignores the members' size; an emissive mesh of thousands of triangles is slow and noisy.
+ * With this flag alone there is no light BVH and no area-weighted pick. RT_SCENE_LIGHTS_MANY brings both; what stays: the pick weighs by area, not by emitted power, and a leaf of the light tree holds one member.
  * RtStats.prim_tests counts the light tests with their kind: triangles in the triangle slot, rects and boxes (six each) in the rect slot,
- * spheres in the sphere slot. A list of bare XZ rects and spheres runs the same kernels and uploads the same bytes with the flag as without. */
-enum { RT_SCENE_LIGHTS_ALL_SHAPES = 1u };
+ * spheres in the sphere slot. A list of bare XZ rects and spheres runs the same kernels and uploads the same bytes with the flag as without.
+ *
+ * RT_SCENE_LIGHTS_MANY (needs RT_SCENE_LIGHTS_ALL_SHAPES: alone it is RT_ERR_INVALID; value 2 stays an unknown bit): the list for many lights.
+ * Every refusal above applies unchanged. What changes:
+ *   - PICK. A member is picked with probability proportional to its surface area, from the desc's f64 parameters: rect |(a1-a0)(b1-b0)|,
+ *     triangle 0.5 |e1 x e2|, box 2 (dx dy + dy dz + dz dx), sphere 4 pi r^2. Host rule, f64, list order: total = the sequential sum of the
+ *     areas; p_k = (float)(A_k / total); cdf_k = (float)((A_0 + .. + A_k) / total), summed sequentially; cdf_{n-1} = 1.0f exactly. Device
+ *     rule: u = ONE rnd() draw (where the uniform pick spends one next64()), k = the first index with cdf_k > u (binary search). The member's
+ *     own `random` is unchanged, the box's uniform side pick included. RtLightSample.light stays the member's index in the caller's list.
+ *   - PDF. The list's pdf at (p, d) is sum_k p_k pdf_k(p, d) over all members, occluded or not: with the pick above the estimator stays
+ *     unbiased. It is evaluated through a binary tree over the members' padded world-space boxes (built on the host, deterministic; one
+ *     member per leaf, 2n - 1 records in pre-order with skip links): a member whose box the ray (t > 0.001) misses is not tested. The
+ *     tree only culls; the sum runs over the members in the tree's leaf order with one fmaf per member, whichever way it is evaluated
+ *     (RT_LIGHTQ_LINEAR below). rt_scene_light_tree_dump shows the records, the order and the weights.
+ *   - The scene always takes the extended light records (RtCompileInfo.features has 256 and 512), also for a list of bare XZ rects and spheres.
+ *   - RtStats.prim_tests counts the member tests that are made, by kind, as above; the light tree's own box tests are NOT counted into
+ *     node_tests (that figure stays the world walk's). */
+enum { RT_SCENE_LIGHTS_ALL_SHAPES = 1u, RT_SCENE_LIGHTS_MANY = 4u };
 
 typedef struct RtSceneDesc {
     uint32_t abi_version;   /* RT_ABI_VERSION */
@@ -672,10 +689,14 @@ int rt_occluded_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* 
  * Works with RT_SCENE_LIGHTS_ALL_SHAPES set or clear (clear: the reference's kinds, LK_DEFAULT members included). A scene with lights = -1
  * is RT_ERR_UNSUPPORTED. An unknown bit in RtLightQueryOptions.flags (known: RT_FLAG_TIMING), struct_bytes < sizeof(RtLightQueryOptions),
  * n >= 2^32, or a NULL queries / results pointer with n > 0 is RT_ERR_INVALID; device buffers must be 8-byte aligned; a refused call
- * writes nothing. n == 0 is a no-op. An unknown bit in a QUERY's flags is ignored. One kernel on the context's stream, one lane per
+ * writes nothing. n == 0 is a no-op. An unknown bit in a QUERY's flags is ignored.
+ * RT_SCENE_LIGHTS_MANY scenes: the pick is the area-weighted one (ONE rnd() draw, RtSceneDesc.scene_flags has the rule) and pdf is the
+ * weighted sum, evaluated through the light tree. RT_LIGHTQ_LINEAR in a query's flags: the pdf is evaluated by the plain loop over the
+ * table instead, same order, same weights, no boxes; the two agree bit for bit unless a box culled a member the loop counts, which is
+ * a bug. In any other scene the bit changes nothing. One kernel on the context's stream, one lane per
  * query, no pool; results[i] is a function of (scene, query i) alone. RtStats: samples = n; render_ms; with RT_FLAG_TIMING other_ms =
  * the kernel. Both variants block until done. */
-enum { RT_LIGHTQ_DIRECTION_GIVEN = 1u };
+enum { RT_LIGHTQ_DIRECTION_GIVEN = 1u, RT_LIGHTQ_LINEAR = 2u };
 typedef struct RtLightQuery  { float p[3]; uint32_t flags; uint64_t rng_state; float d[3]; float _pad; } RtLightQuery;      /* 40 B */
 typedef struct RtLightSample { float d[3]; float pdf; int32_t light; uint32_t n_draws; } RtLightSample;                      /* 24 B */
 typedef struct RtLightQueryOptions {
@@ -828,7 +849,8 @@ typedef struct RtCompileInfo {
     uint64_t n_box_nodes;   /* of which carry a box (= BVHNode count of the reference tree) */
     uint64_t n_spheres, n_moving, n_rects, n_tris, n_media, n_xforms, n_lights, n_materials;
     uint32_t features;      /* kernel feature bits the scene needs (128: a triangle on the device carries attributes, n_tri_attrs > 0;
-                               256: RT_SCENE_LIGHTS_ALL_SHAPES and a light that is not a bare XZ rect or sphere) */
+                               256: RT_SCENE_LIGHTS_ALL_SHAPES and a light that is not a bare XZ rect or sphere, or RT_SCENE_LIGHTS_MANY;
+                               512: RT_SCENE_LIGHTS_MANY, the lights table carries the light tree) */
     uint32_t fits_lds;      /* nodes + sphere records fit the LDS staging budget */
     uint32_t n_first;       /* primitives tested when a walk begins instead of being met by it (none with RT_LAYOUT_LISTS_AS_REFERENCE) ... */
     uint32_t first[4];      /* ... as leaf words: kind << 28 | count << 24 | first index (kind 1 = sphere, 2 = moving sphere, 5 = medium); they are not in the node records */
@@ -842,6 +864,17 @@ int rt_scene_compile_dump(const RtSceneDesc* desc, void* nodes, uint64_t cap_nod
                           float* spheres, uint32_t* sphere_meta, uint64_t cap_spheres);
 int rt_scene_compile_dump_ex(const RtSceneDesc* desc, const RtUploadOptions* options, void* nodes, uint64_t cap_nodes,
                              float* spheres, uint32_t* sphere_meta, uint64_t cap_spheres);
+
+/* RT_SCENE_LIGHTS_MANY (host only): the light tree and the weights as the upload lays them out. n = members of the lights list.
+     nodes   2n - 1 records of 32 B in pre-order, the device's form (csrc/device_types.h NodeDev): f32 cx, cy, hx, hy, cz, hz (the box is
+             centre -+ half extent, pad included), u32 skip (index of the first record after this one's subtree, <= 2n - 1), u32 leaf
+             (0: an inner record, its first child is the next record; else 1 + the slot of its member)
+     slot_member[s]  the member (index in the caller's list) whose record is slot s of the reordered table: the leaves left to right
+     p[k], cdf[k]    by member k, in list order (RtSceneDesc.scene_flags has the rule)
+   Any output pointer may be NULL; *out_n_lights and *out_n_nodes are always written. cap_nodes < 2n - 1 with nodes, or cap_lights < n
+   with one of the other three, is RT_ERR_INVALID; so is a scene without the flag. */
+int rt_scene_light_tree_dump(const RtSceneDesc* desc, void* nodes, uint64_t cap_nodes, uint32_t* slot_member, float* p, float* cdf, uint64_t cap_lights,
+                             uint64_t* out_n_lights, uint64_t* out_n_nodes);
 
 /* Builds the layout used when a scene does not fit LDS as a whole — the array in HBM plus an LDS copy of the top of the tree (at most
    max_top records), linked in one address space — and checks it on the host: the walk that passes every box enumerates all records

@@ -18,4 +18,4 @@ from .progressive import Progressive, check_checkpoint, std_error  # noqa: F401
 from .scene import SceneBuilder  # noqa: F401
 from .scene_json import JsonScene, load_scene, parse_obj, parse_obj_attrs  # noqa: F401
 from .mesh import icosphere, interpolate_reference, sphere_uv  # noqa: F401
-from .lights import light_reference, solid_angle_triangle  # noqa: F401
+from .lights import light_reference, light_tree, light_weights, solid_angle_triangle  # noqa: F401

@@ -26,8 +26,11 @@ RT_FEATURES_ACCUMULATE = 1
 RT_TRI_NORMALS, RT_TRI_UVS = 1, 2
 RT_FEATURE_TRI_ATTR = 128      # RtCompileInfo.features: a triangle carries attributes (csrc/kernels.h F_TRI_ATTR)
 RT_FEATURE_LIGHTS_EXT = 256    # RtCompileInfo.features: the lights table holds extended records (csrc/kernels.h F_LIGHTS_EXT)
+RT_FEATURE_LIGHTS_TREE = 512   # RtCompileInfo.features: the lights table carries the light tree (csrc/kernels.h F_LIGHTS_TREE)
 RT_SCENE_LIGHTS_ALL_SHAPES = 1  # RtSceneDesc.scene_flags
+RT_SCENE_LIGHTS_MANY = 4        # RtSceneDesc.scene_flags: area-weighted pick and the light tree; needs RT_SCENE_LIGHTS_ALL_SHAPES
 RT_LIGHTQ_DIRECTION_GIVEN = 1   # RtLightQuery.flags
+RT_LIGHTQ_LINEAR = 2            # RtLightQuery.flags: a scene with a light tree evaluates the pdf by the plain loop over the table
 # RtUploadOptions.layout_flags
 (RT_LAYOUT_LISTS_AS_REFERENCE, RT_LAYOUT_LISTS_CULLED, RT_LAYOUT_NO_MEMBER_BOXES, RT_LAYOUT_MEMBER_BOXES, RT_LAYOUT_CHILD_ORDER_AS_REFERENCE,
  RT_LAYOUT_SCENE_IN_HBM, RT_LAYOUT_NODES_32B, RT_LAYOUT_NO_SHADE_TABLES_IN_LDS, RT_LAYOUT_NO_EXTEND_TABLES_IN_LDS, RT_LAYOUT_WIDE_NODES,
@@ -198,7 +201,7 @@ RT_HIP_SYMBOLS = ["rt_ctx_create", "rt_ctx_destroy", "rt_scene_upload", "rt_scen
                   "rt_adaptive_check", "rt_adaptive_select", "rt_render_pass_pixels_device", "rt_resolve_counts_device",
                   "rt_denoise_check", "rt_denoise_device", "rt_denoise_guided_check", "rt_denoise_guided_device",
                   "rt_ray_query_check", "rt_trace_rays_device", "rt_trace_rays", "rt_occluded_rays_device", "rt_occluded_rays",
-                  "rt_sample_lights_device", "rt_sample_lights",
+                  "rt_sample_lights_device", "rt_sample_lights", "rt_scene_light_tree_dump",
                   "rt_features_check", "rt_render_features_device",
                   "rt_feature_moments_check", "rt_render_feature_moments_device", "rt_denoise_guided_moments_check", "rt_denoise_guided_moments_device"]
 RT_HOST_SYMBOLS = ["rt_host_scene_create", "rt_host_scene_desc", "rt_host_scene_camera", "rt_host_scene_destroy", "rt_host_camera_new",
@@ -297,6 +300,8 @@ def declare(lib):
     lib.rt_scene_compile_dump_ex.argtypes = [P(RtSceneDesc), P(RtUploadOptions), vp, u64, P(C.c_float), P(u32), u64]
     lib.rt_scene_wide_layout_check.restype = i32
     lib.rt_scene_wide_layout_check.argtypes = [P(RtSceneDesc), P(RtWideInfo)]
+    lib.rt_scene_light_tree_dump.restype = i32
+    lib.rt_scene_light_tree_dump.argtypes = [P(RtSceneDesc), vp, u64, P(u32), P(C.c_float), P(C.c_float), u64, P(u64), P(u64)]
     lib.rt_scene_compile_dump.restype = i32
     lib.rt_scene_compile_dump.argtypes = [P(RtSceneDesc), vp, u64, P(C.c_float), P(u32), u64]
     lib.rt_untile_rgb8.restype = i32

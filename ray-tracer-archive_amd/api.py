@@ -571,15 +571,16 @@ class Context:
         q["p"], q["rng_state"] = points, states
         return self._light_queries(scene, q, with_stats)
 
-    def light_pdf(self, scene, points, dirs, with_stats=False):
+    def light_pdf(self, scene, points, dirs, with_stats=False, linear=False):
         """rt_sample_lights with RT_LIGHTQ_DIRECTION_GIVEN: the lights list's pdf_value at (point, direction), nothing drawn. Returns the pdfs
-        (float32, n)."""
+        (float32, n). linear: RT_LIGHTQ_LINEAR — a scene with a light tree (RT_SCENE_LIGHTS_MANY) evaluates the sum by the plain loop over its
+        table instead of through the tree; any other scene ignores it."""
         points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
         dirs = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
         if dirs.shape[0] != points.shape[0]:
             raise ValueError("one direction per point")
         q = np.zeros(points.shape[0], dtype=LIGHTQUERY_DTYPE)
-        q["p"], q["d"], q["flags"] = points, dirs, A.RT_LIGHTQ_DIRECTION_GIVEN
+        q["p"], q["d"], q["flags"] = points, dirs, A.RT_LIGHTQ_DIRECTION_GIVEN | (A.RT_LIGHTQ_LINEAR if linear else 0)
         r = self._light_queries(scene, q, with_stats)
         return (r[0]["pdf"].copy(), r[1]) if with_stats else r["pdf"].copy()
 

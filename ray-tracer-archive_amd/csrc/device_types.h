@@ -139,10 +139,18 @@ enum LightXKind : uint32_t { LX_RECT = 1, LX_SPHERE = 2, LX_TRI = 3, LX_BOX = 4 
 struct LightX {
     uint32_t kind;
     uint32_t has_xform;      // 1: the member sits under Translate / RotateY wrappers, composed into xf (world -> the member's own space)
-    uint32_t _pad[2];
-    float p[12];             // rect: a0 a1 b0 b1 k kaxis(0 = Yz, 1 = Xz, 2 = Xy)   sphere: c.xyz r   triangle: v0 v1 v2   box: x0 x1 y0 y1 z0 z1
+    uint32_t _pad[2];        // light tree (below): [0] = the bits of p_k (f32), the member's weight in the list's pdf; [1] = its index in the caller's list
+    float p[12];            // rect: a0 a1 b0 b1 k kaxis(0 = Yz, 1 = Xz, 2 = Xy)   sphere: c.xyz r   triangle: v0 v1 v2   box: x0 x1 y0 y1 z0 z1
     Xform xf;
 };
 static_assert(sizeof(Light) == 32 && sizeof(LightX) == 3 * sizeof(Light), "an extended light record takes three slots of the lights table");
+// RT_SCENE_LIGHTS_MANY (kernels.h F_LIGHTS_TREE): the ONE lights allocation holds, for n members and in units of 32-byte slots,
+//   [0, 3n)          the LightX records in LEAF order of the tree below (slot s = the s-th leaf from the left)
+//   [3n, 5n - 1)     the light tree: 2n - 1 NodeDev records in pre-order. skip_bytes = INDEX of the first record after the subtree (<= 2n - 1),
+//                    leaf = 0 for an inner record (first child: the next record), 1 + slot for a leaf
+//   [5n - 1, ..)     cdf[n] (f32, LIST order), then member -> slot [n] (u32), zero-filled up to a whole slot
+// Everything is found from (lights, n_lights): SceneDev does not change, and the table moves into k_shade's LDS blob as one piece when it is small.
+inline uint32_t light_tree_nodes(uint32_t n) { return 2u * n - 1u; }
+inline uint32_t light_tree_slots(uint32_t n) { return 5u * n - 1u + (8u * n + 31u) / 32u; }   // Light slots of the whole table (n < 2^28: scene_compile.cpp)
 
 }  // namespace rtd

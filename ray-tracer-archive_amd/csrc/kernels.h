@@ -17,7 +17,10 @@ enum : uint32_t {
     F_TRI_ATTR = 128u,
     // the lights table holds rtd::LightX records (device_types.h): RT_SCENE_LIGHTS_ALL_SHAPES and a member that is not a bare XzRect or Sphere.
     // Not part of F_ALL either: only k_shade and the drain / fused form of k_extend have instances with it, and only for the full variant.
-    F_LIGHTS_EXT = 256u
+    F_LIGHTS_EXT = 256u,
+    // RT_SCENE_LIGHTS_MANY: the lights table also holds the light tree, the cdf of the area-weighted pick and the member -> slot table
+    // (device_types.h); always together with F_LIGHTS_EXT. The same kernels have instances with it, and k_sample_lights one.
+    F_LIGHTS_TREE = 512u
 };
 #define RT_N_PRIM_TYPES_K 6
 enum : uint32_t { CTR_NODE_TESTS = 0, CTR_PRIM_TESTS = 1, CTR_SAMPLES = 7, CTR_DEBUG = 8, CTR_SEGMENTS = 13, CTR_ITERATIONS = 14, CTR_COUNT = 16 };
@@ -204,9 +207,9 @@ hipError_t launch_occluded_import(const void* rays, uint32_t first, uint32_t n, 
 hipError_t launch_extend_any(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
                              uint32_t* head, uint32_t* count_out_to_zero, unsigned long long* counters, hipStream_t stream);
 hipError_t launch_occluded_export(const PoolDev& pool, uint32_t queue_cap, uint32_t max_count, const uint32_t* counts, void* occluded, hipStream_t stream);
-// light-sample queries (kernels.hip "light-sample queries"): n RtLightQuery records -> n RtLightSample records, one lane each, no pool. ext: the scene's
-// lights table holds rtd::LightX records (F_LIGHTS_EXT). The scene has lights (n_lights > 0).
-hipError_t launch_sample_lights(const SceneDev& sc, bool ext, const void* queries, void* results, uint32_t n, hipStream_t stream);
+// light-sample queries (kernels.hip "light-sample queries"): n RtLightQuery records -> n RtLightSample records, one lane each, no pool. features: the
+// scene's (F_LIGHTS_EXT: the lights table holds rtd::LightX records; F_LIGHTS_TREE: and the light tree). The scene has lights (n_lights > 0).
+hipError_t launch_sample_lights(const SceneDev& sc, uint32_t features, const void* queries, void* results, uint32_t n, hipStream_t stream);
 // first-hit features (kernels.hip "first-hit features"). FeatDev: one chunk of a feature pass — samples [k0, k0 + nk) of the pass, of output
 // slots [slot0, slot0 + ns) — and where its results go; its own block, like RaySrcDev. Ray r = k * ns + s of the chunk is sample
 // first_sample + k0 + k of slot slot0 + s; its 32-byte record is rec[2 r], rec[2 r + 1].

@@ -1766,14 +1766,76 @@ DEVI V3 lightx_random(const rtd::LightX& l, V3 o, Rng& g) {
 // the Lambertian branch of shade_segment in the instances with F_LIGHTS_EXT. The instances without the bit keep the same statements in line
 // (over the same light_random / light_pdf_value): written as calls, their loop came out of hipcc with its exit test inverted, and the
 // instruction text of the existing instances is pinned.
+// RT_SCENE_LIGHTS_MANY (rt_hip.h; instances with F_LIGHTS_TREE only): where the parts of the lights table lie behind its n LightX records
+// (device_types.h), all found from (sc.lights, sc.n_lights) — in HBM or, for a small table, in k_shade's LDS blob alike.
+DEVI const Float4* light_tree_records(const SceneDev& sc) { return reinterpret_cast<const Float4*>(sc.lights + 3u * sc.n_lights); }
+DEVI const float* light_tree_cdf(const SceneDev& sc) { return reinterpret_cast<const float*>(sc.lights + (5u * sc.n_lights - 1u)); }
+DEVI const uint32_t* light_tree_slots(const SceneDev& sc) { return reinterpret_cast<const uint32_t*>(light_tree_cdf(sc) + sc.n_lights); }
+// one member's share of the list's pdf. ONE function and an explicit fmaf: the walk of the tree and the plain loop round alike, so
+// they differ only where a box culled a member the loop counts (a member that is skipped would have added w * 0 = nothing).
+DEVI float light_accumulate(float sum, float w, float pdf) { return fmaf(w, pdf, sum); }
 template <uint32_t FEAT>
 DEVI V3 lights_random(const SceneDev& sc, V3 p, Rng& g, uint32_t& k) {
+    if constexpr ((FEAT & F_LIGHTS_TREE) != 0u) {
+        // area-weighted pick: ONE draw, the first member whose cdf exceeds it (cdf in list order, its last entry exactly 1 > u). The
+        // interval halves every trip: 32 trips cover any n, whatever the table holds.
+        const float u = g.rnd();
+        const float* cdf = light_tree_cdf(sc);
+        uint32_t lo = 0u, hi = sc.n_lights - 1u;
+        for (uint32_t trip = 0u; trip < 32u && lo < hi; ++trip) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (cdf[mid] > u) hi = mid; else lo = mid + 1u;
+        }
+        k = lo;
+        const uint32_t slot = min(light_tree_slots(sc)[k], sc.n_lights - 1u);
+        return lightx_random(reinterpret_cast<const rtd::LightX*>(sc.lights)[slot], p, g);
+    }
     k = (uint32_t)(g.next64() % (uint64_t)sc.n_lights);   // hittable_list.rs:81-84
     if constexpr ((FEAT & F_LIGHTS_EXT) != 0u) return lightx_random(reinterpret_cast<const rtd::LightX*>(sc.lights)[k], p, g);
     else return light_random(sc.lights[k], p, g);
 }
+// The list's pdf through the light tree: sum of p_k pdf_k over the members whose box the ray meets at some t in (kTMin, inf), one lane per
+// ray. A record is the world walk's (NodeDev: centre and half extent, set_slab_ray's constants, the same slab expressions); a miss follows
+// the skip link, a hit goes on to the next record, and at a leaf the member's own pdf is evaluated first. Leaves come in slot order, the
+// order of the plain loop below. The host has checked every link (index < skip <= n_nodes); the trip count bounds the walk all the same.
+// The tree's box tests are not counted (RtStats.node_tests is the world walk's); the member tests are, by kind.
+DEVI float lights_tree_pdf_value(const SceneDev& sc, V3 p, V3 dir, unsigned long long& c_light_rect, unsigned long long& c_light_sphere, unsigned long long& c_light_tri) {
+    const uint32_t n_nodes = 2u * sc.n_lights - 1u;
+    const Float4* recs = light_tree_records(sc);
+    SlabRay sr;
+    set_slab_ray(p, dir, sr);
+    float lsum = 0.f;
+    uint32_t node = 0u;
+    for (uint32_t trip = 0u; trip < n_nodes && node < n_nodes; ++trip) {
+        const Float4 n0 = recs[2u * node], n1 = recs[2u * node + 1u];
+        const F2 tc = __builtin_elementwise_fma(F2{n0.x, n0.y}, sr.inv_xy, sr.noi_xy);
+        const F2 th = __builtin_elementwise_fma(F2{n0.z, n0.w}, sr.ainv_xy, sr.e_xy);
+        const F2 tz = __builtin_elementwise_fma(F2{n1.x, n1.y}, sr.inv_z, sr.noi_z);
+        const F2 lo = tc - th, hi = tc + th;
+        const float tnear = fmaxf(fmaxf(lo.x, lo.y), fmaxf(tz.x - tz.y, kTMin));
+        const float tfar = fminf(fminf(hi.x, hi.y), fminf(tz.x + tz.y, kInf));
+        const uint32_t skip = __float_as_uint(n1.z), leaf = __float_as_uint(n1.w);
+        const bool pass = tnear <= tfar;
+        if (pass && leaf != 0u && leaf <= sc.n_lights) {
+            const rtd::LightX l = reinterpret_cast<const rtd::LightX*>(sc.lights)[leaf - 1u];
+            lsum = light_accumulate(lsum, __uint_as_float(l._pad[0]), lightx_pdf_value(l, p, dir, c_light_rect, c_light_sphere, c_light_tri));
+        }
+        node = (pass && leaf == 0u) ? node + 1u : skip;
+    }
+    return lsum;
+}
 template <uint32_t FEAT>
-DEVI float lights_pdf_value(const SceneDev& sc, V3 p, V3 dir, unsigned long long& c_light_rect, unsigned long long& c_light_sphere, unsigned long long& c_light_tri) {
+DEVI float lights_pdf_value(const SceneDev& sc, V3 p, V3 dir, unsigned long long& c_light_rect, unsigned long long& c_light_sphere, unsigned long long& c_light_tri,
+                            bool linear = false) {
+    if constexpr ((FEAT & F_LIGHTS_TREE) != 0u) {
+        if (!linear) return lights_tree_pdf_value(sc, p, dir, c_light_rect, c_light_sphere, c_light_tri);
+        float lsum = 0.f;                                  // RT_LIGHTQ_LINEAR: every member, in the table's order, with its own weight
+        for (uint32_t k = 0; k < sc.n_lights; ++k) {
+            const rtd::LightX l = reinterpret_cast<const rtd::LightX*>(sc.lights)[k];
+            lsum = light_accumulate(lsum, __uint_as_float(l._pad[0]), lightx_pdf_value(l, p, dir, c_light_rect, c_light_sphere, c_light_tri));
+        }
+        return lsum;
+    }
     const float weight = 1.0f / (float)sc.n_lights;
     float lsum = 0.f;
     if constexpr ((FEAT & F_LIGHTS_EXT) != 0u) {
@@ -2465,10 +2527,11 @@ __global__ void __launch_bounds__(256) k_occluded_export(PoolDev pool, uint32_t 
 // Records as rt_hip.h declares them (RtLightQuery 40 B, RtLightSample 24 B). The generator is seeded (rng_state, 0 draws); the pick, the draw
 // and the list's pdf are lights_random / lights_pdf_value, the functions shade_segment calls. The tables are read where the upload put
 // them (no LDS staging: a query kernel is a few loads per lane). EXT: the scene's lights table holds rtd::LightX records (F_LIGHTS_EXT).
+// k_sample_lights_tree: the same for a table with the light tree (F_LIGHTS_TREE); RT_LIGHTQ_LINEAR in a query's flags asks for the plain loop.
 struct LightQueryDev { float p[3]; uint32_t flags; uint64_t rng_state; float d[3]; float _pad; };
 struct LightSampleDev { float d[3]; float pdf; int32_t light; uint32_t n_draws; };
 static_assert(sizeof(LightQueryDev) == 40 && sizeof(LightSampleDev) == 24, "light query records: 40 and 24 bytes");
-constexpr uint32_t kLightQDirectionGiven = 1u;
+constexpr uint32_t kLightQDirectionGiven = 1u, kLightQLinear = 2u;
 template <bool EXT>
 __global__ void __launch_bounds__(256) k_sample_lights(SceneDev sc, const LightQueryDev* __restrict__ queries, LightSampleDev* __restrict__ results, uint32_t n) {
     constexpr uint32_t FEAT = F_LIGHTS | (EXT ? F_LIGHTS_EXT : 0u);
@@ -2486,6 +2549,25 @@ __global__ void __launch_bounds__(256) k_sample_lights(SceneDev sc, const LightQ
     }
     unsigned long long c0 = 0, c1 = 0, c2 = 0;
     r.pdf = lights_pdf_value<FEAT>(sc, p, dir, c0, c1, c2);
+    r.d[0] = dir.x; r.d[1] = dir.y; r.d[2] = dir.z;
+    results[i] = r;
+}
+__global__ void __launch_bounds__(256) k_sample_lights_tree(SceneDev sc, const LightQueryDev* __restrict__ queries, LightSampleDev* __restrict__ results, uint32_t n) {
+    constexpr uint32_t FEAT = F_LIGHTS | F_LIGHTS_EXT | F_LIGHTS_TREE;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const LightQueryDev q = queries[i];
+    const V3 p = v3(q.p[0], q.p[1], q.p[2]);
+    V3 dir = v3(q.d[0], q.d[1], q.d[2]);
+    LightSampleDev r; r.light = -1; r.n_draws = 0u;
+    if ((q.flags & kLightQDirectionGiven) == 0u) {
+        Rng g; g.s = q.rng_state; g.n = 0u;
+        uint32_t k;
+        dir = lights_random<FEAT>(sc, p, g, k);
+        r.light = (int32_t)k; r.n_draws = g.n;
+    }
+    unsigned long long c0 = 0, c1 = 0, c2 = 0;
+    r.pdf = lights_pdf_value<FEAT>(sc, p, dir, c0, c1, c2, (q.flags & kLightQLinear) != 0u);
     r.d[0] = dir.x; r.d[1] = dir.y; r.d[2] = dir.z;
     results[i] = r;
 }
@@ -2767,9 +2849,15 @@ template <class F> static auto with_record_variant(uint32_t features, F&& f) {
 // ... and k_shade and the drain / fused form of k_extend two more for scenes whose lights table holds extended records (F_LIGHTS_EXT: RT_SCENE_LIGHTS_ALL_SHAPES
 // with a member that is not a bare XzRect or Sphere): the full variant, without and with triangle attributes. The ray-query and feature-export kernels
 // sample no light and never see the bit (with_record_variant).
+// ... and two more again for scenes whose lights table carries the light tree (F_LIGHTS_TREE: RT_SCENE_LIGHTS_MANY, always with F_LIGHTS_EXT).
 constexpr uint32_t kVariantAllLx = F_ALL | F_LIGHTS_EXT, kVariantAllAttrLx = F_ALL | F_TRI_ATTR | F_LIGHTS_EXT;
+constexpr uint32_t kVariantAllLt = kVariantAllLx | F_LIGHTS_TREE, kVariantAllAttrLt = kVariantAllAttrLx | F_LIGHTS_TREE;
 template <class F> static auto with_shade_variant(uint32_t features, F&& f) {
     if ((features & F_LIGHTS_EXT) == 0u) return with_record_variant(features, f);
+    if ((features & F_LIGHTS_TREE) != 0u) {
+        if ((features & F_TRI_ATTR) == 0u) return f(std::integral_constant<uint32_t, kVariantAllLt>{});
+        return f(std::integral_constant<uint32_t, kVariantAllAttrLt>{});
+    }
     if ((features & F_TRI_ATTR) == 0u) return f(std::integral_constant<uint32_t, kVariantAllLx>{});
     return f(std::integral_constant<uint32_t, kVariantAllAttrLx>{});
 }
@@ -2982,11 +3070,13 @@ hipError_t launch_occluded_export(const PoolDev& pool, uint32_t queue_cap, uint3
     return hipGetLastError();
 }
 
-hipError_t launch_sample_lights(const SceneDev& sc, bool ext, const void* queries, void* results, uint32_t n, hipStream_t stream) {
+hipError_t launch_sample_lights(const SceneDev& sc, uint32_t features, const void* queries, void* results, uint32_t n, hipStream_t stream) {
     const uint32_t blocks = (n + 255u) / 256u;
     if (blocks == 0u) return hipSuccess;
     if (sc.n_lights == 0u) return hipErrorInvalidValue;                  // (the host refuses a scene without lights before anything is launched)
-    with_flag(ext, [&](auto e) {
+    if ((features & F_LIGHTS_TREE) != 0u)
+        hipLaunchKernelGGL(k_sample_lights_tree, dim3(blocks), dim3(256), 0, stream, sc, (const LightQueryDev*)queries, (LightSampleDev*)results, n);
+    else with_flag((features & F_LIGHTS_EXT) != 0u, [&](auto e) {
         hipLaunchKernelGGL(k_sample_lights<decltype(e)::value>, dim3(blocks), dim3(256), 0, stream, sc, (const LightQueryDev*)queries, (LightSampleDev*)results, n); });
     return hipGetLastError();
 }

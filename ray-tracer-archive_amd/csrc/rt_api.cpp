@@ -46,6 +46,7 @@ static uint32_t scene_features(const rtc::CompiledScene& cs) {
     for (uint32_t mb : cs.mat_b) { const uint32_t kind = mb & 15u; if ((mb >> 4) != rtd::TEX_INLINE && kind != rtd::MK_METAL && kind != rtd::MK_DIELECTRIC) f |= rtk::F_TEX; }
     if (cs.has_lights) f |= rtk::F_LIGHTS;
     if (cs.lights_ext) f |= rtk::F_LIGHTS_EXT;
+    if (cs.lights_tree) f |= rtk::F_LIGHTS_TREE;
     return f;
 }
 
@@ -1338,7 +1339,7 @@ static int sample_lights_impl(RtCtx* ctx, const RtScene* scene, const RtLightQue
     StreamTimer tm{ctx};
     hipEvent_t ea = nullptr, eb = nullptr;
     if (timing) HIP_TRY(ctx, tm.mark(ea));
-    LAUNCH_TRY(rtk::launch_sample_lights(scene->dev, (scene->features & rtk::F_LIGHTS_EXT) != 0u, d_queries, d_results, (uint32_t)n, ctx->stream));
+    LAUNCH_TRY(rtk::launch_sample_lights(scene->dev, scene->features, d_queries, d_results, (uint32_t)n, ctx->stream));
     if (timing) { HIP_TRY(ctx, tm.mark(eb)); tm.span(ea, eb, 1); }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (stats) {
@@ -1544,6 +1545,24 @@ int rt_scene_compile_info_ex(const RtSceneDesc* desc, const RtUploadOptions* opt
         out->n_first = (uint32_t)std::min<size_t>(first.size(), 4);
         for (uint32_t k = 0; k < 4u; ++k) out->first[k] = k < first.size() ? first[k] : 0u;
     }
+    return RT_OK;
+}
+
+int rt_scene_light_tree_dump(const RtSceneDesc* desc, void* nodes, uint64_t cap_nodes, uint32_t* slot_member, float* p, float* cdf, uint64_t cap_lights,
+                             uint64_t* out_n_lights, uint64_t* out_n_nodes) {
+    if (!desc || !out_n_lights || !out_n_nodes) return set_err(nullptr, RT_ERR_INVALID, "null argument");
+    *out_n_lights = 0; *out_n_nodes = 0;
+    rtc::CompiledScene cs;
+    const int rc = rtc::compile_scene(*desc, cs);
+    if (rc != RT_OK) return set_err(nullptr, rc, "scene: " + cs.error);
+    if (!cs.lights_tree) return set_err(nullptr, RT_ERR_INVALID, "the scene has no light tree (RtSceneDesc.scene_flags without RT_SCENE_LIGHTS_MANY, or no lights list)");
+    const uint64_t n = cs.n_lights, n_nodes = rtd::light_tree_nodes(cs.n_lights);
+    *out_n_lights = n; *out_n_nodes = n_nodes;
+    if ((nodes && cap_nodes < n_nodes) || ((slot_member || p || cdf) && cap_lights < n)) return set_err(nullptr, RT_ERR_INVALID, "capacity too small");
+    if (nodes) std::memcpy(nodes, cs.lights.data() + 3 * n, n_nodes * sizeof(rtd::NodeDev));   // the records as the upload copies them
+    if (slot_member) std::memcpy(slot_member, cs.light_slot_member.data(), n * 4);
+    if (p) std::memcpy(p, cs.light_p.data(), n * 4);
+    if (cdf) std::memcpy(cdf, cs.light_cdf.data(), n * 4);
     return RT_OK;
 }
 

@@ -904,7 +904,9 @@ struct Compiler {
     // scene is refused. A list of bare XzRects and Spheres keeps the records (and the kernels) of a scene without the flag.
     void compile_lights_all_shapes(const std::vector<int>& ids) {
         std::vector<rtd::LightX> xs;
-        bool ext = false;
+        const bool many = (d.scene_flags & RT_SCENE_LIGHTS_MANY) != 0u;
+        std::vector<double> areas;                                             // RT_SCENE_LIGHTS_MANY: from the desc's f64 parameters (rt_hip.h has the rule)
+        bool ext = many;                                                       // ... which always takes the extended records
         for (size_t k = 0; k < ids.size(); ++k) {
             const std::string who = "lights list member " + std::to_string(k) + ": ";
             Chain c;
@@ -918,19 +920,22 @@ struct Compiler {
                 if (!((p[1] - p[0]) * (p[3] - p[2]) != 0.0)) { fail(who + "a rect of zero area cannot be sampled"); return; }
                 x.kind = rtd::LX_RECT; for (int i = 0; i < 5; ++i) x.p[i] = (float)p[i];
                 x.p[5] = h->kind == RT_HIT_XY_RECT ? 2.f : (h->kind == RT_HIT_XZ_RECT ? 1.f : 0.f);
+                areas.push_back(std::fabs((p[1] - p[0]) * (p[3] - p[2])));
                 break;
             case RT_HIT_TRIANGLE: {
                 const double e1[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]}, e2[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
                 const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
                 if (!(n[0] * n[0] + n[1] * n[1] + n[2] * n[2] > 0.0)) { fail(who + "a triangle of zero area cannot be sampled"); return; }
                 x.kind = rtd::LX_TRI; for (int i = 0; i < 9; ++i) x.p[i] = (float)p[i];
+                areas.push_back(0.5 * std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]));
                 break;
             }
             case RT_HIT_BOX:
                 for (int a = 0; a < 3; ++a) if (!(p[3 + a] - p[a] != 0.0)) { fail(who + "a box with sides of zero area cannot be sampled"); return; }
                 x.kind = rtd::LX_BOX; for (int a = 0; a < 3; ++a) { x.p[2 * a] = (float)p[a]; x.p[2 * a + 1] = (float)p[3 + a]; }
+                { const double dx = std::fabs(p[3] - p[0]), dy = std::fabs(p[4] - p[1]), dz = std::fabs(p[5] - p[2]); areas.push_back(2.0 * (dx * dy + dy * dz + dz * dx)); }
                 break;
-            case RT_HIT_SPHERE: x.kind = rtd::LX_SPHERE; for (int i = 0; i < 4; ++i) x.p[i] = (float)p[i]; break;
+            case RT_HIT_SPHERE: x.kind = rtd::LX_SPHERE; for (int i = 0; i < 4; ++i) x.p[i] = (float)p[i]; areas.push_back(4.0 * PI * p[3] * p[3]); break;
             case RT_HIT_MOVING_SPHERE: fail(who + "a moving sphere cannot be sampled as a light"); return;
             case RT_HIT_CONSTANT_MEDIUM: fail(who + "a constant medium cannot be sampled as a light"); return;
             case RT_HIT_LIST: fail(who + "a nested list cannot be sampled as a light (list its members)"); return;
@@ -952,8 +957,139 @@ struct Compiler {
             return;
         }
         out.lights_ext = true;
+        if (many) { compile_light_tree(ids, xs, areas); return; }
         out.lights.resize(3 * xs.size());
         std::memcpy(out.lights.data(), xs.data(), xs.size() * sizeof(rtd::LightX));
+    }
+
+    // RT_SCENE_LIGHTS_MANY (rt_hip.h): the weights, the light tree and the table device_types.h lays out.
+    //
+    // THE PAD. A box of the tree may only cull: it has to hold every point at which a member's own test (kernels.hip lightx_pdf_value) accepts
+    // a ray, and the slab test has to pass whenever the ray meets that set with t > t_min. The start is the compiler's own bounding_box of the
+    // wrapped member (bbox above: exact in f64, flat shapes 1e-4 thick), the boxes the world walk trusts. On top of it, per member and on
+    // every axis (L = the diagonal of that box, M = its largest |coordinate|):
+    //   (a) triangles: tri_hit's closed edges accept barycentrics with u, v >= -s and u + v <= 1 + s, s = kTriSlackMax = 2^-10. The farthest such
+    //       point is v2 + s (2 e2 - e1) (or its mirror image), at most 3 s L from the triangle; the f32 barycentrics are themselves off by at
+    //       most the rule's own bound, again <= s: 4 s L.
+    //   (b) every kind: the member is tested in f32 from f32 parameters, under a wrapper chain through an f32 sine and cosine, on a ray whose
+    //       origin the chain moves first. Each of these steps is a handful of roundings of quantities no larger than the ray's distance to
+    //       the member plus the member's own coordinates: the points a test accepts lie within some tens of eps (= 2^-24) times that
+    //       size of the exact shape (the grazing case, where the barycentrics are worst, moves the accepted crossing ALONG the ray, which
+    //       stays within its height above the plane). 2^-18 (M + L) = 64 eps (M + L) covers rays that start within a few M of the member,
+    //       which is every ray of a scene whose lights are part of it.
+    //   (c) the slab test's own rounding is paid where the world walk's is: 4.5 eps (|c| + h) per record (rt_api.cpp node_boxes has the
+    //       derivation), applied below to every record, and 5.5 eps |o| per ray (kernels.hip set_slab_ray).
+    // A parent's box is the union of its children's FINISHED boxes (centre -+ half extent as the device reads them), so containment holds
+    // for the numbers the device sees. The pad only costs tests: at Cornell size (M = 555) it is 3 mm.
+    static constexpr double kLightTriSlack = 0.0009765625;                     // kernels.hip kTriSlackMax
+    struct LightNode { double mn[3], mx[3]; uint32_t skip, leaf; };
+    uint32_t build_light_tree(std::vector<LightNode>& nodes, std::vector<uint32_t>& slot_member, const std::vector<Box3>& boxes, std::vector<uint32_t>& idx, size_t s, size_t e) {
+        const uint32_t me = (uint32_t)nodes.size();
+        nodes.push_back(LightNode{});
+        if (e - s == 1) {
+            const Box3& b = boxes[idx[s]];
+            for (int a = 0; a < 3; ++a) { nodes[me].mn[a] = b.mn[a]; nodes[me].mx[a] = b.mx[a]; }
+            slot_member.push_back(idx[s]);
+            nodes[me].leaf = (uint32_t)slot_member.size();                      // 1 + slot
+            nodes[me].skip = me + 1u;
+            return me;
+        }
+        // median split on the longest axis of the centroid bounds; ties by member index (a total order: the tree depends on the list alone)
+        double cmn[3], cmx[3];
+        for (int a = 0; a < 3; ++a) { cmn[a] = std::numeric_limits<double>::infinity(); cmx[a] = -cmn[a]; }
+        auto centre = [&](uint32_t k, int a) { return 0.5 * (boxes[k].mn[a] + boxes[k].mx[a]); };
+        for (size_t i = s; i < e; ++i) for (int a = 0; a < 3; ++a) { cmn[a] = std::min(cmn[a], centre(idx[i], a)); cmx[a] = std::max(cmx[a], centre(idx[i], a)); }
+        int axis = 0;
+        for (int a = 1; a < 3; ++a) if (cmx[a] - cmn[a] > cmx[axis] - cmn[axis]) axis = a;
+        std::sort(idx.begin() + (ptrdiff_t)s, idx.begin() + (ptrdiff_t)e, [&](uint32_t x, uint32_t y) {
+            const double cx = centre(x, axis), cy = centre(y, axis);
+            return cx < cy || (cx == cy && x < y);
+        });
+        const size_t mid = s + (e - s + 1) / 2;
+        build_light_tree(nodes, slot_member, boxes, idx, s, mid);
+        build_light_tree(nodes, slot_member, boxes, idx, mid, e);
+        nodes[me].leaf = 0u;
+        nodes[me].skip = (uint32_t)nodes.size();
+        return me;
+    }
+    // the box [mn, mx] as the device's centre and half extent, rounded outwards, with the record's share of the slab test's rounding (c above)
+    static void light_box_record(const double* mn, const double* mx, rtd::NodeDev& r) {
+        constexpr double kEps = 5.9604644775390625e-8;
+        const float inf = std::numeric_limits<float>::infinity();
+        float c[3], h[3];
+        for (int a = 0; a < 3; ++a) {
+            c[a] = (float)(0.5 * (mn[a] + mx[a]));
+            double hd = std::max(mx[a] - (double)c[a], (double)c[a] - mn[a]);
+            hd += 4.5 * kEps * (std::fabs((double)c[a]) + hd);
+            float hf = (float)hd; if ((double)hf < hd) hf = std::nextafterf(hf, inf);
+            h[a] = hf;
+        }
+        r.cx = c[0]; r.cy = c[1]; r.hx = h[0]; r.hy = h[1]; r.cz = c[2]; r.hz = h[2];
+    }
+    void compile_light_tree(const std::vector<int>& ids, const std::vector<rtd::LightX>& xs, const std::vector<double>& areas) {
+        const size_t n = xs.size();
+        if (n >= (1u << 24)) { fail("RT_SCENE_LIGHTS_MANY: more than 2^24 - 1 lights"); return; }
+        // ---- the weights (rt_hip.h: f64, list order, sequential sums) ----
+        double total = 0.0;
+        for (size_t k = 0; k < n; ++k) total += areas[k];
+        if (!(total > 0.0) || !std::isfinite(total)) { fail("RT_SCENE_LIGHTS_MANY: the lights' total area is not a positive finite number"); return; }
+        out.light_p.resize(n); out.light_cdf.resize(n);
+        double run = 0.0;
+        for (size_t k = 0; k < n; ++k) { run += areas[k]; out.light_p[k] = (float)(areas[k] / total); out.light_cdf[k] = (float)(run / total); }
+        out.light_cdf[n - 1] = 1.0f;
+        // ---- the members' padded boxes ----
+        std::vector<Box3> boxes(n);
+        for (size_t k = 0; k < n; ++k) {
+            Box3 b;
+            if (!bbox(ids[k], 0.0, 1.0, b)) { fail("lights list member " + std::to_string(k) + ": no bounding box"); return; }
+            double l2 = 0.0, m = 0.0;
+            for (int a = 0; a < 3; ++a) { l2 += (b.mx[a] - b.mn[a]) * (b.mx[a] - b.mn[a]); m = std::max(m, std::max(std::fabs(b.mn[a]), std::fabs(b.mx[a]))); }
+            const double l = std::sqrt(l2);
+            const double pad = (xs[k].kind == rtd::LX_TRI ? 4.0 * kLightTriSlack * l : 0.0) + (m + l) / 262144.0;
+            if (!std::isfinite(pad)) { fail("lights list member " + std::to_string(k) + ": its bounding box is not finite"); return; }
+            for (int a = 0; a < 3; ++a) { b.mn[a] -= pad; b.mx[a] += pad; }
+            boxes[k] = b;
+        }
+        // ---- the tree, then its records bottom-up ----
+        std::vector<LightNode> nodes; nodes.reserve(2 * n - 1);
+        std::vector<uint32_t> idx(n); for (size_t k = 0; k < n; ++k) idx[k] = (uint32_t)k;
+        out.light_slot_member.clear();
+        build_light_tree(nodes, out.light_slot_member, boxes, idx, 0, n);
+        const uint32_t n_nodes = (uint32_t)nodes.size();
+        std::vector<rtd::NodeDev> recs(n_nodes);
+        for (uint32_t i = n_nodes; i-- > 0u;) {
+            LightNode& nd = nodes[i];
+            if (nd.leaf == 0u) {
+                const uint32_t kids[2] = {i + 1u, nodes[i + 1u].skip};
+                for (int a = 0; a < 3; ++a) { nd.mn[a] = std::numeric_limits<double>::infinity(); nd.mx[a] = -nd.mn[a]; }
+                for (uint32_t c : kids) {
+                    const rtd::NodeDev& r = recs[c];
+                    const double cc[3] = {r.cx, r.cy, r.cz}, hh[3] = {r.hx, r.hy, r.hz};
+                    for (int a = 0; a < 3; ++a) { nd.mn[a] = std::min(nd.mn[a], cc[a] - hh[a]); nd.mx[a] = std::max(nd.mx[a], cc[a] + hh[a]); }
+                }
+            }
+            light_box_record(nd.mn, nd.mx, recs[i]);
+            recs[i].skip_bytes = nd.skip; recs[i].leaf = nd.leaf;
+        }
+        // ---- guard: no record may be able to send a walk backwards or out of the table (the device bounds its trips as well) ----
+        if (n_nodes != rtd::light_tree_nodes((uint32_t)n) || out.light_slot_member.size() != n) { fail("RT_SCENE_LIGHTS_MANY: the light tree does not have 2n - 1 records"); return; }
+        for (uint32_t i = 0; i < n_nodes; ++i)
+            if (!(recs[i].skip_bytes > i && recs[i].skip_bytes <= n_nodes) || recs[i].leaf > n) { fail("RT_SCENE_LIGHTS_MANY: light tree record " + std::to_string(i) + " has a link out of range"); return; }
+        // ---- the table ----
+        out.lights.assign(rtd::light_tree_slots((uint32_t)n), rtd::Light{});
+        unsigned char* base = reinterpret_cast<unsigned char*>(out.lights.data());
+        std::vector<uint32_t> member_slot(n);
+        for (size_t s = 0; s < n; ++s) {
+            const uint32_t k = out.light_slot_member[s];
+            member_slot[k] = (uint32_t)s;
+            rtd::LightX x = xs[k];
+            std::memcpy(&x._pad[0], &out.light_p[k], 4); x._pad[1] = k;
+            std::memcpy(base + s * sizeof(rtd::LightX), &x, sizeof(x));
+        }
+        std::memcpy(base + 3 * n * 32, recs.data(), (size_t)n_nodes * 32);
+        std::memcpy(base + (5 * n - 1) * 32, out.light_cdf.data(), n * 4);
+        std::memcpy(base + (5 * n - 1) * 32 + n * 4, member_slot.data(), n * 4);
+        out.lights_tree = true;
     }
 };
 
@@ -962,7 +1098,8 @@ struct Compiler {
 int compile_scene(const RtSceneDesc& desc, const CompileOptions& opt, CompiledScene& out) {
     out = CompiledScene();
     if (desc.abi_version != RT_ABI_VERSION) { out.error = "RtSceneDesc.abi_version mismatch"; return RT_ERR_INVALID; }
-    if (desc.scene_flags & ~(uint32_t)RT_SCENE_LIGHTS_ALL_SHAPES) { out.error = "RtSceneDesc.scene_flags holds an unknown bit (known: RT_SCENE_LIGHTS_ALL_SHAPES)"; return RT_ERR_INVALID; }
+    if (desc.scene_flags & ~(uint32_t)(RT_SCENE_LIGHTS_ALL_SHAPES | RT_SCENE_LIGHTS_MANY)) { out.error = "RtSceneDesc.scene_flags holds an unknown bit (known: RT_SCENE_LIGHTS_ALL_SHAPES, RT_SCENE_LIGHTS_MANY)"; return RT_ERR_INVALID; }
+    if ((desc.scene_flags & RT_SCENE_LIGHTS_MANY) && !(desc.scene_flags & RT_SCENE_LIGHTS_ALL_SHAPES)) { out.error = "RtSceneDesc.scene_flags: RT_SCENE_LIGHTS_MANY needs RT_SCENE_LIGHTS_ALL_SHAPES"; return RT_ERR_INVALID; }
     if (!desc.hittables || desc.n_hittables == 0) { out.error = "scene has no hittables"; return RT_ERR_INVALID; }
     if ((desc.n_children && !desc.children) || (desc.n_materials && !desc.materials) || (desc.n_textures && !desc.textures) ||
         (desc.n_perlins && !desc.perlins) || (desc.n_images && !desc.images)) { out.error = "null array with non-zero count"; return RT_ERR_INVALID; }

@@ -28,7 +28,10 @@ struct CompiledScene {
     std::vector<rtd::Light> lights;                                          // one record per light — or, lights_ext, one rtd::LightX in three slots each
     uint32_t n_lights = 0;                                                   // members of the lights list
     bool lights_ext = false;                                                 // RT_SCENE_LIGHTS_ALL_SHAPES and a member that is not a bare XzRect / Sphere
-    uint32_t first_leaf = 0;                                                 // leaf word of the spheres a walk tests before it enters the tree (emit_bvh: spheres as large as the scene), 0: none
+    bool lights_tree = false;                                                // RT_SCENE_LIGHTS_MANY: `lights` is the table device_types.h lays out (records in leaf order, tree, cdf, member -> slot)
+    std::vector<uint32_t> light_slot_member;                                 // ... and what rt_scene_light_tree_dump copies out beside the tree: slot -> member,
+    std::vector<float> light_p, light_cdf;                                   // p_k and cdf_k by member (list order)
+    uint32_t first_leaf = 0;                                                // leaf word of the spheres a walk tests before it enters the tree (emit_bvh: spheres as large as the scene), 0: none
     std::vector<uint32_t> prologue;                                          // leaf payloads of the root list's every-ray members (scene_compile.cpp: prologue_member)
     int background_mode = 0; float background[3] = {0, 0, 0};
     bool has_lights = false;

@@ -7,13 +7,17 @@ inputs are the device's: light parameters and wrapper maps rounded to f32 as the
 A division is a * (1 / b), as the device forms it (v_rcp_f32); in f64 that is a division to the last bit or two.
 
 Draw orders (one SplitMix64 stream per query, seeded with the query's state, as kernels.hip Rng):
-    pick        next64() % n_lights
+    pick        next64() % n_lights; with RT_SCENE_LIGHTS_MANY one rnd() u, the first member k with cdf_k > u (light_weights)
     rect        range(a0, a1), range(b0, b1); the point has k on the rect's axis
     triangle    r1, r2; s = sqrt(r1); (1 - s) v0 + s (1 - r2) v1 + s r2 v2   (pdf: the kernel's tri_hit, closed edges included)
     box         next64() % 6 picks a side in boxes.rs order (z1 z0 y1 y0 x1 x0), then that rect's two draws
     sphere      r1, r2 of random_to_sphere (pdf.rs:82-91)
 A member under Translate / RotateY / FlipFace: the chain is one rigid map (world -> the member's space); the point goes there, the drawn
-direction is rotated back, the pdf is evaluated there."""
+direction is rotated back, the pdf is evaluated there.
+
+RT_SCENE_LIGHTS_MANY: the list's pdf is sum_k p_k pdf_k with the f32 weights of light_weights, summed here in LIST order (the device sums in
+the leaf order of its light tree, light_tree: the same terms, another order of rounding)."""
+import ctypes as C
 import math
 
 import numpy as np
@@ -92,23 +96,63 @@ def lights_of(desc):
             if (p[1] - p[0]) * (p[3] - p[2]) == 0.0:
                 raise ValueError("a rect of zero area")
             kaxis = {A.RT_HIT_XY_RECT: 2.0, A.RT_HIT_XZ_RECT: 1.0, A.RT_HIT_YZ_RECT: 0.0}[h.kind]
-            rec = dict(kind="rect", p=[f32(p[i]) for i in range(5)] + [kaxis])
+            rec = dict(kind="rect", p=[f32(p[i]) for i in range(5)] + [kaxis], area=abs((p[1] - p[0]) * (p[3] - p[2])))
         elif h.kind == A.RT_HIT_TRIANGLE:
             v = np.array([p[i] for i in range(9)]).reshape(3, 3)
             if not np.any(np.cross(v[1] - v[0], v[2] - v[0]) != 0.0):
                 raise ValueError("a triangle of zero area")
-            rec = dict(kind="tri", p=[f32(p[i]) for i in range(9)])
+            rec = dict(kind="tri", p=[f32(p[i]) for i in range(9)], area=0.5 * math.sqrt(float(np.sum(np.cross(v[1] - v[0], v[2] - v[0]) ** 2))))
         elif h.kind == A.RT_HIT_BOX:
             if any(p[3 + a] - p[a] == 0.0 for a in range(3)):
                 raise ValueError("a box with sides of zero area")
-            rec = dict(kind="box", p=[f32(p[0]), f32(p[3]), f32(p[1]), f32(p[4]), f32(p[2]), f32(p[5])])
+            dx, dy, dz = abs(p[3] - p[0]), abs(p[4] - p[1]), abs(p[5] - p[2])
+            rec = dict(kind="box", p=[f32(p[0]), f32(p[3]), f32(p[1]), f32(p[4]), f32(p[2]), f32(p[5])], area=2.0 * (dx * dy + dy * dz + dz * dx))
         elif h.kind == A.RT_HIT_SPHERE:
-            rec = dict(kind="sphere", p=[f32(p[i]) for i in range(4)])
+            rec = dict(kind="sphere", p=[f32(p[i]) for i in range(4)], area=4.0 * math.pi * p[3] * p[3])
         else:
             raise ValueError(f"hittable kind {h.kind} cannot be sampled as a light")
         rec.update(has_xform=not identity, sin=f32(math.sin(theta)), cos=f32(math.cos(theta)), off=[f32(x) for x in off])
         out.append(rec)
     return out
+
+
+def light_weights(desc, dtype=np.float32):
+    """(p, cdf), arrays by member: the area-weighted pick of RT_SCENE_LIGHTS_MANY as include/rt_hip.h states it. Areas from the desc's f64
+    parameters; in f64 and list order total = the sequential sum, p_k = (float)(A_k / total), cdf_k = (float)((A_0 + .. + A_k) / total) with a
+    sequential running sum, cdf_{n-1} = 1.0f exactly. dtype float32: the device's table, to the bit; float64: the same rule without the
+    final rounding, the yardstick's weights."""
+    T = np.dtype(dtype).type
+    areas = [float(l["area"]) for l in lights_of(desc)]
+    total = 0.0
+    for a in areas:
+        total += a
+    if not (total > 0.0 and math.isfinite(total)):
+        raise ValueError("the lights' total area is not a positive finite number")
+    p, cdf, run = np.empty(len(areas), T), np.empty(len(areas), T), 0.0
+    for k, a in enumerate(areas):
+        run += a
+        p[k], cdf[k] = T(a / total), T(run / total)
+    cdf[-1] = T(1.0)
+    return p, cdf
+
+
+LIGHT_NODE_DTYPE = np.dtype([("cx", np.float32), ("cy", np.float32), ("hx", np.float32), ("hy", np.float32), ("cz", np.float32), ("hz", np.float32),
+                             ("skip", np.uint32), ("leaf", np.uint32)])
+
+
+def light_tree(desc):
+    """rt_scene_light_tree_dump: dict(nodes (LIGHT_NODE_DTYPE, 2n - 1 records in pre-order: box = centre -+ half extent, skip = index of the first
+    record after the subtree, leaf = 0 or 1 + slot), slot_member (uint32, n: the member in table slot s), p, cdf (float32, n, by member)) of a
+    scene with RT_SCENE_LIGHTS_MANY. Host only."""
+    from .api import _check, lib
+    n, m = C.c_uint64(), C.c_uint64()
+    _check(lib().rt_scene_light_tree_dump(C.byref(desc), None, 0, None, None, None, 0, C.byref(n), C.byref(m)))
+    nodes = np.zeros(m.value, dtype=LIGHT_NODE_DTYPE)
+    slot_member, p, cdf = np.zeros(n.value, np.uint32), np.zeros(n.value, np.float32), np.zeros(n.value, np.float32)
+    fp = C.POINTER(C.c_float)
+    _check(lib().rt_scene_light_tree_dump(C.byref(desc), nodes.ctypes.data_as(C.c_void_p), len(nodes), slot_member.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                          p.ctypes.data_as(fp), cdf.ctypes.data_as(fp), n.value, C.byref(n), C.byref(m)))
+    return dict(nodes=nodes, slot_member=slot_member, p=p, cdf=cdf)
 
 
 def _box_side(p, s):
@@ -323,22 +367,32 @@ def light_reference(desc, points, states=None, dirs=None, dtype=np.float64):
     (np.float64 or np.float32). points, dirs: (n, 3), read as f32; states: n uint64.
 
     Returns dict(d (n, 3), pdf (n), light (n, int32), n_draws (n, uint32)) plus what decides whether a query can be held to the yardstick at
-    all: cos_min (the smallest |cos| at which the ray meets a light), edge_min (the smallest distance of a crossing from a rect's edge, in
+    all: pick_gap (RT_SCENE_LIGHTS_MANY: the distance of the pick's draw from the nearest inner cdf edge; else inf), cos_min (the smallest |cos|
+    at which the ray meets a light), edge_min (the smallest distance of a crossing from a rect's edge, in
     scene units, or from a triangle's edge, in barycentrics — near misses count) and tmin_gap (distance of the nearest crossing from t_min)."""
     T = np.dtype(dtype).type
     M = _Ops(T)
     lights = lights_of(desc)
     if not lights:
         raise ValueError("the scene has no lights list")
+    many = bool(desc.scene_flags & A.RT_SCENE_LIGHTS_MANY)
+    if many:
+        p_k, cdf = light_weights(desc, T)
     pts = np.asarray(points, dtype=np.float32).reshape(-1, 3)
     n = pts.shape[0]
     o = [pts[:, i].astype(T) for i in range(3)]
     light = np.full(n, -1, dtype=np.int32)
     n_draws = np.zeros(n, dtype=np.uint32)
+    pick_gap = np.full(n, np.inf)
     if dirs is None:
         g = _Rng(np.asarray(states, dtype=np.uint64).reshape(-1), T)
         every = np.ones(n, dtype=bool)
-        light = (g.next64(every) % np.uint64(len(lights))).astype(np.int32)
+        if many:                                            # one rnd(): 24 bits, exact in either dtype; the first member whose cdf (in T) exceeds it
+            u = g.rnd(every).astype(np.float64)
+            light = np.searchsorted(cdf.astype(np.float64), u, side="right").astype(np.int32)
+            pick_gap = np.abs(u[:, None] - cdf.astype(np.float64)[None, :-1]).min(axis=1) if len(lights) > 1 else pick_gap
+        else:
+            light = (g.next64(every) % np.uint64(len(lights))).astype(np.int32)
         d = [np.zeros(n, dtype=T) for _ in range(3)]
         for k, l in enumerate(lights):
             live = light == k
@@ -354,9 +408,9 @@ def light_reference(desc, points, states=None, dirs=None, dtype=np.float64):
     diag = dict(cos=np.full(n, np.inf), edge=np.full(n, np.inf), tmin=np.full(n, np.inf))
     weight = T(T(1.0) / T(len(lights)))
     lsum = np.zeros(n, dtype=T)
-    for l in lights:
-        lsum = lsum + weight * _light_pdf(M, l, o, d, diag)
-    return dict(d=np.stack(d, axis=1), pdf=lsum, light=light, n_draws=n_draws, cos_min=diag["cos"], edge_min=diag["edge"], tmin_gap=diag["tmin"])
+    for k, l in enumerate(lights):
+        lsum = lsum + (T(p_k[k]) if many else weight) * _light_pdf(M, l, o, d, diag)
+    return dict(d=np.stack(d, axis=1), pdf=lsum, light=light, n_draws=n_draws, pick_gap=pick_gap, cos_min=diag["cos"], edge_min=diag["edge"], tmin_gap=diag["tmin"])
 
 
 def solid_angle_triangle(p, a, b, c):

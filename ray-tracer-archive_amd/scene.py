@@ -148,16 +148,18 @@ class SceneBuilder:
         return self._hit(A.RT_HIT_CONSTANT_MEDIUM, self.isotropic(color), boundary, 1, [density])
 
     # ---- finish ----
-    def desc(self, world, lights=-1, lights_all_shapes=False):
+    def desc(self, world, lights=-1, lights_all_shapes=False, lights_many=False):
         """lights_all_shapes: RT_SCENE_LIGHTS_ALL_SHAPES — every member of the lights list (rects of any orientation, triangles, boxes,
-        spheres, each under Translate / RotateY / FlipFace) is sampled as a light; False: the reference's XzRect and Sphere only."""
+        spheres, each under Translate / RotateY / FlipFace) is sampled as a light; False: the reference's XzRect and Sphere only.
+        lights_many: RT_SCENE_LIGHTS_MANY — the pick weighs the members by area and the list's pdf is evaluated through a light tree
+        (for emissive meshes); the library refuses it without lights_all_shapes."""
         def arr(T, items):
             return (T * max(1, len(items)))(*items)
         keep = dict(h=arr(A.RtHittable, self.hittables), c=arr(C.c_int32, self.children), m=arr(A.RtMaterial, self.materials),
                     t=arr(A.RtTexture, self.textures), p=arr(A.RtPerlin, self.perlins), i=arr(A.RtImage, self.images))
         d = A.RtSceneDesc()
         d.abi_version = A.RT_ABI_VERSION
-        d.scene_flags = A.RT_SCENE_LIGHTS_ALL_SHAPES if lights_all_shapes else 0
+        d.scene_flags = (A.RT_SCENE_LIGHTS_ALL_SHAPES if lights_all_shapes else 0) | (A.RT_SCENE_LIGHTS_MANY if lights_many else 0)
         d.hittables, d.n_hittables = keep["h"], len(self.hittables)
         d.children, d.n_children = keep["c"], len(self.children)
         d.materials, d.n_materials = keep["m"], len(self.materials)

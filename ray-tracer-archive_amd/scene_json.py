@@ -22,6 +22,7 @@ SceneBuilder calls — nothing here touches the device.
                     "mesh":  {"obj": "bunny.obj", "material": "steel", "scale": 1.0, "offset": [0, 0, 0], "smooth": true, "textured": false}},
       "world":  {"list": ["floor", "tall", "fog"]},  # or {"bvh": [...]} = BVHNode::construct2 over the members
       "lights": ["lamp_rect", "ball"],              # optional: XzRect / Sphere objects (main.rs:669-686)
+      "lights_many": false,                         # true (with lights_all_shapes): RT_SCENE_LIGHTS_MANY — area-weighted pick, light tree
       "lights_all_shapes": false,                   # true: RT_SCENE_LIGHTS_ALL_SHAPES — rects of any orientation, triangles, boxes, wrapped members
       "bvh": {"seed": 1, "builder": "reference"}    # or "sah"
     }
@@ -149,7 +150,10 @@ class JsonScene:
         las = doc.get("lights_all_shapes", False)
         if not isinstance(las, bool):
             raise ValueError(f"lights_all_shapes: expected true or false, got {las!r}")
-        self.desc = self.b.desc(world, lights, lights_all_shapes=las)
+        lm = doc.get("lights_many", False)
+        if not isinstance(lm, bool):
+            raise ValueError(f"lights_many: expected true or false, got {lm!r}")
+        self.desc = self.b.desc(world, lights, lights_all_shapes=las, lights_many=lm)
         self.triangle_attrs = self.b.triangle_attrs()
 
     # ---- textures / materials ----
