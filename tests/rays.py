@@ -1,15 +1,17 @@
 """Ray sets for the ray-query tests (tests/test_rays_host.py, tests/test_gpu_rays.py, tests/test_gpu_occlusion.py): six small scenes that
 fit LDS, and per scene a fixed list of f32 rays — pixel-centre camera rays plus one generation of secondary rays from the CPU checker's
 hit points in seeded random directions — with the checker's f64 answer for every ray, which rays are DECIDABLE, and which object every
-hit lies on. And one scene that does not fit LDS (`field`, with `field_sah`: tests/test_gpu_rays_hbm.py), its set made the same way, the
-uploads it is walked through (field_matrix) and the checker's own f32 figures that bound the device there (MEASURED_F32_CHECKER).
+hit lies on. And two scenes that do not fit LDS (tests/test_gpu_rays_hbm.py) — `field`, a static BVH, and `yard`, a BVH over a time
+range with instances and moving spheres, each with a `_sah` twin — their sets made the same way, the uploads they are walked through
+(field_matrix) and the checker's own f32 figures that bound the device there (MEASURED_F32_CHECKER).
 And two families of rays those sets never hold (further down): axis_set — directions with zero, signed-zero, subnormal or 1e-30
 components from origins on the 1/4 lattice, with the rim and edge subsets — and segment_set — point-to-point rays d = q - p with a
 t_max of their own near 1.
 
 A ray is undecidable when the checker's answer changes under a perturbation of its direction by +-R f32 ulps per component (8 fixed sign
 patterns): hit <-> miss, t moving by more than 1e-3 * max(1, t), or front_face flipping. Such a ray grazes a silhouette or an edge; an f32
-traversal may land on either side of it, and the tests leave it out (and say how many there were)."""
+traversal may land on either side of it, and the tests leave it out (and say how many there were). Where an instance frame lies far
+from the world's (`yard`, instance C) the origin is perturbed too: O_ULPS, origin_undecidable."""
 import ctypes as C
 import os
 
@@ -28,8 +30,16 @@ SIGNS = [(1, 1, 1), (1, 1, -1), (1, -1, 1), (1, -1, -1), (-1, 1, 1), (-1, 1, -1)
 SCENES = ["book1", "cornell", "mesh", "moving", "rotated_sphere", "earth"]
 STATIC_SCENES = ["book1", "cornell", "mesh", "rotated_sphere", "earth"]
 # the ray set of scenes that do not fit LDS (tests/test_gpu_rays_hbm.py): one geometry, the reference's BVH builder and the SAH one
-HBM_SCENES = ["field", "field_sah"]
+HBM_SCENES = ["field", "field_sah", "yard", "yard_sah"]
+HBM_OF = {"field": ["field", "field_sah"], "yard": ["yard", "yard_sah"]}
+HBM_GEOMETRY = {"field": "field", "field_sah": "field", "yard": "yard", "yard_sah": "yard"}   # the sets depend on the geometry alone
 FIELD_SPHERES, FIELD_GRID, FIELD_SEED, FIELD_BOX_RAYS = 1250, 23, 20250317, 64
+# `yard` (yard_scene): what stands alone in a cell of the unit lattice, the frame instance C is built in, and the xz footprints
+# (x0, x1, z0, z1) the lattice keeps free for the instances A, B, C, D
+YARD_SEED, YARD_FAR = 20261020, 400.0
+YARD_SPHERES, YARD_MOVING, YARD_BOXES, YARD_RECTS = 450, 450, 80, 60
+YARD_BLOCKS = {"A": (-7.5, -0.5, -7.5, -0.5), "B": (0.4, 7.6, 0.4, 7.6), "C": (-10.6, -5.4, -0.6, 4.6), "D": (2.4, 9.6, -9.6, -2.4)}
+YARD_D = ((90.0, (4.2, -6.0)), (180.0, (7.8, -6.0)))      # D's two groups: the angle of the RotateY above each, and where it stands in the world (x, z)
 GRID = (48, 32)         # camera rays per scene: pixel centres of a 48 x 32 frame (+ as many secondary rays as they have hits)
 
 
@@ -79,14 +89,20 @@ def field_scene(pkg, builder):
     return Built(desc, cam, b, 14.0)
 
 
-def field_matrix(A):
-    """The uploads of tests/test_gpu_rays_hbm.py: case -> (scene, layout flags, the other RtUploadOptions fields). None of them fits LDS
-    (tests/test_rays_host.py::test_field_does_not_fit_lds), but `collapse_4`: leaf_collapse = 4 folds the tree to ~1,600 records, which do;
-    `collapse_4_hbm` is the same upload kept out of LDS by flag."""
+# a top of `yard` that holds the LT_XFORM records of the instances A, B and C and not their subtrees (the reference's builder makes a
+# balanced tree over 1,043 members: the instances sit 11 levels down, below every smaller top): tests/test_rays_host.py::test_yard_top_layouts
+YARD_TOP = 3000
+
+
+def field_matrix(A, scene="field"):
+    """The uploads of tests/test_gpu_rays_hbm.py for `field` or `yard`: case -> (scene, layout flags, the other RtUploadOptions fields).
+    None of them fits LDS (tests/test_rays_host.py::test_field_does_not_fit_lds), but `collapse_4`: leaf_collapse = 4 folds the tree to
+    ~1,600 records (yard: ~1,900), which do; `collapse_4_hbm` is the same upload kept out of LDS by flag. On `yard`, which is no static
+    BVH, the `wide` cases keep the binary walk."""
     m = {"c16": (0, {}), "c16_one_order": (A.RT_LAYOUT_CHILD_ORDER_AS_REFERENCE, {})}
     for k in range(1, 8):
         m[f"c16_axes_{k}"] = (0, dict(octant_axes=k))
-    for k in (1, 2, 3, 7, 100, 0, 4096):
+    for k in (1, 2, 3, 7, 100, 0, 4096) + ((YARD_TOP,) if scene == "yard" else ()):
         m[f"top_{k or 1024}"] = (A.RT_LAYOUT_NODES_32B, dict(lds_top_records=k))
     m["top_one_order"] = (A.RT_LAYOUT_NODES_32B | A.RT_LAYOUT_CHILD_ORDER_AS_REFERENCE, dict(lds_top_records=7))
     m["member_boxes"] = (A.RT_LAYOUT_MEMBER_BOXES, {})
@@ -96,9 +112,9 @@ def field_matrix(A):
     m["wide"] = (A.RT_LAYOUT_WIDE_NODES, {})
     m["collapse_4"] = (0, dict(leaf_collapse=4))
     m["collapse_4_hbm"] = (A.RT_LAYOUT_SCENE_IN_HBM, dict(leaf_collapse=4))
-    out = {k: ("field",) + v for k, v in m.items()}
+    out = {k: (scene,) + v for k, v in m.items()}
     for k in ("c16", "top_1024", "wide"):
-        out[k + "_sah"] = ("field_sah",) + m[k]
+        out[k + "_sah"] = (scene + "_sah",) + m[k]
     return out
 
 
@@ -109,21 +125,40 @@ def top_rule(skip, max_top):
     """Records of the top of the tree a NODES_32B upload keeps in LDS (RtStats.lds_top_nodes), restated from the skip links of the
     compiled records: depth = the number of enclosing subtrees [i, skip_i); the top is every record above the deepest cut that holds at
     most max_top records — or nothing, when the first level alone exceeds max_top or the whole tree fits."""
-    n, ends, per_depth = len(skip), [], []
+    return int(top_mask(skip, max_top).sum())
+
+
+def top_mask(skip, max_top):
+    """top_rule's records themselves: a mask over the compiled records."""
+    n, ends, depth = len(skip), [], np.zeros(len(skip), np.int64)
     for i in range(n):
         while ends and ends[-1] <= i:
             ends.pop()
-        if len(ends) == len(per_depth):
-            per_depth.append(0)
-        per_depth[len(ends)] += 1
+        depth[i] = len(ends)
         if skip[i] > i + 1:
             ends.append(int(skip[i]))
-    total = 0
+    per_depth = np.bincount(depth)
+    total = cut = 0
     for count in per_depth:
         if total + count > max_top:
             break
         total += count
-    return total if 0 < total < n else 0
+        cut += 1
+    return depth < cut if 0 < total < n else np.zeros(n, bool)
+
+
+def xform_pairs(leaf):
+    """[(enter, exit)] record indices of every LT_XFORM pair of a compiled record array (csrc/device_types.h: leaf type 6, bit 23 set on
+    the record that closes a wrapper), innermost pairs first as they close."""
+    kind, is_exit = np.asarray(leaf) >> 28, (np.asarray(leaf) & (1 << 23)) != 0
+    open_, pairs = [], []
+    for i in np.flatnonzero(kind == 6):
+        if is_exit[i]:
+            pairs.append((open_.pop(), int(i)))
+        else:
+            open_.append(int(i))
+    assert not open_
+    return pairs
 
 
 def field_box_rays(rng):
@@ -135,10 +170,189 @@ def field_box_rays(rng):
     return make_rays(o, to - o, np.zeros(FIELD_BOX_RAYS))
 
 
+def rot_y(deg, x, z, inverse=False):
+    """RotateY's map of a point (hittable.rs:152-157: child -> parent), or its inverse (parent -> child)."""
+    th = np.radians(deg); c, s = np.cos(th), np.sin(th)
+    return (c * x - s * z, s * x + c * z) if inverse else (c * x + s * z, -s * x + c * z)
+
+
+def yard_scene(pkg, builder):
+    """A BVH over a time range that does not fit LDS, with instances and moving spheres (tests/test_gpu_rays_hbm.py): spheres, moving
+    spheres, Translate(RotateY(Box)) with an angle each, and rects of all three axes (every second one under FlipFace), each alone
+    in a cell of the unit lattice over [-12, 12) x [0, 4) x [-12, 12); and in the footprints the lattice keeps free (YARD_BLOCKS):
+    A  Translate(RotateY(BVH(500 spheres on a 0.5 lattice), 30), (-4, 0, -4)), the shape of main.rs:640-646;
+    B  RotateY(Translate(RotateY(BVH(12 x 12 x 2 triangles), 20), T), 25) with T such that it stands at (4, 0, 4): a chain of three;
+    C  Translate(BVH(50 spheres + 50 moving spheres around (far, 0, far), 0, 1), (-8 - far, 0, 2 - far)), far = YARD_FAR: an instance
+       whose own coordinates lie hundreds of units from where it stands (they stretch the compressed records' grid over the whole
+       scene), with moving spheres inside;
+    D  two groups of spheres, moving spheres, rects and a Box, under RotateY(90) and RotateY(180): the f32 sine / cosine of those is
+       ~6e-17, not 0, so a world axis ray becomes a local ray with a component of that size made by the library itself.
+    The ground rect lies beside the BVH in a HittableList. No two surfaces meet: every object keeps 0.05 from its cell's faces, and the
+    instances from each other's footprints. Built.parts maps "A", "B", "C", "D" to the hittable ids of their primitives."""
+    rng = np.random.default_rng(YARD_SEED)
+    b = pkg.SceneBuilder(background=(0.5, 0.7, 1.0), background_mode=pkg._abi.RT_BG_SKY_GRADIENT, bvh_builder=builder)
+    mats = [b.lambertian((0.7, 0.3, 0.3)), b.metal((0.8, 0.8, 0.8), 0.1), b.dielectric(1.5), b.lambertian((0.3, 0.4, 0.8)), b.metal((0.9, 0.6, 0.2), 0.3)]
+    mat = lambda: mats[int(rng.integers(0, len(mats)))]
+    u = rng.uniform
+
+    def moving(cc, r):                                        # centres moving at most 0.2 per axis over times 0 .. 1, about cc
+        delta = u(-0.2, 0.2, 3)
+        return b.moving_sphere(cc - delta / 2, cc + delta / 2, 0.0, 1.0, r, mat())
+
+    def rect(axis, cc, half, flip):
+        lo, hi = cc - half, cc + half
+        h = (b.xy_rect(lo[0], hi[0], lo[1], hi[1], cc[2], mat()) if axis == 0 else
+             b.yz_rect(lo[1], hi[1], lo[2], hi[2], cc[0], mat()) if axis == 1 else b.xz_rect(lo[0], hi[0], lo[2], hi[2], cc[1], mat()))
+        return b.flip_face(h) if flip else h
+
+    free = lambda i, k: not any(i + 1 > x0 and i < x1 and k + 1 > z0 and k < z1 for x0, x1, z0, z1 in YARD_BLOCKS.values())
+    cells = np.array([(i, j, k) for i in range(-12, 12) for k in range(-12, 12) if free(i, k) for j in range(4)], np.float64)
+    cells = cells[rng.permutation(len(cells))][:YARD_SPHERES + YARD_MOVING + YARD_BOXES + YARD_RECTS] + 0.5
+    ids = []
+    for n, cc in enumerate(cells):
+        if n < YARD_SPHERES:
+            r = u(0.2, 0.3)
+            ids.append(b.sphere(cc + u(-0.15, 0.15, 3), r, mat()))
+        elif n < YARD_SPHERES + YARD_MOVING:
+            ids.append(moving(cc + u(-0.05, 0.05, 3), u(0.15, 0.25)))
+        elif n < YARD_SPHERES + YARD_MOVING + YARD_BOXES:
+            h = u(0.15, 0.25, 3)
+            ids.append(b.translate(b.rotate_y(b.box(-h, h, mat()), u(-180.0, 180.0)), cc + u(-0.05, 0.05, 3)))
+        else:
+            k = n - (YARD_SPHERES + YARD_MOVING + YARD_BOXES)
+            ids.append(rect(k % 3, cc + u(-0.05, 0.05, 3), 0.35, (k // 3) & 1 == 1))        # the three axes take turns, plain and flipped
+    parts, first = {}, 0
+
+    def part(name):
+        nonlocal first
+        parts[name] = np.array([i for i in range(first, len(b.hittables)) if b.hittables[i].material >= 0])
+        first = len(b.hittables)
+    part("bare")
+    # A
+    sub = [b.sphere((-2.25 + 0.5 * i + u(-0.03, 0.03), 0.25 + 0.5 * j + u(-0.03, 0.03), -2.25 + 0.5 * k + u(-0.03, 0.03)), u(0.1, 0.2), mat())
+           for i in range(10) for j in range(5) for k in range(10)]
+    ids.append(b.translate(b.rotate_y(b.bvh(sub), 30.0), (-4.0, 0.0, -4.0)))
+    part("A")
+    # B
+    n = 12
+    h = rng.uniform(0.3, 1.2, (n + 1, n + 1))
+    P = lambda i, j: (-2.5 + 5.0 * i / n, float(h[i, j]), -2.5 + 5.0 * j / n)
+    sub = []
+    for i in range(n):
+        for j in range(n):
+            sub.append(b.triangle(P(i, j), P(i + 1, j), P(i, j + 1), mats[(i + j) & 1]))
+            sub.append(b.triangle(P(i + 1, j), P(i + 1, j + 1), P(i, j + 1), mats[3 + ((i + j) & 1)]))
+    tx, tz = rot_y(25.0, 4.0, 4.0, inverse=True)
+    ids.append(b.rotate_y(b.translate(b.rotate_y(b.bvh(sub), 20.0), (tx, 0.0, tz)), 25.0))
+    part("B")
+    # C
+    far, sub = YARD_FAR, []
+    for i in range(5):
+        for j in range(4):
+            for k in range(5):
+                cc = np.array([far - 2.0 + i, 0.5 + j, far - 2.0 + k]) + u(-0.1, 0.1, 3)
+                sub.append(moving(cc, u(0.15, 0.25)) if (i + j + k) & 1 else b.sphere(cc, u(0.2, 0.3), mat()))
+    ids.append(b.translate(b.bvh(sub, 0.0, 1.0), (-8.0 - far, 0.0, 2.0 - far)))
+    part("C")
+    # D: twelve objects per group at world offsets (x, z) in {-1, 0, 1} x {-2.5 .. 2.5} about where the group stands, built in the group's own frame
+    for deg, (wx, wz) in YARD_D:
+        spots = [(ox, oy, oz) for ox in (-1.0, 0.0, 1.0) for oz in (-2.5, -1.5, -0.5, 0.5, 1.5, 2.5) for oy in (0.5, 1.5, 2.5)]
+        sub = []
+        for n, s in enumerate([spots[i] for i in rng.permutation(len(spots))[:12]]):
+            lx, lz = rot_y(round(deg), wx + s[0], wz + s[2], inverse=True)
+            cc = np.array([np.round(lx, 6), s[1], np.round(lz, 6)]) + u(-0.05, 0.05, 3)
+            if n < 6:
+                sub.append(b.sphere(cc, u(0.2, 0.3), mat()))
+            elif n < 8:
+                sub.append(moving(cc, u(0.15, 0.25)))
+            elif n < 11:
+                sub.append(rect(n % 3, cc, 0.35, n == 9))
+            else:
+                e = u(0.15, 0.3, 3)
+                sub.append(b.box(cc - e, cc + e, mat()))
+        ids.append(b.rotate_y(b.bvh(sub, 0.0, 1.0), deg))
+    part("D")
+    ground = b.xz_rect(-14, 14, -14, 14, -0.25, b.lambertian((0.5, 0.5, 0.5)))
+    desc = b.desc(b.hittable_list([b.bvh(ids, 0.0, 1.0), ground]))
+    cam = pkg.camera_new((14.0, 6.0, 16.0), (0.0, 1.0, 0.0), (0, 1, 0), 40.0, 1.5, 0.0, 10.0, 0.0, 1.0)
+    built = Built(desc, cam, b, 14.0)
+    built.parts = parts
+    return built
+
+
+def moving_centre(h, tm):
+    a = list(h.p)
+    return np.array(a[0:3]) + (tm - a[6]) / (a[7] - a[6]) * (np.array(a[3:6]) - np.array(a[0:3]))
+
+
+def yard_aimed_rays(pkg, built, rng):
+    """Primary rays at what the camera of yard_scene sees too little of, in the manner of field_box_rays: two at every xy and yz rect of
+    the lattice, plain and flipped, one from each side out of the rect's own cell; 48 each at A, B and D and 96 at C from seeded points above the
+    instance towards one of its objects; and 64 at bare moving spheres out of the sphere's own
+    cell, at times within 0.02 of 0 and of 1. They get their secondary rays like every other primary ray."""
+    A = pkg._abi
+    H, u = built.desc.hittables, rng.uniform
+    chains = {i: (h, chain) for i, h, chain in primitives(pkg, built.desc)}
+    o, to, tm = [], [], []
+
+    def add(a, b_, t):
+        o.append(a); to.append(b_); tm.append(t)
+
+    def to_world(chain, q):                                   # child -> parent, innermost wrapper first
+        q = np.array(q, np.float64)
+        for kind, prm in reversed(chain):
+            if kind == A.RT_HIT_ROTATE_Y:
+                q[0], q[2] = rot_y(prm[0], q[0], q[2])
+            elif kind == A.RT_HIT_TRANSLATE:
+                q = q + np.array(prm[:3])
+        return q
+
+    def centre(i, t):
+        h, chain = chains[int(i)]
+        a = list(h.p)
+        if h.kind == A.RT_HIT_SPHERE:
+            c = np.array(a[:3])
+        elif h.kind == A.RT_HIT_MOVING_SPHERE:
+            c = moving_centre(h, t)
+        elif h.kind == A.RT_HIT_BOX:
+            c = (np.array(a[0:3]) + np.array(a[3:6])) / 2
+        elif h.kind == A.RT_HIT_TRIANGLE:
+            c = (np.array(a[0:3]) + np.array(a[3:6]) + np.array(a[6:9])) / 3
+        else:
+            axes = {A.RT_HIT_XY_RECT: (0, 1, 2), A.RT_HIT_XZ_RECT: (0, 2, 1), A.RT_HIT_YZ_RECT: (1, 2, 0)}[h.kind]
+            c = np.zeros(3)
+            c[axes[0]], c[axes[1]], c[axes[2]] = (a[0] + a[1]) / 2, (a[2] + a[3]) / 2, a[4]
+        return to_world(chain, c)
+    for i in built.parts["bare"]:
+        k = H[int(i)].kind
+        if k in (A.RT_HIT_XY_RECT, A.RT_HIT_YZ_RECT):
+            normal = 2 if k == A.RT_HIT_XY_RECT else 0
+            for side in (-1.0, 1.0):
+                c = centre(i, 0.0)
+                a, t = c + u(-0.2, 0.2, 3), c + u(-0.25, 0.25, 3)
+                a[normal], t[normal] = c[normal] + side * u(0.3, 0.4), c[normal]
+                add(a, t, u(0.0, 1.0))
+    for name, count in (("A", 48), ("B", 48), ("C", 96), ("D", 48)):
+        ids = built.parts[name]
+        for n in range(count):
+            t = u(0.0, 1.0)
+            c = centre(ids[rng.integers(0, len(ids))], t)
+            add(np.array([c[0] + u(-3.0, 3.0), u(4.5, 7.0), c[2] + u(-3.0, 3.0)]), c + u(-0.1, 0.1, 3), t)
+    bare_moving = [i for i in built.parts["bare"] if H[int(i)].kind == A.RT_HIT_MOVING_SPHERE]
+    for n, i in enumerate(rng.choice(bare_moving, 64, replace=False)):
+        t = u(0.0, 0.02) if n & 1 else u(0.98, 1.0)
+        c = centre(i, t)
+        d = rng.normal(size=3); d *= 0.42 / np.linalg.norm(d)
+        add(np.floor(c) + 0.5 + d, c + u(-0.05, 0.05, 3), t)
+    o, to = np.array(o), np.array(to)
+    return make_rays(o, to - o, np.array(tm))
+
+
 def build_scene(pkg, name):
     A = pkg._abi
     if name in HBM_SCENES:
-        return field_scene(pkg, A.RT_BVH_SAH if name == "field_sah" else A.RT_BVH_REFERENCE)
+        builder = A.RT_BVH_SAH if name.endswith("_sah") else A.RT_BVH_REFERENCE
+        return yard_scene(pkg, builder) if HBM_GEOMETRY[name] == "yard" else field_scene(pkg, builder)
     if name == "book1":
         hs = pkg.HostScene("book1", 1)
         # (the book's camera looks at the origin, which is the north pole of the r = 1000 ground sphere: u is ill-conditioned within 3 units
@@ -282,6 +496,70 @@ def undecidable(orc, desc, rays, ref, r_ulps=R_ULPS, small=SMALL):
     return bad
 
 
+def to_local(pkg, chain, q):
+    """The world points q (n, 3) in the frame below the wrappers `chain` (outermost first), in f64."""
+    A = pkg._abi
+    for kind, prm in chain:
+        if kind == A.RT_HIT_TRANSLATE:
+            q = q - np.array(prm[:3])
+        elif kind == A.RT_HIT_ROTATE_Y:
+            th = np.radians(prm[0]); c, s = np.cos(th), np.sin(th)
+            q = np.stack([c * q[:, 0] - s * q[:, 2], q[:, 1], s * q[:, 0] + c * q[:, 2]], axis=1)
+    return q
+
+
+# O: 3 ulps of the coarsest frame, from the device's own arithmetic as R is. Below a Translate / RotateY the device tests a primitive
+# against o_l = fl(o - offset) (csrc/kernels.hip xform_ray) and a centre it keeps in f32 (a moving sphere's: interpolated in f32): three
+# roundings of half an ulp of the FRAME's coordinates in o_l - c, per axis. Where the frame's coordinates are no larger than the
+# world's that is the rounding the ray's origin took when the set was made, and nothing new; in instance C of `yard`, 400 units out,
+# it is 4.6e-5 units on a ray whose origin has an ulp of 5e-7 — a secondary ray that leaves a sphere of C at 89 degrees from the
+# normal starts up to that far inside it and finds the sphere again at t = 4.6e-5 / cos = 2.6e-3 > t_min, which no perturbation of d
+# produces (the f32 checker does, and so does the device: 1 decidable ray of the set by the rule on d alone). O = 3 is a factor of
+# two, as R keeps.
+O_ULPS = 3
+
+
+def origin_undecidable(pkg, orc, desc, rays, ref, o_ulps=O_ULPS):
+    """The rule of the module's docstring for the ORIGIN, where an instance frame makes it coarser: per ray, the frames (wrapper chains
+    with a Translate or a RotateY) in which the origin's largest coordinate has a larger f32 ulp than in the world; the origin is moved
+    by +-O of the largest such ulp per component (the 8 sign patterns), and a changed answer counts where the primitive hit, before or
+    after, lies in one of those frames — the error enters in the tests of that frame's primitives and nowhere else. A scene without
+    such a frame keeps its mask."""
+    A = pkg._abi
+    prims = primitives(pkg, desc)
+    key = lambda chain: tuple((k, tuple(p[:3])) for k, p in chain if k != A.RT_HIT_FLIP_FACE)
+    frames = {}
+    for col, (_, _, chain) in enumerate(prims):
+        if key(chain):
+            frames.setdefault(key(chain), (chain, []))[1].append(col)
+    bad = np.zeros(len(rays), bool)
+    if not frames:
+        return bad
+    o = rays["o"].astype(np.float64)
+    own = np.spacing(np.abs(rays["o"]).max(axis=1))
+    step, coarse = np.zeros(len(rays), np.float32), np.zeros((len(rays), len(prims)), bool)      # coarse[i, k]: primitive k lies in a coarser frame of ray i
+    for chain, cols in frames.values():
+        ulp = np.spacing(np.abs(to_local(pkg, chain, o)).max(axis=1).astype(np.float32))
+        coarse[:, cols] = (ulp > own)[:, None]
+        step = np.where(ulp > own, np.maximum(step, ulp), step)
+    touched = np.flatnonzero(step > 0)
+    if not len(touched):
+        return bad
+    sub = rays[touched]
+    sub_ref = {k: v[touched] for k, v in ref.items()}
+    tm = sub["time"].astype(np.float64)
+    on_ref = objects_at(pkg, desc, sub_ref["p"], tm, 0.0)[1] & sub_ref["hit"][:, None]
+    for s in SIGNS:
+        q = sub.copy()
+        q["o"] = sub["o"] + np.asarray(s, np.float32) * (np.float32(o_ulps) * step[touched])[:, None]
+        a = ask(orc, desc, q)
+        k = np.flatnonzero(changed(a, sub_ref))
+        if len(k):
+            on_new = objects_at(pkg, desc, a["p"][k], tm[k], 0.0)[1] & a["hit"][k][:, None]
+            bad[touched[k]] |= ((on_ref[k] | on_new) & coarse[touched[k]]).any(axis=1)
+    return bad
+
+
 # ---- which object a hit point lies on: a walk of the description in f64 -----------------------------------------------------------------
 def primitives(pkg, desc):
     """[(hittable id, record, wrapper chain outermost first)] of every primitive reachable from desc.world."""
@@ -304,13 +582,7 @@ def primitives(pkg, desc):
 def surface_distance(pkg, h, chain, p, tm):
     """Distance of the world points p (n, 3) from the surface of primitive h under its wrappers, at the times tm."""
     A = pkg._abi
-    q = p.copy()
-    for kind, prm in chain:                                   # world -> local, outermost wrapper first
-        if kind == A.RT_HIT_TRANSLATE:
-            q = q - np.array(prm[:3])
-        elif kind == A.RT_HIT_ROTATE_Y:
-            th = np.radians(prm[0]); c, s = np.cos(th), np.sin(th)
-            q = np.stack([c * q[:, 0] - s * q[:, 2], q[:, 1], s * q[:, 0] + c * q[:, 2]], axis=1)
+    q = to_local(pkg, chain, p)                               # world -> local, outermost wrapper first
     a = list(h.p)
     if h.kind == A.RT_HIT_SPHERE:
         return np.abs(np.linalg.norm(q - np.array(a[:3]), axis=1) - abs(a[3]))
@@ -351,6 +623,23 @@ def objects_at(pkg, desc, p, tm, extent):
     return np.array([i for i, _, _ in prims]), dist <= 1e-7 * max(1.0, extent)
 
 
+def yard_hit_classes(pkg, s):
+    """{class: mask over the rays of a set of `yard`}: the checker's hit point lies on a primitive of that class — by kind, by the
+    instance that holds it (Built.parts), and `flipped`: a rect of the lattice under FlipFace."""
+    A = pkg._abi
+    built, ids, on = s["built"], s["ids"], s["on"]
+    kind = np.array([built.desc.hittables[int(i)].kind for i in ids])
+    flipped = np.array([any(k == A.RT_HIT_FLIP_FACE for k, _ in chain) for _, _, chain in primitives(pkg, built.desc)])
+    part = {name: np.isin(ids, members) for name, members in built.parts.items()}
+    cols = {"bare spheres": part["bare"] & (kind == A.RT_HIT_SPHERE), "bare moving spheres": part["bare"] & (kind == A.RT_HIT_MOVING_SPHERE),
+            "wrapped Boxes": part["bare"] & (kind == A.RT_HIT_BOX), "xy rects": part["bare"] & (kind == A.RT_HIT_XY_RECT),
+            "yz rects": part["bare"] & (kind == A.RT_HIT_YZ_RECT), "flipped rects": part["bare"] & flipped,
+            "spheres in A": part["A"] & (kind == A.RT_HIT_SPHERE), "triangles in B": part["B"] & (kind == A.RT_HIT_TRIANGLE),
+            "spheres in C": part["C"] & (kind == A.RT_HIT_SPHERE), "moving spheres in C": part["C"] & (kind == A.RT_HIT_MOVING_SPHERE),
+            "primitives in D": part["D"]}
+    return {name: s["ref"]["hit"] & on[:, c].any(axis=1) for name, c in cols.items()}
+
+
 def deviations(pkg, s, k, t, p, n, u, v):
     """Worst deviation from the set's f64 answers on the rays k, in the definitions of tests/test_gpu_rays.py: dict(t = relative |dt|,
     p = |dp| / extent, n = |dn|, uv = |d(u, v)| with u modulo 1 and sphere hits within 1e-3 of a pole left out, ta = |dt| / max(1, t), tabs = |dt|)
@@ -374,6 +663,7 @@ def deviations(pkg, s, k, t, p, n, u, v):
 # tests/test_gpu_paths.py. Nothing here comes from a GPU.
 MEASURED_F32_CHECKER = {
     "field": dict(t=1.451e-2, p=2.312e-4, n=8.155e-3, uv=4.650e-3, ta=1.595e-4),
+    "yard": dict(t=2.042e-3, p=2.076e-4, n=1.561e-2, uv=1.589e-3, ta=1.056e-4),
     # the axis sets and the segment sets (f32_figures; tabs = |dt| itself: a segment's t lies in [0, 1.5])
     "axis/book1": dict(t=2.055e-03, p=4.401e-07, n=2.297e-04, uv=8.022e-05, ta=1.815e-04, tabs=3.059e-04),
     "axis/cornell": dict(t=3.684e-06, p=3.697e-07, n=7.452e-07, uv=6.125e-07, ta=2.048e-06, tabs=3.302e-04),
@@ -382,11 +672,13 @@ MEASURED_F32_CHECKER = {
     "axis/rotated_sphere": dict(t=2.224e-06, p=7.986e-07, n=8.008e-06, uv=3.712e-06, ta=2.215e-06, tabs=1.260e-05),
     "axis/earth": dict(t=8.187e-05, p=4.391e-07, n=5.618e-06, uv=7.993e-06, ta=3.000e-05, tabs=4.451e-05),
     "axis/field": dict(t=2.407e-04, p=9.187e-06, n=3.806e-04, uv=1.074e-04, ta=1.154e-05, tabs=1.370e-04),
+    "axis/yard": dict(t=1.229e-04, p=2.070e-05, n=1.243e-03, uv=2.235e-04, ta=1.768e-05, tabs=2.448e-04),
     "segments/book1": dict(t=4.815e-04, p=5.186e-06, n=3.406e-04, uv=1.564e-04, ta=1.958e-04, tabs=1.958e-04),
     "segments/cornell": dict(t=4.599e-06, p=4.664e-06, n=2.878e-05, uv=1.407e-05, ta=4.463e-06, tabs=4.463e-06),
     "segments/mesh": dict(t=2.977e-05, p=2.824e-07, n=1.922e-07, uv=5.427e-06, ta=7.834e-07, tabs=7.834e-07),
     "segments/moving": dict(t=1.879e-03, p=1.113e-05, n=7.259e-04, uv=3.158e-05, ta=9.867e-05, tabs=9.867e-05),
     "segments/field": dict(t=3.449e-03, p=1.498e-05, n=9.245e-04, uv=1.278e-04, ta=1.614e-05, tabs=1.614e-05),
+    "segments/yard": dict(t=8.289e-03, p=1.461e-05, n=9.159e-04, uv=8.093e-05, ta=6.173e-05, tabs=6.173e-05),
 }
 
 
@@ -402,40 +694,45 @@ _cache = {}
 
 
 def ray_set(pkg, orc, name):
-    """dict(built, rays, ref, undecidable, ids, on) for one scene, computed once per process."""
+    """dict(built, rays, ref, undecidable, by_origin, ids, on) for one scene, computed once per process. undecidable: by the rule on d
+    or by the rule on o (origin_undecidable); by_origin: by the latter alone."""
     if name in _cache:
         return _cache[name]
     built = build_scene(pkg, name)
-    if name == "field_sah":                                   # the geometry of "field": the checker's answers do not depend on the device's builder
-        _cache[name] = dict(ray_set(pkg, orc, "field"), built=built)
+    if HBM_GEOMETRY.get(name, name) != name:                  # the geometry of "field" / "yard": the checker's answers do not depend on the device's builder
+        _cache[name] = dict(ray_set(pkg, orc, HBM_GEOMETRY[name]), built=built)
         return _cache[name]
     rng = np.random.default_rng(7 + (SCENES + HBM_SCENES).index(name))
     prim = camera_rays(built.cam, GRID[0], GRID[1], rng)
     if name == "field":
         prim = np.concatenate([prim, field_box_rays(rng)])
+    if name == "yard":
+        prim = np.concatenate([prim, yard_aimed_rays(pkg, built, rng)])
     first = ask(orc, built.desc, prim)
     k = np.flatnonzero(first["hit"])
     dirs = rng.normal(size=(len(k), 3)); dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
     sec = make_rays(first["p"][k], dirs, prim["time"][k])
     rays = np.concatenate([prim, sec])
     ref = ask(orc, built.desc, rays)
-    und = undecidable(orc, built.desc, rays, ref)
+    by_d = undecidable(orc, built.desc, rays, ref)
+    und = by_d | origin_undecidable(pkg, orc, built.desc, rays, ref)
     ids, on = objects_at(pkg, built.desc, ref["p"], rays["time"].astype(np.float64), built.extent)
-    _cache[name] = dict(built=built, rays=rays, ref=ref, undecidable=und, ids=ids, on=on)
+    _cache[name] = dict(built=built, rays=rays, ref=ref, undecidable=und, by_origin=und & ~by_d, ids=ids, on=on)
     return _cache[name]
 
 
 # ---- axis rays: directions with zero-class components, origins on the 1/4 lattice -------------------------------------------------------
 # The slab tests cap |1/d| (csrc/kernels.hip set_slab_ray and its two copies), go_root picks the octant from the sign bit, and the
 # primitive tests reject inf and NaN roots: none of which a camera ray or a random secondary ray reaches. These sets do.
-AXIS_SCENES = ["book1", "cornell", "mesh", "moving", "rotated_sphere", "earth", "field"]
+AXIS_SCENES = ["book1", "cornell", "mesh", "moving", "rotated_sphere", "earth", "field", "yard"]
+TIMED_SCENES = ("moving", "yard")                                                   # scenes with a time range: ray times are seeded over [0, 1]
 AXIS_RAYS, AXIS_SEED = 2000, 99
 ZERO_CLASS = np.array([0.0, -0.0, 1e-40, -1e-40, 1e-30, -1e-30], np.float32)        # +-0, a subnormal, a tiny normal
 # origins: uniform in this box around the scene's content (the Cornell box without its walls' planes; above book-1's ground)
 AXIS_BOX = {"book1": ((-11, 0.05, -11), (11, 3, 11)), "cornell": ((5, 5, 5), (550, 550, 550)), "mesh": ((-5, -0.2, -5), (5, 2, 5)),
             "moving": ((-3, 0, -3), (3, 2.5, 3)), "rotated_sphere": ((-4, 0.05, -4), (4, 2.5, 4)), "earth": ((-3, 0.05, -3), (3, 2.5, 3)),
-            "field": ((-13, -1.2, -13), (13, 6, 13))}
-RIM_SCENES, EDGE_SCENES = ("field", "mesh", "cornell"), ("mesh", "field")
+            "field": ((-13, -1.2, -13), (13, 6, 13)), "yard": ((-13, -0.2, -13), (13, 5, 13))}
+RIM_SCENES, EDGE_SCENES = ("field", "mesh", "cornell", "yard"), ("mesh", "field")
 EDGE_RAY = ((2.75, 0.5, 1.0), (-4.0, -0.24134248, -1e-30))      # in the plane z = 1 of `mesh`, through an edge two triangles share
 
 
@@ -463,8 +760,8 @@ def rim_rays(name, rng):
     zero = lambda: rng.choice(ZERO_CLASS[:2])
     q = lambda lo, hi: np.round(rng.uniform(lo, hi) * 4) / 4
     o, d = [], []
-    if name in ("field", "mesh"):                    # the ground rect, from above, outside the height field and the spheres
-        e, top = (14.0, 6.0) if name == "field" else (6.0, 2.0)
+    if name in ("field", "mesh", "yard"):            # the ground rect, from above, outside the height field and the spheres (yard: the lattice)
+        e, top = (6.0, 2.0) if name == "mesh" else (14.0, 6.0)
         for k in range(48):
             a, b = rng.choice([-e, e]), (rng.choice([-e, e]) if k % 4 == 0 else q(-e, e))
             o.append((a, q(0.0, top), b) if k & 1 else (b, q(0.0, top), a))
@@ -528,9 +825,12 @@ def twin(rays):
 
 
 def finish_set(pkg, orc, built, rays, und):
+    """und(ref): the set's rule on d; the rule on o (origin_undecidable) is added here, and `by_origin` are the rays it alone leaves out."""
     ref = ask(orc, built.desc, rays)
     ids, on = objects_at(pkg, built.desc, ref["p"], rays["time"].astype(np.float64), built.extent)
-    return dict(built=built, rays=rays, ref=ref, ids=ids, on=on, undecidable=und(ref))
+    by_d = und(ref)
+    both = by_d | origin_undecidable(pkg, orc, built.desc, rays, ref)
+    return dict(built=built, rays=rays, ref=ref, ids=ids, on=on, undecidable=both, by_origin=both & ~by_d)
 
 
 def axis_set(pkg, orc, name):
@@ -541,8 +841,8 @@ def axis_set(pkg, orc, name):
     if key in _cache:
         return _cache[key]
     built = build_scene(pkg, name)
-    if name == "field_sah":                                   # the geometry of "field" (as ray_set)
-        _cache[key] = dict(axis_set(pkg, orc, "field"), built=built)
+    if HBM_GEOMETRY.get(name, name) != name:                  # the geometry of "field" / "yard" (as ray_set)
+        _cache[key] = dict(axis_set(pkg, orc, HBM_GEOMETRY[name]), built=built)
         return _cache[key]
     rng = np.random.default_rng(AXIS_SEED + AXIS_SCENES.index(name))
     n = AXIS_RAYS
@@ -551,7 +851,7 @@ def axis_set(pkg, orc, name):
     snapped = rng.integers(0, 2, n).astype(bool)
     o[snapped] = np.round(o[snapped] * 4) / 4
     d = axis_dirs(rng, n)
-    tm = rng.uniform(0.0, 1.0, n) if name == "moving" else np.zeros(n)
+    tm = rng.uniform(0.0, 1.0, n) if name in TIMED_SCENES else np.zeros(n)
     ro, rd = rim_rays(name, rng) if name in RIM_SCENES else (np.zeros((0, 3)), np.zeros((0, 3), np.float32))
     eo, ed = edge_rays(name, rng) if name in EDGE_SCENES else (np.zeros((0, 3)), np.zeros((0, 3), np.float32))
     rays = make_rays(np.concatenate([o, ro, eo]), np.concatenate([d, rd, ed]), np.concatenate([tm, np.zeros(len(ro) + len(eo))]))
@@ -563,13 +863,14 @@ def axis_set(pkg, orc, name):
     tri = np.array([built.desc.hittables[int(h)].kind == pkg._abi.RT_HIT_TRIANGLE for h in s["ids"]])
     edge |= s["ref"]["hit"] & (s["on"][:, tri].sum(axis=1) >= 2)
     s["undecidable"] &= ~(rim | edge)
+    s["by_origin"] &= ~(rim | edge)
     s.update(snapped=np.concatenate([snapped, np.ones(len(ro) + len(eo), bool)]), rim=rim, edge=edge, decidable=~s["undecidable"])
     _cache[key] = s
     return s
 
 
 # ---- segments: point-to-point rays, d = q - p, the interval ending near t = 1 -------------------------------------------------------------
-SEGMENT_SCENES = ["book1", "cornell", "mesh", "moving", "field"]
+SEGMENT_SCENES = ["book1", "cornell", "mesh", "moving", "field", "yard"]
 SEGMENTS, SEGMENT_SEED, SEGMENT_MIN, SEGMENT_CAP = 2000, 5, 0.5, 0.05
 T_SURFACE, T_FREE = 0.98, 1.5           # t_max of a segment whose target lies on a surface / is a free point
 # both ends within this distance of the origin: segments that start or end hundreds of units out on a ground sphere say nothing about
@@ -577,7 +878,13 @@ T_SURFACE, T_FREE = 0.98, 1.5           # t_max of a segment whose target lies o
 SEGMENT_REACH = {"book1": 15.0, "moving": 15.0}
 # free targets within this distance of the source, per axis: `field` is dense (1250 spheres), and a segment across it is blocked nine
 # times in ten
-SEGMENT_LOCAL = {"field": 2.0}
+SEGMENT_LOCAL = {"field": 2.0, "yard": 2.0}
+# surface targets within this distance of the source: a long segment is undecidable more often (t_min and t_max -+ 1e-3 are in units of
+# |d|: 0.04 units at |d| = 20), and `yard` is held to a cap of 1 %. Every SEGMENT_LONG-th surface target stays where the seed put it,
+# anywhere in the scene, so that long segments that end on a surface remain in the set
+SEGMENT_NEAR = {"yard": 6.0}
+SEGMENT_LONG = 8
+SEGMENT_CAPS = {"yard": 0.01}           # (the others: SEGMENT_CAP)
 
 
 def segment_undecidable(orc, desc, rays, ref):
@@ -611,7 +918,12 @@ def segment_set(pkg, orc, name):
     lo, hi = np.array(AXIS_BOX[name][0], np.float64), np.array(AXIS_BOX[name][1], np.float64)
     if name in SEGMENT_LOCAL:
         lo, hi = np.maximum(lo, p - SEGMENT_LOCAL[name]), np.minimum(hi, p + SEGMENT_LOCAL[name])
-    q = np.where(on_surface[:, None], ref0["p"][k[rng.integers(0, len(k), SEGMENTS)]], rng.uniform(lo, hi, (SEGMENTS, 3))).astype(np.float32)
+    other = k[rng.integers(0, len(k), SEGMENTS)]
+    if name in SEGMENT_NEAR:                                  # the first of a seeded order of the hit points that lies near enough
+        for i in np.flatnonzero((np.linalg.norm(ref0["p"][other] - p, axis=1) > SEGMENT_NEAR[name]) & (np.arange(SEGMENTS) // 2 % SEGMENT_LONG != 0)):
+            near = k[np.linalg.norm(ref0["p"][k] - p[i], axis=1) <= SEGMENT_NEAR[name]]
+            other[i] = near[rng.integers(0, len(near))]
+    q = np.where(on_surface[:, None], ref0["p"][other], rng.uniform(lo, hi, (SEGMENTS, 3))).astype(np.float32)
     d = q - p
     keep = np.linalg.norm(d.astype(np.float64), axis=1) >= SEGMENT_MIN
     rays = make_rays(p[keep], d[keep], s["rays"]["time"][src][keep], np.where(on_surface[keep], np.float32(T_SURFACE), np.float32(T_FREE)))
