@@ -98,6 +98,7 @@ pub const RT_FLAG_COUNTERS: u32 = 1;
 pub const RT_FLAG_TIMING: u32 = 2;
 pub const RT_FLAG_SAMPLE_BLOCKS: u32 = 4;
 pub const RT_FLAG_FUSED: u32 = 8;         // diagnostic: the whole render by the fused per-path (tail) kernel
+pub const RT_FLAG_NO_CAMERA_LISTS: u32 = 16;   // A/B: camera rays are walked like every other ray (same frame); an unknown bit is RT_ERR_INVALID
 #[repr(C)] #[derive(Clone, Copy, Default, Debug)]
 pub struct RtParams {
     pub width: u32, pub height: u32, pub samples_per_pixel: u32, pub max_depth: u32, pub seed: u64,
@@ -367,6 +368,12 @@ extern "C" {
     pub fn rt_scene_top_layout_check(desc: *const RtSceneDesc, max_top: u32, out_n_top: *mut u64) -> c_int;
     pub fn rt_scene_compile_dump(desc: *const RtSceneDesc, nodes: *mut c_void, cap_nodes: u64, spheres: *mut f32,
                                  sphere_meta: *mut u32, cap_spheres: u64) -> c_int;
+    /// camera lists: 17 words per 8 x 8-pixel square (count or 0xFFFFFFFF = "walk", then sphere indices in leaf order); lists may be null
+    /// host only: the lists of a scene compiled with the default options; *out_n_squares = 0: the lists do not serve this scene or camera
+    pub fn rt_camera_lists_host(desc: *const RtSceneDesc, cam: *const RtCamera, width: u32, height: u32, lists: *mut u32, cap_words: u64,
+                                out_n_squares: *mut u64) -> c_int;
+    /// the lists the last render or pass of this context built on the device; *out_n_squares = 0: it built none
+    pub fn rt_camera_lists_last(ctx: *mut RtCtx, lists: *mut u32, cap_words: u64, out_n_squares: *mut u64) -> c_int;
 }
 
 /// The reference's error convention is panic (main.rs:656,762,777,779): a negative status becomes one, with the library's message.

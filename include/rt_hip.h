@@ -211,8 +211,11 @@ enum {
     RT_FLAG_TIMING = 2u,    /* bracket every kernel launch with HIP events (RtStats *_ms) */
     RT_FLAG_SAMPLE_BLOCKS = 4u, /* work items of 16 consecutive samples of a pixel, as for images of 2^32 - 2^28 samples and more
                                    (default below that: one sample per item). Per-pixel sums then differ in the last bits. */
-    RT_FLAG_FUSED = 8u          /* diagnostic: the whole render by the fused per-path kernel that normally carries only the tail (one
+    RT_FLAG_FUSED = 8u,         /* diagnostic: the whole render by the fused per-path kernel that normally carries only the tail (one
                                    lane per path from first ray to last bounce). Bit-identical frame, slower. */
+    RT_FLAG_NO_CAMERA_LISTS = 16u /* camera rays are walked through the tree like every other ray instead of being tested, where they are made,
+                                   against the list of spheres their 8 x 8-pixel square can meet (sphere-only scenes in LDS). Bit-identical
+                                   frame; for A/B runs and tests. An unknown bit in flags is RT_ERR_INVALID. */
 };
 
 typedef struct RtParams {
@@ -864,6 +867,19 @@ int rt_scene_compile_dump(const RtSceneDesc* desc, void* nodes, uint64_t cap_nod
                           float* spheres, uint32_t* sphere_meta, uint64_t cap_spheres);
 int rt_scene_compile_dump_ex(const RtSceneDesc* desc, const RtUploadOptions* options, void* nodes, uint64_t cap_nodes,
                              float* spheres, uint32_t* sphere_meta, uint64_t cap_spheres);
+
+/* Camera lists (csrc/camera_lists.h): per 8 x 8-pixel square of a width x height frame, row-major over ceil(width / 8) x ceil(height / 8)
+   squares, 17 words: the number of spheres of the tree a camera ray of that square can meet (0xFFFFFFFF: more than 16, the square's rays are
+   walked), then their indices into rt_scene_compile_dump's sphere records, in the order the node records reach their leaves; unused words
+   are 0. A sphere tested before the tree (RtCompileInfo.first) is not in the lists.
+     rt_camera_lists_host  (host only) the lists of a scene as compiled with the default options, by the predicate the device runs.
+                           *out_n_squares = 0: the lists do not serve this scene (a primitive that is no static sphere) or camera (not finite).
+     rt_camera_lists_last  the lists the last render or pass of this context built on the device; *out_n_squares = 0: it built none
+                           (RT_FLAG_NO_CAMERA_LISTS, RT_FLAG_COUNTERS, RT_FLAG_FUSED, a scene that is not sphere-only or not walked from LDS).
+   lists may be NULL (the count only); cap_words < 17 * squares is RT_ERR_INVALID. */
+int rt_camera_lists_host(const RtSceneDesc* desc, const RtCamera* cam, uint32_t width, uint32_t height, uint32_t* lists, uint64_t cap_words,
+                         uint64_t* out_n_squares);
+int rt_camera_lists_last(RtCtx* ctx, uint32_t* lists, uint64_t cap_words, uint64_t* out_n_squares);
 
 /* RT_SCENE_LIGHTS_MANY (host only): the light tree and the weights as the upload lays them out. n = members of the lights list.
      nodes   2n - 1 records of 32 B in pre-order, the device's form (csrc/device_types.h NodeDev): f32 cx, cy, hx, hy, cz, hz (the box is

@@ -13,7 +13,8 @@ RT_MAT_LAMBERTIAN, RT_MAT_METAL, RT_MAT_DIELECTRIC, RT_MAT_DIFFUSE_LIGHT, RT_MAT
 RT_BG_CONSTANT, RT_BG_SKY_GRADIENT = 0, 1
 RT_BVH_REFERENCE, RT_BVH_SAH = 0, 1
 RT_NAN_PER_SAMPLE, RT_NAN_REFERENCE = 0, 1
-RT_FLAG_COUNTERS, RT_FLAG_TIMING, RT_FLAG_SAMPLE_BLOCKS, RT_FLAG_FUSED = 1, 2, 4, 8
+RT_FLAG_COUNTERS, RT_FLAG_TIMING, RT_FLAG_SAMPLE_BLOCKS, RT_FLAG_FUSED, RT_FLAG_NO_CAMERA_LISTS = 1, 2, 4, 8, 16
+RT_CAMERA_LIST_WORDS, RT_CAMERA_LIST_WALK = 17, 0xFFFFFFFF    # csrc/camera_lists.h: words per square (count + 16 indices), the "walk" count
 RT_OUT_RGB_SUM_F32, RT_OUT_RGB8 = 0, 1
 RT_PASS_ACCUMULATE = 1
 RT_COMM_ID_BYTES = 128
@@ -203,7 +204,8 @@ RT_HIP_SYMBOLS = ["rt_ctx_create", "rt_ctx_destroy", "rt_scene_upload", "rt_scen
                   "rt_ray_query_check", "rt_trace_rays_device", "rt_trace_rays", "rt_occluded_rays_device", "rt_occluded_rays",
                   "rt_sample_lights_device", "rt_sample_lights", "rt_scene_light_tree_dump",
                   "rt_features_check", "rt_render_features_device",
-                  "rt_feature_moments_check", "rt_render_feature_moments_device", "rt_denoise_guided_moments_check", "rt_denoise_guided_moments_device"]
+                  "rt_feature_moments_check", "rt_render_feature_moments_device", "rt_denoise_guided_moments_check", "rt_denoise_guided_moments_device",
+                  "rt_camera_lists_host", "rt_camera_lists_last"]
 RT_HOST_SYMBOLS = ["rt_host_scene_create", "rt_host_scene_desc", "rt_host_scene_camera", "rt_host_scene_destroy", "rt_host_camera_new",
                    "rt_host_write_color", "rt_host_tonemap", "rt_host_write_png", "rt_host_write_jpeg", "rt_host_write_image"]
 
@@ -302,6 +304,10 @@ def declare(lib):
     lib.rt_scene_wide_layout_check.argtypes = [P(RtSceneDesc), P(RtWideInfo)]
     lib.rt_scene_light_tree_dump.restype = i32
     lib.rt_scene_light_tree_dump.argtypes = [P(RtSceneDesc), vp, u64, P(u32), P(C.c_float), P(C.c_float), u64, P(u64), P(u64)]
+    lib.rt_camera_lists_host.restype = i32
+    lib.rt_camera_lists_host.argtypes = [P(RtSceneDesc), P(RtCamera), u32, u32, P(u32), u64, P(u64)]
+    lib.rt_camera_lists_last.restype = i32
+    lib.rt_camera_lists_last.argtypes = [vp, P(u32), u64, P(u64)]
     lib.rt_scene_compile_dump.restype = i32
     lib.rt_scene_compile_dump.argtypes = [P(RtSceneDesc), vp, u64, P(C.c_float), P(u32), u64]
     lib.rt_untile_rgb8.restype = i32

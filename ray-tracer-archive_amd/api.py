@@ -249,6 +249,19 @@ def compile_dump(desc, layout_flags=0, **more):
     return nodes, spheres[:info["n_spheres"]], meta[:info["n_spheres"]]
 
 
+def camera_lists_host(desc, cam, width, height):
+    """rt_camera_lists_host: the camera lists of a width x height frame as a (squares, 17) uint32 array — row-major over
+    ceil(width / 8) x ceil(height / 8) squares; column 0 the count (A.RT_CAMERA_LIST_WALK: more than 16), then sphere indices in leaf
+    order. None: the lists do not serve this scene or camera."""
+    n = C.c_uint64(0)
+    _check(lib().rt_camera_lists_host(C.byref(desc), C.byref(cam), width, height, None, 0, C.byref(n)))
+    if n.value == 0:
+        return None
+    out = np.zeros((n.value, A.RT_CAMERA_LIST_WORDS), dtype=np.uint32)
+    _check(lib().rt_camera_lists_host(C.byref(desc), C.byref(cam), width, height, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, C.byref(n)))
+    return out
+
+
 class HostScene:
     """A scene function of main.rs, built by the C++ host mirror (host/rt_host.hpp)."""
 
@@ -387,6 +400,16 @@ class Context:
         if params.shard_count <= 1:
             out = out.reshape(params.height, params.width, 3)
         return out, st.as_dict()
+
+    def camera_lists_last(self):
+        """rt_camera_lists_last: the camera lists the last render or pass built on the device, as camera_lists_host returns them; None: it built none."""
+        n = C.c_uint64(0)
+        _check(lib().rt_camera_lists_last(self._h, None, 0, C.byref(n)), self._h)
+        if n.value == 0:
+            return None
+        out = np.zeros((n.value, A.RT_CAMERA_LIST_WORDS), dtype=np.uint32)
+        _check(lib().rt_camera_lists_last(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, C.byref(n)), self._h)
+        return out
 
     def render_device(self, scene, cam, params, device_ptr):
         """rt_render_device: result stays in caller-owned device memory (e.g. a torch tensor's data_ptr())."""

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "camera_lists.h"
 #include "device_types.h"
 
 namespace rtk {
@@ -147,7 +148,17 @@ struct RenderDev {
     const uint32_t* list_map;
     FastDiv div_list;       // n_list
     uint32_t* counts;       // k_resolve_list: counts[slot] = spp (the pass's end)
+    // Camera lists (camera_lists.h; nullptr: none): per 8 x 8-pixel square of the image, (x >> 3, y >> 3) of the GLOBAL pixel, the spheres a camera
+    // ray of that square can meet. A camera ray is tested against them where it is made (k_generate, k_shade's regeneration) instead of in a walk:
+    // the kernel that made it writes its hit record and sets kRayAnswered in the ray record. Only for the sphere-only instances, the scene in LDS,
+    // no counting (rt_api.cpp render_impl).
+    const uint32_t* cam_lists; uint32_t cam_squares_x;
+    const rtd::Float4* cam_spheres;   // the scene's spheres in HBM (k_generate has no SceneDev)
 };
+// Bit 31 of a ray record's `from` word (ray_d.w): the ray's hit record is already written, k_extend's refill hands its lane no walk. Primitive ids
+// are type << 28 | index with type < 8, so the bit is free; it is only ever set on camera rays (from = 0), and every reader of the word that
+// can meet it masks it off (the refill of the sphere-only LDS walk, the drain's load), so `from` means downstream what it meant.
+constexpr uint32_t kRayAnswered = 0x80000000u;
 
 struct LaunchCfg {
     uint32_t n_cu;            // k_extend runs as a persistent grid: n_cu x (resident workgroups per CU)
@@ -159,6 +170,12 @@ struct LaunchCfg {
 
 // what a launcher has to say about the error it has just returned (nullptr: nothing beyond hipGetErrorString)
 const char* launch_note();
+// the camera lists of a frame: one thread per square (kernels.hip k_camera_lists); `order`: the tree's spheres in the order the record array
+// reaches their leaves (rt_api.cpp camera_order); lists: n_squares * rtcl::kListWords words
+struct CamListsDev { rtcl::Camera cam; const float* spheres; const uint32_t* order; uint32_t n_order; uint32_t* lists; uint32_t n_squares; };
+hipError_t launch_camera_lists(const CamListsDev& cl, hipStream_t stream);
+// whether the kernels a scene of these features runs are the ones compiled to honour kRayAnswered (the sphere-only variant)
+bool camera_lists_fit(uint32_t features);
 hipError_t launch_generate(const PoolDev& pool, const RenderDev& rd, uint32_t n_init, uint32_t* out_count, hipStream_t stream);
 // One wavefront iteration = launch_extend then launch_shade. No memsets in between: k_extend zeroes
 // the count the following k_shade appends to, k_shade zeroes the queue head of the next k_extend.

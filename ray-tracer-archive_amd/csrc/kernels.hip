@@ -644,7 +644,7 @@ enum : uint32_t { SH_FINISHED = 1u, SH_TIME_ZERO = 2u };
 template <uint32_t FEAT> DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& d, float tm, PathState& s, Rng& g, uint32_t& depth, uint2 hit, V3& L,
                                                      unsigned long long& c_light_rect, unsigned long long& c_light_sphere, unsigned long long& c_light_tri);
 DEVI bool finish_sample(const RenderDev& rd, PathState& s, Rng& g, uint32_t& depth, V3 L, V3& o, V3& d, float& tm);
-template <bool LIST> DEVI void start_item(const RenderDev& rd, uint32_t work, PathState& s, Rng& g, V3& o, V3& d, float& tm);
+template <bool LIST> DEVI void start_item(const RenderDev& rd, uint32_t work, PathState& s, Rng& g, V3& o, V3& d, float& tm, uint32_t* square = nullptr);
 // L, the radiance of the sample in flight, is not part of the state: `emitted` is non-zero only for
 // DiffuseLight, which never scatters (material.rs:12-14,184-190), and the background is returned on a miss
 // (main.rs:74-76) — so radiance is only ever added by the event that ENDS the path, in the same shading step
@@ -687,6 +687,9 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
     static_assert(!ANYHIT || (!COUNT && !DRAIN && !LIST && (FEAT & F_MEDIUM) == 0u), "the any-hit walk serves ray queries: no counters, drain, list or media");
     extern __shared__ float4 lds[];
     constexpr bool LDS = MODE == M_LDS, TOP = MODE == M_TOP, C16 = MODE == M_C16;
+    // the instances a render with camera lists runs (rt_api.cpp render_impl): a ray record can carry kRayAnswered (kernels.h). Every other
+    // instance never meets the mark and is the program it was.
+    constexpr bool MARKS = LDS && FEAT == 0u && !COUNT && !ANYHIT;
     constexpr int kSteps = (FEAT & F_ALL) == F_ALL ? kStepsAll : kStepsPlain;
     // The pool is kQueues independent queues (kernels.h): a wave serves the queue of its number mod kQueues, a DRAIN workgroup the
     // queue of its block number; every counter exists once per queue, 128 bytes apart.
@@ -888,6 +891,7 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
             o = v3(ro.x, ro.y, ro.z); d = v3(rdv.x, rdv.y, rdv.z); tm = ro.w;
             if (rd.first_in_shade != 0u) tm = 0.f;     // (the slot held the first sphere's t for a k_extend of the other kind; this walk starts parked at that sphere)
             ps.T = v3(s0.x, s0.y, s0.z); ps.work = __float_as_uint(s0.w); ps.from = __float_as_uint(rdv.w);
+            if constexpr (MARKS) ps.from &= ~kRayAnswered;     // a camera ray answered where it was made is walked here all the same: same hit, no second path
             uint32_t stored = 0u;
             if (with_acc) { const Float4 s1 = pool.s1[qbase + i]; ps.acc = v3(s1.x, s1.y, s1.z); stored = __float_as_uint(s1.w); }
             depth = sd & 0xFFu;
@@ -913,7 +917,11 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
                 const int src = (int)(rank & 63u);
                 const float ox = __shfl(No.x, src), oy = __shfl(No.y, src), oz = __shfl(No.z, src), ot = __shfl(No.w, src);
                 const float dx = __shfl(Nd.x, src), dy = __shfl(Nd.y, src), dz = __shfl(Nd.z, src), dfrom = __shfl(Nd.w, src);
-                if (lane_idle && rank < take) {
+                // (MARKS) a ray answered where it was made: its hit record is written, the lane stays idle and takes the next refill's ray. (A refill
+                // that goes on handing out rays at once while kRefillMin lanes are still idle measured the same: DESIGN.md section 4.)
+                bool answered = false;
+                if constexpr (MARKS) answered = (__float_as_uint(dfrom) & kRayAnswered) != 0u;
+                if (lane_idle && rank < take && !answered) {
                     slot = w_next + rank;
                     o = v3(ox, oy, oz); d = v3(dx, dy, dz); tm = ot;
                     from = __float_as_uint(dfrom);            // primitive this ray starts on (0: camera / medium)
@@ -1561,16 +1569,60 @@ DEVI float first_sphere_hit(const RenderDev& rd, V3 o, V3 d, uint32_t from) {
 }
 
 // A fresh path for work item `work` (first sample of its block).
+// `square` (optional): out — the pixel's square of the camera lists (kernels.h RenderDev::cam_lists)
 template <bool LIST>
-DEVI void start_item(const RenderDev& rd, uint32_t work, PathState& s, Rng& g, V3& o, V3& d, float& tm) {
+DEVI void start_item(const RenderDev& rd, uint32_t work, PathState& s, Rng& g, V3& o, V3& d, float& tm, uint32_t* square) {
     const WorkItem it = decode_work<LIST>(rd, work);
+    if (square != nullptr) *square = (it.y >> 3) * rd.cam_squares_x + (it.x >> 3);
     const uint32_t sample = rd.first_sample + (it.blk << rd.block_shift);   // absolute: a pass starts at first_sample
     new_camera_ray(rd, it.x, it.y, sample, g, o, d, tm);
     s.T = v3(1, 1, 1); s.acc = v3(0, 0, 0);
     s.work = item_id(rd, it.x, it.y, it.blk); s.sample = sample; s.from = 0u;
 }
 
-template <bool LIST>
+// RenderDev::cam_lists: the closest hit of the camera ray (o, d) of `square` with the spheres of the tree, from (tmax, hit_prim) = what was
+// tested before the tree (the first sphere's hit, or nothing). The walk's sphere pass (k_extend LT_SPHERE) over the square's list as ONE leaf:
+// sphere_fast in list order = the order the walk reaches the leaves, then sphere_roots for the undecided, the kBigSphere rule; a camera ray
+// starts on nothing, so no sphere is its `from`. (One way this differs from the walk, which finishes a leaf — fast, then roots — before the
+// next: two spheres of different leaves hit at exactly the same f32 t, the earlier decided by sphere_roots and the later by sphere_fast,
+// resolve to the earlier one here and to the later one there. No such pair has been met; a test's t is a function of ray and sphere alone,
+// so nothing short of an exact tie depends on the order.) A second copy of that pass, not a shared function: the walk's reads a contiguous run of the
+// staged spheres, this one gathers by index from HBM, and k_extend's text stays what it was. False: the square is marked "walk".
+DEVI bool camera_list_hit(const RenderDev& rd, uint32_t square, V3 o, V3 d, float& tmax, uint32_t& hit_prim) {
+    const uint32_t* list = rd.cam_lists + square * rtcl::kListWords;
+    const uint32_t cnt = list[0];
+    if (cnt == rtcl::kWalk) return false;
+    const float a = len2(d);
+    uint32_t surv = 0u;
+    for (uint32_t k = 0; k < cnt; ++k) {
+        const uint32_t idx = list[1u + k];
+        const Float4 s = rd.cam_spheres[idx];
+        float t;
+        const int r = s.w >= kBigSphere ? 2 : sphere_fast(o, d, a, v3(s.x, s.y, s.z), s.w, kTMin, tmax, t);
+        if (r == 1) { tmax = t; hit_prim = (rtd::LT_SPHERE << 28) | idx; }
+        surv |= (r == 2 ? 1u : 0u) << k;
+    }
+    while (surv != 0u) {
+        const uint32_t k = (uint32_t)__builtin_ctz(surv);
+        surv &= surv - 1u;
+        const uint32_t idx = list[1u + k];
+        const Float4 s = rd.cam_spheres[idx];
+        float t;
+        if (sphere_roots(o, d, a, v3(s.x, s.y, s.z), s.w, kTMin, tmax, t)) { tmax = t; hit_prim = (rtd::LT_SPHERE << 28) | idx; }
+    }
+    return true;
+}
+
+// one thread per square of the frame (camera_lists.h)
+__global__ void __launch_bounds__(64) k_camera_lists(CamListsDev cl) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cl.n_squares) return;
+    const uint32_t sqx = rtcl::squares_x(cl.cam.width);
+    rtcl::build_list(cl.cam, i % sqx, i / sqx, cl.spheres, cl.order, cl.n_order, cl.lists + (size_t)i * rtcl::kListWords);
+}
+
+// CAML: the render has camera lists (kernels.h RenderDev::cam_lists): the ray is answered here, k_extend hands it no walk
+template <bool LIST, bool CAML>
 __global__ void __launch_bounds__(kShadeThreads) k_generate(PoolDev pool, RenderDev rd, uint32_t n_init, uint32_t* __restrict__ out_count) {
     // the first fill of the pool needs no allocator: work item i goes to queue (i / 512) mod kQueues, slot (i / 4096) * 512 + i mod 512
     // of it (the host passes n_init <= total_items), and the counters get their values from kQueues threads. (With the atomics +
@@ -1582,9 +1634,16 @@ __global__ void __launch_bounds__(kShadeThreads) k_generate(PoolDev pool, Render
     }
     if (i < n_init) {
         PathState s; V3 o, d; float tm; Rng g;
-        start_item<LIST>(rd, i, s, g, o, d, tm);
+        uint32_t square = 0u;
+        start_item<LIST>(rd, i, s, g, o, d, tm, CAML ? &square : nullptr);
         if (rd.first_in_shade != 0u) tm = first_sphere_hit(rd, o, d, 0u);         // (the time slot of a motionless scene: kernels.h)
         const uint32_t q = (i >> 9) & (kQueues - 1u), slot = ((i / (512u * kQueues)) << 9) | (i & 511u);
+        if constexpr (CAML) {
+            // as k_extend's refill begins such a ray: the first sphere's t from the time slot, or nothing
+            float tmax = rd.first_in_shade != 0u ? tm : kInf;
+            uint32_t hit_prim = tmax < kInf ? rd.first_id : rtd::HIT_NONE;
+            if (camera_list_hit(rd, square, o, d, tmax, hit_prim)) { pool.hit[q * rd.queue_cap + slot] = make_uint2(__float_as_uint(tmax), hit_prim); s.from = kRayAnswered; }
+        }
         store_path(pool, q * rd.queue_cap + slot, o, d, tm, s, g.n, 0u, rd.block_shift != 0u);
     }
 }
@@ -2082,7 +2141,8 @@ DEVI bool finish_sample(const RenderDev& rd, PathState& s, Rng& g, uint32_t& dep
     return true;
 }
 
-template <uint32_t FEAT, bool COUNT, bool LIST>
+// CAML: camera lists (kernels.h RenderDev::cam_lists) — a path that has just begun an item answers its camera ray here
+template <uint32_t FEAT, bool COUNT, bool LIST, bool CAML = false>
 // The Cornell variant (rects, instance transforms, light sampling) at 6 waves per SIMD (79 VGPRs and 20 B of scratch instead of 87 and
 // none): k_shade 36.0 -> 32.2 ms on config 4. The full variant loses at every forced occupancy (5: 34.0 -> 36.7 ms on the book-2 final
 // scene, 6: 43.0), the sphere-only ones already run 8 waves.
@@ -2153,6 +2213,7 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
     unsigned long long c_samples = 0, c_light_rect = 0, c_light_sphere = 0, c_light_tri = 0;
     Rng g; g.s = 0; g.n = 0u; uint32_t depth = 0u;
     bool began = false;                // this thread's path has just begun a new work item (a camera ray)
+    uint32_t cam_square = 0u;          // CAML: ... and the square of its pixel
     if (alive) {
         const Float4 ro = in.ray_o[qbase + i], rdv = in.ray_d[qbase + i], s0 = in.s0[qbase + i];
         const uint32_t sd = in.sd[qbase + i]; const uint2 hit = in.hit[qbase + i];
@@ -2182,7 +2243,7 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
                 // no counter, no atomic, no barrier (round 2 drew items from a per-queue counter: one returning atomic and three barriers
                 // per workgroup) ----
                 const uint32_t next = w + rd.lineage;
-                if (next < rd.total_items) { start_item<LIST>(rd, next, s, g, o, d, tm); depth = 0u; began = true; }
+                if (next < rd.total_items) { start_item<LIST>(rd, next, s, g, o, d, tm, CAML ? &cam_square : nullptr); depth = 0u; began = true; }
                 else alive = false;
             }
         }
@@ -2210,6 +2271,13 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
         }
         SSTAMP(4);
         if (rd.first_in_shade != 0u && alive) tm = first_sphere_hit(rd, o, d, s.from);
+        if constexpr (CAML) {
+            if (alive && began) {      // as in k_generate
+                float tmax = rd.first_in_shade != 0u ? tm : kInf;
+                uint32_t hit_prim = tmax < kInf ? rd.first_id : rtd::HIT_NONE;
+                if (camera_list_hit(rd, cam_square, o, d, tmax, hit_prim)) { out.hit[qbase + dst] = make_uint2(__float_as_uint(tmax), hit_prim); s.from = kRayAnswered; }
+            }
+        }
         if (alive) store_path(out, qbase + dst, o, d, tm, s, g.n, depth, with_acc);
     }
 #ifdef RT_SHADE_STAMPS
@@ -2979,6 +3047,12 @@ hipError_t launch_shade(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev&
                         hipStream_t stream) {
     const uint32_t blocks = rd.q_n * ((max_count + kShadeThreads - 1u) / kShadeThreads);   // max_count = upper bound of the paths in ONE queue
     if (blocks == 0u) return hipSuccess;
+    if (rd.cam_lists != nullptr) {     // (render_impl: the sphere-only variant, no counting)
+        with_flag(rd.n_list != 0u, [&](auto list) {
+            hipLaunchKernelGGL((k_shade<0u, false, decltype(list)::value, true>), dim3(blocks), dim3(kShadeThreads), sc.shade_blob_bytes, stream,
+                               sc, in, out, rd, count_in, count_out, hz, counters); });
+        return hipGetLastError();
+    }
     with_shade_variant(cfg.features, [&](auto feat) { with_flag(count, [&](auto cnt) { with_flag(rd.n_list != 0u, [&](auto list) {
         hipLaunchKernelGGL((k_shade<decltype(feat)::value, decltype(cnt)::value, decltype(list)::value>), dim3(blocks), dim3(kShadeThreads), sc.shade_blob_bytes, stream,
                            sc, in, out, rd, count_in, count_out, hz, counters); }); }); });
@@ -2988,10 +3062,18 @@ hipError_t launch_shade(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev&
 hipError_t launch_generate(const PoolDev& pool, const RenderDev& rd, uint32_t n_init, uint32_t* out_count, hipStream_t stream) {
     const uint32_t blocks = (n_init + kShadeThreads - 1u) / kShadeThreads;
     if (blocks == 0u) return hipSuccess;
-    with_flag(rd.n_list != 0u, [&](auto list) { hipLaunchKernelGGL(k_generate<decltype(list)::value>, dim3(blocks), dim3(kShadeThreads), 0, stream, pool, rd, n_init, out_count); });
+    with_flag(rd.n_list != 0u, [&](auto list) { with_flag(rd.cam_lists != nullptr, [&](auto caml) {
+        hipLaunchKernelGGL((k_generate<decltype(list)::value, decltype(caml)::value>), dim3(blocks), dim3(kShadeThreads), 0, stream, pool, rd, n_init, out_count); }); });
     return hipGetLastError();
 }
 
+hipError_t launch_camera_lists(const CamListsDev& cl, hipStream_t stream) {
+    if (cl.n_squares == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_camera_lists, dim3((cl.n_squares + 63u) / 64u), dim3(64), 0, stream, cl);
+    return hipGetLastError();
+}
+
+bool camera_lists_fit(uint32_t features) { return features == 0u; }
 bool can_test_first_in_shade(uint32_t features) { return (features & (F_MOVING | F_MEDIUM)) == 0u; }
 
 hipError_t launch_resolve(const RenderDev& rd, float* out, uint32_t n_valid_pixels, hipStream_t stream) {

@@ -50,6 +50,38 @@ static uint32_t scene_features(const rtc::CompiledScene& cs) {
     return f;
 }
 
+// Camera lists (csrc/camera_lists.h): the spheres of the tree in the order the threaded record array reaches their leaves, which is the
+// order a list names its candidates in. Empty for a scene the lists do not serve: a primitive that is no static sphere, a sphere that bounds
+// a medium, or several primitives tested before the tree (one such sphere is tested where rays are made and is not in the lists).
+static std::vector<uint32_t> camera_order(const rtc::CompiledScene& cs) {
+    std::vector<uint32_t> order;
+    if (scene_features(cs) != 0u || !cs.prologue.empty() || cs.spheres.empty()) return order;
+    if (cs.first_leaf != 0u && !((cs.first_leaf >> 28) == rtd::LT_SPHERE && ((cs.first_leaf >> 24) & 15u) == 1u)) return order;
+    for (const rtd::Node& n : cs.nodes) {
+        if (n.leaf == 0u) continue;
+        const uint32_t type = n.leaf >> 28, cnt = (n.leaf >> 24) & 15u, first = n.leaf & rtd::LEAF_MAX_FIRST;
+        if (type != rtd::LT_SPHERE) return std::vector<uint32_t>();
+        for (uint32_t k = 0; k < cnt; ++k) order.push_back(first + k);
+    }
+    return order;
+}
+static rtcl::Camera camera_lists_camera(const RtCamera* cam, uint32_t width, uint32_t height) {
+    rtcl::Camera c{};
+    auto cp3 = [](double* d, const RtVec3& v) { d[0] = (double)(float)v.x; d[1] = (double)(float)v.y; d[2] = (double)(float)v.z; };   // the f32 values new_camera_ray reads
+    cp3(c.org, cam->origin); cp3(c.llc, cam->lower_left_corner); cp3(c.hor, cam->horizontal); cp3(c.ver, cam->vertical);
+    double u[3], v[3]; cp3(u, cam->u); cp3(v, cam->v);
+    c.lens_radius = std::fabs((double)(float)cam->lens_radius) * rtcl::lens_reach(u, v);   // (an RtCamera filled by hand need not hold orthonormal u, v)
+    c.width = width; c.height = height;
+    return c;
+}
+static bool camera_is_finite(const RtCamera* cam) {
+    const double v[] = {cam->origin.x, cam->origin.y, cam->origin.z, cam->lower_left_corner.x, cam->lower_left_corner.y, cam->lower_left_corner.z, cam->horizontal.x,
+                        cam->horizontal.y, cam->horizontal.z, cam->vertical.x, cam->vertical.y, cam->vertical.z, cam->u.x, cam->u.y, cam->u.z, cam->v.x, cam->v.y, cam->v.z,
+                        cam->lens_radius};
+    for (double x : v) if (!std::isfinite((double)(float)x)) return false;
+    return true;
+}
+
 int rti::validate_params(RtCtx* ctx, const RtParams* p) {
     if (!p) return set_err(ctx, RT_ERR_INVALID, "params is null");
     if (p->width < 2 || p->height < 2) return set_err(ctx, RT_ERR_INVALID, "width and height must be >= 2 (u = (i+rnd)/(W-1), main.rs:752)");
@@ -58,6 +90,8 @@ int rti::validate_params(RtCtx* ctx, const RtParams* p) {
     if (p->samples_per_pixel == 0) return set_err(ctx, RT_ERR_INVALID, "samples_per_pixel must be >= 1");
     if (p->max_depth == 0 || p->max_depth > 255) return set_err(ctx, RT_ERR_INVALID, "max_depth must be in 1..255");
     if (p->nan_policy > 1) return set_err(ctx, RT_ERR_INVALID, "bad nan_policy");
+    if (p->flags & ~(uint32_t)(RT_FLAG_COUNTERS | RT_FLAG_TIMING | RT_FLAG_SAMPLE_BLOCKS | RT_FLAG_FUSED | RT_FLAG_NO_CAMERA_LISTS))
+        return set_err(ctx, RT_ERR_INVALID, "RtParams.flags holds an unknown bit");
     Tiling t;
     if (make_tiling(*p, t) != RT_OK) return set_err(ctx, RT_ERR_INVALID, "bad tile_size / shard_index / shard_count");
     return RT_OK;
@@ -655,6 +689,8 @@ int rti::scene_image_upload(RtCtx* ctx, const SceneImage& im, RtScene** out_scen
         up(s->sphere_mat_a, sphere_ma); up(s->sphere_mat_b, sphere_mb);
     }
     if (im.use_wide) up(s->wide, im.wide.words);
+    const std::vector<uint32_t> cam_order = im.in_lds ? camera_order(cs) : std::vector<uint32_t>();
+    if (!cam_order.empty()) up(s->cam_order, cam_order);
     if (!im.blob.empty()) up(s->shade_blob, im.blob);
     if (!im.eblob.empty()) up(s->ext_blob, im.eblob);
     if (r == RT_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) r = set_err(ctx, RT_ERR_DEVICE, "scene upload failed");   // the image is the caller's: its vectors outlive this wait
@@ -703,6 +739,7 @@ int rti::scene_image_upload(RtCtx* ctx, const SceneImage& im, RtScene** out_scen
             std::memcpy(s->first_prim, &cs.rects[2 * k], 32);
         }
     }
+    s->n_cam_order = (uint32_t)cam_order.size();
     s->n_nodes = cs.nodes.size();
     s->n_prims = cs.sphere_meta.size() + cs.moving_meta.size() + cs.rect_meta.size() + cs.tri_meta.size() + cs.media.size();
     s->bytes = cs.nodes.size() * 32 + cs.spheres.size() * 16 + cs.moving.size() * 16 + cs.rects.size() * 16 + (cs.tris.size() + tri_front) * 16 +
@@ -927,6 +964,21 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     // the ground sphere tested where a ray is made (kernels.h RenderDev::first_in_shade): a scene without motion, one such sphere, no counting
     rd.first_in_shade = scene->first_id != 0u && rtk::can_test_first_in_shade(scene->features) && !counting ? 1u : 0u;
     rd.first_id = scene->first_id; for (int k = 0; k < 8; ++k) rd.first_prim[k] = scene->first_prim[k];
+    // Camera lists (kernels.h RenderDev::cam_lists), rebuilt for this camera and frame: the sphere-only instances over a scene in LDS, not while
+    // counting (the counts are the walk's), not for the fused diagnostic, and a finite camera. Keyed by the global pixel, so a shard, a pass
+    // and a pixel list use the same lists. Otherwise the render is what it was.
+    ctx->cam_squares = 0u;
+    if (scene->n_cam_order != 0u && scene->in_lds && rtk::camera_lists_fit(scene->features) && !counting &&
+        (prm->flags & (RT_FLAG_FUSED | RT_FLAG_NO_CAMERA_LISTS)) == 0u && camera_is_finite(cam)) {
+        rtk::CamListsDev cl{};
+        cl.cam = camera_lists_camera(cam, prm->width, prm->height);
+        cl.n_squares = rtcl::squares_x(prm->width) * rtcl::squares_y(prm->height);
+        HIP_TRY(ctx, ctx->cam_lists.ensure((size_t)cl.n_squares * rtcl::kListWords * 4u));
+        cl.spheres = (const float*)scene->dev.spheres; cl.order = (const uint32_t*)scene->cam_order.p; cl.n_order = scene->n_cam_order; cl.lists = (uint32_t*)ctx->cam_lists.p;
+        LAUNCH_TRY(rtk::launch_camera_lists(cl, ctx->stream));
+        rd.cam_lists = cl.lists; rd.cam_squares_x = rtcl::squares_x(prm->width); rd.cam_spheres = scene->dev.spheres;
+        ctx->cam_squares = cl.n_squares;
+    }
     HIP_TRY(ctx, rtk::launch_generate(pd[0], rd, n_init, cb.count[0], ctx->stream));
     if (timing) { HIP_TRY(ctx, tm.mark(e1)); tm.span(e0, e1, 2); }
     // The host never waits for an iteration it has just enqueued: the kernels read the pool size from device memory and size-check
@@ -1563,6 +1615,35 @@ int rt_scene_light_tree_dump(const RtSceneDesc* desc, void* nodes, uint64_t cap_
     if (slot_member) std::memcpy(slot_member, cs.light_slot_member.data(), n * 4);
     if (p) std::memcpy(p, cs.light_p.data(), n * 4);
     if (cdf) std::memcpy(cdf, cs.light_cdf.data(), n * 4);
+    return RT_OK;
+}
+
+int rt_camera_lists_host(const RtSceneDesc* desc, const RtCamera* cam, uint32_t width, uint32_t height, uint32_t* lists, uint64_t cap_words, uint64_t* out_n_squares) {
+    if (!desc || !cam || !out_n_squares) return set_err(nullptr, RT_ERR_INVALID, "null argument");
+    *out_n_squares = 0;
+    if (width < 2u || height < 2u || width > 65536u || height > 65536u) return set_err(nullptr, RT_ERR_INVALID, "width and height must be in 2..65536");
+    rtc::CompiledScene cs;
+    const int rc = rtc::compile_scene(*desc, cs);
+    if (rc != RT_OK) return set_err(nullptr, rc, "scene: " + cs.error);
+    const std::vector<uint32_t> order = camera_order(cs);
+    if (order.empty() || !camera_is_finite(cam)) return RT_OK;                 // a scene or camera the lists do not serve: no squares
+    const rtcl::Camera c = camera_lists_camera(cam, width, height);
+    const uint32_t sqx = rtcl::squares_x(width), n = sqx * rtcl::squares_y(height);
+    *out_n_squares = n;
+    if (!lists) return RT_OK;
+    if (cap_words < (uint64_t)n * rtcl::kListWords) return set_err(nullptr, RT_ERR_INVALID, "capacity too small");
+    for (uint32_t i = 0; i < n; ++i) rtcl::build_list(c, i % sqx, i / sqx, &cs.spheres[0].x, order.data(), (uint32_t)order.size(), lists + (size_t)i * rtcl::kListWords);
+    return RT_OK;
+}
+
+int rt_camera_lists_last(RtCtx* ctx, uint32_t* lists, uint64_t cap_words, uint64_t* out_n_squares) {
+    if (!ctx || !out_n_squares) return set_err(ctx, RT_ERR_INVALID, "null argument");
+    *out_n_squares = ctx->cam_squares;
+    if (!lists || ctx->cam_squares == 0u) return RT_OK;
+    if (cap_words < (uint64_t)ctx->cam_squares * rtcl::kListWords) return set_err(ctx, RT_ERR_INVALID, "capacity too small");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(lists, ctx->cam_lists.p, (size_t)ctx->cam_squares * rtcl::kListWords * 4u, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 

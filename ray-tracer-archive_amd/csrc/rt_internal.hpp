@@ -57,6 +57,7 @@ struct RtCtx {
     rti::DevBuf denoise_planes;                  // rt_denoise_device: per-pixel mean and variance of the mean, three float2 planes (denoise.hip)
     rti::DevBuf denoise_guide;                   // rt_denoise_guided_device: per pixel one 16-byte record of 8 binary16 guide components (denoise.hip);
                                                  // rt_denoise_guided_moments_device: those, then per pixel one 8-byte record of the standard errors
+    rti::DevBuf cam_lists; uint32_t cam_squares = 0;   // the camera lists of the last render (csrc/camera_lists.h); cam_squares = 0: it built none
     uint32_t fail_renders = 0;                   // rt_test_fail_next_renders: renders still to fail (fault injection for the failure-path tests)
 };
 
@@ -66,6 +67,7 @@ struct RtScene {
     rti::DevBuf sphere_src, moving_src, rect_src, tri_src;   // ray queries: the RtHittable record of every primitive (no render kernel reads them)
     rtk::SceneDev dev{};
     rtk::RaySrcDev src{};
+    rti::DevBuf cam_order; uint32_t n_cam_order = 0;   // camera lists: the tree's spheres in leaf order (rt_api.cpp camera_order); 0: the lists do not serve this scene
     uint32_t features = 0; bool in_lds = false;
     uint32_t first_id = 0; float first_prim[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the ONE sphere or rect every walk tests first (hit id; centre + radius, or the rect's two records), first_id = 0: none or several
     int bg_mode = 0; float bg[3] = {0, 0, 0};
