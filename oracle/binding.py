@@ -54,6 +54,17 @@ def lib():
         u32p = C.POINTER(C.c_uint32)
         L.orc_render_paths.restype = C.c_int
         L.orc_render_paths.argtypes = [vp, vp, vp, C.POINTER(OrcOpts), C.c_int32, C.POINTER(C.c_int32), f64p, f64p, u32p, u32p, u32p, f64p, f64p, C.POINTER(OrcStats)]
+        u64p = C.POINTER(C.c_uint64)
+        L.orc_render_paths_ex.restype = C.c_int
+        L.orc_render_paths_ex.argtypes = [vp, vp, vp, C.POINTER(OrcOpts), vp, C.c_uint64, C.c_int32, C.POINTER(C.c_int32), f64p, f64p, u32p, u32p, u64p,
+                                          f64p, f64p, f64p, f64p, f64p, C.POINTER(OrcStats)]
+        L.orc_world_hit_many_ex.restype = C.c_int
+        L.orc_world_hit_many_ex.argtypes = [vp, vp, C.c_uint64, C.c_uint64, f64p, f64p, f64p, C.c_double, f64p, C.c_double, C.c_int, f64p, C.POINTER(C.c_uint8)]
+        f32p = C.POINTER(C.c_float)
+        L.orc_sample_lights.restype = C.c_int
+        L.orc_sample_lights.argtypes = [vp, C.c_uint64, f32p, u64p, f32p, C.c_int, f64p, f64p, C.POINTER(C.c_int32), u32p, f64p, f64p]
+        L.orc_light_weights.restype = C.c_int
+        L.orc_light_weights.argtypes = [vp, f32p, f32p, C.c_uint64]
         L.orc_render_crops.restype = C.c_int
         L.orc_render_crops.argtypes = [vp, vp, vp, C.POINTER(OrcOpts), C.c_int32, C.POINTER(C.c_int32), f64p, C.POINTER(OrcStats)]
         L.orc_render_reference_shaped.restype = C.c_int
@@ -122,15 +133,23 @@ EVENT_NAMES = ["lambertian_cosine_only", "lambertian_light_xz_rect", "lambertian
                "dielectric_refract", "dielectric_reflect_schlick", "dielectric_reflect_cannot_refract", "dielectric_back_face", "isotropic",
                "medium_scattered", "medium_passed", "tex_solid", "tex_checker", "tex_noise", "tex_image", "tex_empty_image",
                "hit_sphere", "hit_moving_sphere", "hit_rect", "hit_triangle", "hit_box_side", "under_translate", "under_rotate_y", "under_flip_face",
-               "lens_offset", "time"]
+               "lens_offset", "time",
+               # RtSceneDesc.scene_flags and triangle attributes (bits 27 .. 34: the mask is 64 bits wide)
+               "lambertian_light_xy_yz_rect", "lambertian_light_triangle", "lambertian_light_box", "lambertian_light_wrapped", "lambertian_light_cdf_pick",
+               "normal_interpolated", "normal_fallback", "uv_interpolated"]
 EVENTS = {n: 1 << k for k, n in enumerate(EVENT_NAMES)}
 TERM_MISS, TERM_EMITTER_FRONT, TERM_EMITTER_BACK, TERM_DEPTH, TERM_NONFINITE = range(5)
 
 
-def render_paths(desc, cam, params, precision=64, n_threads=1, rect=None, count=False, r_ulps=0, signs=(1, 1, 1)):
-    """render(..., per_sample=True) with every sample's path record. Returns a dict: radiance float64 (h,w,spp,3), segments, terminal,
-    events uint32 (h,w,spp), margin and tmin_margin float64 (h,w,spp), rgb_sum (H,W,3), stats. r_ulps > 0: every traced ray's direction is rounded to
-    f32 and moved by signs[c] * r_ulps f32 ulps per component."""
+def _attrs(attrs):
+    return (attrs, len(attrs)) if attrs is not None and len(attrs) else (None, 0)
+
+
+def render_paths(desc, cam, params, precision=64, n_threads=1, rect=None, count=False, r_ulps=0, signs=(1, 1, 1), attrs=None):
+    """render(..., per_sample=True) with every sample's path record. Returns a dict: radiance float64 (h,w,spp,3), segments, terminal uint32,
+    events uint64 (h,w,spp), margin, tmin_margin, light_edge, light_cos and normal_margin float64 (h,w,spp), rgb_sum (H,W,3), stats. r_ulps > 0:
+    every traced ray's direction is rounded to f32 and moved by signs[c] * r_ulps f32 ulps per component. attrs: the RtTriangleAttrs array that
+    travels beside the desc (None: none)."""
     L = lib()
     H, W, spp = params.height, params.width, params.samples_per_pixel
     x0, y0, x1, y1 = rect if rect else (0, 0, W, H)
@@ -138,16 +157,20 @@ def render_paths(desc, cam, params, precision=64, n_threads=1, rect=None, count=
     out = np.zeros((H, W, 3), dtype=np.float64)
     shape = (y1 - y0, x1 - x0, spp)
     ps = np.zeros(shape + (3,), dtype=np.float64)
-    seg, term, ev = (np.zeros(shape, dtype=np.uint32) for _ in range(3))
-    margin, tmin = np.zeros(shape, dtype=np.float64), np.zeros(shape, dtype=np.float64)
+    seg, term = (np.zeros(shape, dtype=np.uint32) for _ in range(2))
+    ev = np.zeros(shape, dtype=np.uint64)
+    margin, tmin, ledge, lcos, nmargin = (np.zeros(shape, dtype=np.float64) for _ in range(5))
     st = OrcStats()
     f64p, u32p = C.POINTER(C.c_double), C.POINTER(C.c_uint32)
-    rc = L.orc_render_paths(C.byref(desc), C.byref(cam), C.byref(params), C.byref(opts), int(r_ulps), (C.c_int32 * 3)(*[int(v) for v in signs]),
-                            out.ctypes.data_as(f64p), ps.ctypes.data_as(f64p), seg.ctypes.data_as(u32p), term.ctypes.data_as(u32p), ev.ctypes.data_as(u32p),
-                            margin.ctypes.data_as(f64p), tmin.ctypes.data_as(f64p), C.byref(st))
+    a, na = _attrs(attrs)
+    rc = L.orc_render_paths_ex(C.byref(desc), C.byref(cam), C.byref(params), C.byref(opts), a, na, int(r_ulps), (C.c_int32 * 3)(*[int(v) for v in signs]),
+                               out.ctypes.data_as(f64p), ps.ctypes.data_as(f64p), seg.ctypes.data_as(u32p), term.ctypes.data_as(u32p),
+                               ev.ctypes.data_as(C.POINTER(C.c_uint64)), margin.ctypes.data_as(f64p), tmin.ctypes.data_as(f64p), ledge.ctypes.data_as(f64p),
+                               lcos.ctypes.data_as(f64p), nmargin.ctypes.data_as(f64p), C.byref(st))
     if rc != 0:
         raise RuntimeError("oracle: " + L.orc_last_error().decode())
-    return dict(radiance=ps, segments=seg, terminal=term, events=ev, margin=margin, tmin_margin=tmin, rgb_sum=out, stats=st.as_dict())
+    return dict(radiance=ps, segments=seg, terminal=term, events=ev, margin=margin, tmin_margin=tmin, light_edge=ledge, light_cos=lcos,
+                normal_margin=nmargin, rgb_sum=out, stats=st.as_dict())
 
 
 def render_crops(desc, cam, params, rects, precision=64, n_threads=1, count=False):
@@ -211,10 +234,10 @@ def world_hit(desc, o, d, tm=0.0, t_min=0.001, t_max=float("inf")):
     return hit_out(n, buf)
 
 
-def world_hit_many(desc, o, d, tm, t_min=0.001, t_max=float("inf"), precision=64):
+def world_hit_many(desc, o, d, tm, t_min=0.001, t_max=float("inf"), precision=64, attrs=None):
     """world.hit for n rays with one scene build: o, d (n, 3), tm (n,), t_max a scalar or (n,). Returns (hit bool (n,), rec float64 (n, 10):
     t, p, normal, u, v, front_face as orc_world_hit writes them; rows of misses are 0). precision 64 gives world_hit's bits; 32 runs the
-    checker's f32 instance."""
+    checker's f32 instance. attrs: RtTriangleAttrs records (normal, u, v, front_face of a hit on such a triangle are the interpolated ones)."""
     o, d = np.ascontiguousarray(o, dtype=np.float64).reshape(-1, 3), np.ascontiguousarray(d, dtype=np.float64).reshape(-1, 3)
     n = len(o)
     tm = np.ascontiguousarray(np.broadcast_to(np.asarray(tm, dtype=np.float64), (n,)))
@@ -227,7 +250,8 @@ def world_hit_many(desc, o, d, tm, t_min=0.001, t_max=float("inf"), precision=64
             raise ValueError("t_max must be a scalar or hold one value per ray")
     rec, hit = np.zeros((n, 10), dtype=np.float64), np.zeros(n, dtype=np.uint8)
     f64p = C.POINTER(C.c_double)
-    rc = lib().orc_world_hit_many(C.byref(desc), n, o.ctypes.data_as(f64p), d.ctypes.data_as(f64p), tm.ctypes.data_as(f64p), float(t_min),
+    a, na = _attrs(attrs)
+    rc = lib().orc_world_hit_many_ex(C.byref(desc), a, na, n, o.ctypes.data_as(f64p), d.ctypes.data_as(f64p), tm.ctypes.data_as(f64p), float(t_min),
                                   per_ray.ctypes.data_as(f64p) if per_ray is not None else None, float(t_max) if per_ray is None else 0.0, int(precision),
                                   rec.ctypes.data_as(f64p), hit.ctypes.data_as(C.POINTER(C.c_uint8)))
     if rc != 0:
@@ -242,3 +266,30 @@ def rng_stream(seed, pixel_index, sample_index, n):
     lib().orc_rng_stream(seed, pixel_index, sample_index, n, raw.ctypes.data_as(C.POINTER(C.c_uint64)), f64.ctypes.data_as(C.POINTER(C.c_double)),
                          f32.ctypes.data_as(C.POINTER(C.c_float)))
     return raw, f64, f32
+
+
+def sample_lights(desc, points, states=None, dirs=None, precision=64):
+    """The lights list of a scene with scene_flags set, queried as rt_sample_lights queries it (points f32 (n, 3), states uint64 (n)), or, with
+    `dirs`, its pdf of given directions. Returns dict(d float64 (n, 3), pdf float64 (n), light int32 (n), n_draws uint32 (n), light_edge, light_cos float64 (n): render_paths'
+    margins of the same names for the one evaluation of the list's pdf)."""
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    n = len(pts)
+    st = None if states is None else np.ascontiguousarray(states, dtype=np.uint64).reshape(-1)
+    dd = None if dirs is None else np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    d, pdf, light, draws, edge, cosine = np.zeros((n, 3)), np.zeros(n), np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n), np.zeros(n)
+    f32p, f64p = C.POINTER(C.c_float), C.POINTER(C.c_double)
+    rc = lib().orc_sample_lights(C.byref(desc), n, pts.ctypes.data_as(f32p), None if st is None else st.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                 None if dd is None else dd.ctypes.data_as(f32p), int(precision), d.ctypes.data_as(f64p), pdf.ctypes.data_as(f64p),
+                                 light.ctypes.data_as(C.POINTER(C.c_int32)), draws.ctypes.data_as(C.POINTER(C.c_uint32)), edge.ctypes.data_as(f64p), cosine.ctypes.data_as(f64p))
+    if rc != 0:
+        raise RuntimeError("oracle: " + lib().orc_last_error().decode())
+    return dict(d=d, pdf=pdf, light=light, n_draws=draws, light_edge=edge, light_cos=cosine)
+
+
+def light_weights(desc, cap=1 << 16):
+    """(p, cdf) float32 by member: the weighted pick of RT_SCENE_LIGHTS_MANY as the checker builds it."""
+    p, cdf = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+    n = lib().orc_light_weights(C.byref(desc), p.ctypes.data_as(C.POINTER(C.c_float)), cdf.ctypes.data_as(C.POINTER(C.c_float)), cap)
+    if n < 0:
+        raise RuntimeError("oracle: " + lib().orc_last_error().decode())
+    return p[:n].copy(), cdf[:n].copy()

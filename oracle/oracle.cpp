@@ -26,7 +26,10 @@
 //     (constant_medium.rs:31-71, material.rs:193-220) under the live scatter signature; the
 //     medium's free-path draw is keyed by (path, segment, medium) instead of taken from the
 //     sequential stream so that closest-hit does not depend on list order;
-//   - Triangle and the book-1 sky gradient do not exist in the reference and are defined here.
+//   - Triangle and the book-1 sky gradient do not exist in the reference and are defined here;
+//   - RtSceneDesc.scene_flags (lights of every shape, the area-weighted pick) and triangle attributes (per-vertex normals and uv) do not
+//     exist in the reference either: LightList and Triangle::hit restate include/rt_hip.h's statement of them, not the kernels' text. With
+//     scene_flags == 0 and no attributes every entry point computes what it computed before they were added.
 //
 // Build: make -C oracle   (g++ -O2 -ffp-contract=off, see Makefile)
 
@@ -83,20 +86,30 @@ enum { PT_SPHERE = 0, PT_MOVING = 1, PT_RECT = 2, PT_TRI = 3, PT_MEDIUM = 4, PT_
 // Path records (orc_render_paths): which branch every segment of a path took, how it ended, and how closely its random-number
 // thresholds were decided. Filled only where Ctx::path / Rng::margin are set; null on every other entry point, whose arithmetic they
 // do not touch.
-enum : uint32_t {
+enum : uint64_t {
     EV_LAMB_COSINE_ONLY = 1u << 0, EV_LAMB_LIGHT_XZRECT = 1u << 1, EV_LAMB_LIGHT_SPHERE = 1u << 2, EV_LAMB_MIX_COSINE = 1u << 3,
     EV_METAL = 1u << 4, EV_DIEL_REFRACT = 1u << 5, EV_DIEL_REFLECT_SCHLICK = 1u << 6, EV_DIEL_REFLECT_TIR = 1u << 7, EV_DIEL_BACK_FACE = 1u << 8,
     EV_ISOTROPIC = 1u << 9, EV_MEDIUM_SCATTERED = 1u << 10, EV_MEDIUM_PASSED = 1u << 11,
     EV_TEX_SOLID = 1u << 12, EV_TEX_CHECKER = 1u << 13, EV_TEX_NOISE = 1u << 14, EV_TEX_IMAGE = 1u << 15, EV_TEX_EMPTY_IMAGE = 1u << 16,
     EV_HIT_SPHERE = 1u << 17, EV_HIT_MOVING = 1u << 18, EV_HIT_RECT = 1u << 19, EV_HIT_TRI = 1u << 20, EV_HIT_BOX_SIDE = 1u << 21,
-    EV_UNDER_TRANSLATE = 1u << 22, EV_UNDER_ROTATE_Y = 1u << 23, EV_UNDER_FLIP_FACE = 1u << 24, EV_LENS = 1u << 25, EV_TIME = 1u << 26
+    EV_UNDER_TRANSLATE = 1u << 22, EV_UNDER_ROTATE_Y = 1u << 23, EV_UNDER_FLIP_FACE = 1u << 24, EV_LENS = 1u << 25, EV_TIME = 1u << 26,
+    // RtSceneDesc.scene_flags and triangle attributes (rt_hip.h): the light half drew from an XY or YZ rect, a triangle, a box, a member under a
+    // wrapper chain; the pick was the area-weighted one; a hit used an interpolated normal, kept the geometric one because the vertex normals
+    // cancelled, used an interpolated uv
+    EV_LAMB_LIGHT_XY_YZ_RECT = 1ull << 27, EV_LAMB_LIGHT_TRI = 1ull << 28, EV_LAMB_LIGHT_BOX = 1ull << 29, EV_LAMB_LIGHT_WRAPPED = 1ull << 30,
+    EV_LAMB_LIGHT_CDF_PICK = 1ull << 31, EV_NORMAL_INTERP = 1ull << 32, EV_NORMAL_FALLBACK = 1ull << 33, EV_UV_INTERP = 1ull << 34
 };
 enum : uint32_t { TERM_MISS = 0, TERM_EMITTER_FRONT = 1, TERM_EMITTER_BACK = 2, TERM_DEPTH = 3, TERM_NONFINITE = 4 };
 struct PathRec {
-    uint32_t events = 0, terminal = TERM_MISS;
+    uint64_t events = 0; uint32_t terminal = TERM_MISS;
     double margin = std::numeric_limits<double>::infinity();   // smallest distance by which a random-number threshold was decided
     double tmin_margin = std::numeric_limits<double>::infinity();   // smallest |root - t_min| * |d . n| of a primitive test: how far along the
                                                                     // normal the ray's origin would have to move to carry a root across t_min
+    // list-pdf evaluations against a light of a kind the reference has not (rt_hip.h RT_SCENE_LIGHTS_ALL_SHAPES): the smallest distance of a
+    // crossing from the member's edge (rects: scene units; triangles: barycentrics; near misses count) and the smallest |cos| at a member met
+    double light_edge = std::numeric_limits<double>::infinity(), light_cos = std::numeric_limits<double>::infinity();
+    // RT_TRI_NORMALS: smallest | |sum|^2 - FLT_MIN | / (largest term)^2 over the interpolated normals of the path
+    double normal_margin = std::numeric_limits<double>::infinity();
     int r_ulps = 0; int sign[3] = {1, 1, 1};                   // perturbation of every traced ray's direction (0: none)
 };
 
@@ -113,7 +126,8 @@ template <class R> struct Rng {
     void decided_by(double d) { if (margin && d < *margin) *margin = d; }
     void root_at(double root, double t_min, double d_dot_n) { if (tmin) { double m = std::fabs(root - t_min) * std::fabs(d_dot_n); if (m < *tmin) *tmin = m; } }
     uint64_t next64() { state += GAMMA; if (cnt) cnt->draws++; return fin(state); }
-    R random_double() { return Uni<R>::cv(next64()); }                                    // rt_weekend.rs:8-11
+    bool u24 = false;           // orc_sample_lights: every uniform is the device's 24-bit one, at either precision
+    R random_double() { const uint64_t z = next64(); return u24 ? (R)Uni<float>::cv(z) : Uni<R>::cv(z); }   // rt_weekend.rs:8-11
     R random_double_range(R lo, R hi) { return lo + (hi - lo) * random_double(); }        // rt_weekend.rs:13-15
     uint32_t random_int(uint32_t lo, uint32_t hi) {                                       // rt_weekend.rs:16-19
         return lo + (uint32_t)std::floor(random_double() * (R)(hi - lo + 1));
@@ -261,16 +275,16 @@ template <class R> struct Aabb {
 // ------------------------------------------------------------------------------------------------
 template <class R> struct Texture {
     virtual ~Texture() {}
-    virtual Vec3<R> value(R u, R v, const Vec3<R>& p, uint32_t* ev = nullptr) const = 0;   // texture.rs:7-9 (ev: a path record's event mask, or null)
+    virtual Vec3<R> value(R u, R v, const Vec3<R>& p, uint64_t* ev = nullptr) const = 0;   // texture.rs:7-9 (ev: a path record's event mask, or null)
 };
 template <class R> struct SolidColor : Texture<R> {               // texture.rs:34-38
     Vec3<R> c;
     explicit SolidColor(const Vec3<R>& c_) : c(c_) {}
-    Vec3<R> value(R, R, const Vec3<R>&, uint32_t* ev) const override { if (ev) *ev |= EV_TEX_SOLID; return c; }
+    Vec3<R> value(R, R, const Vec3<R>&, uint64_t* ev) const override { if (ev) *ev |= EV_TEX_SOLID; return c; }
 };
 template <class R> struct CheckerTexture : Texture<R> {           // texture.rs:60-69
     std::shared_ptr<Texture<R>> even, odd;
-    Vec3<R> value(R u, R v, const Vec3<R>& p, uint32_t* ev) const override {
+    Vec3<R> value(R u, R v, const Vec3<R>& p, uint64_t* ev) const override {
         if (ev) *ev |= EV_TEX_CHECKER;
         R sines = std::sin((R)10 * p.x()) * std::sin((R)10 * p.y()) * std::sin((R)10 * p.z());
         return sines < (R)0 ? odd->value(u, v, p, ev) : even->value(u, v, p, ev);
@@ -319,7 +333,7 @@ template <class R> struct Perlin {                                 // perlin.rs
 };
 template <class R> struct NoiseTexture : Texture<R> {             // texture.rs:90-96
     std::shared_ptr<Perlin<R>> noise; R scale = 1;
-    Vec3<R> value(R, R, const Vec3<R>& p, uint32_t* ev) const override {
+    Vec3<R> value(R, R, const Vec3<R>& p, uint64_t* ev) const override {
         if (ev) *ev |= EV_TEX_NOISE;
         return Vec3<R>(1, 1, 1) * (R)0.5 * ((R)1 + std::sin(scale * p.z() + (R)10 * noise->turb(p)));
     }
@@ -327,7 +341,7 @@ template <class R> struct NoiseTexture : Texture<R> {             // texture.rs:
 template <class R> static R clamp(R x, R lo, R hi) { return x < lo ? lo : (x > hi ? hi : x); }   // rt_weekend.rs:21-29
 template <class R> struct ImageTexture : Texture<R> {             // texture.rs:117-140
     std::vector<uint8_t> data; uint32_t width = 0, height = 0;
-    Vec3<R> value(R u, R v, const Vec3<R>&, uint32_t* ev) const override {
+    Vec3<R> value(R u, R v, const Vec3<R>&, uint64_t* ev) const override {
         if (ev) *ev |= data.empty() ? EV_TEX_EMPTY_IMAGE : EV_TEX_IMAGE;
         if (data.empty()) return Vec3<R>(0, 1, 1);
         u = clamp(u, (R)0, (R)1);
@@ -347,7 +361,7 @@ template <class R> struct ImageTexture : Texture<R> {             // texture.rs:
 template <class R> struct Material;
 template <class R> struct HitRecord {                             // hittable.rs:11-19
     Vec3<R> p, normal; const Material<R>* mat_ptr = nullptr; R t = 0, u = 0, v = 0; bool front_face = false;
-    uint32_t tags = 0;   // EV_HIT_* of the primitive, EV_UNDER_* of the wrappers above it, EV_MEDIUM_SCATTERED (path records only)
+    uint64_t tags = 0;   // EV_HIT_* of the primitive, EV_UNDER_* of the wrappers above it, EV_MEDIUM_SCATTERED (path records only)
     void set_face_normal(const Ray<R>& r, const Vec3<R>& outward_normal) {   // hittable.rs:41-48
         front_face = dot(r.dir, outward_normal) < (R)0;
         normal = front_face ? outward_normal : -outward_normal;
@@ -357,8 +371,8 @@ template <class R> struct HitRecord {                             // hittable.rs
 // What the reference reads from thread-local state: the RNG; plus our counters.
 template <class R> struct Ctx {
     Rng<R>* rng; Counters* cnt; int order; PathRec* path;   // path: null unless a path record is being filled
-    void ev(uint32_t bits) { if (path) path->events |= bits; }
-    uint32_t* evp() { return path ? &path->events : nullptr; }
+    void ev(uint64_t bits) { if (path) path->events |= bits; }
+    uint64_t* evp() { return path ? &path->events : nullptr; }
 };
 
 template <class R> struct Hittable {                              // hittable.rs:51-60
@@ -673,6 +687,7 @@ template <class R> inline bool tri_close_edges(R nd, R n1, R n2, R ntv, R inv, R
 }
 template <class R> struct Triangle : Hittable<R> {
     Vec3<R> v0, v1, v2; const Material<R>* mp = nullptr;
+    uint32_t aflags = 0; Vec3<R> vn[3]; R uv[3][2] = {{0, 0}, {0, 0}, {0, 0}};   // RtTriangleAttrs: flags, unit vertex normals (f32 values), uv
     bool hit(const Ray<R>& r, R t_min, R t_max, HitRecord<R>& rec, Ctx<R>& cx) const override {
         if (cx.cnt) cx.cnt->prim_tests[PT_TRI]++;
         Vec3<R> e1 = v1 - v0, e2 = v2 - v0;
@@ -691,9 +706,30 @@ template <class R> struct Triangle : Hittable<R> {
         if (t < t_min || t > t_max || !std::isfinite(t)) return false;
         rec.t = t; rec.u = u; rec.v = v;
         rec.p = r.at(t);
-        rec.set_face_normal(r, cross(e1, e2).unit());
-        rec.mat_ptr = mp;
         rec.tags = EV_HIT_TRI;
+        Vec3<R> outward = cross(e1, e2).unit();
+        // rt_hip.h "triangle attributes": (u, v) are the barycentrics after the closed-edge clamp
+        if (aflags & RT_TRI_NORMALS) {
+            const R w0 = (R)1 - u - v;
+            const Vec3<R> a = w0 * vn[0], b = u * vn[1], c = v * vn[2];
+            const Vec3<R> s = a + b + c;
+            const R l2 = s.length_squared();
+            // "not a positive normal f32 number": below FLT_MIN (zero, subnormal, negative cannot be), infinite or NaN
+            const bool usable = l2 >= (R)1.17549435e-38f && l2 < std::numeric_limits<R>::infinity();
+            if (usable) { outward = s.unit(); rec.tags |= EV_NORMAL_INTERP; } else rec.tags |= EV_NORMAL_FALLBACK;
+            if (cx.path) {
+                const double big = std::max((double)a.length_squared(), std::max((double)b.length_squared(), (double)c.length_squared()));
+                const double m = std::fabs((double)l2 - 1.17549435e-38) / big;
+                if (!(m >= cx.path->normal_margin)) cx.path->normal_margin = m;   // (a NaN margin sticks: undecidable)
+            }
+        }
+        if (aflags & RT_TRI_UVS) {
+            rec.u = uv[0][0] + u * (uv[1][0] - uv[0][0]) + v * (uv[2][0] - uv[0][0]);
+            rec.v = uv[0][1] + u * (uv[1][1] - uv[0][1]) + v * (uv[2][1] - uv[0][1]);
+            rec.tags |= EV_UV_INTERP;
+        }
+        rec.set_face_normal(r, outward);
+        rec.mat_ptr = mp;
         return true;
     }
     bool bounding_box(R, R, Aabb<R>& out) const override {
@@ -831,6 +867,152 @@ template <class R> struct FlipFace : Hittable<R> {
         return true;
     }
     bool bounding_box(R t0, R t1, Aabb<R>& out) const override { return ptr->bounding_box(t0, t1, out); }
+};
+
+// ------------------------------------------------------------------------------------------------
+// RtSceneDesc.scene_flags (rt_hip.h): the lights list of a scene with RT_SCENE_LIGHTS_ALL_SHAPES, and with RT_SCENE_LIGHTS_MANY. NOT in the
+// reference, which samples XzRect and Sphere only; restated from the header. A member is one shape and one rigid map, the composition of the
+// wrapper chain above it, as the upload makes them: the shape's parameters and the map's sine, cosine and offset are the desc's f64 values
+// rounded to f32 (at either precision: it is the upload's rule, as for the vertex normals), the areas of the weighted pick are the desc's own
+// f64. The member's hit test is the walk's own (AARect, Triangle with its closed edges, Sphere). With MANY the checker builds no tree: the
+// list's pdf is the plain sum over all members, so a member the device's tree culls wrongly shows as a wrong sample.
+// ------------------------------------------------------------------------------------------------
+enum { LX_RECT = 0, LX_TRI = 1, LX_BOX = 2, LX_SPHERE = 3 };
+template <class R> struct LightX {
+    int kind = LX_RECT; bool wrapped = false, has_xform = false; R sin_t = 0, cos_t = 1; Vec3<R> off;
+    double area = 0; float p_k = 0, cdf_k = 0;
+    AARect<R> rect; Triangle<R> tri; Sphere<R> sph; R box[6] = {0, 0, 0, 0, 0, 0};   // box: x0 x1 y0 y1 z0 z1
+    // side s of the box in boxes.rs order (z1 z0 y1 y0 x1 x0)
+    AARect<R> side(int s) const {
+        AARect<R> q; q.box_side = true;
+        q.kaxis = s < 2 ? 2 : (s < 4 ? 1 : 0);
+        q.a0 = s < 4 ? box[0] : box[2]; q.a1 = s < 4 ? box[1] : box[3];
+        q.b0 = s < 2 ? box[2] : box[4]; q.b1 = s < 2 ? box[3] : box[5];
+        q.k = s == 0 ? box[5] : s == 1 ? box[4] : s == 2 ? box[3] : s == 3 ? box[2] : s == 4 ? box[1] : box[0];
+        return q;
+    }
+    bool new_kind() const { return kind == LX_TRI || kind == LX_BOX || (kind == LX_RECT && (rect.kaxis != 1 || wrapped)) || (kind == LX_SPHERE && wrapped); }
+    Vec3<R> to_local_point(const Vec3<R>& o) const {
+        if (!has_xform) return o;
+        const Vec3<R> m = o - off;
+        return Vec3<R>(cos_t * m.x() - sin_t * m.z(), m.y(), sin_t * m.x() + cos_t * m.z());
+    }
+    Vec3<R> to_local_dir(const Vec3<R>& v) const { return has_xform ? Vec3<R>(cos_t * v.x() - sin_t * v.z(), v.y(), sin_t * v.x() + cos_t * v.z()) : v; }
+    Vec3<R> dir_back(const Vec3<R>& d) const { return has_xform ? Vec3<R>(cos_t * d.x() + sin_t * d.z(), d.y(), -sin_t * d.x() + cos_t * d.z()) : d; }
+};
+constexpr double kLightNear = 1e-4;   // a crossing this close to a member's edge is recorded even where it misses (tests/lights_cases.py EDGE_MIN)
+template <class R> static void light_margins(Ctx<R>& cx, bool record, double edge, double cosine) {
+    if (!record || !cx.path) return;
+    if (edge < cx.path->light_edge) cx.path->light_edge = edge;
+    if (cosine < cx.path->light_cos) cx.path->light_cos = cosine;
+}
+// aarect.rs:107-117 for every orientation: pdf = t^2 |v|^2 / (|cos| area)
+template <class R> static R rectx_pdf_value(const AARect<R>& q, const Vec3<R>& o, const Vec3<R>& v, Ctx<R>& cx, bool record) {
+    const R inf = std::numeric_limits<R>::infinity();
+    if (record && cx.path) {
+        int ia, ib; q.axes(ia, ib);
+        const double t = ((double)q.k - (double)o.e[q.kaxis]) / (double)v.e[q.kaxis];
+        if (!(t < 0.001) && std::isfinite(t)) {
+            const double a = (double)o.e[ia] + t * (double)v.e[ia], b = (double)o.e[ib] + t * (double)v.e[ib];
+            if (a > (double)q.a0 - kLightNear && a < (double)q.a1 + kLightNear && b > (double)q.b0 - kLightNear && b < (double)q.b1 + kLightNear)
+                light_margins(cx, true, std::min(std::min(std::fabs(a - (double)q.a0), std::fabs((double)q.a1 - a)), std::min(std::fabs(b - (double)q.b0), std::fabs((double)q.b1 - b))), inf);
+        }
+    }
+    HitRecord<R> rec;
+    if (!q.hit(Ray<R>(o, v, 0), (R)0.001, inf, rec, cx)) return 0;
+    const R area = (q.a1 - q.a0) * (q.b1 - q.b0);
+    const R distance_squared = rec.t * rec.t * v.length_squared();
+    const R cosine = std::fabs(dot(v, rec.normal) / v.length());
+    light_margins(cx, record, inf, (double)cosine);
+    return distance_squared / cosine / area;
+}
+template <class R> static R trix_pdf_value(const Triangle<R>& tr, const Vec3<R>& o, const Vec3<R>& v, Ctx<R>& cx, bool record) {
+    const R inf = std::numeric_limits<R>::infinity();
+    const Vec3<R> e1 = tr.v1 - tr.v0, e2 = tr.v2 - tr.v0;
+    if (record && cx.path) {   // how far the crossing lies from the lines that decide hit or miss: the edges, and the edges moved out by the f32 rule's own bound
+        const Vec3<R> pv = cross(v, e2), tv = o - tr.v0, qv = cross(tv, e1);
+        const double det = (double)dot(e1, pv);
+        if (det != 0.0) {
+            const double inv = 1.0 / det, u = (double)dot(tv, pv) * inv, w = (double)dot(v, qv) * inv, t = (double)dot(e2, qv) * inv;
+            if (!(t < 0.001) && std::isfinite(t)) {
+                const double s = (double)norm1(v) * ((double)norm1(e2) * ((double)norm1(tv) + (double)norm1(e1)) + (double)norm1(tv) * (double)norm1(e1));
+                const double tol = std::min(8.0 * 5.9604644775390625e-8 * (s * std::fabs(inv) + 1.0), (double)kTriSlackMax<R>);
+                if (u > -tol - kLightNear && w > -tol - kLightNear && u + w < 1.0 + kLightNear + tol) {
+                    double edge = std::min(std::min(std::fabs(u), std::fabs(w)), std::fabs(1.0 - (u + w)));
+                    edge = std::min(edge, std::min(std::min(std::fabs(u + tol), std::fabs(w + tol)), std::fabs(1.0 + tol - (u + w))));
+                    // between an edge and the edge moved out by the f32 bound the closed-edge rule answers by precision (the walk's bound is
+                    // that of its own arithmetic): a hit in f32, a miss in f64, however far from both lines
+                    const bool outside = u < 0.0 || w < 0.0 || u + w > 1.0;
+                    if (outside && u >= -tol && w >= -tol && u + w <= 1.0 + tol) edge = 0.0;
+                    light_margins(cx, true, edge, inf);
+                }
+            }
+        }
+    }
+    HitRecord<R> rec;
+    if (!tr.hit(Ray<R>(o, v, 0), (R)0.001, inf, rec, cx)) return 0;
+    const Vec3<R> nn = cross(e1, e2);
+    const R ln = nn.length();
+    const R distance_squared = rec.t * rec.t * v.length_squared();
+    const R cosine = std::fabs(dot(v, nn) / (v.length() * ln));
+    light_margins(cx, record, inf, (double)cosine);
+    return distance_squared / cosine / ((R)0.5 * ln);
+}
+template <class R> static Vec3<R> rectx_random(const AARect<R>& q, const Vec3<R>& o, Ctx<R>& cx) {   // aarect.rs:118-125 for every orientation
+    const R ra = cx.rng->random_double_range(q.a0, q.a1);
+    const R rb = cx.rng->random_double_range(q.b0, q.b1);
+    return (q.kaxis == 0 ? Vec3<R>(q.k, ra, rb) : q.kaxis == 1 ? Vec3<R>(ra, q.k, rb) : Vec3<R>(ra, rb, q.k)) - o;
+}
+template <class R> struct LightList : Hittable<R> {
+    std::vector<LightX<R>> members; bool many = false;
+    bool hit(const Ray<R>&, R, R, HitRecord<R>&, Ctx<R>&) const override { return false; }   // the list is sampled, never traced
+    bool bounding_box(R, R, Aabb<R>&) const override { return false; }
+    R member_pdf(const LightX<R>& l, const Vec3<R>& ow, const Vec3<R>& vw, Ctx<R>& cx) const {
+        const Vec3<R> o = l.to_local_point(ow), v = l.to_local_dir(vw);
+        const bool record = l.new_kind();
+        if (l.kind == LX_RECT) return rectx_pdf_value(l.rect, o, v, cx, record);
+        if (l.kind == LX_TRI) return trix_pdf_value(l.tri, o, v, cx, record);
+        if (l.kind == LX_BOX) {                                  // the list rule (hittable_list.rs:73-80) over the box's own sides
+            R sum = 0;
+            for (int s = 0; s < 6; ++s) sum += ((R)1 / (R)6) * rectx_pdf_value(l.side(s), o, v, cx, record);
+            return sum;
+        }
+        return l.sph.pdf_value(o, v, cx);
+    }
+    Vec3<R> member_random(const LightX<R>& l, const Vec3<R>& ow, Ctx<R>& cx) const {
+        const Vec3<R> o = l.to_local_point(ow);
+        Vec3<R> d;
+        if (l.wrapped) cx.ev(EV_LAMB_LIGHT_WRAPPED);
+        if (l.kind == LX_RECT) { cx.ev(l.rect.kaxis == 1 ? EV_LAMB_LIGHT_XZRECT : EV_LAMB_LIGHT_XY_YZ_RECT); d = rectx_random(l.rect, o, cx); }
+        else if (l.kind == LX_TRI) {
+            cx.ev(EV_LAMB_LIGHT_TRI);
+            const R r1 = cx.rng->random_double(), r2 = cx.rng->random_double();
+            const R s = std::sqrt(r1);
+            d = (((R)1 - s) * l.tri.v0 + (s * ((R)1 - r2)) * l.tri.v1 + (s * r2) * l.tri.v2) - o;
+        } else if (l.kind == LX_BOX) {
+            cx.ev(EV_LAMB_LIGHT_BOX);
+            const int s = (int)(cx.rng->random_usize() % 6ull);   // hittable_list.rs:81-84 over the sides
+            d = rectx_random(l.side(s), o, cx);
+        } else d = l.sph.random(o, cx);
+        return l.dir_back(d);
+    }
+    R pdf_value(const Vec3<R>& o, const Vec3<R>& v, Ctx<R>& cx) const override {
+        const R weight = (R)1 / (R)members.size(); R sum = 0;
+        for (const LightX<R>& l : members) sum += (many ? (R)l.p_k : weight) * member_pdf(l, o, v, cx);
+        return sum;
+    }
+    // the pick: next64() % n, or with MANY one draw and the first member whose cdf exceeds it. That draw is the device's 24-bit uniform at
+    // either precision: the pick is a look-up in an f32 table, not arithmetic that precision 64 refines.
+    size_t pick(Ctx<R>& cx) const {
+        if (!many) return (size_t)(cx.rng->random_usize() % (uint64_t)members.size());
+        cx.ev(EV_LAMB_LIGHT_CDF_PICK);
+        const float u = Uni<float>::cv(cx.rng->next64());
+        size_t k = 0;
+        while (k + 1 < members.size() && !(members[k].cdf_k > u)) ++k;
+        for (size_t j = 0; j + 1 < members.size(); ++j) cx.rng->decided_by(std::fabs((double)u - (double)members[j].cdf_k));
+        return k;
+    }
+    Vec3<R> random(const Vec3<R>& o, Ctx<R>& cx) const override { return member_random(members[pick(cx)], o, cx); }
 };
 
 // constant_medium.rs:31-71 (commented-out spec)
@@ -1000,7 +1182,11 @@ template <class R> struct Scene {
             q->a0 = (R)p[0]; q->a1 = (R)p[1]; q->b0 = (R)p[2]; q->b1 = (R)p[3]; q->k = (R)p[4]; q->mp = mat(d, h.material);
             out = std::move(q); break;
         }
-        case RT_HIT_TRIANGLE: { auto t = std::make_unique<Triangle<R>>(); t->v0 = V<R>(p); t->v1 = V<R>(p + 3); t->v2 = V<R>(p + 6); t->mp = mat(d, h.material); out = std::move(t); break; }
+        case RT_HIT_TRIANGLE: {
+            auto t = std::make_unique<Triangle<R>>(); t->v0 = V<R>(p); t->v1 = V<R>(p + 3); t->v2 = V<R>(p + 6); t->mp = mat(d, h.material);
+            if (!attr_of.empty() && attr_of[id] >= 0) set_attrs(*t, tri_attrs[attr_of[id]]);
+            out = std::move(t); break;
+        }
         case RT_HIT_BOX: out = std::make_unique<BoxObj<R>>(V<R>(p), V<R>(p + 3), mat(d, h.material)); break;
         case RT_HIT_LIST: { auto l = std::make_unique<HittableList<R>>(); children(l->objects); out = std::move(l); break; }
         case RT_HIT_BVH: {
@@ -1029,8 +1215,120 @@ template <class R> struct Scene {
         return by_id[id];
     }
 
-    bool load(const RtSceneDesc& d) {
+    // ---- triangle attributes (rt_hip.h RtTriangleAttrs): checked as the upload checks them, then read where the triangle is built ----
+    const RtTriangleAttrs* tri_attrs = nullptr; std::vector<int64_t> attr_of;   // hittable id -> index into tri_attrs, or -1
+    bool check_attrs(const RtSceneDesc& d, const RtTriangleAttrs* attrs, uint64_t n) {
+        if (n == 0) return true;
+        if (!attrs) { error = "n_triangle_attrs > 0 with a NULL pointer"; return false; }
+        tri_attrs = attrs; attr_of.assign(d.n_hittables, -1);
+        for (uint64_t i = 0; i < n; ++i) {
+            const RtTriangleAttrs& a = attrs[i];
+            if (a.hittable < 0 || (uint64_t)a.hittable >= d.n_hittables || d.hittables[a.hittable].kind != RT_HIT_TRIANGLE) { error = "triangle attributes: not an RT_HIT_TRIANGLE"; return false; }
+            if (attr_of[a.hittable] >= 0) { error = "triangle attributes: an id listed twice"; return false; }
+            if (a.flags & ~(uint32_t)(RT_TRI_NORMALS | RT_TRI_UVS)) { error = "triangle attributes: unknown flag bit"; return false; }
+            for (int v = 0; v < 3; ++v) {
+                if (a.flags & RT_TRI_NORMALS) {
+                    const double l2 = (double)a.n[v][0] * a.n[v][0] + (double)a.n[v][1] * a.n[v][1] + (double)a.n[v][2] * a.n[v][2];
+                    if (!std::isfinite(l2)) { error = "triangle attributes: a non-finite normal"; return false; }
+                    if (l2 == 0.0) { error = "triangle attributes: a vertex normal of zero length"; return false; }
+                }
+                if ((a.flags & RT_TRI_UVS) && !(std::isfinite(a.uv[v][0]) && std::isfinite(a.uv[v][1]))) { error = "triangle attributes: a non-finite uv"; return false; }
+            }
+            attr_of[a.hittable] = (int64_t)i;
+        }
+        return true;
+    }
+    static void set_attrs(Triangle<R>& t, const RtTriangleAttrs& a) {
+        t.aflags = a.flags;
+        for (int v = 0; v < 3; ++v) {
+            if (a.flags & RT_TRI_NORMALS) {   // made unit in f64, then rounded to f32: the upload's rule, at either precision
+                const double x = a.n[v][0], y = a.n[v][1], z = a.n[v][2], l = std::sqrt(x * x + y * y + z * z);
+                t.vn[v] = Vec3<R>((R)(float)(x / l), (R)(float)(y / l), (R)(float)(z / l));
+            }
+            t.uv[v][0] = (R)a.uv[v][0]; t.uv[v][1] = (R)a.uv[v][1];
+        }
+    }
+
+    // ---- the lights list under RtSceneDesc.scene_flags: one LightX per member, or an error for what the header says is refused ----
+    static R f32(double x) { return (R)(float)x; }
+    const Hittable<R>* build_lights(const RtSceneDesc& d) {
+        if (d.lights < 0 || (uint64_t)d.lights >= d.n_hittables) { error = "bad lights id"; return nullptr; }
+        auto list = std::make_unique<LightList<R>>();
+        list->many = (d.scene_flags & RT_SCENE_LIGHTS_MANY) != 0;
+        const RtHittable& L = d.hittables[d.lights];
+        std::vector<int32_t> ids;
+        if (L.kind == RT_HIT_LIST) {
+            for (int c = 0; c < L.n_children; ++c) {
+                const uint64_t ci = (uint64_t)L.first_child + c;
+                if (ci >= d.n_children) { error = "children out of range"; return nullptr; }
+                ids.push_back(d.children[ci]);
+            }
+        } else ids.push_back(d.lights);
+        if (ids.empty()) { error = "an empty lights list"; return nullptr; }
+        for (int32_t hid : ids) {
+            if (hid < 0 || (uint64_t)hid >= d.n_hittables) { error = "bad hittable id"; return nullptr; }
+            const RtHittable* h = &d.hittables[hid];
+            double theta = 0.0, off[3] = {0, 0, 0}; int ops = 0; bool identity = true;
+            while (h->kind == RT_HIT_TRANSLATE || h->kind == RT_HIT_ROTATE_Y || h->kind == RT_HIT_FLIP_FACE) {
+                if (h->kind == RT_HIT_TRANSLATE) {                  // the offset, turned into the frame of the rotations above it
+                    const double s = std::sin(theta), k = std::cos(theta);
+                    const double x = off[0] + k * h->p[0] + s * h->p[2], y = off[1] + h->p[1], z = off[2] - s * h->p[0] + k * h->p[2];
+                    off[0] = x; off[1] = y; off[2] = z; identity = false;
+                } else if (h->kind == RT_HIT_ROTATE_Y) { theta += h->p[0] * 3.14159265358979323846264338327950288 / 180.0; identity = false; }
+                if (++ops > 6) { error = "lights list: a chain of more than 6 wrappers"; return nullptr; }
+                if (h->first_child < 0 || (uint64_t)h->first_child >= d.n_hittables) { error = "bad hittable id"; return nullptr; }
+                h = &d.hittables[h->first_child];
+            }
+            LightX<R> l; const double* p = h->p;
+            switch (h->kind) {
+            case RT_HIT_XY_RECT: case RT_HIT_XZ_RECT: case RT_HIT_YZ_RECT:
+                if ((p[1] - p[0]) * (p[3] - p[2]) == 0.0) { error = "lights list: a rect of zero area"; return nullptr; }
+                l.kind = LX_RECT; l.rect.kaxis = h->kind == RT_HIT_XY_RECT ? 2 : (h->kind == RT_HIT_XZ_RECT ? 1 : 0);
+                l.rect.a0 = f32(p[0]); l.rect.a1 = f32(p[1]); l.rect.b0 = f32(p[2]); l.rect.b1 = f32(p[3]); l.rect.k = f32(p[4]);
+                l.area = std::fabs((p[1] - p[0]) * (p[3] - p[2]));
+                break;
+            case RT_HIT_TRIANGLE: {
+                const Vec3<double> a(p[3] - p[0], p[4] - p[1], p[5] - p[2]), b(p[6] - p[0], p[7] - p[1], p[8] - p[2]), n = cross(a, b);
+                if (n.x() == 0.0 && n.y() == 0.0 && n.z() == 0.0) { error = "lights list: a triangle of zero area"; return nullptr; }
+                l.kind = LX_TRI; l.tri.v0 = Vec3<R>(f32(p[0]), f32(p[1]), f32(p[2])); l.tri.v1 = Vec3<R>(f32(p[3]), f32(p[4]), f32(p[5])); l.tri.v2 = Vec3<R>(f32(p[6]), f32(p[7]), f32(p[8]));
+                l.area = 0.5 * std::sqrt(n.length_squared());
+                break;
+            }
+            case RT_HIT_BOX: {
+                const double dx = std::fabs(p[3] - p[0]), dy = std::fabs(p[4] - p[1]), dz = std::fabs(p[5] - p[2]);
+                if (dx == 0.0 || dy == 0.0 || dz == 0.0) { error = "lights list: a box with sides of zero area"; return nullptr; }
+                l.kind = LX_BOX; l.box[0] = f32(p[0]); l.box[1] = f32(p[3]); l.box[2] = f32(p[1]); l.box[3] = f32(p[4]); l.box[4] = f32(p[2]); l.box[5] = f32(p[5]);
+                l.area = 2.0 * (dx * dy + dy * dz + dz * dx);
+                break;
+            }
+            case RT_HIT_SPHERE:
+                l.kind = LX_SPHERE; l.sph.center = Vec3<R>(f32(p[0]), f32(p[1]), f32(p[2])); l.sph.radius = f32(p[3]);
+                l.area = 4.0 * 3.14159265358979323846264338327950288 * p[3] * p[3];
+                break;
+            default: error = "lights list: a member that cannot be sampled as a light"; return nullptr;
+            }
+            l.wrapped = ops > 0; l.has_xform = !identity;
+            l.sin_t = f32(std::sin(theta)); l.cos_t = f32(std::cos(theta)); l.off = Vec3<R>(f32(off[0]), f32(off[1]), f32(off[2]));
+            list->members.push_back(std::move(l));
+        }
+        if (list->many) {   // rt_hip.h PICK: sequential f64 sums in list order, each quotient cast to float, the last cdf entry exactly 1
+            double total = 0.0;
+            for (const LightX<R>& l : list->members) total += l.area;
+            if (!(total > 0.0 && std::isfinite(total))) { error = "lights list: the total area is not a positive finite number"; return nullptr; }
+            double run = 0.0;
+            for (LightX<R>& l : list->members) { run += l.area; l.p_k = (float)(l.area / total); l.cdf_k = (float)(run / total); }
+            list->members.back().cdf_k = 1.0f;
+        }
+        const Hittable<R>* out = list.get();
+        pool.push_back(std::move(list));
+        return out;
+    }
+
+    bool load(const RtSceneDesc& d, const RtTriangleAttrs* attrs = nullptr, uint64_t n_attrs = 0) {
         if (d.abi_version != RT_ABI_VERSION) { error = "abi version mismatch"; return false; }
+        if (d.scene_flags & ~(uint32_t)(RT_SCENE_LIGHTS_ALL_SHAPES | RT_SCENE_LIGHTS_MANY)) { error = "scene_flags: unknown bit"; return false; }
+        if ((d.scene_flags & RT_SCENE_LIGHTS_MANY) && !(d.scene_flags & RT_SCENE_LIGHTS_ALL_SHAPES)) { error = "scene_flags: RT_SCENE_LIGHTS_MANY needs RT_SCENE_LIGHTS_ALL_SHAPES"; return false; }
+        if (!check_attrs(d, attrs, n_attrs)) return false;
         for (uint64_t i = 0; i < d.n_perlins; ++i) {
             auto pl = std::make_shared<Perlin<R>>();
             for (int k = 0; k < 256; ++k) {
@@ -1054,7 +1352,7 @@ template <class R> struct Scene {
         }
         by_id.assign(d.n_hittables, nullptr);
         world = build(d, d.world);
-        if (d.lights >= 0) lights = build(d, d.lights);
+        if (d.lights >= 0) { lights = d.scene_flags ? build_lights(d) : build(d, d.lights); if (!lights) return false; }
         background_mode = d.background_mode; background = V<R>(d.background);
         return world != nullptr && error.empty();
     }
@@ -1173,7 +1471,8 @@ static Camera<R> camera_from(const RtCamera* cam_d) {
 // The sample loop main.rs:731-784 over the pixel rectangle [x0,x1) x [y0,y1). `compact`: rgb_sum holds the rectangle
 // only (row-major, (y1-y0) x (x1-x0) x 3) instead of the whole H x W frame.
 // Where orc_render_paths wants its per-sample records: arrays of [n_pixels_in_rect][spp], and the perturbation of every traced ray.
-struct PathOut { uint32_t* segments; uint32_t* terminal; uint32_t* events; double* margin; double* tmin_margin; int r_ulps; int sign[3]; };
+struct PathOut { uint32_t* segments; uint32_t* terminal; uint64_t* events; double* margin; double* tmin_margin; int r_ulps; int sign[3];
+                 double* light_edge; double* light_cos; double* normal_margin; };   // the last three: or null
 
 template <class R>
 static int render_rect(const Scene<R>& sc, const Camera<R>& cam, const RtParams* prm, int nt, bool count, int x0, int y0, int x1, int y1, bool compact,
@@ -1214,6 +1513,9 @@ static int render_rect(const Scene<R>& sc, const Camera<R>& cam, const RtParams*
                     if (po) {
                         size_t k = ((size_t)(y - y0) * (size_t)(x1 - x0) + (size_t)(x - x0)) * spp + s;
                         po->segments[k] = g.segment; po->terminal[k] = finite ? pr.terminal : TERM_NONFINITE; po->events[k] = pr.events; po->margin[k] = pr.margin; po->tmin_margin[k] = pr.tmin_margin;
+                        if (po->light_edge) po->light_edge[k] = pr.light_edge;
+                        if (po->light_cos) po->light_cos[k] = pr.light_cos;
+                        if (po->normal_margin) po->normal_margin[k] = pr.normal_margin;
                     }
                 }
                 double* o = compact ? rgb_sum + ((size_t)(y - y0) * (size_t)(x1 - x0) + (size_t)(x - x0)) * 3 : rgb_sum + ((size_t)y * W + x) * 3;
@@ -1236,9 +1538,9 @@ static int render_rect(const Scene<R>& sc, const Camera<R>& cam, const RtParams*
 
 template <class R>
 static int render_t(const RtSceneDesc* desc, const RtCamera* cam_d, const RtParams* prm, const OrcOpts* opt, double* rgb_sum, OrcStats* st,
-                    double* per_sample, const PathOut* po = nullptr) {
+                    double* per_sample, const PathOut* po = nullptr, const RtTriangleAttrs* attrs = nullptr, uint64_t n_attrs = 0) {
     Scene<R> sc;
-    if (!sc.load(*desc)) { g_err = "scene: " + sc.error; return -1; }
+    if (!sc.load(*desc, attrs, n_attrs)) { g_err = "scene: " + sc.error; return -1; }
     const Camera<R> cam = camera_from<R>(cam_d);
     int x0 = opt->x0, y0 = opt->y0, x1 = opt->x1, y1 = opt->y1;
     if (x1 <= x0 || y1 <= y0) { x0 = 0; y0 = 0; x1 = (int)prm->width; y1 = (int)prm->height; }
@@ -1317,9 +1619,9 @@ static int render_crops_t(const RtSceneDesc* desc, const RtCamera* cam_d, const 
 // world.hit for a list of rays with ONE scene build (orc_world_hit builds per call: 8 s for 1,536 rays of a 2,650-primitive scene).
 template <class R>
 static int world_hit_many(const RtSceneDesc* desc, uint64_t n, const double* o, const double* d, const double* tm, double t_min, const double* t_max,
-                          double t_max_all, double* out10, uint8_t* hit) {
+                          double t_max_all, double* out10, uint8_t* hit, const RtTriangleAttrs* attrs = nullptr, uint64_t n_attrs = 0) {
     Scene<R> sc;
-    if (!sc.load(*desc)) { g_err = "scene: " + sc.error; return -1; }
+    if (!sc.load(*desc, attrs, n_attrs)) { g_err = "scene: " + sc.error; return -1; }
     for (uint64_t i = 0; i < n; ++i) {
         Rng<R> g; Ctx<R> cx{&g, nullptr, 0, nullptr};                        // per ray, as orc_world_hit makes them
         HitRecord<R> rec;
@@ -1329,6 +1631,31 @@ static int world_hit_many(const RtSceneDesc* desc, uint64_t n, const double* o, 
         double* q = out10 + 10 * i;
         q[0] = (double)rec.t; for (int a = 0; a < 3; ++a) { q[1 + a] = (double)rec.p.e[a]; q[4 + a] = (double)rec.normal.e[a]; }
         q[7] = (double)rec.u; q[8] = (double)rec.v; q[9] = rec.front_face ? 1.0 : 0.0;
+    }
+    return 0;
+}
+
+template <class R>
+static int sample_lights(const RtSceneDesc* desc, uint64_t n, const float* points, const uint64_t* states, const float* dirs, double* d3, double* pdf,
+                         int32_t* light, uint32_t* n_draws, double* edge, double* cosine) {
+    Scene<R> sc;
+    if (!sc.load(*desc)) { g_err = "scene: " + sc.error; return -1; }
+    const auto* list = dynamic_cast<const LightList<R>*>(sc.lights);
+    if (!list) { g_err = "no lights list"; return -1; }
+    for (uint64_t i = 0; i < n; ++i) {
+        Counters cnt;
+        Rng<R> g; g.u24 = true; g.cnt = &cnt; if (states) { g.state = states[i]; g.base = states[i]; }
+        PathRec pr;
+        Ctx<R> cx{&g, nullptr, 0, &pr};
+        const Vec3<R> o((R)points[3 * i], (R)points[3 * i + 1], (R)points[3 * i + 2]);
+        Vec3<R> d;
+        if (dirs) { d = Vec3<R>((R)dirs[3 * i], (R)dirs[3 * i + 1], (R)dirs[3 * i + 2]); light[i] = -1; }
+        else { const size_t k = list->pick(cx); light[i] = (int32_t)k; d = list->member_random(list->members[k], o, cx); }
+        n_draws[i] = (uint32_t)cnt.draws;
+        pdf[i] = (double)list->pdf_value(o, d, cx);
+        for (int a = 0; a < 3; ++a) d3[3 * i + a] = (double)d.e[a];
+        if (edge) edge[i] = pr.light_edge;
+        if (cosine) cosine[i] = pr.light_cos;
     }
     return 0;
 }
@@ -1364,10 +1691,33 @@ int orc_render_paths(const RtSceneDesc* desc, const RtCamera* cam, const RtParam
     if (!desc || !cam || !prm || !opt || !rgb_sum || !per_sample || !segments || !terminal || !events || !margin || !tmin_margin || (r_ulps > 0 && !sign3) || r_ulps < 0) {
         g_err = "null argument"; return -1;
     }
-    orc::PathOut po{segments, terminal, events, margin, tmin_margin, r_ulps, {1, 1, 1}};
+    int x0 = opt->x0, y0 = opt->y0, x1 = opt->x1, y1 = opt->y1;
+    if (x1 <= x0 || y1 <= y0) { x0 = 0; y0 = 0; x1 = (int)prm->width; y1 = (int)prm->height; }
+    std::vector<uint64_t> wide((size_t)std::max(0, x1 - x0) * (size_t)std::max(0, y1 - y0) * prm->samples_per_pixel);
+    orc::PathOut po{segments, terminal, wide.data(), margin, tmin_margin, r_ulps, {1, 1, 1}, nullptr, nullptr, nullptr};
     if (r_ulps > 0) for (int c = 0; c < 3; ++c) po.sign[c] = sign3[c] < 0 ? -1 : 1;
-    if (opt->precision == 32) return orc::render_t<float>(desc, cam, prm, opt, rgb_sum, st, per_sample, &po);
-    return orc::render_t<double>(desc, cam, prm, opt, rgb_sum, st, per_sample, &po);
+    const int rc = opt->precision == 32 ? orc::render_t<float>(desc, cam, prm, opt, rgb_sum, st, per_sample, &po)
+                                        : orc::render_t<double>(desc, cam, prm, opt, rgb_sum, st, per_sample, &po);
+    if (rc == 0) for (size_t k = 0; k < wide.size(); ++k) events[k] = (uint32_t)wide[k];   // the bits this entry point has always had
+    return rc;
+}
+
+/* orc_render_paths for scenes with RtSceneDesc.scene_flags and triangle attributes (attrs: the RtTriangleAttrs array that travels beside the
+ * desc, or NULL with n_attrs 0). events is 64 bits wide (bits 27 and up: oracle/binding.py names them). Three more margins per sample:
+ * light_edge / light_cos: over the list-pdf evaluations against lights of a kind the reference has not, the smallest distance of a crossing
+ * from the member's edge (rects: scene units, triangles: barycentrics; near misses count) and the smallest |cos| at a member that is met;
+ * normal_margin: over the interpolated normals, the smallest | |sum|^2 - FLT_MIN | / (largest term)^2. inf where nothing was recorded. */
+int orc_render_paths_ex(const RtSceneDesc* desc, const RtCamera* cam, const RtParams* prm, const OrcOpts* opt, const RtTriangleAttrs* attrs, uint64_t n_attrs,
+                        int32_t r_ulps, const int32_t* sign3, double* rgb_sum, double* per_sample, uint32_t* segments, uint32_t* terminal, uint64_t* events,
+                        double* margin, double* tmin_margin, double* light_edge, double* light_cos, double* normal_margin, OrcStats* st) {
+    if (!desc || !cam || !prm || !opt || !rgb_sum || !per_sample || !segments || !terminal || !events || !margin || !tmin_margin || !light_edge || !light_cos ||
+        !normal_margin || (r_ulps > 0 && !sign3) || r_ulps < 0) {
+        g_err = "null argument"; return -1;
+    }
+    orc::PathOut po{segments, terminal, events, margin, tmin_margin, r_ulps, {1, 1, 1}, light_edge, light_cos, normal_margin};
+    if (r_ulps > 0) for (int c = 0; c < 3; ++c) po.sign[c] = sign3[c] < 0 ? -1 : 1;
+    if (opt->precision == 32) return orc::render_t<float>(desc, cam, prm, opt, rgb_sum, st, per_sample, &po, attrs, n_attrs);
+    return orc::render_t<double>(desc, cam, prm, opt, rgb_sum, st, per_sample, &po, attrs, n_attrs);
 }
 
 /* n_rects rectangles (x0, y0, x1, y1 each) of one frame, scene built once; out = the rectangles back to back (compact). */
@@ -1478,6 +1828,37 @@ int orc_world_hit_many(const RtSceneDesc* desc, uint64_t n, const double* o, con
     if (precision != 64 && precision != 32) { g_err = "precision must be 64 or 32"; return -1; }
     return precision == 64 ? orc::world_hit_many<double>(desc, n, o, d, tm, t_min, t_max, t_max_all, out10, hit)
                            : orc::world_hit_many<float>(desc, n, o, d, tm, t_min, t_max, t_max_all, out10, hit);
+}
+/* orc_world_hit_many with triangle attributes: normal, u, v and front_face of a hit on a triangle that carries some are the interpolated ones */
+int orc_world_hit_many_ex(const RtSceneDesc* desc, const RtTriangleAttrs* attrs, uint64_t n_attrs, uint64_t n, const double* o, const double* d, const double* tm,
+                          double t_min, const double* t_max, double t_max_all, int precision, double* out10, uint8_t* hit) {
+    if (!desc || (n && (!o || !d || !tm || !out10 || !hit))) { g_err = "null argument"; return -1; }
+    if (precision != 64 && precision != 32) { g_err = "precision must be 64 or 32"; return -1; }
+    return precision == 64 ? orc::world_hit_many<double>(desc, n, o, d, tm, t_min, t_max, t_max_all, out10, hit, attrs, n_attrs)
+                           : orc::world_hit_many<float>(desc, n, o, d, tm, t_min, t_max, t_max_all, out10, hit, attrs, n_attrs);
+}
+/* The lights list of a scene with scene_flags set, queried as rt_sample_lights queries it: for point i (f32) and generator state i one pick,
+ * the picked member's draw and the list's pdf of the drawn direction; with dirs (f32, n x 3) the list's pdf of the given directions and no
+ * draw (light -1). Every uniform is the device's 24-bit one at either precision. d (n x 3) and pdf are widened to f64. edge, cosine (or NULL):
+ * the margins orc_render_paths_ex calls light_edge and light_cos, for the one evaluation of the list's pdf. */
+int orc_sample_lights(const RtSceneDesc* desc, uint64_t n, const float* points, const uint64_t* states, const float* dirs, int precision, double* d3, double* pdf,
+                      int32_t* light, uint32_t* n_draws, double* edge, double* cosine) {
+    if (!desc || (n && (!points || (!states && !dirs) || !d3 || !pdf || !light || !n_draws))) { g_err = "null argument"; return -1; }
+    if (precision != 64 && precision != 32) { g_err = "precision must be 64 or 32"; return -1; }
+    if (!desc->scene_flags || desc->lights < 0) { g_err = "orc_sample_lights needs a lights list and scene_flags"; return -1; }
+    return precision == 64 ? orc::sample_lights<double>(desc, n, points, states, dirs, d3, pdf, light, n_draws, edge, cosine)
+                           : orc::sample_lights<float>(desc, n, points, states, dirs, d3, pdf, light, n_draws, edge, cosine);
+}
+/* p and cdf of the weighted pick (RT_SCENE_LIGHTS_MANY), by member in list order; returns the number of members, or -1 */
+int orc_light_weights(const RtSceneDesc* desc, float* p, float* cdf, uint64_t cap) {
+    if (!desc || !p || !cdf) { g_err = "null argument"; return -1; }
+    orc::Scene<double> sc;
+    if (!sc.load(*desc)) { g_err = "scene: " + sc.error; return -1; }
+    const auto* list = dynamic_cast<const orc::LightList<double>*>(sc.lights);
+    if (!list || !list->many) { g_err = "not a scene with RT_SCENE_LIGHTS_MANY"; return -1; }
+    if (list->members.size() > cap) { g_err = "cap too small"; return -1; }
+    for (size_t k = 0; k < list->members.size(); ++k) { p[k] = list->members[k].p_k; cdf[k] = list->members[k].cdf_k; }
+    return (int)list->members.size();
 }
 /* texture value of texture `id` of a scene, f64 */
 int orc_texture_value(const RtSceneDesc* desc, int id, double u, double v, const double* p, double* out3) {

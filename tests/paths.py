@@ -28,6 +28,23 @@ case; 3e-5 for |oc| = 10 and r = 0.2, the limits of these scenes), which moves t
 exit. The margin is that displacement; 6e-5 is twice the largest delta. (The device's sphere_fast and start-primitive rules, DESIGN.md
 section 2, remove this error; the f32 checker, which stands in for the device on the CPU, has it.)
 
+RtSceneDesc.scene_flags and triangle attributes (include/rt_hip.h) add three margins, each recorded by the checker at precision 64:
+  * LIGHT_EDGE_MARGIN = 1e-4 and LIGHT_COS_MARGIN = 1e-2, the thresholds tests/lights_cases.py uses for single queries. MixturePdf::value is
+    called with the direction that was drawn, not with the perturbed one the next segment traces, so the +-R-ulp runs do not see the list's
+    pdf jump where that direction passes the edge of a light it does not reach (an occluded one, or one behind the light it was drawn
+    from). Every evaluation of the list's pdf against a member of a kind the reference has not (XY and YZ rects, triangles, boxes, anything
+    under a wrapper chain) records how far its crossing with the member's plane lies from the member's edge (rects: scene units; triangles:
+    barycentrics; near misses count) and |cos| at a member it meets: pdf = t^2 |v|^2 / (|cos| area) loses 1 / |cos| of its digits. A
+    crossing between a triangle's edge and that edge moved out by the f32 closed-edge bound (oracle.cpp tri_close_edges with the device's
+    unit roundoff) records 0: there the rule answers by precision, a hit in f32 and a miss in f64. The reference's own bare XZ rect and
+    sphere lights keep the rule they had.
+  * the weighted pick of RT_SCENE_LIGHTS_MANY records min_k |u - cdf_k| into the same margin as the other draws (DRAW_MARGIN).
+  * NORMAL_MARGIN = 1e-8: an interpolated normal records | |s|^2 - FLT_MIN | / max_i |w_i n_i|^2 for s = w0 n0 + bu n1 + bv n2. Each
+    component of s carries 3 roundings of terms no larger than the largest: |ds| <= 3 * 2^-24 max|w_i n_i| in f32, so the DIRECTION of
+    unit(s) is off by 1.8e-7 / (|s| / max|w_i n_i|); at a ratio of 1e-4 (1e-8 squared) that is 1.8e-3 rad, beyond SPREAD, and the +-R-ulp
+    runs, which move (bu, bv) and not the rounding of the sum, need not show it. Below it, and on the line itself, which side of FLT_MIN
+    the squared length falls is an accident of the arithmetic.
+
 R: rays.py derives 64 ulps from the device's sphere discriminant for |oc| / (4 r) up to 31. The probe scenes keep everything within about
 10 units of the origin and radii >= 0.2, so |oc| / (4 r) <= 12.5 < 31: the same R covers them with more room."""
 import os
@@ -42,6 +59,8 @@ R_ULPS = RAYS.R_ULPS
 SIGNS = RAYS.SIGNS
 DRAW_MARGIN = 1e-5
 TMIN_MARGIN = 6e-5
+LIGHT_EDGE_MARGIN, LIGHT_COS_MARGIN = 1e-4, 1e-2      # tests/lights_cases.py EDGE_MIN, COS_MIN
+NORMAL_MARGIN = 1e-8
 SPREAD = 1e-3
 CAP = 0.05
 COVERAGE = 50                 # decidable samples that must carry each required event bit (at max_depth 8)
@@ -55,19 +74,53 @@ FORMS = ("own", "all")
 # variants are in SCENES below and test_paths_host.py checks them against what the library reports.
 F_MOVING, F_RECT, F_TRI, F_MEDIUM, F_XFORM, F_TEX, F_LIGHTS, F_ALL = 1, 2, 4, 8, 16, 32, 64, 127
 VARIANT_SETS = (("0", 0), ("mesh", F_RECT | F_TRI), ("box", F_RECT | F_XFORM | F_LIGHTS), ("all", F_ALL))
+# ... and the kernels that rebuild a HitRecord and shade have six more instances (with_record_variant, with_shade_variant): triangle attributes
+# (128) on the mesh set or the full one; extended light records (256: RT_SCENE_LIGHTS_ALL_SHAPES with a member of a new kind, or
+# RT_SCENE_LIGHTS_MANY) and the light tree (512: RT_SCENE_LIGHTS_MANY) always on the full one, each without and with attributes.
+F_TRI_ATTR, F_LIGHTS_EXT, F_LIGHTS_TREE = 128, 256, 512
+NEW_INSTANCES = ("mesh+attr", "all+attr", "all+lx", "all+attr+lx", "all+lt", "all+attr+lt")
 
 
-def variant_of(pkg, desc):
-    need = pkg.compile_info(desc)["features"]
-    for name, have in VARIANT_SETS:
-        if need & ~have == 0:
-            return name
-    raise AssertionError(need)
+def features_of(pkg, built):
+    return pkg.compile_info(built.desc, **(dict(triangle_attrs=built.attrs) if built.attrs is not None else {}))["features"]
+
+
+def variant_of(pkg, built):
+    need = features_of(pkg, built)
+    assert need & ~(F_ALL | F_TRI_ATTR | F_LIGHTS_EXT | F_LIGHTS_TREE) == 0 and (not need & F_LIGHTS_TREE or need & F_LIGHTS_EXT), need
+    name = "all" if need & F_LIGHTS_EXT else next(n for n, have in VARIANT_SETS if need & F_ALL & ~have == 0)
+    if need & F_TRI_ATTR:
+        name = ("all" if name != "mesh" else "mesh") + "+attr"
+    return name + ("+lt" if need & F_LIGHTS_TREE else "+lx" if need & F_LIGHTS_EXT else "")
 
 
 class Built:
-    def __init__(self, desc, cam, keep):
-        self.desc, self.cam, self.keep = desc, cam, keep
+    def __init__(self, desc, cam, keep, attrs=None):
+        self.desc, self.cam, self.keep, self.attrs = desc, cam, keep, attrs      # attrs: the RtTriangleAttrs array that travels beside the desc, or None
+
+
+def _ico(pkg, b, centre, radius, mat, subdivisions=1):
+    """mesh.icosphere about `centre` with sphere normals and the sphere's own (u, v) at its vertices; returns the triangles' ids"""
+    tris, nrm = pkg.icosphere(subdivisions)
+    uv = pkg.sphere_uv(nrm)
+    return [b.triangle(*(radius * tris[k] + np.asarray(centre, float)), mat, normals=nrm[k], uvs=uv[k]) for k in range(len(tris))]
+
+
+def _lamp_members(pkg, b, lamp):
+    """The lights list of `lights_many`: a quad of 2 x 2 at y = 3.2 as 4 x 4 graded cells (32 triangles, areas 0.005 to 0.68), a small sphere
+    (2.0), a large box (15.5) and a YZ rect under Translate(RotateY(..)): p_k from 2e-4 to 0.7.
+    The sphere's radius is 0.4, the bulbs' of the older scenes, and no less: sphere.rs:75-84 forms pdf = 1 / (2 pi (1 - cos_max)) with
+    cos_max = sqrt(1 - r^2 / d^2), and 1 - cos_max = r^2 / (2 d^2) keeps an absolute error of an ulp of 1 (two roundings at 1, 2^-24 each) —
+    a relative one of 2^-23 * 2 d^2 / r^2 in f32: 5e-5 at d = 6 for r = 0.4, which the older scenes' figures show, and 2e-4 for r = 0.2.
+    (The first device run of this scene had r = 0.2: one decidable sample of smooth_lit, (y, x, s) = (14, 4, 4) at depth 8, whose direction
+    met that sphere 3.5 units away, stood 9.8e-5 of its radiance from the f64 checker where the f32 checker stands 2.6e-5 from it — neither
+    wrong, both within that bound — and the scene's 101 sphere samples had not shown the f32 checker's own tail.)"""
+    import lights_many_cases as LM
+    out = [b.triangle(*t, lamp) for t in LM.graded_lamp_triangles(cells=4, y=3.2)]
+    out.append(b.sphere((2.8, 1.9, 1.4), 0.4, lamp))
+    out.append(b.box((1.8, -0.2, -2.3), (3.6, 1.3, -0.9), lamp))
+    out.append(b.translate(b.rotate_y(b.yz_rect(0.0, 1.2, -0.6, 0.6, 0.0, lamp), 25.0), (-3.4, 0.0, -1.2)))
+    return out
 
 
 def _camera(pkg, lookfrom, lookat, vfov=40.0, aperture=0.0, t0=0.0, t1=0.0):
@@ -227,16 +280,82 @@ def build_scene(pkg, name, form):
         cam = _camera(pkg, (0, 1.5, 7), (0, 0.2, 0), 40.0, aperture=0.3, t0=0.0, t1=1.0)
         at = (2.4, 1.7, 1.0)
         own = "all"
+    elif name in ("lights_shapes", "lights_shapes_wrapped", "lights_many", "lights_many_padded", "lights_many_one", "lights_many_two", "smooth_lit", "smooth_lit_many"):
+        # RtSceneDesc.scene_flags: Lambertian receivers (a floor, a back wall, three spheres) under a lights list of the new kinds; every
+        # member is emissive and is in the world too (but the 1e-6 member of lights_many_two, which nothing could see)
+        b = pkg.SceneBuilder(background=(0.3, 0.4, 0.5))
+        lamp = b.diffuse_light((5.0, 5.0, 4.0))
+        ids = [b.xz_rect(-8, 8, -8, 8, -0.5, b.lambertian((0.6, 0.6, 0.6))), b.xy_rect(-4, 4, -0.5, 3.5, -2.5, b.lambertian((0.7, 0.5, 0.3)))]
+        if name.startswith("smooth_lit"):
+            ids.append(b.bvh(_ico(pkg, b, (0.0, 0.5, 0.2), 1.0, b.lambertian((0.8, 0.4, 0.3)))))
+        else:
+            ids += [b.sphere((-1.6 + 1.6 * k, 0.2, 0.3 * k), 0.7, b.lambertian(c)) for k, c in enumerate([(0.8, 0.3, 0.3), (0.3, 0.8, 0.3), (0.3, 0.3, 0.8)])]
+        in_world = None
+        if name == "lights_shapes":          # unequal sizes: 1.5, 2.25, 2.9, 7.6 and 2.0 square units
+            lights = [b.xy_rect(-3.2, -1.7, 1.4, 2.4, -1.2, lamp), b.yz_rect(0.4, 1.9, -1.0, 0.5, 3.3, lamp),
+                      b.triangle((-0.8, 3.0, -0.6), (1.0, 3.3, 0.2), (0.0, 2.8, 1.5), lamp), b.box((1.4, 1.6, -2.0), (2.7, 2.5, -0.8), lamp),
+                      b.sphere((2.8, 1.3, 1.2), 0.4, lamp)]
+        elif name == "lights_shapes_wrapped":
+            lights = [b.translate(b.rotate_y(b.xy_rect(-0.8, 0.7, -0.5, 0.5, 0.0, lamp), 35.0), (-0.9, 2.4, -1.7)),
+                      b.flip_face(b.translate(b.triangle((-0.8, 0.0, -0.6), (1.0, 0.3, 0.2), (0.0, -0.2, 1.5), lamp), (0.2, 3.0, 0.0))),
+                      b.rotate_y(b.box((1.7, 1.9, -1.5), (2.4, 2.4, -0.8), lamp), 20.0),
+                      b.rotate_y(b.translate(b.rotate_y(b.sphere((0.5, 0.0, 0.0), 0.4, lamp), 40.0), (-3.0, 1.6, 0.4)), -25.0),
+                      b.xz_rect(2.2, 3.4, 0.2, 1.4, 2.9, lamp)]
+        elif name == "lights_many_one":
+            lights = [b.triangle((-0.8, 3.0, -0.6), (1.0, 3.3, 0.2), (0.0, 2.8, 1.5), lamp)]
+        elif name == "lights_many_two":      # areas 4 and 4e-6: p = (1 - 1e-6, 1e-6) and cdf = (1 - 1e-6, 1) as floats
+            lights = [b.xz_rect(-1.0, 1.0, -1.0, 1.0, 3.2, lamp), b.triangle((2.0, 3.0, 0.0), (2.0 + 8.0 ** 0.5 * 1e-3, 3.0, 0.0), (2.0, 3.0, 8.0 ** 0.5 * 1e-3), lamp)]
+            in_world = lights[:1]
+        else:
+            lights = _lamp_members(pkg, b, lamp)
+        ids += lights if in_world is None else in_world
+        if name == "lights_many_padded":     # lights_many with PADDING Lambertian spheres behind the camera, which no camera ray sees (test_gpu_paths.py)
+            grey = b.lambertian((0.5, 0.5, 0.5))
+            ids += [b.sphere((x, y, z), 0.2, grey) for x, y, z in np.random.default_rng(3).uniform((-6.0, 0.0, 8.5), (6.0, 6.0, 10.5), (PADDING, 3))]
+        cam = _camera(pkg, (0.5, 2.0, 7.5), (0, 0.6, 0), 40.0)
+        at = (-2.6, 1.7, 1.0)
+        flags = dict(lights_all_shapes=True, lights_many=name.startswith("lights_many") or name == "smooth_lit_many")
+        own = {"lights_shapes": "all+lx", "lights_shapes_wrapped": "all+lx", "smooth_lit": "all+attr+lx", "smooth_lit_many": "all+attr+lt"}.get(name, "all+lt")
+    elif name == "smooth_mesh":
+        # triangle attributes on every material that reads the normal: the subdivision-1 icosphere three times, each with sphere normals and
+        # the sphere's (u, v) — Lambertian under the image texture, glass under Translate(RotateY(..)), metal under FlipFace — beside a plain
+        # triangle and one whose record has flags 0
+        b = pkg.SceneBuilder(**sky)
+        grey = b.lambertian((0.5, 0.5, 0.5))
+        plain = b.triangle((-3.4, -0.4, -1.6), (-1.6, -0.4, -2.2), (-2.6, 1.6, -1.9), b.lambertian((0.7, 0.3, 0.3)))
+        inert = b.triangle((1.4, -0.4, -2.2), (3.4, -0.4, -1.6), (2.4, 1.6, -1.9), b.lambertian((0.3, 0.7, 0.3)))
+        b.tri_attrs.append(A.RtTriangleAttrs(inert, 0))
+        ids = [b.xz_rect(-8, 8, -8, 8, -0.5, grey), plain, inert,
+               b.bvh(_ico(pkg, b, (-2.0, 0.4, 0.0), 0.9, b.lambertian(texture=b.image(_image())))),
+               b.translate(b.rotate_y(b.bvh(_ico(pkg, b, (0.0, 0.0, 0.0), 0.9, b.dielectric(1.5))), 25.0), (0.1, 0.4, 0.3)),
+               b.flip_face(b.bvh(_ico(pkg, b, (2.1, 0.4, 0.0), 0.9, b.metal((0.8, 0.8, 0.9), 0.0))))]
+        cam = _camera(pkg, (0.4, 1.6, 7), (0, 0.3, 0), 40.0)
+        at = (0.2, 2.4, 1.2)
+        own = "all+attr"
+    elif name == "smooth_cancel":
+        # vertex normals a, -a, a: the sum (w0 - bu + bv) a cancels on the line bu = 1 / 2, which runs through the middle of the frame; beside
+        # it the normal is +-a. A second triangle carries normals of lengths 3, 0.2 and 40.
+        b = pkg.SceneBuilder(**sky)
+        a = (0.2, 0.3, 1.0)
+        ids = [b.xz_rect(-8, 8, -8, 8, -0.5, b.lambertian((0.5, 0.5, 0.5))),
+               b.triangle((-2.6, -0.4, 0.0), (2.6, -0.4, 0.0), (0.0, 2.6, -0.6), b.lambertian((0.8, 0.6, 0.3)), normals=(a, tuple(-x for x in a), a)),
+               b.triangle((-3.2, -0.4, 1.6), (-1.2, -0.4, 2.0), (-2.4, 0.9, 1.4), b.lambertian((0.3, 0.5, 0.8)),
+                          normals=((0.6, 0.0, 2.94), (-0.04, 0.08, 0.18), (0.0, 16.0, 36.7)), uvs=((0.1, 0.2), (0.9, 0.3), (0.4, 0.8)))]
+        cam = _camera(pkg, (0.0, 1.4, 7), (0, 0.8, 0), 40.0)
+        at = (2.4, 1.6, 1.2)
+        own = "mesh+attr"
     else:
         raise KeyError(name)
+    if not name.startswith(("lights_shapes", "lights_many", "smooth_lit")):
+        flags = {}
     if form == "all":
         more, lamp = _cluster(pkg, b, at, 3.0 if name.startswith("wrap_") else 2.0)
         ids, lights = ids + more, lights + lamp
     elif form != "own":
         raise KeyError(form)
     world = b.hittable_list(ids) if name in ("lights_both", "wrap_translate", "media_inside") else b.bvh(ids, 0.0, 1.0)
-    desc = b.desc(world, b.hittable_list(lights) if lights else -1)
-    return Built(desc, cam, b), own
+    desc = b.desc(world, b.hittable_list(lights) if lights else -1, **flags)
+    return Built(desc, cam, b, b.triangle_attrs()), own
 
 
 # ---- scene -> the event bits it is meant to exercise: each on at least COVERAGE decidable samples at max_depth 8, in both forms ----------
@@ -266,10 +385,29 @@ REQUIRED = {
     "wrap_double_rotate": _WRAP + ["under_translate", "under_rotate_y"],
     "rotated_sphere": ["under_rotate_y", "hit_sphere", "dielectric_refract", "lambertian_cosine_only"],
     "camera": ["lens_offset", "time", "hit_moving_sphere", "metal", "lambertian_cosine_only"],
+    # RtSceneDesc.scene_flags and triangle attributes
+    "lights_shapes": ["lambertian_light_xy_yz_rect", "lambertian_light_triangle", "lambertian_light_box", "lambertian_light_sphere", "lambertian_mixture_cosine"],
+    "lights_shapes_wrapped": ["lambertian_light_wrapped", "lambertian_light_xy_yz_rect", "lambertian_light_triangle", "lambertian_light_box",
+                              "lambertian_light_sphere", "lambertian_light_xz_rect", "under_flip_face", "under_rotate_y", "under_translate"],
+    "lights_many": ["lambertian_light_cdf_pick", "lambertian_light_triangle", "lambertian_light_box", "lambertian_light_sphere", "lambertian_light_wrapped",
+                    "lambertian_mixture_cosine"],
+    "lights_many_one": ["lambertian_light_cdf_pick", "lambertian_light_triangle"],
+    "lights_many_two": ["lambertian_light_cdf_pick", "lambertian_light_xz_rect"],
+    "smooth_mesh": ["normal_interpolated", "uv_interpolated", "tex_image", "dielectric_refract", "metal", "hit_triangle",
+                    "under_translate", "under_rotate_y", "under_flip_face"],
+    "smooth_cancel": ["normal_interpolated", "uv_interpolated", "hit_triangle"],
+    "smooth_lit": ["normal_interpolated", "lambertian_light_triangle", "lambertian_light_box"],
+    "smooth_lit_many": ["normal_interpolated", "lambertian_light_cdf_pick", "lambertian_light_triangle", "lambertian_light_box"],
 }
+# normal_fallback (the vertex normals cancel: |sum|^2 below FLT_MIN) is taken on a set of measure zero — the sum of three unit vectors with
+# weights of a point INSIDE a triangle vanishes on a line at most, and a ray meets a line only by an accident of rounding — so no render can
+# be asked for COVERAGE samples of it. smooth_cancel is there for the samples BESIDE the line (NORMAL_MARGIN); the branch itself is held by
+# known answers on rays aimed at points where the sum is exactly 0 (tests/test_oracle_kat.py, tests/test_mesh_attrs_host.py).
+MEASURE_ZERO = ["normal_fallback"]
 SCENES = list(REQUIRED)
 # what the cluster adds to every "all" form
 REQUIRED_ALL_FORM = ["hit_triangle", "under_translate", "under_rotate_y", "tex_checker", "medium_scattered", "lambertian_light_sphere"]
+PADDING = 512
 CASES = [(s, f, d) for s in SCENES for f in FORMS for d in DEPTHS]
 
 # ---- the f32 checker against the f64 checker on decidable samples: worst |L32 - L64| / max(1, |L64|) over the four depths, per scene and
@@ -315,6 +453,24 @@ MEASURED_F32_ORACLE = {
     ("rotated_sphere", "all"): 7.24e-05,
     ("camera", "own"): 5.78e-05,
     ("camera", "all"): 7.84e-05,
+    ("lights_shapes", "own"): 7.37e-05,
+    ("lights_shapes", "all"): 5.56e-05,
+    ("lights_shapes_wrapped", "own"): 2.48e-05,
+    ("lights_shapes_wrapped", "all"): 4.83e-05,
+    ("lights_many", "own"): 5.85e-05,
+    ("lights_many", "all"): 6.37e-05,
+    ("lights_many_one", "own"): 1.52e-05,
+    ("lights_many_one", "all"): 3.11e-05,
+    ("lights_many_two", "own"): 7.09e-05,
+    ("lights_many_two", "all"): 1.05e-04,
+    ("smooth_mesh", "own"): 3.67e-06,
+    ("smooth_mesh", "all"): 7.83e-06,
+    ("smooth_cancel", "own"): 4.56e-06,
+    ("smooth_cancel", "all"): 8.93e-07,
+    ("smooth_lit", "own"): 8.72e-06,
+    ("smooth_lit", "all"): 1.44e-05,
+    ("smooth_lit_many", "own"): 1.70e-05,
+    ("smooth_lit_many", "all"): 7.13e-06,
 }
 
 _cache = {}
@@ -344,19 +500,33 @@ def decide(pkg, orc, name, form, depth, threads=8):
         return _cache[key]
     built, _ = scene(pkg, name, form)
     prm = params(pkg, depth)
-    base = orc.render_paths(built.desc, built.cam, prm, precision=64, n_threads=threads, count=True)
+    base = orc.render_paths(built.desc, built.cam, prm, precision=64, n_threads=threads, count=True, attrs=built.attrs)
     same = np.ones(base["segments"].shape, bool)
     lo, hi, margin, tmin = base["radiance"].copy(), base["radiance"].copy(), base["margin"].copy(), base["tmin_margin"].copy()
+    more = {k: base[k].copy() for k in ("light_edge", "light_cos", "normal_margin")}
     for s in SIGNS:
-        q = orc.render_paths(built.desc, built.cam, prm, precision=64, n_threads=threads, r_ulps=R_ULPS, signs=s)
+        q = orc.render_paths(built.desc, built.cam, prm, precision=64, n_threads=threads, r_ulps=R_ULPS, signs=s, attrs=built.attrs)
+        more = {k: np.minimum(v, q[k]) for k, v in more.items()}
         same &= (q["segments"] == base["segments"]) & (q["terminal"] == base["terminal"]) & (q["events"] == base["events"])
         lo, hi, margin = np.minimum(lo, q["radiance"]), np.maximum(hi, q["radiance"]), np.minimum(margin, q["margin"])
         tmin = np.minimum(tmin, q["tmin_margin"])
     size = np.maximum(1.0, np.abs(base["radiance"]).max(axis=-1))
     decidable = same & ((hi - lo).max(axis=-1) <= SPREAD * size) & (margin >= DRAW_MARGIN) & (tmin >= TMIN_MARGIN)
-    f32 = orc.render_paths(built.desc, built.cam, prm, precision=32, n_threads=threads)
+    decidable &= (more["light_edge"] >= LIGHT_EDGE_MARGIN) & (more["light_cos"] >= LIGHT_COS_MARGIN) & (more["normal_margin"] >= NORMAL_MARGIN)
+    f32 = orc.render_paths(built.desc, built.cam, prm, precision=32, n_threads=threads, attrs=built.attrs)
     _cache[key] = dict(built=built, base=base, decidable=decidable, f32=f32)
     return _cache[key]
+
+
+def all_form_variant(own):
+    """the instance the "all" form of a scene runs on: the full set, with what the scene's own instance carries beyond the seven old bits"""
+    return "all" + (own[own.index("+"):] if "+" in own else "")
+
+
+# the feature bits 128 / 256 / 512 (RtCompileInfo.features) each new scene is meant to report, in either form
+NEW_FEATURES = {"lights_shapes": F_LIGHTS_EXT, "lights_shapes_wrapped": F_LIGHTS_EXT, "lights_many": F_LIGHTS_EXT | F_LIGHTS_TREE,
+                "lights_many_one": F_LIGHTS_EXT | F_LIGHTS_TREE, "lights_many_two": F_LIGHTS_EXT | F_LIGHTS_TREE, "smooth_mesh": F_TRI_ATTR,
+                "smooth_cancel": F_TRI_ATTR, "smooth_lit": F_TRI_ATTR | F_LIGHTS_EXT, "smooth_lit_many": F_TRI_ATTR | F_LIGHTS_EXT | F_LIGHTS_TREE}
 
 
 def bit(orc, name):

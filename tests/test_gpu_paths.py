@@ -31,7 +31,7 @@ def uploaded(pkg, gpu, name, form, layout=0):
     key = (name, form, layout)
     if key not in _uploaded:
         built, _ = P.scene(pkg, name, form)
-        _uploaded[key] = gpu.upload(built.desc, layout)
+        _uploaded[key] = gpu.upload(built.desc, layout, **(dict(triangle_attrs=built.attrs) if built.attrs is not None else {}))
     return _uploaded[key]
 
 
@@ -112,10 +112,11 @@ def test_carriers_bit_for_bit(pkg, gpu, name, form):
         assert sa["samples"] == sb["samples"] == P.W * P.H * P.SPP and sa["segments"] == sb["segments"], kw
 
 
-@pytest.mark.parametrize("name,form", [("glass", "own"), ("lights_none", "own"), ("glass_mesh", "own"), ("wrap_flip_both", "own"), ("textures_wrapped", "all")])
+@pytest.mark.parametrize("name,form", [("glass", "own"), ("lights_none", "own"), ("glass_mesh", "own"), ("wrap_flip_both", "own"), ("textures_wrapped", "all"),
+                                       ("lights_many", "own"), ("smooth_lit", "own")])
 def test_layouts_bit_for_bit(pkg, gpu, name, form):
-    """Scenes of every kernel variant (0 twice: glass with its hollow ball, Lambertian spheres; mesh, box, all): shading does not depend on
-    where the walk found its records."""
+    """Scenes of every kernel variant (0 twice: glass with its hollow ball, Lambertian spheres; mesh, box, all; the light tree; attributes
+    under extended lights): shading does not depend on where the walk found its records."""
     A = pkg._abi
     built, _ = P.scene(pkg, name, form)
     prm = P.params(pkg, 8)
@@ -125,3 +126,36 @@ def test_layouts_bit_for_bit(pkg, gpu, name, form):
         assert a.tobytes() == b.tobytes(), layout
         assert sa["segments"] == sb["segments"], layout
     assert sa["bvh_in_lds"] == 1 and gpu.render(uploaded(pkg, gpu, name, form, A.RT_LAYOUT_SCENE_IN_HBM), built.cam, prm)[1]["bvh_in_lds"] == 0
+
+
+def test_lights_table_reads_the_same_from_lds_and_hbm(pkg, orc, gpu):
+    """k_shade finds the lights table of RT_SCENE_LIGHTS_MANY (LightX records, tree records, cdf, slots) in its LDS blob where the shade
+    tables fit 8 KB (rt_api.cpp) and in HBM otherwise. `lights_many` fits; `lights_many_padded` is the same scene with paths.PADDING
+    Lambertian spheres behind the camera, whose sphere records alone exceed 8 KB. Every sample whose path the checker finds decidable in
+    both scenes, and the same in both (segments, terminal, events and radiance, bit for bit: it never meets the padding — a padding sphere
+    that is tested and missed changes nothing), must be bit-identical on the device.
+    The library reports nowhere whether the blob was built, so the two sizes are bounded here from the compiled tables' counts
+    (rt_scene_compile_info) and the record sizes of csrc/device_types.h, as rt_api.cpp sums them: 12 tables, each padded to 16 bytes."""
+    a, b = P.decide(pkg, orc, "lights_many", "own", 8), P.decide(pkg, orc, "lights_many_padded", "own", 8)
+
+    def blob_bounds(built):
+        i = pkg.compile_info(built.desc)
+        n = i["n_lights"]
+        lights = 96 * n + 32 * (2 * n - 1) + 8 * n                      # LightX records, tree records, cdf and slots
+        low = 20 * i["n_spheres"] + 36 * i["n_rects"] + lights
+        # a moving sphere 48 + 4 B; a material 20 B; an Xform 32 B; a Wrap 112 B, one per composite transform and wrap 0 (the scene has no
+        # chain of FlipFace alone); a Texture 32 B, at most one per texture of the builder
+        high = low + 52 * i["n_moving"] + 20 * i["n_materials"] + 32 * i["n_xforms"] + 112 * (i["n_xforms"] + 1) + 32 * len(built.keep.textures) + 12 * 15
+        return low, high
+    assert blob_bounds(a["built"])[1] <= 8 * 1024 < blob_bounds(b["built"])[0], (blob_bounds(a["built"]), blob_bounds(b["built"]))
+    same = a["decidable"] & b["decidable"]
+    for k in ("segments", "terminal", "events", "radiance"):
+        eq = a["base"][k] == b["base"][k]
+        same &= eq.all(axis=-1) if eq.ndim == 4 else eq
+    assert same.mean() > 0.9, same.mean()
+    assert int((same & ((a["base"]["events"] & np.uint64(orc.EVENTS["lambertian_light_cdf_pick"])) != 0)).sum()) >= P.COVERAGE
+    La, _ = device_samples(pkg, gpu, uploaded(pkg, gpu, "lights_many", "own"), a["built"].cam, 8)
+    Lb, _ = device_samples(pkg, gpu, uploaded(pkg, gpu, "lights_many_padded", "own"), b["built"].cam, 8)
+    differ = np.argwhere(same & (La.view(np.uint32) != Lb.view(np.uint32)).any(axis=-1))
+    print(f"lights table in LDS against HBM: {int(same.sum())} of {same.size} samples compared, {len(differ)} differ")
+    assert len(differ) == 0, [tuple(int(v) for v in i) for i in differ[:8]]

@@ -233,3 +233,137 @@ def test_oracle_reproduces_its_golden_fixture(orc, pkg):
     hs = pkg.HostScene("book1", 1)
     img, _ = orc.render(hs.desc, hs.camera(64 / 40), pkg.make_params(64, 40, 8, seed=1), precision=64, n_threads=3)
     assert np.array_equal(img, g)          # bit-exact, and independent of the thread count
+
+
+# ---- RtSceneDesc.scene_flags and triangle attributes (include/rt_hip.h): NOT in the reference; the header's statement, by hand ----------------
+def _lights_scene(pkg, make, many=False):
+    b = pkg.SceneBuilder()
+    lamp = b.diffuse_light((4.0, 4.0, 4.0))
+    lights = make(b, lamp)
+    floor = b.xz_rect(-50.0, 50.0, -50.0, 50.0, -2.0, b.lambertian((0.7, 0.7, 0.7)))
+    return b.desc(b.hittable_list([floor] + lights), b.hittable_list(lights), lights_all_shapes=True, lights_many=many), b
+
+
+def _uniform24(state, k):
+    """the k-th uniform (k = 1, 2, ..) of the stream that starts at `state`: SplitMix64, top 24 bits (the draw rt_sample_lights makes)"""
+    m = (1 << 64) - 1
+    z = (state + k * 0x9E3779B97F4A7C15) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return ((z ^ (z >> 31)) >> 40) / 16777216.0
+
+
+def test_triangle_light_pdf_from_its_axis(orc, pkg):
+    """pdf = t^2 |v|^2 / (|cos| area). The triangle (-1, 2, -1), (1, 2, -1), (0, 2, 2) has e1 x e2 = (2, 0, 0) x (1, 0, 3) = (0, -6, 0): area 3,
+    centroid (0, 2, 0). From the origin, on the axis through the centroid: distance 2, cos 1, pdf = 4 / 3, whatever the length of v. From
+    (1, 0, 0) towards the centroid: distance^2 = 5, cos = 2 / sqrt(5), pdf = 5 sqrt(5) / 6. Past the triangle's edge: 0."""
+    desc, keep = _lights_scene(pkg, lambda b, lamp: [b.triangle((-1, 2, -1), (1, 2, -1), (0, 2, 2), lamp)])
+    r = orc.sample_lights(desc, [(0, 0, 0), (0, 0, 0), (1, 0, 0), (0, 0, 0)], dirs=[(0, 1, 0), (0, 0.25, 0), (-1, 2, 0), (0, 2, 2.5)])
+    assert r["pdf"][:3] == pytest.approx([4 / 3, 4 / 3, 5 * math.sqrt(5) / 6], rel=1e-14) and r["pdf"][3] == 0.0
+    assert (r["light"] == -1).all() and (r["n_draws"] == 0).all()
+    # the draw: r1 then r2, s = sqrt(r1), the point (1 - s) v0 + s (1 - r2) v1 + s r2 v2; one next64() for the pick of the list's only member
+    state = 0x1234567887654321
+    q = orc.sample_lights(desc, [(0.5, -1, 0.25)], states=[state])
+    r1, r2 = _uniform24(state, 2), _uniform24(state, 3)
+    s = math.sqrt(r1)
+    pt = (1 - s) * np.array([-1.0, 2, -1]) + s * (1 - r2) * np.array([1.0, 2, -1]) + s * r2 * np.array([0.0, 2, 2])
+    assert q["d"][0] == pytest.approx(pt - np.array([0.5, -1, 0.25]), rel=1e-14) and q["n_draws"][0] == 3 and q["light"][0] == 0
+    assert q["pdf"][0] == pytest.approx(float(np.dot(q["d"][0], q["d"][0])) ** 1.5 / (abs(q["d"][0][1]) * 3.0), rel=1e-13)   # t = 1: |v|^2 / ((|v_y| / |v|) area)
+
+
+def test_box_light_pdf_is_a_sixth_of_the_sides_met(orc, pkg):
+    """The box (-1, 2, -1) .. (1, 3, 1): every side has area 4. A ray up the y axis from the origin meets the y0 side squarely at distance 2
+    and the y1 side at 3 (a line through a box meets two sides): pdf = (4 / 4 + 9 / 4) / 6 = 13 / 24. From (0, 2.5, 0), inside, it meets the y1
+    side alone, at 0.5: one rect's pdf over six, 0.25 / 4 / 6 = 1 / 96. The draw: next64() % 6 picks the side in boxes.rs order (z1 z0 y1 y0
+    x1 x0), then that rect's two draws."""
+    desc, keep = _lights_scene(pkg, lambda b, lamp: [b.box((-1, 2, -1), (1, 3, 1), lamp)])
+    r = orc.sample_lights(desc, [(0, 0, 0), (0, 2.5, 0), (0, 0, 0)], dirs=[(0, 1, 0), (0, 3, 0), (1, 0, 0)])
+    assert r["pdf"] == pytest.approx([13 / 24, 1 / 96, 0.0], rel=1e-14)
+    sides = [(2, 1.0), (2, -1.0), (1, 3.0), (1, 2.0), (0, 1.0), (0, -1.0)]           # (constant axis, k) in boxes.rs order
+    lo, hi = np.array([-1.0, 2, -1]), np.array([1.0, 3, 1])
+    seen = set()
+    for state in range(1, 40):
+        q = orc.sample_lights(desc, [(0, 0, 0)], states=[state])
+        m = (1 << 64) - 1
+        z = (state + 2 * 0x9E3779B97F4A7C15) & m             # the second next64(): the first picked the list's only member
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+        side = (z ^ (z >> 31)) % 6
+        axis, k = sides[side]
+        ia, ib = [a for a in range(3) if a != axis]
+        pt = np.zeros(3)
+        pt[axis], pt[ia], pt[ib] = k, lo[ia] + (hi[ia] - lo[ia]) * _uniform24(state, 3), lo[ib] + (hi[ib] - lo[ib]) * _uniform24(state, 4)
+        assert q["d"][0] == pytest.approx(pt, rel=1e-14, abs=1e-15) and q["n_draws"][0] == 4
+        seen.add(side)
+    assert seen == set(range(6))
+
+
+def test_wrapped_rect_light_is_the_rect_moved_by_hand(orc, pkg):
+    """Translate((0.5, 3, 0.2), RotateY(90 degrees, XzRect x in [-1, 2], z in [-0.5, 0.5], y = 0)): RotateY's local -> world map is
+    (x, z) -> (cos x + sin z, -sin x + cos z) = (z, -x) (hittable.rs:166-167), so the member is the bare XzRect x in [0, 1], z in [-1.8, 1.2],
+    y = 3. Its pdf is the bare one's (a rigid map keeps it) to the f32 rounding of the map's sine and cosine (cos 90 degrees = 6e-17 in
+    f64 rounds to a float of that size; the offset 0.2 to 3e-9): 1e-6 relative. The drawn point: the local (-1 + 3 r1, 0, -0.5 + r2)."""
+    wrapped, k1 = _lights_scene(pkg, lambda b, lamp: [b.translate(b.rotate_y(b.xz_rect(-1.0, 2.0, -0.5, 0.5, 0.0, lamp), 90.0), (0.5, 3.0, 0.2))])
+    bare, k2 = _lights_scene(pkg, lambda b, lamp: [b.xz_rect(0.0, 1.0, -1.8, 1.2, 3.0, lamp)])
+    rng = np.random.default_rng(5)
+    pts = rng.uniform(-2.0, 2.0, (256, 3)) * np.array([1.0, 0.5, 1.0])
+    aim = np.stack([rng.uniform(-0.3, 1.3, 256), np.full(256, 3.0), rng.uniform(-2.1, 1.5, 256)], axis=1) - pts       # some past the edges
+    a, b = orc.sample_lights(wrapped, pts, dirs=aim), orc.sample_lights(bare, pts, dirs=aim)
+    inside = (b["light_edge"] > 1e-4)
+    assert inside.sum() > 200 and (b["pdf"][inside] > 0).sum() > 100 and (b["pdf"][inside] == 0).sum() > 20
+    assert a["pdf"][inside] == pytest.approx(b["pdf"][inside], rel=1e-6)
+    state = 0xABCDEF0123456789
+    q = orc.sample_lights(wrapped, [(0.3, 0.1, -0.4)], states=[state])
+    xl, zl = -1.0 + 3.0 * _uniform24(state, 2), -0.5 + _uniform24(state, 3)
+    assert q["d"][0] == pytest.approx(np.array([zl + 0.5, 3.0, -xl + 0.2]) - np.array([0.3, 0.1, -0.4]), abs=1e-6) and q["n_draws"][0] == 3
+
+
+def test_scene_flags_refusals(orc, pkg):
+    """An unknown bit, MANY without ALL_SHAPES and a member the header says is refused are errors from the checker, not defaults."""
+    A = pkg._abi
+    cam = pkg.camera_new((0, 0, 5), (0, 0, 0), (0, 1, 0), 40.0, 1.0, 0.0, 5.0, 0.0, 0.0)
+    prm = pkg.make_params(2, 2, 1, max_depth=2, seed=1)
+    desc, keep = _lights_scene(pkg, lambda b, lamp: [b.triangle((-1, 2, -1), (1, 2, -1), (0, 2, 2), lamp)])
+    orc.render_paths(desc, cam, prm)
+    for flags in (2, 8, A.RT_SCENE_LIGHTS_MANY, 1 << 31):
+        desc.scene_flags = flags
+        with pytest.raises(RuntimeError):
+            orc.render_paths(desc, cam, prm)
+    bad = [lambda b, lamp: [b.moving_sphere((0, 2, 0), (0, 2.5, 0), 0.0, 1.0, 0.5, lamp)],
+           lambda b, lamp: [b.constant_medium(b.sphere((0, 2, 0), 0.5, lamp), 1.0, (0.5, 0.5, 0.5))],
+           lambda b, lamp: [b.hittable_list([b.sphere((0, 2, 0), 0.5, lamp)])],
+           lambda b, lamp: [b.bvh([b.sphere((0, 2, 0), 0.5, lamp), b.sphere((2, 2, 0), 0.5, lamp)])],
+           lambda b, lamp: [b.xy_rect(1.0, 1.0, 0.0, 2.0, 3.0, lamp)],
+           lambda b, lamp: [b.triangle((0, 2, 0), (1, 2, 0), (2, 2, 0), lamp)],
+           lambda b, lamp: [b.box((0, 2, 0), (1, 2, 1), lamp)],
+           lambda b, lamp: [b.flip_face(b.flip_face(b.flip_face(b.flip_face(b.flip_face(b.flip_face(b.flip_face(b.sphere((0, 2, 0), 0.5, lamp))))))))]]
+    for make in bad:
+        desc, keep = _lights_scene(pkg, make)
+        with pytest.raises(RuntimeError):
+            orc.render_paths(desc, cam, prm)
+        with pytest.raises(pkg.RtError):                      # ... as the library refuses them
+            pkg.compile_info(desc)
+    # six wrappers are the limit, not beyond it
+    desc, keep = _lights_scene(pkg, lambda b, lamp: [b.flip_face(b.flip_face(b.flip_face(b.flip_face(b.flip_face(b.flip_face(b.sphere((0, 2, 0), 0.5, lamp)))))))])
+    orc.render_paths(desc, cam, prm)
+
+
+def test_cancelled_vertex_normals_fall_back_to_the_facet(orc, pkg):
+    """Vertex normals a, a, -a on the triangle (-1, 0, 0), (1, 0, 0), (0, 1, 0): s = (w0 + bu - bv) a vanishes where bv = 1 / 2. The ray from
+    (0, 0.5, 1) along -z meets (0, 0.5, 0) = v0 + 0.25 e1 + 0.5 e2: every operand is a dyadic rational, the barycentrics are exact, and
+    0.25 a + 0.25 a - 0.5 a is exactly 0 for any float a — the hit keeps the geometric normal (0, 0, 1). A ray beside it has +-unit(a)."""
+    b = pkg.SceneBuilder()
+    a = np.array([0.6, 0.0, 0.8])
+    t = b.triangle((-1, 0, 0), (1, 0, 0), (0, 1, 0), b.lambertian((0.5, 0.5, 0.5)), normals=(2 * a, 0.5 * a, -4 * a))      # powers of two: the three unit normals are the same floats
+    desc = b.desc(b.hittable_list([t]))
+    o = np.array([(0.0, 0.5, 1.0), (0.0, 0.25, 1.0), (0.0, 0.75, 1.0)])
+    hit, rec = orc.world_hit_many(desc, o, np.tile([0.0, 0.0, -1.0], (3, 1)), 0.0, attrs=b.triangle_attrs())
+    assert hit.all() and (rec[:, 7:9] == [(0.25, 0.5), (0.375, 0.25), (0.125, 0.75)]).all()
+    a32 = a.astype(np.float32).astype(np.float64)
+    a32 = (a32 / np.linalg.norm(a32)).astype(np.float32).astype(np.float64)            # made unit in f64, then rounded to f32
+    assert (rec[0, 4:7] == (0.0, 0.0, 1.0)).all() and rec[0, 9] == 1.0
+    assert rec[1, 4:7] == pytest.approx(a32 / np.linalg.norm(a32), rel=1e-15) and rec[1, 9] == 1.0       # bv < 1 / 2: +a, against the ray
+    assert rec[2, 4:7] == pytest.approx(a32 / np.linalg.norm(a32), rel=1e-15) and rec[2, 9] == 0.0       # bv > 1 / 2: -a, seen from behind, turned against the ray
+    # without the attributes: the facet's normal everywhere
+    hit, rec = orc.world_hit_many(desc, o, np.tile([0.0, 0.0, -1.0], (3, 1)), 0.0)
+    assert (rec[:, 4:7] == (0.0, 0.0, 1.0)).all()

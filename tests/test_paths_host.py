@@ -180,8 +180,19 @@ def test_kat_medium_and_isotropic(pkg, orc):
 # ---- the probe scenes --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,form", [(s, f) for s in P.SCENES for f in P.FORMS])
 def test_scene_runs_on_the_variant_it_is_meant_for(pkg, name, form):
+    """The instance every case runs (pick_variant, with_record_variant and with_shade_variant of csrc/kernels.hip, restated in paths.variant_of),
+    from the feature bits rt_scene_compile_info reports. "own" forms of the scenes of scene_flags and triangle attributes:
+        lights_shapes, lights_shapes_wrapped            kVariantAllLx       (all+lx)
+        lights_many, lights_many_one, lights_many_two   kVariantAllLt       (all+lt)
+        smooth_mesh                                     kVariantAllAttr     (all+attr)
+        smooth_cancel                                   kVariantMeshAttr    (mesh+attr)
+        smooth_lit                                      kVariantAllAttrLx   (all+attr+lx)
+        smooth_lit_many                                 kVariantAllAttrLt   (all+attr+lt)
+    Their "all" forms run the same instance (smooth_cancel: kVariantAllAttr); the older scenes' run 0, mesh, box or all, and all."""
     built, own = P.scene(pkg, name, form)
-    assert P.variant_of(pkg, built.desc) == (own if form == "own" else "all")
+    assert P.variant_of(pkg, built) == (own if form == "own" else P.all_form_variant(own))
+    new = P.F_TRI_ATTR | P.F_LIGHTS_EXT | P.F_LIGHTS_TREE
+    assert P.features_of(pkg, built) & new == P.NEW_FEATURES.get(name, 0)
 
 
 def test_a_hollow_sphere_is_found_whatever_the_tree(pkg, orc):
@@ -218,7 +229,7 @@ def test_a_hollow_sphere_is_found_whatever_the_tree(pkg, orc):
 
 
 def test_scenes_reach_all_four_variants(pkg):
-    assert {P.scene(pkg, s, "own")[1] for s in P.SCENES} == {"0", "mesh", "box", "all"}
+    assert {P.scene(pkg, s, "own")[1] for s in P.SCENES} == {"0", "mesh", "box", "all"} | set(P.NEW_INSTANCES)        # every instance pick_variant can choose
     assert set(P.MEASURED_F32_ORACLE) == {(s, f) for s in P.SCENES for f in P.FORMS}
 
 
@@ -238,7 +249,8 @@ def test_every_branch_is_covered_by_decidable_samples(pkg, orc, name, form):
 
 
 def test_every_event_bit_is_required_somewhere(orc):
-    assert set(orc.EVENT_NAMES) == {n for need in P.REQUIRED.values() for n in need} | set(P.REQUIRED_ALL_FORM)
+    assert set(orc.EVENT_NAMES) == {n for need in P.REQUIRED.values() for n in need} | set(P.REQUIRED_ALL_FORM) | set(P.MEASURE_ZERO)
+    assert not set(P.MEASURE_ZERO) & {n for need in P.REQUIRED.values() for n in need}
 
 
 def test_nonfinite_samples_are_covered(pkg, orc):
