@@ -230,6 +230,16 @@ pub struct RtLightQuery { pub p: [f32; 3], pub flags: u32, pub rng_state: u64, p
 pub struct RtLightSample { pub d: [f32; 3], pub pdf: f32, pub light: i32, pub n_draws: u32 }                           // 24 B
 #[repr(C)] #[derive(Clone, Copy, Default, Debug)]
 pub struct RtLightQueryOptions { pub struct_bytes: u32, pub flags: u32 }
+// radiance queries (rt_radiance_rays): the path tracer on caller-supplied rays, per-ray sums over a sample range
+pub const RT_RADIANCE_ACCUMULATE: u32 = 1;
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtPathRay { pub o: [f32; 3], pub time: f32, pub d: [f32; 3], pub first_draw: u32 }                           // 32 B
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtRadianceOptions {
+    pub struct_bytes: u32, pub flags: u32, pub render_flags: u32, pub nan_policy: u32,
+    pub samples: u32, pub first_sample: u32, pub max_depth: u32, pub pool_slots: u32,
+    pub seed: u64, pub first_stream: u64, pub tail_paths: u32, pub _pad: u32,
+}
 
 pub const RT_OUT_RGB_SUM_F32: u32 = 0;
 pub const RT_OUT_RGB8: u32 = 1;
@@ -312,6 +322,13 @@ extern "C" {
                                    results_device: *mut c_void, stats: *mut RtStats) -> c_int;
     pub fn rt_sample_lights(ctx: *mut RtCtx, scene: *const RtScene, options: *const RtLightQueryOptions, queries_host: *const RtLightQuery, n: u64,
                             results_host: *mut RtLightSample, stats: *mut RtStats) -> c_int;
+    /// host only: validates (options, n_rays) of a radiance query
+    pub fn rt_radiance_check(options: *const RtRadianceOptions, n_rays: u64) -> c_int;
+    /// radiance along n_rays RtPathRay records: per-ray RGB sums over the samples (3 f32 each), optional sums of squares and flag bytes
+    pub fn rt_radiance_rays_device(ctx: *mut RtCtx, scene: *const RtScene, options: *const RtRadianceOptions, rays_device: *const c_void, n_rays: u64,
+                                   rgb_sum_device: *mut c_void, sq_sum_device: *mut c_void, invalid_device: *mut c_void, stats: *mut RtStats) -> c_int;
+    pub fn rt_radiance_rays(ctx: *mut RtCtx, scene: *const RtScene, options: *const RtRadianceOptions, rays_host: *const RtPathRay, n_rays: u64,
+                            rgb_sum_host: *mut f32, sq_sum_host: *mut f32, invalid_host: *mut u8, stats: *mut RtStats) -> c_int;
     /// host only: validates a feature pass (params, options)
     pub fn rt_features_check(params: *const RtParams, options: *const RtFeatureOptions) -> c_int;
     /// first-hit feature sums of samples [first_sample, first_sample + samples_per_pixel) into the caller's device planes (null = not wanted)

@@ -711,6 +711,65 @@ int rt_sample_lights_device(RtCtx* ctx, const RtScene* scene, const RtLightQuery
 int rt_sample_lights(RtCtx* ctx, const RtScene* scene, const RtLightQueryOptions* options /* NULL = defaults */, const RtLightQuery* queries_host, uint64_t n,
                      RtLightSample* results_host, RtStats* stats);
 
+/* ---- radiance queries: the path tracer itself on caller-supplied rays -----------------------------------------------------------------------
+ *
+ * What the other queries leave out: the radiance along a caller's own ray — a host's own camera model (fisheye, panorama, orthographic,
+ * stereo, lens distortion), light probes, lightmap texels, the secondary rays of a hybrid integrator. Ray i of the list is traced S =
+ * `samples` times; rgb_sum[3 i + c] receives the sum of the S samples.
+ *   - SAMPLE RULE. Sample s of ray i is what ray_color (main.rs:63-139, in the scene's integrator mode) returns for the ray (o, d, time), which
+ *     starts on nothing, as every query ray does. Its random stream is path_base(seed, first_stream + i, first_sample + s) — the stream a
+ *     render gives sample first_sample + s of the pixel with index first_stream + i — ADVANCED BY first_draw DRAWS. first_draw is 0 for an
+ *     ordinary caller; a caller who made the ray from the first draws of that very stream (as a render's camera does: jitter, lens, time)
+ *     passes how many it spent, and the path goes on where it stopped. The path runs through the kernels and device functions of a render
+ *     (the wavefront loop, the drain, the fold); it is not a restatement of them.
+ *   - OUTPUTS. rgb_sum: 3 f32 per ray, the sum over the S samples, folded sequentially in sample order in f32 from 0 — or, under
+ *     RT_RADIANCE_ACCUMULATE, from the value already there. sq_sum (NULL = not wanted): the same for the squares of the samples, formed in
+ *     f32 (x * x, rounded, then added). The standard-error formula of rt_render_pass applies with m = 1 and k = the samples folded so far.
+ *     invalid (NULL = not wanted): one byte per ray, RT_RAYHIT_INVALID_RAY for an invalid ray and 0 for every other.
+ *   - GUARANTEES, bit for bit. out[i] is a function of (scene, layout, ray i, its stream index first_stream + i, seed, the sample range,
+ *     max_depth, nan_policy) alone: not of pool_slots, tail_paths, the chunking, or the host / device variant; not of how a list is split
+ *     over calls (rays [a, b) with first_stream = f + a give the bits the same rays get inside a call over [0, n) with first_stream = f);
+ *     not of how a sample range is split ([0, k) and then [k, S) accumulating give one call's bits). Hence a caller shards a list over GPUs
+ *     itself: there is no multi-GPU entry point.
+ *   - INVALID rays: rt_trace_rays' rule (a non-finite origin, direction or time, or |d|^2 not a positive normal f32), and first_draw >= 2^16.
+ *     They are never traced; their sums are 0, or untouched under RT_RADIANCE_ACCUMULATE.
+ *   - SCENES. Every scene a render accepts: a ConstantMedium included (a path has a stream, which the bare ray of rt_trace_rays lacks),
+ *     lights lists, RT_SCENE_LIGHTS_*, triangle attributes, every RT_LAYOUT_*. In a motionless scene the time is read by nothing, as in a
+ *     render (it must still be finite).
+ *   - OPTIONS are required. max_depth 1..255, nan_policy, seed, pool_slots and tail_paths mean what they mean in RtParams; pool_slots caps
+ *     the paths in flight (0 = the renderer's rule), and a call of more (ray, sample) pairs runs in chunks — over rays first, then samples.
+ *   - REFUSED with RT_ERR_INVALID and the reason in rt_last_error, nothing written: NULL options; struct_bytes < sizeof(RtRadianceOptions);
+ *     an unknown bit in flags or in render_flags (known there: RT_FLAG_TIMING; no counters); a bad nan_policy or max_depth; samples == 0;
+ *     first_sample + samples >= 2^32; first_stream + n_rays > 2^32 - 1 (a stream index is 32 bits: the exact limit — so up to 2^32 - 1 rays
+ *     per call from first_stream 0); a NULL rays or rgb_sum with n_rays > 0; for the device variant rays, rgb_sum or sq_sum not 16-byte
+ *     aligned (invalid needs no alignment). n_rays == 0 is a no-op.
+ *   - RtStats: samples = valid rays x S; segments, render_ms, iterations, pool_slots and drain_paths as for a render; with RT_FLAG_TIMING
+ *     also extend_ms, shade_ms, drain_ms and other_ms (the kernel that reads the rays, and the fold). Both variants block until done; the
+ *     host variant stages rays and sums through the context's buffers (uploading the caller's sums first when accumulating). */
+typedef struct RtPathRay { float o[3]; float time; float d[3]; uint32_t first_draw; } RtPathRay;   /* 32 B: RtRay with t_max's word = first_draw */
+enum { RT_RADIANCE_ACCUMULATE = 1u };
+typedef struct RtRadianceOptions {
+    uint32_t struct_bytes;    /* sizeof(RtRadianceOptions) as the caller compiled it (the struct may grow at its end) */
+    uint32_t flags;           /* RT_RADIANCE_*; an unknown bit is RT_ERR_INVALID */
+    uint32_t render_flags;    /* RT_FLAG_TIMING only; any other bit is RT_ERR_INVALID */
+    uint32_t nan_policy;      /* RtNanPolicy */
+    uint32_t samples;         /* S >= 1 samples per ray ... */
+    uint32_t first_sample;    /* ... with the absolute indices first_sample .. first_sample + S - 1 */
+    uint32_t max_depth;       /* as RtParams */
+    uint32_t pool_slots;      /* as RtParams */
+    uint64_t seed;            /* as RtParams */
+    uint64_t first_stream;    /* ray i runs on stream first_stream + i */
+    uint32_t tail_paths;      /* as RtParams.tail_paths */
+    uint32_t _pad;
+} RtRadianceOptions;
+/* Host only, no device: validates (options, n_rays) and reports the reason through rt_last_error. */
+int rt_radiance_check(const RtRadianceOptions* options, uint64_t n_rays);
+int rt_radiance_rays_device(RtCtx* ctx, const RtScene* scene, const RtRadianceOptions* options, const void* rays_device, uint64_t n_rays,
+                            void* rgb_sum_device, void* sq_sum_device /* NULL = not wanted */, void* invalid_device /* n_rays bytes; NULL = not wanted */,
+                            RtStats* stats);
+int rt_radiance_rays(RtCtx* ctx, const RtScene* scene, const RtRadianceOptions* options, const RtPathRay* rays_host, uint64_t n_rays,
+                     float* rgb_sum_host, float* sq_sum_host /* NULL = not wanted */, uint8_t* invalid_host /* NULL = not wanted */, RtStats* stats);
+
 /* ---- first-hit features: albedo, normal and depth of the render's own camera rays ----------------------------------------------------------
  *
  * What a feature-guided filter or an external denoiser starts from: per-pixel SUMS, over a range of samples, of the first hit's colour,

@@ -24,6 +24,7 @@ RT_DENOISE_GUIDED_MOMENTS_MAX_WINDOW_RADIUS = 8
 RT_DENOISE_MOMENTS_SIGMA_ALBEDO, RT_DENOISE_MOMENTS_SIGMA_NORMAL, RT_DENOISE_MOMENTS_SIGMA_DEPTH, RT_DENOISE_MOMENTS_VARIANCE_STRENGTH = 0.01, 0.025, 0.01, 64.0
 RT_RAYHIT_HIT, RT_RAYHIT_FRONT_FACE, RT_RAYHIT_INVALID_RAY = 1, 2, 4
 RT_FEATURES_ACCUMULATE = 1
+RT_RADIANCE_ACCUMULATE = 1
 RT_TRI_NORMALS, RT_TRI_UVS = 1, 2
 RT_FEATURE_TRI_ATTR = 128      # RtCompileInfo.features: a triangle carries attributes (csrc/kernels.h F_TRI_ATTR)
 RT_FEATURE_LIGHTS_EXT = 256    # RtCompileInfo.features: the lights table holds extended records (csrc/kernels.h F_LIGHTS_EXT)
@@ -173,6 +174,16 @@ class RtLightQueryOptions(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class RtPathRay(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("time", C.c_float), ("d", C.c_float * 3), ("first_draw", C.c_uint32)]
+
+
+class RtRadianceOptions(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32), ("render_flags", C.c_uint32), ("nan_policy", C.c_uint32),
+                ("samples", C.c_uint32), ("first_sample", C.c_uint32), ("max_depth", C.c_uint32), ("pool_slots", C.c_uint32),
+                ("seed", C.c_uint64), ("first_stream", C.c_uint64), ("tail_paths", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class RtFeatureOptions(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32), ("first_sample", C.c_uint32), ("pool_slots", C.c_uint32)]
 
@@ -203,6 +214,7 @@ RT_HIP_SYMBOLS = ["rt_ctx_create", "rt_ctx_destroy", "rt_scene_upload", "rt_scen
                   "rt_denoise_check", "rt_denoise_device", "rt_denoise_guided_check", "rt_denoise_guided_device",
                   "rt_ray_query_check", "rt_trace_rays_device", "rt_trace_rays", "rt_occluded_rays_device", "rt_occluded_rays",
                   "rt_sample_lights_device", "rt_sample_lights", "rt_scene_light_tree_dump",
+                  "rt_radiance_check", "rt_radiance_rays_device", "rt_radiance_rays",
                   "rt_features_check", "rt_render_features_device",
                   "rt_feature_moments_check", "rt_render_feature_moments_device", "rt_denoise_guided_moments_check", "rt_denoise_guided_moments_device",
                   "rt_camera_lists_host", "rt_camera_lists_last"]
@@ -278,6 +290,12 @@ def declare(lib):
     lib.rt_sample_lights_device.argtypes = [vp, vp, P(RtLightQueryOptions), vp, u64, vp, P(RtStats)]
     lib.rt_sample_lights.restype = i32
     lib.rt_sample_lights.argtypes = [vp, vp, P(RtLightQueryOptions), vp, u64, vp, P(RtStats)]
+    lib.rt_radiance_check.restype = i32
+    lib.rt_radiance_check.argtypes = [P(RtRadianceOptions), u64]
+    lib.rt_radiance_rays_device.restype = i32
+    lib.rt_radiance_rays_device.argtypes = [vp, vp, P(RtRadianceOptions), vp, u64, vp, vp, vp, P(RtStats)]
+    lib.rt_radiance_rays.restype = i32
+    lib.rt_radiance_rays.argtypes = [vp, vp, P(RtRadianceOptions), vp, u64, vp, vp, vp, P(RtStats)]
     lib.rt_features_check.restype = i32
     lib.rt_features_check.argtypes = [P(RtParams), P(RtFeatureOptions)]
     lib.rt_render_features_device.restype = i32

@@ -120,6 +120,23 @@ def ray_query_check(options=None, n_rays=0):
     _check(lib().rt_ray_query_check(C.byref(options) if options is not None else None, n_rays))
 
 
+# ... and of RtPathRay ("radiance queries"): 32 bytes, RAY_DTYPE with first_draw in the place of t_max
+PATHRAY_DTYPE = np.dtype([("o", np.float32, 3), ("time", np.float32), ("d", np.float32, 3), ("first_draw", np.uint32)])
+
+
+def radiance_options(samples, max_depth=50, seed=1, first_sample=0, first_stream=0, accumulate=False, nan_policy=A.RT_NAN_PER_SAMPLE, pool_slots=0,
+                     tail_paths=0, render_flags=0, flags=None):
+    """RtRadianceOptions (include/rt_hip.h, "radiance queries"); flags overrides the accumulate bit when given."""
+    f = (A.RT_RADIANCE_ACCUMULATE if accumulate else 0) if flags is None else int(flags)
+    return A.RtRadianceOptions(C.sizeof(A.RtRadianceOptions), f, int(render_flags), int(nan_policy), int(samples), int(first_sample), int(max_depth),
+                               int(pool_slots), int(seed), int(first_stream), int(tail_paths), 0)
+
+
+def radiance_check(options, n_rays=0):
+    """rt_radiance_check (host only): raises RtError (RT_ERR_INVALID, with the reason) for options or a ray count a radiance query refuses."""
+    _check(lib().rt_radiance_check(C.byref(options) if options is not None else None, n_rays))
+
+
 def feature_options(first_sample=0, accumulate=False, pool_slots=0, flags=None):
     """RtFeatureOptions (include/rt_hip.h, "first-hit features"); flags overrides the accumulate bit when given."""
     f = (A.RT_FEATURES_ACCUMULATE if accumulate else 0) if flags is None else int(flags)
@@ -606,6 +623,63 @@ class Context:
         q["p"], q["d"], q["flags"] = points, dirs, A.RT_LIGHTQ_DIRECTION_GIVEN | (A.RT_LIGHTQ_LINEAR if linear else 0)
         r = self._light_queries(scene, q, with_stats)
         return (r[0]["pdf"].copy(), r[1]) if with_stats else r["pdf"].copy()
+
+    # ---- radiance queries (include/rt_hip.h, "radiance queries") ----
+    def radiance(self, scene, rays, samples, max_depth=50, seed=1, first_sample=0, first_stream=0, accumulate=False, rgb_sum=None, sq_sum=None,
+                 invalid=None, nan_policy=A.RT_NAN_PER_SAMPLE, pool_slots=0, tail_paths=0, with_stats=False, options=None):
+        """rt_radiance_rays / rt_radiance_rays_device: the path tracer on the caller's rays. Ray i is traced `samples` times on the streams
+        (seed, first_stream + i, first_sample .. first_sample + samples - 1); returns (rgb_sum, sq_sum, invalid): per ray the RGB sum of the
+        samples, the sum of their squares (both float32, shape (n, 3)) and a flag byte (RT_RAYHIT_INVALID_RAY for a ray that is never traced).
+
+        Host variant: `rays` is a numpy array of PATHRAY_DTYPE (or float32 of shape (n, 8): o, time, d, and first_draw's bits); numpy results.
+        Device variant: `rays` is a contiguous float32 CUDA tensor of shape (n, 8); CUDA tensors. rgb_sum / sq_sum / invalid receive the
+        results when given (same kind, 3 n / 3 n / n elements); accumulate=True folds on from the sums they hold. A refused call raises RtError
+        and leaves them untouched. options: an RtRadianceOptions to pass as it is (radiance_options). with_stats: also return the stats."""
+        st = A.RtStats()
+        if options is None:
+            options = radiance_options(samples, max_depth, seed, first_sample, first_stream, accumulate, nan_policy, pool_slots, tail_paths)
+        acc = bool(options.flags & A.RT_RADIANCE_ACCUMULATE)
+        if acc and (rgb_sum is None or sq_sum is None):
+            raise ValueError("accumulate needs the rgb_sum and sq_sum of the samples so far")
+        if hasattr(rays, "data_ptr"):
+            import torch
+            if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
+                raise ValueError("device rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
+            n = rays.shape[0]
+            if rgb_sum is None:
+                rgb_sum = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+            if sq_sum is None:
+                sq_sum = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+            if invalid is None:
+                invalid = torch.empty((n,), dtype=torch.uint8, device=rays.device)
+            _check_device(rgb_sum, sq_sum, 3 * n, "rgb_sum / sq_sum", True)
+            if not invalid.is_cuda or invalid.dtype != torch.uint8 or not invalid.is_contiguous() or invalid.numel() != n:
+                raise ValueError("invalid must be a contiguous uint8 CUDA tensor of n elements")
+            if rays.device.index != self.device_id or any(t.device != rays.device for t in (rgb_sum, sq_sum, invalid)):
+                raise ValueError(f"rays and outputs must live on this context's device (cuda:{self.device_id})")
+            torch.cuda.synchronize(rays.device)           # the library's stream is not torch's
+            ptr = lambda t: C.c_void_p(t.data_ptr() if n else None)
+            _check(lib().rt_radiance_rays_device(self._h, scene._h, C.byref(options), ptr(rays), n, ptr(rgb_sum), ptr(sq_sum), ptr(invalid), C.byref(st)), self._h)
+        else:
+            rays = np.asarray(rays)
+            if rays.dtype != PATHRAY_DTYPE:
+                if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+                    raise ValueError("host rays must be a numpy array of PATHRAY_DTYPE, or float32 of shape (n, 8)")
+                rays = np.ascontiguousarray(rays).view(PATHRAY_DTYPE).reshape(-1)
+            rays = np.ascontiguousarray(rays).reshape(-1)
+            n = rays.shape[0]
+            if rgb_sum is None:
+                rgb_sum = np.empty((n, 3), dtype=np.float32)
+            if sq_sum is None:
+                sq_sum = np.empty((n, 3), dtype=np.float32)
+            if invalid is None:
+                invalid = np.empty(n, dtype=np.uint8)
+            for a, dt, k, what in ((rgb_sum, np.float32, 3 * n, "rgb_sum"), (sq_sum, np.float32, 3 * n, "sq_sum"), (invalid, np.uint8, n, "invalid")):
+                if not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous or a.size != k:
+                    raise ValueError(f"{what} must be a C-contiguous numpy array of {k} {np.dtype(dt).name}")
+            ptr = lambda a: C.c_void_p(a.ctypes.data if n else None)
+            _check(lib().rt_radiance_rays(self._h, scene._h, C.byref(options), ptr(rays), n, ptr(rgb_sum), ptr(sq_sum), ptr(invalid), C.byref(st)), self._h)
+        return (rgb_sum, sq_sum, invalid, st.as_dict()) if with_stats else (rgb_sum, sq_sum, invalid)
 
     # ---- first-hit features (include/rt_hip.h, "first-hit features"): device tensors only ----
     def render_features(self, scene, cam, params, first_sample=0, accumulate=False, albedo=None, normal=None, depth=None, hits=None, pool_slots=0,

@@ -247,6 +247,22 @@ hipError_t launch_features_fold(const RenderDev& rd, const FeatDev& fd, hipStrea
 // own block beside FeatDev, so that the kernels which take FeatDev alone keep their arguments.
 struct FeatMomDev { float* albedo_sq; float* normal_sq; float* depth_sq; };
 hipError_t launch_features_fold_moments(const RenderDev& rd, const FeatDev& fd, const FeatMomDev& fm, hipStream_t stream);
+// radiance queries (kernels.hip "radiance queries"). RadianceDev: one chunk of a query — samples [rd.first_sample, rd.first_sample + n_samples)
+// of rays [ray0, ray0 + n) of the caller's list — as a pixel-list pass over a virtual unsharded frame whose pixel index is the ray's STREAM:
+// item blk * n + i is sample blk of ray ray0 + i, which runs on stream (pixel) stream0 + i. Its own block, like RaySrcDev and FeatDev.
+struct RadianceDev {
+    const void* rays;           // the caller's RtPathRay records (32 bytes each), the whole list
+    uint64_t ray0;              // first ray of the chunk
+    uint32_t n, n_samples;      // rays and samples of the chunk; n * n_samples <= kQueues * rd.queue_cap
+    FastDiv div_n;
+    uint32_t stream0;           // stream of ray ray0; (stream0 + n) * n_samples <= 2^32 - 1 (the item id, kernels.hip item_id)
+    uint32_t* iota;             // [n], written here: iota[i] = i. The pass's rd.list is this table and its rd.list_map is (iota - stream0)
+    uint8_t* invalid;           // the caller's flag bytes, the whole list (nullptr = not wanted)
+};
+// the chunk's rays as full path records into `pool` (T = 1, the ray starts on nothing, first_draw draws made), spread over its queues; `counts`
+// (zeroed by the caller) receives the queues' sizes, counters[CTR_SAMPLES] counts the paths DROPPED. An invalid ray is dropped: its flag byte is
+// written, and its items' sums in rd.blocksum are zero. rd: the pass's RenderDev (n_blocks = n_samples, queue geometry, blocksum, first_in_shade).
+hipError_t launch_radiance_import(const RenderDev& rd, const RadianceDev& qd, const PoolDev& pool, uint32_t* counts, unsigned long long* counters, hipStream_t stream);
 // multi-GPU root: gathered shard buffers -> full frame (rt_multi.cpp)
 hipError_t launch_untile_f32(const float* gathered, float* frame, uint32_t width, uint32_t height, uint32_t ts, uint32_t tiles_x, uint32_t world, uint64_t per_shard,
                              hipStream_t stream);

@@ -2865,6 +2865,52 @@ __global__ void __launch_bounds__(256) k_features_fold_moments(RenderDev rd, Fea
 }
 
 // ------------------------------------------------------------------------------------------------
+// radiance queries (rt_hip.h "radiance queries"): caller's rays -> full path records -> the render's own loop
+// ------------------------------------------------------------------------------------------------
+// A chunk is a pixel-list pass (LIST instances of k_shade and of the drain, k_resolve_list) over a virtual unsharded frame 65536 pixels wide
+// whose pixel index is the ray's STREAM: item blk * n + i of the chunk is sample rd.first_sample + blk of ray ray0 + i, and its path carries the
+// item id (stream0 + i) * n_blocks + blk, from which path_rng and the medium key decode (stream, sample) as they decode (pixel, sample) for a
+// render. The pass's rd.lineage is >= rd.total_items, so no path of it is ever regenerated and neither rd.list's decode nor the camera is read.
+// k_radiance_import is k_rays_import's twin for the 32-byte RtPathRay records: thread t = blk * n + i of the chunk reads ray ray0 + i and stores
+// what k_generate stores for a fresh path — T = 1, from = 0 (the ray starts on nothing), depth 0 — with sd = first_draw << 8: the stream stands
+// where a caller who spent first_draw draws on making the ray left it. Where rd.first_in_shade is set the time slot carries first_sphere_hit,
+// as k_generate's does. Workgroup b feeds queue b mod kQueues; slots from the queue's size counter; the host keeps n * n_samples <=
+// kQueues * queue_cap. DROPPED, never stored: a ray query_ray_valid refuses, or whose first_draw is >= 2^16. Its items' sums are written here —
+// minus zero, so that the fold leaves an accumulated sum as it was, bit for bit, and starts a fresh one at +0 — and the thread of its sample 0
+// writes the flag byte (0 for a stored ray) and the chunk's iota table (kernels.h RadianceDev). counters[CTR_SAMPLES] counts the paths dropped.
+__global__ void __launch_bounds__(kRaysImportThreads) k_radiance_import(RenderDev rd, RadianceDev qd, PoolDev pool, uint32_t* __restrict__ counts,
+                                                                         unsigned long long* __restrict__ counters) {
+    __shared__ uint32_t s_scan[kRaysImportThreads / 64 + 1];
+    const uint32_t t = blockIdx.x * kRaysImportThreads + threadIdx.x, q = blockIdx.x & (kQueues - 1u);
+    const uint32_t blk = fdivu(t, qd.div_n), i = t - blk * qd.n;
+    const bool mine = blk < qd.n_samples;
+    Float4 ro = Float4{0.f, 0.f, 0.f, 0.f}, rdv = Float4{0.f, 0.f, 0.f, 0.f};
+    if (mine) { const Float4* r = (const Float4*)qd.rays + 2ull * (qd.ray0 + i); ro = r[0]; rdv = r[1]; }
+    const uint32_t first_draw = __float_as_uint(rdv.w);
+    const bool valid = mine && query_ray_valid(ro, rdv) && first_draw < 65536u;
+    const uint32_t slot = block_alloc(valid, counts + q * kQStride, s_scan);      // every thread of the workgroup calls it
+    const bool stored = valid && slot < rd.queue_cap;
+    if (stored) {
+        const V3 o = v3(ro.x, ro.y, ro.z), d = v3(rdv.x, rdv.y, rdv.z);
+        float tm = ro.w;
+        if (rd.first_in_shade != 0u) tm = first_sphere_hit(rd, o, d, 0u);         // (the time slot of a motionless scene: kernels.h)
+        PathState s;
+        s.T = v3(1, 1, 1); s.acc = v3(0, 0, 0);
+        s.work = (qd.stream0 + i) * rd.n_blocks + blk; s.sample = rd.first_sample + blk; s.from = 0u;
+        store_path(pool, q * rd.queue_cap + slot, o, d, tm, s, first_draw, 0u, false);
+    }
+    if (mine && !stored) rd.blocksum[t] = Float4{-0.f, -0.f, -0.f, 0.f};
+    if (mine && blk == 0u) {
+        qd.iota[i] = i;
+        if (qd.invalid != nullptr) qd.invalid[qd.ray0 + i] = stored ? (uint8_t)0 : (uint8_t)kRayHitInvalid;
+    }
+    // counted: the paths DROPPED. A wave without an invalid ray — every wave of an ordinary call — makes no atomic (one per wave on the paths stored
+    // was 360 000 same-address atomics for 23 M paths: the kernel took 4.33 ms, and takes 0.26 without them; k_generate 0.24: DESIGN.md section 16)
+    const uint64_t m = __ballot(mine && !stored);
+    if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(&counters[CTR_SAMPLES], (unsigned long long)__popcll(m));
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 static thread_local const char* g_launch_note = nullptr;
@@ -3192,6 +3238,17 @@ hipError_t launch_features_fold_moments(const RenderDev& rd, const FeatDev& fd, 
     const uint32_t blocks = (fd.ns + 255u) / 256u;
     if (blocks == 0u) return hipSuccess;
     hipLaunchKernelGGL(k_features_fold_moments, dim3(blocks), dim3(256), 0, stream, rd, fd, fm);
+    return hipGetLastError();
+}
+
+hipError_t launch_radiance_import(const RenderDev& rd, const RadianceDev& qd, const PoolDev& pool, uint32_t* counts, unsigned long long* counters, hipStream_t stream) {
+    const uint64_t items = (uint64_t)qd.n * qd.n_samples;
+    if (items == 0u) return hipSuccess;
+    // (k_radiance_import: a slot is < queue_cap, an item's sum lies inside blocksum, an item id fits 32 bits)
+    if (items > (uint64_t)kQueues * rd.queue_cap || (rd.queue_cap & 511u) != 0u || items != rd.total_items || qd.n_samples != rd.n_blocks ||
+        ((uint64_t)qd.stream0 + qd.n) * qd.n_samples > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const uint32_t blocks = (uint32_t)((items + kRaysImportThreads - 1u) / kRaysImportThreads);
+    hipLaunchKernelGGL(k_radiance_import, dim3(blocks), dim3(kRaysImportThreads), 0, stream, rd, qd, pool, counts, counters);
     return hipGetLastError();
 }
 

@@ -874,6 +874,78 @@ static rtk::RenderDev frame_render_dev(const RtScene* scene, const RtCamera* cam
     return rd;
 }
 
+// The tail of a wavefront loop goes to the drain kernel: once at most this many paths are alive, ONE launch carries each of them to its end
+// (kernels.hip DRAIN). `fused` (RT_FLAG_FUSED) hands the whole render to it (a diagnostic: bit-identical frame, slower).
+// Measured on the bench workload (LDS-resident scene): hand-over at 2^18 paths 103.2 ms, never 104.1, at 2^21 106.5, at 2^24 121. Scene in
+// HBM (config-5 stand-in, 2048^2 x 32, near-first record orders): 2^18 126.0 ms, 2^20 126.2, 2^21 131.7, 2^22 143.4, 2^24 193.8. (With ONE
+// record order a k_extend launch of that scene did not get shorter than 1.5-2 ms however few rays it carried — the longest far-first walk
+// of the launch — and 2^21 was the best hand-over: 185.9 ms against 211.5 at 2^18.)
+static uint32_t drain_threshold(const RtScene* scene, uint32_t tail_paths, bool fused) {
+    uint32_t drain_at = tail_paths ? tail_paths : (1u << 18);                    // RtParams.tail_paths (1 = never: a pool holds 8 queues of >= 1 path)
+    // the 8-wide walk resolves hits that tie within rounding in its own way; handing a tail to the per-path kernel (binary records) would
+    // make such pixels depend on WHEN the hand-over happens, so a wide scene's wavefront loop runs to its end
+    if (scene->dev.wide != nullptr) drain_at = 0u;
+    if (fused) drain_at = 0xFFFFFFFFu;
+    return drain_at;
+}
+
+// The wavefront loop over the pool's kQueues queues, from a first fill of n_init paths in pd[0] (whose queue sizes are in cb.count[0]) until no
+// path is alive: launch pairs of k_extend and k_shade, then the drain (render_impl and radiance_impl; rd is the pass's RenderDev).
+// launched += the launch pairs; drained = the bound of the paths handed to the drain kernel (0: the loop ran to its end).
+// The host never waits for an iteration it has just enqueued: the kernels read the pool size from device memory and size-check
+// themselves, so the host only needs (a) an UPPER BOUND of the pool size to size k_shade's grid and (b) to learn that it has
+// reached 0. After every iteration the size is copied to a pinned ring slot behind an event; before enqueuing the next
+// iteration the host takes whatever copies have landed (the size never grows, so an older value is a valid bound) and blocks
+// only when it is kAhead iterations ahead. (Batches of 4, 8, 16, 32 iterations with a blocking read in between sized eight
+// launches of k_shade by the 268 M paths of the start while 5 M were alive — 0.6 ms each for empty workgroups.)
+static int wavefront_loop(RtCtx* ctx, const RtScene* scene, const rtk::RenderDev& rd, const rtk::PoolDev pd[2], const CounterBlock& cb, rtk::LaunchCfg& cfg, StreamTimer& tm,
+                          bool timing, bool counting, uint32_t drain_at, uint32_t n_init, uint32_t& launched, uint32_t& drained) {
+    constexpr uint32_t kAhead = 3, kRing = 4;
+    // upper bound of the size of the LARGEST queue from here on (a queue never grows): it sizes the grids, and 0 ends the render
+    uint32_t live = std::min<uint32_t>(rd.queue_cap, (n_init + rtk::kQueues - 1u) / rtk::kQueues + 512u);
+    uint32_t iterations = 0u;
+    int cur = 0;
+    struct Pending { hipEvent_t ev; uint32_t ring; };
+    std::vector<Pending> pending; size_t head = 0;
+    auto take = [&](const Pending& pd_) {
+        uint32_t m = 0; for (uint32_t k = 0; k < rtk::kQueues; ++k) m = std::max(m, ctx->h_count[pd_.ring * rtk::kQueues + k]);
+        live = std::min(live, m);
+    };
+    for (;;) {
+        while (head < pending.size() && hipEventQuery(pending[head].ev) == hipSuccess) take(pending[head++]);
+        if (live != 0u && pending.size() - head >= kAhead) {
+            HIP_TRY(ctx, hipEventSynchronize(pending[head].ev));
+            take(pending[head++]);
+        }
+        if (live == 0u) break;
+        if ((uint64_t)live * rtk::kQueues <= drain_at) {
+            hipEvent_t ea = nullptr, eb = nullptr;
+            if (timing) HIP_TRY(ctx, tm.mark(ea));
+            LAUNCH_TRY(rtk::launch_drain(cfg, scene->dev, pd[cur], rd, live, cb.count[cur], cb.head, cb.count[1 - cur], cb.c64, counting, ctx->stream));
+            if (timing) { HIP_TRY(ctx, tm.mark(eb)); tm.span(ea, eb, 3); }
+            drained = live * rtk::kQueues;
+            break;
+        }
+        hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr;
+        if (timing) HIP_TRY(ctx, tm.mark(ea));
+        cfg.max_rays = (uint32_t)std::min<uint64_t>((uint64_t)live * rtk::kQueues, 0xFFFFFFFFull);
+        LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd[cur], rd, cb.count[cur], cb.head, cb.count[1 - cur], cb.c64, counting, ctx->stream));
+        if (timing) HIP_TRY(ctx, tm.mark(eb));
+        HIP_TRY(ctx, rtk::launch_shade(cfg, scene->dev, pd[cur], pd[1 - cur], rd, live, cb.count[cur], cb.count[1 - cur], cb.head, cb.c64, counting, ctx->stream));
+        if (timing) { HIP_TRY(ctx, tm.mark(ec)); tm.span(ea, eb, 0); tm.span(eb, ec, 1); }
+        cur = 1 - cur;
+        const uint32_t ring = iterations % kRing;
+        HIP_TRY(ctx, hipMemcpy2DAsync(ctx->h_count + ring * rtk::kQueues, sizeof(uint32_t), cb.count[cur], CounterBlock::kLine, sizeof(uint32_t), rtk::kQueues, hipMemcpyDeviceToHost,
+                                      ctx->stream));   // the kQueues pool sizes, one per line
+        hipEvent_t ev = nullptr;
+        HIP_TRY(ctx, tm.mark(ev));
+        pending.push_back({ev, ring});
+        ++launched;
+        if (++iterations > 100000000u) return set_err(ctx, RT_ERR_DEVICE, "render loop did not terminate");
+    }
+    return RT_OK;
+}
+
 static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtPassOptions& pass, void* d_out, void* d_sq, RtStats* stats,
                        const ListPass* lp) {
     using clk = std::chrono::steady_clock;
@@ -981,67 +1053,9 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     }
     HIP_TRY(ctx, rtk::launch_generate(pd[0], rd, n_init, cb.count[0], ctx->stream));
     if (timing) { HIP_TRY(ctx, tm.mark(e1)); tm.span(e0, e1, 2); }
-    // The host never waits for an iteration it has just enqueued: the kernels read the pool size from device memory and size-check
-    // themselves, so the host only needs (a) an UPPER BOUND of the pool size to size k_shade's grid and (b) to learn that it has
-    // reached 0. After every iteration the size is copied to a pinned ring slot behind an event; before enqueuing the next
-    // iteration the host takes whatever copies have landed (the size never grows, so an older value is a valid bound) and blocks
-    // only when it is kAhead iterations ahead. (Batches of 4, 8, 16, 32 iterations with a blocking read in between sized eight
-    // launches of k_shade by the 268 M paths of the start while 5 M were alive — 0.6 ms each for empty workgroups.)
-    constexpr uint32_t kAhead = 3, kRing = 4;
-    // The tail goes to the drain kernel: once at most `drain_at` paths are alive, ONE launch carries each of them to its end
-    // (kernels.hip DRAIN). RT_FLAG_FUSED hands the whole render to it (a diagnostic: bit-identical frame, slower).
-    // Measured on the bench workload (LDS-resident scene): hand-over at 2^18 paths 103.2 ms, never 104.1, at 2^21 106.5, at 2^24 121. Scene in
-    // HBM (config-5 stand-in, 2048^2 x 32, near-first record orders): 2^18 126.0 ms, 2^20 126.2, 2^21 131.7, 2^22 143.4, 2^24 193.8. (With ONE
-    // record order a k_extend launch of that scene did not get shorter than 1.5-2 ms however few rays it carried — the longest far-first walk
-    // of the launch — and 2^21 was the best hand-over: 185.9 ms against 211.5 at 2^18.)
-    uint32_t drain_at = prm->tail_paths ? prm->tail_paths : (1u << 18);          // RtParams.tail_paths (1 = never: a pool holds 8 queues of >= 1 path)
-    // the 8-wide walk resolves hits that tie within rounding in its own way; handing a tail to the per-path kernel (binary records) would
-    // make such pixels depend on WHEN the hand-over happens, so a wide scene's wavefront loop runs to its end
-    if (scene->dev.wide != nullptr) drain_at = 0u;
-    if (prm->flags & RT_FLAG_FUSED) drain_at = 0xFFFFFFFFu;
-
-    // ---- the wavefront loop over the pool's kQueues queues ----------------------------------------------------------------------------------
-    // upper bound of the size of the LARGEST queue from here on (a queue never grows): it sizes the grids, and 0 ends the render
-    uint32_t live = std::min<uint32_t>(rd.queue_cap, (n_init + rtk::kQueues - 1u) / rtk::kQueues + 512u);
     uint32_t launched = 0u, drained = 0u;
-    int cur = 0;
-    struct Pending { hipEvent_t ev; uint32_t ring; };
-    std::vector<Pending> pending; size_t head = 0;
-    auto take = [&](const Pending& pd_) {
-        uint32_t m = 0; for (uint32_t k = 0; k < rtk::kQueues; ++k) m = std::max(m, ctx->h_count[pd_.ring * rtk::kQueues + k]);
-        live = std::min(live, m);
-    };
-    for (;;) {
-        while (head < pending.size() && hipEventQuery(pending[head].ev) == hipSuccess) take(pending[head++]);
-        if (live != 0u && pending.size() - head >= kAhead) {
-            HIP_TRY(ctx, hipEventSynchronize(pending[head].ev));
-            take(pending[head++]);
-        }
-        if (live == 0u) break;
-        if ((uint64_t)live * rtk::kQueues <= drain_at) {
-            hipEvent_t ea = nullptr, eb = nullptr;
-            if (timing) HIP_TRY(ctx, tm.mark(ea));
-            LAUNCH_TRY(rtk::launch_drain(cfg, scene->dev, pd[cur], rd, live, cb.count[cur], cb.head, cb.count[1 - cur], cb.c64, counting, ctx->stream));
-            if (timing) { HIP_TRY(ctx, tm.mark(eb)); tm.span(ea, eb, 3); }
-            drained = live * rtk::kQueues;
-            break;
-        }
-        hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr;
-        if (timing) HIP_TRY(ctx, tm.mark(ea));
-        cfg.max_rays = (uint32_t)std::min<uint64_t>((uint64_t)live * rtk::kQueues, 0xFFFFFFFFull);
-        LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd[cur], rd, cb.count[cur], cb.head, cb.count[1 - cur], cb.c64, counting, ctx->stream));
-        if (timing) HIP_TRY(ctx, tm.mark(eb));
-        HIP_TRY(ctx, rtk::launch_shade(cfg, scene->dev, pd[cur], pd[1 - cur], rd, live, cb.count[cur], cb.count[1 - cur], cb.head, cb.c64, counting, ctx->stream));
-        if (timing) { HIP_TRY(ctx, tm.mark(ec)); tm.span(ea, eb, 0); tm.span(eb, ec, 1); }
-        cur = 1 - cur;
-        const uint32_t ring = launched % kRing;
-        HIP_TRY(ctx, hipMemcpy2DAsync(ctx->h_count + ring * rtk::kQueues, sizeof(uint32_t), cb.count[cur], CounterBlock::kLine, sizeof(uint32_t), rtk::kQueues, hipMemcpyDeviceToHost,
-                                      ctx->stream));   // the kQueues pool sizes, one per line
-        hipEvent_t ev = nullptr;
-        HIP_TRY(ctx, tm.mark(ev));
-        pending.push_back({ev, ring});
-        if (++launched > 100000000u) return set_err(ctx, RT_ERR_DEVICE, "render loop did not terminate");
-    }
+    { const int r = wavefront_loop(ctx, scene, rd, pd, cb, cfg, tm, timing, counting, drain_threshold(scene, prm->tail_paths, (prm->flags & RT_FLAG_FUSED) != 0u), n_init, launched, drained);
+      if (r != RT_OK) return r; }
     hipEvent_t r0 = nullptr, r1 = nullptr;
     if (timing) HIP_TRY(ctx, tm.mark(r0));
     if (sc > 1 && !rd.accumulate && !lp) {   // clipped pixels of edge tiles stay 0 (an accumulating pass finds them 0 from its first pass; a list pass writes listed slots only)
@@ -1426,6 +1440,170 @@ int rt_sample_lights(RtCtx* ctx, const RtScene* scene, const RtLightQueryOptions
     const int r = rt_sample_lights_device(ctx, scene, options, ctx->rays_tmp.p, n, ctx->hits_tmp.p, stats);
     if (r != RT_OK) return r;
     HIP_TRY(ctx, hipMemcpyAsync(results_host, ctx->hits_tmp.p, (size_t)n * sizeof(RtLightSample), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT_OK;
+}
+
+// ---- radiance queries (include/rt_hip.h): caller's rays through the render's own path loop, per-ray sums over a sample range ------------------
+static_assert(sizeof(RtPathRay) == 32 && sizeof(RtRadianceOptions) == 56, "radiance query records: 32 and 56 bytes");
+// first_stream + n_rays may reach this: a path's 32-bit item id is stream * (samples in its chunk) + sample of the chunk (radiance_impl), and a
+// chunk of one sample must be able to hold the call's last stream
+constexpr uint64_t kMaxStreams = 0xFFFFFFFFull;
+static int check_radiance(RtCtx* ctx, const RtRadianceOptions* o, uint64_t n_rays) {
+    if (!o) return set_err(ctx, RT_ERR_INVALID, "radiance options are null");
+    if (o->struct_bytes < sizeof(RtRadianceOptions) || o->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtRadianceOptions.struct_bytes is not set (sizeof(RtRadianceOptions))");
+    if (o->flags & ~(uint32_t)RT_RADIANCE_ACCUMULATE) return set_err(ctx, RT_ERR_INVALID, "RtRadianceOptions.flags holds an unknown bit");
+    if (o->render_flags & ~(uint32_t)RT_FLAG_TIMING) return set_err(ctx, RT_ERR_INVALID, "RtRadianceOptions.render_flags holds an unknown bit (known: RT_FLAG_TIMING)");
+    if (o->nan_policy > 1) return set_err(ctx, RT_ERR_INVALID, "bad nan_policy");
+    if (o->samples == 0u) return set_err(ctx, RT_ERR_INVALID, "samples must be >= 1");
+    if ((uint64_t)o->first_sample + o->samples > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "first_sample + samples must be < 2^32");
+    if (o->max_depth == 0 || o->max_depth > 255) return set_err(ctx, RT_ERR_INVALID, "max_depth must be in 1..255");
+    if (n_rays > kMaxStreams || o->first_stream > kMaxStreams || o->first_stream + n_rays > kMaxStreams)
+        return set_err(ctx, RT_ERR_INVALID, "first_stream + n_rays must be <= 2^32 - 1 (a stream index is 32 bits; split the list, or choose streams below that)");
+    return RT_OK;
+}
+int rt_radiance_check(const RtRadianceOptions* options, uint64_t n_rays) { return check_radiance(nullptr, options, n_rays); }
+
+// The chunk loop. A chunk — rays [r0, r0 + n) x samples [s0, s0 + sc) of the call — is a pixel-list pass of the render loop over a virtual
+// unsharded frame 65536 pixels wide whose pixel index is the ray's stream (kernels.hip "radiance queries"): k_radiance_import fills the pool
+// (no k_generate: the rays are the caller's), wavefront_loop runs it empty, k_resolve_list folds the chunk's item sums into the caller's
+// sums. The list of such a pass is the run of streams [stream0, stream0 + n): rd.list is the iota table (entry i -> output slot i of the
+// buffers offset to r0), and rd.list_map, which takes a stream back to its entry, is the same table addressed from stream0 entries before
+// its start — never dereferenced outside [stream0, stream0 + n). Rays are chunked first and samples second, so that every path of a chunk
+// is in flight at once (lineage = the chunk's items: nothing is ever regenerated) and (stream0 + n) * sc fits the 32-bit item id; a later
+// sample chunk accumulates on the earlier ones, which continues the same sequential fold: the sums do not depend on the chunking.
+static int radiance_impl(RtCtx* ctx, const RtScene* scene, const RtRadianceOptions* opt, const void* d_rays, uint64_t n_rays, void* d_rgb, void* d_sq, void* d_invalid,
+                         RtStats* stats) {
+    using clk = std::chrono::steady_clock;
+    const auto t_begin = clk::now();
+    const bool timing = (opt->render_flags & RT_FLAG_TIMING) != 0u;
+    const uint32_t S = opt->samples;
+    // the ray queries' pool rule over the call's items; per slot: both pools, the item's sum, and its share of the tables below
+    const uint64_t items = n_rays * (uint64_t)S;
+    const uint32_t P = pool_grain(pool_size(opt->pool_slots, items, 2 * pool_slot_bytes(5) + 16 + 8,
+                                            ctx->blocksum.bytes + ctx->list_map.bytes + pool_held_bytes(ctx, 0, 5) + pool_held_bytes(ctx, 1, 5), 0));
+    rtk::PoolDev pd[2];
+    for (int k = 0; k < 2; ++k) { const int r = pool_bind(ctx, k, P, 5, pd[k]); if (r != RT_OK) return r; }
+    const uint32_t n_chunk = (uint32_t)std::min<uint64_t>(n_rays, P);                       // rays of a chunk
+    const uint32_t s_chunk = (uint32_t)std::min<uint64_t>(S, std::max<uint32_t>(1u, P / n_chunk));   // samples of a chunk, at most
+    HIP_TRY(ctx, ctx->blocksum.ensure((size_t)n_chunk * s_chunk * 16));
+    HIP_TRY(ctx, ctx->list_map.ensure((size_t)n_chunk * 8u));   // [0, n): the iota table; [n, 2n): where k_resolve_list's counts[] go (nobody reads them)
+    CounterBlock cb;
+    HIP_TRY(ctx, cb.ensure(ctx));
+    HIP_TRY(ctx, cb.zero_all());
+
+    rtk::RenderDev rd{};
+    rd.width = 65536u; rd.height = 65536u; rd.div_width = rtk::make_fastdiv(65536u);       // pixel (stream) = y * 65536 + x, every u32
+    rd.shard_count = 1u; rd.shard_index = 0u; rd.tile_size = 32u; rd.tiles_x = 2048u; rd.tiles_y = 2048u;
+    rd.div_ts = rtk::make_fastdiv(32u); rd.div_ts2 = rtk::make_fastdiv(1024u); rd.div_tiles_x = rtk::make_fastdiv(2048u); rd.div_shards = rtk::make_fastdiv(1u);
+    rd.div_sq_row = rtk::make_fastdiv(4u); rd.div_item_tile = rtk::make_fastdiv(1024u); rd.div_row_items = rtk::make_fastdiv(1u);
+    rd.seed = opt->seed; rd.max_depth = opt->max_depth; rd.nan_policy = opt->nan_policy;
+    rd.bg_mode = scene->bg_mode; for (int i = 0; i < 3; ++i) rd.bg[i] = scene->bg[i];
+    rd.block_shift = 0u;                                                                     // one sample per item: nothing regenerates, no camera is read
+    rd.queue_cap = P / rtk::kQueues; rd.q_lo = 0u; rd.q_n = rtk::kQueues; rd.q_shift = rtk::kQShift;
+    rd.first_in_shade = scene->first_id != 0u && rtk::can_test_first_in_shade(scene->features) ? 1u : 0u;
+    rd.first_id = scene->first_id; for (int k = 0; k < 8; ++k) rd.first_prim[k] = scene->first_prim[k];
+    rd.blocksum = (rtd::Float4*)ctx->blocksum.p;
+    uint32_t* const iota = (uint32_t*)ctx->list_map.p;
+    rd.list = iota; rd.counts = iota + n_chunk;
+
+    rtk::LaunchCfg cfg{};
+    uint32_t extend_geometry[2] = {0u, 0u};
+    cfg.n_cu = (uint32_t)ctx->n_cu; cfg.extend_geometry = extend_geometry; cfg.features = scene->features; cfg.scene_in_lds = scene->in_lds;
+    const uint32_t drain_at = drain_threshold(scene, opt->tail_paths, false);
+    StreamTimer tm{ctx};
+    uint32_t launched = 0u, drained = 0u;
+    bool first_chunk = true;
+    for (uint64_t r0 = 0; r0 < n_rays; r0 += n_chunk) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(n_chunk, n_rays - r0);
+        const uint64_t stream0 = opt->first_stream + r0;
+        for (uint32_t s0 = 0; s0 < S;) {
+            const uint32_t sc = (uint32_t)std::min<uint64_t>(std::min<uint32_t>(s_chunk, S - s0), 0xFFFFFFFFull / (stream0 + n));   // >= 1: check_radiance
+            rd.first_sample = opt->first_sample + s0; rd.spp = rd.first_sample + sc;
+            rd.n_blocks = sc; rd.div_nblocks = rtk::make_fastdiv(sc);
+            rd.total_items = n * sc; rd.n_init = rd.total_items; rd.lineage = rd.total_items;
+            rd.n_list = n; rd.div_list = rtk::make_fastdiv(n);
+            rd.list_map = (const uint32_t*)((uintptr_t)iota - 4ull * stream0);   // list_map[stream0 + i] = iota[i] = i
+            rd.accumulate = ((opt->flags & RT_RADIANCE_ACCUMULATE) != 0u || s0 != 0u) ? 1u : 0u;
+            rd.sq_sum = d_sq ? (float*)d_sq + 3ull * r0 : nullptr;
+            rtk::RadianceDev qd{};
+            qd.rays = d_rays; qd.ray0 = r0; qd.n = n; qd.n_samples = sc; qd.div_n = rtk::make_fastdiv(n); qd.stream0 = (uint32_t)stream0;
+            qd.iota = iota; qd.invalid = (uint8_t*)d_invalid;
+            hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr, ed = nullptr;
+            if (!first_chunk) HIP_TRY(ctx, cb.zero_queue_lines());
+            first_chunk = false;
+            if (timing) HIP_TRY(ctx, tm.mark(ea));
+            LAUNCH_TRY(rtk::launch_radiance_import(rd, qd, pd[0], cb.count[0], cb.c64, ctx->stream));
+            if (timing) { HIP_TRY(ctx, tm.mark(eb)); tm.span(ea, eb, 2); }
+            { const int r = wavefront_loop(ctx, scene, rd, pd, cb, cfg, tm, timing, false, drain_at, rd.n_init, launched, drained); if (r != RT_OK) return r; }
+            if (timing) HIP_TRY(ctx, tm.mark(ec));
+            HIP_TRY(ctx, rtk::launch_resolve_list(rd, (float*)d_rgb + 3ull * r0, ctx->stream));
+            if (timing) { HIP_TRY(ctx, tm.mark(ed)); tm.span(ec, ed, 2); }
+            s0 += sc;
+        }
+    }
+    HIP_TRY(ctx, cb.read_stats(ctx));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) {
+        double part_ms[4] = {0.0, 0.0, 0.0, 0.0};                     // extend, shade, import and fold, drain
+        tm.sum(part_ms);
+        stats->extend_ms = part_ms[0]; stats->shade_ms = part_ms[1]; stats->other_ms = part_ms[2]; stats->drain_ms = part_ms[3];
+        stats->samples = items - ctx->h_counters[rtk::CTR_SAMPLES];    // less the paths the imports dropped: valid rays x samples
+        stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];
+        stats->iterations = (uint32_t)ctx->h_counters[rtk::CTR_ITERATIONS]; stats->extend_launches = launched; stats->shade_launches = launched; stats->pool_slots = P;
+        stats->drain_paths = drained;
+        scene_stats(stats, scene, extend_geometry);
+        stats->render_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
+    }
+    return RT_OK;
+}
+
+// the argument checks of both variants: a refused call has written nothing
+static int radiance_refuse(RtCtx* ctx, const RtScene* scene, const RtRadianceOptions* options, const void* rays, uint64_t n_rays, const void* rgb, const void* sq, bool device) {
+    if (!scene) return set_err(ctx, RT_ERR_INVALID, "scene is null");
+    const int v = check_radiance(ctx, options, n_rays); if (v != RT_OK) return v;
+    if (n_rays != 0u && (!rays || !rgb)) return set_err(ctx, RT_ERR_INVALID, "rays / rgb_sum is null");
+    if (device && ((((uintptr_t)rays) | ((uintptr_t)rgb) | ((uintptr_t)sq)) & 15u)) return set_err(ctx, RT_ERR_INVALID, "rays / rgb_sum / sq_sum must be 16-byte aligned");
+    return RT_OK;
+}
+
+int rt_radiance_rays_device(RtCtx* ctx, const RtScene* scene, const RtRadianceOptions* options, const void* rays_device, uint64_t n_rays, void* rgb_sum_device,
+                            void* sq_sum_device, void* invalid_device, RtStats* stats) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    const int v = radiance_refuse(ctx, scene, options, rays_device, n_rays, rgb_sum_device, sq_sum_device, true); if (v != RT_OK) return v;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n_rays == 0u) return RT_OK;
+    if (ctx->fail_renders != 0u) { --ctx->fail_renders; return set_err(ctx, RT_ERR_DEVICE, "injected failure (rt_test_fail_next_renders)"); }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return drain_on_failure(ctx, radiance_impl(ctx, scene, options, rays_device, n_rays, rgb_sum_device, sq_sum_device, invalid_device, stats));
+}
+// the host variant: rays (and, accumulating, the caller's sums) staged in, the device variant on the context's own buffers, the sums and flag
+// bytes staged out; render_ms covers all of it
+int rt_radiance_rays(RtCtx* ctx, const RtScene* scene, const RtRadianceOptions* options, const RtPathRay* rays_host, uint64_t n_rays, float* rgb_sum_host,
+                     float* sq_sum_host, uint8_t* invalid_host, RtStats* stats) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    const int v = radiance_refuse(ctx, scene, options, rays_host, n_rays, rgb_sum_host, sq_sum_host, false); if (v != RT_OK) return v;   // (host buffers are copied: no alignment asked)
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n_rays == 0u) return RT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t bytes = (size_t)n_rays * 3u * sizeof(float);
+    HIP_TRY(ctx, ctx->rays_tmp.ensure((size_t)n_rays * sizeof(RtPathRay)));
+    HIP_TRY(ctx, ctx->out_tmp.ensure(bytes));
+    if (sq_sum_host) HIP_TRY(ctx, ctx->sq_tmp.ensure(bytes));
+    if (invalid_host) HIP_TRY(ctx, ctx->hits_tmp.ensure((size_t)n_rays));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->rays_tmp.p, rays_host, (size_t)n_rays * sizeof(RtPathRay), hipMemcpyHostToDevice, ctx->stream));
+    if (options->flags & RT_RADIANCE_ACCUMULATE) {   // the fold goes on from the caller's sums
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->out_tmp.p, rgb_sum_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (sq_sum_host) HIP_TRY(ctx, hipMemcpyAsync(ctx->sq_tmp.p, sq_sum_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const int r = rt_radiance_rays_device(ctx, scene, options, ctx->rays_tmp.p, n_rays, ctx->out_tmp.p, sq_sum_host ? ctx->sq_tmp.p : nullptr,
+                                          invalid_host ? ctx->hits_tmp.p : nullptr, stats);
+    if (r != RT_OK) return r;
+    HIP_TRY(ctx, hipMemcpyAsync(rgb_sum_host, ctx->out_tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (sq_sum_host) HIP_TRY(ctx, hipMemcpyAsync(sq_sum_host, ctx->sq_tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (invalid_host) HIP_TRY(ctx, hipMemcpyAsync(invalid_host, ctx->hits_tmp.p, (size_t)n_rays, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return RT_OK;

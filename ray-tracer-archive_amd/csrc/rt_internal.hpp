@@ -50,7 +50,8 @@ struct RtCtx {
     rti::DevBuf comm_words;                      // status words of the agreement that precedes every exchange (rt_multi.cpp agree_on_status)
     uint32_t* h_words = nullptr;                 // pinned: the same words on the host
     hipEvent_t ev_gather[2] = {nullptr, nullptr}; // brackets the exchange (RtStats.gather_ms); made at the first gather, kept
-    rti::DevBuf list_map;                        // adaptive sampling: output slot -> list index of a list pass (rt_render_pass_pixels_device)
+    rti::DevBuf list_map;                        // adaptive sampling: output slot -> list index of a list pass (rt_render_pass_pixels_device);
+                                                 // radiance queries: a chunk's iota table and the words its fold's counts go to (rt_api.cpp radiance_impl)
     rti::DevBuf sel_masks, sel_offsets, adaptive_word;   // rt_adaptive_select's wave ballots and their scan; the list check's verdict / the list's length
     rti::DevBuf rays_tmp, hits_tmp;              // rt_trace_rays (host variant): the caller's rays and hits on their way to and from the device
     rti::DevBuf feature_rec;                     // rt_render_features_device: the per-ray feature records of a chunk between export and fold (kernels.h FeatDev)
