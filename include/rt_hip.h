@@ -447,7 +447,8 @@ typedef struct RtAdaptiveOptions {
 } RtAdaptiveOptions;
 /* Host only, no device: validates (params, options, first_sample, frame_samples): first_sample on a work-item boundary, <= frame_samples. */
 int rt_adaptive_check(const RtParams* params, const RtAdaptiveOptions* options, uint32_t first_sample, uint32_t frame_samples);
-/* pixels_device_out: room for rt_output_floats / 3 entries; *n_out = the list's length. Blocks until done. */
+/* pixels_device_out: room for rt_output_floats / 3 entries; *n_out = the list's length. Blocks until done. A shard that owns no tile has
+ * no slots: RT_OK, *n_out = 0, no buffer is read or written. */
 int rt_adaptive_select(RtCtx* ctx, const RtParams* params, const RtAdaptiveOptions* options, uint32_t first_sample, uint32_t frame_samples,
                        const void* rgb_sum_device, const void* sq_sum_device, const void* counts_device, void* pixels_device_out, uint32_t* n_out);
 int rt_render_pass_pixels_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* params, const RtPassOptions* options,

@@ -103,20 +103,13 @@ __global__ void __launch_bounds__(256) k_select_scatter(const unsigned long long
     out[offsets[p >> 6] + below] = p;
 }
 
-// k_write_color (kernels.hip) with spp = counts[pixel]
+// k_write_color (kernels.hip) with spp = counts[pixel]: the same write_color_byte (kernels.h); a pixel without a sample is black
 __global__ void __launch_bounds__(256) k_write_color_counts(const float* __restrict__ rgb_sum, const uint32_t* __restrict__ counts, uint32_t n_pixels,
                                                             uint8_t* __restrict__ rgb8) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pixels * 3u) return;
     const uint32_t spp = counts[i / 3u];
-    if (spp == 0u) { rgb8[i] = 0u; return; }
-    float c = rgb_sum[i];
-    if (c != c) c = 0.f;
-    const float scale = 1.0f / (float)spp;
-    c = sqrtf(scale * c);
-    c = c < 0.f ? 0.f : (c > 0.999f ? 0.999f : c);
-    const float q = 256.0f * c;
-    rgb8[i] = q != q ? (uint8_t)0 : (uint8_t)q;
+    rgb8[i] = spp == 0u ? (uint8_t)0 : write_color_byte(rgb_sum[i], spp);
 }
 
 }  // namespace

@@ -203,6 +203,18 @@ struct SelectArgs {
 };
 // wave ballots (masks: slots / 64 rounded up), one-workgroup scan of their popcounts (offsets, *n_out), scatter into out
 hipError_t launch_select(const SelectArgs& a, unsigned long long* masks, uint32_t* offsets, uint32_t* out, uint32_t* n_out, hipStream_t stream);
+// write_color (main.rs:141-169) of one channel sum, in the reference's f64, operation for operation (host/rt_host.hpp rt::write_color is
+// the definition): the body of k_write_color (kernels.hip) and of k_write_color_counts (adaptive.hip). In f32 the byte is off by one on
+// sums next to a byte's boundary (1703 of 10023 such inputs), a handful per 1200 x 800 frame.
+__device__ inline uint8_t write_color_byte(float sum, uint32_t spp) {
+    double c = (double)sum;
+    if (c != c) c = 0.0;
+    const double scale = 1.0 / (double)spp;
+    c = sqrt(scale * c);
+    c = c < 0.0 ? 0.0 : (c > 0.999 ? 0.999 : c);
+    const double q = 256.0 * c;
+    return q != q ? (uint8_t)0 : (uint8_t)q;   // Rust `as u8`: saturating, NaN -> 0
+}
 hipError_t launch_write_color_counts(const float* rgb_sum, const uint32_t* counts, uint32_t n_pixels, uint8_t* rgb8, hipStream_t stream);
 hipError_t launch_write_color(const float* rgb_sum, uint32_t n_pixels, uint32_t spp, uint8_t* rgb8, hipStream_t stream);
 // ray queries (kernels.hip "ray queries"). RaySrcDev: the RtHittable record every primitive came from, by kind (scene_compile.hpp) — its own

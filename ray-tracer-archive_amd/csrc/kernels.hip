@@ -2373,17 +2373,11 @@ __global__ void __launch_bounds__(256) k_resolve_list(RenderDev rd, float* __res
     rd.counts[slot] = rd.spp;
 }
 
-// write_color (main.rs:141-169) on the device
+// write_color (main.rs:141-169) on the device, in f64 as the reference computes it (kernels.h write_color_byte)
 __global__ void __launch_bounds__(256) k_write_color(const float* __restrict__ rgb_sum, uint32_t n_pixels, uint32_t spp, uint8_t* __restrict__ rgb8) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pixels * 3u) return;
-    float c = rgb_sum[i];
-    if (c != c) c = 0.f;
-    const float scale = 1.0f / (float)spp;
-    c = sqrtf(scale * c);
-    c = c < 0.f ? 0.f : (c > 0.999f ? 0.999f : c);
-    const float q = 256.0f * c;
-    rgb8[i] = q != q ? (uint8_t)0 : (uint8_t)q;   // Rust `as u8`: saturating, NaN -> 0
+    rgb8[i] = write_color_byte(rgb_sum[i], spp);
 }
 
 // Gathered shard buffers (shard s = tiles s, s + world, ...; each tile ts*ts pixels row-major, shards `per_shard` elements apart)

@@ -1173,6 +1173,7 @@ int rt_adaptive_select(RtCtx* ctx, const RtParams* prm, const RtAdaptiveOptions*
     a.rel_error = options->rel_error; a.abs_error = options->abs_error;
     a.width = prm->width; a.height = prm->height; a.shard_count = prm->shard_count <= 1u ? 1u : prm->shard_count; a.shard_index = prm->shard_count <= 1u ? 0u : prm->shard_index;
     a.tile_size = tl.ts; a.tiles_x = tl.tiles_x;
+    if (a.slots == 0u) return RT_OK;   // a shard that owns no tile: no kernel runs, so no count comes back (the word holds an earlier call's)
     const size_t n_waves = (a.slots + 63u) / 64u;
     HIP_TRY(ctx, ctx->sel_masks.ensure(n_waves * 8u));
     HIP_TRY(ctx, ctx->sel_offsets.ensure(n_waves * 4u));
