@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _abi as A
 from .api import adaptive_check, adaptive_options, output_floats, pass_check
-from .progressive import CHECKPOINT_VERSION, camera_array, check_checkpoint, params_array, params_from_array
+from .progressive import CHECKPOINT_VERSION, camera_array, check_checkpoint, denoise_front, on_device, params_array, params_from_array
 
 KIND = "adaptive"
 ADAPTIVE_VERSION = 1
@@ -221,8 +221,7 @@ class Adaptive:
         if p.shard_count <= 1:
             rgb, cnt = self._rgb, self._counts
         else:
-            rgb = torch.from_numpy(np.ascontiguousarray(self.rgb_sum()).reshape(-1)).to(dev)
-            cnt = torch.from_numpy(np.ascontiguousarray(self.counts()).view(np.int32).reshape(-1)).to(dev)
+            rgb, cnt = on_device(self.rgb_sum(), dev), on_device(self.counts().view(np.int32), dev)
         out = torch.empty(p.height * p.width * 3, dtype=torch.uint8, device=dev)
         self.ctx.resolve_counts_device(rgb, cnt, p.width, p.height, out)
         return out.cpu().numpy().reshape(p.height, p.width, 3)
@@ -235,20 +234,10 @@ class Adaptive:
         feature_variance=True with feature_samples = N >= 2: the pass keeps the features' second moments (Context.render_feature_moments)
         and the filter is rt_denoise_guided_moments_device (sigmas and variance_strength: RtDenoiseGuideMoments, 0 = the default;
         window_radius 0 = 8, at most 8)."""
-        from .denoise import denoise_frame, render_guide
-        if feature_variance and int(feature_samples) < 2:
-            raise ValueError("feature_variance needs feature_samples >= 2")
-        import torch
-        p, dev = self.params, self._rgb.device
-        if feature_samples:
-            opts["guide"] = render_guide(self.ctx, self.scene, self.cam, p, feature_samples, sigma_albedo, sigma_normal, sigma_depth, moments=bool(feature_variance),
-                                         variance_strength=variance_strength)
-        if p.shard_count <= 1:
-            rgb, sq, cnt = self._rgb, self._sq, self._counts
-        else:
-            rgb = torch.from_numpy(np.ascontiguousarray(self.rgb_sum()).reshape(-1)).to(dev)
-            sq = torch.from_numpy(np.ascontiguousarray(self.sq_sum()).reshape(-1)).to(dev)
-            cnt = torch.from_numpy(np.ascontiguousarray(self.counts()).view(np.int32).reshape(-1)).to(dev)
+        from .denoise import denoise_frame
+        p = self.params
+        rgb, sq, sharded = denoise_front(self, opts, feature_samples, sigma_albedo, sigma_normal, sigma_depth, feature_variance, variance_strength)
+        cnt = on_device(self.counts().view(np.int32), rgb.device) if sharded else self._counts
         return denoise_frame(self.ctx, rgb, sq, p.width, p.height, self.samples_per_item, counts=cnt, rgb8=rgb8, **opts)
 
     def features(self, samples):

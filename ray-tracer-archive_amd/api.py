@@ -159,6 +159,17 @@ def feature_moments_check(params, options, buffers):
     _check(lib().rt_feature_moments_check(C.byref(params), C.byref(options) if options is not None else None, C.byref(buffers) if buffers is not None else None))
 
 
+def _feature_buffers(albedo=None, normal=None, depth=None, hits=None):
+    """RtFeatureBuffers (include/rt_hip.h, "first-hit features"): CUDA tensors, or None for a plane not wanted."""
+    return A.RtFeatureBuffers(*[t.data_ptr() if t is not None else None for t in (albedo, normal, depth, hits)])
+
+
+# the two feature passes (Context._feature_pass)
+_FEATURE_PLANES = ("rt_render_features_device", _feature_buffers, (3, 3, 1, 1), ((0, 1, "albedo / normal"), (2, None, "depth"), (3, None, "hits")))
+_MOMENT_PLANES = ("rt_render_feature_moments_device", feature_moment_buffers, (3, 3, 1, 1, 3, 3, 1),
+                  ((0, 1, "albedo / normal"), (4, 5, "albedo_sq / normal_sq"), (2, 6, "depth / depth_sq"), (3, None, "hits")))
+
+
 def _check_device(a, b, n, what, float_):
     """a (and b, unless None) are contiguous CUDA tensors of n elements (n None: any), float32 or a 32-bit integer type."""
     import torch
@@ -166,6 +177,42 @@ def _check_device(a, b, n, what, float_):
     for t in (a, b):
         if t is not None and (not t.is_cuda or t.dtype not in ok or not t.is_contiguous() or (n is not None and t.numel() != n)):
             raise ValueError(f"{what}: contiguous CUDA tensors of {'float32' if float_ else '32-bit integers'}" + (f", {n} elements" if n is not None else ""))
+
+
+def _host_rays(rays, dtype, dtype_name):
+    """A host ray list as a flat C-contiguous array of `dtype` records (RAY_DTYPE, PATHRAY_DTYPE): given as such, or as float32 of shape
+    (n, floats per record)."""
+    k = dtype.itemsize // 4
+    rays = np.asarray(rays)
+    if rays.dtype != dtype:
+        if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != k:
+            raise ValueError(f"host rays must be a numpy array of {dtype_name}, or float32 of shape (n, {k})")
+        rays = np.ascontiguousarray(rays).view(dtype).reshape(-1)
+    return np.ascontiguousarray(rays).reshape(-1)
+
+
+def _device_rays(rays, dtype):
+    """A device ray list: a contiguous float32 CUDA tensor of shape (n, floats per `dtype` record). Returns n."""
+    import torch
+    k = dtype.itemsize // 4
+    if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != k:
+        raise ValueError(f"device rays must be a contiguous float32 CUDA tensor of shape (n, {k})")
+    return rays.shape[0]
+
+
+def _check_out(out, device, dtype, size, message):
+    """An output buffer of `size` elements of `dtype`: a contiguous CUDA tensor (device; a torch dtype) or a C-contiguous numpy array."""
+    if device:
+        ok = getattr(out, "is_cuda", False) and out.dtype == dtype and out.is_contiguous() and out.numel() == size
+    else:
+        ok = isinstance(out, np.ndarray) and out.dtype == dtype and out.flags.c_contiguous and out.size == size
+    if not ok:
+        raise ValueError(message)
+
+
+# the two kinds of ray query (Context._ray_query): an RtRayHit record per ray, or one byte
+_CLOSEST_HIT = ("rt_trace_rays", RAYHIT_DTYPE, "n RAYHIT_DTYPE records", "float32", 12)
+_OCCLUSION = ("rt_occluded_rays", np.dtype(np.uint8), "n uint8", "uint8", 1)
 
 
 def output_floats(params):
@@ -512,6 +559,34 @@ class Context:
                                               C.c_void_p(rgb8_out.data_ptr())), self._h)
 
     # ---- ray queries (include/rt_hip.h, "ray queries") ----
+    def _ray_query(self, kind, scene, rays, options, out, with_stats):
+        """trace_rays and occluded: kind = (host entry point — its device variant is that + "_device", a result's numpy dtype, what the
+        host message calls n of them, the torch dtype's name and the elements per ray of a device result). The two call it through the
+        class: a host test hands them a stand-in for a context, which the argument checks below never touch."""
+        name, np_dtype, n_of_them, torch_name, per_ray = kind
+        st = A.RtStats()
+        opt = C.byref(options) if options is not None else None
+        if hasattr(rays, "data_ptr"):
+            import torch
+            n = _device_rays(rays, RAY_DTYPE)
+            if out is None:
+                out = torch.empty((n, per_ray) if per_ray > 1 else (n,), dtype=getattr(torch, torch_name), device=rays.device)
+            _check_out(out, True, getattr(torch, torch_name), per_ray * n,
+                       f"out must be a contiguous {torch_name} CUDA tensor of {'n * %d' % per_ray if per_ray > 1 else 'n'} elements")
+            if rays.device.index != self.device_id or out.device != rays.device:      # another GPU's pointer means nothing to this context's kernels
+                raise ValueError(f"rays and out must live on this context's device (cuda:{self.device_id})")
+            torch.cuda.synchronize(rays.device)           # the library's stream is not torch's
+            fn, p_rays, p_out = getattr(lib(), name + "_device"), rays.data_ptr(), out.data_ptr()
+        else:
+            rays = _host_rays(rays, RAY_DTYPE, "RAY_DTYPE")
+            n = rays.shape[0]
+            if out is None:
+                out = np.empty(n, dtype=np_dtype)
+            _check_out(out, False, np_dtype, n, f"out must be a C-contiguous numpy array of {n_of_them}")
+            fn, p_rays, p_out = getattr(lib(), name), rays.ctypes.data, out.ctypes.data
+        _check(fn(self._h, scene._h, opt, C.c_void_p(p_rays if n else None), n, C.c_void_p(p_out if n else None), C.byref(st)), self._h)
+        return (out, st.as_dict()) if with_stats else out
+
     def trace_rays(self, scene, rays, options=None, out=None, with_stats=False):
         """rt_trace_rays / rt_trace_rays_device: the closest hit of every ray.
 
@@ -519,37 +594,7 @@ class Context:
         Device variant: `rays` is a contiguous float32 CUDA tensor of shape (n, 8); returns a float32 CUDA tensor of shape (n, 12) holding
         the RtRayHit records (view the integer fields with .view(torch.int32), or RAYHIT_DTYPE after .cpu().numpy()). `out` receives the
         hits when given (same kind and size); a refused call raises RtError and leaves it untouched. with_stats: also return the stats."""
-        st = A.RtStats()
-        opt = C.byref(options) if options is not None else None
-        if hasattr(rays, "data_ptr"):
-            import torch
-            if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
-                raise ValueError("device rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
-            n = rays.shape[0]
-            if out is None:
-                out = torch.empty((n, 12), dtype=torch.float32, device=rays.device)
-            if not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != 12 * n:
-                raise ValueError("out must be a contiguous float32 CUDA tensor of n * 12 elements")
-            if rays.device.index != self.device_id or out.device != rays.device:      # another GPU's pointer means nothing to this context's kernels
-                raise ValueError(f"rays and out must live on this context's device (cuda:{self.device_id})")
-            torch.cuda.synchronize(rays.device)           # the library's stream is not torch's
-            _check(lib().rt_trace_rays_device(self._h, scene._h, opt, C.c_void_p(rays.data_ptr() if n else None), n, C.c_void_p(out.data_ptr() if n else None),
-                                              C.byref(st)), self._h)
-            return (out, st.as_dict()) if with_stats else out
-        rays = np.asarray(rays)
-        if rays.dtype != RAY_DTYPE:
-            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
-                raise ValueError("host rays must be a numpy array of RAY_DTYPE, or float32 of shape (n, 8)")
-            rays = np.ascontiguousarray(rays).view(RAY_DTYPE).reshape(-1)
-        rays = np.ascontiguousarray(rays).reshape(-1)
-        n = rays.shape[0]
-        if out is None:
-            out = np.empty(n, dtype=RAYHIT_DTYPE)
-        if not isinstance(out, np.ndarray) or out.dtype != RAYHIT_DTYPE or not out.flags.c_contiguous or out.size != n:
-            raise ValueError("out must be a C-contiguous numpy array of n RAYHIT_DTYPE records")
-        _check(lib().rt_trace_rays(self._h, scene._h, opt, C.c_void_p(rays.ctypes.data if n else None), n, C.c_void_p(out.ctypes.data if n else None),
-                                   C.byref(st)), self._h)
-        return (out, st.as_dict()) if with_stats else out
+        return Context._ray_query(self, _CLOSEST_HIT, scene, rays, options, out, with_stats)
 
     def occluded(self, scene, rays, options=None, out=None, with_stats=False):
         """rt_occluded_rays / rt_occluded_rays_device: one byte per ray — RT_RAYHIT_HIT (1) when anything is hit in [0.001, t_max], else 0;
@@ -558,37 +603,7 @@ class Context:
         `rays` as for trace_rays: a numpy array of RAY_DTYPE or float32 of shape (n, 8) (host variant, returns a uint8 numpy array of length
         n), or a contiguous float32 CUDA tensor of shape (n, 8) (device variant, returns a uint8 CUDA tensor of length n). `out` receives
         the bytes when given (same kind, n elements); a refused call raises RtError and leaves it untouched. with_stats: also the stats."""
-        st = A.RtStats()
-        opt = C.byref(options) if options is not None else None
-        if hasattr(rays, "data_ptr"):
-            import torch
-            if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
-                raise ValueError("device rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
-            n = rays.shape[0]
-            if out is None:
-                out = torch.empty((n,), dtype=torch.uint8, device=rays.device)
-            if not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != n:
-                raise ValueError("out must be a contiguous uint8 CUDA tensor of n elements")
-            if rays.device.index != self.device_id or out.device != rays.device:
-                raise ValueError(f"rays and out must live on this context's device (cuda:{self.device_id})")
-            torch.cuda.synchronize(rays.device)           # the library's stream is not torch's
-            _check(lib().rt_occluded_rays_device(self._h, scene._h, opt, C.c_void_p(rays.data_ptr() if n else None), n, C.c_void_p(out.data_ptr() if n else None),
-                                                 C.byref(st)), self._h)
-            return (out, st.as_dict()) if with_stats else out
-        rays = np.asarray(rays)
-        if rays.dtype != RAY_DTYPE:
-            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
-                raise ValueError("host rays must be a numpy array of RAY_DTYPE, or float32 of shape (n, 8)")
-            rays = np.ascontiguousarray(rays).view(RAY_DTYPE).reshape(-1)
-        rays = np.ascontiguousarray(rays).reshape(-1)
-        n = rays.shape[0]
-        if out is None:
-            out = np.empty(n, dtype=np.uint8)
-        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or out.size != n:
-            raise ValueError("out must be a C-contiguous numpy array of n uint8")
-        _check(lib().rt_occluded_rays(self._h, scene._h, opt, C.c_void_p(rays.ctypes.data if n else None), n, C.c_void_p(out.ctypes.data if n else None),
-                                      C.byref(st)), self._h)
-        return (out, st.as_dict()) if with_stats else out
+        return Context._ray_query(self, _OCCLUSION, scene, rays, options, out, with_stats)
 
     # ---- light-sample queries (include/rt_hip.h, "light-sample queries") ----
     def _light_queries(self, scene, q, with_stats):
@@ -643,9 +658,7 @@ class Context:
             raise ValueError("accumulate needs the rgb_sum and sq_sum of the samples so far")
         if hasattr(rays, "data_ptr"):
             import torch
-            if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
-                raise ValueError("device rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
-            n = rays.shape[0]
+            n = _device_rays(rays, PATHRAY_DTYPE)
             if rgb_sum is None:
                 rgb_sum = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
             if sq_sum is None:
@@ -653,20 +666,14 @@ class Context:
             if invalid is None:
                 invalid = torch.empty((n,), dtype=torch.uint8, device=rays.device)
             _check_device(rgb_sum, sq_sum, 3 * n, "rgb_sum / sq_sum", True)
-            if not invalid.is_cuda or invalid.dtype != torch.uint8 or not invalid.is_contiguous() or invalid.numel() != n:
-                raise ValueError("invalid must be a contiguous uint8 CUDA tensor of n elements")
+            _check_out(invalid, True, torch.uint8, n, "invalid must be a contiguous uint8 CUDA tensor of n elements")
             if rays.device.index != self.device_id or any(t.device != rays.device for t in (rgb_sum, sq_sum, invalid)):
                 raise ValueError(f"rays and outputs must live on this context's device (cuda:{self.device_id})")
             torch.cuda.synchronize(rays.device)           # the library's stream is not torch's
             ptr = lambda t: C.c_void_p(t.data_ptr() if n else None)
             _check(lib().rt_radiance_rays_device(self._h, scene._h, C.byref(options), ptr(rays), n, ptr(rgb_sum), ptr(sq_sum), ptr(invalid), C.byref(st)), self._h)
         else:
-            rays = np.asarray(rays)
-            if rays.dtype != PATHRAY_DTYPE:
-                if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
-                    raise ValueError("host rays must be a numpy array of PATHRAY_DTYPE, or float32 of shape (n, 8)")
-                rays = np.ascontiguousarray(rays).view(PATHRAY_DTYPE).reshape(-1)
-            rays = np.ascontiguousarray(rays).reshape(-1)
+            rays = _host_rays(rays, PATHRAY_DTYPE, "PATHRAY_DTYPE")
             n = rays.shape[0]
             if rgb_sum is None:
                 rgb_sum = np.empty((n, 3), dtype=np.float32)
@@ -675,13 +682,34 @@ class Context:
             if invalid is None:
                 invalid = np.empty(n, dtype=np.uint8)
             for a, dt, k, what in ((rgb_sum, np.float32, 3 * n, "rgb_sum"), (sq_sum, np.float32, 3 * n, "sq_sum"), (invalid, np.uint8, n, "invalid")):
-                if not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous or a.size != k:
-                    raise ValueError(f"{what} must be a C-contiguous numpy array of {k} {np.dtype(dt).name}")
+                _check_out(a, False, dt, k, f"{what} must be a C-contiguous numpy array of {k} {np.dtype(dt).name}")
             ptr = lambda a: C.c_void_p(a.ctypes.data if n else None)
             _check(lib().rt_radiance_rays(self._h, scene._h, C.byref(options), ptr(rays), n, ptr(rgb_sum), ptr(sq_sum), ptr(invalid), C.byref(st)), self._h)
         return (rgb_sum, sq_sum, invalid, st.as_dict()) if with_stats else (rgb_sum, sq_sum, invalid)
 
     # ---- first-hit features (include/rt_hip.h, "first-hit features"): device tensors only ----
+    def _feature_pass(self, table, scene, cam, params, first_sample, accumulate, planes, pool_slots, with_stats):
+        """render_features and render_feature_moments: table = (entry point, what makes its buffers record of the planes, elements per slot
+        of every plane — plane 3, hits, holds integers —, the planes checked together as (plane, plane or None, what the message calls them))."""
+        import torch
+        name, make_buffers, per_slot, checked = table
+        slots = output_floats(params) // 3
+        if all(t is None for t in planes):
+            if accumulate:
+                raise ValueError("an accumulating feature pass needs the planes to add into")
+            dev = torch.device("cuda", self.device_id)
+            planes = tuple(torch.zeros(k * slots, dtype=torch.int32 if i == 3 else torch.float32, device=dev) for i, k in enumerate(per_slot))
+        for i, j, what in checked:
+            _check_device(planes[i], planes[j] if j is not None else None, n=per_slot[i] * slots, what=what, float_=i != 3)
+        if any(t is not None and t.device.index != self.device_id for t in planes):      # another GPU's pointer means nothing to this context's kernels
+            raise ValueError(f"feature planes must live on this context's device (cuda:{self.device_id})")
+        opt = feature_options(first_sample, accumulate, pool_slots)
+        buf = make_buffers(*planes)
+        st = A.RtStats()
+        torch.cuda.synchronize(torch.device("cuda", self.device_id))        # the library's stream is not torch's
+        _check(getattr(lib(), name)(self._h, scene._h, C.byref(cam), C.byref(params), C.byref(opt), C.byref(buf), C.byref(st)), self._h)
+        return planes + (st.as_dict(),) if with_stats else planes
+
     def render_features(self, scene, cam, params, first_sample=0, accumulate=False, albedo=None, normal=None, depth=None, hits=None, pool_slots=0,
                         with_stats=False):
         """rt_render_features_device: per-slot sums of the first hit's albedo, normal and depth, and the number of hits, over samples
@@ -691,26 +719,7 @@ class Context:
         32-bit integer tensor of slots. Only the planes given are written; with none given all four are made (zero-filled, so clipped slots
         of a sharded layout read 0). accumulate: the fold starts from the planes' values. Returns (albedo, normal, depth, hits), None for a
         plane not wanted, and the stats too with with_stats. A refused call raises RtError and leaves the planes untouched."""
-        import torch
-        slots = output_floats(params) // 3
-        if albedo is None and normal is None and depth is None and hits is None:
-            if accumulate:
-                raise ValueError("an accumulating feature pass needs the planes to add into")
-            dev = torch.device("cuda", self.device_id)
-            albedo, normal = torch.zeros(3 * slots, dtype=torch.float32, device=dev), torch.zeros(3 * slots, dtype=torch.float32, device=dev)
-            depth, hits = torch.zeros(slots, dtype=torch.float32, device=dev), torch.zeros(slots, dtype=torch.int32, device=dev)
-        _check_device(albedo, normal, n=3 * slots, what="albedo / normal", float_=True)
-        _check_device(depth, None, n=slots, what="depth", float_=True)
-        _check_device(hits, None, n=slots, what="hits", float_=False)
-        planes = (albedo, normal, depth, hits)
-        if any(t is not None and t.device.index != self.device_id for t in planes):      # another GPU's pointer means nothing to this context's kernels
-            raise ValueError(f"feature planes must live on this context's device (cuda:{self.device_id})")
-        opt = feature_options(first_sample, accumulate, pool_slots)
-        buf = A.RtFeatureBuffers(*[t.data_ptr() if t is not None else None for t in planes])
-        st = A.RtStats()
-        torch.cuda.synchronize(torch.device("cuda", self.device_id))        # the library's stream is not torch's
-        _check(lib().rt_render_features_device(self._h, scene._h, C.byref(cam), C.byref(params), C.byref(opt), C.byref(buf), C.byref(st)), self._h)
-        return planes + (st.as_dict(),) if with_stats else planes
+        return self._feature_pass(_FEATURE_PLANES, scene, cam, params, first_sample, accumulate, (albedo, normal, depth, hits), pool_slots, with_stats)
 
     def render_feature_moments(self, scene, cam, params, first_sample=0, accumulate=False, albedo=None, normal=None, depth=None, hits=None, albedo_sq=None,
                                normal_sq=None, depth_sq=None, pool_slots=0, with_stats=False):
@@ -718,71 +727,45 @@ class Context:
         float32 of 3 * slots elements, depth_sq float32 of slots. Only the planes given are written; with none given all seven are made
         (zero-filled). Returns (albedo, normal, depth, hits, albedo_sq, normal_sq, depth_sq), None for a plane not wanted, and the stats
         too with with_stats. A refused call raises RtError and leaves the planes untouched."""
-        import torch
-        slots = output_floats(params) // 3
-        planes = (albedo, normal, depth, hits, albedo_sq, normal_sq, depth_sq)
-        if all(t is None for t in planes):
-            if accumulate:
-                raise ValueError("an accumulating feature pass needs the planes to add into")
-            dev = torch.device("cuda", self.device_id)
-            planes = tuple(torch.zeros(n * slots, dtype=torch.int32 if i == 3 else torch.float32, device=dev) for i, n in enumerate((3, 3, 1, 1, 3, 3, 1)))
-        albedo, normal, depth, hits, albedo_sq, normal_sq, depth_sq = planes
-        _check_device(albedo, normal, n=3 * slots, what="albedo / normal", float_=True)
-        _check_device(albedo_sq, normal_sq, n=3 * slots, what="albedo_sq / normal_sq", float_=True)
-        _check_device(depth, depth_sq, n=slots, what="depth / depth_sq", float_=True)
-        _check_device(hits, None, n=slots, what="hits", float_=False)
-        if any(t is not None and t.device.index != self.device_id for t in planes):      # another GPU's pointer means nothing to this context's kernels
-            raise ValueError(f"feature planes must live on this context's device (cuda:{self.device_id})")
-        opt = feature_options(first_sample, accumulate, pool_slots)
-        buf = feature_moment_buffers(*planes)
-        st = A.RtStats()
-        torch.cuda.synchronize(torch.device("cuda", self.device_id))        # the library's stream is not torch's
-        _check(lib().rt_render_feature_moments_device(self._h, scene._h, C.byref(cam), C.byref(params), C.byref(opt), C.byref(buf), C.byref(st)), self._h)
-        return planes + (st.as_dict(),) if with_stats else planes
+        return self._feature_pass(_MOMENT_PLANES, scene, cam, params, first_sample, accumulate, (albedo, normal, depth, hits, albedo_sq, normal_sq, depth_sq), pool_slots,
+                                  with_stats)
 
     # ---- denoising (include/rt_hip.h, "denoising"): device tensors only ----
-    def denoise(self, rgb_sum, sq_sum, width, height, samples=0, counts=None, options=None, out=None):
-        """rt_denoise_device: the filtered MEAN radiance of a full frame from its sums (float32 CUDA tensors of width * height * 3
-        elements) and either the uniform sample count `samples` or per-pixel `counts` (32-bit integer tensor of width * height). Returns
-        `out` (a new float32 tensor of width * height * 3 elements when None); a refused call raises RtError and leaves `out` untouched."""
+    def _denoise(self, name, guide, planes, rgb_sum, sq_sum, width, height, samples, counts, options, out):
+        """The three denoise methods: name = the entry point, guide = its guide record (None: the plain filter, which takes none), planes
+        = the guide's tensors as _check_device takes them: (a, b or None, elements per pixel, what the message calls them, float_)."""
         import torch
         n = 3 * width * height
         _check_device(rgb_sum, sq_sum, n=n, what="rgb_sum / sq_sum", float_=True)
         if counts is not None:
             _check_device(counts, None, n=width * height, what="counts", float_=False)
+        for a, b, per_pixel, what, float_ in planes:
+            _check_device(a, b, n=per_pixel * width * height, what=what, float_=float_)
+        if any(t is not None and t.device != rgb_sum.device for a, b, *_ in planes for t in (a, b, counts, sq_sum)):
+            raise ValueError("the sums, the counts and the feature planes must live on one device")
         if out is None:
             out = torch.empty(n, dtype=torch.float32, device=rgb_sum.device)
         _check_device(out, None, n=n, what="out", float_=True)
         torch.cuda.synchronize(rgb_sum.device)        # the library's stream is not torch's
-        _check(lib().rt_denoise_device(self._h, C.byref(options) if options is not None else None, width, height, C.c_void_p(rgb_sum.data_ptr()),
-                                       C.c_void_p(sq_sum.data_ptr()), int(samples), C.c_void_p(counts.data_ptr()) if counts is not None else None,
-                                       C.c_void_p(out.data_ptr())), self._h)
+        records = (C.byref(options) if options is not None else None,) + ((C.byref(guide),) if guide is not None else ())
+        _check(getattr(lib(), name)(self._h, *records, width, height, C.c_void_p(rgb_sum.data_ptr()), C.c_void_p(sq_sum.data_ptr()), int(samples),
+                                    C.c_void_p(counts.data_ptr()) if counts is not None else None, C.c_void_p(out.data_ptr())), self._h)
         return out
+
+    def denoise(self, rgb_sum, sq_sum, width, height, samples=0, counts=None, options=None, out=None):
+        """rt_denoise_device: the filtered MEAN radiance of a full frame from its sums (float32 CUDA tensors of width * height * 3
+        elements) and either the uniform sample count `samples` or per-pixel `counts` (32-bit integer tensor of width * height). Returns
+        `out` (a new float32 tensor of width * height * 3 elements when None); a refused call raises RtError and leaves `out` untouched."""
+        return self._denoise("rt_denoise_device", None, (), rgb_sum, sq_sum, width, height, samples, counts, options, out)
 
     def denoise_guided(self, rgb_sum, sq_sum, width, height, feature_samples, albedo=None, normal=None, depth=None, hits=None, samples=0, counts=None,
                        options=None, sigma_albedo=0.0, sigma_normal=0.0, sigma_depth=0.0, out=None):
         """rt_denoise_guided_device: Context.denoise with the weights joined with full-frame feature planes (render_features with
         shard_count <= 1: albedo / normal float32 of width * height * 3, depth float32 and hits 32-bit integers of width * height; None =
         not used) folded over feature_samples samples. Returns `out`; a refused call raises RtError and leaves `out` untouched."""
-        import torch
-        n = 3 * width * height
-        _check_device(rgb_sum, sq_sum, n=n, what="rgb_sum / sq_sum", float_=True)
-        if counts is not None:
-            _check_device(counts, None, n=width * height, what="counts", float_=False)
-        _check_device(albedo, normal, n=n, what="albedo / normal", float_=True)
-        _check_device(depth, None, n=width * height, what="depth", float_=True)
-        _check_device(hits, None, n=width * height, what="hits", float_=False)
-        if any(t is not None and t.device != rgb_sum.device for t in (albedo, normal, depth, hits, counts, sq_sum)):
-            raise ValueError("the sums, the counts and the feature planes must live on one device")
-        if out is None:
-            out = torch.empty(n, dtype=torch.float32, device=rgb_sum.device)
-        _check_device(out, None, n=n, what="out", float_=True)
         guide = denoise_guide(feature_samples, albedo, normal, depth, hits, sigma_albedo, sigma_normal, sigma_depth)
-        torch.cuda.synchronize(rgb_sum.device)        # the library's stream is not torch's
-        _check(lib().rt_denoise_guided_device(self._h, C.byref(options) if options is not None else None, C.byref(guide), width, height,
-                                              C.c_void_p(rgb_sum.data_ptr()), C.c_void_p(sq_sum.data_ptr()), int(samples),
-                                              C.c_void_p(counts.data_ptr()) if counts is not None else None, C.c_void_p(out.data_ptr())), self._h)
-        return out
+        planes = ((albedo, normal, 3, "albedo / normal", True), (depth, None, 1, "depth", True), (hits, None, 1, "hits", False))
+        return self._denoise("rt_denoise_guided_device", guide, planes, rgb_sum, sq_sum, width, height, samples, counts, options, out)
 
     def denoise_guided_moments(self, rgb_sum, sq_sum, width, height, feature_samples, albedo=None, normal=None, depth=None, hits=None, albedo_sq=None,
                                normal_sq=None, depth_sq=None, samples=0, counts=None, options=None, sigma_albedo=0.0, sigma_normal=0.0, sigma_depth=0.0,
@@ -791,27 +774,11 @@ class Context:
         from the squared sums of render_feature_moments (albedo_sq / normal_sq float32 of width * height * 3, depth_sq float32 of
         width * height; None = that group's variance is 0), feature_samples >= 2. window_radius 0 means 8 here, at most 8. Returns `out`;
         a refused call raises RtError and leaves `out` untouched."""
-        import torch
-        n = 3 * width * height
-        _check_device(rgb_sum, sq_sum, n=n, what="rgb_sum / sq_sum", float_=True)
-        if counts is not None:
-            _check_device(counts, None, n=width * height, what="counts", float_=False)
-        _check_device(albedo, normal, n=n, what="albedo / normal", float_=True)
-        _check_device(albedo_sq, normal_sq, n=n, what="albedo_sq / normal_sq", float_=True)
-        _check_device(depth, depth_sq, n=width * height, what="depth / depth_sq", float_=True)
-        _check_device(hits, None, n=width * height, what="hits", float_=False)
-        if any(t is not None and t.device != rgb_sum.device for t in (albedo, normal, depth, hits, albedo_sq, normal_sq, depth_sq, counts, sq_sum)):
-            raise ValueError("the sums, the counts and the feature planes must live on one device")
-        if out is None:
-            out = torch.empty(n, dtype=torch.float32, device=rgb_sum.device)
-        _check_device(out, None, n=n, what="out", float_=True)
         guide = denoise_guide_moments(feature_samples, albedo, normal, depth, hits, albedo_sq, normal_sq, depth_sq, sigma_albedo, sigma_normal, sigma_depth,
                                       variance_strength)
-        torch.cuda.synchronize(rgb_sum.device)        # the library's stream is not torch's
-        _check(lib().rt_denoise_guided_moments_device(self._h, C.byref(options) if options is not None else None, C.byref(guide), width, height,
-                                                      C.c_void_p(rgb_sum.data_ptr()), C.c_void_p(sq_sum.data_ptr()), int(samples),
-                                                      C.c_void_p(counts.data_ptr()) if counts is not None else None, C.c_void_p(out.data_ptr())), self._h)
-        return out
+        planes = ((albedo, normal, 3, "albedo / normal", True), (albedo_sq, normal_sq, 3, "albedo_sq / normal_sq", True), (depth, depth_sq, 1, "depth / depth_sq", True),
+                  (hits, None, 1, "hits", False))
+        return self._denoise("rt_denoise_guided_moments_device", guide, planes, rgb_sum, sq_sum, width, height, samples, counts, options, out)
 
     # ---- one process per GPU: RCCL communicator on this context (rt_multi.cpp) ----
     def comm_init_rank(self, unique_id, rank, world):

@@ -110,12 +110,20 @@ static uint32_t frame_block_shift(const RtParams& p, uint32_t frame_samples) {
     return block_shift;
 }
 
+// The head of every options record of the ABI: struct_bytes holds the caller's sizeof of the record `name` (unset, or a shorter record of
+// another header, is refused), and its flags word no bit outside `known`; known_names: what the message lists after "known:", if it lists any.
+// A record without a flags word passes none.
+static int check_header(RtCtx* ctx, uint32_t struct_bytes, size_t size, const std::string& name, uint32_t flags = 0u, uint32_t known = 0u, const char* known_names = nullptr) {
+    if (struct_bytes < size || struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, name + ".struct_bytes is not set (sizeof(" + name + "))");
+    if (flags & ~known) return set_err(ctx, RT_ERR_INVALID, name + ".flags holds an unknown bit" + (known_names ? std::string(" (known: ") + known_names + ")" : std::string()));
+    return RT_OK;
+}
+
 // RtPassOptions against the params (rt_pass_check): the message names what is wrong. *shift = the frame's grouping.
 static int check_pass(RtCtx* ctx, const RtParams* p, const RtPassOptions* o, uint32_t* shift) {
     const int v = validate_params(ctx, p); if (v != RT_OK) return v;
     if (!o) return set_err(ctx, RT_ERR_INVALID, "pass options are null");
-    if (o->struct_bytes < sizeof(RtPassOptions) || o->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtPassOptions.struct_bytes is not set (sizeof(RtPassOptions))");
-    if (o->flags & ~(uint32_t)RT_PASS_ACCUMULATE) return set_err(ctx, RT_ERR_INVALID, "RtPassOptions.flags holds an unknown bit");
+    const int h = check_header(ctx, o->struct_bytes, sizeof(RtPassOptions), "RtPassOptions", o->flags, RT_PASS_ACCUMULATE); if (h != RT_OK) return h;
     const uint64_t end = (uint64_t)o->first_sample + p->samples_per_pixel;
     if (end > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "first_sample + samples_per_pixel must be < 2^32");
     if (o->frame_samples < end) return set_err(ctx, RT_ERR_INVALID, "frame_samples is smaller than the end of the pass (first_sample + samples_per_pixel)");
@@ -143,6 +151,38 @@ static int render_pass_checked(RtCtx* ctx, const RtScene* scene, const RtCamera*
                                RtStats* stats, const ListPass* lp = nullptr) {
     if (ctx->fail_renders != 0u) { --ctx->fail_renders; return set_err(ctx, RT_ERR_DEVICE, "injected failure (rt_test_fail_next_renders)"); }
     return drain_on_failure(ctx, render_impl(ctx, scene, cam, prm, pass, d_out, d_sq, stats, lp));
+}
+
+// The entry sequence of a query, host or device variant: ctx null -> the feature's own refusal (a refused call has written nothing) ->
+// the stats zeroed -> nothing to do -> an injected failure, where the feature takes them (radiance queries, as the renders do:
+// render_pass_checked) -> the context's device current -> the work, drained if it fails.
+static int query_entry(RtCtx* ctx, RtStats* stats, bool nothing_to_do, bool injectable, const std::function<int()>& refuse, const std::function<int()>& work) {
+    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
+    const int v = refuse(); if (v != RT_OK) return v;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (nothing_to_do) return RT_OK;
+    if (injectable && ctx->fail_renders != 0u) { --ctx->fail_renders; return set_err(ctx, RT_ERR_DEVICE, "injected failure (rt_test_fail_next_renders)"); }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return drain_on_failure(ctx, work());
+}
+
+// The host variant of a call: each buffer of the list grown to `bytes` and, where it has a source, filled from it; the device variant on
+// those buffers; then each buffer with a destination copied out, and ONE wait. Nothing is written to caller memory when the device variant
+// fails, and stats->render_ms covers the staging. An entry with neither source nor destination is a buffer the caller did not ask for.
+struct Staged { DevBuf* buf; const void* src; void* dst; size_t bytes; };
+static int staged_call(RtCtx* ctx, std::initializer_list<Staged> list, RtStats* stats, const std::function<int()>& device_variant) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (const Staged& s : list) {
+        if (!s.src && !s.dst) continue;
+        HIP_TRY(ctx, s.buf->ensure(s.bytes));
+        if (s.src) HIP_TRY(ctx, hipMemcpyAsync(s.buf->p, s.src, s.bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const int r = device_variant();
+    if (r != RT_OK) return r;
+    for (const Staged& s : list) if (s.dst) HIP_TRY(ctx, hipMemcpyAsync(s.dst, s.buf->p, s.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT_OK;
 }
 // the whole frame as one pass that overwrites: what rt_render computes
 static RtPassOptions one_shot(const RtParams* prm) { return RtPassOptions{(uint32_t)sizeof(RtPassOptions), 0u, 0u, prm->samples_per_pixel}; }
@@ -534,6 +574,21 @@ static int tri_attr_table(const RtSceneDesc& desc, const RtUploadOptions* o, con
     return RT_OK;
 }
 
+// What every compile of a caller's scene begins with: the options checked, the graph compiled under them, the triangle attributes checked
+// against the result (tri_attr_table: `table` receives their device records, nullptr = checked and counted only).
+static int compile_checked(const RtSceneDesc& desc, const RtUploadOptions* options, rtc::CompiledScene& cs, std::vector<rtd::Float4>* table, uint32_t* n_with, std::string& err) {
+    { const int ok = check_options(options, err); if (ok != RT_OK) return ok; }
+    const int rc = rtc::compile_scene(desc, resolve_options(options).compile, cs);
+    if (rc != RT_OK) { err = "scene: " + cs.error; return rc; }
+    return tri_attr_table(desc, options, cs, table, n_with, err);
+}
+// how far an entry's box of the 8-wide tree lies outside what is below it (rtw::build; rt_scene_wide_layout_check holds the tree to it)
+static float wide_margin(const std::vector<rtd::Node>& nodes) {
+    double extent = 0.0;
+    for (int a = 0; a < 3; ++a) extent = std::max(extent, std::max(std::fabs((double)nodes[0].mn[a]), std::fabs((double)nodes[0].mx[a])));
+    return (float)(6e-7 * extent);
+}
+
 // ---- the host image of a scene: everything an upload copies to a device, built ONCE (rt_scene_upload_multi uploads it n times) ---------
 struct rti::SceneImage {
     rtc::CompiledScene cs;
@@ -552,26 +607,18 @@ void rti::scene_image_free(SceneImage* im) { delete im; }
 
 int rti::scene_image_build(const RtSceneDesc* desc, const RtUploadOptions* options, SceneImage** out, std::string& err) {
     *out = nullptr;
-    { const int ok = check_options(options, err); if (ok != RT_OK) return ok; }
-    const UploadOpts opt = resolve_options(options);
     std::unique_ptr<SceneImage> im(new SceneImage());
     rtc::CompiledScene& cs = im->cs;
-    const int rc = rtc::compile_scene(*desc, opt.compile, cs);
-    if (rc != RT_OK) { err = "scene: " + cs.error; return rc; }
+    uint32_t n_with = 0u;
+    { const int ok = compile_checked(*desc, options, cs, &im->tri_attrs, &n_with, err); if (ok != RT_OK) return ok; }
+    const UploadOpts opt = resolve_options(options);
     im->in_lds = opt.lds_scene && lds_scene_bytes(cs) <= kLdsSceneBudget;
-    im->features = scene_features(cs);
-    {   // attributes change what is shaded, never what is walked: every test on `features` below sees the scene's own bits
-        uint32_t n_with = 0u;
-        const int ok = tri_attr_table(*desc, options, cs, &im->tri_attrs, &n_with, err);
-        if (ok != RT_OK) return ok;
-    }
+    im->features = scene_features(cs);   // attributes change what is shaded, never what is walked: every test on `features` below sees the scene's own bits
     // RT_LAYOUT_WIDE_NODES: a static BVH in HBM (spheres / rects / triangles / boxes under box nodes only) walked 8 lanes to a ray over an
     // 8-wide tree (kernels.hip k_extend_wide) instead of the binary records below.
     if (!im->in_lds && opt.wide_nodes && opt.node16 && (im->features & ~(rtk::F_RECT | rtk::F_TRI)) == 0u && cs.prologue.empty() && cs.first_leaf == 0u && rtw::eligible(cs.nodes)) {   // (k_extend_wide tests nothing before the tree)
-        double extent = 0.0;
-        for (int a = 0; a < 3; ++a) extent = std::max(extent, std::max(std::fabs((double)cs.nodes[0].mn[a]), std::fabs((double)cs.nodes[0].mx[a])));
         std::string werr;
-        im->use_wide = rtw::build(cs.nodes, (float)(6e-7 * extent), im->wide, werr) && im->wide.depth < rtd::WIDE_MAX_DEPTH;
+        im->use_wide = rtw::build(cs.nodes, wide_margin(cs.nodes), im->wide, werr) && im->wide.depth < rtd::WIDE_MAX_DEPTH;
         if (!im->use_wide) im->wide = rtw::WideTree();
     }
     // 16-byte compressed records for a scene that does not fit LDS (RT_LAYOUT_NODES_32B: 32-byte records with the top of the tree in LDS)
@@ -859,6 +906,31 @@ static void scene_stats(RtStats* stats, const RtScene* scene, const uint32_t ext
     stats->scene_nodes = scene->n_nodes; stats->scene_prims = scene->n_prims; stats->scene_bytes = scene->bytes; stats->bvh_in_lds = scene->in_lds ? 1u : 0u;
 }
 
+// the launch configuration a scene's kernels take on this context; extend_geometry receives what k_extend was launched with (scene_stats)
+static rtk::LaunchCfg scene_launch_cfg(const RtCtx* ctx, const RtScene* scene, uint32_t extend_geometry[2]) {
+    rtk::LaunchCfg cfg{};
+    cfg.n_cu = (uint32_t)ctx->n_cu; cfg.extend_geometry = extend_geometry; cfg.features = scene->features; cfg.scene_in_lds = scene->in_lds;
+    return cfg;
+}
+// the queue geometry of a pool of P slots (pool_grain): all kQueues queues, each with its share of the slots
+static void set_queue_geometry(rtk::RenderDev& rd, uint32_t P) { rd.queue_cap = P / rtk::kQueues; rd.q_lo = 0u; rd.q_n = rtk::kQueues; rd.q_shift = rtk::kQShift; }
+// what an export scans of every queue after a chunk of n rays: a queue holds at most its share of the chunk's 512-ray groups
+static uint32_t export_bound(uint32_t queue_cap, uint32_t n) { return std::min<uint32_t>(queue_cap, ((n + 511u) / 512u + rtk::kQueues - 1u) / rtk::kQueues * 512u); }
+// The end of a chunk loop: the counters come back and the host waits, once per call. Then what every kind of call reports: the times of
+// its kernels by the kinds of its spans, the segments, the k_extend launches, the pool, the scene's part and the wall time since t_begin.
+static int finish_call(RtCtx* ctx, const CounterBlock& cb, const StreamTimer& tm, double* part_ms, std::chrono::steady_clock::time_point t_begin, const RtScene* scene,
+                       const rtk::LaunchCfg& cfg, uint32_t P, uint32_t launched, RtStats* stats) {
+    HIP_TRY(ctx, cb.read_stats(ctx));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (!stats) return RT_OK;
+    stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    tm.sum(part_ms);
+    stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];
+    stats->extend_launches = launched; stats->pool_slots = P;
+    scene_stats(stats, scene, cfg.extend_geometry);
+    return RT_OK;
+}
+
 // camera, frame, seed, background and tiling: what new_camera_ray and the slot <-> pixel decodes of every kernel read (kernels.h RenderDev)
 static rtk::RenderDev frame_render_dev(const RtScene* scene, const RtCamera* cam, const RtParams* prm, const Tiling& tl) {
     rtk::RenderDev rd{};
@@ -1003,7 +1075,7 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     // not the cap itself but total / k for the smallest k that fits the cap: 480 M items under a cap of 2^28 run as 2 x 240 M.
     if (!prm->pool_slots && P < total_items) { const uint64_t k = (total_items + P - 1u) / P; P = (uint32_t)((total_items + k - 1u) / k); }
     P = pool_grain(P);
-    rd.queue_cap = P / rtk::kQueues;
+    set_queue_geometry(rd, P);
     rtk::PoolDev pd[2];
     for (int k = 0; k < 2; ++k) { const int r = pool_bind(ctx, k, P, n_arrays, pd[k]); if (r != RT_OK) return r; }
     HIP_TRY(ctx, ctx->blocksum.ensure((size_t)total_items * 16));
@@ -1022,9 +1094,8 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     HIP_TRY(ctx, cb.zero_all());
 
     const bool counting = (prm->flags & RT_FLAG_COUNTERS) != 0, timing = (prm->flags & RT_FLAG_TIMING) != 0;
-    rtk::LaunchCfg cfg{};
     uint32_t extend_geometry[2] = {0u, 0u};
-    cfg.n_cu = (uint32_t)ctx->n_cu; cfg.extend_geometry = extend_geometry; cfg.features = scene->features; cfg.scene_in_lds = scene->in_lds;
+    rtk::LaunchCfg cfg = scene_launch_cfg(ctx, scene, extend_geometry);
 
     StreamTimer tm{ctx};
 
@@ -1032,7 +1103,6 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     if (timing) HIP_TRY(ctx, tm.mark(e0));
     const uint32_t n_init = (uint32_t)std::min<uint64_t>(P, total_items);
     rd.n_init = n_init; rd.lineage = P;
-    rd.q_lo = 0u; rd.q_n = rtk::kQueues; rd.q_shift = rtk::kQShift;
     // the ground sphere tested where a ray is made (kernels.h RenderDev::first_in_shade): a scene without motion, one such sphere, no counting
     rd.first_in_shade = scene->first_id != 0u && rtk::can_test_first_in_shade(scene->features) && !counting ? 1u : 0u;
     rd.first_id = scene->first_id; for (int k = 0; k < 8; ++k) rd.first_prim[k] = scene->first_prim[k];
@@ -1065,15 +1135,11 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     if (lp) HIP_TRY(ctx, rtk::launch_resolve_list(rd, (float*)d_out, ctx->stream));
     else HIP_TRY(ctx, rtk::launch_resolve(rd, (float*)d_out, (uint32_t)valid_pixels, ctx->stream));
     if (timing) { HIP_TRY(ctx, tm.mark(r1)); tm.span(r0, r1, 2); }
-    HIP_TRY(ctx, cb.read_stats(ctx));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    double part_ms[4] = {0.0, 0.0, 0.0, 0.0};                         // extend, shade, generate and resolve, drain
+    { const int r = finish_call(ctx, cb, tm, part_ms, t_begin, scene, cfg, P, launched, stats); if (r != RT_OK) return r; }
     if (stats) {
-        stats->render_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
-        double part_ms[4] = {0.0, 0.0, 0.0, 0.0};                     // extend, shade, generate and resolve, drain
-        tm.sum(part_ms);
         stats->extend_ms = part_ms[0]; stats->shade_ms = part_ms[1]; stats->other_ms = part_ms[2]; stats->drain_ms = part_ms[3];
         stats->samples = (lp ? (uint64_t)lp->n : valid_pixels) * prm->samples_per_pixel;
-        stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];
 #if defined(RT_STAMPS) || defined(RT_SHADE_STAMPS)
         const bool copy_counts = true;    // k_extend's pass statistics travel in these slots (scripts/gpu_stamps.py)
 #else
@@ -1087,9 +1153,7 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
 #ifdef RT_STAMPS
         stats->debug[5] = ctx->h_counters[rtk::CTR_SAMPLES];       // node steps of all waves (scripts/gpu_stamps.py)
 #endif
-        stats->iterations = (uint32_t)ctx->h_counters[rtk::CTR_ITERATIONS]; stats->extend_launches = launched; stats->shade_launches = launched; stats->pool_slots = P;
-        stats->drain_paths = drained;
-        scene_stats(stats, scene, extend_geometry);
+        stats->iterations = (uint32_t)ctx->h_counters[rtk::CTR_ITERATIONS]; stats->shade_launches = launched; stats->drain_paths = drained;
     }
     return RT_OK;
 }
@@ -1117,29 +1181,17 @@ int rt_render_pass(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const 
     const int v = check_pass(ctx, prm, options, nullptr); if (v != RT_OK) return v;
     uint64_t n = 0; rt_output_floats(prm, &n);
     const size_t bytes = n * sizeof(float);
-    const bool acc = (options->flags & RT_PASS_ACCUMULATE) != 0u;
+    const bool acc = (options->flags & RT_PASS_ACCUMULATE) != 0u;   // the fold then goes on from the caller's sums
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, ctx->out_tmp.ensure(bytes));
-    if (sq_sum_host) HIP_TRY(ctx, ctx->sq_tmp.ensure(bytes));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (acc) {   // the fold goes on from the caller's sums
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->out_tmp.p, rgb_sum_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (sq_sum_host) HIP_TRY(ctx, hipMemcpyAsync(ctx->sq_tmp.p, sq_sum_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    const int r = render_pass_checked(ctx, scene, cam, prm, *options, ctx->out_tmp.p, sq_sum_host ? ctx->sq_tmp.p : nullptr, stats);
-    if (r != RT_OK) return r;
-    HIP_TRY(ctx, hipMemcpyAsync(rgb_sum_host, ctx->out_tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (sq_sum_host) HIP_TRY(ctx, hipMemcpyAsync(sq_sum_host, ctx->sq_tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return RT_OK;
+    return staged_call(ctx, {{&ctx->out_tmp, acc ? rgb_sum_host : nullptr, rgb_sum_host, bytes}, {&ctx->sq_tmp, acc ? sq_sum_host : nullptr, sq_sum_host, bytes}}, stats,
+                       [&] { return render_pass_checked(ctx, scene, cam, prm, *options, ctx->out_tmp.p, sq_sum_host ? ctx->sq_tmp.p : nullptr, stats); });
 }
 
 // ---- adaptive sampling (include/rt_hip.h): selection of the active list, passes over a pixel list, per-pixel write_color ----------------
 static int check_adaptive(RtCtx* ctx, const RtParams* p, const RtAdaptiveOptions* o, uint32_t first_sample, uint32_t frame_samples, uint32_t* samples_per_item) {
     const int v = validate_params(ctx, p); if (v != RT_OK) return v;
     if (!o) return set_err(ctx, RT_ERR_INVALID, "adaptive options are null");
-    if (o->struct_bytes < sizeof(RtAdaptiveOptions) || o->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtAdaptiveOptions.struct_bytes is not set (sizeof(RtAdaptiveOptions))");
+    const int h = check_header(ctx, o->struct_bytes, sizeof(RtAdaptiveOptions), "RtAdaptiveOptions"); if (h != RT_OK) return h;
     if (!(std::isfinite(o->rel_error) && o->rel_error >= 0.0)) return set_err(ctx, RT_ERR_INVALID, "RtAdaptiveOptions.rel_error must be finite and >= 0");
     if (!(std::isfinite(o->abs_error) && o->abs_error >= 0.0)) return set_err(ctx, RT_ERR_INVALID, "RtAdaptiveOptions.abs_error must be finite and >= 0");
     if (frame_samples == 0u) return set_err(ctx, RT_ERR_INVALID, "frame_samples must be >= 1");
@@ -1254,10 +1306,7 @@ int rt_render(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtPar
 // ---- ray queries (include/rt_hip.h): caller's rays through the traversal kernels of a render, one RtRayHit each ---------------------------
 static_assert(sizeof(RtRay) == 32 && sizeof(RtRayHit) == 48 && sizeof(RtRayQueryOptions) == 16, "ray query records: 32, 48 and 16 bytes");
 static int check_ray_query(RtCtx* ctx, const RtRayQueryOptions* o, uint64_t n_rays) {
-    if (o) {
-        if (o->struct_bytes < sizeof(RtRayQueryOptions) || o->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtRayQueryOptions.struct_bytes is not set (sizeof(RtRayQueryOptions))");
-        if (o->flags & ~(uint32_t)RT_FLAG_TIMING) return set_err(ctx, RT_ERR_INVALID, "RtRayQueryOptions.flags holds an unknown bit (known: RT_FLAG_TIMING)");
-    }
+    if (o) { const int h = check_header(ctx, o->struct_bytes, sizeof(RtRayQueryOptions), "RtRayQueryOptions", o->flags, RT_FLAG_TIMING, "RT_FLAG_TIMING"); if (h != RT_OK) return h; }
     if (n_rays > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "n_rays must be < 2^32 (split the list)");
     return RT_OK;
 }
@@ -1282,11 +1331,10 @@ static int trace_rays_impl(RtCtx* ctx, const RtScene* scene, const RtRayQueryOpt
     HIP_TRY(ctx, cb.zero_all());
 
     rtk::RenderDev rd{};                     // a walk needs the queue geometry only; first_in_shade = 0: the record's time slot is the ray's time
-    rd.queue_cap = queue_cap; rd.q_lo = 0u; rd.q_n = rtk::kQueues; rd.q_shift = rtk::kQShift;
+    set_queue_geometry(rd, P);
     rd.div_nblocks = rtk::make_fastdiv(1u); rd.n_blocks = 1u;
-    rtk::LaunchCfg cfg{};
     uint32_t extend_geometry[2] = {0u, 0u};
-    cfg.n_cu = (uint32_t)ctx->n_cu; cfg.extend_geometry = extend_geometry; cfg.features = scene->features; cfg.scene_in_lds = scene->in_lds;
+    rtk::LaunchCfg cfg = scene_launch_cfg(ctx, scene, extend_geometry);
 
     StreamTimer tm{ctx};
     uint32_t launched = 0u;
@@ -1302,23 +1350,17 @@ static int trace_rays_impl(RtCtx* ctx, const RtScene* scene, const RtRayQueryOpt
         if (any_hit) LAUNCH_TRY(rtk::launch_extend_any(cfg, scene->dev, pd, rd, cb.count[0], cb.head, cb.count[1], cb.c64, ctx->stream));
         else LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd, rd, cb.count[0], cb.head, cb.count[1], cb.c64, false, ctx->stream));
         if (timing) HIP_TRY(ctx, tm.mark(ec));
-        // a queue holds at most its share of the chunk's 512-ray groups
-        const uint32_t per_queue = std::min<uint32_t>(queue_cap, ((n + 511u) / 512u + rtk::kQueues - 1u) / rtk::kQueues * 512u);
+        const uint32_t per_queue = export_bound(queue_cap, n);
         if (any_hit) LAUNCH_TRY(rtk::launch_occluded_export(pd, queue_cap, per_queue, cb.count[0], d_hits, ctx->stream));
         else LAUNCH_TRY(rtk::launch_rays_export(cfg, scene->dev, scene->src, pd, queue_cap, per_queue, cb.count[0], d_hits, ctx->stream));
         if (timing) { HIP_TRY(ctx, tm.mark(ed)); tm.span(ea, eb, 1); tm.span(eb, ec, 0); tm.span(ec, ed, 1); }
         ++launched;
     }
-    HIP_TRY(ctx, cb.read_stats(ctx));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    double part_ms[2] = {0.0, 0.0};                                   // extend, import and export
+    { const int r = finish_call(ctx, cb, tm, part_ms, t_begin, scene, cfg, P, launched, stats); if (r != RT_OK) return r; }
     if (stats) {
-        double part_ms[2] = {0.0, 0.0};                               // extend, import and export
-        tm.sum(part_ms);
         stats->extend_ms = part_ms[0]; stats->other_ms = part_ms[1];
-        stats->samples = stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];
-        stats->iterations = launched; stats->extend_launches = launched; stats->pool_slots = P;
-        scene_stats(stats, scene, extend_geometry);
-        stats->render_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
+        stats->samples = stats->segments; stats->iterations = launched;
     }
     return RT_OK;
 }
@@ -1341,31 +1383,16 @@ static int trace_rays_refuse(RtCtx* ctx, const RtScene* scene, const RtRayQueryO
 
 static int ray_query_device(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const void* rays_device, uint64_t n_rays, void* out_device, RtStats* stats,
                             const RayQueryKind& kind) {
-    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
-    const int v = trace_rays_refuse(ctx, scene, options, rays_device, n_rays, out_device, true, kind.out_align); if (v != RT_OK) return v;
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n_rays == 0u) return RT_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return drain_on_failure(ctx, trace_rays_impl(ctx, scene, options, rays_device, n_rays, out_device, stats, kind.any_hit));
+    return query_entry(ctx, stats, n_rays == 0u, false, [&] { return trace_rays_refuse(ctx, scene, options, rays_device, n_rays, out_device, true, kind.out_align); },
+                       [&] { return trace_rays_impl(ctx, scene, options, rays_device, n_rays, out_device, stats, kind.any_hit); });
 }
-// the host variant: the rays staged in, the device variant on the context's own buffers, the results staged out; render_ms covers all of it
+// the host variant: the rays staged in, the device variant on the context's own buffers, the results staged out (host buffers are copied: no alignment asked)
 static int ray_query_host(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const RtRay* rays_host, uint64_t n_rays, void* out_host, RtStats* stats,
                           const RayQueryKind& kind) {
-    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
-    const int v = trace_rays_refuse(ctx, scene, options, rays_host, n_rays, out_host, false, kind.out_align); if (v != RT_OK) return v;   // (host buffers are copied: no alignment asked)
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n_rays == 0u) return RT_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(ctx, ctx->rays_tmp.ensure((size_t)n_rays * sizeof(RtRay)));
-    HIP_TRY(ctx, ctx->hits_tmp.ensure((size_t)n_rays * kind.out_bytes));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->rays_tmp.p, rays_host, (size_t)n_rays * sizeof(RtRay), hipMemcpyHostToDevice, ctx->stream));
-    const int r = ray_query_device(ctx, scene, options, ctx->rays_tmp.p, n_rays, ctx->hits_tmp.p, stats, kind);
-    if (r != RT_OK) return r;
-    HIP_TRY(ctx, hipMemcpyAsync(out_host, ctx->hits_tmp.p, (size_t)n_rays * kind.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return RT_OK;
+    return query_entry(ctx, stats, n_rays == 0u, false, [&] { return trace_rays_refuse(ctx, scene, options, rays_host, n_rays, out_host, false, kind.out_align); }, [&] {
+        return staged_call(ctx, {{&ctx->rays_tmp, rays_host, nullptr, (size_t)n_rays * sizeof(RtRay)}, {&ctx->hits_tmp, nullptr, out_host, (size_t)n_rays * kind.out_bytes}}, stats,
+                           [&] { return ray_query_device(ctx, scene, options, ctx->rays_tmp.p, n_rays, ctx->hits_tmp.p, stats, kind); });
+    });
 }
 
 int rt_trace_rays_device(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* options, const void* rays_device, uint64_t n_rays, void* hits_device, RtStats* stats) {
@@ -1388,10 +1415,7 @@ int rt_occluded_rays(RtCtx* ctx, const RtScene* scene, const RtRayQueryOptions* 
 static_assert(sizeof(RtLightQuery) == 40 && sizeof(RtLightSample) == 24 && sizeof(RtLightQueryOptions) == 8, "light query records: 40, 24 and 8 bytes");
 static int light_query_refuse(RtCtx* ctx, const RtScene* scene, const RtLightQueryOptions* o, const void* queries, uint64_t n, const void* results, bool device) {
     if (!scene) return set_err(ctx, RT_ERR_INVALID, "scene is null");
-    if (o) {
-        if (o->struct_bytes < sizeof(RtLightQueryOptions) || o->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtLightQueryOptions.struct_bytes is not set (sizeof(RtLightQueryOptions))");
-        if (o->flags & ~(uint32_t)RT_FLAG_TIMING) return set_err(ctx, RT_ERR_INVALID, "RtLightQueryOptions.flags holds an unknown bit (known: RT_FLAG_TIMING)");
-    }
+    if (o) { const int h = check_header(ctx, o->struct_bytes, sizeof(RtLightQueryOptions), "RtLightQueryOptions", o->flags, RT_FLAG_TIMING, "RT_FLAG_TIMING"); if (h != RT_OK) return h; }
     if (n > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "n must be < 2^32 (split the list)");
     if ((scene->features & rtk::F_LIGHTS) == 0u || scene->dev.n_lights == 0u)
         return set_err(ctx, RT_ERR_UNSUPPORTED, "light-sample queries: the scene was uploaded without a lights list (RtSceneDesc.lights = -1)");
@@ -1421,29 +1445,15 @@ static int sample_lights_impl(RtCtx* ctx, const RtScene* scene, const RtLightQue
     return RT_OK;
 }
 int rt_sample_lights_device(RtCtx* ctx, const RtScene* scene, const RtLightQueryOptions* options, const void* queries_device, uint64_t n, void* results_device, RtStats* stats) {
-    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
-    const int v = light_query_refuse(ctx, scene, options, queries_device, n, results_device, true); if (v != RT_OK) return v;
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n == 0u) return RT_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return drain_on_failure(ctx, sample_lights_impl(ctx, scene, options, queries_device, n, results_device, stats));
+    return query_entry(ctx, stats, n == 0u, false, [&] { return light_query_refuse(ctx, scene, options, queries_device, n, results_device, true); },
+                       [&] { return sample_lights_impl(ctx, scene, options, queries_device, n, results_device, stats); });
 }
+// (host buffers are copied: no alignment asked)
 int rt_sample_lights(RtCtx* ctx, const RtScene* scene, const RtLightQueryOptions* options, const RtLightQuery* queries_host, uint64_t n, RtLightSample* results_host, RtStats* stats) {
-    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
-    const int v = light_query_refuse(ctx, scene, options, queries_host, n, results_host, false); if (v != RT_OK) return v;   // (host buffers are copied: no alignment asked)
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n == 0u) return RT_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(ctx, ctx->rays_tmp.ensure((size_t)n * sizeof(RtLightQuery)));
-    HIP_TRY(ctx, ctx->hits_tmp.ensure((size_t)n * sizeof(RtLightSample)));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->rays_tmp.p, queries_host, (size_t)n * sizeof(RtLightQuery), hipMemcpyHostToDevice, ctx->stream));
-    const int r = rt_sample_lights_device(ctx, scene, options, ctx->rays_tmp.p, n, ctx->hits_tmp.p, stats);
-    if (r != RT_OK) return r;
-    HIP_TRY(ctx, hipMemcpyAsync(results_host, ctx->hits_tmp.p, (size_t)n * sizeof(RtLightSample), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return RT_OK;
+    return query_entry(ctx, stats, n == 0u, false, [&] { return light_query_refuse(ctx, scene, options, queries_host, n, results_host, false); }, [&] {
+        return staged_call(ctx, {{&ctx->rays_tmp, queries_host, nullptr, (size_t)n * sizeof(RtLightQuery)}, {&ctx->hits_tmp, nullptr, results_host, (size_t)n * sizeof(RtLightSample)}}, stats,
+                           [&] { return rt_sample_lights_device(ctx, scene, options, ctx->rays_tmp.p, n, ctx->hits_tmp.p, stats); });
+    });
 }
 
 // ---- radiance queries (include/rt_hip.h): caller's rays through the render's own path loop, per-ray sums over a sample range ------------------
@@ -1453,8 +1463,7 @@ static_assert(sizeof(RtPathRay) == 32 && sizeof(RtRadianceOptions) == 56, "radia
 constexpr uint64_t kMaxStreams = 0xFFFFFFFFull;
 static int check_radiance(RtCtx* ctx, const RtRadianceOptions* o, uint64_t n_rays) {
     if (!o) return set_err(ctx, RT_ERR_INVALID, "radiance options are null");
-    if (o->struct_bytes < sizeof(RtRadianceOptions) || o->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtRadianceOptions.struct_bytes is not set (sizeof(RtRadianceOptions))");
-    if (o->flags & ~(uint32_t)RT_RADIANCE_ACCUMULATE) return set_err(ctx, RT_ERR_INVALID, "RtRadianceOptions.flags holds an unknown bit");
+    const int h = check_header(ctx, o->struct_bytes, sizeof(RtRadianceOptions), "RtRadianceOptions", o->flags, RT_RADIANCE_ACCUMULATE); if (h != RT_OK) return h;
     if (o->render_flags & ~(uint32_t)RT_FLAG_TIMING) return set_err(ctx, RT_ERR_INVALID, "RtRadianceOptions.render_flags holds an unknown bit (known: RT_FLAG_TIMING)");
     if (o->nan_policy > 1) return set_err(ctx, RT_ERR_INVALID, "bad nan_policy");
     if (o->samples == 0u) return set_err(ctx, RT_ERR_INVALID, "samples must be >= 1");
@@ -1502,16 +1511,15 @@ static int radiance_impl(RtCtx* ctx, const RtScene* scene, const RtRadianceOptio
     rd.seed = opt->seed; rd.max_depth = opt->max_depth; rd.nan_policy = opt->nan_policy;
     rd.bg_mode = scene->bg_mode; for (int i = 0; i < 3; ++i) rd.bg[i] = scene->bg[i];
     rd.block_shift = 0u;                                                                     // one sample per item: nothing regenerates, no camera is read
-    rd.queue_cap = P / rtk::kQueues; rd.q_lo = 0u; rd.q_n = rtk::kQueues; rd.q_shift = rtk::kQShift;
+    set_queue_geometry(rd, P);
     rd.first_in_shade = scene->first_id != 0u && rtk::can_test_first_in_shade(scene->features) ? 1u : 0u;
     rd.first_id = scene->first_id; for (int k = 0; k < 8; ++k) rd.first_prim[k] = scene->first_prim[k];
     rd.blocksum = (rtd::Float4*)ctx->blocksum.p;
     uint32_t* const iota = (uint32_t*)ctx->list_map.p;
     rd.list = iota; rd.counts = iota + n_chunk;
 
-    rtk::LaunchCfg cfg{};
     uint32_t extend_geometry[2] = {0u, 0u};
-    cfg.n_cu = (uint32_t)ctx->n_cu; cfg.extend_geometry = extend_geometry; cfg.features = scene->features; cfg.scene_in_lds = scene->in_lds;
+    rtk::LaunchCfg cfg = scene_launch_cfg(ctx, scene, extend_geometry);
     const uint32_t drain_at = drain_threshold(scene, opt->tail_paths, false);
     StreamTimer tm{ctx};
     uint32_t launched = 0u, drained = 0u;
@@ -1544,18 +1552,12 @@ static int radiance_impl(RtCtx* ctx, const RtScene* scene, const RtRadianceOptio
             s0 += sc;
         }
     }
-    HIP_TRY(ctx, cb.read_stats(ctx));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    double part_ms[4] = {0.0, 0.0, 0.0, 0.0};                         // extend, shade, import and fold, drain
+    { const int r = finish_call(ctx, cb, tm, part_ms, t_begin, scene, cfg, P, launched, stats); if (r != RT_OK) return r; }
     if (stats) {
-        double part_ms[4] = {0.0, 0.0, 0.0, 0.0};                     // extend, shade, import and fold, drain
-        tm.sum(part_ms);
         stats->extend_ms = part_ms[0]; stats->shade_ms = part_ms[1]; stats->other_ms = part_ms[2]; stats->drain_ms = part_ms[3];
         stats->samples = items - ctx->h_counters[rtk::CTR_SAMPLES];    // less the paths the imports dropped: valid rays x samples
-        stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];
-        stats->iterations = (uint32_t)ctx->h_counters[rtk::CTR_ITERATIONS]; stats->extend_launches = launched; stats->shade_launches = launched; stats->pool_slots = P;
-        stats->drain_paths = drained;
-        scene_stats(stats, scene, extend_geometry);
-        stats->render_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
+        stats->iterations = (uint32_t)ctx->h_counters[rtk::CTR_ITERATIONS]; stats->shade_launches = launched; stats->drain_paths = drained;
     }
     return RT_OK;
 }
@@ -1571,43 +1573,22 @@ static int radiance_refuse(RtCtx* ctx, const RtScene* scene, const RtRadianceOpt
 
 int rt_radiance_rays_device(RtCtx* ctx, const RtScene* scene, const RtRadianceOptions* options, const void* rays_device, uint64_t n_rays, void* rgb_sum_device,
                             void* sq_sum_device, void* invalid_device, RtStats* stats) {
-    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
-    const int v = radiance_refuse(ctx, scene, options, rays_device, n_rays, rgb_sum_device, sq_sum_device, true); if (v != RT_OK) return v;
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n_rays == 0u) return RT_OK;
-    if (ctx->fail_renders != 0u) { --ctx->fail_renders; return set_err(ctx, RT_ERR_DEVICE, "injected failure (rt_test_fail_next_renders)"); }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return drain_on_failure(ctx, radiance_impl(ctx, scene, options, rays_device, n_rays, rgb_sum_device, sq_sum_device, invalid_device, stats));
+    return query_entry(ctx, stats, n_rays == 0u, true, [&] { return radiance_refuse(ctx, scene, options, rays_device, n_rays, rgb_sum_device, sq_sum_device, true); },
+                       [&] { return radiance_impl(ctx, scene, options, rays_device, n_rays, rgb_sum_device, sq_sum_device, invalid_device, stats); });
 }
 // the host variant: rays (and, accumulating, the caller's sums) staged in, the device variant on the context's own buffers, the sums and flag
-// bytes staged out; render_ms covers all of it
+// bytes staged out (host buffers are copied: no alignment asked)
 int rt_radiance_rays(RtCtx* ctx, const RtScene* scene, const RtRadianceOptions* options, const RtPathRay* rays_host, uint64_t n_rays, float* rgb_sum_host,
                      float* sq_sum_host, uint8_t* invalid_host, RtStats* stats) {
-    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
-    const int v = radiance_refuse(ctx, scene, options, rays_host, n_rays, rgb_sum_host, sq_sum_host, false); if (v != RT_OK) return v;   // (host buffers are copied: no alignment asked)
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n_rays == 0u) return RT_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t bytes = (size_t)n_rays * 3u * sizeof(float);
-    HIP_TRY(ctx, ctx->rays_tmp.ensure((size_t)n_rays * sizeof(RtPathRay)));
-    HIP_TRY(ctx, ctx->out_tmp.ensure(bytes));
-    if (sq_sum_host) HIP_TRY(ctx, ctx->sq_tmp.ensure(bytes));
-    if (invalid_host) HIP_TRY(ctx, ctx->hits_tmp.ensure((size_t)n_rays));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->rays_tmp.p, rays_host, (size_t)n_rays * sizeof(RtPathRay), hipMemcpyHostToDevice, ctx->stream));
-    if (options->flags & RT_RADIANCE_ACCUMULATE) {   // the fold goes on from the caller's sums
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->out_tmp.p, rgb_sum_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (sq_sum_host) HIP_TRY(ctx, hipMemcpyAsync(ctx->sq_tmp.p, sq_sum_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    const int r = rt_radiance_rays_device(ctx, scene, options, ctx->rays_tmp.p, n_rays, ctx->out_tmp.p, sq_sum_host ? ctx->sq_tmp.p : nullptr,
-                                          invalid_host ? ctx->hits_tmp.p : nullptr, stats);
-    if (r != RT_OK) return r;
-    HIP_TRY(ctx, hipMemcpyAsync(rgb_sum_host, ctx->out_tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (sq_sum_host) HIP_TRY(ctx, hipMemcpyAsync(sq_sum_host, ctx->sq_tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (invalid_host) HIP_TRY(ctx, hipMemcpyAsync(invalid_host, ctx->hits_tmp.p, (size_t)n_rays, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (stats) stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return RT_OK;
+    return query_entry(ctx, stats, n_rays == 0u, false, [&] { return radiance_refuse(ctx, scene, options, rays_host, n_rays, rgb_sum_host, sq_sum_host, false); }, [&] {
+        const size_t bytes = (size_t)n_rays * 3u * sizeof(float);
+        const bool acc = (options->flags & RT_RADIANCE_ACCUMULATE) != 0u;   // the fold then goes on from the caller's sums
+        return staged_call(ctx, {{&ctx->rays_tmp, rays_host, nullptr, (size_t)n_rays * sizeof(RtPathRay)}, {&ctx->out_tmp, acc ? rgb_sum_host : nullptr, rgb_sum_host, bytes},
+                                 {&ctx->sq_tmp, acc ? sq_sum_host : nullptr, sq_sum_host, bytes}, {&ctx->hits_tmp, nullptr, invalid_host, (size_t)n_rays}}, stats, [&] {
+            return rt_radiance_rays_device(ctx, scene, options, ctx->rays_tmp.p, n_rays, ctx->out_tmp.p, sq_sum_host ? ctx->sq_tmp.p : nullptr,
+                                           invalid_host ? ctx->hits_tmp.p : nullptr, stats);
+        });
+    });
 }
 
 // ---- first-hit features (include/rt_hip.h): albedo, normal and depth of the render's own camera rays, as per-pixel sums ---------------------
@@ -1615,8 +1596,7 @@ static_assert(sizeof(RtFeatureOptions) == 16 && sizeof(RtFeatureBuffers) == 4 * 
 static int check_features(RtCtx* ctx, const RtParams* p, const RtFeatureOptions* o) {
     const int v = validate_params(ctx, p); if (v != RT_OK) return v;
     if (!o) return set_err(ctx, RT_ERR_INVALID, "feature options are null");
-    if (o->struct_bytes < sizeof(RtFeatureOptions) || o->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtFeatureOptions.struct_bytes is not set (sizeof(RtFeatureOptions))");
-    if (o->flags & ~(uint32_t)RT_FEATURES_ACCUMULATE) return set_err(ctx, RT_ERR_INVALID, "RtFeatureOptions.flags holds an unknown bit (known: RT_FEATURES_ACCUMULATE)");
+    const int h = check_header(ctx, o->struct_bytes, sizeof(RtFeatureOptions), "RtFeatureOptions", o->flags, RT_FEATURES_ACCUMULATE, "RT_FEATURES_ACCUMULATE"); if (h != RT_OK) return h;
     if ((uint64_t)o->first_sample + p->samples_per_pixel > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "first_sample + samples_per_pixel must be < 2^32");
     if (p->flags & (RT_FLAG_COUNTERS | RT_FLAG_FUSED)) return set_err(ctx, RT_ERR_INVALID, "a feature pass takes neither RT_FLAG_COUNTERS nor RT_FLAG_FUSED");
     return RT_OK;
@@ -1642,7 +1622,7 @@ static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, 
 
     // one pool, every ray in flight, plus 32 bytes of feature record per slot
     const uint32_t P = pool_grain(pool_size(opt->pool_slots, n_rays, pool_slot_bytes(5) + 32, pool_held_bytes(ctx, 0, 5) + ctx->feature_rec.bytes, 0));
-    rd.queue_cap = P / rtk::kQueues; rd.q_lo = 0u; rd.q_n = rtk::kQueues; rd.q_shift = rtk::kQShift;
+    set_queue_geometry(rd, P);
     rtk::PoolDev pd{};
     { const int r = pool_bind(ctx, 0, P, 5, pd); if (r != RT_OK) return r; }
     HIP_TRY(ctx, ctx->feature_rec.ensure((size_t)P * 32u));
@@ -1650,9 +1630,8 @@ static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, 
     HIP_TRY(ctx, cb.ensure(ctx));
     HIP_TRY(ctx, cb.zero_all());
 
-    rtk::LaunchCfg cfg{};
     uint32_t extend_geometry[2] = {0u, 0u};
-    cfg.n_cu = (uint32_t)ctx->n_cu; cfg.extend_geometry = extend_geometry; cfg.features = scene->features; cfg.scene_in_lds = scene->in_lds;
+    rtk::LaunchCfg cfg = scene_launch_cfg(ctx, scene, extend_geometry);
     rtk::FeatDev fd{};
     fd.first_sample = opt->first_sample; fd.rec = (rtd::Float4*)ctx->feature_rec.p;
     fd.albedo = (float*)out->albedo_sum; fd.normal = (float*)out->normal_sum; fd.depth = (float*)out->depth_sum; fd.hits = (uint32_t*)out->hits;
@@ -1674,9 +1653,7 @@ static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, 
             cfg.max_rays = n;
             LAUNCH_TRY(rtk::launch_extend(cfg, scene->dev, pd, rd, cb.count[0], cb.head, cb.count[1], cb.c64, false, ctx->stream));
             if (timing) HIP_TRY(ctx, tm.mark(ec));
-            // a queue holds at most its share of the chunk's 512-ray groups
-            const uint32_t per_queue = std::min<uint32_t>(rd.queue_cap, ((n + 511u) / 512u + rtk::kQueues - 1u) / rtk::kQueues * 512u);
-            LAUNCH_TRY(rtk::launch_features_export(cfg, scene->dev, rd, fd, pd, per_queue, cb.count[0], ctx->stream));
+            LAUNCH_TRY(rtk::launch_features_export(cfg, scene->dev, rd, fd, pd, export_bound(rd.queue_cap, n), cb.count[0], ctx->stream));
             if (timing) HIP_TRY(ctx, tm.mark(ed));
             if (moments) LAUNCH_TRY(rtk::launch_features_fold_moments(rd, fd, *moments, ctx->stream));
             else LAUNCH_TRY(rtk::launch_features_fold(rd, fd, ctx->stream));
@@ -1684,17 +1661,12 @@ static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, 
             ++launched;
         }
     }
-    HIP_TRY(ctx, cb.read_stats(ctx));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    double part_ms[4] = {0.0, 0.0, 0.0, 0.0};                         // extend, import, export, fold
+    { const int r = finish_call(ctx, cb, tm, part_ms, t_begin, scene, cfg, P, launched, stats); if (r != RT_OK) return r; }
     if (stats) {
-        double part_ms[4] = {0.0, 0.0, 0.0, 0.0};                     // extend, import, export, fold
-        tm.sum(part_ms);
         stats->extend_ms = part_ms[0]; stats->other_ms = part_ms[1] + part_ms[2] + part_ms[3];
         for (int k = 0; k < 3; ++k) stats->debug[k] = (uint64_t)(part_ms[k + 1] * 1000.0 + 0.5);     // microseconds of the import, export and fold kernels
-        stats->samples = stats->segments = ctx->h_counters[rtk::CTR_SEGMENTS];
-        stats->iterations = launched; stats->extend_launches = launched; stats->pool_slots = P;
-        scene_stats(stats, scene, extend_geometry);
-        stats->render_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
+        stats->samples = stats->segments; stats->iterations = launched;
     }
     return RT_OK;
 }
@@ -1702,7 +1674,6 @@ static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, 
 // What both feature entry points check, in two parts because the moments variant checks its own record in between: the call (a refused
 // call has written nothing), then the caller's planes — one wanted at least, each 16-byte aligned.
 static int features_refuse(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* options) {
-    if (!ctx) return set_err(nullptr, RT_ERR_INVALID, "ctx is null");
     if (!scene || !cam) return set_err(ctx, RT_ERR_INVALID, "scene / cam is null");
     const int v = check_features(ctx, prm, options); if (v != RT_OK) return v;
     if (scene->features & rtk::F_MEDIUM)
@@ -1718,35 +1689,36 @@ static int feature_planes_refuse(RtCtx* ctx, std::initializer_list<const void*> 
 
 int rt_render_features_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* options, const RtFeatureBuffers* buffers,
                               RtStats* stats) {
-    const int v = features_refuse(ctx, scene, cam, prm, options); if (v != RT_OK) return v;
     const RtFeatureBuffers none{nullptr, nullptr, nullptr, nullptr}, &b = buffers ? *buffers : none;
-    const int w = feature_planes_refuse(ctx, {b.albedo_sum, b.normal_sum, b.depth_sum, b.hits}, "no feature buffer is wanted (all four pointers are null)"); if (w != RT_OK) return w;
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return drain_on_failure(ctx, features_impl(ctx, scene, cam, prm, options, buffers, stats, nullptr));
+    return query_entry(ctx, stats, false, false, [&] {
+        const int v = features_refuse(ctx, scene, cam, prm, options);
+        return v != RT_OK ? v : feature_planes_refuse(ctx, {b.albedo_sum, b.normal_sum, b.depth_sum, b.hits}, "no feature buffer is wanted (all four pointers are null)");
+    }, [&] { return features_impl(ctx, scene, cam, prm, options, buffers, stats, nullptr); });
 }
 
 // ---- first-hit features, second moments (include/rt_hip.h): the same pass, with the per-slot sums of squares beside the sums ---------------
 static_assert(sizeof(RtFeatureMomentBuffers) == 8 * sizeof(void*), "feature moment buffers: struct_bytes (padded) and seven pointers");
+static int check_moment_buffers(RtCtx* ctx, const RtFeatureMomentBuffers* b) {
+    if (!b) return set_err(ctx, RT_ERR_INVALID, "feature moment buffers are null");
+    return check_header(ctx, b->struct_bytes, sizeof(RtFeatureMomentBuffers), "RtFeatureMomentBuffers");
+}
 int rt_feature_moments_check(const RtParams* params, const RtFeatureOptions* options, const RtFeatureMomentBuffers* buffers) {
-    const int v = check_features(nullptr, params, options); if (v != RT_OK) return v;
-    if (!buffers) return set_err(nullptr, RT_ERR_INVALID, "feature moment buffers are null");
-    if (buffers->struct_bytes < sizeof(RtFeatureMomentBuffers) || buffers->struct_bytes > 4096u) return set_err(nullptr, RT_ERR_INVALID, "RtFeatureMomentBuffers.struct_bytes is not set (sizeof(RtFeatureMomentBuffers))");
-    return RT_OK;
+    const int v = check_features(nullptr, params, options);
+    return v != RT_OK ? v : check_moment_buffers(nullptr, buffers);
 }
 
 int rt_render_feature_moments_device(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* options,
                                      const RtFeatureMomentBuffers* b, RtStats* stats) {
-    const int v = features_refuse(ctx, scene, cam, prm, options); if (v != RT_OK) return v;
-    if (!b) return set_err(ctx, RT_ERR_INVALID, "feature moment buffers are null");
-    if (b->struct_bytes < sizeof(RtFeatureMomentBuffers) || b->struct_bytes > 4096u) return set_err(ctx, RT_ERR_INVALID, "RtFeatureMomentBuffers.struct_bytes is not set (sizeof(RtFeatureMomentBuffers))");
-    const int w = feature_planes_refuse(ctx, {b->albedo_sum, b->normal_sum, b->depth_sum, b->hits, b->albedo_sq_sum, b->normal_sq_sum, b->depth_sq_sum},
-                                        "no feature buffer is wanted (all seven pointers are null)"); if (w != RT_OK) return w;
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const RtFeatureBuffers sums{b->albedo_sum, b->normal_sum, b->depth_sum, b->hits};
-    const rtk::FeatMomDev fm{(float*)b->albedo_sq_sum, (float*)b->normal_sq_sum, (float*)b->depth_sq_sum};
-    return drain_on_failure(ctx, features_impl(ctx, scene, cam, prm, options, &sums, stats, &fm));
+    return query_entry(ctx, stats, false, false, [&] {
+        int v = features_refuse(ctx, scene, cam, prm, options);
+        if (v == RT_OK) v = check_moment_buffers(ctx, b);
+        return v != RT_OK ? v : feature_planes_refuse(ctx, {b->albedo_sum, b->normal_sum, b->depth_sum, b->hits, b->albedo_sq_sum, b->normal_sq_sum, b->depth_sq_sum},
+                                                      "no feature buffer is wanted (all seven pointers are null)");
+    }, [&] {
+        const RtFeatureBuffers sums{b->albedo_sum, b->normal_sum, b->depth_sum, b->hits};
+        const rtk::FeatMomDev fm{(float*)b->albedo_sq_sum, (float*)b->normal_sq_sum, (float*)b->depth_sq_sum};
+        return features_impl(ctx, scene, cam, prm, options, &sums, stats, &fm);
+    });
 }
 
 int rt_untile(const RtParams* p, const float* gathered, float* rgb_sum) { return untile_host<float>(p, gathered, rgb_sum); }
@@ -1755,20 +1727,13 @@ int rt_untile_rgb8(const RtParams* p, const uint8_t* gathered, uint8_t* rgb8) { 
 int rt_scene_compile_info(const RtSceneDesc* desc, RtCompileInfo* out) { return rt_scene_compile_info_ex(desc, nullptr, out); }
 int rt_scene_compile_info_ex(const RtSceneDesc* desc, const RtUploadOptions* options, RtCompileInfo* out) {
     if (!desc || !out) return set_err(nullptr, RT_ERR_INVALID, "null argument");
-    { std::string why; const int ok = check_options(options, why); if (ok != RT_OK) return set_err(nullptr, ok, why); }
-    rtc::CompiledScene cs;
-    const int rc = rtc::compile_scene(*desc, resolve_options(options).compile, cs);
-    if (rc != RT_OK) return set_err(nullptr, rc, "scene: " + cs.error);
+    rtc::CompiledScene cs; std::string why; uint32_t n_with = 0u;
+    { const int ok = compile_checked(*desc, options, cs, nullptr, &n_with, why); if (ok != RT_OK) return set_err(nullptr, ok, why); }
     out->n_nodes = cs.nodes.size(); out->n_box_nodes = cs.n_box_nodes; out->n_spheres = cs.sphere_meta.size(); out->n_moving = cs.moving_meta.size();
     out->n_rects = cs.rect_meta.size(); out->n_tris = cs.tri_meta.size(); out->n_media = cs.media.size(); out->n_xforms = cs.xforms.size();
     out->n_lights = cs.n_lights; out->n_materials = cs.mat_b.size();
-    out->features = scene_features(cs);
-    {
-        std::string why;
-        const int ok = tri_attr_table(*desc, options, cs, nullptr, &out->n_tri_attrs, why);
-        if (ok != RT_OK) return set_err(nullptr, ok, why);
-        if (out->n_tri_attrs != 0u) out->features |= rtk::F_TRI_ATTR;
-    }
+    out->features = scene_features(cs) | (n_with != 0u ? rtk::F_TRI_ATTR : 0u);
+    out->n_tri_attrs = n_with;
     out->fits_lds = lds_scene_bytes(cs) <= kLdsSceneBudget ? 1u : 0u;
     {   // what a walk tests before it enters the tree: the root list's every-ray members, then the root BVH's scene-sized spheres
         std::vector<uint32_t> first = cs.prologue;
@@ -1874,11 +1839,8 @@ int rt_scene_compile_dump(const RtSceneDesc* desc, void* nodes, uint64_t cap_nod
 int rt_scene_compile_dump_ex(const RtSceneDesc* desc, const RtUploadOptions* options, void* nodes, uint64_t cap_nodes, float* spheres, uint32_t* sphere_meta,
                              uint64_t cap_spheres) {
     if (!desc) return set_err(nullptr, RT_ERR_INVALID, "null argument");
-    { std::string why; const int ok = check_options(options, why); if (ok != RT_OK) return set_err(nullptr, ok, why); }
-    rtc::CompiledScene cs;
-    const int rc = rtc::compile_scene(*desc, resolve_options(options).compile, cs);
-    if (rc != RT_OK) return set_err(nullptr, rc, "scene: " + cs.error);
-    { uint32_t n_with; std::string why; const int ok = tri_attr_table(*desc, options, cs, nullptr, &n_with, why); if (ok != RT_OK) return set_err(nullptr, ok, why); }
+    rtc::CompiledScene cs; std::string why; uint32_t n_with = 0u;
+    { const int ok = compile_checked(*desc, options, cs, nullptr, &n_with, why); if (ok != RT_OK) return set_err(nullptr, ok, why); }
     if ((nodes && cap_nodes < cs.nodes.size()) || ((spheres || sphere_meta) && cap_spheres < cs.sphere_meta.size())) return set_err(nullptr, RT_ERR_INVALID, "capacity too small");
     if (nodes) std::memcpy(nodes, cs.nodes.data(), cs.nodes.size() * sizeof(rtd::Node));
     if (spheres) std::memcpy(spheres, cs.spheres.data(), cs.spheres.size() * sizeof(rtd::Float4));
@@ -1894,9 +1856,7 @@ int rt_scene_wide_layout_check(const RtSceneDesc* desc, RtWideInfo* out) {
     const int rc = rtc::compile_scene(*desc, copt, cs);
     if (rc != RT_OK) return set_err(nullptr, rc, "scene: " + cs.error);
     if (!rtw::eligible(cs.nodes)) return set_err(nullptr, RT_ERR_UNSUPPORTED, "not a static BVH: the scene keeps the binary walk");
-    double extent = 0.0;
-    for (int a = 0; a < 3; ++a) extent = std::max(extent, std::max(std::fabs((double)cs.nodes[0].mn[a]), std::fabs((double)cs.nodes[0].mx[a])));
-    const float margin = (float)(6e-7 * extent);
+    const float margin = wide_margin(cs.nodes);
     rtw::WideTree wt; std::string err;
     if (!rtw::build(cs.nodes, margin, wt, err)) return set_err(nullptr, RT_ERR_UNSUPPORTED, err);
     // true box of one primitive (f64 from the compiled f32 data: what the kernel's tests see)

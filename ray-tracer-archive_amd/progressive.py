@@ -85,6 +85,28 @@ def std_error(rgb_sum, sq_sum, samples, samples_per_item):
     return np.sqrt(var) / m
 
 
+def on_device(a, dev):
+    """A host array (an untiled plane of sums or counts) as a flat tensor on `dev`."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(dev)
+
+
+def denoise_front(frame, opts, feature_samples, sigma_albedo, sigma_normal, sigma_depth, feature_variance, variance_strength):
+    """The front of Progressive.denoised and Adaptive.denoised: the argument check, the guide of a feature pass of the frame's camera rays
+    (into opts["guide"]), and the frame's sums as full-frame device tensors — its own, or for a sharded frame its untiled ones. Returns
+    (rgb_sum, sq_sum, sharded)."""
+    from .denoise import render_guide
+    if feature_variance and int(feature_samples) < 2:
+        raise ValueError("feature_variance needs feature_samples >= 2")
+    p, dev = frame.params, frame._rgb.device
+    if feature_samples:
+        opts["guide"] = render_guide(frame.ctx, frame.scene, frame.cam, p, feature_samples, sigma_albedo, sigma_normal, sigma_depth, moments=bool(feature_variance),
+                                     variance_strength=variance_strength)
+    if p.shard_count <= 1:
+        return frame._rgb, frame._sq, False
+    return on_device(frame.rgb_sum(), dev), on_device(frame.sq_sum(), dev), True
+
+
 class Progressive:
     """A frame rendered in passes into device accumulators owned by this object (torch tensors on the context's GPU)."""
 
@@ -175,7 +197,7 @@ class Progressive:
             raise ValueError("no samples rendered yet")
         p = self.params
         dev = self._rgb.device
-        src = self._rgb if p.shard_count <= 1 else torch.from_numpy(self.rgb_sum().reshape(-1)).to(dev)
+        src = self._rgb if p.shard_count <= 1 else on_device(self.rgb_sum(), dev)
         out = torch.empty(p.height * p.width * 3, dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
         self.ctx.resolve_device(src.data_ptr(), p.width, p.height, self.samples_done, out.data_ptr())
@@ -190,27 +212,20 @@ class Progressive:
         feature_variance=True with feature_samples = N >= 2: the pass keeps the features' second moments (Context.render_feature_moments)
         and the filter is rt_denoise_guided_moments_device (sigmas and variance_strength: RtDenoiseGuideMoments, 0 = the default;
         window_radius 0 = 8, at most 8)."""
-        from .denoise import denoise_frame, render_guide
-        if feature_variance and int(feature_samples) < 2:
-            raise ValueError("feature_variance needs feature_samples >= 2")
+        from .denoise import denoise_frame
         if self.samples_done == 0:
             raise ValueError("no samples rendered yet")
         if self._sq is None:
             raise ValueError("this frame keeps no squared sums (sq_sum=False)")
-        import torch
-        p, dev = self.params, self._rgb.device
-        if feature_samples:
-            opts["guide"] = render_guide(self.ctx, self.scene, self.cam, p, feature_samples, sigma_albedo, sigma_normal, sigma_depth, moments=bool(feature_variance),
-                                         variance_strength=variance_strength)
-        if p.shard_count <= 1:
-            return denoise_frame(self.ctx, self._rgb, self._sq, p.width, p.height, self.samples_per_item, samples=self.samples_done, rgb8=rgb8, **opts)
+        p = self.params
+        rgb, sq, sharded = denoise_front(self, opts, feature_samples, sigma_albedo, sigma_normal, sigma_depth, feature_variance, variance_strength)
+        if not sharded:
+            return denoise_frame(self.ctx, rgb, sq, p.width, p.height, self.samples_per_item, samples=self.samples_done, rgb8=rgb8, **opts)
         from .adaptive import slot_pixels
         x, y, ok = slot_pixels(p)
         cnt = np.zeros((p.height, p.width), dtype=np.int32)          # the other shards' pixels hold no sample: nobody's neighbours
         cnt[y[ok], x[ok]] = self.samples_done
-        rgb = torch.from_numpy(np.ascontiguousarray(self.rgb_sum()).reshape(-1)).to(dev)
-        sq = torch.from_numpy(np.ascontiguousarray(self.sq_sum()).reshape(-1)).to(dev)
-        return denoise_frame(self.ctx, rgb, sq, p.width, p.height, self.samples_per_item, counts=torch.from_numpy(cnt.reshape(-1)).to(dev), rgb8=rgb8, **opts)
+        return denoise_frame(self.ctx, rgb, sq, p.width, p.height, self.samples_per_item, counts=on_device(cnt, rgb.device), rgb8=rgb8, **opts)
 
     def features(self, samples):
         """First-hit features of this frame's camera rays (rt_render_features_device), from a pass of its own of `samples` samples per pixel
