@@ -153,12 +153,29 @@ struct RenderDev {
     // the kernel that made it writes its hit record and sets kRayAnswered in the ray record. Only for the sphere-only instances, the scene in LDS,
     // no counting (rt_api.cpp render_impl).
     const uint32_t* cam_lists; uint32_t cam_squares_x;
-    const rtd::Float4* cam_spheres;   // the scene's spheres in HBM (k_generate has no SceneDev)
+    uint32_t cam_shade;               // in-place camera shading, below (in what was padding: the block keeps its size, no kernel's hidden arguments move)
+    const rtd::Float4* cam_spheres;   // the scene's spheres in HBM (camera_list_hit reads them there in every kernel)
+    // In-place camera shading (cam_shade; 0: off; only with cam_lists): a camera ray that its square's list answers with a HIT is shaded by the lane that
+    // made it, which holds ray, RNG, throughput and hit in registers, and the scattered ray is what gets stored (depth 1, kRayShaded set) — no
+    // record and hit written, walked past by k_extend and read back by k_shade only to be shaded. kCamShadeGenerate: in k_generate;
+    // kCamShadeRegen: in k_shade's regeneration. The host sets it only where such a shade always leaves a path that goes on (max_depth >= 2, no
+    // DiffuseLight sphere) and the time slot of every record is >= 0 (rt_api.cpp render_impl).
 };
+constexpr uint32_t kCamShadeGenerate = 1u, kCamShadeRegen = 2u;
+#ifndef RT_CAMERA_SHADE
+#define RT_CAMERA_SHADE 3   // tuning builds: 0 = off, 1 = k_generate only, 3 = k_generate and k_shade's regeneration
+#endif
 // Bit 31 of a ray record's `from` word (ray_d.w): the ray's hit record is already written, k_extend's refill hands its lane no walk. Primitive ids
 // are type << 28 | index with type < 8, so the bit is free; it is only ever set on camera rays (from = 0), and every reader of the word that
 // can meet it masks it off (the refill of the sphere-only LDS walk, the drain's load), so `from` means downstream what it meant.
 constexpr uint32_t kRayAnswered = 0x80000000u;
+// The sign bit of a ray record's time slot (ray_o.w), only in renders with RenderDev::cam_shade: the segment before this ray was shaded where its
+// camera ray was made, so it stood in no queue and the k_shade (or the drain) that reads this record counts it into `segments`. The slot holds
+// the first sphere's t (>= 0 or +inf) or a time >= 0 in such renders, so the bit is free; every reader of the slot that can meet it takes the
+// magnitude (the refill of the sphere-only LDS walk, the drain's load, k_shade's load). A k_shade workgroup's count of them leaves in the upper
+// half of its ONE allocation atomic, 64 bits wide on the queue's size line: size += n_alloc, the word behind it += n_shaded. k_extend zeroes the
+// lower word only, so the upper words accumulate over the render and the host adds them to CTR_SEGMENTS (rt_api.cpp render_impl).
+constexpr uint32_t kRayShaded = 0x80000000u;
 
 struct LaunchCfg {
     uint32_t n_cu;            // k_extend runs as a persistent grid: n_cu x (resident workgroups per CU)
@@ -176,7 +193,8 @@ struct CamListsDev { rtcl::Camera cam; const float* spheres; const uint32_t* ord
 hipError_t launch_camera_lists(const CamListsDev& cl, hipStream_t stream);
 // whether the kernels a scene of these features runs are the ones compiled to honour kRayAnswered (the sphere-only variant)
 bool camera_lists_fit(uint32_t features);
-hipError_t launch_generate(const PoolDev& pool, const RenderDev& rd, uint32_t n_init, uint32_t* out_count, hipStream_t stream);
+// sc: the scene, for the in-place shade of the instances with camera lists (RenderDev::cam_shade)
+hipError_t launch_generate(const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, uint32_t n_init, uint32_t* out_count, hipStream_t stream);
 // One wavefront iteration = launch_extend then launch_shade. No memsets in between: k_extend zeroes
 // the count the following k_shade appends to, k_shade zeroes the queue head of the next k_extend.
 hipError_t launch_extend(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,

@@ -889,6 +889,7 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
             const Float4 ro = pool.ray_o[qbase + i], rdv = pool.ray_d[qbase + i], s0 = pool.s0[qbase + i];
             const uint32_t sd = pool.sd[qbase + i];
             o = v3(ro.x, ro.y, ro.z); d = v3(rdv.x, rdv.y, rdv.z); tm = ro.w;
+            if constexpr (MARKS) { if (rd.cam_shade != 0u) { c_segments += (__float_as_uint(tm) & kRayShaded) != 0u ? 1ull : 0ull; tm = fabsf(tm); } }   // (kernels.h kRayShaded)
             if (rd.first_in_shade != 0u) tm = 0.f;     // (the slot held the first sphere's t for a k_extend of the other kind; this walk starts parked at that sphere)
             ps.T = v3(s0.x, s0.y, s0.z); ps.work = __float_as_uint(s0.w); ps.from = __float_as_uint(rdv.w);
             if constexpr (MARKS) ps.from &= ~kRayAnswered;     // a camera ray answered where it was made is walked here all the same: same hit, no second path
@@ -915,7 +916,7 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
             if (take != 0u) {
                 const uint32_t rank = lane_rank(idle);
                 const int src = (int)(rank & 63u);
-                const float ox = __shfl(No.x, src), oy = __shfl(No.y, src), oz = __shfl(No.z, src), ot = __shfl(No.w, src);
+                const float ox = __shfl(No.x, src), oy = __shfl(No.y, src), oz = __shfl(No.z, src), ot = MARKS ? fabsf(__shfl(No.w, src)) : __shfl(No.w, src);   // (kRayShaded)
                 const float dx = __shfl(Nd.x, src), dy = __shfl(Nd.y, src), dz = __shfl(Nd.z, src), dfrom = __shfl(Nd.w, src);
                 // (MARKS) a ray answered where it was made: its hit record is written, the lane stays idle and takes the next refill's ray. (A refill
                 // that goes on handing out rays at once while kRefillMin lanes are still idle measured the same: DESIGN.md section 4.)
@@ -1519,6 +1520,26 @@ DEVI uint32_t block_alloc_two(bool a, bool b, uint32_t* counter, uint32_t* s_sca
     return a ? base + (prefix & 0xFFFFu) + lane_rank(ma) : b ? base + n_a + (prefix >> 16) + lane_rank(mb) : 0xFFFFFFFFu;
 }
 
+// block_alloc_two that also counts the `c` threads of the workgroup — the paths whose record carries kRayShaded (kernels.h) — and hands that
+// count on in the upper half of the same atomic, 64 bits wide: *counter += n_a + n_b, the word behind it += n_c. No atomic of its own: a
+// per-workgroup atomic on one more address per queue is what the queues were introduced to avoid.
+DEVI uint32_t block_alloc_two_counted(bool a, bool b, bool c, uint32_t* counter, uint32_t* s_scan) {
+    static_assert(kShadeThreads <= 512u, "three totals of 10 bits each in one word");
+    const uint32_t wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const uint64_t ma = __ballot(a), mb = __ballot(b), mc = __ballot(c);
+    if ((threadIdx.x & 63u) == 0u) s_scan[wave] = (uint32_t)__popcll(ma) | ((uint32_t)__popcll(mb) << 10) | ((uint32_t)__popcll(mc) << 20);
+    __syncthreads();
+    uint32_t prefix = 0, total = 0;
+    for (uint32_t w = 0; w < nw; ++w) { const uint32_t n = s_scan[w]; prefix += (w < wave) ? n : 0u; total += n; }
+    const uint32_t n_a = total & 0x3FFu, n_b = (total >> 10) & 0x3FFu, n_c = total >> 20;
+    if (threadIdx.x == 0u && total != 0u)
+        s_scan[nw] = (uint32_t)atomicAdd(reinterpret_cast<unsigned long long*>(counter), (unsigned long long)(n_a + n_b) | ((unsigned long long)n_c << 32));
+    __syncthreads();
+    const uint32_t base = s_scan[nw];
+    __syncthreads();
+    return a ? base + (prefix & 0x3FFu) + lane_rank(ma) : b ? base + n_a + ((prefix >> 10) & 0x3FFu) + lane_rank(mb) : 0xFFFFFFFFu;
+}
+
 // The same allocation, but the workgroup's survivors leave it ORDERED by `key` (< kSortBins; counting sort in LDS): paths of one key get
 // consecutive slots, keys in ascending order. For scenes walked from HBM the key is (direction octant, cell of the origin): the 64 rays
 // a wave of k_extend then takes together start in the same record array and near each other, so their first visits hit the same cache
@@ -1621,9 +1642,24 @@ __global__ void __launch_bounds__(64) k_camera_lists(CamListsDev cl) {
     rtcl::build_list(cl.cam, i % sqx, i / sqx, cl.spheres, cl.order, cl.n_order, cl.lists + (size_t)i * rtcl::kListWords);
 }
 
+// In-place camera shading (kernels.h RenderDev::cam_shade), the part k_generate and k_shade's regeneration share: the camera ray (o, d) of a
+// path that has just begun an item was answered with the hit (tmax, hit_prim) of a sphere. Shade that segment here, as the next k_shade would
+// have from the stored record — same function, same values — and take the first sphere's t for the scattered ray as k_shade does for a ray it
+// scatters. The host grants cam_shade only where the shade cannot end the path, so the lane leaves with a ray to store: depth 1, no hit record,
+// kRayShaded in the time slot.
+DEVI void camera_shade(const SceneDev& sc, const RenderDev& rd, V3& o, V3& d, float& tm, PathState& s, Rng& g, uint32_t& depth, float tmax, uint32_t hit_prim) {
+    V3 L; unsigned long long c0 = 0, c1 = 0, c2 = 0;
+    const float tm_ray = rd.first_in_shade != 0u ? 0.f : tm;              // (k_shade's load: the slot carried the first sphere's t, nothing moves)
+    const uint32_t sh = shade_segment<0u>(sc, rd, o, d, tm_ray, s, g, depth, make_uint2(__float_as_uint(tmax), hit_prim), L, c0, c1, c2);
+    tm = (sh & SH_TIME_ZERO) ? 0.0f : tm_ray;
+    if (rd.first_in_shade != 0u) tm = first_sphere_hit(rd, o, d, s.from);
+    tm = __uint_as_float(__float_as_uint(tm) | kRayShaded);
+}
+
 // CAML: the render has camera lists (kernels.h RenderDev::cam_lists): the ray is answered here, k_extend hands it no walk
+// sc: the scene, for the in-place shade of an answered ray that hit (CAML only; nullptr otherwise)
 template <bool LIST, bool CAML>
-__global__ void __launch_bounds__(kShadeThreads) k_generate(PoolDev pool, RenderDev rd, uint32_t n_init, uint32_t* __restrict__ out_count) {
+DEVI void generate_paths(const PoolDev& pool, const RenderDev& rd, uint32_t n_init, uint32_t* __restrict__ out_count, const SceneDev* sc) {
     // the first fill of the pool needs no allocator: work item i goes to queue (i / 512) mod kQueues, slot (i / 4096) * 512 + i mod 512
     // of it (the host passes n_init <= total_items), and the counters get their values from kQueues threads. (With the atomics +
     // barriers of block_alloc this kernel was latency-bound: 6.0 ms for 268 M paths at 41 % of the HBM write rate.)
@@ -1634,7 +1670,7 @@ __global__ void __launch_bounds__(kShadeThreads) k_generate(PoolDev pool, Render
     }
     if (i < n_init) {
         PathState s; V3 o, d; float tm; Rng g;
-        uint32_t square = 0u;
+        uint32_t square = 0u, depth = 0u;
         start_item<LIST>(rd, i, s, g, o, d, tm, CAML ? &square : nullptr);
         if (rd.first_in_shade != 0u) tm = first_sphere_hit(rd, o, d, 0u);         // (the time slot of a motionless scene: kernels.h)
         const uint32_t q = (i >> 9) & (kQueues - 1u), slot = ((i / (512u * kQueues)) << 9) | (i & 511u);
@@ -1642,10 +1678,25 @@ __global__ void __launch_bounds__(kShadeThreads) k_generate(PoolDev pool, Render
             // as k_extend's refill begins such a ray: the first sphere's t from the time slot, or nothing
             float tmax = rd.first_in_shade != 0u ? tm : kInf;
             uint32_t hit_prim = tmax < kInf ? rd.first_id : rtd::HIT_NONE;
-            if (camera_list_hit(rd, square, o, d, tmax, hit_prim)) { pool.hit[q * rd.queue_cap + slot] = make_uint2(__float_as_uint(tmax), hit_prim); s.from = kRayAnswered; }
+            if (camera_list_hit(rd, square, o, d, tmax, hit_prim)) {
+                if ((RT_CAMERA_SHADE & kCamShadeGenerate) != 0u && (rd.cam_shade & kCamShadeGenerate) != 0u && hit_prim != rtd::HIT_NONE)
+                    camera_shade(*sc, rd, o, d, tm, s, g, depth, tmax, hit_prim);
+                else { pool.hit[q * rd.queue_cap + slot] = make_uint2(__float_as_uint(tmax), hit_prim); s.from = kRayAnswered; }
+            }
         }
-        store_path(pool, q * rd.queue_cap + slot, o, d, tm, s, g.n, 0u, rd.block_shift != 0u);
+        store_path(pool, q * rd.queue_cap + slot, o, d, tm, s, g.n, depth, rd.block_shift != 0u);
     }
+}
+template <bool LIST, bool CAML>
+__global__ void __launch_bounds__(kShadeThreads) k_generate(PoolDev pool, RenderDev rd, uint32_t n_init, uint32_t* __restrict__ out_count) {
+    static_assert(!CAML, "the instances with camera lists take the scene");
+    generate_paths<LIST, false>(pool, rd, n_init, out_count, nullptr);
+}
+// ... and with camera lists: the same kernel with the scene as one more argument, which the instances above do not have
+template <bool LIST, bool CAML>
+__global__ void __launch_bounds__(kShadeThreads) k_generate(PoolDev pool, RenderDev rd, uint32_t n_init, uint32_t* __restrict__ out_count, SceneDev sc) {
+    static_assert(CAML, "only the instances with camera lists take the scene");
+    generate_paths<LIST, true>(pool, rd, n_init, out_count, &sc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2149,7 +2200,9 @@ template <uint32_t FEAT, bool COUNT, bool LIST, bool CAML = false>
 #ifndef RT_SHADE_WAVES
 #define RT_SHADE_WAVES (FEAT == (F_RECT | F_XFORM | F_LIGHTS) ? 6 : 4)
 #endif
-__attribute__((amdgpu_waves_per_eu(RT_SHADE_WAVES, 8)))
+// (the instance that shades camera rays in place is held to the 8 waves every sphere-only instance runs at: left to itself the second inlined
+// shade_segment takes it to 63 VGPRs, 65 with LIST; so bounded it takes 59 and no scratch)
+__attribute__((amdgpu_waves_per_eu((CAML && (RT_CAMERA_SHADE & 2) != 0) ? 8 : RT_SHADE_WAVES, 8)))
 __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in, PoolDev out, RenderDev rd, const uint32_t* __restrict__ count_in_ptr,
                                                 uint32_t* __restrict__ count_out, uint32_t* __restrict__ head_to_zero,
                                                 unsigned long long* __restrict__ counters) {
@@ -2214,10 +2267,12 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
     Rng g; g.s = 0; g.n = 0u; uint32_t depth = 0u;
     bool began = false;                // this thread's path has just begun a new work item (a camera ray)
     uint32_t cam_square = 0u;          // CAML: ... and the square of its pixel
+    bool shaded = false;               // CAML: the record carries kRayShaded (kernels.h): the segment before this one stood in no queue
     if (alive) {
         const Float4 ro = in.ray_o[qbase + i], rdv = in.ray_d[qbase + i], s0 = in.s0[qbase + i];
         const uint32_t sd = in.sd[qbase + i]; const uint2 hit = in.hit[qbase + i];
         o = v3(ro.x, ro.y, ro.z); d = v3(rdv.x, rdv.y, rdv.z); tm = ro.w;
+        if constexpr (CAML) { if (rd.cam_shade != 0u) { shaded = (__float_as_uint(tm) & kRayShaded) != 0u; tm = fabsf(tm); } }
         if (rd.first_in_shade != 0u) tm = 0.f;        // the slot carried the first sphere's t to k_extend; nothing moves in such a scene
         s.T = v3(s0.x, s0.y, s0.z); s.work = __float_as_uint(s0.w);
         uint32_t stored = 0u;
@@ -2256,7 +2311,7 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
     SSTAMP(3);
     {
         uint32_t dst;
-        if (sc.sort_rays != 0u) {
+        if (!CAML && sc.sort_rays != 0u) {      // (a render with camera lists walks its scene in LDS)
             // scenes walked from HBM: survivors ordered by (direction octant of the record arrays, 4 x 4 x 4 cell of the origin over the scene's bounds)
             const uint32_t oct = ((d.x < 0.f ? 1u : 0u) | (d.y < 0.f ? 2u : 0u) | (d.z < 0.f ? 4u : 0u)) & sc.oct_mask;
             const float k4 = 4.0f / 65536.0f;
@@ -2267,6 +2322,8 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
         } else {
             // the paths that go on first, the new camera rays behind them: the waves of k_extend that take the latter walk the same boxes
             // together (book-1 k_extend -1.2 ms), and it costs the scan nothing
+            if constexpr (CAML) dst = block_alloc_two_counted(alive && !began, alive && began, shaded, count_out, s_scan);
+            else
             dst = block_alloc_two(alive && !began, alive && began, count_out, s_scan);
         }
         SSTAMP(4);
@@ -2275,7 +2332,11 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
             if (alive && began) {      // as in k_generate
                 float tmax = rd.first_in_shade != 0u ? tm : kInf;
                 uint32_t hit_prim = tmax < kInf ? rd.first_id : rtd::HIT_NONE;
-                if (camera_list_hit(rd, cam_square, o, d, tmax, hit_prim)) { out.hit[qbase + dst] = make_uint2(__float_as_uint(tmax), hit_prim); s.from = kRayAnswered; }
+                if (camera_list_hit(rd, cam_square, o, d, tmax, hit_prim)) {
+                    if ((RT_CAMERA_SHADE & kCamShadeRegen) != 0u && (rd.cam_shade & kCamShadeRegen) != 0u && hit_prim != rtd::HIT_NONE)
+                        camera_shade(sc, rd, o, d, tm, s, g, depth, tmax, hit_prim);
+                    else { out.hit[qbase + dst] = make_uint2(__float_as_uint(tmax), hit_prim); s.from = kRayAnswered; }
+                }
             }
         }
         if (alive) store_path(out, qbase + dst, o, d, tm, s, g.n, depth, with_acc);
@@ -3099,11 +3160,14 @@ hipError_t launch_shade(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev&
     return hipGetLastError();
 }
 
-hipError_t launch_generate(const PoolDev& pool, const RenderDev& rd, uint32_t n_init, uint32_t* out_count, hipStream_t stream) {
+hipError_t launch_generate(const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, uint32_t n_init, uint32_t* out_count, hipStream_t stream) {
     const uint32_t blocks = (n_init + kShadeThreads - 1u) / kShadeThreads;
     if (blocks == 0u) return hipSuccess;
-    with_flag(rd.n_list != 0u, [&](auto list) { with_flag(rd.cam_lists != nullptr, [&](auto caml) {
-        hipLaunchKernelGGL((k_generate<decltype(list)::value, decltype(caml)::value>), dim3(blocks), dim3(kShadeThreads), 0, stream, pool, rd, n_init, out_count); }); });
+    with_flag(rd.n_list != 0u, [&](auto list) {
+        if (rd.cam_lists != nullptr)
+            hipLaunchKernelGGL((k_generate<decltype(list)::value, true>), dim3(blocks), dim3(kShadeThreads), 0, stream, pool, rd, n_init, out_count, sc);
+        else
+            hipLaunchKernelGGL((k_generate<decltype(list)::value, false>), dim3(blocks), dim3(kShadeThreads), 0, stream, pool, rd, n_init, out_count); });
     return hipGetLastError();
 }
 

@@ -774,6 +774,8 @@ int rti::scene_image_upload(RtCtx* ctx, const SceneImage& im, RtScene** out_scen
     d.sb_mat_a = sb[6]; d.sb_mat_b = sb[7]; d.sb_xforms = sb[8]; d.sb_wraps = sb[9]; d.sb_lights = sb[10]; d.sb_textures = sb[11];
     s->src = rtk::RaySrcDev{(const uint32_t*)s->sphere_src.p, (const uint32_t*)s->moving_src.p, (const uint32_t*)s->rect_src.p, (const uint32_t*)s->tri_src.p};
     s->features = im.features;
+    // a sphere with a DiffuseLight material: a camera ray can end on it, so such a scene's camera rays are not shaded where they are made (render_impl)
+    for (const uint32_t meta : cs.sphere_meta) if ((cs.mat_b[meta & rtd::META_MAT_MASK] & 15u) == rtd::MK_DIFFUSE_LIGHT) s->sphere_emits = true;
     s->in_lds = im.in_lds; s->lds_bytes = lds_scene_bytes(cs);
     s->bg_mode = cs.background_mode; for (int i = 0; i < 3; ++i) s->bg[i] = cs.background[i];
     if (cs.first_leaf != 0u && ((cs.first_leaf >> 24) & 15u) == 1u) {
@@ -1120,8 +1122,13 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
         LAUNCH_TRY(rtk::launch_camera_lists(cl, ctx->stream));
         rd.cam_lists = cl.lists; rd.cam_squares_x = rtcl::squares_x(prm->width); rd.cam_spheres = scene->dev.spheres;
         ctx->cam_squares = cl.n_squares;
+        // In-place camera shading (kernels.h RenderDev::cam_shade): only where the shade of a camera ray that hit a sphere always leaves a path
+        // that goes on — it cannot reach the depth limit (max_depth >= 2) and cannot end on an emitter (no DiffuseLight sphere; a throughput that
+        // is not finite still scatters) — so the first fill gets no holes. The mark of such a record is the sign of its time slot (kRayShaded):
+        // that slot is the first sphere's t, or the camera's time, which then must not be negative.
+        if (prm->max_depth >= 2u && !scene->sphere_emits && (rd.first_in_shade != 0u || (rd.cam_time0 >= 0.f && rd.cam_time1 >= 0.f))) rd.cam_shade = RT_CAMERA_SHADE;
     }
-    HIP_TRY(ctx, rtk::launch_generate(pd[0], rd, n_init, cb.count[0], ctx->stream));
+    HIP_TRY(ctx, rtk::launch_generate(scene->dev, pd[0], rd, n_init, cb.count[0], ctx->stream));
     if (timing) { HIP_TRY(ctx, tm.mark(e1)); tm.span(e0, e1, 2); }
     uint32_t launched = 0u, drained = 0u;
     { const int r = wavefront_loop(ctx, scene, rd, pd, cb, cfg, tm, timing, counting, drain_threshold(scene, prm->tail_paths, (prm->flags & RT_FLAG_FUSED) != 0u), n_init, launched, drained);
@@ -1135,9 +1142,14 @@ static int render_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, co
     if (lp) HIP_TRY(ctx, rtk::launch_resolve_list(rd, (float*)d_out, ctx->stream));
     else HIP_TRY(ctx, rtk::launch_resolve(rd, (float*)d_out, (uint32_t)valid_pixels, ctx->stream));
     if (timing) { HIP_TRY(ctx, tm.mark(r1)); tm.span(r0, r1, 2); }
+    // the segments shaded where their camera ray was made stood in no queue: k_shade counted them into the word behind every queue size
+    // (kernels.h kRayShaded). The wavefront loop has read its last ring slot by now, so the ring (4 x kQueues words) takes the 2 x kQueues.
+    if (rd.cam_shade != 0u && stats)
+        HIP_TRY(ctx, hipMemcpy2DAsync(ctx->h_count, sizeof(uint32_t), cb.count[0] + 1, CounterBlock::kLine, sizeof(uint32_t), 2u * rtk::kQueues, hipMemcpyDeviceToHost, ctx->stream));
     double part_ms[4] = {0.0, 0.0, 0.0, 0.0};                         // extend, shade, generate and resolve, drain
     { const int r = finish_call(ctx, cb, tm, part_ms, t_begin, scene, cfg, P, launched, stats); if (r != RT_OK) return r; }
     if (stats) {
+        if (rd.cam_shade != 0u) for (uint32_t k = 0; k < 2u * rtk::kQueues; ++k) stats->segments += ctx->h_count[k];
         stats->extend_ms = part_ms[0]; stats->shade_ms = part_ms[1]; stats->other_ms = part_ms[2]; stats->drain_ms = part_ms[3];
         stats->samples = (lp ? (uint64_t)lp->n : valid_pixels) * prm->samples_per_pixel;
 #if defined(RT_STAMPS) || defined(RT_SHADE_STAMPS)

@@ -70,6 +70,7 @@ struct RtScene {
     rtk::RaySrcDev src{};
     rti::DevBuf cam_order; uint32_t n_cam_order = 0;   // camera lists: the tree's spheres in leaf order (rt_api.cpp camera_order); 0: the lists do not serve this scene
     uint32_t features = 0; bool in_lds = false;
+    bool sphere_emits = false;                          // a sphere has a DiffuseLight material
     uint32_t first_id = 0; float first_prim[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the ONE sphere or rect every walk tests first (hit id; centre + radius, or the rect's two records), first_id = 0: none or several
     int bg_mode = 0; float bg[3] = {0, 0, 0};
     uint64_t n_nodes = 0, n_prims = 0, bytes = 0, lds_bytes = 0;
