@@ -239,18 +239,17 @@ hipError_t launch_write_color(const float* rgb_sum, uint32_t n_pixels, uint32_t 
 // block, not part of SceneDev: no render kernel's arguments change.
 struct RaySrcDev { const uint32_t* sphere; const uint32_t* moving; const uint32_t* rect; const uint32_t* tri; };
 // rays [first, first + n) of the list (RtRay records) into `pool`, spread over its queues; `counts` (zeroed by the caller) receives the queues'
-// sizes, invalid rays get their RtRayHit at once, counters[CTR_SEGMENTS] counts the rays stored. n <= kQueues * queue_cap, queue_cap % 512 == 0.
-hipError_t launch_rays_import(const void* rays, uint32_t first, uint32_t n, const PoolDev& pool, uint32_t queue_cap, uint32_t* counts, void* hits,
-                              unsigned long long* counters, hipStream_t stream);
+// sizes, counters[CTR_SEGMENTS] counts the rays stored. n <= kQueues * queue_cap, queue_cap % 512 == 0. An invalid ray gets its answer at once:
+// its RtRayHit in `answers`, or with `occlusion` (kernels.hip "occlusion queries") its byte, RT_RAYHIT_INVALID_RAY. limit_in_d (occlusion only) =
+// !extend_any_is_closest(scene): the record carries the ray's limit where the any-hit walk reads it.
+hipError_t launch_rays_import(const void* rays, uint32_t first, uint32_t n, const PoolDev& pool, uint32_t queue_cap, uint32_t* counts, void* answers,
+                              unsigned long long* counters, bool occlusion, bool limit_in_d, hipStream_t stream);
 // after launch_extend: one RtRayHit per pool slot, at its ray's index (max_count: upper bound of the rays in one queue)
 hipError_t launch_rays_export(const LaunchCfg& cfg, const SceneDev& sc, const RaySrcDev& src, const PoolDev& pool, uint32_t queue_cap, uint32_t max_count,
                               const uint32_t* counts, void* hits, hipStream_t stream);
-// occlusion queries (kernels.hip "occlusion queries"): the import writes RT_RAYHIT_INVALID_RAY into the byte of a dropped ray; limit_in_d =
-// !extend_any_is_closest(scene): the record carries the ray's limit where the any-hit walk reads it. launch_extend_any: the any-hit k_extend, or
-// the closest-hit k_extend_wide for a scene uploaded with the 8-wide tree; the export writes 0 / RT_RAYHIT_HIT at every stored ray's index.
+// occlusion queries: launch_extend_any is the any-hit k_extend, or the closest-hit k_extend_wide for a scene uploaded with the 8-wide tree; the
+// export writes 0 / RT_RAYHIT_HIT at every stored ray's index.
 bool extend_any_is_closest(const SceneDev& sc);
-hipError_t launch_occluded_import(const void* rays, uint32_t first, uint32_t n, const PoolDev& pool, uint32_t queue_cap, uint32_t* counts, void* occluded,
-                                  unsigned long long* counters, bool limit_in_d, hipStream_t stream);
 hipError_t launch_extend_any(const LaunchCfg& cfg, const SceneDev& sc, const PoolDev& pool, const RenderDev& rd, const uint32_t* count_ptr,
                              uint32_t* head, uint32_t* count_out_to_zero, unsigned long long* counters, hipStream_t stream);
 hipError_t launch_occluded_export(const PoolDev& pool, uint32_t queue_cap, uint32_t max_count, const uint32_t* counts, void* occluded, hipStream_t stream);
@@ -272,11 +271,10 @@ hipError_t launch_features_import(const RenderDev& rd, const FeatDev& fd, const 
 // after launch_extend: one feature record per pool slot (max_count: upper bound of the rays in one queue); then the per-slot fold into the planes
 hipError_t launch_features_export(const LaunchCfg& cfg, const SceneDev& sc, const RenderDev& rd, const FeatDev& fd, const PoolDev& pool, uint32_t max_count,
                                   const uint32_t* counts, hipStream_t stream);
-hipError_t launch_features_fold(const RenderDev& rd, const FeatDev& fd, hipStream_t stream);
-// the fold with second moments (rt_hip.h "first-hit features, second moments"): the caller's squared-sum planes, nullptr = not wanted. Its
-// own block beside FeatDev, so that the kernels which take FeatDev alone keep their arguments.
+// moments (rt_hip.h "first-hit features, second moments"): the caller's squared-sum planes beside the sums, nullptr = not wanted. Its own block
+// beside FeatDev, so that the kernels which take FeatDev alone keep their arguments.
 struct FeatMomDev { float* albedo_sq; float* normal_sq; float* depth_sq; };
-hipError_t launch_features_fold_moments(const RenderDev& rd, const FeatDev& fd, const FeatMomDev& fm, hipStream_t stream);
+hipError_t launch_features_fold(const RenderDev& rd, const FeatDev& fd, const FeatMomDev* moments, hipStream_t stream);
 // radiance queries (kernels.hip "radiance queries"). RadianceDev: one chunk of a query — samples [rd.first_sample, rd.first_sample + n_samples)
 // of rays [ray0, ray0 + n) of the caller's list — as a pixel-list pass over a virtual unsharded frame whose pixel index is the ray's STREAM:
 // item blk * n + i is sample blk of ray ray0 + i, which runs on stream (pixel) stream0 + i. Its own block, like RaySrcDev and FeatDev.

@@ -676,7 +676,7 @@ __host__ DEVI uint32_t lds_record_bytes(const SceneDev& sc) { return sc.n_record
 //
 // ANYHIT: the occlusion walk of a ray query (rt_hip.h rt_occluded_rays): "is anything hit in [t_min, t_max]?". Three differences, all
 // `if constexpr`, so that every ANYHIT = false instance is the program it was: (1) a walk begins with the ray's own limit as t_max — the
-// record's ray_d.w carries it (k_occluded_import; such a ray starts on nothing, so `from` is 0) — and boxes beyond the target are culled
+// record's ray_d.w carries it (k_rays_import<true>; such a ray starts on nothing, so `from` is 0) — and boxes beyond the target are culled
 // from the first node on; (2) a lane that holds a hit after the prologue or after a primitive pass stores it and retires at once, also
 // inside a Translate / RotateY instance: no record is rebuilt, so nothing has to be switched back; (3) nothing else: pool.hit gets the
 // same (t, primitive) pair, of which k_occluded_export reads "is there one". Queries only: no counters, no drain, no pixel list.
@@ -940,7 +940,7 @@ __global__ void __launch_bounds__(TPB) k_extend(SceneDev sc, PoolDev pool, const
                         mkey = path_base(rd.seed, (uint64_t)pixel, smp);
                     }
                     if constexpr (ANYHIT) {
-                        // the interval is the ray's own (k_occluded_import: +inf for "no limit"); a prologue member that is hit ends the walk
+                        // the interval is the ray's own (k_rays_import<true>: +inf for "no limit"); a prologue member that is hit ends the walk
                         tmax = dfrom; hit_prim = rtd::HIT_NONE; go_root();
                         prologue();
                         if (hit_prim != rtd::HIT_NONE) { pool.hit[qbase + slot] = make_uint2(__float_as_uint(tmax), hit_prim); go_idle(); }
@@ -2370,6 +2370,28 @@ __global__ void __launch_bounds__(kShadeThreads) k_shade(SceneDev sc, PoolDev in
 // The fold is sequential in sample order, in f32, with no atomics: a pass that starts from the value already in the output
 // (rd.accumulate) continues exactly the additions one render over all samples makes, so passes over [0, a), [a, b), ... leave the same
 // bits as one render over [0, b) (rt_render_pass). sq_sum folds the squares of the same item sums in the same order.
+DEVI void resolve_fold(const RenderDev& rd, float* __restrict__ out, uint64_t o, uint64_t first, uint64_t stride) {
+    float* q = out + o;                                                  // item sums blocksum[first + blk * stride] -> the three floats at o
+    float r = 0.f, gg = 0.f, b = 0.f;
+    if (rd.accumulate != 0u) { r = q[0]; gg = q[1]; b = q[2]; }
+    if (rd.sq_sum != nullptr) {
+        float* qs = rd.sq_sum + o;
+        float r2 = 0.f, g2 = 0.f, b2 = 0.f;
+        if (rd.accumulate != 0u) { r2 = qs[0]; g2 = qs[1]; b2 = qs[2]; }
+        for (uint32_t blk = 0; blk < rd.n_blocks; ++blk) {
+            const Float4 v = rd.blocksum[first + (uint64_t)blk * stride];
+            r += v.x; gg += v.y; b += v.z;
+            r2 += v.x * v.x; g2 += v.y * v.y; b2 += v.z * v.z;   // (-ffp-contract=off: a rounded product, then the add)
+        }
+        qs[0] = r2; qs[1] = g2; qs[2] = b2;
+    } else {
+        for (uint32_t blk = 0; blk < rd.n_blocks; ++blk) {
+            const Float4 v = rd.blocksum[first + (uint64_t)blk * stride];
+            r += v.x; gg += v.y; b += v.z;
+        }
+    }
+    q[0] = r; q[1] = gg; q[2] = b;
+}
 __global__ void __launch_bounds__(256) k_resolve(RenderDev rd, float* __restrict__ out) {
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;          // one thread per in-image pixel of this shard
     if (gid >= rd.tile_prefix[rd.n_local_tiles]) return;
@@ -2382,55 +2404,16 @@ __global__ void __launch_bounds__(256) k_resolve(RenderDev rd, float* __restrict
     tile_pixel(rd, g, p, px, py);
     const uint64_t o = rd.shard_count <= 1u ? ((uint64_t)(g.y0 + py) * rd.width + (g.x0 + px)) * 3u
                                             : ((uint64_t)lt * ts2 + (uint64_t)py * rd.tile_size + px) * 3u;   // tile-compact layout
-    float* q = out + o;
-    float r = 0.f, gg = 0.f, b = 0.f;
-    if (rd.accumulate != 0u) { r = q[0]; gg = q[1]; b = q[2]; }
-    if (rd.sq_sum != nullptr) {
-        float* qs = rd.sq_sum + o;
-        float r2 = 0.f, g2 = 0.f, b2 = 0.f;
-        if (rd.accumulate != 0u) { r2 = qs[0]; g2 = qs[1]; b2 = qs[2]; }
-        for (uint32_t blk = 0; blk < rd.n_blocks; ++blk) {
-            const Float4 v = rd.blocksum[base + (uint64_t)blk * valid];
-            r += v.x; gg += v.y; b += v.z;
-            r2 += v.x * v.x; g2 += v.y * v.y; b2 += v.z * v.z;   // (-ffp-contract=off: a rounded product, then the add)
-        }
-        qs[0] = r2; qs[1] = g2; qs[2] = b2;
-    } else {
-        for (uint32_t blk = 0; blk < rd.n_blocks; ++blk) {
-            const Float4 v = rd.blocksum[base + (uint64_t)blk * valid];
-            r += v.x; gg += v.y; b += v.z;
-        }
-    }
-    q[0] = r; q[1] = gg; q[2] = b;
+    resolve_fold(rd, out, o, base, valid);
 }
 
-// k_resolve of a pass over a pixel list: one thread per list entry, item sums blocksum[blk * n_list + i] folded in block order with
-// k_resolve's arithmetic, into the entry's output slot; counts[slot] = the pass's end
+// k_resolve of a pass over a pixel list: one thread per list entry, item sums blocksum[blk * n_list + i] folded the same way into the
+// entry's output slot; counts[slot] = the pass's end
 __global__ void __launch_bounds__(256) k_resolve_list(RenderDev rd, float* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rd.n_list) return;
     const uint32_t slot = rd.list[i];
-    const uint64_t o = (uint64_t)slot * 3u;
-    float* q = out + o;
-    float r = 0.f, gg = 0.f, b = 0.f;
-    if (rd.accumulate != 0u) { r = q[0]; gg = q[1]; b = q[2]; }
-    if (rd.sq_sum != nullptr) {
-        float* qs = rd.sq_sum + o;
-        float r2 = 0.f, g2 = 0.f, b2 = 0.f;
-        if (rd.accumulate != 0u) { r2 = qs[0]; g2 = qs[1]; b2 = qs[2]; }
-        for (uint32_t blk = 0; blk < rd.n_blocks; ++blk) {
-            const Float4 v = rd.blocksum[(uint64_t)blk * rd.n_list + i];
-            r += v.x; gg += v.y; b += v.z;
-            r2 += v.x * v.x; g2 += v.y * v.y; b2 += v.z * v.z;
-        }
-        qs[0] = r2; qs[1] = g2; qs[2] = b2;
-    } else {
-        for (uint32_t blk = 0; blk < rd.n_blocks; ++blk) {
-            const Float4 v = rd.blocksum[(uint64_t)blk * rd.n_list + i];
-            r += v.x; gg += v.y; b += v.z;
-        }
-    }
-    q[0] = r; q[1] = gg; q[2] = b;
+    resolve_fold(rd, out, (uint64_t)slot * 3u, i, rd.n_list);
     rd.counts[slot] = rd.spp;
 }
 
@@ -2481,229 +2464,49 @@ DEVI void store_ray_miss(Float4* __restrict__ hits, uint32_t idx, uint32_t flags
     hits[1] = Float4{0.f, 0.f, 0.f, 0.f};
     hits[2] = Float4{0.f, 0.f, 0.f, 0.f};
 }
+// The tail the import kernels share: workgroup b feeds queue b mod kQueues; a slot from the queue's size counter (every thread of the
+// workgroup calls this); false where the thread stores nothing. `at`: the record's index in the pool.
+DEVI bool import_slot(bool valid, uint32_t* __restrict__ counts, uint32_t queue_cap, uint32_t* s_scan, uint32_t& at) {
+    const uint32_t q = blockIdx.x & (kQueues - 1u);
+    const uint32_t slot = block_alloc(valid, counts + q * kQStride, s_scan);
+    at = q * queue_cap + slot;
+    return valid && slot < queue_cap;
+}
+// OCCLUSION (rt_hip.h rt_occluded_rays: the same rays -> the any-hit k_extend -> one byte per ray): a dropped ray gets its BYTE,
+// RT_RAYHIT_INVALID_RAY, and with limit_in_d the record's ray_d.w — "the primitive this ray starts on", 0 for every query ray — carries the
+// ray's limit as the any-hit walk wants it (+inf for t_max <= 0, +inf or NaN), so that the walk's refill finds it in the words it prefetches
+// anyway. Without limit_in_d (scenes walked by k_extend_wide, closest hit) the slot stays 0. s0.x keeps the caller's t_max.
+template <bool OCCLUSION>
 __global__ void __launch_bounds__(kRaysImportThreads) k_rays_import(const Float4* __restrict__ rays, uint32_t first, uint32_t n, PoolDev pool, uint32_t queue_cap,
-                                                                     uint32_t* __restrict__ counts, Float4* __restrict__ hits, unsigned long long* __restrict__ counters) {
+                                                                     uint32_t* __restrict__ counts, void* __restrict__ answers,
+                                                                     unsigned long long* __restrict__ counters, uint32_t limit_in_d) {
     __shared__ uint32_t s_scan[kRaysImportThreads / 64 + 1];
-    const uint32_t i = blockIdx.x * kRaysImportThreads + threadIdx.x, q = blockIdx.x & (kQueues - 1u);
+    const uint32_t i = blockIdx.x * kRaysImportThreads + threadIdx.x;
     Float4 ro = Float4{0.f, 0.f, 0.f, 0.f}, rdv = Float4{0.f, 0.f, 0.f, 0.f};
     const bool mine = i < n;
     if (mine) { const Float4* r = rays + 2ull * (first + i); ro = r[0]; rdv = r[1]; }
-    const bool valid = mine && query_ray_valid(ro, rdv);
-    const uint32_t slot = block_alloc(valid, counts + q * kQStride, s_scan);      // every thread of the workgroup calls it
-    const bool stored = valid && slot < queue_cap;
+    uint32_t at;
+    const bool stored = import_slot(mine && query_ray_valid(ro, rdv), counts, queue_cap, s_scan, at);
     if (stored) {
-        const uint32_t at = q * queue_cap + slot;
-        pool.ray_o[at] = ro;
-        pool.ray_d[at] = Float4{rdv.x, rdv.y, rdv.z, __uint_as_float(0u)};
-        pool.s0[at] = Float4{rdv.w, 0.f, 0.f, __uint_as_float(first + i)};
-        pool.sd[at] = 0u;
-    }
-    if (mine && !stored) store_ray_miss(hits, first + i, kRayHitInvalid);
-    const uint64_t m = __ballot(stored);
-    if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(&counters[CTR_SEGMENTS], (unsigned long long)__popcll(m));
-}
-
-// k_rays_export: (ray, hit = (t, primitive)) of every pool slot -> one RtRayHit at the ray's index. The HitRecord is rebuilt with the
-// arithmetic of shade_segment's block "rebuild the HitRecord" — restated here, not shared, because that function's code must not move (its
-// register counts sit at occupancy boundaries; DESIGN.md section 2 has its miscompile) — with two differences: u, v of a sphere are always
-// computed, and a medium cannot occur (the host refuses such scenes). tests/test_gpu_rays.py::test_export_agrees_with_shade keeps the two in
-// step. The tables are read where the upload put them (HBM / L2): one pass over the pool, nothing staged.
-template <uint32_t FEAT>
-__global__ void __launch_bounds__(256) k_rays_export(SceneDev sc, RaySrcDev src, PoolDev pool, uint32_t queue_cap, const uint32_t* __restrict__ counts,
-                                                      Float4* __restrict__ hits) {
-    const uint32_t q = blockIdx.x & (kQueues - 1u), i = (blockIdx.x >> kQShift) * blockDim.x + threadIdx.x;
-    if (i >= min(counts[q * kQStride], queue_cap)) return;
-    const uint32_t at = q * queue_cap + i;
-    const Float4 ro = pool.ray_o[at], rdv = pool.ray_d[at], s0 = pool.s0[at];
-    const uint2 hit = pool.hit[at];
-    const uint32_t ray = __float_as_uint(s0.w);
-    const float t = __uint_as_float(hit.x), t_max = s0.x, tm = ro.w;
-    const bool limited = t_max > 0.f && t_max < kInf;                             // (t_max <= 0, +inf or NaN: no limit)
-    if (hit.y == rtd::HIT_NONE || (limited && t > t_max)) { store_ray_miss(hits, ray, 0u); return; }
-    const V3 o = v3(ro.x, ro.y, ro.z), d = v3(rdv.x, rdv.y, rdv.z);
-    // ---- rebuild the HitRecord (hittable.rs:11-19) from (ray, t, primitive): shade_segment's block ----
-    const uint32_t type = hit.y >> 28, idx = hit.y & rtd::LEAF_MAX_FIRST;
-    const uint32_t meta = type == rtd::LT_SPHERE ? sc.sphere_meta[idx]
-                        : ((FEAT & F_RECT) && type == rtd::LT_RECT) ? sc.rect_meta[idx]
-                        : ((FEAT & F_MOVING) && type == rtd::LT_MOVING) ? sc.moving_meta[idx]
-                        : ((FEAT & F_TRI) && type == rtd::LT_TRI) ? sc.tri_meta[idx] : 0u;
-    const uint32_t hittable = type == rtd::LT_SPHERE ? src.sphere[idx]
-                            : ((FEAT & F_RECT) && type == rtd::LT_RECT) ? src.rect[idx]
-                            : ((FEAT & F_MOVING) && type == rtd::LT_MOVING) ? src.moving[idx]
-                            : ((FEAT & F_TRI) && type == rtd::LT_TRI) ? src.tri[idx] : 0xFFFFFFFFu;
-    const uint32_t wrap = (FEAT & F_XFORM) ? (meta >> 22) : 0u;
-    rtd::Wrap W{};
-    if ((FEAT & F_XFORM) && wrap) W = sc.wraps[wrap];
-    const uint32_t xf = W.xform;
-    V3 ol = o, dl = d;
-    if ((FEAT & F_XFORM) && xf) xform_ray(sc.xforms[xf], o, d, ol, dl);
-    V3 p, n, outward; float hu = 0.f, hv = 0.f; bool ff;
-    if (type == rtd::LT_SPHERE) {
-        const Float4 sp = sc.spheres[idx];
-        p = ol + dl * t;                                            // sphere.rs:59
-        outward = (p - v3(sp.x, sp.y, sp.z)) / sp.w;                // :60
-        sphere_uv(outward, hu, hv);                                 // :62
-    } else if ((FEAT & F_RECT) && type == rtd::LT_RECT) {
-        const Float4 r0 = sc.rects[2 * idx], r1 = sc.rects[2 * idx + 1];
-        const int kaxis = (int)r1.y & 3; const int ia = kaxis == 0 ? 1 : 0, ib = kaxis == 2 ? 1 : 2;
-        p = ol + dl * t;                                            // aarect.rs:46
-        const float a = comp(p, ia), b = comp(p, ib);
-        hu = fdiv(a - r0.x, r0.y - r0.x); hv = fdiv(b - r0.z, r0.w - r0.z);   // :41-42
-        if (kaxis == 0) p.x = r1.x; else if (kaxis == 1) p.y = r1.x; else p.z = r1.x;   // on the plane exactly
-        outward = v3(kaxis == 0 ? 1.f : 0.f, kaxis == 1 ? 1.f : 0.f, kaxis == 2 ? 1.f : 0.f);
-    } else if ((FEAT & F_MOVING) && type == rtd::LT_MOVING) {
-        const Float4 m0 = sc.moving[3 * idx], m1 = sc.moving[3 * idx + 1], m2 = sc.moving[3 * idx + 2];
-        p = ol + dl * t;
-        outward = (p - moving_center(m0, m1, m2, tm)) / m0.w;       // moving_sphere.rs:58 (u,v not set: 0)
-    } else if ((FEAT & F_TRI) && type == rtd::LT_TRI) {
-        const V3 v0 = f4xyz(sc.tris[3 * idx]), v1 = f4xyz(sc.tris[3 * idx + 1]), v2 = f4xyz(sc.tris[3 * idx + 2]);
-        TriAttr ta{};
-        if (FEAT & F_TRI_ATTR) ta = tri_attr_load(sc.tris, idx);
-        float tt, bu = 0.f, bv = 0.f;
-        tri_hit(ol, dl, v0, v1, v2, -kInf, kInf, tt, bu, bv);
-        hu = bu; hv = bv;
-        p = ol + dl * t;
-        outward = unit(cross(v1 - v0, v2 - v0));
-        if (FEAT & F_TRI_ATTR) tri_attr_apply(ta, bu, bv, outward, hu, hv);
-    } else { store_ray_miss(hits, ray, 0u); return; }               // a primitive kind this instance was not compiled for: cannot occur (pick_variant)
-    ff = dot(dl, outward) < 0.f;                                    // set_face_normal, hittable.rs:41-48
-    n = ff ? outward : -outward;
-    if ((FEAT & F_XFORM) && wrap) {
-        if (xf) p = xform_point_back(sc.xforms[xf], p);
-        // the wrappers from the innermost out; dk: the ray direction each wrapper hands to its child (hittable.rs:154-155)
-        V3 dk[rtd::MAX_WRAP_OPS + 1];
-        dk[0] = d;
-#pragma unroll
-        for (uint32_t k = 0; k < rtd::MAX_WRAP_OPS; ++k) {
-            const float sn = W.op[k].sin_t, cs = W.op[k].cos_t;
-            const V3 qv = dk[k];
-            dk[k + 1] = (k < W.n_ops && W.op[k].kind == rtd::WO_ROTATE_Y) ? v3(cs * qv.x - sn * qv.z, qv.y, sn * qv.x + cs * qv.z) : qv;
-        }
-#pragma unroll
-        for (int k = (int)rtd::MAX_WRAP_OPS - 1; k >= 0; --k) {
-            if ((uint32_t)k < W.n_ops) {
-                const uint32_t kind = W.op[k].kind;
-                if (kind == rtd::WO_FLIP_FACE) ff = !ff;                                   // hittable.rs:199
-                else {
-                    if (kind == rtd::WO_ROTATE_Y) {                                        // hittable.rs:169-170
-                        const float sn = W.op[k].sin_t, cs = W.op[k].cos_t;
-                        n = v3(cs * n.x + sn * n.z, n.y, -sn * n.x + cs * n.z);
-                    }
-                    ff = dot(dk[k + 1], n) < 0.f;                                          // hittable.rs:82-83 / 173
-                    n = ff ? n : -n;
-                }
-            }
-        }
-    }
-    // 48 bytes, three 16-byte stores
-    hits += 3ull * ray;
-    hits[0] = Float4{t, __uint_as_float(hittable), __uint_as_float(meta & rtd::META_MAT_MASK), __uint_as_float(kRayHitHit | (ff ? kRayHitFrontFace : 0u))};
-    hits[1] = Float4{p.x, p.y, p.z, hu};
-    hits[2] = Float4{n.x, n.y, n.z, hv};
-}
-
-// ---- occlusion queries (rt_hip.h rt_occluded_rays): the same rays -> pool records -> the any-hit k_extend -> one byte per ray ----
-// k_occluded_import: k_rays_import's twin (same validity rule, same slots, same counter) with two differences: a dropped ray gets its BYTE,
-// RT_RAYHIT_INVALID_RAY, and with limit_in_d the record's ray_d.w — "the primitive this ray starts on", 0 for every query ray — carries
-// the ray's limit as the any-hit walk wants it (+inf for t_max <= 0, +inf or NaN), so that the walk's refill finds it in the words it
-// prefetches anyway. Without limit_in_d (scenes walked by k_extend_wide, closest hit) the slot stays 0. s0.x keeps the caller's t_max.
-__global__ void __launch_bounds__(kRaysImportThreads) k_occluded_import(const Float4* __restrict__ rays, uint32_t first, uint32_t n, PoolDev pool, uint32_t queue_cap,
-                                                                         uint32_t* __restrict__ counts, uint8_t* __restrict__ occluded,
-                                                                         unsigned long long* __restrict__ counters, uint32_t limit_in_d) {
-    __shared__ uint32_t s_scan[kRaysImportThreads / 64 + 1];
-    const uint32_t i = blockIdx.x * kRaysImportThreads + threadIdx.x, q = blockIdx.x & (kQueues - 1u);
-    Float4 ro = Float4{0.f, 0.f, 0.f, 0.f}, rdv = Float4{0.f, 0.f, 0.f, 0.f};
-    const bool mine = i < n;
-    if (mine) { const Float4* r = rays + 2ull * (first + i); ro = r[0]; rdv = r[1]; }
-    const bool valid = mine && query_ray_valid(ro, rdv);
-    const uint32_t slot = block_alloc(valid, counts + q * kQStride, s_scan);      // every thread of the workgroup calls it
-    const bool stored = valid && slot < queue_cap;
-    if (stored) {
-        const uint32_t at = q * queue_cap + slot;
         const float limit = (rdv.w > 0.f && rdv.w < kInf) ? rdv.w : kInf;         // (NaN fails both comparisons: no limit)
         pool.ray_o[at] = ro;
-        pool.ray_d[at] = Float4{rdv.x, rdv.y, rdv.z, limit_in_d != 0u ? limit : __uint_as_float(0u)};
+        pool.ray_d[at] = Float4{rdv.x, rdv.y, rdv.z, OCCLUSION && limit_in_d != 0u ? limit : __uint_as_float(0u)};
         pool.s0[at] = Float4{rdv.w, 0.f, 0.f, __uint_as_float(first + i)};
         pool.sd[at] = 0u;
     }
-    if (mine && !stored) occluded[(uint64_t)first + i] = (uint8_t)kRayHitInvalid;
+    if (mine && !stored) {
+        if constexpr (OCCLUSION) ((uint8_t*)answers)[(uint64_t)first + i] = (uint8_t)kRayHitInvalid;
+        else store_ray_miss((Float4*)answers, first + i, kRayHitInvalid);
+    }
     const uint64_t m = __ballot(stored);
     if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(&counters[CTR_SEGMENTS], (unsigned long long)__popcll(m));
 }
 
-// k_occluded_export: pool.hit of every slot -> the byte at its ray's index, by k_rays_export's own rule for "a hit": a primitive, and a t
-// not beyond the ray's limit. After the any-hit walk the second half always holds (the walk accepted nothing beyond the limit); after
-// k_extend_wide it is the comparison k_rays_export makes. No FEAT variants: nothing of the HitRecord is rebuilt.
-__global__ void __launch_bounds__(256) k_occluded_export(PoolDev pool, uint32_t queue_cap, const uint32_t* __restrict__ counts, uint8_t* __restrict__ occluded) {
-    const uint32_t q = blockIdx.x & (kQueues - 1u), i = (blockIdx.x >> kQShift) * blockDim.x + threadIdx.x;
-    if (i >= min(counts[q * kQStride], queue_cap)) return;
-    const uint32_t at = q * queue_cap + i;
-    const Float4 s0 = pool.s0[at];
-    const uint2 hit = pool.hit[at];
-    const float t = __uint_as_float(hit.x), t_max = s0.x;
-    const bool limited = t_max > 0.f && t_max < kInf;                             // (t_max <= 0, +inf or NaN: no limit)
-    const bool miss = hit.y == rtd::HIT_NONE || (limited && t > t_max);
-    occluded[__float_as_uint(s0.w)] = miss ? (uint8_t)0u : (uint8_t)kRayHitHit;
-}
-
-// ---- light-sample queries (rt_hip.h rt_sample_lights): the light half of shade_segment's Lambertian branch, one lane per query ----
-// Records as rt_hip.h declares them (RtLightQuery 40 B, RtLightSample 24 B). The generator is seeded (rng_state, 0 draws); the pick, the draw
-// and the list's pdf are lights_random / lights_pdf_value, the functions shade_segment calls. The tables are read where the upload put
-// them (no LDS staging: a query kernel is a few loads per lane). EXT: the scene's lights table holds rtd::LightX records (F_LIGHTS_EXT).
-// k_sample_lights_tree: the same for a table with the light tree (F_LIGHTS_TREE); RT_LIGHTQ_LINEAR in a query's flags asks for the plain loop.
-struct LightQueryDev { float p[3]; uint32_t flags; uint64_t rng_state; float d[3]; float _pad; };
-struct LightSampleDev { float d[3]; float pdf; int32_t light; uint32_t n_draws; };
-static_assert(sizeof(LightQueryDev) == 40 && sizeof(LightSampleDev) == 24, "light query records: 40 and 24 bytes");
-constexpr uint32_t kLightQDirectionGiven = 1u, kLightQLinear = 2u;
-template <bool EXT>
-__global__ void __launch_bounds__(256) k_sample_lights(SceneDev sc, const LightQueryDev* __restrict__ queries, LightSampleDev* __restrict__ results, uint32_t n) {
-    constexpr uint32_t FEAT = F_LIGHTS | (EXT ? F_LIGHTS_EXT : 0u);
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const LightQueryDev q = queries[i];
-    const V3 p = v3(q.p[0], q.p[1], q.p[2]);
-    V3 dir = v3(q.d[0], q.d[1], q.d[2]);
-    LightSampleDev r; r.light = -1; r.n_draws = 0u;
-    if ((q.flags & kLightQDirectionGiven) == 0u) {
-        Rng g; g.s = q.rng_state; g.n = 0u;
-        uint32_t k;
-        dir = lights_random<FEAT>(sc, p, g, k);
-        r.light = (int32_t)k; r.n_draws = g.n;
-    }
-    unsigned long long c0 = 0, c1 = 0, c2 = 0;
-    r.pdf = lights_pdf_value<FEAT>(sc, p, dir, c0, c1, c2);
-    r.d[0] = dir.x; r.d[1] = dir.y; r.d[2] = dir.z;
-    results[i] = r;
-}
-__global__ void __launch_bounds__(256) k_sample_lights_tree(SceneDev sc, const LightQueryDev* __restrict__ queries, LightSampleDev* __restrict__ results, uint32_t n) {
-    constexpr uint32_t FEAT = F_LIGHTS | F_LIGHTS_EXT | F_LIGHTS_TREE;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const LightQueryDev q = queries[i];
-    const V3 p = v3(q.p[0], q.p[1], q.p[2]);
-    V3 dir = v3(q.d[0], q.d[1], q.d[2]);
-    LightSampleDev r; r.light = -1; r.n_draws = 0u;
-    if ((q.flags & kLightQDirectionGiven) == 0u) {
-        Rng g; g.s = q.rng_state; g.n = 0u;
-        uint32_t k;
-        dir = lights_random<FEAT>(sc, p, g, k);
-        r.light = (int32_t)k; r.n_draws = g.n;
-    }
-    unsigned long long c0 = 0, c1 = 0, c2 = 0;
-    r.pdf = lights_pdf_value<FEAT>(sc, p, dir, c0, c1, c2, (q.flags & kLightQLinear) != 0u);
-    r.d[0] = dir.x; r.d[1] = dir.y; r.d[2] = dir.z;
-    results[i] = r;
-}
-
-// ------------------------------------------------------------------------------------------------
-// first-hit features (rt_hip.h "first-hit features"): the render's own camera rays -> pool records -> k_extend -> per-ray feature
-// records -> per-pixel sums
-// ------------------------------------------------------------------------------------------------
-// The HitRecord of (ray, t, primitive) as a function: k_rays_export's block "rebuild the HitRecord" above, statement for statement (u, v always
-// computed, no medium). k_rays_export keeps its own copy: calling this function from it moved its register figures in all four instances
-// (23/36/62/72 VGPRs -> 19/37/58/64), and the figures of the existing kernels are pinned. The identity test of
-// tests/test_gpu_features.py and the yardstick tests, whose expected values come from k_rays_export, keep the two in step. false: a primitive
-// kind this instance was not compiled for — cannot occur (pick_variant).
+// The HitRecord of (ray, t, primitive), with the arithmetic of shade_segment's block "rebuild the HitRecord" — restated here, not shared,
+// because that function's code must not move (DESIGN.md section 2 has its miscompile) — with two differences: u, v of a sphere are always
+// computed, and a medium cannot occur (the host refuses such scenes). tests/test_gpu_rays.py::test_export_agrees_with_shade and the identity
+// test of tests/test_gpu_features.py keep the two in step. false: a primitive kind this instance was not compiled for — cannot occur
+// (pick_variant).
 struct HitRec { V3 p, n; float u, v; bool ff; uint32_t meta; };
 template <uint32_t FEAT>
 DEVI bool rebuild_hit(const SceneDev& sc, V3 o, V3 d, float tm, float t, uint32_t prim, HitRec& h) {
@@ -2780,6 +2583,83 @@ DEVI bool rebuild_hit(const SceneDev& sc, V3 o, V3 d, float tm, float t, uint32_
     return true;
 }
 
+// k_rays_export: (ray, hit = (t, primitive)) of every pool slot -> one RtRayHit at the ray's index. The tables are read where the upload put
+// them (HBM / L2): one pass over the pool, nothing staged.
+template <uint32_t FEAT>
+__global__ void __launch_bounds__(256) k_rays_export(SceneDev sc, RaySrcDev src, PoolDev pool, uint32_t queue_cap, const uint32_t* __restrict__ counts,
+                                                      Float4* __restrict__ hits) {
+    const uint32_t q = blockIdx.x & (kQueues - 1u), i = (blockIdx.x >> kQShift) * blockDim.x + threadIdx.x;
+    if (i >= min(counts[q * kQStride], queue_cap)) return;
+    const uint32_t at = q * queue_cap + i;
+    const Float4 ro = pool.ray_o[at], rdv = pool.ray_d[at], s0 = pool.s0[at];
+    const uint2 hit = pool.hit[at];
+    const uint32_t ray = __float_as_uint(s0.w);
+    const float t = __uint_as_float(hit.x), t_max = s0.x;
+    const bool limited = t_max > 0.f && t_max < kInf;                             // (t_max <= 0, +inf or NaN: no limit)
+    if (hit.y == rtd::HIT_NONE || (limited && t > t_max)) { store_ray_miss(hits, ray, 0u); return; }
+    const uint32_t type = hit.y >> 28, idx = hit.y & rtd::LEAF_MAX_FIRST;
+    const uint32_t hittable = type == rtd::LT_SPHERE ? src.sphere[idx]
+                            : ((FEAT & F_RECT) && type == rtd::LT_RECT) ? src.rect[idx]
+                            : ((FEAT & F_MOVING) && type == rtd::LT_MOVING) ? src.moving[idx]
+                            : ((FEAT & F_TRI) && type == rtd::LT_TRI) ? src.tri[idx] : 0xFFFFFFFFu;
+    HitRec h;
+    if (!rebuild_hit<FEAT>(sc, v3(ro.x, ro.y, ro.z), v3(rdv.x, rdv.y, rdv.z), ro.w, t, hit.y, h)) { store_ray_miss(hits, ray, 0u); return; }   // (cannot occur)
+    // 48 bytes, three 16-byte stores
+    hits += 3ull * ray;
+    hits[0] = Float4{t, __uint_as_float(hittable), __uint_as_float(h.meta & rtd::META_MAT_MASK), __uint_as_float(kRayHitHit | (h.ff ? kRayHitFrontFace : 0u))};
+    hits[1] = Float4{h.p.x, h.p.y, h.p.z, h.u};
+    hits[2] = Float4{h.n.x, h.n.y, h.n.z, h.v};
+}
+
+// k_occluded_export: pool.hit of every slot -> the byte at its ray's index, by k_rays_export's own rule for "a hit": a primitive, and a t
+// not beyond the ray's limit. After the any-hit walk the second half always holds (the walk accepted nothing beyond the limit); after
+// k_extend_wide it is the comparison k_rays_export makes. No FEAT variants: nothing of the HitRecord is rebuilt.
+__global__ void __launch_bounds__(256) k_occluded_export(PoolDev pool, uint32_t queue_cap, const uint32_t* __restrict__ counts, uint8_t* __restrict__ occluded) {
+    const uint32_t q = blockIdx.x & (kQueues - 1u), i = (blockIdx.x >> kQShift) * blockDim.x + threadIdx.x;
+    if (i >= min(counts[q * kQStride], queue_cap)) return;
+    const uint32_t at = q * queue_cap + i;
+    const Float4 s0 = pool.s0[at];
+    const uint2 hit = pool.hit[at];
+    const float t = __uint_as_float(hit.x), t_max = s0.x;
+    const bool limited = t_max > 0.f && t_max < kInf;                             // (t_max <= 0, +inf or NaN: no limit)
+    const bool miss = hit.y == rtd::HIT_NONE || (limited && t > t_max);
+    occluded[__float_as_uint(s0.w)] = miss ? (uint8_t)0u : (uint8_t)kRayHitHit;
+}
+
+// ---- light-sample queries (rt_hip.h rt_sample_lights): the light half of shade_segment's Lambertian branch, one lane per query ----
+// Records as rt_hip.h declares them (RtLightQuery 40 B, RtLightSample 24 B). The generator is seeded (rng_state, 0 draws); the pick, the draw
+// and the list's pdf are lights_random / lights_pdf_value, the functions shade_segment calls. The tables are read where the upload put
+// them (no LDS staging: a query kernel is a few loads per lane). LF: 0, F_LIGHTS_EXT (the scene's lights table holds rtd::LightX records), or
+// F_LIGHTS_EXT | F_LIGHTS_TREE (it carries the light tree; RT_LIGHTQ_LINEAR in a query's flags then asks for the plain loop, and means nothing without a tree).
+struct LightQueryDev { float p[3]; uint32_t flags; uint64_t rng_state; float d[3]; float _pad; };
+struct LightSampleDev { float d[3]; float pdf; int32_t light; uint32_t n_draws; };
+static_assert(sizeof(LightQueryDev) == 40 && sizeof(LightSampleDev) == 24, "light query records: 40 and 24 bytes");
+constexpr uint32_t kLightQDirectionGiven = 1u, kLightQLinear = 2u;
+template <uint32_t LF>
+__global__ void __launch_bounds__(256) k_sample_lights(SceneDev sc, const LightQueryDev* __restrict__ queries, LightSampleDev* __restrict__ results, uint32_t n) {
+    constexpr uint32_t FEAT = F_LIGHTS | LF;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const LightQueryDev q = queries[i];
+    const V3 p = v3(q.p[0], q.p[1], q.p[2]);
+    V3 dir = v3(q.d[0], q.d[1], q.d[2]);
+    LightSampleDev r; r.light = -1; r.n_draws = 0u;
+    if ((q.flags & kLightQDirectionGiven) == 0u) {
+        Rng g; g.s = q.rng_state; g.n = 0u;
+        uint32_t k;
+        dir = lights_random<FEAT>(sc, p, g, k);
+        r.light = (int32_t)k; r.n_draws = g.n;
+    }
+    unsigned long long c0 = 0, c1 = 0, c2 = 0;
+    r.pdf = lights_pdf_value<FEAT>(sc, p, dir, c0, c1, c2, (q.flags & kLightQLinear) != 0u);
+    r.d[0] = dir.x; r.d[1] = dir.y; r.d[2] = dir.z;
+    results[i] = r;
+}
+
+// ------------------------------------------------------------------------------------------------
+// first-hit features (rt_hip.h "first-hit features"): the render's own camera rays -> pool records -> k_extend -> per-ray feature
+// records -> per-pixel sums
+// ------------------------------------------------------------------------------------------------
 // A chunk = samples [k0, k0 + nk) of output slots [slot0, slot0 + ns): ray r = k * ns + s of the chunk is sample k0 + k of slot slot0 + s, so
 // that a wave of the import makes the rays of 64 neighbouring pixels and the fold reads its records coalesced.
 // k_features_import: lane r makes that ray with new_camera_ray — the function k_generate and k_shade call, so the ray is the render's, bit for
@@ -2788,17 +2668,16 @@ DEVI bool rebuild_hit(const SceneDev& sc, V3 o, V3 d, float tm, float t, uint32_
 __global__ void __launch_bounds__(kRaysImportThreads) k_features_import(RenderDev rd, FeatDev fd, PoolDev pool, uint32_t* __restrict__ counts,
                                                                          unsigned long long* __restrict__ counters) {
     __shared__ uint32_t s_scan[kRaysImportThreads / 64 + 1];
-    const uint32_t r = blockIdx.x * kRaysImportThreads + threadIdx.x, q = blockIdx.x & (kQueues - 1u);
+    const uint32_t r = blockIdx.x * kRaysImportThreads + threadIdx.x;
     const uint32_t k = fdivu(r, fd.div_ns), s = r - k * fd.ns;
     uint32_t x = 0u, y = 0u;
     if (k < fd.nk) slot_pixel(rd, fd.slot0 + s, x, y);
     const bool valid = k < fd.nk && x < rd.width && y < rd.height;
     V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f); float tm = 0.f;
     if (valid) { Rng g; new_camera_ray(rd, x, y, fd.first_sample + fd.k0 + k, g, o, d, tm); }
-    const uint32_t slot = block_alloc(valid, counts + q * kQStride, s_scan);      // every thread of the workgroup calls it
-    const bool stored = valid && slot < rd.queue_cap;
+    uint32_t at;
+    const bool stored = import_slot(valid, counts, rd.queue_cap, s_scan, at);
     if (stored) {
-        const uint32_t at = q * rd.queue_cap + slot;
         pool.ray_o[at] = Float4{o.x, o.y, o.z, tm};
         pool.ray_d[at] = Float4{d.x, d.y, d.z, __uint_as_float(0u)};
         pool.s0[at] = Float4{0.f, 0.f, 0.f, __uint_as_float(r)};
@@ -2850,7 +2729,11 @@ __global__ void __launch_bounds__(256) k_features_export(SceneDev sc, RenderDev 
 // k_features_fold: one thread per slot of the chunk adds the slot's nk records, in sample order, in f32, into the wanted planes — from the
 // value already there when fd.accumulate is set (RT_FEATURES_ACCUMULATE, or a later sample range of the same call), else from 0. No atomics:
 // passes over [0, a) and [a, N) leave the bits of one pass over [0, N). Clipped slots are never written.
-__global__ void __launch_bounds__(256) k_features_fold(RenderDev rd, FeatDev fd) {
+// MOMENTS: the second moments beside the sums (rt_hip.h, "first-hit features, second moments"): per record the square of each value is formed
+// in f32 (x * x: the build contracts nothing) and added, after the record's sums, into the wanted squared planes. The sums take the same
+// additions in the same order either way, so the four sum planes have the same bits. Same records; nothing new per ray.
+template <bool MOMENTS>
+__global__ void __launch_bounds__(256) k_features_fold(RenderDev rd, FeatDev fd, FeatMomDev fm) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= fd.ns) return;
     const uint32_t slot = fd.slot0 + s;
@@ -2860,40 +2743,9 @@ __global__ void __launch_bounds__(256) k_features_fold(RenderDev rd, FeatDev fd)
     float* pn = fd.normal ? fd.normal + 3ull * slot : nullptr;
     float* pd = fd.depth ? fd.depth + slot : nullptr;
     uint32_t* ph = fd.hits ? fd.hits + slot : nullptr;
-    V3 a = v3(0.f, 0.f, 0.f), n = v3(0.f, 0.f, 0.f); float dep = 0.f; uint32_t nh = 0u;
-    if (fd.accumulate != 0u) {
-        if (pa) a = v3(pa[0], pa[1], pa[2]);
-        if (pn) n = v3(pn[0], pn[1], pn[2]);
-        if (pd) dep = *pd;
-        if (ph) nh = *ph;
-    }
-    for (uint32_t k = 0; k < fd.nk; ++k) {
-        const Float4* rec = fd.rec + 2ull * ((uint64_t)k * fd.ns + s);
-        const Float4 r0 = rec[0], r1 = rec[1];
-        a = a + v3(r0.x, r0.y, r0.z); n = n + v3(r1.x, r1.y, r1.z); dep += r0.w; nh += __float_as_uint(r1.w);
-    }
-    if (pa) { pa[0] = a.x; pa[1] = a.y; pa[2] = a.z; }
-    if (pn) { pn[0] = n.x; pn[1] = n.y; pn[2] = n.z; }
-    if (pd) *pd = dep;
-    if (ph) *ph = nh;
-}
-
-// k_features_fold_moments: k_features_fold with the second moments beside the sums (rt_hip.h, "first-hit features, second moments"): per
-// record the square of each value is formed in f32 (x * x: the build contracts nothing) and added, in sample order, into the wanted squared
-// planes. The sums take k_features_fold's additions in its order, so the four sum planes are its bits. Same records; nothing new per ray.
-__global__ void __launch_bounds__(256) k_features_fold_moments(RenderDev rd, FeatDev fd, FeatMomDev fm) {
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= fd.ns) return;
-    const uint32_t slot = fd.slot0 + s;
-    uint32_t x, y; slot_pixel(rd, slot, x, y);
-    if (x >= rd.width || y >= rd.height) return;
-    float* pa = fd.albedo ? fd.albedo + 3ull * slot : nullptr;
-    float* pn = fd.normal ? fd.normal + 3ull * slot : nullptr;
-    float* pd = fd.depth ? fd.depth + slot : nullptr;
-    uint32_t* ph = fd.hits ? fd.hits + slot : nullptr;
-    float* qa = fm.albedo_sq ? fm.albedo_sq + 3ull * slot : nullptr;
-    float* qn = fm.normal_sq ? fm.normal_sq + 3ull * slot : nullptr;
-    float* qd = fm.depth_sq ? fm.depth_sq + slot : nullptr;
+    float* qa = MOMENTS && fm.albedo_sq ? fm.albedo_sq + 3ull * slot : nullptr;
+    float* qn = MOMENTS && fm.normal_sq ? fm.normal_sq + 3ull * slot : nullptr;
+    float* qd = MOMENTS && fm.depth_sq ? fm.depth_sq + slot : nullptr;
     V3 a = v3(0.f, 0.f, 0.f), n = v3(0.f, 0.f, 0.f), a2 = v3(0.f, 0.f, 0.f), n2 = v3(0.f, 0.f, 0.f); float dep = 0.f, dep2 = 0.f; uint32_t nh = 0u;
     if (fd.accumulate != 0u) {
         if (pa) a = v3(pa[0], pa[1], pa[2]);
@@ -2908,7 +2760,7 @@ __global__ void __launch_bounds__(256) k_features_fold_moments(RenderDev rd, Fea
         const Float4* rec = fd.rec + 2ull * ((uint64_t)k * fd.ns + s);
         const Float4 r0 = rec[0], r1 = rec[1];
         a = a + v3(r0.x, r0.y, r0.z); n = n + v3(r1.x, r1.y, r1.z); dep += r0.w; nh += __float_as_uint(r1.w);
-        a2 = a2 + v3(r0.x * r0.x, r0.y * r0.y, r0.z * r0.z); n2 = n2 + v3(r1.x * r1.x, r1.y * r1.y, r1.z * r1.z); dep2 += r0.w * r0.w;
+        if constexpr (MOMENTS) { a2 = a2 + v3(r0.x * r0.x, r0.y * r0.y, r0.z * r0.z); n2 = n2 + v3(r1.x * r1.x, r1.y * r1.y, r1.z * r1.z); dep2 += r0.w * r0.w; }
     }
     if (pa) { pa[0] = a.x; pa[1] = a.y; pa[2] = a.z; }
     if (pn) { pn[0] = n.x; pn[1] = n.y; pn[2] = n.z; }
@@ -2943,7 +2795,7 @@ __global__ void __launch_bounds__(kRaysImportThreads) k_radiance_import(RenderDe
     if (mine) { const Float4* r = (const Float4*)qd.rays + 2ull * (qd.ray0 + i); ro = r[0]; rdv = r[1]; }
     const uint32_t first_draw = __float_as_uint(rdv.w);
     const bool valid = mine && query_ray_valid(ro, rdv) && first_draw < 65536u;
-    const uint32_t slot = block_alloc(valid, counts + q * kQStride, s_scan);      // every thread of the workgroup calls it
+    const uint32_t slot = block_alloc(valid, counts + q * kQStride, s_scan);      // (import_slot, spelled out: through it the stores below came out in another order)
     const bool stored = valid && slot < rd.queue_cap;
     if (stored) {
         const V3 o = v3(ro.x, ro.y, ro.z), d = v3(rdv.x, rdv.y, rdv.z);
@@ -3194,18 +3046,25 @@ hipError_t launch_resolve_list(const RenderDev& rd, float* out, hipStream_t stre
     return hipGetLastError();
 }
 
-hipError_t launch_rays_import(const void* rays, uint32_t first, uint32_t n, const PoolDev& pool, uint32_t queue_cap, uint32_t* counts, void* hits,
-                              unsigned long long* counters, hipStream_t stream) {
+// what every import launcher checks of its n records: a queue gets at most ceil(n / 512) / kQueues workgroups of 512, so a slot is < queue_cap
+static bool import_fits(uint64_t n, uint32_t queue_cap) { return n <= (uint64_t)kQueues * queue_cap && (queue_cap & 511u) == 0u; }
+// the grid of every export kernel: 256-thread groups over max_count, the upper bound of the rays in ONE queue, for each of the queues
+static uint32_t export_blocks(uint32_t max_count, uint32_t queue_cap) { return kQueues * ((std::min(max_count, queue_cap) + 255u) / 256u); }
+
+hipError_t launch_rays_import(const void* rays, uint32_t first, uint32_t n, const PoolDev& pool, uint32_t queue_cap, uint32_t* counts, void* answers,
+                              unsigned long long* counters, bool occlusion, bool limit_in_d, hipStream_t stream) {
     const uint32_t blocks = (n + kRaysImportThreads - 1u) / kRaysImportThreads;
     if (blocks == 0u) return hipSuccess;
-    if ((uint64_t)n > (uint64_t)kQueues * queue_cap || (queue_cap & 511u) != 0u) return hipErrorInvalidValue;   // (k_rays_import: a slot is < queue_cap)
-    hipLaunchKernelGGL(k_rays_import, dim3(blocks), dim3(kRaysImportThreads), 0, stream, (const Float4*)rays, first, n, pool, queue_cap, counts, (Float4*)hits, counters);
+    if (!import_fits(n, queue_cap)) return hipErrorInvalidValue;
+    with_flag(occlusion, [&](auto occ) {
+        hipLaunchKernelGGL(k_rays_import<decltype(occ)::value>, dim3(blocks), dim3(kRaysImportThreads), 0, stream, (const Float4*)rays, first, n, pool, queue_cap, counts,
+                           answers, counters, limit_in_d ? 1u : 0u); });
     return hipGetLastError();
 }
 
 hipError_t launch_rays_export(const LaunchCfg& cfg, const SceneDev& sc, const RaySrcDev& src, const PoolDev& pool, uint32_t queue_cap, uint32_t max_count,
                               const uint32_t* counts, void* hits, hipStream_t stream) {
-    const uint32_t blocks = kQueues * ((std::min(max_count, queue_cap) + 255u) / 256u);   // max_count = upper bound of the rays in ONE queue
+    const uint32_t blocks = export_blocks(max_count, queue_cap);
     if (blocks == 0u) return hipSuccess;
     with_record_variant(cfg.features, [&](auto feat) {
         hipLaunchKernelGGL((k_rays_export<decltype(feat)::value>), dim3(blocks), dim3(256), 0, stream, sc, src, pool, queue_cap, counts, (Float4*)hits); });
@@ -3239,18 +3098,8 @@ hipError_t launch_extend_any(const LaunchCfg& cfg, const SceneDev& sc, const Poo
         return launch_extend_any_c<decltype(mode)::value, F>(cfg, sc, pool, rd, count_ptr, head, cz, counters, stream); }); });
 }
 
-hipError_t launch_occluded_import(const void* rays, uint32_t first, uint32_t n, const PoolDev& pool, uint32_t queue_cap, uint32_t* counts, void* occluded,
-                                  unsigned long long* counters, bool limit_in_d, hipStream_t stream) {
-    const uint32_t blocks = (n + kRaysImportThreads - 1u) / kRaysImportThreads;
-    if (blocks == 0u) return hipSuccess;
-    if ((uint64_t)n > (uint64_t)kQueues * queue_cap || (queue_cap & 511u) != 0u) return hipErrorInvalidValue;   // (k_occluded_import: a slot is < queue_cap)
-    hipLaunchKernelGGL(k_occluded_import, dim3(blocks), dim3(kRaysImportThreads), 0, stream, (const Float4*)rays, first, n, pool, queue_cap, counts, (uint8_t*)occluded,
-                       counters, limit_in_d ? 1u : 0u);
-    return hipGetLastError();
-}
-
 hipError_t launch_occluded_export(const PoolDev& pool, uint32_t queue_cap, uint32_t max_count, const uint32_t* counts, void* occluded, hipStream_t stream) {
-    const uint32_t blocks = kQueues * ((std::min(max_count, queue_cap) + 255u) / 256u);   // max_count = upper bound of the rays in ONE queue
+    const uint32_t blocks = export_blocks(max_count, queue_cap);
     if (blocks == 0u) return hipSuccess;
     hipLaunchKernelGGL(k_occluded_export, dim3(blocks), dim3(256), 0, stream, pool, queue_cap, counts, (uint8_t*)occluded);
     return hipGetLastError();
@@ -3260,17 +3109,19 @@ hipError_t launch_sample_lights(const SceneDev& sc, uint32_t features, const voi
     const uint32_t blocks = (n + 255u) / 256u;
     if (blocks == 0u) return hipSuccess;
     if (sc.n_lights == 0u) return hipErrorInvalidValue;                  // (the host refuses a scene without lights before anything is launched)
-    if ((features & F_LIGHTS_TREE) != 0u)
-        hipLaunchKernelGGL(k_sample_lights_tree, dim3(blocks), dim3(256), 0, stream, sc, (const LightQueryDev*)queries, (LightSampleDev*)results, n);
-    else with_flag((features & F_LIGHTS_EXT) != 0u, [&](auto e) {
-        hipLaunchKernelGGL(k_sample_lights<decltype(e)::value>, dim3(blocks), dim3(256), 0, stream, sc, (const LightQueryDev*)queries, (LightSampleDev*)results, n); });
+    const uint32_t lf = features & (F_LIGHTS_EXT | F_LIGHTS_TREE);       // (a tree comes with extended records only)
+    const auto go = [&](auto f) {
+        hipLaunchKernelGGL(k_sample_lights<decltype(f)::value>, dim3(blocks), dim3(256), 0, stream, sc, (const LightQueryDev*)queries, (LightSampleDev*)results, n); };
+    if (lf == 0u) go(std::integral_constant<uint32_t, 0u>{});
+    else if (lf == F_LIGHTS_EXT) go(std::integral_constant<uint32_t, F_LIGHTS_EXT>{});
+    else go(std::integral_constant<uint32_t, F_LIGHTS_EXT | F_LIGHTS_TREE>{});
     return hipGetLastError();
 }
 
 hipError_t launch_features_import(const RenderDev& rd, const FeatDev& fd, const PoolDev& pool, uint32_t* counts, unsigned long long* counters, hipStream_t stream) {
     const uint64_t n = (uint64_t)fd.ns * fd.nk;
     if (n == 0u) return hipSuccess;
-    if (n > (uint64_t)kQueues * rd.queue_cap || (rd.queue_cap & 511u) != 0u) return hipErrorInvalidValue;   // (k_features_import: a slot is < queue_cap)
+    if (!import_fits(n, rd.queue_cap)) return hipErrorInvalidValue;
     const uint32_t blocks = (uint32_t)((n + kRaysImportThreads - 1u) / kRaysImportThreads);
     hipLaunchKernelGGL(k_features_import, dim3(blocks), dim3(kRaysImportThreads), 0, stream, rd, fd, pool, counts, counters);
     return hipGetLastError();
@@ -3278,24 +3129,18 @@ hipError_t launch_features_import(const RenderDev& rd, const FeatDev& fd, const 
 
 hipError_t launch_features_export(const LaunchCfg& cfg, const SceneDev& sc, const RenderDev& rd, const FeatDev& fd, const PoolDev& pool, uint32_t max_count,
                                   const uint32_t* counts, hipStream_t stream) {
-    const uint32_t blocks = kQueues * ((std::min(max_count, rd.queue_cap) + 255u) / 256u);   // max_count = upper bound of the rays in ONE queue
+    const uint32_t blocks = export_blocks(max_count, rd.queue_cap);
     if (blocks == 0u) return hipSuccess;
     with_record_variant(cfg.features, [&](auto feat) {
         hipLaunchKernelGGL((k_features_export<decltype(feat)::value>), dim3(blocks), dim3(256), 0, stream, sc, rd, fd, pool, counts); });
     return hipGetLastError();
 }
 
-hipError_t launch_features_fold(const RenderDev& rd, const FeatDev& fd, hipStream_t stream) {
+hipError_t launch_features_fold(const RenderDev& rd, const FeatDev& fd, const FeatMomDev* moments, hipStream_t stream) {
     const uint32_t blocks = (fd.ns + 255u) / 256u;
     if (blocks == 0u) return hipSuccess;
-    hipLaunchKernelGGL(k_features_fold, dim3(blocks), dim3(256), 0, stream, rd, fd);
-    return hipGetLastError();
-}
-
-hipError_t launch_features_fold_moments(const RenderDev& rd, const FeatDev& fd, const FeatMomDev& fm, hipStream_t stream) {
-    const uint32_t blocks = (fd.ns + 255u) / 256u;
-    if (blocks == 0u) return hipSuccess;
-    hipLaunchKernelGGL(k_features_fold_moments, dim3(blocks), dim3(256), 0, stream, rd, fd, fm);
+    if (moments) hipLaunchKernelGGL(k_features_fold<true>, dim3(blocks), dim3(256), 0, stream, rd, fd, *moments);
+    else hipLaunchKernelGGL(k_features_fold<false>, dim3(blocks), dim3(256), 0, stream, rd, fd, FeatMomDev{});
     return hipGetLastError();
 }
 
@@ -3303,7 +3148,7 @@ hipError_t launch_radiance_import(const RenderDev& rd, const RadianceDev& qd, co
     const uint64_t items = (uint64_t)qd.n * qd.n_samples;
     if (items == 0u) return hipSuccess;
     // (k_radiance_import: a slot is < queue_cap, an item's sum lies inside blocksum, an item id fits 32 bits)
-    if (items > (uint64_t)kQueues * rd.queue_cap || (rd.queue_cap & 511u) != 0u || items != rd.total_items || qd.n_samples != rd.n_blocks ||
+    if (!import_fits(items, rd.queue_cap) || items != rd.total_items || qd.n_samples != rd.n_blocks ||
         ((uint64_t)qd.stream0 + qd.n) * qd.n_samples > 0xFFFFFFFFull) return hipErrorInvalidValue;
     const uint32_t blocks = (uint32_t)((items + kRaysImportThreads - 1u) / kRaysImportThreads);
     hipLaunchKernelGGL(k_radiance_import, dim3(blocks), dim3(kRaysImportThreads), 0, stream, rd, qd, pool, counts, counters);

@@ -1355,8 +1355,7 @@ static int trace_rays_impl(RtCtx* ctx, const RtScene* scene, const RtRayQueryOpt
         hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr, ed = nullptr;
         if (first != 0u) HIP_TRY(ctx, cb.zero_queue_lines());
         if (timing) HIP_TRY(ctx, tm.mark(ea));
-        if (any_hit) LAUNCH_TRY(rtk::launch_occluded_import(d_rays, (uint32_t)first, n, pd, queue_cap, cb.count[0], d_hits, cb.c64, !rtk::extend_any_is_closest(scene->dev), ctx->stream));
-        else LAUNCH_TRY(rtk::launch_rays_import(d_rays, (uint32_t)first, n, pd, queue_cap, cb.count[0], d_hits, cb.c64, ctx->stream));
+        LAUNCH_TRY(rtk::launch_rays_import(d_rays, (uint32_t)first, n, pd, queue_cap, cb.count[0], d_hits, cb.c64, any_hit, !rtk::extend_any_is_closest(scene->dev), ctx->stream));
         if (timing) HIP_TRY(ctx, tm.mark(eb));
         cfg.max_rays = n;
         if (any_hit) LAUNCH_TRY(rtk::launch_extend_any(cfg, scene->dev, pd, rd, cb.count[0], cb.head, cb.count[1], cb.c64, ctx->stream));
@@ -1620,7 +1619,7 @@ int rt_features_check(const RtParams* params, const RtFeatureOptions* options) {
 // the whole sample run of as many slots as the pool has room for; only a pass with more samples per pixel than pool slots is cut along the
 // samples too, its later parts folding on from the planes — the same additions in the same order, so the cut does not show.
 static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, const RtParams* prm, const RtFeatureOptions* opt, const RtFeatureBuffers* out, RtStats* stats,
-                         const rtk::FeatMomDev* moments) {                // moments: the squared-sum planes of rt_render_feature_moments_device; the fold is then k_features_fold_moments
+                         const rtk::FeatMomDev* moments) {                // moments: the squared-sum planes of rt_render_feature_moments_device; the fold is then k_features_fold<true>
     using clk = std::chrono::steady_clock;
     const auto t_begin = clk::now();
     const bool timing = (prm->flags & RT_FLAG_TIMING) != 0u;
@@ -1667,8 +1666,7 @@ static int features_impl(RtCtx* ctx, const RtScene* scene, const RtCamera* cam, 
             if (timing) HIP_TRY(ctx, tm.mark(ec));
             LAUNCH_TRY(rtk::launch_features_export(cfg, scene->dev, rd, fd, pd, export_bound(rd.queue_cap, n), cb.count[0], ctx->stream));
             if (timing) HIP_TRY(ctx, tm.mark(ed));
-            if (moments) LAUNCH_TRY(rtk::launch_features_fold_moments(rd, fd, *moments, ctx->stream));
-            else LAUNCH_TRY(rtk::launch_features_fold(rd, fd, ctx->stream));
+            LAUNCH_TRY(rtk::launch_features_fold(rd, fd, moments, ctx->stream));
             if (timing) { HIP_TRY(ctx, tm.mark(ee)); tm.span(ea, eb, 1); tm.span(eb, ec, 0); tm.span(ec, ed, 2); tm.span(ed, ee, 3); }
             ++launched;
         }

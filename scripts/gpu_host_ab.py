@@ -9,7 +9,10 @@ The calls: book-1 and the Cornell box rendered at 64 x 40 x 8 and 150 x 90 x 3 â
 RT_FLAG_SAMPLE_BLOCKS, RT_FLAG_COUNTERS, tail_paths = 1 and RT_FLAG_FUSED, with pool_slots 4096; a progressive pair of passes with squared
 sums and an adaptive list pass; 10 000 rays and occlusion rays on device and host variants with pool_slots 0 and 4096 (three chunks);
 features and feature moments at 64 x 40 x 8 with pool_slots 0, 4096 and 4, overwriting and accumulating; book-1 uploaded with
-RT_LAYOUT_SCENE_IN_HBM and with RT_LAYOUT_WIDE_NODES beside it.
+RT_LAYOUT_SCENE_IN_HBM and with RT_LAYOUT_WIDE_NODES beside it; 256 light-sample queries, half of them with a direction given, on the
+Cornell box with each kind of lights table (plain, RT_SCENE_LIGHTS_ALL_SHAPES with the lamp as two triangles, RT_SCENE_LIGHTS_MANY on
+that); a radiance query of 256 rays x 4 samples on the Cornell box with one invalid ray; the three denoisers on a 64 x 40 x 8 book-1
+frame with its features and moments, at patch radii 1 and 3.
 
 --timing PATH adds, in a file of its own (never compared), the median and the range of render_ms over 20 calls after 3 warm ones of a
 4096-ray rt_trace_rays_device call and a 64 x 40 x 2 rt_render_device call: a change of host code shows first in small calls.
@@ -128,6 +131,47 @@ def main():
         *planes, st = ctx.render_features(scene, cam, prm, with_stats=True)
         record(f"features book1 {ln}", planes, st, chunked=True)
         scene.close()
+    # light-sample queries on the three kinds of lights table
+    doc = json.load(open(os.path.join(ROOT, "examples", "cornell_box.json")))
+    tri = json.loads(json.dumps(doc))                # the lamp's rectangle as two triangles whose front faces the floor
+    tri["objects"]["lamp_a"] = {"triangle": [[213, 554, 227], [343, 554, 332], [213, 554, 332]], "material": "light"}
+    tri["objects"]["lamp_b"] = {"triangle": [[213, 554, 227], [343, 554, 227], [343, 554, 332]], "material": "light"}
+    tri["world"] = {"list": ["left", "right", "lamp_a", "lamp_b", "floor", "ceiling", "back", "block_placed", "ball"]}
+    tri["lights"] = ["lamp_a", "lamp_b", "light_ball"]
+    rng = np.random.default_rng(19)
+    q = np.zeros(256, dtype=pkg.LIGHTQUERY_DTYPE)
+    q["p"] = rng.uniform(20.0, 530.0, (256, 3)).astype(np.float32)
+    q["rng_state"] = rng.integers(0, 1 << 63, 256, dtype=np.uint64)
+    q["d"][128:] = np.float32([278.0, 554.0, 279.5]) + rng.uniform(-60.0, 60.0, (128, 3)).astype(np.float32) * np.float32([1, 0, 1]) - q["p"][128:]
+    q["flags"][128:] = A.RT_LIGHTQ_DIRECTION_GIVEN
+    for kind, d in (("plain", doc), ("all_shapes", dict(tri, lights_all_shapes=True)), ("lights_many", dict(tri, lights_all_shapes=True, lights_many=True))):
+        js = pkg.JsonScene(d)
+        scene = ctx.upload(js.desc)
+        out, st = ctx._light_queries(scene, q, True)
+        record(f"sample_lights cornell {kind}", [out], st)
+        scene.close()
+    # a radiance query: 256 pixel-centre rays of the Cornell box, 4 samples each, ray 100 without a direction
+    hs = scenes["cornell"]
+    scene = ctx.upload(hs.desc)
+    rays = camera_rays(np, hs.camera(1.0), 16, 16)
+    rays[100, 4:7] = 0.0
+    rgb, sq, invalid, st = ctx.radiance(scene, rays, 4, seed=7, with_stats=True)
+    record("radiance cornell 256x4", [rgb, sq, invalid], st, chunked=True)
+    scene.close()
+    # the three denoisers on a book-1 frame with its features and moments
+    hs = scenes["book1"]
+    W, H = 64, 40
+    cam = hs.camera(W / H)
+    prm = pkg.make_params(W, H, 8, seed=7)
+    scene = ctx.upload(hs.desc)
+    rgb, sq, st = ctx.render_pass(scene, cam, prm, 0, 8, False, torch.zeros(W * H * 3, dtype=torch.float32, device=dev), torch.zeros(W * H * 3, dtype=torch.float32, device=dev))
+    alb, nrm, dep, hits, alb2, nrm2, dep2 = ctx.render_feature_moments(scene, cam, prm)
+    for f in (1, 3):
+        opt = pkg.denoise_options(patch_radius=f)
+        record(f"denoise book1 {W}x{H}x8 f{f}", [ctx.denoise(rgb, sq, W, H, samples=8, options=opt)], st)
+        record(f"denoise_guided book1 {W}x{H}x8 f{f}", [ctx.denoise_guided(rgb, sq, W, H, 8, alb, nrm, dep, hits, samples=8, options=opt)], st)
+        record(f"denoise_guided_moments book1 {W}x{H}x8 f{f}", [ctx.denoise_guided_moments(rgb, sq, W, H, 8, alb, nrm, dep, hits, alb2, nrm2, dep2, samples=8, options=opt)], st)
+    scene.close()
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
     print(f"{len(lines)} calls -> {args.out}")

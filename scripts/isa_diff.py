@@ -23,7 +23,7 @@ def kernels(path):
             ln = re.sub(r'\.LBB\d+_', '.LBB_', ln.split(';')[0]).replace(n, 'SELF').strip()
             if ln:
                 lines.append(ln)
-        out[re.sub(r'^void ', '', re.sub(r'\(.*', '', d))] = lines
+        out[re.sub(r'^void ', '', re.sub(r'\(.*', '', d.replace('(anonymous namespace)', '{anonymous}')))] = lines   # (denoise.hip's kernels)
     return out
 
 

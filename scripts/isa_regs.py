@@ -9,6 +9,6 @@ for b in t.split('  - .agpr_count')[1:]:
     sp = re.search(r'\.private_segment_fixed_size:\s+(\d+)', b).group(1)
     lds = re.search(r'\.group_segment_fixed_size:\s+(\d+)', b).group(1)
     d = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip()
-    d = re.sub(r'\(.*', '', d)
+    d = re.sub(r'\(.*', '', d.replace('(anonymous namespace)', '{anonymous}'))
     if flt in d:
         print(f"vgpr {v:>3} sgpr {sg:>3} scratch {sp:>4} lds {lds:>5}  {d}")

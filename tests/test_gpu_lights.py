@@ -6,7 +6,8 @@ a. rt_sample_lights against light_reference, query by query: the picked light an
        xy_rect 6.8e-08 / 3.9e-07   xz_rect 5.8e-08 / 4.2e-07   yz_rect 5.9e-08 / 3.8e-07   triangle 1.8e-07 / 1.1e-06   box 1.0e-07 / 2.3e-06
        wrapped_rect 1.2e-07 / 4.9e-07   wrapped_triangle 2.2e-07 / 1.6e-06   icosphere 2.1e-07 / 1.5e-05   mixed 6.7e-06 / 8.2e-06
    undecidable share (|cos| < 1e-2 at a light, or a crossing within 1e-4 of an edge, in f64): at most 1.4 % (icosphere).
-b. the flag changes nothing for a list of an XzRect and a Sphere: frames and query results equal as arrays.
+b. the flag changes nothing for a list of an XzRect and a Sphere: frames and query results equal as arrays; RT_LIGHTQ_LINEAR changes no
+   answer of a table without a light tree.
 c. direct lighting of a floor by one emitter against Lambert's polygon form factor, in the three kernel forms, bit-identical.
 d. the Cornell box with its lamp as two triangles (flag on) against the reference's rect lamp (flag off): the same picture, statistically.
 e. a refused lights list uploads nothing; a scene uploaded, destroyed and uploaded again renders the same frame."""
@@ -72,6 +73,33 @@ def test_flag_on_is_flag_off_for_an_xz_rect_and_a_sphere(pkg, gpu):
     assert np.array_equal(frames[0], frames[1])
     assert np.array_equal(samples[0].view(np.uint8), samples[1].view(np.uint8))
     assert set(samples[0]["light"]) == {0, 1} and (samples[0]["n_draws"] == 3).all()
+
+
+def test_the_linear_flag_means_nothing_without_a_light_tree(pkg, gpu):
+    """RT_LIGHTQ_LINEAR asks a table with a light tree for the plain loop. One kernel body serves every table kind and hands the flag to
+    lights_pdf_value always, so on a table without a tree — plain records, and RT_SCENE_LIGHTS_ALL_SHAPES records — the answers must not
+    depend on it: 64 queries on the Cornell box (its lamp as a rect, and as two triangles with the flag), half drawing and half with a
+    direction towards the lamp given, equal as bytes."""
+    A = pkg._abi
+    rng = np.random.default_rng(19)
+    q = np.zeros(64, dtype=pkg.LIGHTQUERY_DTYPE)
+    q["p"] = rng.uniform(20.0, 530.0, (64, 3)).astype(np.float32)
+    q["rng_state"] = rng.integers(0, 1 << 63, 64, dtype=np.uint64)
+    q["d"][32:] = np.float32([278.0, 554.0, 279.5]) + rng.uniform(-60.0, 60.0, (32, 3)).astype(np.float32) * np.float32([1, 0, 1]) - q["p"][32:]
+    q["flags"][32:] = A.RT_LIGHTQ_DIRECTION_GIVEN
+    lin = q.copy()
+    lin["flags"] |= A.RT_LIGHTQ_LINEAR
+    for tri in (False, True):
+        js = pkg.JsonScene(LC.cornell_doc(tri))
+        assert js.desc.scene_flags == (A.RT_SCENE_LIGHTS_ALL_SHAPES if tri else 0)
+        assert bool(pkg.compile_info(js.desc)["features"] & A.RT_FEATURE_LIGHTS_EXT) == tri
+        scene = gpu.upload(js.desc)
+        try:
+            plain, linear = gpu._light_queries(scene, q, False), gpu._light_queries(scene, lin, False)
+        finally:
+            scene.close()
+        assert (plain["pdf"][32:] > 0).any() and (plain["n_draws"][:32] > 0).all() and (plain["n_draws"][32:] == 0).all()
+        assert np.array_equal(plain.view(np.uint8), linear.view(np.uint8)), tri
 
 
 # ---- c. direct lighting against the closed form -----------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """Occlusion queries without a GPU (include/rt_hip.h, "occlusion queries"): the two symbols are declared, exported and bound; they refuse
 a call without a context; the Python wrapper accepts the three ray forms as far as a host without a device can tell; and the kernels the
-feature adds — the any-hit instances of k_extend, k_occluded_import, k_occluded_export — are in the gfx950 code object the build made,
+feature adds — the any-hit instances of k_extend, k_rays_import<true>, k_occluded_export — are in the gfx950 code object the build made,
 one k_extend instance per (mode, variant), with no scratch and (the walks) no static LDS."""
 import ctypes as C
 import os
@@ -119,9 +119,9 @@ def test_new_kernels_are_built_for_gfx950_without_scratch(pkg, tmp_path):
     for name, (vgpr, sgpr, scratch, lds) in anyhit.items():
         # no scratch; no static LDS (the staged scene starts at LDS address 0); within the 128 registers a 1024-thread group leaves a lane
         assert scratch == 0 and lds == 0 and vgpr <= 128, (name, vgpr, sgpr, scratch, lds)
-    for k in ("rtk::k_occluded_import", "rtk::k_occluded_export"):
+    for k in ("void rtk::k_rays_import<true>", "rtk::k_occluded_export"):
         assert k in meta, k + " is not in the code object"
         assert meta[k][2] == 0, (k, meta[k])
     assert meta["rtk::k_occluded_export"][3] == 0
     # the closest-hit kernels of a query are still there beside them
-    assert "rtk::k_rays_import" in meta and any(k.startswith("void rtk::k_rays_export<") for k in meta)
+    assert "void rtk::k_rays_import<false>" in meta and any(k.startswith("void rtk::k_rays_export<") for k in meta)
