@@ -126,10 +126,26 @@ pub const RT_TRI_UVS: u32 = 2;
 pub struct RtTriangleAttrs {
     pub hittable: i32, pub flags: u32, pub n: [[f32; 3]; 3], pub uv: [[f32; 2]; 3],
 }
+// an environment map: an HDR equirectangular image as background and, with RT_ENV_SAMPLED, as one more light (RtEnvMap.flags)
+pub const RT_ENV_SAMPLED: u32 = 1;
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct RtEnvMap {
+    pub struct_bytes: u32, pub flags: u32, pub width: u32, pub height: u32, pub rgb: *const f32, pub scale: f32, pub _pad: u32,
+}
 #[repr(C)] #[derive(Clone, Copy, Debug)]
 pub struct RtUploadOptions {
     pub struct_bytes: u32, pub layout_flags: u32, pub lds_top_records: u32, pub octant_axes: u32, pub leaf_collapse: u32, pub list_park_cost: f32,
     pub triangle_attrs: *const RtTriangleAttrs, pub n_triangle_attrs: u64,
+}
+// the options record grown at its end: hand `&x.base` (base.struct_bytes = size_of::<RtUploadOptionsEnv>()) to every entry point that takes options
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct RtUploadOptionsEnv {
+    pub base: RtUploadOptions, pub env_map: *const RtEnvMap,
+}
+impl RtUploadOptionsEnv {
+    pub fn new(env_map: *const RtEnvMap) -> Self {
+        RtUploadOptionsEnv { base: RtUploadOptions { struct_bytes: std::mem::size_of::<RtUploadOptionsEnv>() as u32, ..Default::default() }, env_map }
+    }
 }
 impl Default for RtUploadOptions {
     fn default() -> Self {
@@ -379,6 +395,7 @@ extern "C" {
     pub fn rt_scene_compile_dump_ex(desc: *const RtSceneDesc, options: *const RtUploadOptions, nodes: *mut c_void, cap_nodes: u64,
                                     spheres: *mut f32, sphere_meta: *mut u32, cap_spheres: u64) -> c_int;
     /// host only: the light tree of an RT_SCENE_LIGHTS_MANY scene (32-byte records), slot -> member, p and cdf by member; any output may be null
+    pub fn rt_env_tables(env_map: *const RtEnvMap, marg: *mut f32, cond: *mut f32) -> c_int;
     pub fn rt_scene_light_tree_dump(desc: *const RtSceneDesc, nodes: *mut c_void, cap_nodes: u64, slot_member: *mut u32, p: *mut f32, cdf: *mut f32,
                                     cap_lights: u64, out_n_lights: *mut u64, out_n_nodes: *mut u64) -> c_int;
     pub fn rt_scene_wide_layout_check(desc: *const RtSceneDesc, out: *mut RtWideInfo) -> c_int;

@@ -100,6 +100,15 @@ impl SceneBuilder {
     }
 }
 
+/// An environment map for `RtUploadOptionsEnv.env_map` (the reference has none: a host that loads an HDR panorama hands it over here). `rgb`:
+/// width * height * 3 linear radiance values, row 0 = up; it must outlive the upload that reads the record. `sampled`: RT_ENV_SAMPLED,
+/// the map is one more member of the lights list.
+pub fn env_map(rgb: &[f32], width: u32, height: u32, sampled: bool, scale: f32) -> RtEnvMap {
+    assert_eq!(rgb.len(), width as usize * height as usize * 3);
+    RtEnvMap { struct_bytes: std::mem::size_of::<RtEnvMap>() as u32, flags: if sampled { RT_ENV_SAMPLED } else { 0 }, width, height,
+               rgb: rgb.as_ptr(), scale, _pad: 0 }
+}
+
 /// What `Hittable`, `Material`, `Texture` gain (written as separate traits here so that this file stands alone; in the crate the method
 /// is added to the existing traits and `Arc<dyn Hittable>` is used where `Arc<dyn Flatten>` appears).
 pub trait Flatten { fn flatten(&self, b: &mut SceneBuilder) -> i32; }

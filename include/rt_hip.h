@@ -338,6 +338,52 @@ typedef struct RtTriangleAttrs {      /* 68 B */
     float    uv[3][2];                /* texture coordinates at v0, v1, v2 */
 } RtTriangleAttrs;
 
+/* ---- environment map: an HDR equirectangular image as background and, with RT_ENV_SAMPLED, as a light ----------------------------------------
+ * Travels beside the scene in RtUploadOptionsEnv.env_map, the grown options record below (rt_scene_upload_ex, rt_scene_upload_multi_ex, rt_scene_compile_info_ex). When it is
+ * present a ray that leaves the scene returns the map's radiance; RtSceneDesc.background_mode and background are then not read. The map is
+ * served by everything that shades a miss: renders in every kernel form, passes and pixel lists, radiance queries, rt_render_features* (the
+ * albedo of a miss is the map's radiance, as it is the background's without a map) and rt_sample_lights. The pointers are the caller's;
+ * nothing is retained after the upload returns. A scene uploaded without a map runs exactly the kernels it runs without this struct.
+ *
+ * LOOKUP, f32 on the device. The image texture's rule, so that a map equals that image on an enclosing sphere: ud = unit(d);
+ *   u = (atan2(-ud.z, ud.x) + pi) / (2 pi), v = acos(-ud.y) / pi (sphere.rs:32-37); then texture.rs:117-140: u, v clamped to [0, 1],
+ *   v := 1 - v, i = (uint)(u W), j = (uint)(v H), each clamped to W - 1, H - 1. Radiance = scale * rgb[(j W + i) * 3 ..]. Row 0 is up (+y);
+ *   column 0 begins at -x and the columns turn towards +z.
+ *   LIMITS: the nearest texel, no filtering; no rotation of the map.
+ * TABLES, on the host in f64, sequentially (the style of the RT_SCENE_LIGHTS_MANY cdf): f_ij = (0.2126 R + 0.7152 G + 0.0722 B) *
+ *   sin(pi (j + 0.5) / H) from the texels as given (scale left out: it cancels). Row sum r_j = f_j0 + f_j1 + ..; total = r_0 + r_1 + ..;
+ *   marg[j] = (float)((r_0 + .. + r_j) / total), a sequential running sum, marg[H-1] = 1.0f exactly; cond[j][i] = (float)((f_j0 + .. + f_ji)
+ *   / r_j), cond[j][W-1] = 1.0f exactly; a row with r_j = 0 gets the uniform cdf (float)((i + 1) / W). A map whose total is 0 gets the
+ *   uniform marginal as well (and cannot be sampled, below). rt_env_tables returns the tables as the upload builds them.
+ * DRAW, exactly two rnd(): u1 gives j = the first index with marg[j] > u1, u2 gives i = the first index with cond[j][i] > u2 (binary
+ *   searches). fy = (u1 - lo) / (hi - lo) with lo, hi the cdf entries before and at j (lo = 0 for j = 0), fx likewise. With a = (i + fx) / W
+ *   and b = (j + fy) / H the direction is the inverse of the lookup: d = (-sin(pi b) cos(2 pi a), cos(pi b), sin(pi b) sin(2 pi a)).
+ * PDF, always from the direction, by the LOOKUP's texel (i, j), never from the drawn texel: mass_ij W H / (2 pi^2 sin_theta) with mass_ij
+ *   = (marg[j] - marg[j-1]) (cond[j][i] - cond[j][i-1]) in f32 (entry -1 = 0) and sin_theta = sqrt(1 - ud.y^2); 0 where sin_theta is 0.
+ * RT_ENV_SAMPLED: the map is one more member of the lights list, after the caller's n members: the pick is next64() % (n + 1), the list's pdf
+ *   is the mean over the n + 1 members, RtLightSample.light is n for the map, and RtSceneDesc.lights = -1 gives a list of the map alone.
+ *   Without the flag the map is found by the cosine draws only (and by the other lights' directions that happen to miss everything).
+ * A scene with a map always takes the extended light records, as RT_SCENE_LIGHTS_MANY does (RtCompileInfo.features has 256 and 1024); the
+ *   lights list keeps the semantics its scene_flags give it.
+ * LIMIT: RT_ENV_SAMPLED together with RT_SCENE_LIGHTS_MANY is RT_ERR_INVALID: the pick of that list weighs by area and the map has none.
+ *   (An unsampled map with RT_SCENE_LIGHTS_MANY is refused too, for now: the map's kernels carry no light tree.)
+ * COST: a sampled map costs the light half of the Lambertian bounces two binary searches, log2 H + log2 W dependent loads (about 25 for a
+ *   4096 x 2048 map), and every bounce one pdf evaluation (four loads). An alias table would make the draw two loads; it is not built.
+ * REFUSED with RT_ERR_INVALID, the reason in rt_last_error, nothing uploaded: struct_bytes < sizeof(RtEnvMap); an unknown flag; a width or
+ * height of 0 or above 16384; NULL rgb; a texel or a scale that is not finite or is negative; RT_ENV_SAMPLED on a map of zero total weight;
+ * a map together with RT_SCENE_LIGHTS_MANY. */
+enum { RT_ENV_SAMPLED = 1u };
+typedef struct RtEnvMap {
+    uint32_t struct_bytes, flags;      /* sizeof(RtEnvMap) as the caller compiled it; RT_ENV_*, an unknown bit is RT_ERR_INVALID */
+    uint32_t width, height;            /* equirectangular, row 0 = up (+y), 1..16384 each */
+    const float* rgb;                  /* width * height * 3 f32, linear radiance, finite, >= 0 */
+    float scale;                       /* multiplies every texel; finite, >= 0 */
+    uint32_t _pad;
+} RtEnvMap;
+/* Host only, no device: the map checked as an upload checks it (without a scene: the RT_SCENE_LIGHTS_MANY rule is the upload's), and the two
+ * tables as the upload builds them: marg[height], cond[height * width]. Either pointer may be NULL = not wanted. */
+int rt_env_tables(const RtEnvMap* env_map, float* marg, float* cond);
+
 /* Checked, not dropped: a layout bit this library does not know, a switch set both ways (LISTS_AS_REFERENCE with LISTS_CULLED,
  * NO_MEMBER_BOXES with MEMBER_BOXES), struct_bytes < 8 or a negative list_park_cost is RT_ERR_INVALID with the reason in rt_last_error. */
 typedef struct RtUploadOptions {
@@ -353,6 +399,14 @@ typedef struct RtUploadOptions {
     const RtTriangleAttrs* triangle_attrs;   /* per-vertex normals / texture coordinates of RT_HIT_TRIANGLE records, see RtTriangleAttrs above */
     uint64_t n_triangle_attrs;               /* records in triangle_attrs; > 0 with a NULL pointer is RT_ERR_INVALID */
 } RtUploadOptions;
+/* The options record grown at its end, under its struct_bytes rule: the 40 bytes above, then what newer callers add. Every entry point that
+ * takes a const RtUploadOptions* takes &x.base of one of these with x.base.struct_bytes = sizeof(RtUploadOptionsEnv); what lies behind the
+ * 40 bytes is read only when struct_bytes covers it, so a caller compiled against RtUploadOptions (24 or 40 bytes) keeps working, and
+ * sizeof(RtUploadOptions) stays what those callers compiled. */
+typedef struct RtUploadOptionsEnv {
+    RtUploadOptions base;                    /* base.struct_bytes = sizeof(RtUploadOptionsEnv) */
+    const RtEnvMap* env_map;                 /* an environment map, see RtEnvMap above; NULL = none */
+} RtUploadOptionsEnv;
 int rt_scene_upload_ex(RtCtx* ctx, const RtSceneDesc* desc, const RtUploadOptions* options /* NULL = defaults */, RtScene** out_scene);
 
 /* Number of floats rt_render writes: 3 * pixels covered by this shard's tiles. For
@@ -913,7 +967,8 @@ typedef struct RtCompileInfo {
     uint64_t n_spheres, n_moving, n_rects, n_tris, n_media, n_xforms, n_lights, n_materials;
     uint32_t features;      /* kernel feature bits the scene needs (128: a triangle on the device carries attributes, n_tri_attrs > 0;
                                256: RT_SCENE_LIGHTS_ALL_SHAPES and a light that is not a bare XZ rect or sphere, or RT_SCENE_LIGHTS_MANY;
-                               512: RT_SCENE_LIGHTS_MANY, the lights table carries the light tree) */
+                               512: RT_SCENE_LIGHTS_MANY, the lights table carries the light tree;
+                               1024: the upload options carry an environment map, always with 256) */
     uint32_t fits_lds;      /* nodes + sphere records fit the LDS staging budget */
     uint32_t n_first;       /* primitives tested when a walk begins instead of being met by it (none with RT_LAYOUT_LISTS_AS_REFERENCE) ... */
     uint32_t first[4];      /* ... as leaf words: kind << 28 | count << 24 | first index (kind 1 = sphere, 2 = moving sphere, 5 = medium); they are not in the node records */

@@ -29,6 +29,8 @@ RT_TRI_NORMALS, RT_TRI_UVS = 1, 2
 RT_FEATURE_TRI_ATTR = 128      # RtCompileInfo.features: a triangle carries attributes (csrc/kernels.h F_TRI_ATTR)
 RT_FEATURE_LIGHTS_EXT = 256    # RtCompileInfo.features: the lights table holds extended records (csrc/kernels.h F_LIGHTS_EXT)
 RT_FEATURE_LIGHTS_TREE = 512   # RtCompileInfo.features: the lights table carries the light tree (csrc/kernels.h F_LIGHTS_TREE)
+RT_FEATURE_ENV = 1024          # RtCompileInfo.features: the upload options carry an environment map (csrc/kernels.h F_ENV)
+RT_ENV_SAMPLED = 1              # RtEnvMap.flags
 RT_SCENE_LIGHTS_ALL_SHAPES = 1  # RtSceneDesc.scene_flags
 RT_SCENE_LIGHTS_MANY = 4        # RtSceneDesc.scene_flags: area-weighted pick and the light tree; needs RT_SCENE_LIGHTS_ALL_SHAPES
 RT_LIGHTQ_DIRECTION_GIVEN = 1   # RtLightQuery.flags
@@ -119,10 +121,20 @@ class RtTriangleAttrs(C.Structure):
     _fields_ = [("hittable", C.c_int32), ("flags", C.c_uint32), ("n", (C.c_float * 3) * 3), ("uv", (C.c_float * 2) * 3)]
 
 
+class RtEnvMap(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("rgb", C.POINTER(C.c_float)),
+                ("scale", C.c_float), ("_pad", C.c_uint32)]
+
+
 class RtUploadOptions(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("layout_flags", C.c_uint32), ("lds_top_records", C.c_uint32), ("octant_axes", C.c_uint32),
                 ("leaf_collapse", C.c_uint32), ("list_park_cost", C.c_float),
                 ("triangle_attrs", C.POINTER(RtTriangleAttrs)), ("n_triangle_attrs", C.c_uint64)]
+
+
+class RtUploadOptionsEnv(C.Structure):
+    """the options record grown at its end: pass `base` (with base.struct_bytes = sizeof(RtUploadOptionsEnv)) where RtUploadOptions is taken"""
+    _fields_ = [("base", RtUploadOptions), ("env_map", C.POINTER(RtEnvMap))]
 
 
 class RtPassOptions(C.Structure):
@@ -213,7 +225,7 @@ RT_HIP_SYMBOLS = ["rt_ctx_create", "rt_ctx_destroy", "rt_scene_upload", "rt_scen
                   "rt_adaptive_check", "rt_adaptive_select", "rt_render_pass_pixels_device", "rt_resolve_counts_device",
                   "rt_denoise_check", "rt_denoise_device", "rt_denoise_guided_check", "rt_denoise_guided_device",
                   "rt_ray_query_check", "rt_trace_rays_device", "rt_trace_rays", "rt_occluded_rays_device", "rt_occluded_rays",
-                  "rt_sample_lights_device", "rt_sample_lights", "rt_scene_light_tree_dump",
+                  "rt_sample_lights_device", "rt_sample_lights", "rt_scene_light_tree_dump", "rt_env_tables",
                   "rt_radiance_check", "rt_radiance_rays_device", "rt_radiance_rays",
                   "rt_features_check", "rt_render_features_device",
                   "rt_feature_moments_check", "rt_render_feature_moments_device", "rt_denoise_guided_moments_check", "rt_denoise_guided_moments_device",
@@ -320,6 +332,8 @@ def declare(lib):
     lib.rt_scene_compile_dump_ex.argtypes = [P(RtSceneDesc), P(RtUploadOptions), vp, u64, P(C.c_float), P(u32), u64]
     lib.rt_scene_wide_layout_check.restype = i32
     lib.rt_scene_wide_layout_check.argtypes = [P(RtSceneDesc), P(RtWideInfo)]
+    lib.rt_env_tables.restype = i32
+    lib.rt_env_tables.argtypes = [P(RtEnvMap), P(C.c_float), P(C.c_float)]
     lib.rt_scene_light_tree_dump.restype = i32
     lib.rt_scene_light_tree_dump.argtypes = [P(RtSceneDesc), vp, u64, P(u32), P(C.c_float), P(C.c_float), u64, P(u64), P(u64)]
     lib.rt_camera_lists_host.restype = i32

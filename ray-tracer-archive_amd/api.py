@@ -361,10 +361,20 @@ class HostScene:
             pass
 
 
-def upload_options(layout_flags=0, lds_top_records=0, octant_axes=0, leaf_collapse=0, list_park_cost=0.0, triangle_attrs=None):
+def upload_options(layout_flags=0, lds_top_records=0, octant_axes=0, leaf_collapse=0, list_park_cost=0.0, triangle_attrs=None, env_map=None):
     """RtUploadOptions (include/rt_hip.h): how the scene is laid out on the device, never what it looks like — and the per-vertex normals /
-    texture coordinates of its triangles: triangle_attrs = a ctypes array or a sequence of RtTriangleAttrs (SceneBuilder.triangle_attrs())."""
-    opt = A.RtUploadOptions(C.sizeof(A.RtUploadOptions), layout_flags, lds_top_records, octant_axes, leaf_collapse, list_park_cost)
+    texture coordinates of its triangles: triangle_attrs = a ctypes array or a sequence of RtTriangleAttrs (SceneBuilder.triangle_attrs()) —
+    and its environment map: env_map = an environment.EnvMap; the record returned is then the first 40 bytes of an RtUploadOptionsEnv, with
+    struct_bytes = its 48."""
+    if env_map is not None:                                 # the grown record: its first 40 bytes are the options, and those are what is handed on
+        ext = A.RtUploadOptionsEnv()
+        ext.env_map = C.pointer(env_map.record)
+        opt = ext.base                                      # (a view into ext, which it keeps alive)
+        opt.struct_bytes, opt.layout_flags, opt.lds_top_records, opt.octant_axes, opt.leaf_collapse, opt.list_park_cost = (
+            C.sizeof(A.RtUploadOptionsEnv), layout_flags, lds_top_records, octant_axes, leaf_collapse, list_park_cost)
+        opt._keep_env = env_map                             # the record points into its texels
+    else:
+        opt = A.RtUploadOptions(C.sizeof(A.RtUploadOptions), layout_flags, lds_top_records, octant_axes, leaf_collapse, list_park_cost)
     if triangle_attrs is not None and len(triangle_attrs):
         arr = triangle_attrs if isinstance(triangle_attrs, C.Array) else (A.RtTriangleAttrs * len(triangle_attrs))(*triangle_attrs)
         opt.triangle_attrs, opt.n_triangle_attrs = arr, len(arr)
@@ -379,10 +389,11 @@ def runtime_libraries():
     return [p for p in buf.value.decode().split("\n") if p], code == A.RT_OK
 
 
-def scene_fingerprint(desc, triangle_attrs=None):
+def scene_fingerprint(desc, triangle_attrs=None, env_map=None):
     """sha256 (hex) over the arrays and scalars of an RtSceneDesc — and over the RtTriangleAttrs records that travel beside it, if any sets a
-    flag: what a progressive checkpoint records of the scene it was rendered from. A scene without attributes has the print it always had;
-    of a record only what its flags make the library read counts, in the order of the hittable ids."""
+    flag, and over the environment map (an environment.EnvMap), if there is one: what a progressive checkpoint records of the scene it was
+    rendered from. A scene without attributes and without a map has the print it always had; of a record only what its flags make the
+    library read counts, in the order of the hittable ids."""
     import hashlib
     h = hashlib.sha256()
 
@@ -415,6 +426,9 @@ def scene_fingerprint(desc, triangle_attrs=None):
                 h.update(bytes(a.n))
             if a.flags & A.RT_TRI_UVS:
                 h.update(bytes(a.uv))
+    if env_map is not None:
+        r = env_map.record
+        h.update(b"env_map" + np.array([r.flags, r.width, r.height], dtype=np.uint32).tobytes() + np.float32(r.scale).tobytes() + env_map.rgb.tobytes())
     return h.hexdigest()
 
 
@@ -424,7 +438,10 @@ class Scene:
         self._h = C.c_void_p()
         _check(lib().rt_scene_upload_ex(ctx._h, C.byref(desc), C.byref(options) if options is not None else None, C.byref(self._h)), ctx._h)
         attrs = getattr(options, "_keep", None) if options is not None and options.struct_bytes >= C.sizeof(A.RtUploadOptions) else None
-        self.fingerprint = scene_fingerprint(desc, attrs)     # (progressive checkpoints: the scene a frame's sums belong to)
+        env = getattr(options, "_keep_env", None) if options is not None and options.struct_bytes >= C.sizeof(A.RtUploadOptionsEnv) else None
+        if env is not None and not getattr(options, "_b_base_").env_map:
+            env = None                                       # (the field was cleared after upload_options set it)
+        self.fingerprint = scene_fingerprint(desc, attrs, env)   # (progressive checkpoints: the scene a frame's sums belong to)
 
     def close(self):
         if self._h and self.ctx._h:
@@ -448,7 +465,7 @@ class Context:
 
     def upload(self, desc, layout_flags=0, **more):
         """rt_scene_upload_ex; layout_flags = RT_LAYOUT_* (A.RT_LAYOUT_REFERENCE_COUNTERS: the layout whose test counts are the reference's);
-        triangle_attrs= (in `more`): RtTriangleAttrs records, see upload_options."""
+        triangle_attrs= (in `more`): RtTriangleAttrs records, env_map= an environment.EnvMap, see upload_options."""
         return Scene(self, desc, upload_options(layout_flags, **more) if (layout_flags or more) else None)
 
     def fail_next_renders(self, n):

@@ -135,7 +135,9 @@ struct Light { uint32_t kind; float p[5]; uint32_t _pad[2]; };   // rect: a0,a1,
 // RT_SCENE_LIGHTS_ALL_SHAPES with a member that is not a bare XzRect or Sphere (kernels.h F_LIGHTS_EXT): the lights table then holds one
 // 96-byte LightX per member INSTEAD of the 32-byte records (three Light slots each, so the table's bytes, its place in the shade blob and
 // SceneDev stay what they are; only the instances compiled with F_LIGHTS_EXT read it this way). A scene without the bit keeps the records above.
-enum LightXKind : uint32_t { LX_RECT = 1, LX_SPHERE = 2, LX_TRI = 3, LX_BOX = 4 };
+enum LightXKind : uint32_t { LX_RECT = 1, LX_SPHERE = 2, LX_TRI = 3, LX_BOX = 4,
+                             LX_DEFAULT = 5 };   // only in the table of a scene with an environment map and WITHOUT RT_SCENE_LIGHTS_ALL_SHAPES (such a scene takes the
+                                                 // extended records too: kernels.h F_ENV): a member the reference cannot sample, the trait defaults (hittable.rs:54-59)
 struct LightX {
     uint32_t kind;
     uint32_t has_xform;      // 1: the member sits under Translate / RotateY wrappers, composed into xf (world -> the member's own space)

@@ -21,7 +21,12 @@ enum : uint32_t {
     F_LIGHTS_EXT = 256u,
     // RT_SCENE_LIGHTS_MANY: the lights table also holds the light tree, the cdf of the area-weighted pick and the member -> slot table
     // (device_types.h); always together with F_LIGHTS_EXT. The same kernels have instances with it, and k_sample_lights one.
-    F_LIGHTS_TREE = 512u
+    F_LIGHTS_TREE = 512u,
+    // the upload carried an environment map (rt_hip.h RtEnvMap): a miss returns the map's radiance, and under RT_ENV_SAMPLED the map is one more
+    // member of the lights list. Not part of F_ALL; always with F_LIGHTS_EXT and never with F_LIGHTS_TREE: k_shade and the drain / fused form of
+    // k_extend have two instances with it (the full variant, without and with F_TRI_ATTR), k_sample_lights one. A scene without a map runs
+    // the instances it ran before the bit existed.
+    F_ENV = 1024u
 };
 #define RT_N_PRIM_TYPES_K 6
 enum : uint32_t { CTR_NODE_TESTS = 0, CTR_PRIM_TESTS = 1, CTR_SAMPLES = 7, CTR_DEBUG = 8, CTR_SEGMENTS = 13, CTR_ITERATIONS = 14, CTR_COUNT = 16 };
@@ -70,6 +75,11 @@ struct SceneDev {
                                // 0: the rect table is not staged (a scene whose rects are mostly box sides: the boxes are staged, a lone rect reads HBM)
     uint32_t sb_perlin_only;   // 1: the blob holds the Perlin tables alone (a scene whose other tables are too big to stage: book-2 final)
     uint32_t sb_spheres, sb_sphere_meta, sb_rects, sb_rect_meta, sb_moving, sb_moving_meta, sb_mat_a, sb_mat_b, sb_xforms, sb_wraps, sb_lights, sb_textures;   // byte offsets
+    // the environment map (rt_hip.h RtEnvMap; nullptr: none): env_w x env_h texels, row 0 = up, as (r, g, b, 0) so that one 128-bit load serves a
+    // look-up; the marginal cdf over the rows [env_h] and the conditional cdfs within the rows [env_h * env_w] (always built; read only by the
+    // instances with F_ENV when env_sampled is set); env_scale multiplies every texel. Always in HBM: a map is no small table.
+    const rtd::Float4* env_texels; const float* env_marg; const float* env_cond;
+    uint32_t env_w, env_h; float env_scale; uint32_t env_sampled;
 };
 
 // Path pool: structure of arrays, one lane-contiguous record per array and slot.

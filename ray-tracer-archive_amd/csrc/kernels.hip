@@ -1872,6 +1872,69 @@ DEVI V3 lightx_random(const rtd::LightX& l, V3 o, Rng& g) {
     }
     return l.has_xform ? xform_normal_back(l.xf, dir) : dir;
 }
+// ---- environment map (rt_hip.h RtEnvMap; instances with F_ENV only, and k_features_export at run time) ----
+// LOOKUP: the image texture's rule (texture_value above) on the unit direction, so that a map equals that image on an enclosing sphere:
+// (u, v) = sphere_uv(ud), clamp, v := 1 - v, nearest texel, index clamped. The index is in bounds whatever d holds (fmaxf drops a NaN).
+DEVI void sphere_uv(V3 p, float& u, float& v);
+DEVI uint32_t env_texel(const SceneDev& sc, V3 ud, uint32_t& i, uint32_t& j) {
+    float u, v;
+    sphere_uv(ud, u, v);
+    u = fminf(fmaxf(u, 0.f), 1.f);
+    v = 1.f - fminf(fmaxf(v, 0.f), 1.f);
+    i = (uint32_t)(u * (float)sc.env_w); j = (uint32_t)(v * (float)sc.env_h);
+    if (i >= sc.env_w) i = sc.env_w - 1u;
+    if (j >= sc.env_h) j = sc.env_h - 1u;
+    return j * sc.env_w + i;                                                   // (< 2^28: both dimensions <= 16384)
+}
+DEVI V3 env_radiance(const SceneDev& sc, V3 d) {
+    uint32_t i, j;
+    const Float4 t = sc.env_texels[env_texel(sc, unit(d), i, j)];
+    return sc.env_scale * v3(t.x, t.y, t.z);
+}
+// PDF, from the direction alone: the mass of the texel the lookup finds (the product of the two f32 cdf differences) over the texel's solid
+// angle (2 pi^2 sin_theta) / (W H); 0 at the poles.
+constexpr float kTwoPiSq = 19.739208802178716f;
+DEVI float env_pdf_value(const SceneDev& sc, V3 d) {
+    const V3 ud = unit(d);
+    uint32_t i, j;
+    const uint32_t at = env_texel(sc, ud, i, j);
+    const float sin_theta = sqrtf(1.0f - ud.y * ud.y);      // (IEEE square root and division here and in the draw: environment.py restates them as such)
+    if (!(sin_theta > 0.f)) return 0.f;
+    const float m_hi = sc.env_marg[j], c_hi = sc.env_cond[at];
+    const float m_lo = j != 0u ? sc.env_marg[j - 1u] : 0.f, c_lo = i != 0u ? sc.env_cond[at - 1u] : 0.f;
+    const float mass = (m_hi - m_lo) * (c_hi - c_lo);
+    return ((mass * (float)sc.env_w) * (float)sc.env_h) / (kTwoPiSq * sin_theta);
+}
+// the first index of cdf[0 .. n) whose entry exceeds u (the last entry is exactly 1 > u); lo_v = the entry before it (0 for the first). The
+// interval halves every trip: 32 trips cover any n, whatever the table holds.
+DEVI uint32_t env_search(const float* cdf, uint32_t n, float u) {
+    uint32_t lo = 0u, hi = n - 1u;
+    for (uint32_t trip = 0u; trip < 32u && lo < hi; ++trip) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (cdf[mid] > u) hi = mid; else lo = mid + 1u;
+    }
+    return lo;
+}
+// DRAW: exactly two rnd(): u1 picks the row, u2 the texel in it; the position inside the texel is the draws' remainders; the direction is
+// the inverse of the lookup map: with a = (i + fx) / W and b = (j + fy) / H, d = (-sin(pi b) cos(2 pi a), cos(pi b), sin(pi b) sin(2 pi a)).
+DEVI V3 env_random(const SceneDev& sc, Rng& g) {
+    const float u1 = g.rnd(), u2 = g.rnd();
+    const uint32_t j = env_search(sc.env_marg, sc.env_h, u1);
+    const float* row = sc.env_cond + j * sc.env_w;
+    const uint32_t i = env_search(row, sc.env_w, u2);
+    const float m_lo = j != 0u ? sc.env_marg[j - 1u] : 0.f, c_lo = i != 0u ? row[i - 1u] : 0.f;
+    const float fy = (u1 - m_lo) / (sc.env_marg[j] - m_lo), fx = (u2 - c_lo) / (row[i] - c_lo);
+    const float a = ((float)i + fx) / (float)sc.env_w, b = ((float)j + fy) / (float)sc.env_h;
+    const float phi = (2.0f * kPi) * a, th = kPi * b;   // libm sine and cosine: the hardware's (sincos_2pi) are off by 1e-6, more than the draw's own rounding
+    const float sb = sinf(th), cb = cosf(th);
+    return v3(-(sb * cosf(phi)), cb, sb * sinf(phi));
+}
+// members of the list the Lambertian branch samples: the caller's, and the map when it is sampled
+template <uint32_t FEAT>
+DEVI uint32_t lights_members(const SceneDev& sc) {
+    if constexpr ((FEAT & F_ENV) != 0u) return sc.n_lights + (sc.env_sampled != 0u ? 1u : 0u);
+    else return sc.n_lights;
+}
 // HittableList::random and pdf_value over the scene's lights (hittable_list.rs:73-84): what the light-sample query (k_sample_lights) calls, and
 // the Lambertian branch of shade_segment in the instances with F_LIGHTS_EXT. The instances without the bit keep the same statements in line
 // (over the same light_random / light_pdf_value): written as calls, their loop came out of hipcc with its exit test inverted, and the
@@ -1886,6 +1949,13 @@ DEVI const uint32_t* light_tree_slots(const SceneDev& sc) { return reinterpret_c
 DEVI float light_accumulate(float sum, float w, float pdf) { return fmaf(w, pdf, sum); }
 template <uint32_t FEAT>
 DEVI V3 lights_random(const SceneDev& sc, V3 p, Rng& g, uint32_t& k) {
+    if constexpr ((FEAT & F_ENV) != 0u) {
+        // the map is member n of a list of n + 1 (rt_hip.h RT_ENV_SAMPLED); a member the reference cannot sample keeps the trait defaults
+        k = (uint32_t)(g.next64() % (uint64_t)lights_members<FEAT>(sc));
+        if (k >= sc.n_lights) return env_random(sc, g);
+        const rtd::LightX l = reinterpret_cast<const rtd::LightX*>(sc.lights)[k];
+        return l.kind == rtd::LX_DEFAULT ? v3(1.f, 0.f, 0.f) : lightx_random(l, p, g);
+    }
     if constexpr ((FEAT & F_LIGHTS_TREE) != 0u) {
         // area-weighted pick: ONE draw, the first member whose cdf exceeds it (cdf in list order, its last entry exactly 1 > u). The
         // interval halves every trip: 32 trips cover any n, whatever the table holds.
@@ -1937,6 +2007,16 @@ DEVI float lights_tree_pdf_value(const SceneDev& sc, V3 p, V3 dir, unsigned long
 template <uint32_t FEAT>
 DEVI float lights_pdf_value(const SceneDev& sc, V3 p, V3 dir, unsigned long long& c_light_rect, unsigned long long& c_light_sphere, unsigned long long& c_light_tri,
                             bool linear = false) {
+    if constexpr ((FEAT & F_ENV) != 0u) {
+        const float weight = 1.0f / (float)lights_members<FEAT>(sc);
+        float lsum = 0.f;
+        for (uint32_t k = 0; k < sc.n_lights; ++k) {
+            const rtd::LightX l = reinterpret_cast<const rtd::LightX*>(sc.lights)[k];
+            lsum += weight * (l.kind == rtd::LX_DEFAULT ? 0.f : lightx_pdf_value(l, p, dir, c_light_rect, c_light_sphere, c_light_tri));
+        }
+        if (sc.env_sampled != 0u) lsum += weight * env_pdf_value(sc, dir);
+        return lsum;
+    }
     if constexpr ((FEAT & F_LIGHTS_TREE) != 0u) {
         if (!linear) return lights_tree_pdf_value(sc, p, dir, c_light_rect, c_light_sphere, c_light_tri);
         float lsum = 0.f;                                  // RT_LIGHTQ_LINEAR: every member, in the table's order, with its own weight
@@ -1985,6 +2065,8 @@ DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& 
     bool finished = false, time_zero = false;
     L = v3(0.f, 0.f, 0.f);          // radiance of this sample: set by the terminal event only
     if (hit.y == rtd::HIT_NONE) {
+        if constexpr ((FEAT & F_ENV) != 0u) L = s.T * env_radiance(sc, d);   // the map takes the background's place (rt_hip.h RtEnvMap)
+        else {
         // main.rs:74-76: the miss returns the background
         V3 bg = v3(rd.bg[0], rd.bg[1], rd.bg[2]);
         if (rd.bg_mode == RT_BG_SKY_GRADIENT_K) {
@@ -1993,6 +2075,7 @@ DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& 
             bg = (1.0f - t) * v3(1.f, 1.f, 1.f) + t * bg;
         }
         L = s.T * bg;
+        }
         finished = true;
     } else {
         // ---- rebuild the HitRecord (hittable.rs:11-19) from (ray, t, primitive) ----
@@ -2106,7 +2189,7 @@ DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& 
                 const Onb uvw = onb_from_w(n);                              // pdf.rs:18-22
                 V3 dir;
                 float pdf_val;
-                if ((FEAT & F_LIGHTS) && sc.n_lights) {
+                if ((FEAT & F_LIGHTS) && lights_members<FEAT>(sc)) {
                     // MixturePdf::generate (pdf.rs:73-79) over HittablePdf(lights) and the cosine pdf
                     float lsum = 0.f;
                     if constexpr ((FEAT & F_LIGHTS_EXT) != 0u) {             // extended light records: the list functions the light-sample query calls too
@@ -2710,6 +2793,7 @@ __global__ void __launch_bounds__(256) k_features_export(SceneDev sc, RenderDev 
             const float t = 0.5f * (ud.y + 1.0f);
             bg = (1.0f - t) * v3(1.f, 1.f, 1.f) + t * bg;
         }
+        if constexpr ((FEAT & F_ENV) != 0u) bg = env_radiance(sc, d);             // a scene with an environment map: the map's radiance
         rec[0] = Float4{bg.x, bg.y, bg.z, 0.f};
         rec[1] = Float4{0.f, 0.f, 0.f, __uint_as_float(0u)};
         return;
@@ -2873,7 +2957,13 @@ template <class F> static auto with_record_variant(uint32_t features, F&& f) {
 // ... and two more again for scenes whose lights table carries the light tree (F_LIGHTS_TREE: RT_SCENE_LIGHTS_MANY, always with F_LIGHTS_EXT).
 constexpr uint32_t kVariantAllLx = F_ALL | F_LIGHTS_EXT, kVariantAllAttrLx = F_ALL | F_TRI_ATTR | F_LIGHTS_EXT;
 constexpr uint32_t kVariantAllLt = kVariantAllLx | F_LIGHTS_TREE, kVariantAllAttrLt = kVariantAllAttrLx | F_LIGHTS_TREE;
+// ... and two for scenes with an environment map (F_ENV, always with F_LIGHTS_EXT, never with F_LIGHTS_TREE: rt_api.cpp scene_image_build).
+constexpr uint32_t kVariantAllEnv = kVariantAllLx | F_ENV, kVariantAllAttrEnv = kVariantAllAttrLx | F_ENV;
 template <class F> static auto with_shade_variant(uint32_t features, F&& f) {
+    if ((features & F_ENV) != 0u) {
+        if ((features & F_TRI_ATTR) == 0u) return f(std::integral_constant<uint32_t, kVariantAllEnv>{});
+        return f(std::integral_constant<uint32_t, kVariantAllAttrEnv>{});
+    }
     if ((features & F_LIGHTS_EXT) == 0u) return with_record_variant(features, f);
     if ((features & F_LIGHTS_TREE) != 0u) {
         if ((features & F_TRI_ATTR) == 0u) return f(std::integral_constant<uint32_t, kVariantAllLt>{});
@@ -3108,11 +3198,13 @@ hipError_t launch_occluded_export(const PoolDev& pool, uint32_t queue_cap, uint3
 hipError_t launch_sample_lights(const SceneDev& sc, uint32_t features, const void* queries, void* results, uint32_t n, hipStream_t stream) {
     const uint32_t blocks = (n + 255u) / 256u;
     if (blocks == 0u) return hipSuccess;
-    if (sc.n_lights == 0u) return hipErrorInvalidValue;                  // (the host refuses a scene without lights before anything is launched)
+    const bool env_member = (features & F_ENV) != 0u && sc.env_sampled != 0u;
+    if (sc.n_lights == 0u && !env_member) return hipErrorInvalidValue;   // (the host refuses a scene without lights before anything is launched)
     const uint32_t lf = features & (F_LIGHTS_EXT | F_LIGHTS_TREE);       // (a tree comes with extended records only)
     const auto go = [&](auto f) {
         hipLaunchKernelGGL(k_sample_lights<decltype(f)::value>, dim3(blocks), dim3(256), 0, stream, sc, (const LightQueryDev*)queries, (LightSampleDev*)results, n); };
-    if (lf == 0u) go(std::integral_constant<uint32_t, 0u>{});
+    if ((features & F_ENV) != 0u) go(std::integral_constant<uint32_t, F_LIGHTS_EXT | F_ENV>{});
+    else if (lf == 0u) go(std::integral_constant<uint32_t, 0u>{});
     else if (lf == F_LIGHTS_EXT) go(std::integral_constant<uint32_t, F_LIGHTS_EXT>{});
     else go(std::integral_constant<uint32_t, F_LIGHTS_EXT | F_LIGHTS_TREE>{});
     return hipGetLastError();
@@ -3131,7 +3223,10 @@ hipError_t launch_features_export(const LaunchCfg& cfg, const SceneDev& sc, cons
                                   const uint32_t* counts, hipStream_t stream) {
     const uint32_t blocks = export_blocks(max_count, rd.queue_cap);
     if (blocks == 0u) return hipSuccess;
-    with_record_variant(cfg.features, [&](auto feat) {
+    // a scene with an environment map: the full variant with F_ENV (a run-time branch on sc.env_texels moved the registers of the existing instances)
+    if ((cfg.features & F_ENV) != 0u) with_flag((cfg.features & F_TRI_ATTR) != 0u, [&](auto attr) {
+        hipLaunchKernelGGL((k_features_export<(decltype(attr)::value ? kVariantAllAttr : F_ALL) | F_ENV>), dim3(blocks), dim3(256), 0, stream, sc, rd, fd, pool, counts); });
+    else with_record_variant(cfg.features, [&](auto feat) {
         hipLaunchKernelGGL((k_features_export<decltype(feat)::value>), dim3(blocks), dim3(256), 0, stream, sc, rd, fd, pool, counts); });
     return hipGetLastError();
 }

@@ -493,9 +493,71 @@ static int check_options(const RtUploadOptions* options, std::string& err) {
     return RT_OK;
 }
 
+// ---- environment map (rt_hip.h RtEnvMap): checked, then its two cdf tables by the header's rule ------------------------------------------------
+// the map of an options record, where the caller's struct reaches that far and names one
+static const RtEnvMap* env_of(const RtUploadOptions* o) {
+    static_assert(sizeof(RtUploadOptions) == 40 && offsetof(RtUploadOptionsEnv, env_map) == 40 && sizeof(RtUploadOptionsEnv) == 48, "the options record grows at its end");
+    if (!o || o->struct_bytes < sizeof(RtUploadOptionsEnv)) return nullptr;
+    return reinterpret_cast<const RtUploadOptionsEnv*>(o)->env_map;
+}
+// f64, sequential sums throughout. *total: the sum of the row sums (0: nothing to sample; both tables are then uniform)
+static void env_tables(const RtEnvMap& e, float* marg, float* cond, double* total) {
+    const size_t W = e.width, H = e.height;
+    std::vector<double> row(H);
+    std::vector<double> f(W);
+    double tot = 0.0;
+    for (size_t j = 0; j < H; ++j) {
+        const double st = std::sin(3.14159265358979323846 * ((double)j + 0.5) / (double)H);
+        double r = 0.0;
+        for (size_t i = 0; i < W; ++i) {
+            const float* t = e.rgb + (j * W + i) * 3;
+            f[i] = (0.2126 * (double)t[0] + 0.7152 * (double)t[1] + 0.0722 * (double)t[2]) * st;
+            r += f[i];
+        }
+        row[j] = r;
+        if (cond) {
+            double run = 0.0;
+            for (size_t i = 0; i < W; ++i) { run += f[i]; cond[j * W + i] = r > 0.0 ? (float)(run / r) : (float)((double)(i + 1) / (double)W); }
+            cond[j * W + W - 1] = 1.0f;
+        }
+    }
+    for (size_t j = 0; j < H; ++j) tot += row[j];
+    if (marg) {
+        double run = 0.0;
+        for (size_t j = 0; j < H; ++j) { run += row[j]; marg[j] = tot > 0.0 ? (float)(run / tot) : (float)((double)(j + 1) / (double)H); }
+        marg[H - 1] = 1.0f;
+    }
+    if (total) *total = tot;
+}
+static int check_env(const RtEnvMap* e, std::string& err) {
+    if (!e) return RT_OK;
+    if (e->struct_bytes < sizeof(RtEnvMap) || e->struct_bytes > 4096u) { err = "RtEnvMap.struct_bytes is not set (sizeof(RtEnvMap))"; return RT_ERR_INVALID; }
+    if (e->flags & ~(uint32_t)RT_ENV_SAMPLED) { err = "RtEnvMap.flags holds an unknown bit (known: RT_ENV_SAMPLED)"; return RT_ERR_INVALID; }
+    if (e->width == 0u || e->height == 0u || e->width > 16384u || e->height > 16384u) { err = "RtEnvMap.width and height must be in 1..16384"; return RT_ERR_INVALID; }
+    if (!e->rgb) { err = "RtEnvMap.rgb is NULL"; return RT_ERR_INVALID; }
+    if (!(std::isfinite(e->scale) && e->scale >= 0.f)) { err = "RtEnvMap.scale is negative or not finite"; return RT_ERR_INVALID; }
+    const size_t n = (size_t)e->width * e->height * 3;
+    for (size_t k = 0; k < n; ++k)
+        if (!(std::isfinite(e->rgb[k]) && e->rgb[k] >= 0.f)) { err = "RtEnvMap.rgb: texel " + std::to_string(k / 3) + " is negative or not finite"; return RT_ERR_INVALID; }
+    if (e->flags & RT_ENV_SAMPLED) {
+        double total = 0.0;
+        env_tables(*e, nullptr, nullptr, &total);
+        if (!(total > 0.0) || !std::isfinite(total)) { err = "RtEnvMap: RT_ENV_SAMPLED on a map whose total weight is not a positive finite number"; return RT_ERR_INVALID; }
+    }
+    return RT_OK;
+}
+int rt_env_tables(const RtEnvMap* env_map, float* marg, float* cond) {
+    if (!env_map) return set_err(nullptr, RT_ERR_INVALID, "null argument");
+    std::string err;
+    { const int ok = check_env(env_map, err); if (ok != RT_OK) return set_err(nullptr, ok, err); }
+    env_tables(*env_map, marg, cond, nullptr);
+    return RT_OK;
+}
+
 static rti::UploadOpts resolve_options(const RtUploadOptions* o) {
     rti::UploadOpts u;
     u.compile.elide_within_lds_bytes = kLdsSceneBudget;
+    u.compile.lights_ext_always = env_of(o) != nullptr;   // a scene with a map runs the instances that read extended light records (kernels.h F_ENV)
     if (o && o->struct_bytes >= 8u) {
         const uint32_t f = o->layout_flags;
         // box records are elided in the layout a scene staged in LDS gets by default only: the reference's counts (LISTS_AS_REFERENCE,
@@ -578,6 +640,11 @@ static int tri_attr_table(const RtSceneDesc& desc, const RtUploadOptions* o, con
 // against the result (tri_attr_table: `table` receives their device records, nullptr = checked and counted only).
 static int compile_checked(const RtSceneDesc& desc, const RtUploadOptions* options, rtc::CompiledScene& cs, std::vector<rtd::Float4>* table, uint32_t* n_with, std::string& err) {
     { const int ok = check_options(options, err); if (ok != RT_OK) return ok; }
+    { const int ok = check_env(env_of(options), err); if (ok != RT_OK) return ok; }
+    if (env_of(options) && (desc.scene_flags & RT_SCENE_LIGHTS_MANY)) {
+        err = "RtEnvMap: an environment map together with RT_SCENE_LIGHTS_MANY is not supported (that list weighs its members by area, and the map has none)";
+        return RT_ERR_INVALID;
+    }
     const int rc = rtc::compile_scene(desc, resolve_options(options).compile, cs);
     if (rc != RT_OK) { err = "scene: " + cs.error; return rc; }
     return tri_attr_table(desc, options, cs, table, n_with, err);
@@ -602,6 +669,9 @@ struct rti::SceneImage {
     uint32_t features = 0u;
     rtw::WideTree wide; bool use_wide = false;     // 8-wide nodes for k_extend_wide (a static BVH that does not fit LDS)
     std::vector<rtd::Float4> tri_attrs;            // tri_attr_table: 4 records per device triangle, empty = the upload gave no attributes
+    std::vector<rtd::Float4> env_texels;           // the environment map (kernels.h SceneDev::env_texels): (r, g, b, 0) per texel, empty = none
+    std::vector<float> env_marg, env_cond;         // ... and its cdf tables (env_tables above)
+    uint32_t env_w = 0u, env_h = 0u, env_sampled = 0u; float env_scale = 0.f;
 };
 void rti::scene_image_free(SceneImage* im) { delete im; }
 
@@ -697,6 +767,15 @@ int rti::scene_image_build(const RtSceneDesc* desc, const RtUploadOptions* optio
         }
     }
     if (!im->tri_attrs.empty()) im->features |= rtk::F_TRI_ATTR;
+    if (const RtEnvMap* e = env_of(options)) {     // (checked by compile_checked)
+        const size_t n = (size_t)e->width * e->height;
+        im->env_texels.resize(n);
+        for (size_t k = 0; k < n; ++k) im->env_texels[k] = rtd::Float4{e->rgb[3 * k], e->rgb[3 * k + 1], e->rgb[3 * k + 2], 0.f};
+        im->env_marg.resize(e->height); im->env_cond.resize(n);
+        env_tables(*e, im->env_marg.data(), im->env_cond.data(), nullptr);
+        im->env_w = e->width; im->env_h = e->height; im->env_scale = e->scale; im->env_sampled = (e->flags & RT_ENV_SAMPLED) ? 1u : 0u;
+        im->features |= rtk::F_LIGHTS_EXT | rtk::F_ENV;   // like F_TRI_ATTR: what is shaded, never what is walked
+    }
     *out = im.release();
     return RT_OK;
 }
@@ -740,6 +819,7 @@ int rti::scene_image_upload(RtCtx* ctx, const SceneImage& im, RtScene** out_scen
     if (!cam_order.empty()) up(s->cam_order, cam_order);
     if (!im.blob.empty()) up(s->shade_blob, im.blob);
     if (!im.eblob.empty()) up(s->ext_blob, im.eblob);
+    if (!im.env_texels.empty()) { up(s->env_texels, im.env_texels); up(s->env_marg, im.env_marg); up(s->env_cond, im.env_cond); }
     if (r == RT_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) r = set_err(ctx, RT_ERR_DEVICE, "scene upload failed");   // the image is the caller's: its vectors outlive this wait
     if (r != RT_OK) { rt_scene_destroy(ctx, s); return r; }
     rtk::SceneDev& d = s->dev;
@@ -772,6 +852,10 @@ int rti::scene_image_upload(RtCtx* ctx, const SceneImage& im, RtScene** out_scen
     d.eb_rect_stride = im.eb_rect_stride; d.eb_rects = eb[0]; d.eb_moving = eb[1]; d.eb_xforms = eb[2]; d.eb_media = eb[3]; d.eb_boxes = eb[4];
     d.sb_perlin_only = im.perlin_only;
     d.sb_mat_a = sb[6]; d.sb_mat_b = sb[7]; d.sb_xforms = sb[8]; d.sb_wraps = sb[9]; d.sb_lights = sb[10]; d.sb_textures = sb[11];
+    if (!im.env_texels.empty()) {
+        d.env_texels = (const rtd::Float4*)s->env_texels.p; d.env_marg = (const float*)s->env_marg.p; d.env_cond = (const float*)s->env_cond.p;
+        d.env_w = im.env_w; d.env_h = im.env_h; d.env_scale = im.env_scale; d.env_sampled = im.env_sampled;
+    }
     s->src = rtk::RaySrcDev{(const uint32_t*)s->sphere_src.p, (const uint32_t*)s->moving_src.p, (const uint32_t*)s->rect_src.p, (const uint32_t*)s->tri_src.p};
     s->features = im.features;
     // a sphere with a DiffuseLight material: a camera ray can end on it, so such a scene's camera rays are not shaded where they are made (render_impl)
@@ -1428,7 +1512,8 @@ static int light_query_refuse(RtCtx* ctx, const RtScene* scene, const RtLightQue
     if (!scene) return set_err(ctx, RT_ERR_INVALID, "scene is null");
     if (o) { const int h = check_header(ctx, o->struct_bytes, sizeof(RtLightQueryOptions), "RtLightQueryOptions", o->flags, RT_FLAG_TIMING, "RT_FLAG_TIMING"); if (h != RT_OK) return h; }
     if (n > 0xFFFFFFFFull) return set_err(ctx, RT_ERR_INVALID, "n must be < 2^32 (split the list)");
-    if ((scene->features & rtk::F_LIGHTS) == 0u || scene->dev.n_lights == 0u)
+    const bool env_member = (scene->features & rtk::F_ENV) != 0u && scene->dev.env_sampled != 0u;   // a sampled map is a list by itself
+    if (((scene->features & rtk::F_LIGHTS) == 0u || scene->dev.n_lights == 0u) && !env_member)
         return set_err(ctx, RT_ERR_UNSUPPORTED, "light-sample queries: the scene was uploaded without a lights list (RtSceneDesc.lights = -1)");
     if (n != 0u && (!queries || !results)) return set_err(ctx, RT_ERR_INVALID, "queries / results is null");
     if (device && ((((uintptr_t)queries) | ((uintptr_t)results)) & 7u)) return set_err(ctx, RT_ERR_INVALID, "queries / results must be 8-byte aligned");
@@ -1742,7 +1827,7 @@ int rt_scene_compile_info_ex(const RtSceneDesc* desc, const RtUploadOptions* opt
     out->n_nodes = cs.nodes.size(); out->n_box_nodes = cs.n_box_nodes; out->n_spheres = cs.sphere_meta.size(); out->n_moving = cs.moving_meta.size();
     out->n_rects = cs.rect_meta.size(); out->n_tris = cs.tri_meta.size(); out->n_media = cs.media.size(); out->n_xforms = cs.xforms.size();
     out->n_lights = cs.n_lights; out->n_materials = cs.mat_b.size();
-    out->features = scene_features(cs) | (n_with != 0u ? rtk::F_TRI_ATTR : 0u);
+    out->features = scene_features(cs) | (n_with != 0u ? rtk::F_TRI_ATTR : 0u) | (env_of(options) ? rtk::F_LIGHTS_EXT | rtk::F_ENV : 0u);
     out->n_tri_attrs = n_with;
     out->fits_lds = lds_scene_bytes(cs) <= kLdsSceneBudget ? 1u : 0u;
     {   // what a walk tests before it enters the tree: the root list's every-ray members, then the root BVH's scene-sized spheres

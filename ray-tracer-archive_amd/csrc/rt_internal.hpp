@@ -64,7 +64,7 @@ struct RtCtx {
 
 struct RtScene {
     rti::DevBuf nodes, spheres, sphere_meta, moving, moving_meta, rects, rect_meta, tris, tri_meta, boxes, media, xforms, wraps, mat_a, mat_b, textures, perlins, images,
-        image_bytes, lights, top_nodes, shade_blob, ext_blob, wide, sphere_mat_a, sphere_mat_b;
+        image_bytes, lights, top_nodes, shade_blob, ext_blob, wide, sphere_mat_a, sphere_mat_b, env_texels, env_marg, env_cond;
     rti::DevBuf sphere_src, moving_src, rect_src, tri_src;   // ray queries: the RtHittable record of every primitive (no render kernel reads them)
     rtk::SceneDev dev{};
     rtk::RaySrcDev src{};

@@ -53,6 +53,7 @@ struct Compiler {
     std::map<std::pair<long long, std::pair<long long, std::pair<long long, long long>>>, uint32_t> xform_cache;
     bool box_pair_members = false;
     bool big_spheres_first = true;
+    bool lights_ext_always = false;   // CompileOptions::lights_ext_always
     bool cull_lists = true;   // HittableList members behind culling boxes (emit_list_culled); RT_LAYOUT_LISTS_AS_REFERENCE: every member probed by every ray, as the reference does
     double park_cost = 6.0;   // what a stop of the walk at a leaf costs, in primitive tests (RtUploadOptions.list_park_cost)
     std::map<std::vector<long long>, uint32_t> wrap_cache;
@@ -890,6 +891,22 @@ struct Compiler {
         if (ids.empty()) { fail("empty lights list (the reference divides by its length, hittable_list.rs:74,82)"); return; }
         out.n_lights = (uint32_t)ids.size();
         if (d.scene_flags & RT_SCENE_LIGHTS_ALL_SHAPES) { compile_lights_all_shapes(ids); return; }
+        if (lights_ext_always) {   // the same members as extended records: a bare XzRect, a Sphere, or the trait defaults (LX_DEFAULT)
+            std::vector<rtd::LightX> xs;
+            for (int id : ids) {
+                const RtHittable* h = H(id); if (!h) return;
+                rtd::LightX x{};
+                x.xf = rtd::Xform{0.f, 1.f, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+                if (h->kind == RT_HIT_XZ_RECT) { x.kind = rtd::LX_RECT; for (int i = 0; i < 5; ++i) x.p[i] = (float)h->p[i]; x.p[5] = 1.f; }
+                else if (h->kind == RT_HIT_SPHERE) { x.kind = rtd::LX_SPHERE; for (int i = 0; i < 4; ++i) x.p[i] = (float)h->p[i]; }
+                else x.kind = rtd::LX_DEFAULT;
+                xs.push_back(x);
+            }
+            out.lights_ext = true;
+            out.lights.resize(3 * xs.size());
+            std::memcpy(out.lights.data(), xs.data(), xs.size() * sizeof(rtd::LightX));
+            return;
+        }
         for (int id : ids) {
             const RtHittable* h = H(id); if (!h) return;
             rtd::Light l{};
@@ -906,7 +923,7 @@ struct Compiler {
         std::vector<rtd::LightX> xs;
         const bool many = (d.scene_flags & RT_SCENE_LIGHTS_MANY) != 0u;
         std::vector<double> areas;                                             // RT_SCENE_LIGHTS_MANY: from the desc's f64 parameters (rt_hip.h has the rule)
-        bool ext = many;                                                       // ... which always takes the extended records
+        bool ext = many || lights_ext_always;                                  // ... which always takes the extended records (as a scene with an environment map does)
         for (size_t k = 0; k < ids.size(); ++k) {
             const std::string who = "lights list member " + std::to_string(k) + ": ";
             Chain c;
@@ -1114,6 +1131,7 @@ int compile_scene(const RtSceneDesc& desc, const CompileOptions& opt, CompiledSc
     c.box_pair_members = opt.member_boxes < 0 ? desc.n_hittables < 8192 : opt.member_boxes != 0;      // scenes of that size are LDS-resident (rt_api.cpp: 144 KB of records and spheres)
     c.park_cost = std::max(0.0, opt.park_cost);
     c.big_spheres_first = opt.big_spheres_first;
+    c.lights_ext_always = opt.lights_ext_always;
     out.xforms.push_back(rtd::Xform{0.f, 1.f, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}});
     out.wraps.push_back(rtd::Wrap{});
     c.compile_materials();

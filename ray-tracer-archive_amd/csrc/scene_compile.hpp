@@ -49,6 +49,8 @@ struct CompileOptions {
     bool big_spheres_first = true;  // a sphere of the root BVH whose box is most of the scene (a ground sphere) is tested when a walk begins, not met by it
     size_t elide_within_lds_bytes = 0;  // a scene whose lds_scene_bytes() is within this budget BEFORE the pass loses the inner box records that cost more tests than they
                                         // save (scene_compile.cpp elide_box_nodes); 0: every box record stays (scenes walked from HBM keep binary nodes)
+    bool lights_ext_always = false;     // the lights table holds rtd::LightX records whatever the list holds (a scene with an environment map: kernels.h F_ENV). Not
+                                        // a layout choice of the caller's: rt_api.cpp sets it from RtUploadOptionsEnv.env_map
 };
 
 // What a workgroup stages of a scene that is walked from LDS: the records, the two closing ones, a park twin per leaf, the sphere data.

@@ -362,9 +362,11 @@ def _light_random(M, l, o, g, live):
     return d
 
 
-def light_reference(desc, points, states=None, dirs=None, dtype=np.float64):
+def light_reference(desc, points, states=None, dirs=None, dtype=np.float64, env=None):
     """What rt_sample_lights returns for (points, states) — or, with `dirs`, for RT_LIGHTQ_DIRECTION_GIVEN queries — restated in `dtype`
-    (np.float64 or np.float32). points, dirs: (n, 3), read as f32; states: n uint64.
+    (np.float64 or np.float32). points, dirs: (n, 3), read as f32; states: n uint64. env: the environment.EnvMap the scene was uploaded with;
+    a sampled one is member n of a list of n + 1 (include/rt_hip.h RT_ENV_SAMPLED), also of a scene without a lights list. Its results carry
+    env_border and env_sin_theta (environment.env_reference: border, sin_theta) of the direction as well.
 
     Returns dict(d (n, 3), pdf (n), light (n, int32), n_draws (n, uint32)) plus what decides whether a query can be held to the yardstick at
     all: pick_gap (RT_SCENE_LIGHTS_MANY: the distance of the pick's draw from the nearest inner cdf edge; else inf), cos_min (the smallest |cos|
@@ -373,9 +375,16 @@ def light_reference(desc, points, states=None, dirs=None, dtype=np.float64):
     T = np.dtype(dtype).type
     M = _Ops(T)
     lights = lights_of(desc)
-    if not lights:
+    env_member = env is not None and env.sampled
+    if not lights and not env_member:
         raise ValueError("the scene has no lights list")
+    n_members = len(lights) + (1 if env_member else 0)
     many = bool(desc.scene_flags & A.RT_SCENE_LIGHTS_MANY)
+    if env_member:
+        from . import environment as E
+        if many:
+            raise ValueError("RT_ENV_SAMPLED together with RT_SCENE_LIGHTS_MANY")
+        e_marg, e_cond, _ = E.tables_reference(env.rgb)
     if many:
         p_k, cdf = light_weights(desc, T)
     pts = np.asarray(points, dtype=np.float32).reshape(-1, 3)
@@ -392,7 +401,7 @@ def light_reference(desc, points, states=None, dirs=None, dtype=np.float64):
             light = np.searchsorted(cdf.astype(np.float64), u, side="right").astype(np.int32)
             pick_gap = np.abs(u[:, None] - cdf.astype(np.float64)[None, :-1]).min(axis=1) if len(lights) > 1 else pick_gap
         else:
-            light = (g.next64(every) % np.uint64(len(lights))).astype(np.int32)
+            light = (g.next64(every) % np.uint64(n_members)).astype(np.int32)
         d = [np.zeros(n, dtype=T) for _ in range(3)]
         for k, l in enumerate(lights):
             live = light == k
@@ -400,16 +409,25 @@ def light_reference(desc, points, states=None, dirs=None, dtype=np.float64):
                 continue
             dk = _light_random(M, l, o, g, live)
             d = [np.where(live, dk[i], d[i]) for i in range(3)]
+        if env_member and (light == len(lights)).any():
+            live = light == len(lights)
+            dk, _, _ = E._draw(M, env.width, env.height, e_marg, e_cond, g, live)
+            d = [np.where(live, dk[i], d[i]) for i in range(3)]
         n_draws = g.n.copy()
         # the direction the device hands on is its f32 result: the pdf of the yardstick is evaluated for the direction in its own dtype
     else:
         dd = np.asarray(dirs, dtype=np.float32).reshape(-1, 3)
         d = [dd[:, i].astype(T) for i in range(3)]
     diag = dict(cos=np.full(n, np.inf), edge=np.full(n, np.inf), tmin=np.full(n, np.inf))
-    weight = T(T(1.0) / T(len(lights)))
+    weight = T(T(1.0) / T(n_members))
     lsum = np.zeros(n, dtype=T)
     for k, l in enumerate(lights):
         lsum = lsum + (T(p_k[k]) if many else weight) * _light_pdf(M, l, o, d, diag)
+    if env_member:
+        e_pdf, _, _, e_border, e_sin = E._pdf(M, env.width, env.height, e_marg, e_cond, d)
+        lsum = lsum + weight * e_pdf
+        return dict(d=np.stack(d, axis=1), pdf=lsum, light=light, n_draws=n_draws, pick_gap=pick_gap, cos_min=diag["cos"], edge_min=diag["edge"],
+                    tmin_gap=diag["tmin"], env_border=e_border, env_sin_theta=e_sin)
     return dict(d=np.stack(d, axis=1), pdf=lsum, light=light, n_draws=n_draws, pick_gap=pick_gap, cos_min=diag["cos"], edge_min=diag["edge"], tmin_gap=diag["tmin"])
 
 

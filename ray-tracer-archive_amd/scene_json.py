@@ -24,7 +24,9 @@ SceneBuilder calls — nothing here touches the device.
       "lights": ["lamp_rect", "ball"],              # optional: XzRect / Sphere objects (main.rs:669-686)
       "lights_many": false,                         # true (with lights_all_shapes): RT_SCENE_LIGHTS_MANY — area-weighted pick, light tree
       "lights_all_shapes": false,                   # true: RT_SCENE_LIGHTS_ALL_SHAPES — rects of any orientation, triangles, boxes, wrapped members
-      "bvh": {"seed": 1, "builder": "reference"}    # or "sah"
+      "bvh": {"seed": 1, "builder": "reference"},   # or "sah"
+      "environment": {"file": "sky.hdr", "sampled": true, "scale": 1.0}   # optional: an environment map (include/rt_hip.h RtEnvMap) — a Radiance
+                                                    # .hdr beside the scene, or "rgb": [[[r, g, b], ...], ...] rows from the top; JsonScene.env_map
     }
 
 Hittable kinds: sphere [center, radius]; moving_sphere [c0, c1, t0, t1, radius]; xy_rect / xz_rect /
@@ -32,7 +34,7 @@ yz_rect [a0, a1, b0, b1, k]; triangle [v0, v1, v2] (+ "normals": [n0, n1, n2], "
 [child, degrees]; flip_face child; constant_medium [boundary, density] (+ "material": an isotropic);
 list [...]; bvh [...]; obj "file.obj" (triangles of a Wavefront OBJ, in a BVH; "smooth": true shades with the file's vn,
 "textured": true maps textures through its vt — faces that name none stay flat / keep their barycentrics). A scene with such attributes
-hands JsonScene.triangle_attrs to upload(..., triangle_attrs=).
+hands JsonScene.triangle_attrs to upload(..., triangle_attrs=), one with an "environment" hands JsonScene.env_map to upload(..., env_map=).
 Errors raise ValueError with the offending key.
 """
 import json
@@ -122,7 +124,7 @@ def parse_obj_attrs(path):
 
 class JsonScene:
     """desc (RtSceneDesc), camera(aspect) -> RtCamera, triangle_attrs (the RtTriangleAttrs array to hand to upload as triangle_attrs=, or
-    None); keeps the arrays the desc points into alive."""
+    None), env_map (the EnvMap to hand to upload as env_map=, or None); keeps the arrays the desc points into alive."""
 
     def __init__(self, doc, base_dir="."):
         if isinstance(doc, (str, bytes)):
@@ -155,6 +157,33 @@ class JsonScene:
             raise ValueError(f"lights_many: expected true or false, got {lm!r}")
         self.desc = self.b.desc(world, lights, lights_all_shapes=las, lights_many=lm)
         self.triangle_attrs = self.b.triangle_attrs()
+        self.env_map = self._environment(doc.get("environment"))
+
+    def _environment(self, e):
+        """the "environment" entry as an environment.EnvMap, None without one"""
+        if e is None:
+            return None
+        from .environment import EnvMap, load_hdr
+        if not isinstance(e, dict) or ("file" in e) == ("rgb" in e) or set(e) - {"file", "rgb", "sampled", "scale"}:
+            raise ValueError('environment: expected {"file": path} or {"rgb": rows}, with "sampled" and "scale" at most')
+        sampled, scale = e.get("sampled", True), e.get("scale", 1.0)
+        if not isinstance(sampled, bool):
+            raise ValueError(f"environment.sampled: expected true or false, got {sampled!r}")
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)):
+            raise ValueError(f"environment.scale: expected a number, got {scale!r}")
+        if "file" in e:
+            try:
+                rgb = load_hdr(os.path.join(self.base_dir, e["file"]))
+            except (OSError, ValueError) as err:
+                raise ValueError(f"environment.file: {err}")
+        else:
+            try:
+                rgb = np.asarray(e["rgb"], dtype=np.float32)
+            except (TypeError, ValueError):
+                rgb = None
+            if rgb is None or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.size == 0:
+                raise ValueError("environment.rgb: expected rows of [r, g, b] texels, all rows of one length")
+        return EnvMap(rgb, sampled=sampled, scale=float(scale))
 
     # ---- textures / materials ----
     def _colour_texture(self, v, what):
