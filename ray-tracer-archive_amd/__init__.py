@@ -12,9 +12,10 @@ from .api import (Context, Scene, HostScene, RtError, camera_new, lib, lib_path,
                   RAY_DTYPE, RAYHIT_DTYPE, LIGHTQUERY_DTYPE, LIGHTSAMPLE_DTYPE, ray_query_check, ray_query_options, feature_options, features_check,
                   denoise_guide_moments, denoise_guided_moments_check, feature_moment_buffers, feature_moments_check, camera_lists_host,
                   PATHRAY_DTYPE, radiance_options, radiance_check)  # noqa: F401
+from .layout import slot_pixels  # noqa: F401
 from .features import feature_means  # noqa: F401
 from .radiance import path_rays, equirect_rays, standard_error  # noqa: F401
-from .adaptive import Adaptive, select_reference, check_counts, check_adaptive_checkpoint, slot_pixels  # noqa: F401
+from .adaptive import Adaptive, select_reference, check_counts, check_adaptive_checkpoint  # noqa: F401
 from .denoise import nlm_reference, nlm_prepare, nlm_guided_reference, guide_prepare, nlm_guided_moments_reference, guide_moments_prepare  # noqa: F401
 from .progressive import Progressive, check_checkpoint, std_error  # noqa: F401
 from .scene import SceneBuilder  # noqa: F401

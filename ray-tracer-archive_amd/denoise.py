@@ -9,6 +9,10 @@ denoise_frame is the device path behind Progressive.denoised() and Adaptive.deno
 """
 import numpy as np
 
+from . import _abi as A
+from .api import denoise_options
+from .layout import in_place, on_device
+
 DEFAULTS = dict(window_radius=10, patch_radius=3, strength=0.45, alpha=1.0, eps=1e-10)
 MOMENTS_MAX_WINDOW_RADIUS = 8                                                     # RT_DENOISE_GUIDED_MOMENTS_MAX_WINDOW_RADIUS, and what 0 means there
 GUIDE_MOMENTS_DEFAULTS = dict(sigma_albedo=0.01, sigma_normal=0.025, sigma_depth=0.01, variance_strength=64.0)   # the library's (include/rt_hip.h; measured: DESIGN.md, "Denoising")
@@ -244,22 +248,12 @@ def render_guide(ctx, scene, cam, params, feature_samples, sigma_albedo=0.0, sig
     the `guide` of denoise_frame: full-frame planes; a sharded frame's planes are untiled as its sums are, the other shards' pixels 0.
     moments: the pass is Context.render_feature_moments and the guide carries the squared sums and variance_strength too — what
     denoise_frame hands to rt_denoise_guided_moments_device."""
-    import torch
-    from . import _abi as A
     prm = A.RtParams.from_buffer_copy(params)
     prm.samples_per_pixel = int(feature_samples)
     prm.flags &= A.RT_FLAG_TIMING | A.RT_FLAG_SAMPLE_BLOCKS      # (a feature pass refuses the counter and the fused-kernel diagnostics)
     planes = ctx.render_feature_moments(scene, cam, prm) if moments else ctx.render_features(scene, cam, prm)
     if prm.shard_count > 1:
-        from .adaptive import slot_pixels
-        x, y, ok = slot_pixels(prm)
-        full = []
-        for t, ch in zip(planes, (3, 3, 1, 1, 3, 3, 1)):
-            a = t.cpu().numpy().reshape(-1, ch)
-            f = np.zeros((prm.height, prm.width, ch), dtype=a.dtype)
-            f[y[ok], x[ok]] = a[ok]
-            full.append(torch.from_numpy(f.reshape(-1)).to(t.device))
-        planes = tuple(full)
+        planes = tuple(on_device(in_place(prm, t.cpu().numpy(), ch), t.device) for t, ch in zip(planes, (3, 3, 1, 1, 3, 3, 1)))
     guide = dict(feature_samples=int(feature_samples), albedo=planes[0], normal=planes[1], depth=planes[2], hits=planes[3],
                  sigma_albedo=sigma_albedo, sigma_normal=sigma_normal, sigma_depth=sigma_depth)
     if moments:
@@ -272,7 +266,6 @@ def denoise_frame(ctx, rgb_sum, sq_sum, width, height, samples_per_item, samples
     returns them) rt_denoise_guided_device, or rt_denoise_guided_moments_device when the guide carries squared sums; the f32 mean (H, W, 3) on the host, or with rgb8 its write_color bytes (rt_resolve_device
     with one sample per pixel: the library's only tone map)."""
     import torch
-    from .api import denoise_options
     o = denoise_options(samples_per_item=samples_per_item, **opts)
     if guide is None:
         out = ctx.denoise(rgb_sum, sq_sum, width, height, samples=samples, counts=counts, options=o)

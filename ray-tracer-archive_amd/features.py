@@ -3,6 +3,7 @@ filter or an external denoiser starts from, for the camera rays of the frame a P
 import numpy as np
 
 from . import _abi as A
+from .layout import in_place
 
 
 def feature_means(ctx, scene, cam, params, samples, first_sample=0, pool_slots=0):
@@ -10,7 +11,6 @@ def feature_means(ctx, scene, cam, params, samples, first_sample=0, pool_slots=0
     (albedo (H, W, 3), normal (H, W, 3), depth (H, W), hit_fraction (H, W)), f32 means: the albedo over the samples, the normal and the
     depth over the samples that hit (0 where none did), the fraction of the samples that hit. A sharded frame is untiled first: this
     shard's tiles in place, the other shards' pixels 0."""
-    from .adaptive import slot_pixels
     samples = int(samples)
     if samples < 1:
         raise ValueError("a feature pass needs at least one sample per pixel")
@@ -22,13 +22,4 @@ def feature_means(ctx, scene, cam, params, samples, first_sample=0, pool_slots=0
     d, h = depth.cpu().numpy(), hits.cpu().numpy().view(np.uint32).astype(np.float32)
     over_hits = np.where(h > 0, h, np.float32(1))
     planes = (a / np.float32(samples), n / over_hits[:, None], d / over_hits, h / np.float32(samples))
-    H, W = int(prm.height), int(prm.width)
-    if prm.shard_count <= 1:
-        return tuple(p.reshape((H, W, 3) if p.ndim == 2 else (H, W)) for p in planes)
-    x, y, ok = slot_pixels(prm)
-    out = []
-    for p in planes:
-        full = np.zeros((H, W, 3) if p.ndim == 2 else (H, W), dtype=np.float32)
-        full[y[ok], x[ok]] = p[ok]
-        out.append(full)
-    return tuple(out)
+    return tuple(in_place(prm, p, 3 if p.ndim == 2 else 1) for p in planes)

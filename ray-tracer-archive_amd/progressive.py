@@ -17,7 +17,10 @@ import time
 import numpy as np
 
 from . import _abi as A
-from .api import output_floats, pass_check, untile
+from .api import output_floats, pass_check
+from .denoise import denoise_frame, render_guide
+from .features import feature_means
+from .layout import in_place, on_device
 
 CHECKPOINT_VERSION = 1
 # every RtParams field but samples_per_pixel (a pass sets its own) and the padding
@@ -72,43 +75,30 @@ def check_checkpoint(meta, params=None, frame_samples=None, cam=None, fingerprin
         raise ValueError("checkpoint scene differs (scene description fingerprint)")
 
 
+def read_checkpoint(path):
+    """The arrays of an .npz checkpoint as a dict."""
+    with np.load(path) as f:
+        return {k: f[k] for k in f.files}
+
+
 def std_error(rgb_sum, sq_sum, samples, samples_per_item):
     """Standard error of every pixel mean, f64 (include/rt_hip.h): SE = sqrt((Q - S^2/k) / (k (k - 1))) / m with k items of m
-    samples; the variance is clamped at 0 (f32 cancellation in near-constant pixels). inf where fewer than two items are folded."""
+    samples; the variance is clamped at 0 (f32 cancellation in near-constant pixels). samples: the frame's one count, or an (H, W) plane
+    of every pixel's own. inf where fewer than two items are folded."""
     m = int(samples_per_item)
-    k = -(-int(samples) // m)
-    S = np.asarray(rgb_sum, dtype=np.float64)
-    if k < 2:
-        return np.full(S.shape, np.inf)
-    Q = np.asarray(sq_sum, dtype=np.float64)
-    var = np.maximum(Q - S * S / k, 0.0) / (k * (k - 1.0))
-    return np.sqrt(var) / m
+    k = (-(-np.asarray(samples, dtype=np.int64) // m)).astype(np.float64)
+    if k.ndim:
+        k = k[..., None]
+    S, Q = np.asarray(rgb_sum, dtype=np.float64), np.asarray(sq_sum, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        var = np.maximum(Q - S * S / k, 0.0) / (k * (k - 1.0))
+        se = np.sqrt(var) / m
+    return np.where(k >= 2, se, np.inf)
 
 
-def on_device(a, dev):
-    """A host array (an untiled plane of sums or counts) as a flat tensor on `dev`."""
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(dev)
-
-
-def denoise_front(frame, opts, feature_samples, sigma_albedo, sigma_normal, sigma_depth, feature_variance, variance_strength):
-    """The front of Progressive.denoised and Adaptive.denoised: the argument check, the guide of a feature pass of the frame's camera rays
-    (into opts["guide"]), and the frame's sums as full-frame device tensors — its own, or for a sharded frame its untiled ones. Returns
-    (rgb_sum, sq_sum, sharded)."""
-    from .denoise import render_guide
-    if feature_variance and int(feature_samples) < 2:
-        raise ValueError("feature_variance needs feature_samples >= 2")
-    p, dev = frame.params, frame._rgb.device
-    if feature_samples:
-        opts["guide"] = render_guide(frame.ctx, frame.scene, frame.cam, p, feature_samples, sigma_albedo, sigma_normal, sigma_depth, moments=bool(feature_variance),
-                                     variance_strength=variance_strength)
-    if p.shard_count <= 1:
-        return frame._rgb, frame._sq, False
-    return on_device(frame.rgb_sum(), dev), on_device(frame.sq_sum(), dev), True
-
-
-class Progressive:
-    """A frame rendered in passes into device accumulators owned by this object (torch tensors on the context's GPU)."""
+class Frame:
+    """What Progressive and Adaptive share: the frame's description, its device accumulators (torch tensors on the context's GPU, owned
+    by this object) and what follows from the sums alone. A subclass renders the passes (step) and knows the samples every pixel holds."""
 
     def __init__(self, ctx, scene, cam, params, frame_samples, sq_sum=True):
         import torch
@@ -118,12 +108,88 @@ class Progressive:
         self.params.samples_per_pixel = self.frame_samples
         self.samples_per_item = pass_check(self.params, 0, self.frame_samples)     # validates the frame; m of every pass
         self.fingerprint = scene.fingerprint
-        n = output_floats(self.params)
+        self.slots = output_floats(self.params) // 3
         dev = torch.device("cuda", ctx.device_id)
-        self._rgb = torch.zeros(n, dtype=torch.float32, device=dev)
-        self._sq = torch.zeros(n, dtype=torch.float32, device=dev) if sq_sum else None
-        self.samples_done = 0
+        self._rgb = torch.zeros(3 * self.slots, dtype=torch.float32, device=dev)
+        self._sq = torch.zeros(3 * self.slots, dtype=torch.float32, device=dev) if sq_sum else None
+        self.samples_done = 0            # first_sample of the next pass
         self.last_stats = None
+
+    def _passes(self, pass_samples, until, seconds, callback, good_enough=None):
+        """The loop of run: passes of `pass_samples` up to `until` samples (None: the whole frame). After every pass, in this order: a step
+        that rendered nothing, a callback(self, stats) that returns False, `seconds` of wall time and good_enough() end it."""
+        target = self.frame_samples if until is None else min(int(until), self.frame_samples)
+        t0 = time.monotonic()
+        while self.samples_done < target:
+            st = self.step(min(int(pass_samples), target - self.samples_done))
+            if st is None:
+                break
+            if callback is not None and callback(self, st) is False:
+                break
+            if seconds is not None and time.monotonic() - t0 >= seconds:
+                break
+            if good_enough is not None and good_enough():
+                break
+        return self.samples_done
+
+    def rgb_sum(self):
+        """Per-pixel RGB sums over the samples rendered, f32 (H, W, 3) (a sharded frame: this shard's tiles in place, 0 elsewhere)."""
+        return in_place(self.params, self._rgb.cpu().numpy(), 3)
+
+    def sq_sum(self):
+        """Per-pixel sums of the squared work-item sums, f32 (H, W, 3), laid out as rgb_sum."""
+        if self._sq is None:
+            raise ValueError("this frame keeps no squared sums (sq_sum=False)")
+        return in_place(self.params, self._sq.cpu().numpy(), 3)
+
+    def denoised(self, rgb8=False, feature_samples=0, sigma_albedo=0.0, sigma_normal=0.0, sigma_depth=0.0, feature_variance=False, variance_strength=0.0, **opts):
+        """The frame so far filtered by rt_denoise_device (non-local means over the sample variance, with the samples every pixel holds;
+        opts: denoise_options fields, the frame's samples per work item is filled in): the mean radiance, f32 (H, W, 3), or its
+        write_color bytes with rgb8=True. A pixel below two work items is copied through. A sharded frame is untiled first: the other
+        shards' pixels hold no sums and come out as they are, 0.
+        feature_samples = N > 0: a feature pass of N samples per pixel is rendered (Context.render_features) and the weights are joined
+        with it (rt_denoise_guided_device; the sigmas: RtDenoiseGuide, 0 = the default). 0: the plain filter.
+        feature_variance=True with feature_samples = N >= 2: the pass keeps the features' second moments (Context.render_feature_moments)
+        and the filter is rt_denoise_guided_moments_device (sigmas and variance_strength: RtDenoiseGuideMoments, 0 = the default;
+        window_radius 0 = 8, at most 8)."""
+        samples, counts = self._denoise_counts()
+        if self._sq is None:
+            raise ValueError("this frame keeps no squared sums (sq_sum=False)")
+        if feature_variance and int(feature_samples) < 2:
+            raise ValueError("feature_variance needs feature_samples >= 2")
+        p, dev = self.params, self._rgb.device
+        if feature_samples:
+            opts["guide"] = render_guide(self.ctx, self.scene, self.cam, p, feature_samples, sigma_albedo, sigma_normal, sigma_depth, moments=bool(feature_variance),
+                                         variance_strength=variance_strength)
+        rgb, sq = (self._rgb, self._sq) if p.shard_count <= 1 else (on_device(self.rgb_sum(), dev), on_device(self.sq_sum(), dev))
+        return denoise_frame(self.ctx, rgb, sq, p.width, p.height, self.samples_per_item, samples=samples, counts=counts, rgb8=rgb8, **opts)
+
+    def features(self, samples):
+        """First-hit features of this frame's camera rays (rt_render_features_device), from a pass of its own of `samples` samples per pixel
+        — uniform, independent of the radiance samples held: (albedo (H, W, 3), normal (H, W, 3), depth (H, W), hit fraction (H, W)), f32
+        means; normal and depth over the samples that hit. A sharded frame is untiled first."""
+        return feature_means(self.ctx, self.scene, self.cam, self.params, samples)
+
+    def _checkpoint(self):
+        """What both kinds of checkpoint hold: samples_done, frame_samples, the RtParams fields, the camera, the scene fingerprint, the sums."""
+        z = dict(samples_done=np.int64(self.samples_done), frame_samples=np.int64(self.frame_samples), params=params_array(self.params),
+                 camera=camera_array(self.cam), fingerprint=np.array(self.fingerprint), rgb_sum=self._rgb.cpu().numpy())
+        if self._sq is not None:
+            z["sq_sum"] = self._sq.cpu().numpy()
+        return z
+
+    def _restore(self, z):
+        """The sums and samples_done of a checked checkpoint into this frame; the caller waits for the copies."""
+        import torch
+        self._rgb.copy_(torch.from_numpy(z["rgb_sum"]))
+        if self._sq is not None:
+            self._sq.copy_(torch.from_numpy(z["sq_sum"]))
+        self.samples_done = int(z["samples_done"])
+
+
+class Progressive(Frame):
+    """A frame rendered in passes into device accumulators owned by this object (torch tensors on the context's GPU); sq_sum=False keeps
+    no squared sums, and with them no standard error and no denoised()."""
 
     @property
     def done(self):
@@ -145,38 +211,7 @@ class Progressive:
         """Passes of `pass_samples` until `until` samples per pixel (default: the whole frame), or `seconds` of wall time, or a relative
         error (relative_error()) of at most `rel_se`, whichever comes first. callback(self, stats) is called after every pass; returning
         False from it stops the loop. Returns samples_done."""
-        target = self.frame_samples if until is None else min(int(until), self.frame_samples)
-        t0 = time.monotonic()
-        while self.samples_done < target:
-            st = self.step(min(int(pass_samples), target - self.samples_done))
-            if callback is not None and callback(self, st) is False:
-                break
-            if seconds is not None and time.monotonic() - t0 >= seconds:
-                break
-            if rel_se is not None and self.relative_error() <= rel_se:
-                break
-        return self.samples_done
-
-    def _untiled(self, flat):
-        p = self.params
-        if p.shard_count <= 1:
-            return flat.reshape(p.height, p.width, 3)
-        # this shard's tiles in place, the other shards' pixels 0
-        q = A.RtParams.from_buffer_copy(p)
-        q.shard_index = 0
-        per = output_floats(q)
-        g = np.zeros(per * p.shard_count, dtype=np.float32)
-        g[p.shard_index * per:p.shard_index * per + flat.size] = flat
-        return untile(p, g)
-
-    def rgb_sum(self):
-        """Per-pixel RGB sums over samples_done samples, f32 (H, W, 3) (a sharded frame: this shard's tiles in place, 0 elsewhere)."""
-        return self._untiled(self._rgb.cpu().numpy())
-
-    def sq_sum(self):
-        if self._sq is None:
-            raise ValueError("this frame keeps no squared sums (sq_sum=False)")
-        return self._untiled(self._sq.cpu().numpy())
+        return self._passes(pass_samples, until, seconds, callback, None if rel_se is None else lambda: self.relative_error() <= rel_se)
 
     def std_error(self):
         """Standard error of every pixel's mean radiance, f64 (H, W, 3)."""
@@ -203,61 +238,32 @@ class Progressive:
         self.ctx.resolve_device(src.data_ptr(), p.width, p.height, self.samples_done, out.data_ptr())
         return out.cpu().numpy().reshape(p.height, p.width, 3)
 
-    def denoised(self, rgb8=False, feature_samples=0, sigma_albedo=0.0, sigma_normal=0.0, sigma_depth=0.0, feature_variance=False, variance_strength=0.0, **opts):
-        """The frame so far filtered by rt_denoise_device (non-local means over the sample variance; opts: denoise_options fields, the
-        frame's samples per work item is filled in): the mean radiance, f32 (H, W, 3), or its write_color bytes with rgb8=True. A
-        sharded frame is untiled first: the other shards' pixels hold no sums and come out as they are, 0.
-        feature_samples = N > 0: a feature pass of N samples per pixel is rendered (Context.render_features) and the weights are joined
-        with it (rt_denoise_guided_device; the sigmas: RtDenoiseGuide, 0 = the default). 0: the plain filter.
-        feature_variance=True with feature_samples = N >= 2: the pass keeps the features' second moments (Context.render_feature_moments)
-        and the filter is rt_denoise_guided_moments_device (sigmas and variance_strength: RtDenoiseGuideMoments, 0 = the default;
-        window_radius 0 = 8, at most 8)."""
-        from .denoise import denoise_frame
+    def _denoise_counts(self):
+        """(samples, counts) of denoise_frame: samples_done for every pixel; a sharded frame: a plane with it at this shard's pixels, as
+        the other shards' pixels hold no sample and are nobody's neighbours."""
         if self.samples_done == 0:
             raise ValueError("no samples rendered yet")
-        if self._sq is None:
-            raise ValueError("this frame keeps no squared sums (sq_sum=False)")
-        p = self.params
-        rgb, sq, sharded = denoise_front(self, opts, feature_samples, sigma_albedo, sigma_normal, sigma_depth, feature_variance, variance_strength)
-        if not sharded:
-            return denoise_frame(self.ctx, rgb, sq, p.width, p.height, self.samples_per_item, samples=self.samples_done, rgb8=rgb8, **opts)
-        from .adaptive import slot_pixels
-        x, y, ok = slot_pixels(p)
-        cnt = np.zeros((p.height, p.width), dtype=np.int32)          # the other shards' pixels hold no sample: nobody's neighbours
-        cnt[y[ok], x[ok]] = self.samples_done
-        return denoise_frame(self.ctx, rgb, sq, p.width, p.height, self.samples_per_item, counts=on_device(cnt, rgb.device), rgb8=rgb8, **opts)
-
-    def features(self, samples):
-        """First-hit features of this frame's camera rays (rt_render_features_device), from a pass of its own of `samples` samples per pixel
-        — uniform, independent of the radiance samples held: (albedo (H, W, 3), normal (H, W, 3), depth (H, W), hit fraction (H, W)), f32
-        means; normal and depth over the samples that hit. A sharded frame is untiled first."""
-        from .features import feature_means
-        return feature_means(self.ctx, self.scene, self.cam, self.params, samples)
+        if self.params.shard_count <= 1:
+            return self.samples_done, None
+        return 0, on_device(in_place(self.params, np.full(self.slots, self.samples_done, dtype=np.int32), 1), self._rgb.device)
 
     def save(self, path):
         """An .npz checkpoint: the sums, samples_done, frame_samples, the RtParams fields, the camera and the scene fingerprint."""
-        z = dict(version=np.int64(CHECKPOINT_VERSION), samples_done=np.int64(self.samples_done), frame_samples=np.int64(self.frame_samples),
-                 params=params_array(self.params), camera=camera_array(self.cam), fingerprint=np.array(self.fingerprint),
-                 rgb_sum=self._rgb.cpu().numpy())
-        if self._sq is not None:
-            z["sq_sum"] = self._sq.cpu().numpy()
-        np.savez(path, **z)
+        np.savez(path, version=np.int64(CHECKPOINT_VERSION), **self._checkpoint())
 
     @classmethod
     def load(cls, path, ctx, scene, cam, params=None):
         """Resumes a checkpoint on `ctx` with `scene` and `cam` (and, if given, `params`). ValueError when the camera, the scene
         description, the params or the buffers do not match the checkpoint's."""
         import torch
-        with np.load(path) as f:
-            z = {k: f[k] for k in f.files}
+        z = read_checkpoint(path)
         check_checkpoint(z, params=params, cam=cam, fingerprint=scene.fingerprint)
         prm = params_from_array(z["params"], int(z["frame_samples"]))
         prog = cls(ctx, scene, cam, prm, int(z["frame_samples"]), sq_sum="sq_sum" in z)
         if z["rgb_sum"].shape != tuple(prog._rgb.shape):
             raise ValueError("checkpoint sums have another size than the frame")
-        prog._rgb.copy_(torch.from_numpy(z["rgb_sum"]))
-        if prog._sq is not None:
-            prog._sq.copy_(torch.from_numpy(z["sq_sum"]))
+        prog._restore(z)
         torch.cuda.synchronize(prog._rgb.device)
-        prog.samples_done = int(z["samples_done"])
         return prog
+
+

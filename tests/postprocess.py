@@ -104,9 +104,16 @@ def size_id(kw):
 
 def layout(kw):
     """slot_pixels of make_params(**kw) without the library: (slots, in-image mask)."""
+    x, _, ok = layout_pixels(kw)
+    return x.size, ok
+
+
+def layout_pixels(kw):
+    """slot_pixels of make_params(**kw) without the library: (x, y, in-image mask) of every slot."""
     W, H, sc = kw["width"], kw["height"], kw.get("shard_count", 1)
     if sc <= 1:
-        return W * H, np.ones(W * H, dtype=bool)
+        s = np.arange(W * H, dtype=np.int64)
+        return s % W, s // W, np.ones(W * H, dtype=bool)
     ts, si = kw["tile_size"], kw["shard_index"]
     tiles_x, tiles_y = -(-W // ts), -(-H // ts)
     n_tiles = tiles_x * tiles_y
@@ -115,7 +122,7 @@ def layout(kw):
     lt, r = s // (ts * ts), s % (ts * ts)
     tile = si + lt * sc
     x, y = (tile % tiles_x) * ts + r % ts, (tile // tiles_x) * ts + r // ts
-    return s.size, (x < W) & (y < H)
+    return x, y, (x < W) & (y < H)
 
 
 def pattern_mask(pattern, valid, rng):

@@ -162,6 +162,39 @@ def test_host_untile_is_the_slot_map(pkg, w, h, tile, world):
         assert pkg.output_floats(PP.shard_params(pkg, w, h, tile, world, 1)) == pkg.output_floats(PP.shard_params(pkg, w, h, tile, world, 2)) == 0
 
 
+@pytest.mark.parametrize("w,h,tile,world", [(70, 40, 32, 2), (40, 40, 16, 3), (130, 100, 64, 3), (17, 9, 8, 4), (16, 16, 16, 3)])
+def test_in_place_is_the_untile_of_one_shard(pkg, w, h, tile, world):
+    """layout.in_place against the path it replaced — the shard's buffer at its offset in a zeroed gathered buffer, then rt_untile — bit
+    for bit, and its one-channel form against this directory's own restatement of the layout. Every slot holds a non-zero value, the
+    clipped slots of edge tiles too, so a scatter that does not drop them shows."""
+    from ray_tracer_archive_amd.layout import in_place
+    rng = np.random.default_rng(1000 * w + h)
+    per_shard = pkg.output_floats(PP.shard_params(pkg, w, h, tile, world, 0))
+    sizes = []
+    for r in range(world):
+        prm = PP.shard_params(pkg, w, h, tile, world, r)
+        x, y, ok = PP.layout_pixels(dict(width=w, height=h, tile_size=tile, shard_index=r, shard_count=world))
+        sizes.append(x.size)
+        assert pkg.output_floats(prm) == 3 * x.size <= per_shard
+        flat = rng.uniform(0.5, 2.0, 3 * x.size).astype(np.float32)
+        gathered = np.zeros(world * per_shard, dtype=np.float32)
+        gathered[r * per_shard:r * per_shard + flat.size] = flat
+        got = in_place(prm, flat, 3)
+        assert got.dtype == np.float32 and got.shape == (h, w, 3)
+        assert np.array_equal(got.view(np.uint32), pkg.untile(prm, gathered).view(np.uint32)), r
+        assert int((got != 0).all(axis=2).sum()) == int(ok.sum())
+        counts = rng.integers(1, 2 ** 32, x.size, dtype=np.uint32)
+        want = np.zeros((h, w), dtype=np.uint32)
+        want[y[ok], x[ok]] = counts[ok]
+        got = in_place(prm, counts, 1)
+        assert got.dtype == np.uint32 and np.array_equal(got, want), r
+    assert (w, h, tile, world) != (16, 16, 16, 3) or sizes == [256, 0, 0]
+    assert (w, h, tile, world) != (17, 9, 8, 4) or sizes == [128, 128, 64, 64]          # 3 x 2 tiles, the right column and the bottom row clipped
+    whole = pkg.make_params(w, h, 1)                          # an unsharded frame: a reshape
+    flat = np.arange(3 * w * h, dtype=np.float32)
+    assert np.array_equal(in_place(whole, flat, 3), flat.reshape(h, w, 3)) and np.array_equal(in_place(whole, flat[:w * h], 1), flat[:w * h].reshape(h, w))
+
+
 # ---- D. pixel lists -------------------------------------------------------------------------------------------------------------------------
 def test_list_cases_put_their_faults_on_the_workgroup_boundary():
     slots = PP.LIST_FRAME[0] * PP.LIST_FRAME[1]
