@@ -147,6 +147,25 @@ impl RtUploadOptionsEnv {
         RtUploadOptionsEnv { base: RtUploadOptions { struct_bytes: std::mem::size_of::<RtUploadOptionsEnv>() as u32, ..Default::default() }, env_map }
     }
 }
+// a normal map: tangent-space shading normals on the triangles of one material (RtNormalMap.flags); the texels are an RtImage of the desc
+pub const RT_NMAP_FLIP_GREEN: u32 = 1;
+pub const RT_FEATURE_NORMAL_MAP: u32 = 2048;   // RtCompileInfo.features: a device triangle carries a map
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtNormalMap {
+    pub material: i32, pub image: i32, pub strength: f32, pub flags: u32,
+}
+// ... grown once more: hand `&x.base.base` (struct_bytes = size_of::<RtUploadOptionsMaps>() = 64); `maps` must outlive the upload
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct RtUploadOptionsMaps {
+    pub base: RtUploadOptionsEnv, pub normal_maps: *const RtNormalMap, pub n_normal_maps: u64,
+}
+impl RtUploadOptionsMaps {
+    pub fn new(env_map: *const RtEnvMap, maps: &[RtNormalMap]) -> Self {
+        let mut base = RtUploadOptionsEnv::new(env_map);
+        base.base.struct_bytes = std::mem::size_of::<RtUploadOptionsMaps>() as u32;
+        RtUploadOptionsMaps { base, normal_maps: if maps.is_empty() { std::ptr::null() } else { maps.as_ptr() }, n_normal_maps: maps.len() as u64 }
+    }
+}
 impl Default for RtUploadOptions {
     fn default() -> Self {
         RtUploadOptions { struct_bytes: std::mem::size_of::<RtUploadOptions>() as u32, layout_flags: 0, lds_top_records: 0, octant_axes: 0, leaf_collapse: 0,

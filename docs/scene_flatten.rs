@@ -109,6 +109,13 @@ pub fn env_map(rgb: &[f32], width: u32, height: u32, sampled: bool, scale: f32) 
                rgb: rgb.as_ptr(), scale, _pad: 0 }
 }
 
+/// A normal map for `RtUploadOptionsMaps.normal_maps` (the reference has none): the tangent-space texels are image `image` of the builder
+/// (8-bit RGB, pushed like an `ImageTexture`'s), bound to material `material`, whose triangles it then shades. `strength` scales the
+/// tangent-plane components; `flip_green` for maps authored with green pointing down.
+pub fn normal_map(material: i32, image: i32, strength: f32, flip_green: bool) -> RtNormalMap {
+    RtNormalMap { material, image, strength, flags: if flip_green { RT_NMAP_FLIP_GREEN } else { 0 } }
+}
+
 /// What `Hittable`, `Material`, `Texture` gain (written as separate traits here so that this file stands alone; in the crate the method
 /// is added to the existing traits and `Arc<dyn Hittable>` is used where `Arc<dyn Flatten>` appears).
 pub trait Flatten { fn flatten(&self, b: &mut SceneBuilder) -> i32; }

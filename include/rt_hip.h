@@ -407,6 +407,51 @@ typedef struct RtUploadOptionsEnv {
     RtUploadOptions base;                    /* base.struct_bytes = sizeof(RtUploadOptionsEnv) */
     const RtEnvMap* env_map;                 /* an environment map, see RtEnvMap above; NULL = none */
 } RtUploadOptionsEnv;
+
+/* ---- normal maps: tangent-space shading normals on triangle meshes ---------------------------------------------------------------------------
+ * A map is bound to a MATERIAL of the desc; its texels are an RtImage of the desc (8-bit RGB). The binding travels beside the desc like the
+ * triangle attributes and the environment map, in RtUploadOptionsMaps, the options record grown once more at its end (rt_scene_upload_ex,
+ * rt_scene_upload_multi_ex, rt_scene_compile_info_ex, rt_scene_compile_dump_ex). The pointers are the caller's; nothing is retained.
+ * The rules apply on a hit of an RT_HIT_TRIANGLE whose material has a map, in f32 on the device, AFTER the RT_TRI_NORMALS and RT_TRI_UVS steps
+ * above. N is the unit normal those steps leave (interpolated, or the facet's unit(cross(e1, e2))); (u, v) the texture coordinates they leave
+ * (attributes, or the barycentrics); uv_k the vertices' coordinates (the attributes, or (0,0), (1,0), (0,1) without RT_TRI_UVS: a triangle
+ * without attributes is mapped too).
+ *   1 TEXEL   the image texture's own rule (texture.rs:117-140, as the environment map's LOOKUP): u, v clamped to [0, 1], v := 1 - v,
+ *             i = (uint)(u W), j = (uint)(v H), clamped to W - 1, H - 1; c = rgb8[(j W + i) 3 ..]. The nearest texel, no filtering: a map
+ *             lines up texel for texel with an albedo image on the same mesh.
+ *   2 DECODE  m = c (2 / 255) - 1 per channel; x = strength m.r, y = strength m.g (negated under RT_NMAP_FLIP_GREEN), z = m.b.
+ *   3 FRAME   e1 = v1 - v0, e2 = v2 - v0, (du1, dv1) = uv1 - uv0, (du2, dv2) = uv2 - uv0, det = du1 dv2 - du2 dv1;
+ *             T = dv2 e1 - dv1 e2, B = du1 e2 - du2 e1, both negated when det < 0; t = unit(T - N (N.T)); b = +-cross(N, t) with the sign
+ *             that makes dot(b, B) >= 0. Red is +u; green is +v, which is towards row 0 of the image.
+ *   4 RESULT  ns = unit(x t + y b + z N) takes the place of N and nothing downstream changes: front_face = dot(d, ns) < 0, normal = +-ns,
+ *             then the Translate / RotateY / FlipFace replay and the materials. ns lives in the triangle's own space, as vertex normals do.
+ *   5 FALLBACKS  N stays when det is 0 or not finite, when the squared length of T - N (N.T) is not a positive normal f32, or when the
+ *             squared length of x t + y b + z N is not a positive normal f32.
+ * UNCHANGED: t, p, hit / miss, the closed edges, occlusion queries, the primitive a scattered ray leaves and every light's pdf_value /
+ * random stay geometric; the documented limit of RT_TRI_NORMALS applies (a direction scattered about ns may point below the facet).
+ * SERVED BY renders in every kernel form (wavefront, drain tail, fused, passes, pixel lists), radiance queries, rt_trace_rays* (n,
+ * FRONT_FACE) and rt_render_features* / rt_render_feature_moments* (normal). A triangle the graph reaches under several wrappers is mapped
+ * in every copy. A scene with a map runs the all-features kernels (RtCompileInfo.features has 32, and 2048 when a device triangle is
+ * mapped; n_tri_attrs counts every device triangle that carries a record, mapped ones without attributes included).
+ * LIMITS: the nearest texel with clamped u, v; per-triangle tangents, no per-vertex tangents; triangles only.
+ * REFUSED with RT_ERR_INVALID, the reason in rt_last_error, nothing uploaded: n_normal_maps > 0 with a NULL pointer; a material id out of
+ * range; a material listed twice; an image id out of range, or an image with NULL data or a zero dimension; a strength that is not finite
+ * or is negative; an unknown flag; a material of kind RT_MAT_DIFFUSE_LIGHT or RT_MAT_ISOTROPIC; a mapped material used by a primitive that
+ * is not a triangle (sphere, moving sphere, rect, box, medium), for now — by any such record of RtSceneDesc.hittables, whether the world
+ * reaches it or not: the rule is checked on the desc, before the graph is walked. A mapped material that no record uses is legal and changes
+ * nothing; a scene uploaded without maps is uploaded byte for byte as before. */
+enum { RT_NMAP_FLIP_GREEN = 1u };        /* maps authored with green pointing down (-v) */
+typedef struct RtNormalMap {             /* 16 B */
+    int32_t  material;                   /* id of an RtMaterial of the desc */
+    int32_t  image;                      /* id of an RtImage of the desc */
+    float    strength;                   /* scales the tangent-plane components; finite, >= 0 */
+    uint32_t flags;                      /* RT_NMAP_*; an unknown bit is RT_ERR_INVALID */
+} RtNormalMap;
+typedef struct RtUploadOptionsMaps {
+    RtUploadOptionsEnv base;             /* base.base.struct_bytes = sizeof(RtUploadOptionsMaps) */
+    const RtNormalMap* normal_maps;      /* read only when struct_bytes covers both fields (callers of the 24-, 40- and 48-byte records keep working) */
+    uint64_t n_normal_maps;              /* records in normal_maps; > 0 with a NULL pointer is RT_ERR_INVALID */
+} RtUploadOptionsMaps;
 int rt_scene_upload_ex(RtCtx* ctx, const RtSceneDesc* desc, const RtUploadOptions* options /* NULL = defaults */, RtScene** out_scene);
 
 /* Number of floats rt_render writes: 3 * pixels covered by this shard's tiles. For

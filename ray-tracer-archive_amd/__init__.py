@@ -20,6 +20,6 @@ from .denoise import nlm_reference, nlm_prepare, nlm_guided_reference, guide_pre
 from .progressive import Progressive, check_checkpoint, std_error  # noqa: F401
 from .scene import SceneBuilder  # noqa: F401
 from .scene_json import JsonScene, load_scene, parse_obj, parse_obj_attrs  # noqa: F401
-from .mesh import icosphere, interpolate_reference, sphere_uv  # noqa: F401
+from .mesh import icosphere, interpolate_reference, sphere_uv, normal_map_reference, height_to_normal_map, texel_of  # noqa: F401
 from .environment import EnvMap, env_reference, env_tables, load_hdr  # noqa: F401
 from .lights import light_reference, light_tree, light_weights, solid_angle_triangle  # noqa: F401

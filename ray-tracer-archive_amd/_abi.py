@@ -30,6 +30,8 @@ RT_FEATURE_TRI_ATTR = 128      # RtCompileInfo.features: a triangle carries attr
 RT_FEATURE_LIGHTS_EXT = 256    # RtCompileInfo.features: the lights table holds extended records (csrc/kernels.h F_LIGHTS_EXT)
 RT_FEATURE_LIGHTS_TREE = 512   # RtCompileInfo.features: the lights table carries the light tree (csrc/kernels.h F_LIGHTS_TREE)
 RT_FEATURE_ENV = 1024          # RtCompileInfo.features: the upload options carry an environment map (csrc/kernels.h F_ENV)
+RT_FEATURE_NORMAL_MAP = 2048   # RtCompileInfo.features: a device triangle carries a normal map (csrc/kernels.h F_NORMAL_MAP)
+RT_NMAP_FLIP_GREEN = 1          # RtNormalMap.flags
 RT_ENV_SAMPLED = 1              # RtEnvMap.flags
 RT_SCENE_LIGHTS_ALL_SHAPES = 1  # RtSceneDesc.scene_flags
 RT_SCENE_LIGHTS_MANY = 4        # RtSceneDesc.scene_flags: area-weighted pick and the light tree; needs RT_SCENE_LIGHTS_ALL_SHAPES
@@ -135,6 +137,15 @@ class RtUploadOptions(C.Structure):
 class RtUploadOptionsEnv(C.Structure):
     """the options record grown at its end: pass `base` (with base.struct_bytes = sizeof(RtUploadOptionsEnv)) where RtUploadOptions is taken"""
     _fields_ = [("base", RtUploadOptions), ("env_map", C.POINTER(RtEnvMap))]
+
+
+class RtNormalMap(C.Structure):
+    _fields_ = [("material", C.c_int32), ("image", C.c_int32), ("strength", C.c_float), ("flags", C.c_uint32)]
+
+
+class RtUploadOptionsMaps(C.Structure):
+    """... grown once more: pass `base.base` (with base.base.struct_bytes = sizeof(RtUploadOptionsMaps)) where RtUploadOptions is taken"""
+    _fields_ = [("base", RtUploadOptionsEnv), ("normal_maps", C.POINTER(RtNormalMap)), ("n_normal_maps", C.c_uint64)]
 
 
 class RtPassOptions(C.Structure):

@@ -361,20 +361,33 @@ class HostScene:
             pass
 
 
-def upload_options(layout_flags=0, lds_top_records=0, octant_axes=0, leaf_collapse=0, list_park_cost=0.0, triangle_attrs=None, env_map=None):
+def upload_options(layout_flags=0, lds_top_records=0, octant_axes=0, leaf_collapse=0, list_park_cost=0.0, triangle_attrs=None, env_map=None, normal_maps=None):
     """RtUploadOptions (include/rt_hip.h): how the scene is laid out on the device, never what it looks like — and the per-vertex normals /
     texture coordinates of its triangles: triangle_attrs = a ctypes array or a sequence of RtTriangleAttrs (SceneBuilder.triangle_attrs()) —
     and its environment map: env_map = an environment.EnvMap; the record returned is then the first 40 bytes of an RtUploadOptionsEnv, with
-    struct_bytes = its 48."""
-    if env_map is not None:                                 # the grown record: its first 40 bytes are the options, and those are what is handed on
+    struct_bytes = its 48 — and the normal maps of its materials: normal_maps = a ctypes array or a sequence of RtNormalMap
+    (SceneBuilder.normal_maps(); an empty sequence is a list of none); the record is then the first 40 bytes of an RtUploadOptionsMaps, with
+    struct_bytes = its 64."""
+    if normal_maps is not None:                             # the record grown twice: its first 40 bytes are the options, and those are what is handed on
+        big = A.RtUploadOptionsMaps()
+        opt = big.base.base                                 # (a view into big, which it keeps alive)
+        opt.struct_bytes = C.sizeof(A.RtUploadOptionsMaps)
+        if len(normal_maps):
+            maps = normal_maps if isinstance(normal_maps, C.Array) else (A.RtNormalMap * len(normal_maps))(*normal_maps)
+            big.normal_maps, big.n_normal_maps = maps, len(maps)
+            opt._keep_maps = maps                           # the record points into it
+        if env_map is not None:
+            big.base.env_map = C.pointer(env_map.record)
+            opt._keep_env = env_map                         # the record points into its texels
+    elif env_map is not None:                               # the grown record, likewise
         ext = A.RtUploadOptionsEnv()
         ext.env_map = C.pointer(env_map.record)
-        opt = ext.base                                      # (a view into ext, which it keeps alive)
-        opt.struct_bytes, opt.layout_flags, opt.lds_top_records, opt.octant_axes, opt.leaf_collapse, opt.list_park_cost = (
-            C.sizeof(A.RtUploadOptionsEnv), layout_flags, lds_top_records, octant_axes, leaf_collapse, list_park_cost)
-        opt._keep_env = env_map                             # the record points into its texels
+        opt = ext.base
+        opt.struct_bytes = C.sizeof(A.RtUploadOptionsEnv)
+        opt._keep_env = env_map
     else:
-        opt = A.RtUploadOptions(C.sizeof(A.RtUploadOptions), layout_flags, lds_top_records, octant_axes, leaf_collapse, list_park_cost)
+        opt = A.RtUploadOptions(C.sizeof(A.RtUploadOptions))
+    opt.layout_flags, opt.lds_top_records, opt.octant_axes, opt.leaf_collapse, opt.list_park_cost = layout_flags, lds_top_records, octant_axes, leaf_collapse, list_park_cost
     if triangle_attrs is not None and len(triangle_attrs):
         arr = triangle_attrs if isinstance(triangle_attrs, C.Array) else (A.RtTriangleAttrs * len(triangle_attrs))(*triangle_attrs)
         opt.triangle_attrs, opt.n_triangle_attrs = arr, len(arr)
@@ -389,11 +402,12 @@ def runtime_libraries():
     return [p for p in buf.value.decode().split("\n") if p], code == A.RT_OK
 
 
-def scene_fingerprint(desc, triangle_attrs=None, env_map=None):
+def scene_fingerprint(desc, triangle_attrs=None, env_map=None, normal_maps=None):
     """sha256 (hex) over the arrays and scalars of an RtSceneDesc — and over the RtTriangleAttrs records that travel beside it, if any sets a
-    flag, and over the environment map (an environment.EnvMap), if there is one: what a progressive checkpoint records of the scene it was
-    rendered from. A scene without attributes and without a map has the print it always had; of a record only what its flags make the
-    library read counts, in the order of the hittable ids."""
+    flag, over the environment map (an environment.EnvMap), if there is one, and over the RtNormalMap records, if there are any (their
+    images are the desc's, so covered already): what a progressive checkpoint records of the scene it was rendered from. A scene without
+    attributes and without maps has the print it always had; of a record only what its flags make the library read counts, in the order of
+    the hittable ids (normal maps: of the material ids)."""
     import hashlib
     h = hashlib.sha256()
 
@@ -429,6 +443,11 @@ def scene_fingerprint(desc, triangle_attrs=None, env_map=None):
     if env_map is not None:
         r = env_map.record
         h.update(b"env_map" + np.array([r.flags, r.width, r.height], dtype=np.uint32).tobytes() + np.float32(r.scale).tobytes() + env_map.rgb.tobytes())
+    maps = sorted(normal_maps if normal_maps is not None else (), key=lambda m: m.material)
+    if maps:
+        h.update(b"normal_maps" + len(maps).to_bytes(8, "little"))
+        for m in maps:
+            h.update(np.array([m.material, m.image, m.flags], dtype=np.int64).tobytes() + np.float32(m.strength).tobytes())
     return h.hexdigest()
 
 
@@ -441,7 +460,8 @@ class Scene:
         env = getattr(options, "_keep_env", None) if options is not None and options.struct_bytes >= C.sizeof(A.RtUploadOptionsEnv) else None
         if env is not None and not getattr(options, "_b_base_").env_map:
             env = None                                       # (the field was cleared after upload_options set it)
-        self.fingerprint = scene_fingerprint(desc, attrs, env)   # (progressive checkpoints: the scene a frame's sums belong to)
+        maps = getattr(options, "_keep_maps", None) if options is not None and options.struct_bytes >= C.sizeof(A.RtUploadOptionsMaps) else None
+        self.fingerprint = scene_fingerprint(desc, attrs, env, maps)   # (progressive checkpoints: the scene a frame's sums belong to)
 
     def close(self):
         if self._h and self.ctx._h:
@@ -465,7 +485,7 @@ class Context:
 
     def upload(self, desc, layout_flags=0, **more):
         """rt_scene_upload_ex; layout_flags = RT_LAYOUT_* (A.RT_LAYOUT_REFERENCE_COUNTERS: the layout whose test counts are the reference's);
-        triangle_attrs= (in `more`): RtTriangleAttrs records, env_map= an environment.EnvMap, see upload_options."""
+        triangle_attrs= (in `more`): RtTriangleAttrs records, env_map= an environment.EnvMap, normal_maps= RtNormalMap records, see upload_options."""
         return Scene(self, desc, upload_options(layout_flags, **more) if (layout_flags or more) else None)
 
     def fail_next_renders(self, n):

@@ -126,6 +126,10 @@ inline uint32_t make_mat_b(uint32_t kind, uint32_t tex) { return kind | (tex << 
 enum TexKind : uint32_t { TK_SOLID = 0, TK_CHECKER = 1, TK_NOISE = 2, TK_IMAGE = 3 };
 constexpr uint32_t MAX_CHECKER_NESTING = 8;   // CheckerTexture inside CheckerTexture (texture.rs:60-69 recurses); deeper graphs and cycles are rejected at compile
 struct Texture { uint32_t kind; int32_t a, b; float scale; float color[3]; uint32_t _pad; };   // 32 B
+// The flags word of a triangle's 64-byte attribute record (rt_api.cpp tri_attr_table): bits 0-1 RT_TRI_NORMALS / RT_TRI_UVS as the caller gave
+// them; for a triangle whose material has a normal map (rt_hip.h RtNormalMap) bit 2, bit 3 for RT_NMAP_FLIP_GREEN, and in bits 8.. the id of
+// the Texture record that holds the map (kind TK_IMAGE, a = the image, scale = the strength), appended behind the desc's textures.
+constexpr uint32_t TRI_ATTR_MAP = 4u, TRI_ATTR_MAP_FLIP_GREEN = 8u, TRI_ATTR_MAP_TEX_SHIFT = 8u;
 struct PerlinTable { Float4 ranvec[256]; uint32_t perm_x[256], perm_y[256], perm_z[256]; };
 struct Image { uint64_t offset; uint32_t width, height; };   // offset into the image byte pool
 

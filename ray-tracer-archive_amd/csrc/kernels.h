@@ -26,7 +26,11 @@ enum : uint32_t {
     // member of the lights list. Not part of F_ALL; always with F_LIGHTS_EXT and never with F_LIGHTS_TREE: k_shade and the drain / fused form of
     // k_extend have two instances with it (the full variant, without and with F_TRI_ATTR), k_sample_lights one. A scene without a map runs
     // the instances it ran before the bit existed.
-    F_ENV = 1024u
+    F_ENV = 1024u,
+    // a device triangle carries a normal map (rt_hip.h RtNormalMap). Not part of F_ALL; always with F_TRI_ATTR and F_TEX (the map is a texture record):
+    // every full-variant instance with F_TRI_ATTR has a twin with it (kernels.hip with_attr_variant), which applies the map on the map bit of the
+    // triangle's attribute record (kernels.hip normal_map_apply). A scene without a map runs the instances it ran before the bit existed.
+    F_NORMAL_MAP = 2048u
 };
 #define RT_N_PRIM_TYPES_K 6
 enum : uint32_t { CTR_NODE_TESTS = 0, CTR_PRIM_TESTS = 1, CTR_SAMPLES = 7, CTR_DEBUG = 8, CTR_SEGMENTS = 13, CTR_ITERATIONS = 14, CTR_COUNT = 16 };

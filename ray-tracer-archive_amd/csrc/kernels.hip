@@ -378,6 +378,41 @@ DEVI void tri_attr_apply(const TriAttr& a, float bu, float bv, V3& outward, floa
         hv = v0 + bu * (a.r3.x - v0) + bv * (a.r3.z - v0);
     }
 }
+// Normal map (rt_hip.h RtNormalMap; instances with F_NORMAL_MAP only), after tri_attr_apply: `outward` is the unit normal N and
+// (hu, hv) the texture coordinates that function leaves. The triangle's record names the map in its flags word (device_types.h TRI_ATTR_MAP*):
+// a Texture record (a = the image, scale = the strength) read where texture_value reads its own, so from k_shade's LDS blob when that is staged.
+// The steps and their order are the header's (TEXEL, DECODE, FRAME, RESULT, FALLBACKS); mesh.normal_map_reference restates them in numpy.
+DEVI void normal_map_apply(const SceneDev& sc, const TriAttr& a, V3 v0, V3 v1, V3 v2, float hu, float hv, V3& outward) {
+    const uint32_t flags = __float_as_uint(a.r3.w);
+    if ((flags & rtd::TRI_ATTR_MAP) == 0u) return;
+    const rtd::Texture tx = sc.textures[flags >> rtd::TRI_ATTR_MAP_TEX_SHIFT];
+    const rtd::Image im = sc.images[tx.a];                                      // (the upload refuses a map without texels)
+    const float u = fminf(fmaxf(hu, 0.f), 1.f), v = 1.f - fminf(fmaxf(hv, 0.f), 1.f);   // texture.rs:117-140, as texture_value
+    uint32_t i = (uint32_t)(u * (float)im.width), j = (uint32_t)(v * (float)im.height);
+    if (i >= im.width) i = im.width - 1u;
+    if (j >= im.height) j = im.height - 1u;
+    const uint8_t* px = sc.image_bytes + im.offset + ((size_t)j * im.width + i) * 3u;
+    const float k = 2.f / 255.f;
+    const float x = tx.scale * ((float)px[0] * k - 1.f), yg = tx.scale * ((float)px[1] * k - 1.f), z = (float)px[2] * k - 1.f;
+    const float y = (flags & rtd::TRI_ATTR_MAP_FLIP_GREEN) ? -yg : yg;
+    const bool uvs = (flags & 2u) != 0u;                                        // RT_TRI_UVS; without it uv_k = (0,0), (1,0), (0,1)
+    const float du1 = uvs ? a.r2.w - a.r2.y : 1.f, dv1 = uvs ? a.r3.x - a.r2.z : 0.f;
+    const float du2 = uvs ? a.r3.y - a.r2.y : 0.f, dv2 = uvs ? a.r3.z - a.r2.z : 1.f;
+    const float det = du1 * dv2 - du2 * dv1;
+    if (!(det != 0.f && fabsf(det) < kInf)) return;                             // collinear uv (or NaN, inf): N stays
+    const V3 e1 = v1 - v0, e2 = v2 - v0, N = outward;
+    V3 T = dv2 * e1 - dv1 * e2, B = du1 * e2 - du2 * e1;
+    if (det < 0.f) { T = -T; B = -B; }
+    const V3 tp = T - N * dot(N, T);
+    const float tl2 = len2(tp);
+    if (!(tl2 >= 1.17549435e-38f && tl2 < kInf)) return;
+    const V3 t = unit(tp);
+    V3 b = cross(N, t);
+    if (dot(b, B) < 0.f) b = -b;
+    const V3 s = x * t + y * b + z * N;
+    const float sl2 = len2(s);
+    if (sl2 >= 1.17549435e-38f && sl2 < kInf) outward = unit(s);
+}
 
 // ConstantMedium::hit (constant_medium.rs:31-71). Boundary = sphere or box, optionally under an
 // instance transform. `xi` is the free-path draw keyed by (path, segment, medium).
@@ -2130,6 +2165,7 @@ DEVI uint32_t shade_segment(const SceneDev& sc, const RenderDev& rd, V3& o, V3& 
                 p = ol + dl * t;
                 outward = unit(cross(v1 - v0, v2 - v0));
                 if (FEAT & F_TRI_ATTR) tri_attr_apply(ta, bu, bv, outward, hu, hv);
+                if constexpr ((FEAT & F_NORMAL_MAP) != 0u) normal_map_apply(sc, ta, v0, v1, v2, hu, hv, outward);
             }
             ff = dot(dl, outward) < 0.f;                                    // set_face_normal, hittable.rs:41-48
             n = ff ? outward : -outward;
@@ -2632,6 +2668,7 @@ DEVI bool rebuild_hit(const SceneDev& sc, V3 o, V3 d, float tm, float t, uint32_
         p = ol + dl * t;
         outward = unit(cross(v1 - v0, v2 - v0));
         if (FEAT & F_TRI_ATTR) tri_attr_apply(ta, bu, bv, outward, hu, hv);
+        if constexpr ((FEAT & F_NORMAL_MAP) != 0u) normal_map_apply(sc, ta, v0, v1, v2, hu, hv, outward);
     } else return false;
     ff = dot(dl, outward) < 0.f;                                    // set_face_normal, hittable.rs:41-48
     n = ff ? outward : -outward;
@@ -2946,10 +2983,17 @@ template <class F> static auto with_variant(uint32_t features, F&& f) {
 // for scenes whose triangles carry attributes (F_TRI_ATTR): the mesh variant and the full one. A scene without attributes runs exactly the
 // instances it ran before they existed, and the plain walk (launch_extend, launch_extend_any) never sees the bit.
 constexpr uint32_t kVariantMeshAttr = kVariantMesh | F_TRI_ATTR, kVariantAllAttr = F_ALL | F_TRI_ATTR;
+// ... and the full attribute variant once more for scenes with a normal map (F_NORMAL_MAP, always with F_TRI_ATTR and F_TEX): in the attribute
+// instances themselves the map cost the drain form registers across an occupancy step, so they stay what they were.
+// with_attr_variant: `attr`, or its twin with the map's bit for a scene that carries one.
+template <uint32_t ATTR, class F> static auto with_attr_variant(uint32_t features, F&& f) {
+    if ((features & F_NORMAL_MAP) != 0u) return f(std::integral_constant<uint32_t, ATTR | F_NORMAL_MAP>{});
+    return f(std::integral_constant<uint32_t, ATTR>{});
+}
 template <class F> static auto with_record_variant(uint32_t features, F&& f) {
     if ((features & F_TRI_ATTR) == 0u) return with_variant(features, f);
     if (pick_variant(features) == kVariantMesh) return f(std::integral_constant<uint32_t, kVariantMeshAttr>{});
-    return f(std::integral_constant<uint32_t, kVariantAllAttr>{});
+    return with_attr_variant<kVariantAllAttr>(features, f);
 }
 // ... and k_shade and the drain / fused form of k_extend two more for scenes whose lights table holds extended records (F_LIGHTS_EXT: RT_SCENE_LIGHTS_ALL_SHAPES
 // with a member that is not a bare XzRect or Sphere): the full variant, without and with triangle attributes. The ray-query and feature-export kernels
@@ -2962,15 +3006,15 @@ constexpr uint32_t kVariantAllEnv = kVariantAllLx | F_ENV, kVariantAllAttrEnv = 
 template <class F> static auto with_shade_variant(uint32_t features, F&& f) {
     if ((features & F_ENV) != 0u) {
         if ((features & F_TRI_ATTR) == 0u) return f(std::integral_constant<uint32_t, kVariantAllEnv>{});
-        return f(std::integral_constant<uint32_t, kVariantAllAttrEnv>{});
+        return with_attr_variant<kVariantAllAttrEnv>(features, f);
     }
     if ((features & F_LIGHTS_EXT) == 0u) return with_record_variant(features, f);
     if ((features & F_LIGHTS_TREE) != 0u) {
         if ((features & F_TRI_ATTR) == 0u) return f(std::integral_constant<uint32_t, kVariantAllLt>{});
-        return f(std::integral_constant<uint32_t, kVariantAllAttrLt>{});
+        return with_attr_variant<kVariantAllAttrLt>(features, f);
     }
     if ((features & F_TRI_ATTR) == 0u) return f(std::integral_constant<uint32_t, kVariantAllLx>{});
-    return f(std::integral_constant<uint32_t, kVariantAllAttrLx>{});
+    return with_attr_variant<kVariantAllAttrLx>(features, f);
 }
 // where the walk finds its records (k_extend MODE)
 template <class F> static auto with_mode(const LaunchCfg& cfg, const SceneDev& sc, F&& f) {
@@ -3224,8 +3268,9 @@ hipError_t launch_features_export(const LaunchCfg& cfg, const SceneDev& sc, cons
     const uint32_t blocks = export_blocks(max_count, rd.queue_cap);
     if (blocks == 0u) return hipSuccess;
     // a scene with an environment map: the full variant with F_ENV (a run-time branch on sc.env_texels moved the registers of the existing instances)
-    if ((cfg.features & F_ENV) != 0u) with_flag((cfg.features & F_TRI_ATTR) != 0u, [&](auto attr) {
-        hipLaunchKernelGGL((k_features_export<(decltype(attr)::value ? kVariantAllAttr : F_ALL) | F_ENV>), dim3(blocks), dim3(256), 0, stream, sc, rd, fd, pool, counts); });
+    if ((cfg.features & F_ENV) != 0u) with_flag((cfg.features & F_TRI_ATTR) != 0u, [&](auto attr) { with_flag((cfg.features & F_NORMAL_MAP) != 0u, [&](auto map) {
+        constexpr uint32_t F = (decltype(attr)::value ? kVariantAllAttr | (decltype(map)::value ? F_NORMAL_MAP : 0u) : F_ALL) | F_ENV;   // (a map comes with F_TRI_ATTR only)
+        hipLaunchKernelGGL((k_features_export<F>), dim3(blocks), dim3(256), 0, stream, sc, rd, fd, pool, counts); }); });
     else with_record_variant(cfg.features, [&](auto feat) {
         hipLaunchKernelGGL((k_features_export<decltype(feat)::value>), dim3(blocks), dim3(256), 0, stream, sc, rd, fd, pool, counts); });
     return hipGetLastError();

@@ -582,20 +582,70 @@ static rti::UploadOpts resolve_options(const RtUploadOptions* o) {
     return u;
 }
 
+// ---- normal maps (rt_hip.h RtNormalMap): the list of an options record, where the caller's struct reaches that far ------------------------
+struct NormalMaps { const RtNormalMap* p = nullptr; uint64_t n = 0u; };
+static NormalMaps maps_of(const RtUploadOptions* o) {
+    static_assert(sizeof(RtNormalMap) == 16 && offsetof(RtUploadOptionsMaps, normal_maps) == 48 && sizeof(RtUploadOptionsMaps) == 64, "the options record grows at its end");
+    NormalMaps m;
+    if (!o || o->struct_bytes < sizeof(RtUploadOptionsMaps)) return m;
+    const RtUploadOptionsMaps* x = reinterpret_cast<const RtUploadOptionsMaps*>(o);
+    m.p = x->normal_maps; m.n = x->n_normal_maps;
+    return m;
+}
+// The records checked against the desc (which compile_scene has accepted). map_of: material id -> record, -1 = none; left empty without maps.
+static int check_normal_maps(const RtSceneDesc& desc, const RtUploadOptions* o, std::vector<int64_t>& map_of, std::string& err) {
+    map_of.clear();
+    const NormalMaps maps = maps_of(o);
+    if (maps.n == 0u) return RT_OK;
+    if (!maps.p) { err = "RtUploadOptionsMaps.normal_maps is NULL with n_normal_maps > 0"; return RT_ERR_INVALID; }
+    map_of.assign(desc.n_materials, -1);
+    for (uint64_t k = 0; k < maps.n; ++k) {
+        const RtNormalMap& m = maps.p[k];
+        const std::string what = "RtNormalMap[" + std::to_string(k) + "]: ";
+        if (m.material < 0 || (uint64_t)m.material >= desc.n_materials) { err = what + "material id out of range"; return RT_ERR_INVALID; }
+        if (map_of[m.material] >= 0) { err = what + "material " + std::to_string(m.material) + " is listed twice"; return RT_ERR_INVALID; }
+        if (m.image < 0 || (uint64_t)m.image >= desc.n_images) { err = what + "image id out of range"; return RT_ERR_INVALID; }
+        const RtImage& im = desc.images[m.image];
+        if (!im.data || im.width == 0 || im.height == 0) { err = what + "image " + std::to_string(m.image) + " has NULL data or a zero dimension"; return RT_ERR_INVALID; }
+        if (!(std::isfinite(m.strength) && m.strength >= 0.f)) { err = what + "strength is negative or not finite"; return RT_ERR_INVALID; }
+        if (m.flags & ~(uint32_t)RT_NMAP_FLIP_GREEN) { err = what + "flags: unknown bit (known: RT_NMAP_FLIP_GREEN)"; return RT_ERR_INVALID; }
+        const int kind = desc.materials[m.material].kind;
+        if (kind == RT_MAT_DIFFUSE_LIGHT || kind == RT_MAT_ISOTROPIC) {
+            err = what + "material " + std::to_string(m.material) + " is an RT_MAT_DIFFUSE_LIGHT or RT_MAT_ISOTROPIC (neither scatters about a normal)"; return RT_ERR_INVALID;
+        }
+        map_of[m.material] = (int64_t)k;
+    }
+    for (uint64_t h = 0; h < desc.n_hittables; ++h) {
+        const RtHittable& H = desc.hittables[h];
+        const bool prim = H.kind == RT_HIT_SPHERE || H.kind == RT_HIT_MOVING_SPHERE || H.kind == RT_HIT_XY_RECT || H.kind == RT_HIT_XZ_RECT || H.kind == RT_HIT_YZ_RECT ||
+                          H.kind == RT_HIT_BOX || H.kind == RT_HIT_CONSTANT_MEDIUM;
+        if (prim && H.material >= 0 && (uint64_t)H.material < desc.n_materials && map_of[H.material] >= 0) {
+            err = "RtNormalMap[" + std::to_string(map_of[H.material]) + "]: material " + std::to_string(H.material) + " is used by hittable " + std::to_string(h) +
+                  ", which is not an RT_HIT_TRIANGLE (normal maps are served on triangles only, for now)";
+            return RT_ERR_INVALID;
+        }
+    }
+    return RT_OK;
+}
+
 // ---- triangle attributes (rt_hip.h RtTriangleAttrs): checked against the graph, then laid out by DEVICE triangle index ---------------------
 // The table is parallel to tris[]: one 64-byte record per device triangle — (n0.xyz, n1.x) (n1.yz, n2.xy) (n2.z, uv0, u1) (v1, uv2, flags) —
 // so that a kernel which holds the triangle index of a hit asks for it together with the vertices (no look-up through tri_meta). The
 // index -> hittable map is the one the ray queries report (CompiledScene::tri_src), which every layout keeps: leaf collapse, SAH, the
 // 8-wide tree and the octant arrays reorder records, never tris[]. A triangle the graph reaches several times has one device record per
 // copy, and each gets the attributes. *n_with counts the device triangles that carry some; `table` stays empty when there is none, and table == nullptr checks and counts only.
-static int tri_attr_table(const RtSceneDesc& desc, const RtUploadOptions* o, const rtc::CompiledScene& cs, std::vector<rtd::Float4>* table, uint32_t* n_with,
-                          std::string& err) {
+static int tri_attr_table(const RtSceneDesc& desc, const RtUploadOptions* o, rtc::CompiledScene& cs, std::vector<rtd::Float4>* table, uint32_t* n_with,
+                          uint32_t* n_mapped, std::string& err) {
     if (table) table->clear();
-    *n_with = 0u;
-    if (!o || o->struct_bytes < offsetof(RtUploadOptions, n_triangle_attrs) + sizeof(uint64_t) || o->n_triangle_attrs == 0u) return RT_OK;
-    if (!o->triangle_attrs) { err = "RtUploadOptions.triangle_attrs is NULL with n_triangle_attrs > 0"; return RT_ERR_INVALID; }
+    *n_with = 0u; *n_mapped = 0u;
+    std::vector<int64_t> map_of;                   // material id -> its RtNormalMap record, -1 = none; empty = the upload gave no maps
+    { const int ok = check_normal_maps(desc, o, map_of, err); if (ok != RT_OK) return ok; }
+    const NormalMaps maps = maps_of(o);
+    const bool has_attrs = o && o->struct_bytes >= offsetof(RtUploadOptions, n_triangle_attrs) + sizeof(uint64_t) && o->n_triangle_attrs != 0u;
+    if (!has_attrs && map_of.empty()) return RT_OK;
+    if (has_attrs && !o->triangle_attrs) { err = "RtUploadOptions.triangle_attrs is NULL with n_triangle_attrs > 0"; return RT_ERR_INVALID; }
     std::vector<int64_t> by_id(desc.n_hittables, -1);
-    for (uint64_t k = 0; k < o->n_triangle_attrs; ++k) {
+    for (uint64_t k = 0; has_attrs && k < o->n_triangle_attrs; ++k) {
         const RtTriangleAttrs& a = o->triangle_attrs[k];
         const std::string what = "RtTriangleAttrs[" + std::to_string(k) + "]: ";
         if (a.hittable < 0 || (uint64_t)a.hittable >= desc.n_hittables) { err = what + "hittable id out of range"; return RT_ERR_INVALID; }
@@ -617,20 +667,49 @@ static int tri_attr_table(const RtSceneDesc& desc, const RtUploadOptions* o, con
         const int64_t k = cs.tri_src[i] < by_id.size() ? by_id[cs.tri_src[i]] : -1;
         return k >= 0 && o->triangle_attrs[k].flags != 0u ? &o->triangle_attrs[k] : nullptr;
     };
-    for (size_t i = 0; i < n; ++i) if (record_of(i)) ++*n_with;
+    // ... and the ones whose material has a normal map (tri_meta names the material of every device triangle): a mapped triangle without
+    // attributes gets a record with only the map bits
+    auto map_of_tri = [&](size_t i) -> int64_t {
+        const uint32_t m = cs.tri_meta[i] & rtd::META_MAT_MASK;
+        return m < map_of.size() ? map_of[m] : -1;
+    };
+    for (size_t i = 0; i < n; ++i) {
+        const bool mapped = map_of_tri(i) >= 0;
+        if (record_of(i) || mapped) ++*n_with;
+        if (mapped) ++*n_mapped;
+    }
     if (!table || *n_with == 0u) return RT_OK;
+    // Each map in use becomes one more rtd::Texture record behind the desc's textures (TK_IMAGE, a = the image, scale = the strength), so that
+    // it reaches the kernels through a table they already hold and is staged in k_shade's LDS blob with the others; the triangle's record names
+    // it in the high bits of its flags word (device_types.h TRI_ATTR_*). A map no device triangle uses adds nothing.
+    std::vector<int64_t> tex_of(maps.n, -1);
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t k = map_of_tri(i);
+        if (k < 0 || tex_of[k] >= 0) continue;
+        if (cs.textures.size() >= (1u << (32u - rtd::TRI_ATTR_MAP_TEX_SHIFT))) { err = "RtNormalMap: too many textures"; return RT_ERR_UNSUPPORTED; }
+        rtd::Texture t{};
+        t.kind = rtd::TK_IMAGE; t.a = maps.p[k].image; t.b = -1; t.scale = maps.p[k].strength;
+        tex_of[k] = (int64_t)cs.textures.size();
+        cs.textures.push_back(t);
+    }
     table->assign(4 * n, rtd::Float4{0.f, 0.f, 0.f, 0.f});
     for (size_t i = 0; i < n; ++i) {
         const RtTriangleAttrs* ap = record_of(i);
-        if (!ap) continue;
-        const RtTriangleAttrs& a = *ap;
+        const int64_t k = map_of_tri(i);
+        if (!ap && k < 0) continue;
         float f[16] = {0.f};
-        if (a.flags & RT_TRI_NORMALS) for (int v = 0; v < 3; ++v) {
-            const double x = a.n[v][0], y = a.n[v][1], z = a.n[v][2], l = std::sqrt(x * x + y * y + z * z);     // unit in f64, then rounded
-            f[3 * v] = (float)(x / l); f[3 * v + 1] = (float)(y / l); f[3 * v + 2] = (float)(z / l);
+        uint32_t flags = 0u;
+        if (ap) {
+            const RtTriangleAttrs& a = *ap;
+            if (a.flags & RT_TRI_NORMALS) for (int v = 0; v < 3; ++v) {
+                const double x = a.n[v][0], y = a.n[v][1], z = a.n[v][2], l = std::sqrt(x * x + y * y + z * z);     // unit in f64, then rounded
+                f[3 * v] = (float)(x / l); f[3 * v + 1] = (float)(y / l); f[3 * v + 2] = (float)(z / l);
+            }
+            if (a.flags & RT_TRI_UVS) for (int v = 0; v < 3; ++v) { f[9 + 2 * v] = a.uv[v][0]; f[10 + 2 * v] = a.uv[v][1]; }
+            flags = a.flags;
         }
-        if (a.flags & RT_TRI_UVS) for (int v = 0; v < 3; ++v) { f[9 + 2 * v] = a.uv[v][0]; f[10 + 2 * v] = a.uv[v][1]; }
-        std::memcpy(&f[15], &a.flags, 4);
+        if (k >= 0) flags |= rtd::TRI_ATTR_MAP | ((maps.p[k].flags & RT_NMAP_FLIP_GREEN) ? rtd::TRI_ATTR_MAP_FLIP_GREEN : 0u) | ((uint32_t)tex_of[k] << rtd::TRI_ATTR_MAP_TEX_SHIFT);
+        std::memcpy(&f[15], &flags, 4);
         std::memcpy(&(*table)[4 * i], f, 64);
     }
     return RT_OK;
@@ -638,7 +717,8 @@ static int tri_attr_table(const RtSceneDesc& desc, const RtUploadOptions* o, con
 
 // What every compile of a caller's scene begins with: the options checked, the graph compiled under them, the triangle attributes checked
 // against the result (tri_attr_table: `table` receives their device records, nullptr = checked and counted only).
-static int compile_checked(const RtSceneDesc& desc, const RtUploadOptions* options, rtc::CompiledScene& cs, std::vector<rtd::Float4>* table, uint32_t* n_with, std::string& err) {
+static int compile_checked(const RtSceneDesc& desc, const RtUploadOptions* options, rtc::CompiledScene& cs, std::vector<rtd::Float4>* table, uint32_t* n_with, std::string& err,
+                           uint32_t* n_mapped = nullptr) {
     { const int ok = check_options(options, err); if (ok != RT_OK) return ok; }
     { const int ok = check_env(env_of(options), err); if (ok != RT_OK) return ok; }
     if (env_of(options) && (desc.scene_flags & RT_SCENE_LIGHTS_MANY)) {
@@ -647,7 +727,10 @@ static int compile_checked(const RtSceneDesc& desc, const RtUploadOptions* optio
     }
     const int rc = rtc::compile_scene(desc, resolve_options(options).compile, cs);
     if (rc != RT_OK) { err = "scene: " + cs.error; return rc; }
-    return tri_attr_table(desc, options, cs, table, n_with, err);
+    uint32_t mapped = 0u;
+    const int ok = tri_attr_table(desc, options, cs, table, n_with, &mapped, err);
+    if (n_mapped) *n_mapped = mapped;
+    return ok;
 }
 // how far an entry's box of the 8-wide tree lies outside what is below it (rtw::build; rt_scene_wide_layout_check holds the tree to it)
 static float wide_margin(const std::vector<rtd::Node>& nodes) {
@@ -680,7 +763,8 @@ int rti::scene_image_build(const RtSceneDesc* desc, const RtUploadOptions* optio
     std::unique_ptr<SceneImage> im(new SceneImage());
     rtc::CompiledScene& cs = im->cs;
     uint32_t n_with = 0u;
-    { const int ok = compile_checked(*desc, options, cs, &im->tri_attrs, &n_with, err); if (ok != RT_OK) return ok; }
+    uint32_t n_mapped = 0u;
+    { const int ok = compile_checked(*desc, options, cs, &im->tri_attrs, &n_with, err, &n_mapped); if (ok != RT_OK) return ok; }
     const UploadOpts opt = resolve_options(options);
     im->in_lds = opt.lds_scene && lds_scene_bytes(cs) <= kLdsSceneBudget;
     im->features = scene_features(cs);   // attributes change what is shaded, never what is walked: every test on `features` below sees the scene's own bits
@@ -767,6 +851,7 @@ int rti::scene_image_build(const RtSceneDesc* desc, const RtUploadOptions* optio
         }
     }
     if (!im->tri_attrs.empty()) im->features |= rtk::F_TRI_ATTR;
+    if (n_mapped != 0u) im->features |= rtk::F_TEX | rtk::F_NORMAL_MAP;   // the map is a texture record: the full variant, in its instances with the map's bit (kernels.hip with_attr_variant)
     if (const RtEnvMap* e = env_of(options)) {     // (checked by compile_checked)
         const size_t n = (size_t)e->width * e->height;
         im->env_texels.resize(n);
@@ -1822,12 +1907,13 @@ int rt_untile_rgb8(const RtParams* p, const uint8_t* gathered, uint8_t* rgb8) { 
 int rt_scene_compile_info(const RtSceneDesc* desc, RtCompileInfo* out) { return rt_scene_compile_info_ex(desc, nullptr, out); }
 int rt_scene_compile_info_ex(const RtSceneDesc* desc, const RtUploadOptions* options, RtCompileInfo* out) {
     if (!desc || !out) return set_err(nullptr, RT_ERR_INVALID, "null argument");
-    rtc::CompiledScene cs; std::string why; uint32_t n_with = 0u;
-    { const int ok = compile_checked(*desc, options, cs, nullptr, &n_with, why); if (ok != RT_OK) return set_err(nullptr, ok, why); }
+    rtc::CompiledScene cs; std::string why; uint32_t n_with = 0u, n_mapped = 0u;
+    { const int ok = compile_checked(*desc, options, cs, nullptr, &n_with, why, &n_mapped); if (ok != RT_OK) return set_err(nullptr, ok, why); }
     out->n_nodes = cs.nodes.size(); out->n_box_nodes = cs.n_box_nodes; out->n_spheres = cs.sphere_meta.size(); out->n_moving = cs.moving_meta.size();
     out->n_rects = cs.rect_meta.size(); out->n_tris = cs.tri_meta.size(); out->n_media = cs.media.size(); out->n_xforms = cs.xforms.size();
     out->n_lights = cs.n_lights; out->n_materials = cs.mat_b.size();
-    out->features = scene_features(cs) | (n_with != 0u ? rtk::F_TRI_ATTR : 0u) | (env_of(options) ? rtk::F_LIGHTS_EXT | rtk::F_ENV : 0u);
+    out->features = scene_features(cs) | (n_with != 0u ? rtk::F_TRI_ATTR : 0u) | (env_of(options) ? rtk::F_LIGHTS_EXT | rtk::F_ENV : 0u) |
+                    (n_mapped != 0u ? rtk::F_TEX | rtk::F_NORMAL_MAP : 0u);
     out->n_tri_attrs = n_with;
     out->fits_lds = lds_scene_bytes(cs) <= kLdsSceneBudget ? 1u : 0u;
     {   // what a walk tests before it enters the tree: the root list's every-ray members, then the root BVH's scene-sized spheres

@@ -14,6 +14,7 @@ class SceneBuilder:
         self.hittables, self.children, self.materials, self.textures, self.perlins, self.images = [], [], [], [], [], []
         self._image_arrays = []
         self.tri_attrs = []          # RtTriangleAttrs of the triangles built with normals / uvs
+        self.nmaps = []              # RtNormalMap of the materials given a normal map
         self.background, self.background_mode, self.bvh_seed, self.bvh_builder = background, background_mode, bvh_seed, bvh_builder
         self._keep = None
 
@@ -120,6 +121,23 @@ class SceneBuilder:
     def triangle_attrs(self):
         """The RtTriangleAttrs array of the triangles built with normals / uvs (None when there is none)."""
         return (A.RtTriangleAttrs * len(self.tri_attrs))(*self.tri_attrs) if self.tri_attrs else None
+
+    def normal_map(self, material, image, strength=1.0, flip_green=False):
+        """Binds a tangent-space normal map to `material` (include/rt_hip.h RtNormalMap): image = an (H, W, 3) uint8 array, which becomes an
+        RtImage of the desc (so call this before desc()), or the id of one that is there already. The record travels beside the desc: hand
+        normal_maps() to upload / compile_info as `normal_maps=`. Returns the image id."""
+        if not isinstance(image, (int, np.integer)):
+            arr = np.ascontiguousarray(image, dtype=np.uint8)
+            self._image_arrays.append(arr)
+            h, w, _ = arr.shape
+            self.images.append(A.RtImage(arr.ctypes.data_as(C.POINTER(C.c_uint8)), w, h))
+            image = len(self.images) - 1
+        self.nmaps.append(A.RtNormalMap(int(material), int(image), float(strength), A.RT_NMAP_FLIP_GREEN if flip_green else 0))
+        return int(image)
+
+    def normal_maps(self):
+        """The RtNormalMap array of the materials given a map (None when there is none)."""
+        return (A.RtNormalMap * len(self.nmaps))(*self.nmaps) if self.nmaps else None
 
     def box(self, p0, p1, mat):
         return self._hit(A.RT_HIT_BOX, mat, p=list(p0) + list(p1))

@@ -13,7 +13,10 @@ SceneBuilder calls — nothing here touches the device.
                     "marble": {"noise": 0.1, "seed": 7}, "earth": {"image": "earthmap.png"}},
       "materials": {"wall": {"lambertian": "white"}, "lamp": {"diffuse_light": [15, 15, 15]},
                     "glass": {"dielectric": 1.5}, "steel": {"metal": [0.8, 0.85, 0.88], "fuzz": 0.0},
-                    "smoke": {"isotropic": [1, 1, 1]}},
+                    "smoke": {"isotropic": [1, 1, 1]},
+                    "bumpy": {"lambertian": "white", "normal_map": {"image": "bumps.png", "strength": 1.0, "flip_green": false}}},
+                                                    # a normal map on the material's triangles (include/rt_hip.h RtNormalMap): a file beside the
+                                                    # scene or rows of [r, g, b]; JsonScene.normal_maps goes to upload(..., normal_maps=)
       "objects":   {"floor": {"xz_rect": [0, 555, 0, 555, 0], "material": "wall"},
                     "ball":  {"sphere": [[190, 90, 190], 90], "material": "glass"},
                     "block": {"box": [[0, 0, 0], [165, 330, 165]], "material": "wall"},
@@ -157,6 +160,7 @@ class JsonScene:
             raise ValueError(f"lights_many: expected true or false, got {lm!r}")
         self.desc = self.b.desc(world, lights, lights_all_shapes=las, lights_many=lm)
         self.triangle_attrs = self.b.triangle_attrs()
+        self.normal_maps = self.b.normal_maps()
         self.env_map = self._environment(doc.get("environment"))
 
     def _environment(self, e):
@@ -244,6 +248,29 @@ class JsonScene:
             mid = self.b.isotropic(_vec3(m["isotropic"], w))
         else:
             raise ValueError(f"{w}: expected one of lambertian / metal / dielectric / diffuse_light / isotropic")
+        nm = m.get("normal_map")
+        if nm is not None:
+            if not isinstance(nm, dict) or "image" not in nm or set(nm) - {"image", "strength", "flip_green"}:
+                raise ValueError(f'{w}.normal_map: expected {{"image": file or rows of [r, g, b]}}, with "strength" and "flip_green" at most')
+            strength, flip = nm.get("strength", 1.0), nm.get("flip_green", False)
+            if isinstance(strength, bool) or not isinstance(strength, (int, float)):
+                raise ValueError(f"{w}.normal_map.strength: expected a number, got {strength!r}")
+            if not isinstance(flip, bool):
+                raise ValueError(f"{w}.normal_map.flip_green: expected true or false, got {flip!r}")
+            if isinstance(nm["image"], str):
+                from PIL import Image
+                try:
+                    texels = np.asarray(Image.open(os.path.join(self.base_dir, nm["image"])).convert("RGB"))
+                except OSError as err:
+                    raise ValueError(f"{w}.normal_map.image: {err}")
+            else:
+                try:
+                    texels = np.asarray(nm["image"], dtype=np.uint8)
+                except (TypeError, ValueError):
+                    texels = None
+                if texels is None or texels.ndim != 3 or texels.shape[2] != 3 or texels.size == 0:
+                    raise ValueError(f"{w}.normal_map.image: expected a file name or rows of [r, g, b] texels (0..255), all rows of one length")
+            self.b.normal_map(mid, texels, float(strength), flip)
         self._mat[name] = mid
         return mid
 
